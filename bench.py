@@ -36,10 +36,8 @@ if os.environ.get("OCHIP_BENCH_CPUS"):
     _cpus = sorted(os.sched_getaffinity(0))[:max(1, int(os.environ["OCHIP_BENCH_CPUS"]))]
     os.sched_setaffinity(0, _cpus)
 # The step keeps ~8 HIP streams busy (4 extraction sequences, 3 link runners, the relax of the previous survey, copies).
-# The ROCm runtime maps streams onto 4 hardware queues by default, so a short latency-bound launch can sit behind another
-# stream's long kernel in the same queue; 16 queues measured +5-6 % images/s.  Read by the runtime
-# when it initialises, hence set before anything touches HIP.
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")
+# The number of hardware queues they are mapped onto is left to the environment: the GPU is shared with other processes,
+# and a process opening more queues than the card's fixed slots leaves the device in a state it may not recover from.
 # RCCL across processes needs dmabuf IPC on this driver (already exported on the pool's boxes; kept if it is not)
 os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
 # A survey's feature lists (1.8 MB per image) are allocated by the host tail and freed with the graph one step later.
@@ -900,6 +898,56 @@ def strong_main(args, proc, cfg):
 
 
 # ---------------------------------------------------------------------------------------------------------------------
+DUMP_FEATURE_IMAGES = 8      # feature lists of a fixed sample of images (at most 30 000 features each)
+DUMP_INLIER_EDGES = 64       # inlier sets of a fixed sample of edges
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, g, rel):
+    """--dump-outputs: what the last timed step handed its caller, as float64 arrays in out_dir/<name>.npy.  Everything is
+    in image order (edges sorted by source, then destination image), so two builds can be compared array for array:
+      relax_orientation (n x 4 quaternions), relax_plane (3 x 3), relax_summary (solves, iterations_total, last_iterations,
+        initial_cost, final_cost, residual_blocks)
+      node_features (n x 2: features, sparse features per image)
+      edge_index (E x 4: source image, destination image, matches, inliers), edge_homography (E x 9), edge_poses (E x 32)
+      edge_inliers_sample (rows: edge_index row, f1, f2, match_index, 4 pixel coordinates) of a seeded sample of edges
+      features_sample (rows: image, x, y, strength, the descriptor as 16 32-bit words) of a seeded sample of images"""
+    index_of = {nid: i for i, nid in enumerate(g.node_ids)}
+    n = len(g.node_ids)
+    edges = sorted(g.edges(), key=lambda e: (index_of[e["source"]], index_of[e["dest"]]))
+    nt = g.node_table()
+    out = {
+        "relax_orientation": rel["orientation"],
+        "relax_plane": rel["plane"],
+        "relax_summary": [rel[k] for k in ("solves", "iterations_total", "last_iterations", "initial_cost", "final_cost",
+                                           "residual_blocks")],
+        "node_features": np.stack([nt["features"], nt["sparse"]], 1),
+        "edge_index": np.array([[index_of[e["source"]], index_of[e["dest"]], e["n_matches"], e["n_inliers"]] for e in edges],
+                               np.float64).reshape(-1, 4),
+        "edge_homography": np.array([e["H"].reshape(9) for e in edges]).reshape(-1, 9),
+        "edge_poses": np.array([e["poses"].reshape(32) for e in edges]).reshape(-1, 32),
+    }
+    rng = np.random.default_rng(2024)
+    pick = np.sort(rng.choice(len(edges), min(DUMP_INLIER_EDGES, len(edges)), replace=False))
+    rows = [np.column_stack([np.full(edges[k]["n_inliers"], k), edges[k]["f1"], edges[k]["f2"], edges[k]["match_index"],
+                             edges[k]["px"]]) for k in pick]
+    out["edge_inliers_sample"] = np.concatenate(rows) if rows else np.zeros((0, 8))
+    rows = []
+    for i in np.sort(rng.choice(n, min(DUMP_FEATURE_IMAGES, n), replace=False)):
+        p = g.node_payload(int(i))
+        words = np.ascontiguousarray(p["desc"]).view(np.uint32).reshape(-1, 16)
+        rows.append(np.column_stack([np.full(len(words), i), p["loc"], p["strength"], words]))
+    out["features_sample"] = np.concatenate(rows) if rows else np.zeros((0, 20))
+    out = {k: np.ascontiguousarray(v, np.float64) for k, v in out.items()}
+    total = sum(v.nbytes for v in out.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise RuntimeError(f"--dump-outputs: {total} bytes exceed the {DUMP_LIMIT_BYTES}-byte limit")
+    os.makedirs(out_dir, exist_ok=True)
+    for k, v in out.items():
+        np.save(os.path.join(out_dir, k + ".npy"), v)
+    print(f"bench.py: {len(out)} output arrays ({total / 1e6:.1f} MB) written to {out_dir}", file=sys.stderr, flush=True)
+
+
 def weak_main(args, proc, cfg):
     rank, world = proc.rank, proc.world
     from opencalibration_amd import capi, pipeline, synth
@@ -933,6 +981,8 @@ def weak_main(args, proc, cfg):
 
     def run_steps(n_steps, acc):
         pending = []
+        # --dump-outputs: the graph of the last timed step stays open until its outputs are written (after the timed region)
+        keep_last = acc is not None and bool(args.dump_outputs)
 
         def collect(entry):
             th, g, res, t = entry
@@ -940,7 +990,7 @@ def weak_main(args, proc, cfg):
             if getattr(th, "error", None):
                 raise th.error
             last.update(res=res, t=t, link_work=last.get("link_work"))
-            if not relax_overlap:
+            if not relax_overlap and g is not last.get("graph"):
                 g.close()
             if acc is not None:
                 for k, v in list(t.items()) + [("link_" + k, v) for k, v in res["link_timers"].items()] + \
@@ -966,16 +1016,20 @@ def weak_main(args, proc, cfg):
                                            relax=not relax_overlap))
             tb = time.perf_counter()
             last["link_work"] = dict(g.match_work(), images=grid.n_images)
+            keep = keep_last and step == n_steps - 1
+            if keep:
+                last["graph"] = g
             if relax_overlap:
                 if pending:
                     collect(pending.pop())           # one relax in flight at a time
                 if verbose:
                     print(f"[bench] load+link {tb - ta:.3f} s, collect previous {time.perf_counter() - tb:.3f} s", file=sys.stderr)
 
-                def work(g=g, res=res, t=t):
+                def work(g=g, res=res, t=t, keep=keep):
                     try:
                         pipeline.relax_step(rctx, g, start_ori, res, t)
-                        g.close()                    # (1.8 GB of feature records: freed off the main thread)
+                        if not keep:
+                            g.close()                # (1.8 GB of feature records: freed off the main thread)
                     except Exception as ex:          # surfaces in collect()
                         threading.current_thread().error = ex
 
@@ -1004,6 +1058,11 @@ def weak_main(args, proc, cfg):
     # survey k under load + link of survey k + 1) and so count each other's threads; this one counts everything once
     host_cpu_total = (time.process_time() - cpu_begin) / args.steps
     value = grid.n_images * world * args.steps / hot_max
+    if args.dump_outputs:
+        g_last = last.pop("graph")
+        if rank == 0:
+            dump_outputs(args.dump_outputs, g_last, last["res"]["relax"])
+        g_last.close()
 
     res = last["res"]
     rel = res["relax"]
@@ -1166,7 +1225,15 @@ def main():
                     help="strong scaling only: pipelined = the relax of survey k runs on rank k mod N in the shadow of the next "
                          "surveys (as at N = 1); sharded = inside the step, residual blocks over all ranks, RCCL exchange")
     ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last timed step computed (rank 0's survey: relax result, "
+                         "edges, a fixed sample of feature lists and inlier sets) as DIR/<name>.npy, float64, under 64 MB; "
+                         "weak scaling only")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.dump_outputs and args.scaling != "weak":
+        ap.error("--dump-outputs: the weak (default) scaling mode only")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(launch_ranks(args.gpus))       # (no launcher around us: be the launcher)

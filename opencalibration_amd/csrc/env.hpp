@@ -19,8 +19,7 @@
 //                      branch-free ones for the default scale space's radii; 64 instead of 2 048 list entries in LDS)
 // Other switches (read where they apply): OCHIP_CHAIN_WORKGROUPS (grid of the resident launch; default half the compute units),
 // OCHIP_IP_PRIORITY=0 (och_initial_processing_step: link and relax streams at the default priority), OCHIP_STRIP_MIN_PIXELS
-// (pixels per launch from which a level takes the register-strip kernels), OCHIP_EXTRACT_GATE=0 (two surveys may extract at once),
-// OCHIP_REQUIRE_REF=1 (tests: the pins against the reference's own headers must run)
+// (pixels per launch from which a level takes the register-strip kernels), OCHIP_EXTRACT_GATE=0 (two surveys may extract at once)
 #pragma once
 
 #include <cstdlib>

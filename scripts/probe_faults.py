@@ -5,7 +5,6 @@ import sys
 import time
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")
 os.environ.setdefault("OMP_WAIT_POLICY", "passive")
 import ctypes  # noqa: E402
 

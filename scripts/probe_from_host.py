@@ -6,7 +6,6 @@ import threading
 import time
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")
 os.environ.setdefault("OMP_WAIT_POLICY", "passive")
 import numpy as np  # noqa: E402
 

@@ -7,7 +7,7 @@ R=${GRAFT_REPO_ROOT:-/root/repo}
 OUT=$R/gpurun_out/r04_final
 rm -rf $OUT; mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-export GPU_MAX_HW_QUEUES=16 HSA_ENABLE_IPC_MODE_LEGACY=0
+export HSA_ENABLE_IPC_MODE_LEGACY=0
 # 1. extract alone, one sequence at a time
 bash $R/scripts/r4_extract_trace.sh final > $OUT/extract_only_trace.txt 2>&1
 cp $R/gpurun_out/xtrace_final/kernel_stats.csv $OUT/r04_extract_only_kernel_stats.csv

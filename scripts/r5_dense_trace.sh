@@ -4,7 +4,7 @@ R=${GRAFT_REPO_ROOT:-/root/repo}
 OUT=$R/gpurun_out/densetrace_${1:-x}
 rm -rf $OUT; mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-export GPU_MAX_HW_QUEUES=16 HSA_ENABLE_IPC_MODE_LEGACY=0
+export HSA_ENABLE_IPC_MODE_LEGACY=0
 rocprofv3 --kernel-trace --memory-copy-trace --stats --output-format csv -d $OUT/t -- python3 $R/scripts/probe_dense.py C3 > $OUT/run.log 2>&1
 tail -3 $OUT/run.log
 f=$(ls -t $OUT/t/*/*_kernel_stats.csv | head -1)

@@ -6,7 +6,7 @@ TAG=${1:-x}
 OUT=$R/gpurun_out/ltrace_$TAG
 rm -rf $OUT; mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-export GPU_MAX_HW_QUEUES=16 HSA_ENABLE_IPC_MODE_LEGACY=0 OCHIP_EXTRACT_STREAMS=1
+export HSA_ENABLE_IPC_MODE_LEGACY=0 OCHIP_EXTRACT_STREAMS=1
 rocprofv3 --kernel-trace --output-format csv -d $OUT/t -- python3 $R/scripts/extract_only.py 100 3 > $OUT/run.log 2>&1
 f=$(ls -t $OUT/t/*/*_kernel_trace.csv | head -1)
 python3 - "$f" "${2:-}" <<'PY' | tee $OUT/levels.txt

@@ -6,7 +6,7 @@ TAG=${1:-x}
 OUT=$R/gpurun_out/linktrace_$TAG
 rm -rf $OUT; mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-export GPU_MAX_HW_QUEUES=16 HSA_ENABLE_IPC_MODE_LEGACY=0 OCHIP_BENCH_EXTRAS=0 OCHIP_PIPELINE_OVERLAP=0 OCHIP_EXTRACT_STREAMS=1 OCHIP_LINK_RUNNERS=1
+export HSA_ENABLE_IPC_MODE_LEGACY=0 OCHIP_BENCH_EXTRAS=0 OCHIP_PIPELINE_OVERLAP=0 OCHIP_EXTRACT_STREAMS=1 OCHIP_LINK_RUNNERS=1
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/t -- python3 $R/bench.py --steps 2 --warmup 1 --no-cpu-baseline > $OUT/run.log 2>&1
 grep '^{' $OUT/run.log | tail -1 | python3 -c "import json,sys; d=json.loads(sys.stdin.readline()); print('value', d['value'], 'ms_per_step', d['ms_per_step'])"
 f=$(ls -t $OUT/t/*/*_kernel_stats.csv | head -1)

@@ -1,8 +1,8 @@
-"""Worker of tests/test_gpu_world8.py: EIGHT ranks (gloo rendezvous) sharing cuda:0 - the rank count of the node BASELINE's
-scaling curve is quoted on.  One survey from pixels over the ranks (3 x 8 grid: three images per rank; extraction by block,
-links by owning rank, two all-gathers), its plane relax and its ground-mesh relax sharded over the 8 ranks, then - on a
-400-camera graph linked from synthetic features - the clustered stage with its 8 groups dealt over the ranks.  Every rank
-must end with what ONE process computes, bit for bit."""
+"""Worker of tests/test_gpu_world4.py: FOUR ranks (gloo rendezvous) sharing cuda:0.  One survey from pixels over the ranks
+(3 x 4 grid: three images per rank; extraction by block, links by owning rank, two all-gathers), its plane relax and its
+ground-mesh relax sharded over the 4 ranks, then - on a 400-camera graph linked from synthetic features - the clustered
+stage with its 8 groups dealt over the ranks (two per rank).  Every rank must end with what ONE process computes, bit for
+bit."""
 import os
 import sys
 
@@ -23,7 +23,7 @@ def main():
     ctx = capi.Context(0)
     checks, info = {}, {}
     # ---- one survey from pixels over the ranks
-    grid = synth.make_grid(3, 8, feats=64, seed=41)
+    grid = synth.make_grid(3, 4, feats=64, seed=41)
     images, shape = pipeline.synthetic_views(ctx, grid, seed=9)
     n, h, w = shape
     start = pipeline.perturbed_orientations(grid, 0.05, 3)
@@ -52,7 +52,7 @@ def main():
     info["edges"] = int(g.num_edges)
     single.close(), g.close()
     ctx.synth_views_free(images)
-    # ---- the clustered stage: 400 cameras, 8 groups over the 8 ranks
+    # ---- the clustered stage: 400 cameras, 8 groups over the 4 ranks
     grid2 = synth.make_grid(10, 40, feats=512, seed=78)
     g2 = host.Graph.from_synthetic(grid2)
     start2 = pipeline.perturbed_orientations(grid2, 0.1, 5)
@@ -74,8 +74,8 @@ def main():
     flags = [None] * world
     dist.all_gather_object(flags, (checks, info))
     if rank == 0:
-        ok = world == 8 and all(all(f[0].values()) for f in flags)
-        print("WORLD8", "OK" if ok else "MISMATCH", flags, flush=True)
+        ok = world == 4 and all(all(f[0].values()) for f in flags)
+        print("WORLD4", "OK" if ok else "MISMATCH", flags, flush=True)
     ctx.close()
     dist.destroy_process_group()
 

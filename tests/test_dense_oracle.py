@@ -1,26 +1,18 @@
-"""The restated dense guided matching (oracle/dense.cpp) against the pieces of the reference that compile here
-(oracle/_ref: hilbert.hpp, the jk::KDTree queries densifyMesh makes) and against the ground truth of a synthetic scene."""
+"""The restated dense guided matching (oracle/dense.cpp) against the pieces of the reference that compile on their own
+(hilbert.hpp, the jk::KDTree queries densifyMesh makes: their answers stored in tests/golden/reference_pins.npz) and
+against the ground truth of a synthetic scene."""
 import numpy as np
 import pytest
 
 from oracle import pyoracle
+import reference_pins as rp
 from dense_fixtures import dense_scene, ground_mesh_arrays
 
 
-def _ref():
-    from conftest import require_ref
-
-    return require_ref(pyoracle, "ref_hilbert_xy2d")
-
-
 def test_hilbert_index_is_the_reference_header():
-    import ctypes as C
-    r = _ref()
-    r.ref_hilbert_xy2d.restype = C.c_uint32
-    rng = np.random.default_rng(0)
-    for order in (2, 8, 1024, 4096):
-        for x, y in rng.integers(0, order, (200, 2)):
-            assert pyoracle.hilbert_xy2d(order, x, y) == r.ref_hilbert_xy2d(int(order), int(x), int(y))
+    gold = rp.golden()
+    for key, (order, xy) in rp.hilbert_cases():
+        assert [pyoracle.hilbert_xy2d(order, x, y) for x, y in xy] == gold[key].tolist(), key
     # a bijection on the square (what makes it a walk order)
     assert sorted(pyoracle.hilbert_xy2d(8, x, y) for x in range(8) for y in range(8)) == list(range(64))
 
@@ -28,32 +20,17 @@ def test_hilbert_index_is_the_reference_header():
 def test_reference_kdtree_queries_are_exhaustive_scans():
     """densifyMesh asks the reference's KD-tree for the 11 nearest cameras of a 3-D point and for the features in a disc
     (`squared distance < radius^2`); the restatement scans.  Same sets, same nearest-first order."""
-    import ctypes as C
-    r = _ref()
-    f64p = np.ctypeslib.ndpointer(np.float64, flags="C_CONTIGUOUS")
-    u64p = np.ctypeslib.ndpointer(np.uint64, flags="C_CONTIGUOUS")
-    r.ref_knn3.restype = C.c_size_t
-    r.ref_knn3.argtypes = [f64p, C.c_size_t, f64p, C.c_size_t, u64p]
-    r.ref_ball2.restype = C.c_size_t
-    r.ref_ball2.argtypes = [f64p, C.c_size_t, f64p, C.c_double, u64p]
-    rng = np.random.default_rng(3)
-    cams = rng.uniform(0, 500, (300, 3)) * [1, 1, 0.02] + [0, 0, 100]
-    out = np.zeros(300, np.uint64)
-    for _ in range(50):
-        q = rng.uniform(-50, 550, 3) * [1, 1, 0]
-        k = r.ref_knn3(cams, len(cams), q, 11, out)
+    gold = rp.golden()
+    cams, knn_q, pts, ball_q = rp.kdtree_cases()
+    for i, q in enumerate(knn_q):
         d = np.sum((cams - q) ** 2, axis=1)
-        assert list(out[:k]) == list(np.argsort(d, kind="stable")[:11])
-    pts = rng.uniform(0, 1000, (2000, 2))
-    pts[7] = [400.0, 300.0 + 150.0]                      # exactly on the circle: outside (`<`)
-    got = np.zeros(2000, np.uint64)
-    for q in [np.array([400.0, 300.0])] + [rng.uniform(0, 1000, 2) for _ in range(30)]:
-        k = r.ref_ball2(pts, len(pts), q, 150.0 ** 2, got)
+        assert list(gold[f"knn3/{i}"]) == list(np.argsort(d, kind="stable")[:11])
+    for i, q in enumerate(ball_q):
+        got = gold[f"ball2/{i}"]
         d = np.sum((pts - q) ** 2, axis=1)
-        assert sorted(got[:k]) == sorted(np.nonzero(d < 150.0 ** 2)[0])
-        assert list(d[got[:k].astype(int)]) == sorted(d[got[:k].astype(int)])      # nearest first
-    k = r.ref_ball2(pts, len(pts), np.array([400.0, 300.0]), 150.0 ** 2, got)
-    assert 7 not in got[:k]
+        assert sorted(got) == sorted(np.nonzero(d < 150.0 ** 2)[0])
+        assert list(d[got.astype(int)]) == sorted(d[got.astype(int)])      # nearest first
+    assert 7 not in gold["ball2/0"]                      # (400, 450) lies exactly on the circle around (400, 300)
 
 
 def test_restated_densify_recovers_the_ground():

@@ -1,9 +1,10 @@
 """Pins oracle/match.cpp and oracle/distort.cpp with restated reference tests
-(test/test_match.cpp:44-129, test/test_distort.cpp:8-137) and against oracle/_ref (the reference's
-own KD-tree header compiled in place)."""
+(test/test_match.cpp:44-129, test/test_distort.cpp:8-137) and against the answers of the reference's own KD-tree
+header (tests/golden/reference_pins.npz)."""
 import numpy as np
 import pytest
 
+import reference_pins as rp
 from opencalibration_amd import synth
 
 
@@ -39,19 +40,11 @@ def test_spatial_subsample_properties(oracle):  # test_match.cpp:44-88 (monotone
 
 
 def test_subsample_matches_reference_kdtree(oracle):
-    """The hash-grid restatement must agree with the reference's jk::tree::KDTree driver loop."""
-    from conftest import require_ref
-
-    require_ref(oracle)
-    rng = np.random.default_rng(11)
-    for n, spacing in ((1, 40.0), (50, 40.0), (4000, 40.0), (4000, 8.0), (2000, 123.5)):
-        loc = rng.uniform(0, 4000, (n, 2))
-        # heavy strength ties exercise the unstable std::sort path both sides share
-        strength = (rng.integers(0, 50, n) / 50).astype(np.float32)
-        assert np.array_equal(oracle.subsample(loc, strength, spacing), oracle.ref_subsample(loc, strength, spacing))
-    g = synth.make_grid(1, 2, feats=1024, seed=5)
-    loc, st, _, _ = g.image(0)
-    assert np.array_equal(oracle.subsample(loc, st, 40.0), oracle.ref_subsample(loc, st, 40.0))
+    """The hash-grid restatement must agree with the reference's jk::tree::KDTree driver loop (its answers stored in
+    tests/golden/reference_pins.npz)."""
+    gold = rp.golden()
+    for key, (loc, strength, spacing) in rp.subsample_cases(synth):
+        assert np.array_equal(oracle.subsample(loc, strength, spacing), gold[key]), key
 
 
 def _popcount(a):
@@ -114,12 +107,8 @@ def test_distort_radial_tangential(oracle):  # test_distort.cpp:57-68
 
 def test_knn_reference_has_no_ties_on_synthetic_grid(oracle):
     """positions are jittered so the kNN(10) pair set is tree-independent."""
-    from conftest import require_ref
-
-    require_ref(oracle)
-    g = synth.make_grid(4, 6, feats=64, seed=1)
-    knn = oracle.ref_knn(g.position[:, :2], 10)
-    xy = g.position[:, :2]
+    knn = rp.golden()["knn_grid"]
+    xy = rp.knn_grid(synth)
     d = np.sum((xy[:, None] - xy[None]) ** 2, -1)
     for i in range(len(xy)):
         order = np.argsort(d[i], kind="stable")[:10]

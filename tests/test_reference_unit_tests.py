@@ -7,6 +7,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import reference_pins as rp
 from opencalibration_amd import host
 
 D3 = np.ctypeslib.ndpointer(np.float64, flags="C_CONTIGUOUS")
@@ -179,29 +180,17 @@ def test_mesh_doesnt_intersect_outside(rx, oracle):               # :126-174
         assert _intersect(rx, g, x, 2.01)[0] == OUTSIDE_BORDER
 
 
-# ---- test_combinatorics.cpp / test_tree.cpp: the reference's own headers, compiled in place (oracle/_ref/libref.so)
-def test_interleave_and_kdtree_known_answers(oracle):
+# ---- test_combinatorics.cpp / test_tree.cpp: the reference's own headers' answers (tests/golden/reference_pins.npz)
+def test_interleave_and_kdtree_known_answers():
     """interleave.hpp (pipeline.cpp:553 deals the three stages' runners with it) and jk/KDTree.h under their own unit tests'
     known answers (test_combinatorics.cpp:22-37: a0 b0 c0 a1 b1 b2 a2 b3 b4 a3 b5; test_tree.cpp:10-38: the two nearest of
-    (6, 6) among (1, 2), (1, 3), (7, 7) are (7, 7) then (1, 3)) - through the shim that compiles those headers where they lie."""
-    from conftest import require_ref
-
-    r = require_ref(oracle, "ref_interleave3")
-    u64p = oracle.u64p
-    r.ref_interleave3.restype = C.c_size_t
-    r.ref_interleave3.argtypes = [u64p, C.c_size_t, u64p, C.c_size_t, u64p, C.c_size_t, C.c_int, u64p]
-    a, b, c = np.arange(0, 4, dtype=np.uint64), np.arange(10, 16, dtype=np.uint64), np.array([20], np.uint64)
-    out = np.zeros(16, np.uint64)
-    n = r.ref_interleave3(a, 4, b, 6, c, 1, 1, out)                  # (full_dispersal = true, the default the test uses)
-    assert out[:n].tolist() == [0, 10, 20, 1, 11, 12, 2, 13, 14, 3, 15]
-    assert r.ref_interleave3(a, 0, b, 0, c, 0, 1, out) == 0
-    xy = np.array([[1, 2], [1, 3], [7, 7]], np.float64)
-    q = np.array([[6.0, 6.0]])
-    # ref_knn: for every point of xy its k nearest (itself first); the monster's location as a fourth point
-    pts = np.vstack([xy, q])
-    knn = np.zeros((4, 3), np.uint64)
-    r.ref_knn(np.ascontiguousarray(pts), 4, 3, knn)
-    assert knn[3].tolist() == [3, 2, 1]                           # itself, Melvin (7, 7), Harold (1, 3)
+    (6, 6) among (1, 2), (1, 3), (7, 7) are (7, 7) then (1, 3)) - as the shim that compiles those headers answered them on
+    the inputs of tests/reference_pins.py."""
+    gold = rp.golden()
+    assert gold["interleave3"].tolist() == [0, 10, 20, 1, 11, 12, 2, 13, 14, 3, 15]     # (full_dispersal = true)
+    assert gold["interleave3_empty"].tolist() == [0]
+    # ref_knn: for every point its k nearest (itself first); the monster's location as the fourth point
+    assert gold["kdtree_known"][3].tolist() == [3, 2, 1]                 # itself, Melvin (7, 7), Harold (1, 3)
 
 
 # ---- test_relax.cpp:250-296: DecomposedRotationCost's residuals at the truth and at fixed offsets (fixture :30-37)

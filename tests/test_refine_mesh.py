@@ -1,10 +1,11 @@
 """Mesh refinement of the host library (refine_mesh.cpp) against the reference's own test cases
 (test/test_refine_mesh.cpp: 881-1033 counts / density refinement / variance filter, 1206-1310 locator vs brute force,
 the mesh validity helpers :17-195 restated) and against the real ankerl::unordered_dense for the erase order the
-refinement's choices depend on (oracle/_ref).  No device involved."""
+refinement's choices depend on (tests/golden/reference_pins.npz).  No device involved."""
 import numpy as np
 import pytest
 
+import reference_pins as rp
 from opencalibration_amd import host
 from oracle import pyoracle
 
@@ -62,34 +63,11 @@ def _grid_cloud(lo, hi, step, zf):
 
 
 def test_unordered_dense_erase_moves_the_last_element():
-    """The restated containers (vectors with swap-and-pop) are the real header's behaviour."""
-    import ctypes as C
-    from conftest import require_ref
-
-    r = require_ref(pyoracle, "ref_dense_set_order")
-    r.ref_dense_set_order.restype = C.c_size_t
-    r.ref_dense_set_order.argtypes = [np.ctypeslib.ndpointer(np.int64), C.c_size_t, np.ctypeslib.ndpointer(np.uint64)]
-    rng = np.random.default_rng(1)
-    for _ in range(20):
-        ops, model, live = [], [], set()
-        for step in range(200):
-            if live and rng.uniform() < 0.35:
-                k = int(rng.choice(sorted(live)))
-                ops.append(-k - 1)
-                i = model.index(k)
-                model[i] = model[-1]
-                model.pop()
-                live.discard(k)
-            else:
-                k = int(rng.integers(0, 1 << 40))
-                if k in live:
-                    continue
-                ops.append(k)
-                model.append(k)
-                live.add(k)
-        out = np.zeros(len(ops) + 1, np.uint64)
-        n = r.ref_dense_set_order(np.array(ops, np.int64), len(ops), out)
-        assert list(out[:n]) == model
+    """The restated containers (vectors with swap-and-pop) are the real header's behaviour: its iteration order after
+    the seeded insert / erase sequences of tests/reference_pins.py (stored in tests/golden/reference_pins.npz)."""
+    gold = rp.golden()
+    for key, (ops, model) in rp.dense_set_cases():
+        assert list(gold[key]) == model, key
 
 
 def test_count_points_per_triangle():
