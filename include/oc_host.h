@@ -370,6 +370,41 @@ extern "C"
     void och_surface_locate(const och_surface *s, const double *xy, size_t n, uint64_t *tri3);
     int och_mesh_refinement_run(och_graph *g, ochip_ctx *ctx, och_surface *surface, int max_steps, double *log8);
 
+    /* ---- orthomosaic preview and DSM raster (opencalibration_amd/csrc/host/ortho.hpp; src/ortho/ortho.cpp:228-964) -------
+     * The reference's context: calculateBoundsAndMeanZ (bounds5 = min_x, max_x, min_y, max_y, mean_surface_z; a surface's
+     * clouds count only when it has no mesh), calculateGSD over the given nodes in the given order (thumbnail != 0: the
+     * preview's, at thumbnail scale), prepareOrthoMosaicContext (ctx8 = bounds5, gsd, mean_camera_z,
+     * average_camera_elevation; returns the involved nodes: those with a finite orientation), the two output clamps
+     * (input pixels = the involved nodes' model pixels_cols x pixels_rows) and rayTraceHeight. */
+    /* rows, cols <= 65535 (0 x 0 clears the thumbnail); -1 + och_last_error(g) otherwise */
+    int och_graph_set_thumbnail(och_graph *g, size_t node_index, size_t rows, size_t cols, const uint8_t *rgb /* rows x cols x 3 */);
+    void och_ortho_bounds(const och_surface *const *surfaces, size_t n, double *bounds5);
+    double och_ortho_gsd(const och_graph *g, const uint64_t *node_ids, size_t n_ids, double mean_surface_z, int thumbnail);
+    size_t och_ortho_context(const och_graph *g, const och_surface *const *surfaces, size_t n, int thumbnail, double *ctx8);
+    void och_ortho_clamp_resolution(uint64_t total_input_pixels, double *gsd, int32_t *width, int32_t *height);
+    void och_ortho_clamp_megapixels(double max_output_megapixels, double *gsd, int32_t *width, int32_t *height);
+    double och_ray_trace_height(const och_surface *const *surfaces, size_t n, double x, double y, double mean_camera_z);
+    /* generateOrthomosaic (ortho.cpp:478-653): plan8 = {width, height, gsd, min_x, max_x, min_y, max_y, mean_camera_z} is
+     * always written; rgba == NULL: size query only.  rgba [height][width][4], ids [height][width] (node id & 0xFFFFFFFF,
+     * 0xFFFFFFFF for background and for pixels no surface holds, which get (0, 0, 0, 0)).  Every involved node needs a
+     * thumbnail (och_graph_set_thumbnail).  ctx == NULL: the CPU route, whose heights come from z_in when it is given
+     * (height x width fp64); z_out (may be NULL) returns the fp64 heights used.  -1 + och_last_error(g) on failure. */
+    int och_orthomosaic_thumbnail(och_graph *g, ochip_ctx *ctx, const och_surface *const *surfaces, size_t n, const double *z_in,
+                                  double *plan8, uint8_t *rgba, uint32_t *ids, double *z_out);
+    /* generateDSMGeoTIFF's raster (ortho.cpp:866-964): the full-resolution plan (plan8 as above) with
+     * max_output_megapixels (<= 0: no cap), then bands of it.  och_ortho_mesh_upload builds the surfaces' triangle table on
+     * the device (release with ochip_ortho_mesh_destroy).  och_dsm_render: rows [row0, row0 + rows) into out
+     * [rows][width] as float, NaN where no surface holds the pixel; dev != NULL: on the device (ctx = dev's context; out a
+     * device pointer when out_on_device), dev == NULL: the CPU route (host out).  Debug outputs (host, may be NULL):
+     * tri_out the triangle (index into the table: surfaces in order, each one's triangles by ascending node triple),
+     * z64_out the fp64 heights, capped_walks the CPU route's walks that ran out of steps.  -1 + och_ortho_last_error(). */
+    int och_dsm_plan(const och_graph *g, const och_surface *const *surfaces, size_t n, double max_output_megapixels, double *plan8);
+    int och_ortho_mesh_upload(ochip_ctx *ctx, const och_surface *const *surfaces, size_t n, ochip_ortho_mesh **out);
+    int och_dsm_render(ochip_ctx *ctx, ochip_ortho_mesh *dev, const och_surface *const *surfaces, size_t n, const double *plan8,
+                       int64_t row0, int64_t rows, float *out, int out_on_device, uint32_t *tri_out, double *z64_out,
+                       uint64_t *capped_walks);
+    const char *och_ortho_last_error(void);
+
 #ifdef __cplusplus
 }
 #endif

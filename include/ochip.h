@@ -671,6 +671,37 @@ extern "C"
     int ochip_dense_triangulate(ochip_dense_index *ix, const double *cam_q4, uint32_t n_tracks, const uint32_t *track_start,
                                 const uint32_t *track_member, double max_reprojection_error, double *points3_out, uint8_t *valid_out);
 
+    /* ---- orthomosaic preview and DSM raster (src/ortho/ortho.cpp:478-653, 793-856) -----------------------------------
+     * The mesh table: n_surfaces surfaces in the reference's order (the first that holds a pixel wins), surface s owning
+     * triangles [tri_off[s], tri_off[s + 1]) of tri9 (three corners xyz each, in ascending mesh node order).  The library
+     * bins every surface's triangles into a uniform grid; a pixel takes the first triangle of its cell, in table order,
+     * that contains it (the walker's predicates: a point on an edge is inside).
+     * raster4 = {min_x, max_y, gsd, mean_camera_z}: pixel (row, col) is the vertical ray through
+     * (col * gsd + min_x, max_y - row * gsd) from height mean_camera_z. */
+    typedef struct ochip_ortho_mesh ochip_ortho_mesh;
+    int ochip_ortho_mesh_create(ochip_ctx *ctx, uint32_t n_surfaces, const uint64_t *tri_off, const double *tri9,
+                                ochip_ortho_mesh **out);
+    void ochip_ortho_mesh_destroy(ochip_ortho_mesh *m);
+    /* DSM rows [row0, row0 + rows) of a raster `cols` wide: out[(row - row0) * cols + col] = (float)z, NaN where no surface
+     * holds the pixel.  out_on_device != 0: out is a device pointer of this context's GPU, else a host pointer.  The kernels
+     * run on the context's stream, which does not wait for other streams: the caller finishes its own work on `out` first.
+     * The call returns once the band is written.
+     * Debug outputs (host, may be NULL): tri_out the triangle (table index) that gave z, 0xFFFFFFFF where none did;
+     * z64_out z in fp64. */
+    int ochip_ortho_dsm(ochip_ortho_mesh *m, const double *raster4, int32_t cols, int64_t row0, int64_t rows, float *out,
+                        int out_on_device, uint32_t *tri_out, double *z64_out);
+    /* The preview raster, rows x cols: per pixel z as above; where it exists, the first of the 5 nearest cameras in XY
+     * (squared distance, then camera order) with R_inv * (p - position) in front of it whose projection, scaled by
+     * thumb_scale and truncated, lies strictly inside its thumbnail (0 < px < cols, 0 < py < rows) gives
+     * (r, g, b, 255) and cam_id; none does: checkerboard grey (64 or 128 by (row + col) parity), alpha 0, id 0xFFFFFFFF;
+     * no surface: (0, 0, 0, 0) and 0xFFFFFFFF.
+     * cams24 [n_cams][24]: position 3, R_inv 9 (row-major), f, ppx, ppy, k1, k2, k3, p1, p2, thumb_scale, thumbnail rows,
+     * thumbnail cols, 0.  Thumbnail i: rows x cols x 3 bytes at thumbs + thumb_off[i] (thumb_bytes in all).
+     * rgba_out [rows][cols][4], id_out [rows][cols]; z_out (fp64) and tri_out may be NULL.  Host pointers. */
+    int ochip_ortho_thumbnail(ochip_ortho_mesh *m, const double *raster4, int32_t cols, int32_t rows, uint32_t n_cams,
+                              const double *cams24, const uint32_t *cam_id, const uint64_t *thumb_off, const uint8_t *thumbs,
+                              uint64_t thumb_bytes, uint8_t *rgba_out, uint32_t *id_out, double *z_out, uint32_t *tri_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -35,6 +35,7 @@ EXPORTS = [
     "ochip_dense_index_create", "ochip_dense_index_destroy", "ochip_dense_match", "ochip_dense_link", "ochip_dense_triangulate",
     "ochip_rccl_unique_id", "ochip_rccl_comm_create", "ochip_rccl_comm_destroy", "ochip_rccl_comm_stats",
     "ochip_rccl_relax_exchange",
+    "ochip_ortho_mesh_create", "ochip_ortho_mesh_destroy", "ochip_ortho_dsm", "ochip_ortho_thumbnail",
 ]
 
 _lib = None
@@ -85,6 +86,8 @@ def load():
         L.ochip_synth_views_free.restype = None
         L.ochip_synth_render_views.argtypes = [vp, vp, u32, u32, i32, i32, vp, vp, vp, vp, u32]
         L.ochip_synth_views_read.argtypes = [vp, vp, u32, i32, i32, vp]
+        L.ochip_ortho_mesh_destroy.argtypes = [vp]
+        L.ochip_ortho_mesh_destroy.restype = None
         _lib = L
     return _lib
 

@@ -45,7 +45,7 @@ class TriangleWalker
         v3 c[3];
         for (int i = 0; i < 3; i++)
             c[i] = corner(tri[i]);
-        for (size_t steps = 0;;)
+        for (steps = 0;;)
         {
             if (turns_clockwise(c[0], c[1], c[2]))
             {
@@ -97,6 +97,7 @@ class TriangleWalker
     }
     size_t tri[3] = {0, 0, 0};
     v3 hit{NAN, NAN, NAN};
+    size_t steps = 0; // of the last find(); above 100: the walk ran out of steps
 
   private:
     v3 corner(size_t i) const

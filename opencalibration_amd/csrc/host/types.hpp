@@ -95,6 +95,10 @@ struct image // types/image.hpp:17-33 (fields the hot path touches)
     double orientation[4] = {NAN, NAN, NAN, NAN};
     // carried through graph.json untouched (graph_io.cpp): the base64 PNG thumbnail and the "metadata" object's text
     std::string thumbnail_b64, metadata_json;
+    // the decoded thumbnail the orthomosaic preview samples (image.thumbnail, a 3-layer raster): rows x cols x 3 bytes,
+    // layers in the caller's order; empty until och_graph_set_thumbnail (not serialised)
+    size_t thumbnail_rows = 0, thumbnail_cols = 0;
+    std::vector<uint8_t> thumbnail_pixels;
 };
 
 struct NodeLinks // types/node_links.hpp

@@ -218,6 +218,24 @@ def load():
         L.och_shard_finalize.argtypes = [vp, _f64p, _f64p, _f64p]
         L.och_hilbert_xy2d.argtypes = [C.c_int, C.c_int, C.c_int]
         L.och_hilbert_xy2d.restype = u32
+        i32, i64, f64 = C.c_int32, C.c_int64, C.c_double
+        L.och_graph_set_thumbnail.argtypes = [vp, sz, sz, sz, vp]
+        L.och_ortho_bounds.argtypes = [vp, sz, _f64p]
+        L.och_ortho_bounds.restype = None
+        L.och_ortho_gsd.argtypes = [vp, _u64p, sz, f64, C.c_int]
+        L.och_ortho_gsd.restype = f64
+        L.och_ortho_context.argtypes = [vp, vp, sz, C.c_int, _f64p]
+        L.och_ortho_context.restype = sz
+        for fn in (L.och_ortho_clamp_resolution, L.och_ortho_clamp_megapixels):
+            fn.argtypes = [u64 if fn is L.och_ortho_clamp_resolution else f64, C.POINTER(f64), C.POINTER(i32), C.POINTER(i32)]
+            fn.restype = None
+        L.och_ray_trace_height.argtypes = [vp, sz, f64, f64, f64]
+        L.och_ray_trace_height.restype = f64
+        L.och_orthomosaic_thumbnail.argtypes = [vp, vp, vp, sz, vp, _f64p, vp, vp, vp]
+        L.och_dsm_plan.argtypes = [vp, vp, sz, f64, _f64p]
+        L.och_ortho_mesh_upload.argtypes = [vp, vp, sz, C.POINTER(vp)]
+        L.och_dsm_render.argtypes = [vp, vp, vp, sz, _f64p, i64, i64, vp, C.c_int, vp, vp, C.POINTER(u64)]
+        L.och_ortho_last_error.restype = C.c_char_p
         _lib = L
     return _lib
 
@@ -416,6 +434,175 @@ def rebuild_mesh(cam_xyz, previous=None, minimal=False):
     s = Surface()
     s.L.och_rebuild_mesh(cam_xyz, len(cam_xyz), previous.h if previous is not None else None, int(minimal), s.h)
     return s
+
+
+# ---- orthomosaic preview and DSM raster (include/oc_host.h; src/ortho/ortho.cpp) ---------------------------------------
+PLAN_KEYS = ("width", "height", "gsd", "min_x", "max_x", "min_y", "max_y", "mean_camera_z")
+
+
+def _surface_array(surfaces):
+    surfaces = list(surfaces)
+    return (C.c_void_p * max(len(surfaces), 1))(*[s.h for s in surfaces]), len(surfaces)
+
+
+def _plan_dict(plan8):
+    d = dict(zip(PLAN_KEYS, plan8.tolist()))
+    d["width"], d["height"] = int(d["width"]), int(d["height"])
+    return d
+
+
+def _plan_array(plan):
+    return np.array([plan[k] for k in PLAN_KEYS], np.float64)
+
+
+def ortho_bounds(surfaces):
+    """calculateBoundsAndMeanZ (src/ortho/ortho.cpp:283-342)."""
+    arr, n = _surface_array(surfaces)
+    out = np.zeros(5)
+    load().och_ortho_bounds(arr, n, out)
+    return dict(zip(("min_x", "max_x", "min_y", "max_y", "mean_surface_z"), out.tolist()))
+
+
+def ortho_gsd(graph, node_ids, mean_surface_z, thumbnail=True):
+    """calculateGSD (src/ortho/ortho.cpp:344-377) over node_ids in the given order."""
+    ids = np.ascontiguousarray(node_ids, np.uint64)
+    return load().och_ortho_gsd(graph.h, ids if len(ids) else np.zeros(1, np.uint64), len(ids), mean_surface_z, int(thumbnail))
+
+
+def ortho_context(graph, surfaces, thumbnail=True):
+    """prepareOrthoMosaicContext (src/ortho/ortho.cpp:379-414) without the k-d tree: bounds, gsd, camera heights and the
+    number of involved nodes."""
+    arr, n = _surface_array(surfaces)
+    out = np.zeros(8)
+    k = load().och_ortho_context(graph.h, arr, n, int(thumbnail), out)
+    d = dict(zip(("min_x", "max_x", "min_y", "max_y", "mean_surface_z", "gsd", "mean_camera_z", "average_camera_elevation"),
+                 out.tolist()))
+    d["involved"] = int(k)
+    return d
+
+
+def ortho_clamp_resolution(total_input_pixels, gsd, width, height):
+    """clampOutputResolution (src/ortho/ortho.cpp:228-256) with the input pixel count given: (gsd, width, height)."""
+    g, w, h = C.c_double(gsd), C.c_int32(width), C.c_int32(height)
+    load().och_ortho_clamp_resolution(int(total_input_pixels), C.byref(g), C.byref(w), C.byref(h))
+    return g.value, w.value, h.value
+
+
+def ortho_clamp_megapixels(max_output_megapixels, gsd, width, height):
+    """clampOutputMegapixels (src/ortho/ortho.cpp:258-281): (gsd, width, height)."""
+    g, w, h = C.c_double(gsd), C.c_int32(width), C.c_int32(height)
+    load().och_ortho_clamp_megapixels(float(max_output_megapixels), C.byref(g), C.byref(w), C.byref(h))
+    return g.value, w.value, h.value
+
+
+def ray_trace_height(x, y, mean_camera_z, surfaces):
+    """rayTraceHeight (src/ortho/ortho.cpp:462-472): NaN where no surface holds (x, y)."""
+    arr, n = _surface_array(surfaces)
+    return load().och_ray_trace_height(arr, n, x, y, mean_camera_z)
+
+
+def orthomosaic_thumbnail(graph, surfaces, ctx=None, z_in=None, want_z=False):
+    """generateOrthomosaic (src/ortho/ortho.cpp:478-653): the preview raster from the nodes' thumbnails
+    (Graph.set_thumbnail).  ctx: on that device; None: the CPU route, whose heights are z_in when given.
+    Returns the plan's keys plus rgba (height x width x 4 uint8), ids (uint32) and, with want_z, z (fp64)."""
+    L = load()
+    arr, n = _surface_array(surfaces)
+    plan8 = np.zeros(8)
+    L.och_orthomosaic_thumbnail(graph.h, ctx.h if ctx is not None else None, arr, n, None, plan8, None, None, None)
+    out = _plan_dict(plan8)
+    h, w = out["height"], out["width"]
+    rgba, ids = np.zeros((h, w, 4), np.uint8), np.zeros((h, w), np.uint32)
+    z = np.zeros((h, w)) if want_z else None
+    zi = None
+    if z_in is not None:
+        zi = np.ascontiguousarray(z_in, np.float64)
+        if zi.shape != (h, w):
+            raise ValueError(f"z_in must be {h} x {w}")
+    rc = L.och_orthomosaic_thumbnail(graph.h, ctx.h if ctx is not None else None, arr, n,
+                                     None if zi is None else zi.ctypes.data, plan8, rgba.ctypes.data, ids.ctypes.data,
+                                     None if z is None else z.ctypes.data)
+    if rc != 0:
+        raise capi.OchipError("orthomosaic thumbnail failed: " + L.och_last_error(graph.h).decode())
+    out.update(rgba=rgba, ids=ids)
+    if want_z:
+        out["z"] = z
+    return out
+
+
+def dsm_plan(graph, surfaces, max_output_megapixels=0.0):
+    """The full-resolution DSM raster of generateDSMGeoTIFF (src/ortho/ortho.cpp:866-897): width, height, gsd, bounds,
+    mean_camera_z."""
+    arr, n = _surface_array(surfaces)
+    plan8 = np.zeros(8)
+    load().och_dsm_plan(graph.h, arr, n, float(max_output_megapixels), plan8)
+    return _plan_dict(plan8)
+
+
+class OrthoMesh:
+    """The surfaces' triangle table on the device (ochip_ortho_mesh), for rendering DSM bands."""
+
+    def __init__(self, ctx, surfaces):
+        self.L, self.ctx = load(), ctx
+        arr, n = _surface_array(surfaces)
+        self.h = C.c_void_p()
+        if self.L.och_ortho_mesh_upload(ctx.h, arr, n, C.byref(self.h)) != 0:
+            raise capi.OchipError("ortho mesh upload failed: " + self.L.och_ortho_last_error().decode())
+
+    def close(self):
+        if getattr(self, "h", None):
+            # a context closed first has taken the device with it: the table cannot be handed back to its pool then
+            if getattr(self.ctx, "h", None):
+                capi.load().ochip_ortho_mesh_destroy(self.h)
+            self.h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        self.close()
+
+
+def dsm_render(plan, surfaces=(), mesh=None, row0=0, rows=None, out=None, debug=False):
+    """DSM rows [row0, row0 + rows) of `plan` (dsm_plan) as float32, NaN where no surface holds the pixel.  mesh (an
+    OrthoMesh): on its device, into `out` when that is a float32 CUDA tensor of rows x width (returned as is), else into a
+    new host array; mesh None: the CPU route over `surfaces`.  debug: also the triangle index, the fp64 heights and (CPU
+    route) the walks that ran out of steps, as (z, tri, z64, capped)."""
+    L = load()
+    rows = plan["height"] - row0 if rows is None else rows
+    w = plan["width"]
+    arr, n = _surface_array(surfaces)
+    on_device = out is not None and not isinstance(out, np.ndarray)
+    if on_device:
+        if mesh is None:
+            raise ValueError("a device output needs the device route (mesh)")
+        if tuple(out.shape) != (rows, w) or str(out.dtype) != "torch.float32" or not out.is_cuda or not out.is_contiguous():
+            raise ValueError(f"out must be a contiguous float32 device tensor of {rows} x {w}")
+        if out.device.index != mesh.ctx.device:
+            raise ValueError(f"out is on cuda:{out.device.index}, the mesh's context on device {mesh.ctx.device}")
+        # the kernel runs on the context's own (non-blocking) stream: whatever torch still has queued on its current
+        # stream - the fill that made `out`, a reader of the block the allocator just handed out again - finishes first.
+        # The call returns after the band is written, so torch's later work on `out` is ordered after it.
+        import torch
+
+        torch.cuda.current_stream(out.device).synchronize()
+        ptr = out.data_ptr()
+    else:
+        out = np.zeros((rows, w), np.float32) if out is None else out
+        if out.shape != (rows, w) or out.dtype != np.float32 or not out.flags.c_contiguous:
+            raise ValueError(f"out must be a contiguous float32 array of {rows} x {w}")
+        ptr = out.ctypes.data
+    tri = np.zeros((rows, w), np.uint32) if debug else None
+    z64 = np.zeros((rows, w)) if debug else None
+    capped = C.c_uint64(0)
+    rc = L.och_dsm_render(mesh.ctx.h if mesh is not None else None, mesh.h if mesh is not None else None, arr, n,
+                          _plan_array(plan), int(row0), int(rows), ptr, int(on_device),
+                          None if tri is None else tri.ctypes.data, None if z64 is None else z64.ctypes.data, C.byref(capped))
+    if rc != 0:
+        raise capi.OchipError(L.och_ortho_last_error().decode())
+    return (out, tri, z64, int(capped.value)) if debug else out
 
 
 def relax(ctx, node_pos, node_ori, model10, features, pose_node, pose_ori, packed_edges, options, grid_fraction=0.1,
@@ -863,6 +1050,15 @@ class Graph:
 
     def set_orientations(self, ori):
         self.L.och_graph_set_orientations(self.h, np.ascontiguousarray(ori, np.float64))
+
+    def set_thumbnail(self, index, rgb):
+        """The decoded thumbnail (rows x cols x 3 uint8, layers in the caller's order) of the node at `index` (node
+        order) that the orthomosaic preview samples."""
+        rgb = np.ascontiguousarray(rgb, np.uint8)
+        if rgb.ndim != 3 or rgb.shape[2] != 3:
+            raise ValueError("a thumbnail is rows x cols x 3")
+        if self.L.och_graph_set_thumbnail(self.h, int(index), rgb.shape[0], rgb.shape[1], rgb.ctypes.data) != 0:
+            raise ValueError(self.L.och_last_error(self.h).decode())
 
     def edges_flat(self, node_subset=None):
         """The linked edges as flat dicts (src/dst node index, H, inlier pixel pairs, match indices, match
