@@ -404,6 +404,37 @@ extern "C"
                        int64_t row0, int64_t rows, float *out, int out_on_device, uint32_t *tri_out, double *z64_out,
                        uint64_t *capped_walks);
     const char *och_ortho_last_error(void);
+    /* ---- layered full-resolution orthomosaic (opencalibration_amd/csrc/host/ortho_layers.cpp; src/ortho/ortho.cpp:
+     * 1206-1663) -----------------------------------------------------------------------------------------------------------
+     * och_ortho_layers_cameras: the involved nodes (finite orientation, node order) as ochip_ortho_layers' camera records
+     * (cams [n][28], node_ids, model_ids, image_hw [n][2] = the model's pixels_rows, pixels_cols; each may be NULL);
+     * returns n.  Camera i of the render is involved node i.
+     * och_ortho_layers_render: rows [row0, row0 + rows) of plan8 (och_dsm_plan's full-resolution plan), whole tile rows
+     * from a tile row (the raster's last may be partial); config4 = {num_layers 1..8, tile_size,
+     * correspondence_kernel_radius, correspondence_subsample}.  images [n]: one BGR image per involved camera,
+     * image_hw[i] rows x cols x 3 bytes, refused unless that is the model's size; host pointers for the CPU route, device
+     * pointers for the device route.  ctx and dev (och_ortho_mesh_upload) == NULL: the CPU route (brute-force kNN, one
+     * thread per row, host outputs), whose heights are dsm_in ([rows][width] float) when given; else the device
+     * (out_on_device: bgra / ids / weight are device pointers).  Outputs as ochip_ortho_layers; corr_out == NULL (capacity
+     * 0): *n_corr is the count only.  -1 + och_ortho_layers_last_error() on failure.
+     * och_lab_convert (L1, the conversion both routes use): mode 0 BGR -> 8-bit Lab, 1 8-bit Lab -> BGR (3 bytes each),
+     * 2 BGR -> float Lab (3 floats).  och_ortho_patch_sample: PatchSampler::sampleWithJacobian at world point xyz for one
+     * camera record over img; returns 1 with bgr_out, 0 when the camera does not see the point; pixel2 and J4 (row-major
+     * d pixel / d (x, y)) are always written.  och_ortho_sample_fields: normalized radius, x, y, the blend weight and
+     * acos(cos_view) as the render computes them. */
+    size_t och_ortho_layers_cameras(const och_graph *g, const och_surface *const *surfaces, size_t n, double *cams,
+                                    uint64_t *node_ids, uint32_t *model_ids, int64_t *image_hw);
+    int och_ortho_layers_render(const och_graph *g, ochip_ctx *ctx, ochip_ortho_mesh *dev, const och_surface *const *surfaces,
+                                size_t n, const double *plan8, const int32_t *config4, int64_t row0, int64_t rows,
+                                const uint64_t *images, const int64_t *image_hw, const float *dsm_in, int out_on_device,
+                                uint8_t *bgra, uint64_t *ids, float *weight, ochip_color_corr *corr_out, uint64_t corr_capacity,
+                                uint64_t *n_corr, uint32_t *knn_out);
+    const char *och_ortho_layers_last_error(void);
+    void och_lab_convert(int mode, const uint8_t *in, size_t n, void *out);
+    int och_ortho_patch_sample(const double *cam28, const uint8_t *img, double gsd, const double *xyz, uint8_t *bgr_out,
+                               double *pixel2, double *J4);
+    void och_ortho_sample_fields(double pixel_x, double pixel_y, int32_t width, int32_t height, float camera_distance,
+                                 double cos_view, float *out5);
 
 #ifdef __cplusplus
 }

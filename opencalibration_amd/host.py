@@ -236,6 +236,16 @@ def load():
         L.och_ortho_mesh_upload.argtypes = [vp, vp, sz, C.POINTER(vp)]
         L.och_dsm_render.argtypes = [vp, vp, vp, sz, _f64p, i64, i64, vp, C.c_int, vp, vp, C.POINTER(u64)]
         L.och_ortho_last_error.restype = C.c_char_p
+        L.och_ortho_layers_cameras.argtypes = [vp, vp, sz, vp, vp, vp, vp]
+        L.och_ortho_layers_cameras.restype = sz
+        L.och_ortho_layers_render.argtypes = [vp, vp, vp, vp, sz, _f64p, vp, i64, i64, vp, vp, vp, C.c_int, vp, vp, vp, vp, u64,
+                                              C.POINTER(u64), vp]
+        L.och_ortho_layers_last_error.restype = C.c_char_p
+        L.och_lab_convert.argtypes = [C.c_int, vp, sz, vp]
+        L.och_lab_convert.restype = None
+        L.och_ortho_patch_sample.argtypes = [vp, vp, f64, vp, vp, vp, vp]
+        L.och_ortho_sample_fields.argtypes = [f64, f64, i32, i32, C.c_float, f64, vp]
+        L.och_ortho_sample_fields.restype = None
         _lib = L
     return _lib
 
@@ -603,6 +613,194 @@ def dsm_render(plan, surfaces=(), mesh=None, row0=0, rows=None, out=None, debug=
     if rc != 0:
         raise capi.OchipError(L.och_ortho_last_error().decode())
     return (out, tri, z64, int(capped.value)) if debug else out
+
+
+# ---- layered full-resolution orthomosaic (include/oc_host.h; src/ortho/ortho.cpp:1206-1663) ----------------------------
+# ochip_color_corr (include/ochip.h): a ColorCorrespondence and where it was taken
+CORR_DTYPE = np.dtype([("lab_a", np.float32, 3), ("lab_b", np.float32, 3), ("camera_id_a", np.uint64),
+                       ("camera_id_b", np.uint64), ("model_id_a", np.uint32), ("model_id_b", np.uint32),
+                       ("normalized_radius_a", np.float32), ("normalized_radius_b", np.float32),
+                       ("view_angle_a", np.float32), ("view_angle_b", np.float32), ("normalized_x_a", np.float32),
+                       ("normalized_y_a", np.float32), ("normalized_x_b", np.float32), ("normalized_y_b", np.float32),
+                       ("row", np.int32), ("col", np.int32), ("layer_a", np.uint32), ("layer_b", np.uint32)])
+assert CORR_DTYPE.itemsize == 96
+# OrthoMosaicConfig's defaults (include/opencalibration/ortho/ortho.hpp)
+LAYERS_CONFIG = dict(num_layers=2, tile_size=1024, correspondence_kernel_radius=2, correspondence_subsample=50)
+
+
+def _layers_config(config):
+    cfg = dict(LAYERS_CONFIG, **(config or {}))
+    unknown = set(cfg) - set(LAYERS_CONFIG)
+    if unknown:
+        raise ValueError(f"unknown layered-orthomosaic settings {sorted(unknown)}")
+    return cfg, np.array([cfg[k] for k in ("num_layers", "tile_size", "correspondence_kernel_radius",
+                                           "correspondence_subsample")], np.int32)
+
+
+def ortho_layers_cameras(graph, surfaces):
+    """The involved nodes' camera records of the layered render: cams (n x 28), node_ids, model_ids, image_hw (n x 2).
+    images[i] of ortho_layers belongs to node_ids[i]."""
+    L = load()
+    arr, n = _surface_array(surfaces)
+    k = L.och_ortho_layers_cameras(graph.h, arr, n, None, None, None, None)
+    cams, ids = np.zeros((k, 28)), np.zeros(k, np.uint64)
+    models, hw = np.zeros(k, np.uint32), np.zeros((k, 2), np.int64)
+    L.och_ortho_layers_cameras(graph.h, arr, n, cams.ctypes.data, ids.ctypes.data, models.ctypes.data, hw.ctypes.data)
+    return dict(cams=cams, node_ids=ids, model_ids=models, image_hw=hw)
+
+
+def _corr_bound(rows, width, cfg):
+    """At most this many records in a band: every sampled pixel (boundary: (r + c) % s == 0 per tile row, else the
+    multiples of s) times C(num_layers, 2)."""
+    t, s, nl = cfg["tile_size"], cfg["correspondence_subsample"], cfg["num_layers"]
+    if s <= 0 or nl < 2:
+        return 0
+    total = 0
+    for r0 in range(0, rows, t):
+        th = min(t, rows - r0)
+        for c0 in range(0, width, t):
+            tw = min(t, width - c0)
+            total += th * -(-tw // s) + -(-th // s) * -(-tw // s)
+    return total * nl * (nl - 1) // 2
+
+
+def ortho_layers(plan, graph, surfaces, images, mesh=None, row0=0, tile_rows=None, config=None, out=None, dsm=None,
+                 debug_knn=False):
+    """Rows of tile rows [row0 / tile_size, + tile_rows) of the layered full-resolution orthomosaic (processLayeredTile,
+    src/ortho/ortho.cpp:1206-1429) over `plan` (dsm_plan).  images: one BGR uint8 array per involved node
+    (ortho_layers_cameras' order), pixels_rows x pixels_cols x 3: numpy arrays for the CPU route, CUDA tensors (or raw
+    device pointers, int) for the device route.  mesh (an OrthoMesh): on its device; None: the CPU route, whose heights
+    are `dsm` (float32, rows x width) when given.  config overrides OrthoMosaicConfig's defaults (LAYERS_CONFIG).
+    out (device route): dict of CUDA tensors bgra (L, rows, width, 4) uint8, camera_id (L, rows, width) int64 (the uint64
+    ids' bits) and optionally weight (L, rows, width) float32, written in place.
+    Returns dict(bgra, camera_id, weight, correspondences (CORR_DTYPE), row0, rows[, knn])."""
+    L = load()
+    cfg, config4 = _layers_config(config)
+    t = cfg["tile_size"]
+    if row0 % t:
+        raise ValueError(f"row0 {row0} is not on a tile row (tile_size {t})")
+    rows = plan["height"] - row0 if tile_rows is None else min(tile_rows * t, plan["height"] - row0)
+    w, nl = plan["width"], cfg["num_layers"]
+    arr, n = _surface_array(surfaces)
+    on_device = out is not None
+    keep, tensor_images = [], False
+    ptrs, hw = [], []
+    for im in images:
+        if isinstance(im, int):
+            ptrs.append(im)
+            hw.append(None)
+            continue
+        if isinstance(im, np.ndarray):
+            if mesh is not None:
+                raise ValueError("the device route reads device images (CUDA tensors or device pointers)")
+            if im.dtype != np.uint8 or im.ndim != 3 or im.shape[2] != 3:
+                raise ValueError("an image is rows x cols x 3 uint8")
+            im = np.ascontiguousarray(im)
+            keep.append(im)
+            ptrs.append(im.ctypes.data)
+        else:
+            if mesh is None:
+                raise ValueError("the CPU route reads host images (numpy arrays)")
+            if str(im.dtype) != "torch.uint8" or im.dim() != 3 or im.shape[2] != 3 or not im.is_cuda or not im.is_contiguous():
+                raise ValueError("a device image is a contiguous rows x cols x 3 uint8 CUDA tensor")
+            ptrs.append(im.data_ptr())
+            tensor_images = True
+        hw.append(tuple(im.shape[:2]))
+    cams = ortho_layers_cameras(graph, surfaces)
+    if len(ptrs) != len(cams["node_ids"]):
+        raise ValueError(f"{len(ptrs)} images for {len(cams['node_ids'])} involved nodes")
+    # raw pointers carry the model's size: the caller vouches for it
+    hw = np.array([h if h is not None else tuple(cams["image_hw"][i]) for i, h in enumerate(hw)], np.int64).reshape(-1, 2)
+    ptr_arr = np.array(ptrs, np.uint64)
+    if on_device:
+        if mesh is None:
+            raise ValueError("device outputs need the device route (mesh)")
+        import torch
+
+        shapes = dict(bgra=(nl, rows, w, 4), camera_id=(nl, rows, w), weight=(nl, rows, w))
+        dtypes = dict(bgra="torch.uint8", camera_id="torch.int64", weight="torch.float32")
+        for k in ("bgra", "camera_id") + (("weight",) if out.get("weight") is not None else ()):
+            o = out[k]
+            if tuple(o.shape) != shapes[k] or str(o.dtype) != dtypes[k] or not o.is_cuda or not o.is_contiguous() or \
+                    o.device.index != mesh.ctx.device:
+                raise ValueError(f"out[{k!r}] must be a contiguous {dtypes[k]} tensor of {shapes[k]} on device {mesh.ctx.device}")
+        # the kernels run on the context's own stream: torch's queued work (the allocations' fills) finishes first
+        torch.cuda.current_stream(out["bgra"].device).synchronize()
+        bgra, ids, weight = out["bgra"], out["camera_id"], out.get("weight")
+        p_bgra, p_ids, p_w = bgra.data_ptr(), ids.data_ptr(), None if weight is None else weight.data_ptr()
+    else:
+        bgra, ids, weight = np.zeros((nl, rows, w, 4), np.uint8), np.zeros((nl, rows, w), np.uint64), np.zeros((nl, rows, w), np.float32)
+        p_bgra, p_ids, p_w = bgra.ctypes.data, ids.ctypes.data, weight.ctypes.data
+    if tensor_images and not on_device:
+        import torch
+
+        torch.cuda.current_stream(mesh.ctx.device).synchronize()  # the images' uploads finish first
+    dsm_p = None
+    if dsm is not None:
+        if mesh is not None:
+            raise ValueError("dsm is the CPU route's input")
+        dsm = np.ascontiguousarray(dsm, np.float32)
+        if dsm.shape != (rows, w):
+            raise ValueError(f"dsm must be {rows} x {w}")
+        dsm_p = dsm.ctypes.data
+    cap = _corr_bound(rows, w, cfg)
+    corr = np.zeros(max(cap, 1), CORR_DTYPE)
+    knn = np.zeros((rows, w, 5), np.uint32) if debug_knn else None
+    n_corr = C.c_uint64(0)
+    rc = L.och_ortho_layers_render(graph.h, mesh.ctx.h if mesh is not None else None, mesh.h if mesh is not None else None,
+                                   arr, n, _plan_array(plan), config4.ctypes.data, int(row0), int(rows),
+                                   ptr_arr.ctypes.data if len(ptr_arr) else None, hw.ctypes.data if len(hw) else None,
+                                   dsm_p, int(on_device), p_bgra, p_ids, p_w, corr.ctypes.data, cap, C.byref(n_corr),
+                                   None if knn is None else knn.ctypes.data)
+    if rc != 0:
+        raise capi.OchipError(L.och_ortho_layers_last_error().decode())
+    if n_corr.value > cap:
+        raise capi.OchipError(f"{n_corr.value} correspondences exceed their bound {cap}")
+    res = dict(bgra=bgra, camera_id=ids, weight=weight, correspondences=corr[:n_corr.value], row0=row0, rows=rows)
+    if knn is not None:
+        res["knn"] = knn
+    return res
+
+
+def ortho_layers_bands(plan, graph, surfaces, images, mesh=None, tile_rows=1, config=None):
+    """ortho_layers over the whole raster, tile_rows output tile rows per band, in raster order (generateLayeredGeoTIFF's
+    tile loop, src/ortho/ortho.cpp:1513-1600, row-major): yields each band's result."""
+    cfg, _ = _layers_config(config)
+    for row0 in range(0, plan["height"], tile_rows * cfg["tile_size"]):
+        yield ortho_layers(plan, graph, surfaces, images, mesh=mesh, row0=row0, tile_rows=tile_rows, config=config)
+
+
+def lab_convert(values, mode):
+    """L1, the colour conversion of the layered render: mode "bgr2lab8" / "lab82bgr" (N x 3 uint8 -> uint8) or
+    "bgr2labf" (N x 3 uint8 -> float32)."""
+    v = np.ascontiguousarray(values, np.uint8).reshape(-1, 3)
+    m = {"bgr2lab8": 0, "lab82bgr": 1, "bgr2labf": 2}[mode]
+    out = np.zeros(v.shape, np.float32 if m == 2 else np.uint8)
+    load().och_lab_convert(m, v.ctypes.data, len(v), out.ctypes.data)
+    return out
+
+
+def ortho_patch_sample(cam28, image, gsd, xyz):
+    """PatchSampler::sampleWithJacobian (src/ortho/ortho.cpp:117-213) of one camera record (ortho_layers_cameras) at a
+    world point: (bgr or None, pixel, J)."""
+    img = np.ascontiguousarray(image, np.uint8)
+    cam = np.ascontiguousarray(cam28, np.float64)
+    if img.shape != (int(cam[21]), int(cam[20]), 3):
+        raise ValueError("the image must be the model's pixels_rows x pixels_cols x 3")
+    xyz = np.ascontiguousarray(xyz, np.float64)
+    bgr, pixel, J = np.zeros(3, np.uint8), np.zeros(2), np.zeros(4)
+    ok = load().och_ortho_patch_sample(cam.ctypes.data, img.ctypes.data, float(gsd), xyz.ctypes.data, bgr.ctypes.data,
+                                       pixel.ctypes.data, J.ctypes.data)
+    return (bgr if ok else None), pixel, J.reshape(2, 2)
+
+
+def ortho_sample_fields(pixel_x, pixel_y, width, height, camera_distance, cos_view=1.0):
+    """normalizedImageRadius, normalizedImagePosition, computeBlendWeight and the view angle as the layered render
+    computes them: float32 (radius, x, y, weight, angle)."""
+    out = np.zeros(5, np.float32)
+    load().och_ortho_sample_fields(float(pixel_x), float(pixel_y), int(width), int(height), float(camera_distance),
+                                   float(cos_view), out.ctypes.data)
+    return out
 
 
 def relax(ctx, node_pos, node_ori, model10, features, pose_node, pose_ori, packed_edges, options, grid_fraction=0.1,
