@@ -617,6 +617,22 @@ extern "C"
     /* out[i] = x[i] op y[i] computed on the device with the hot-path kernels' compile flags:
      * op 0: x/y, 1: sqrt(x), 2: log(x), 3: x*y+x (unfused), 4: x+y.  Host pointers. */
     int ochip_debug_fp64(ochip_ctx *ctx, int op, const double *x, const double *y, size_t n, double *out);
+    /* The linear algebra of one relax LM step on a given system, for the tests: the plan of lm_system_resize and the
+     * launches of lm_solve (relax_lm.hip: lm_linear_step).  Input: A (n x n row-major, lower triangle read; a non-zero
+     * outside the envelope is OCHIP_EINVAL), g, scale, diagonal (n each), the trust-region radius and the envelope as
+     * lm_envelope holds it: env_end per 64-column block (ceil(n / 64) entries), tail_begin and n_region_begin first blocks
+     * of the band's regions (may be 0).  route 0: chol_tiles_kernel, 1: the launch chain chol_diag / panel / update.
+     * back 0: the back-solve lm_solve picks, 1: back_solve_kernel (one workgroup), 2: back_solve_regions_kernel with x in
+     * LDS, 3: the same with x in HBM.  Output: x (n) solves (S A S + D) x = S g, y (n) = L^-1 S g (the factored
+     * augmented row), L_out (n x n, may be NULL) the factor with unstored entries 0, W_out ((n + 1) x n, may be NULL) the
+     * system as built, lower triangle, row n = S g; scal1_out the model cost change (may be NULL); info_out[8]: [0] the
+     * factorisation's failure flag, [1] the claim order (0 column order, 1 tail first, 2 regions), [2] the device's
+     * slots for the factorisation's workgroups, [3] stored tiles, [4] claims, [5] regions, [6] the back-solve run (1 - 3),
+     * [7] 0.  Host pointers.  n = 0: nothing to factor, OCHIP_OK. */
+    int ochip_debug_lm_step(ochip_ctx *ctx, int n, const double *A, const double *g, const double *scale, const double *diagonal,
+                            double radius, const int32_t *env_end, int32_t tail_begin, const int32_t *region_begin, int32_t n_region_begin,
+                            int32_t route, int32_t back, double *x_out, double *y_out, double *L_out, double *W_out, double *scal1_out,
+                            int32_t *info_out);
 
     /* ---- dense guided matching: the descriptor search of densifyMesh (src/dense/dense_stereo.cpp:245-283) ------------
      * The index holds, for every image, its dense features sorted by the cell of a uniform grid over the image (cell edge

@@ -31,7 +31,7 @@ EXPORTS = [
     "ochip_relaxp_problem_create", "ochip_relaxp_problem_destroy", "ochip_relaxp_set_structure_only", "ochip_relaxp_solve",
     "ochip_relaxp_get_state",
     "ochip_profile_reset", "ochip_profile_get", "ochip_match_work", "ochip_relax_work", "ochip_relax_memory", "ochip_work_counters",
-    "ochip_debug_fp64", "ochip_debug_std_sort", "ochip_match_sort", "ochip_ransac_homography_batch_sorted", "ochip_edge_lists",
+    "ochip_debug_fp64", "ochip_debug_std_sort", "ochip_debug_lm_step", "ochip_match_sort", "ochip_ransac_homography_batch_sorted", "ochip_edge_lists",
     "ochip_dense_index_create", "ochip_dense_index_destroy", "ochip_dense_match", "ochip_dense_link", "ochip_dense_triangulate",
     "ochip_rccl_unique_id", "ochip_rccl_comm_create", "ochip_rccl_comm_destroy", "ochip_rccl_comm_stats",
     "ochip_rccl_relax_exchange",
@@ -39,6 +39,21 @@ EXPORTS = [
 ]
 
 _lib = None
+
+
+class RelaxgDesc(C.Structure):
+    """include/ochip.h: ochip_relaxg_desc"""
+    _fields_ = [("n_cams", C.c_uint32), ("cam_pos", C.c_void_p), ("cam_q", C.c_void_p), ("cam_optimize", C.c_void_p),
+                ("n_verts", C.c_uint32), ("vert_xy", C.c_void_p), ("vert_z", C.c_void_p), ("vert_optimize", C.c_void_p),
+                ("n_blocks", C.c_uint32), ("blk_n", C.c_void_p), ("blk_intr", C.c_void_p), ("blk_ray_off", C.c_void_p),
+                ("blk_tri", C.c_void_p), ("ray_cam", C.c_void_p), ("ray_dir", C.c_void_p), ("ray_px", C.c_void_p),
+                ("n_down", C.c_uint32), ("down_cam", C.c_void_p), ("down_weight", C.c_double),
+                ("n_diff", C.c_uint32), ("diff_v", C.c_void_p), ("diff_weight", C.c_double), ("anchor_weight", C.c_double),
+                ("n_smooth", C.c_uint32), ("smooth_v", C.c_void_p), ("smooth_weight", C.c_double), ("huber_a", C.c_double),
+                ("model", C.c_double * 8), ("opt_focal", C.c_uint8), ("opt_principal", C.c_uint8), ("n_radial_free", C.c_uint8),
+                ("focal_lo", C.c_double), ("focal_hi", C.c_double), ("mono_observations", C.c_uint32), ("mono_r_max", C.c_double),
+                ("shard_rank", C.c_uint32), ("shard_world", C.c_uint32),
+                ("n_rel", C.c_uint32), ("rel_cam", C.c_void_p), ("rel_pose", C.c_void_p), ("rel_huber_a", C.c_double)]
 
 
 class OchipError(RuntimeError):
@@ -78,6 +93,7 @@ def load():
         L.ochip_relax_memory.argtypes = [vp, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64)]
         L.ochip_debug_fp64.argtypes = [vp, i32, vp, vp, C.c_size_t, vp]
         L.ochip_debug_std_sort.argtypes = [vp, vp, vp, vp, u32, vp, vp, vp]
+        L.ochip_debug_lm_step.argtypes = [vp, i32, vp, vp, vp, vp, C.c_double, vp, i32, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp]
         L.ochip_akaze_batch.argtypes = [vp, vp, u32, i32, i32, u32, vp, vp, vp, vp]
         L.ochip_feature_lists_from_keypoints.argtypes = [vp, vp, vp, vp, u32, u32, i32, i32, C.c_double, C.c_double, vp]
         L.ochip_akaze_batch_dev.argtypes = [vp, vp, u32, i32, i32, u32, vp, vp, vp, vp]
@@ -309,6 +325,83 @@ class Context:
         self._check(self.L.ochip_debug_fp64(self.h, op, x.ctypes.data, y.ctypes.data, x.size, out.ctypes.data),
                     "ochip_debug_fp64")
         return out
+
+    def debug_lm_step(self, A, g, scale, diagonal, radius, env_end, tail_begin, region_begin=(), route=0, back=0, want_L=True,
+                      want_W=True):
+        """ochip_debug_lm_step: one LM step's build, factorisation and back-solve on the dense system A (lower triangle
+        read).  route 0: tiles, 1: launch chain; back 0: lm_solve's choice, 1: single workgroup, 2: regions (x in LDS),
+        3: regions (x in HBM).  Returns dict x, y, L (n x n or None), W ((n + 1) x n or None), scal1, fail, order (0 column
+        order, 1 tail first, 2 regions), slots, tiles, claims, regions, back."""
+        A = np.ascontiguousarray(A, np.float64)
+        n = int(A.shape[0]) if A.ndim == 2 else 0
+        vec = lambda v: np.ascontiguousarray(v, np.float64).reshape(-1) if n else np.zeros(1)
+        g, scale, diagonal = vec(g), vec(scale), vec(diagonal)
+        env = np.ascontiguousarray(env_end, np.int32).reshape(-1)
+        assert len(env) == (n + 63) // 64, (len(env), n)
+        env = env if len(env) else np.zeros(1, np.int32)
+        rb = np.ascontiguousarray(region_begin, np.int32).reshape(-1)
+        n_rb = len(rb)
+        rb = rb if n_rb else np.zeros(1, np.int32)
+        m = max(n, 1)
+        x, y = np.zeros(m), np.zeros(m)
+        L = np.zeros((n, n)) if want_L and n else None
+        W = np.zeros((n + 1, n)) if want_W and n else None
+        s1 = C.c_double()
+        info = np.zeros(8, np.int32)
+        Ain = A if n else np.zeros(1)
+        self._check(self.L.ochip_debug_lm_step(self.h, n, Ain.ctypes.data, g.ctypes.data, scale.ctypes.data, diagonal.ctypes.data,
+                                               float(radius), env.ctypes.data, int(tail_begin), rb.ctypes.data, n_rb, int(route),
+                                               int(back), x.ctypes.data, y.ctypes.data, None if L is None else L.ctypes.data,
+                                               None if W is None else W.ctypes.data, C.byref(s1), info.ctypes.data),
+                    "ochip_debug_lm_step")
+        return dict(x=x[:n], y=y[:n], L=L, W=W, scal1=s1.value, fail=int(info[0]), order=int(info[1]), slots=int(info[2]),
+                    tiles=int(info[3]), claims=int(info[4]), regions=int(info[5]), back=int(info[6]))
+
+    def relaxg_evaluate(self, scene):
+        """One evaluation of a general-engine relax problem (ochip_relaxg_problem_create, ochip_relaxg_evaluate, destroy):
+        (cost, dense J'J, J'r, first unknown per camera / vertex / f / pp / k).  scene: dict of the ochip_relaxg_desc fields
+        (cameras, vertices, 2-ray blocks without intrinsics, priors); what it leaves out is zero."""
+        d = RelaxgDesc()
+        keep = []
+
+        def arr(name, dtype):
+            a = np.ascontiguousarray(scene[name], dtype)
+            keep.append(a)
+            return a.ctypes.data
+
+        d.n_cams = len(scene["cam_pos"])
+        d.cam_pos, d.cam_q, d.cam_optimize = arr("cam_pos", np.float64), arr("cam_q", np.float64), arr("cam_optimize", np.uint8)
+        d.n_verts = len(scene["vert_z"])
+        d.vert_xy, d.vert_z, d.vert_optimize = arr("vert_xy", np.float64), arr("vert_z", np.float64), arr("vert_optimize", np.uint8)
+        d.n_blocks = len(scene["blk_n"])
+        d.blk_n, d.blk_ray_off, d.blk_tri = arr("blk_n", np.uint8), arr("blk_ray_off", np.uint32), arr("blk_tri", np.uint32)
+        d.ray_cam, d.ray_dir = arr("ray_cam", np.uint32), arr("ray_dir", np.float64)
+        d.n_down, d.down_cam, d.down_weight = len(scene["down_cam"]), arr("down_cam", np.uint32), scene["down_weight"]
+        d.n_diff, d.diff_v, d.diff_weight = np.size(scene["diff_v"]) // 2, arr("diff_v", np.uint32), scene["diff_weight"]
+        d.anchor_weight, d.huber_a = scene["anchor_weight"], scene["huber_a"]
+        for i, v in enumerate(scene["model"]):
+            d.model[i] = v
+        d.focal_lo, d.focal_hi = 100.0, 20000.0
+        p = C.c_void_p()
+        self.L.ochip_relaxg_problem_create.argtypes = [C.c_void_p, C.POINTER(RelaxgDesc), C.POINTER(C.c_void_p)]
+        self.L.ochip_relaxg_problem_destroy.argtypes = [C.c_void_p]
+        self.L.ochip_relaxg_problem_destroy.restype = None
+        self.L.ochip_relaxg_evaluate.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int), C.c_void_p, C.c_void_p,
+                                                 C.c_void_p]
+        self._check(self.L.ochip_relaxg_problem_create(self.h, C.byref(d), C.byref(p)), "ochip_relaxg_problem_create")
+        try:
+            cost, n = C.c_double(), C.c_int()
+            order = np.zeros(d.n_cams + d.n_verts + 3, np.int32)
+            rc = self.L.ochip_relaxg_evaluate(p, C.byref(cost), C.byref(n), None, None, order.ctypes.data)
+            if rc < 0:
+                self._check(rc, "ochip_relaxg_evaluate")
+            JtJ, Jtr = np.zeros((n.value, n.value)), np.zeros(n.value)
+            rc = self.L.ochip_relaxg_evaluate(p, C.byref(cost), C.byref(n), JtJ.ctypes.data, Jtr.ctypes.data, None)
+            if rc != 0:
+                raise OchipError(f"ochip_relaxg_evaluate = {rc}: {self.L.ochip_last_error(self.h).decode()}")
+        finally:
+            self.L.ochip_relaxg_problem_destroy(p)
+        return cost.value, JtJ, Jtr, order
 
     def profile_reset(self):
         self._check(self.L.ochip_profile_reset(self.h), "ochip_profile_reset")

@@ -211,6 +211,10 @@ __device__ __forceinline__ void chol_diag_panel_phase(double (&a)[4][4], double 
         }
         const double cross = c10 * rs0;        // l_{j+1,j}
         const double rs1 = rd1 * (piv0 * rs0); // 1 / sqrt(p1) = sqrt(p0) / sqrt(p1 p0)
+        // l_{j+1,j+1} as the inverse implies it: sqrt(p1 p0) / sqrt(p0).  (Not col1_own * rs1: that takes p1 from
+        // c11 - l_{j+1,j}^2, rounded apart from d1, and under cancellation (p1 << c11) the stored factor would differ from
+        // the inverse every solve uses by O(u c11 / p1).)
+        const double l11 = (d1 * rd1) * rs0;
         double li0[4], xr0[4], li1[4], xr1[4], l0full[4], col1_own[4];
 #pragma unroll
         for (int p = JB; p < 4; p++)
@@ -238,7 +242,7 @@ __device__ __forceinline__ void chol_diag_panel_phase(double (&a)[4][4], double 
             v -= li0[p] * l0c;
             v -= li1[p] * l1c;
             const double f0 = (p > JB || ty >= jt) ? l0full[p] : 0.0;
-            const double f1 = (p > JB || ty >= jt + 1) ? col1_own[p] * rs1 : 0.0;
+            const double f1 = (p > JB || ty > jt + 1) ? col1_own[p] * rs1 : (ty == jt + 1 ? l11 : 0.0);
             a[p][JB] = own0 ? f0 : (own1 ? f1 : v);
         }
 #pragma unroll

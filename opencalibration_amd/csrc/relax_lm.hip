@@ -1017,8 +1017,10 @@ int lm_system_resize(lm_system *s, int n_in, const lm_envelope &env)
             }
         }
         s->n_regions = region_bounds.empty() ? 1 : (int)region_bounds.size() - 1;
+        s->chol_slots = slots;
         if (s->n_regions > 1)
         {
+            s->chol_order = LM_ORDER_REGIONS;
             std::vector<int> band_cols;
             int longest = 0;
             for (int r = 0; r < s->n_regions; r++)
@@ -1039,14 +1041,18 @@ int lm_system_resize(lm_system *s, int n_in, const lm_envelope &env)
         }
         else if ((long)tail_tiles * 8 <= (long)slots)
         {
+            s->chol_order = LM_ORDER_TAIL_FIRST;
             for (int J = 0; J < nbc; J++)
                 rows_of(J, true, false);
             for (int J = 0; J < nbc; J++)
                 rows_of(J, false, true);
         }
         else
+        {
+            s->chol_order = LM_ORDER_COLUMNS;
             for (int J = 0; J < nbc; J++)
                 rows_of(J, true, true);
+        }
         int n_fused = 0;
         for (int I = 0; I < nbc; I++)
             n_fused += fused_diag[(size_t)I];
@@ -1161,6 +1167,152 @@ void lm_launch_diag(lm_system &S, const double *scale, const int32_t *fail_ranks
                        S.diagonal, mail);
 }
 
+int lm_back_default(const lm_system &S, bool x_global)
+{
+    // (the per-region kernel also serves the single band, as one region: it is the faster walk - rows of a block split over
+    // the wavefronts, x in LDS)
+    constexpr bool single = false; // (true: the round-2 single-workgroup kernel on a single band)
+    if (S.n_regions > 1 || (!single && S.region_dev))
+        return x_global ? LM_BACK_REGIONS_HBM : LM_BACK_REGIONS_LDS;
+    return LM_BACK_SINGLE;
+}
+
+// Build, factor and back-substitute one LM step: Wm = S A S + D with the augmented row gs = S g, the model's Schur term,
+// L L' = Wm in place (row n becomes y = L^-1 gs), x = L'^-1 y into S.y and the model cost change into scal[1].  Enqueued
+// on the context's stream; the failure flag is S.fail_chol.  lm_solve and ochip_debug_lm_step run this one function.
+int lm_linear_step(lm_system &S, double radius, const lm_step_args &a, bool *candidate_launched)
+{
+    ochip_ctx *ctx = S.ctx;
+    hipStream_t st = ctx->stream;
+    const int n = S.n;
+    lm_model *const M = a.model;
+    const bool eliminated = M && M->has_eliminated();
+    *candidate_launched = false;
+    if (n > 0)
+        hipLaunchKernelGGL(lm_build_kernel, dim3((unsigned)S.chol_n_tiles), dim3(256), 0, st, S.matA(), (const unsigned int *)S.tile_ij,
+                           (const double *)S.g, (const double *)S.scale, (const double *)S.diagonal, radius, S.lm_diag, S.matW(), S.gs,
+                           n, S.chol_sync, S.fail_chol);
+    else
+        OCHIP_HIP(ctx, hipMemsetAsync(S.fail_chol, 0, 4, st));
+    if (eliminated)
+        M->launch_schur(radius, S.scale, S.matW(), n, S.fail_chol);
+    if (a.w_built && n > 0)
+        OCHIP_HIP(ctx, hipMemcpyAsync(a.w_built, S.Wm, S.matrix_bytes(), hipMemcpyDeviceToDevice, st));
+    {
+        const size_t need = (size_t)((n + NB - 1) / NB) * NB * NB;
+        if (need > S.linv_cap)
+        {
+            S.linv = nullptr;
+            S.linv_cap = 0;
+            if (lm_dev_upload<double>(ctx, S.allocs, &S.linv, nullptr, need) != OCHIP_OK)
+                return ochip_fail(ctx, OCHIP_ENOMEM, "device allocation for the diagonal-block inverses failed");
+            S.linv_cap = need;
+        }
+    }
+    // the launch chain on (W, linv); count: add the algorithmic flops of the factorisation to the context's counter
+    auto launch_chain = [&](double *Wt, double *linv, bool launch, bool count) {
+        const lm_matrix W{Wt, S.chol_cols};
+        for (int k0 = 0; k0 < n; k0 += NB)
+        {
+            const int nb = std::min(NB, n - k0);
+            double *linv_k = linv + (size_t)(k0 / NB) * NB * NB;
+            if (launch)
+                hipLaunchKernelGGL(chol_diag_kernel, dim3(1), dim3(256), 0, st, W, n, k0, nb, S.fail_chol, linv_k);
+            // rows below the block that can be non-zero: its envelope as the plan stores it (monotone, whole row blocks),
+            // then the tail (dense unknowns + augmented row)
+            const int below = k0 + nb;
+            const int tail_rows_begin = std::min(S.env.tail_begin, n);
+            const int band_end = std::max(below, std::min(S.cols_host[(size_t)(k0 / NB)].bend * NB, tail_rows_begin));
+            const int tail0 = std::max(tail_rows_begin, below);
+            row_set rs{below, band_end - below, tail0, (band_end - below) + (n + 1 - tail0)};
+            const int tiles = (rs.total + 63) / 64;
+            if (count)
+                ctx->relax_mfma_flops += 2.0 * rs.total * nb * nb + (below < n ? 1.0 * rs.total * rs.total * nb : 0.0);
+            if (!launch)
+                continue;
+            hipLaunchKernelGGL(chol_panel_kernel, dim3(tiles), dim3(256), 0, st, W, n, rs, k0, nb, linv_k);
+            if (below < n)
+                hipLaunchKernelGGL(chol_update_mfma_kernel, dim3(tiles, tiles), dim3(256), 0, st, W, n, rs, k0, nb);
+        }
+    };
+    if (n == 0)
+        ; // (every unknown is eliminated: nothing to factor)
+    else if (a.route == LM_ROUTE_CHAIN)
+        launch_chain(S.Wm, S.linv, true, true);
+    else
+    {
+        const bool verify = a.verify; // run both on the same system and compare
+        double *Wv = nullptr, *linv_v = nullptr;
+        size_t got_w = 0, got_l = 0;
+        if (verify)
+        {
+            Wv = (double *)ochip_pool_get(ctx, S.matrix_bytes(), &got_w);
+            linv_v = (double *)ochip_pool_get(ctx, (size_t)((n + NB - 1) / NB) * NB * NB * 8, &got_l);
+            if (!Wv || !linv_v)
+                return ochip_fail(ctx, OCHIP_ENOMEM, "chol_verify: device allocation failed");
+            OCHIP_HIP(ctx, hipMemcpyAsync(Wv, S.Wm, S.matrix_bytes(), hipMemcpyDeviceToDevice, st));
+        }
+        // operands through LDS in halves (71 KB per workgroup; whole, 104 KB, measured equal alone and slower beside the
+        // extraction's kernels, whose workgroups leave 71 KB free on a compute unit sooner); blocked diagonal tiles
+        hipLaunchKernelGGL(chol_tiles_kernel<32>, dim3((unsigned)S.chol_grid), dim3(256), 0, st, S.Wm, n, (const chol_col *)S.chol_cols,
+                           (const int *)S.chol_kmin, (const unsigned int *)S.chol_tiles, S.chol_n_claims, S.chol_tb, S.chol_sync,
+                           S.linv, S.fail_chol, (unsigned long long *)nullptr, (const int *)S.chol_korder, 1);
+        launch_chain(S.Wm, S.linv, false, true);
+        if (verify)
+        {
+            launch_chain(Wv, linv_v, true, false);
+            std::vector<double> ya(n), yb(n);
+            hipLaunchKernelGGL(lm_aug_row_kernel, dim3((n + 255) / 256), dim3(256), 0, st, S.matW(), n, S.y);
+            OCHIP_HIP(ctx, hipMemcpyAsync(ya.data(), S.y, (size_t)n * 8, hipMemcpyDeviceToHost, st));
+            hipLaunchKernelGGL(lm_aug_row_kernel, dim3((n + 255) / 256), dim3(256), 0, st, lm_matrix{Wv, S.chol_cols}, n, S.y);
+            OCHIP_HIP(ctx, hipMemcpyAsync(yb.data(), S.y, (size_t)n * 8, hipMemcpyDeviceToHost, st));
+            OCHIP_HIP(ctx, ochip_stream_wait(ctx, st));
+            double worst = 0, scale_y = 0;
+            bool nan = false;
+            for (int i = 0; i < n; i++)
+            {
+                scale_y = std::max(scale_y, std::abs(yb[i]));
+                worst = std::max(worst, std::abs(ya[i] - yb[i]));
+                nan = nan || (std::isnan(ya[i]) != std::isnan(yb[i]));
+            }
+            ochip_pool_put(ctx, Wv, got_w);
+            ochip_pool_put(ctx, linv_v, got_l);
+            const bool loud = ochip_verbose("relax");
+            if (loud)
+                fprintf(stderr, "[ochip relax] factorisation check: n=%d forward solve differs by %.3g (scale %.3g)\n", n, worst, scale_y);
+            // (1e-7: the two factorisations round differently - blocked against rank-1 updates, the second pivot of a step
+            // from p1 p0 - and a nearly singular system amplifies that: 1.7e-9 on the 12 unknowns of a point triangulation
+            // with a trust region of 1e16; a misplaced tile shows up as O(1))
+            if (nan || worst > 1e-7 * std::max(scale_y, 1e-300))
+                return ochip_fail(ctx, OCHIP_EINVAL, "chol_verify: the tile factorisation and the launch chain disagree (n = %d, "
+                                  "forward solve differs by %g at scale %g)", n, worst, scale_y);
+        }
+    }
+    // row n now holds y = L^-1 gs; back-substitute L' x = y block by block
+    if (n > 0)
+    {
+        if (a.back == LM_BACK_REGIONS_LDS || a.back == LM_BACK_REGIONS_HBM)
+        {
+            const int x_in_lds = a.back == LM_BACK_REGIONS_LDS ? 1 : 0;
+            const lm_model::back_args ba{S.matW(), n, S.linv, S.y, S.back_work, S.chol_kmin, (n + NB - 1) / NB, S.region_dev, S.chol_tb,
+                                         S.lm_diag, S.gs, S.scal, S.chol_sync + 1, x_in_lds, S.n_regions};
+            if (M && M->speculates() && !M->is_constrained() && !eliminated && M->launch_back_solve_candidate(ba, S.scale))
+                *candidate_launched = true;
+            else
+                hipLaunchKernelGGL(back_solve_regions_kernel, dim3((unsigned)S.n_regions), dim3(LM_TG), 0, st, S.matW(), n,
+                                   (const double *)S.linv, S.y, S.back_work, (const int *)S.chol_kmin, (n + NB - 1) / NB,
+                                   (const int *)S.region_dev, S.chol_tb, (const double *)S.lm_diag, (const double *)S.gs, S.scal,
+                                   S.chol_sync + 1, x_in_lds);
+        }
+        else
+            hipLaunchKernelGGL(back_solve_kernel, dim3(1), dim3(LM_TG), 0, st, S.matW(), n, (const double *)S.linv, S.y,
+                               (const int *)S.chol_kmin, (n + NB - 1) / NB, (const double *)S.lm_diag, (const double *)S.gs, S.scal);
+    }
+    else
+        hipLaunchKernelGGL(lm_model_change_kernel, dim3(1), dim3(LM_TG), 0, st, S.lm_diag, S.gs, S.y, n, S.scal);
+    return OCHIP_OK;
+}
+
 // Trust-region Levenberg-Marquardt, monotonic steps (Ceres TrustRegionMinimizer + LevenbergMarquardtStrategy semantics,
 // SURVEY.md Appendix B).  The control flow runs on the host side of the library; every O(problem) operation is a kernel.
 int lm_solve(lm_system &S, lm_model &M, const ochip_relax_options *opt, ochip_relax_summary *sum)
@@ -1245,131 +1397,20 @@ int lm_solve(lm_system &S, lm_model &M, const ochip_relax_options *opt, ochip_re
         // accepted point's Jacobian - lm_diag_kernel - and divided by this iteration's radius inside lm_build_kernel)
         hipEvent_t e0, e1;
         ochip_prof_begin(ctx, OCHIP_K_RELAX_SOLVE, &e0, &e1);
-        if (n > 0)
-            hipLaunchKernelGGL(lm_build_kernel, dim3((unsigned)S.chol_n_tiles), dim3(256), 0, st, S.matA(), (const unsigned int *)S.tile_ij,
-                               (const double *)S.g, (const double *)S.scale, (const double *)S.diagonal, radius, S.lm_diag, S.matW(), S.gs,
-                               n, S.chol_sync, S.fail_chol);
-        else
-            OCHIP_HIP(ctx, hipMemsetAsync(S.fail_chol, 0, 4, st));
-        if (eliminated)
-            M.launch_schur(radius, S.scale, S.matW(), n, S.fail_chol);
-        {
-            const size_t need = (size_t)((n + NB - 1) / NB) * NB * NB;
-            if (need > S.linv_cap)
-            {
-                S.linv = nullptr;
-                S.linv_cap = 0;
-                if (lm_dev_upload<double>(ctx, S.allocs, &S.linv, nullptr, need) != OCHIP_OK)
-                    return ochip_fail(ctx, OCHIP_ENOMEM, "device allocation for the diagonal-block inverses failed");
-                S.linv_cap = need;
-            }
-        }
-        constexpr bool chain = false; // (true: the launch chain per block column, the round-2 schedule; chol_verify runs it beside the tiles)
-        static const bool verify = ochip_test_hook("chol_verify"); // run both on the same system and compare
-        // the launch chain on (W, linv); count: add the algorithmic flops of the factorisation to the context's counter
-        auto launch_chain = [&](double *Wt, double *linv, bool launch, bool count) {
-            const lm_matrix W{Wt, S.chol_cols};
-            for (int k0 = 0; k0 < n; k0 += NB)
-            {
-                const int nb = std::min(NB, n - k0);
-                double *linv_k = linv + (size_t)(k0 / NB) * NB * NB;
-                if (launch)
-                    hipLaunchKernelGGL(chol_diag_kernel, dim3(1), dim3(256), 0, st, W, n, k0, nb, S.fail_chol, linv_k);
-                // rows below the block that can be non-zero: its envelope as the plan stores it (monotone, whole row blocks),
-                // then the tail (dense unknowns + augmented row)
-                const int below = k0 + nb;
-                const int tail_rows_begin = std::min(S.env.tail_begin, n);
-                const int band_end = std::max(below, std::min(S.cols_host[(size_t)(k0 / NB)].bend * NB, tail_rows_begin));
-                const int tail0 = std::max(tail_rows_begin, below);
-                row_set rs{below, band_end - below, tail0, (band_end - below) + (n + 1 - tail0)};
-                const int tiles = (rs.total + 63) / 64;
-                if (count)
-                    ctx->relax_mfma_flops += 2.0 * rs.total * nb * nb + (below < n ? 1.0 * rs.total * rs.total * nb : 0.0);
-                if (!launch)
-                    continue;
-                hipLaunchKernelGGL(chol_panel_kernel, dim3(tiles), dim3(256), 0, st, W, n, rs, k0, nb, linv_k);
-                if (below < n)
-                    hipLaunchKernelGGL(chol_update_mfma_kernel, dim3(tiles, tiles), dim3(256), 0, st, W, n, rs, k0, nb);
-            }
-        };
-        if (n == 0)
-            ; // (every unknown is eliminated: nothing to factor)
-        else if (chain)
-            launch_chain(S.Wm, S.linv, true, true);
-        else
-        {
-            double *Wv = nullptr, *linv_v = nullptr;
-            size_t got_w = 0, got_l = 0;
-            if (verify)
-            {
-                Wv = (double *)ochip_pool_get(ctx, S.matrix_bytes(), &got_w);
-                linv_v = (double *)ochip_pool_get(ctx, (size_t)((n + NB - 1) / NB) * NB * NB * 8, &got_l);
-                if (!Wv || !linv_v)
-                    return ochip_fail(ctx, OCHIP_ENOMEM, "chol_verify: device allocation failed");
-                OCHIP_HIP(ctx, hipMemcpyAsync(Wv, S.Wm, S.matrix_bytes(), hipMemcpyDeviceToDevice, st));
-            }
-            // operands through LDS in halves (71 KB per workgroup; whole, 104 KB, measured equal alone and slower beside the
-            // extraction's kernels, whose workgroups leave 71 KB free on a compute unit sooner); blocked diagonal tiles
-            hipLaunchKernelGGL(chol_tiles_kernel<32>, dim3((unsigned)S.chol_grid), dim3(256), 0, st, S.Wm, n, (const chol_col *)S.chol_cols,
-                               (const int *)S.chol_kmin, (const unsigned int *)S.chol_tiles, S.chol_n_claims, S.chol_tb, S.chol_sync,
-                               S.linv, S.fail_chol, (unsigned long long *)nullptr, (const int *)S.chol_korder, 1);
-            launch_chain(S.Wm, S.linv, false, true);
-            if (verify)
-            {
-                launch_chain(Wv, linv_v, true, false);
-                std::vector<double> ya(n), yb(n);
-                hipLaunchKernelGGL(lm_aug_row_kernel, dim3((n + 255) / 256), dim3(256), 0, st, S.matW(), n, S.y);
-                OCHIP_HIP(ctx, hipMemcpyAsync(ya.data(), S.y, (size_t)n * 8, hipMemcpyDeviceToHost, st));
-                hipLaunchKernelGGL(lm_aug_row_kernel, dim3((n + 255) / 256), dim3(256), 0, st, lm_matrix{Wv, S.chol_cols}, n, S.y);
-                OCHIP_HIP(ctx, hipMemcpyAsync(yb.data(), S.y, (size_t)n * 8, hipMemcpyDeviceToHost, st));
-                OCHIP_HIP(ctx, ochip_stream_wait(ctx, st));
-                double worst = 0, scale_y = 0;
-                bool nan = false;
-                for (int i = 0; i < n; i++)
-                {
-                    scale_y = std::max(scale_y, std::abs(yb[i]));
-                    worst = std::max(worst, std::abs(ya[i] - yb[i]));
-                    nan = nan || (std::isnan(ya[i]) != std::isnan(yb[i]));
-                }
-                ochip_pool_put(ctx, Wv, got_w);
-                ochip_pool_put(ctx, linv_v, got_l);
-                const bool loud = ochip_verbose("relax");
-                if (loud)
-                    fprintf(stderr, "[ochip relax] factorisation check: n=%d forward solve differs by %.3g (scale %.3g)\n", n, worst, scale_y);
-                // (1e-7: the two factorisations round differently - blocked against rank-1 updates, the second pivot of a step
-                // from p1 p0 - and a nearly singular system amplifies that: 1.7e-9 on the 12 unknowns of a point triangulation
-                // with a trust region of 1e16; a misplaced tile shows up as O(1))
-                if (nan || worst > 1e-7 * std::max(scale_y, 1e-300))
-                    return ochip_fail(ctx, OCHIP_EINVAL, "chol_verify: the tile factorisation and the launch chain disagree (n = %d, "
-                                      "forward solve differs by %g at scale %g)", n, worst, scale_y);
-            }
-        }
-        // row n now holds y = L^-1 gs; back-substitute L' x = y block by block
         bool candidate_launched = false;
-        if (n > 0)
         {
-            // (the per-region kernel also serves the single band, as one region: it is the faster walk - rows of a block
-            // split over the wavefronts, x in LDS; OCHIP_BACK_SOLVE_SINGLE=1: the round-2 kernel)
-            constexpr bool single = false; // (true: the round-2 single-workgroup kernel on a single band)
-            static const bool x_global = ochip_test_hook("back_solve_x_global"); // test knob: x in HBM even when it fits LDS
-            if (S.n_regions > 1 || (!single && S.region_dev))
-            {
-                const lm_model::back_args ba{S.matW(), n, S.linv, S.y, S.back_work, S.chol_kmin, (n + NB - 1) / NB, S.region_dev, S.chol_tb,
-                                             S.lm_diag, S.gs, S.scal, S.chol_sync + 1, x_global ? 0 : 1, S.n_regions};
-                if (M.speculates() && !M.is_constrained() && !eliminated && M.launch_back_solve_candidate(ba, S.scale))
-                    candidate_launched = true;
-                else
-                    hipLaunchKernelGGL(back_solve_regions_kernel, dim3((unsigned)S.n_regions), dim3(LM_TG), 0, st, S.matW(), n,
-                                       (const double *)S.linv, S.y, S.back_work, (const int *)S.chol_kmin, (n + NB - 1) / NB,
-                                       (const int *)S.region_dev, S.chol_tb, (const double *)S.lm_diag, (const double *)S.gs, S.scal,
-                                       S.chol_sync + 1, x_global ? 0 : 1);
-            }
-            else
-                hipLaunchKernelGGL(back_solve_kernel, dim3(1), dim3(LM_TG), 0, st, S.matW(), n, (const double *)S.linv, S.y,
-                                   (const int *)S.chol_kmin, (n + NB - 1) / NB, (const double *)S.lm_diag, (const double *)S.gs, S.scal);
+            constexpr bool chain = false; // (true: the launch chain per block column, the round-2 schedule; chol_verify runs it beside the tiles)
+            static const bool verify = ochip_test_hook("chol_verify");              // factor twice, tiles and chain, and compare
+            static const bool x_global = ochip_test_hook("back_solve_x_global");    // test knob: x in HBM even when it fits LDS
+            lm_step_args sa;
+            sa.route = chain ? LM_ROUTE_CHAIN : LM_ROUTE_TILES;
+            sa.back = lm_back_default(S, x_global);
+            sa.verify = verify;
+            sa.model = &M;
+            const int lrc = lm_linear_step(S, radius, sa, &candidate_launched);
+            if (lrc)
+                return lrc;
         }
-        else
-            hipLaunchKernelGGL(lm_model_change_kernel, dim3(1), dim3(LM_TG), 0, st, S.lm_diag, S.gs, S.y, n, S.scal);
         if (!candidate_launched)
             M.launch_candidate(S.y, S.scale, 1.0, S.scal);
         ochip_prof_end(ctx, OCHIP_K_RELAX_SOLVE, e0, e1);
@@ -1609,3 +1650,153 @@ int lm_solve(lm_system &S, lm_model &M, const ochip_relax_options *opt, ochip_re
 }
 
 } // namespace ochip
+
+// ---- test seam: one LM step's linear algebra on a given system (include/ochip.h: ochip_debug_lm_step) ----------------
+namespace
+{
+// the lower triangle (rows 0 .. rows - 1, columns < n) of a packed matrix as a dense row-major rows x n array; what the
+// envelope does not store is 0
+void lm_unpack_lower(const lm_system &S, const std::vector<double> &tiles, double *out, int rows)
+{
+    const int n = S.n;
+    std::fill(out, out + (size_t)rows * n, 0.0);
+    for (int J = 0; J < S.chol_nbc; J++)
+    {
+        const lm_col &c = S.cols_host[(size_t)J];
+        auto put = [&](int I, int t) {
+            const double *a = tiles.data() + ((size_t)t << 12);
+            for (int r = 0; r < NB; r++)
+                for (int q = 0; q < NB; q++)
+                {
+                    const int i = I * NB + r, j = J * NB + q;
+                    if (i < rows && j < n && j <= i)
+                        out[(size_t)i * n + j] = a[r * NB + q];
+                }
+        };
+        int t = c.first_tile;
+        for (int I = J; I < c.bend; I++)
+            put(I, t++);
+        for (int I = c.tail_start; I < S.chol_nbr; I++)
+            put(I, t++);
+    }
+}
+} // namespace
+
+extern "C" int ochip_debug_lm_step(ochip_ctx *ctx, int n, const double *A, const double *g, const double *scale, const double *diagonal,
+                                   double radius, const int32_t *env_end, int32_t tail_begin, const int32_t *region_begin,
+                                   int32_t n_region_begin, int32_t route, int32_t back, double *x_out, double *y_out, double *L_out,
+                                   double *W_out, double *scal1_out, int32_t *info_out)
+{
+    if (!ctx || n < 0 || !info_out || (n > 0 && (!A || !g || !scale || !diagonal || !env_end || !x_out || !y_out)) ||
+        (n_region_begin > 0 && !region_begin) || n_region_begin < 0 || (route != LM_ROUTE_TILES && route != LM_ROUTE_CHAIN) ||
+        back < 0 || back > LM_BACK_REGIONS_HBM)
+        return OCHIP_EINVAL;
+    OCHIP_HIP(ctx, hipSetDevice(ctx->device));
+    const int nbc = (n + NB - 1) / NB;
+    lm_envelope env;
+    env.env_end.assign(env_end, env_end + nbc);
+    env.tail_begin = tail_begin;
+    env.first_col.assign((size_t)std::max(nbc, 1), 0);
+    if (n_region_begin > 0)
+        env.region_begin.assign(region_begin, region_begin + n_region_begin);
+    // the system and everything it allocates go back to the pool on the way out
+    struct owner
+    {
+        ochip_ctx *ctx = nullptr;
+        std::vector<std::pair<void *, size_t>> allocs;
+        lm_system S;
+        ~owner()
+        {
+            (void)ochip_stream_wait(ctx, ctx->stream);
+            for (auto &a : allocs)
+                ochip_pool_put(ctx, a.first, a.second);
+        }
+    } o;
+    o.ctx = ctx;
+    lm_system &S = o.S;
+    S.ctx = ctx;
+    S.allocs = &o.allocs;
+    int rc = lm_system_resize(&S, n, env);
+    if (rc)
+        return rc;
+    hipStream_t st = ctx->stream;
+    double *w_built = nullptr, *y_dev = nullptr;
+    if (n > 0)
+    {
+        // A's lower triangle into the stored tiles; a non-zero the envelope does not hold is an error, not a silent drop
+        std::vector<double> tiles((size_t)S.chol_n_tiles * NB * NB, 0.0);
+        std::vector<int> tile_of((size_t)S.chol_nbr * std::max(S.chol_nbc, 1), -1);
+        for (int J = 0; J < S.chol_nbc; J++)
+        {
+            const lm_col &c = S.cols_host[(size_t)J];
+            int t = c.first_tile;
+            for (int I = J; I < c.bend; I++)
+                tile_of[(size_t)I * S.chol_nbc + J] = t++;
+            for (int I = c.tail_start; I < S.chol_nbr; I++)
+                tile_of[(size_t)I * S.chol_nbc + J] = t++;
+        }
+        for (int i = 0; i < n; i++)
+            for (int j = 0; j <= i; j++)
+            {
+                const double v = A[(size_t)i * n + j];
+                const int t = tile_of[(size_t)(i / NB) * S.chol_nbc + j / NB];
+                if (t >= 0)
+                    tiles[((size_t)t << 12) + (size_t)((i & 63) * NB + (j & 63))] = v;
+                else if (v != 0.0)
+                    return ochip_fail(ctx, OCHIP_EINVAL, "ochip_debug_lm_step: A(%d, %d) lies outside the envelope", i, j);
+            }
+        OCHIP_HIP(ctx, hipMemcpy(S.A, tiles.data(), S.matrix_bytes(), hipMemcpyHostToDevice));
+        OCHIP_HIP(ctx, hipMemcpy(S.g, g, (size_t)n * 8, hipMemcpyHostToDevice));
+        OCHIP_HIP(ctx, hipMemcpy(S.scale, scale, (size_t)n * 8, hipMemcpyHostToDevice));
+        OCHIP_HIP(ctx, hipMemcpy(S.diagonal, diagonal, (size_t)n * 8, hipMemcpyHostToDevice));
+        if (W_out && lm_dev_upload<double>(ctx, S.allocs, &w_built, nullptr, (size_t)S.chol_n_tiles * NB * NB) != OCHIP_OK)
+            return OCHIP_ENOMEM;
+        if (lm_dev_upload<double>(ctx, S.allocs, &y_dev, nullptr, (size_t)n) != OCHIP_OK)
+            return OCHIP_ENOMEM;
+    }
+    lm_step_args sa;
+    sa.route = route;
+    sa.back = back == 0 ? lm_back_default(S, false) : back;
+    sa.w_built = w_built;
+    bool candidate = false;
+    rc = lm_linear_step(S, radius, sa, &candidate);
+    if (rc)
+        return rc;
+    if (n > 0)
+        hipLaunchKernelGGL(lm_aug_row_kernel, dim3((n + 255) / 256), dim3(256), 0, st, S.matW(), n, y_dev);
+    OCHIP_HIP(ctx, hipGetLastError());
+    OCHIP_HIP(ctx, ochip_stream_wait(ctx, st));
+    double scal[8];
+    int fail = 0;
+    OCHIP_HIP(ctx, hipMemcpy(scal, S.scal, sizeof(scal), hipMemcpyDeviceToHost));
+    OCHIP_HIP(ctx, hipMemcpy(&fail, S.fail_chol, 4, hipMemcpyDeviceToHost));
+    if (n > 0)
+    {
+        OCHIP_HIP(ctx, hipMemcpy(x_out, S.y, (size_t)n * 8, hipMemcpyDeviceToHost));
+        OCHIP_HIP(ctx, hipMemcpy(y_out, y_dev, (size_t)n * 8, hipMemcpyDeviceToHost));
+        std::vector<double> tiles;
+        if (L_out || W_out)
+            tiles.resize((size_t)S.chol_n_tiles * NB * NB);
+        if (L_out)
+        {
+            OCHIP_HIP(ctx, hipMemcpy(tiles.data(), S.Wm, S.matrix_bytes(), hipMemcpyDeviceToHost));
+            lm_unpack_lower(S, tiles, L_out, n);
+        }
+        if (W_out)
+        {
+            OCHIP_HIP(ctx, hipMemcpy(tiles.data(), w_built, S.matrix_bytes(), hipMemcpyDeviceToHost));
+            lm_unpack_lower(S, tiles, W_out, n + 1);
+        }
+    }
+    if (scal1_out)
+        *scal1_out = scal[1];
+    info_out[0] = fail;
+    info_out[1] = S.chol_order;
+    info_out[2] = S.chol_slots;
+    info_out[3] = S.chol_n_tiles;
+    info_out[4] = S.chol_n_claims;
+    info_out[5] = S.n_regions;
+    info_out[6] = n > 0 ? sa.back : 0;
+    info_out[7] = 0;
+    return OCHIP_OK;
+}

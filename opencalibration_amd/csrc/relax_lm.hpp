@@ -108,6 +108,8 @@ struct lm_system
     unsigned int *chol_sync = nullptr;  // [0] claim counter, [4 + tile] done flags; zeroed before every factorisation
     int chol_n_tiles = 0, chol_nbc = 0, chol_nbr = 0, chol_tb = 0, chol_grid = 0;
     int chol_n_claims = 0; // entries of chol_tiles (a fused pair of tiles is one entry)
+    int chol_order = 0;    // claim order the plan chose: LM_ORDER_COLUMNS, LM_ORDER_TAIL_FIRST or LM_ORDER_REGIONS
+    int chol_slots = 0;    // workgroups of chol_tiles_kernel the device holds at once (what the choice was made against)
     size_t chol_sync_bytes = 0;
     // regions of the band (lm_envelope::region_begin): block bounds [n_regions + 1] (the last one = chol_tb), and the
     // backward substitution's private work vectors, [n_regions][n] + [n_regions] partial sums
@@ -315,6 +317,38 @@ struct lm_model
 };
 
 int lm_solve(lm_system &sys, lm_model &model, const ochip_relax_options *opt, ochip_relax_summary *sum);
+
+// ---- the linear algebra of one LM step, shared by lm_solve and the test seam ochip_debug_lm_step ------------------------
+enum
+{
+    LM_ORDER_COLUMNS = 0,    // plain column order: a claimed tile only waits for tiles claimed before it
+    LM_ORDER_TAIL_FIRST = 1, // the dense tail's tiles first (a small tail: tail tiles * 8 <= slots)
+    LM_ORDER_REGIONS = 2,    // the band's regions side by side, then the tail
+};
+enum
+{
+    LM_ROUTE_TILES = 0, // chol_tiles_kernel: the whole factorisation in one launch
+    LM_ROUTE_CHAIN = 1, // chol_diag / chol_panel / chol_update_mfma, three launches per block column
+};
+enum
+{
+    LM_BACK_SINGLE = 1,      // back_solve_kernel: one workgroup walks the row envelope
+    LM_BACK_REGIONS_LDS = 2, // back_solve_regions_kernel, one workgroup per region, x in LDS where it fits
+    LM_BACK_REGIONS_HBM = 3, // the same with x in HBM
+};
+struct lm_step_args
+{
+    int route = LM_ROUTE_TILES;
+    int back = LM_BACK_REGIONS_LDS;
+    bool verify = false;       // tiles only: factor a copy with the launch chain as well and compare the forward solves
+    lm_model *model = nullptr; // its Schur term is subtracted from W; a speculating model may take over the back-solve
+    double *w_built = nullptr; // device, matrix_bytes(): receives W as built, before it is factored
+};
+// the back-solve lm_solve runs on this system (x_global: the back_solve_x_global test hook)
+int lm_back_default(const lm_system &sys, bool x_global);
+// Enqueue build, factorisation and back-solve on the context's stream: x into sys.y, the model cost change into scal[1],
+// the failure flag into sys.fail_chol.  *candidate_launched: the model's back-solve ran and launched its candidate step.
+int lm_linear_step(lm_system &sys, double radius, const lm_step_args &args, bool *candidate_launched);
 
 // enqueue lm_diag_kernel on the system's CURRENT set: scal[4] = max |g|, diagonal = clamp(diag(A) scale^2) when scale is not
 // nullptr, scal[0, 8) and the factorisation's flag mailed to the host block (engines that evaluate a candidate with its
