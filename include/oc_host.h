@@ -435,6 +435,31 @@ extern "C"
                                double *pixel2, double *J4);
     void och_ortho_sample_fields(double pixel_x, double pixel_y, int32_t width, int32_t height, float camera_distance,
                                  double cos_view, float *out5);
+    /* ---- blended full-resolution orthomosaic (opencalibration_amd/csrc/host/ortho_blend.cpp; src/ortho/ortho.cpp:
+     * 1665-1990, src/ortho/blending.cpp) ------------------------------------------------------------------------------------
+     * och_ortho_blend_render: rows [row0, row0 + rows) of plan8 (och_dsm_plan's plan) blended from the layers of
+     * och_ortho_layers_render (bgra, ids: [L][rows][width]) and the DSM band dsm [rows][width]; config4 = {num_layers
+     * 1..8, tile_size 1..4096, pyramid_levels, blend_transition_radius >= 1}.  The colour balance: per node id color_ids[i]
+     * color6[i] = lab_offset 3, brdf, slope 2; per model id vig3[i] = 3 vignetting coefficients, of which only model id
+     * 0's are used.  ctx == NULL: the CPU route (one thread per tile, host memory); else
+     * ochip_ortho_blend on ctx's device (on_device: bgra / ids / dsm / rgba are device pointers).  rgba [rows][width][4];
+     * debug outputs as ochip_ortho_blend's, host, each may be NULL.  -1 + och_ortho_blend_last_error() on failure.
+     * och_laplacian_blend: laplacianBlend on the CPU route (ochip_laplacian_blend's arguments); -1 on a bad argument.
+     * och_blend_chamfer: the sequential two-pass chamfer of a rows x cols mask (non-zero: boundary) in 1e-4 units.
+     * och_blend_pyr: pyrDown (up 0; w x h -> W x H = ((w + 1) / 2, (h + 1) / 2)) or pyrUp (up 1; to W x H) of 1 or 3
+     * interleaved float channels.  och_blend_math: mode 0 exp_restated (n floats), 1 the falloff (n pairs steepness, d),
+     * 2 float Lab -> BGR8 (n triples). */
+    int och_ortho_blend_render(const och_graph *g, ochip_ctx *ctx, const och_surface *const *surfaces, size_t n,
+                               const double *plan8, const int32_t *config4, int64_t row0, int64_t rows, size_t n_color,
+                               const uint64_t *color_ids, const double *color6, size_t n_models, const uint32_t *model_ids,
+                               const double *vig3, int on_device, const uint8_t *bgra, const uint64_t *ids, const float *dsm,
+                               uint8_t *rgba, float *weight_out, float *dist_out, float *lab_out);
+    const char *och_ortho_blend_last_error(void);
+    int och_laplacian_blend(int32_t num_layers, int32_t rows, int32_t cols, int32_t pyramid_levels, const float *lab,
+                            const float *weight, uint8_t *bgra_out);
+    void och_blend_chamfer(int32_t rows, int32_t cols, const uint8_t *boundary, int32_t *dist);
+    void och_blend_pyr(int up, int32_t channels, int32_t w, int32_t h, int32_t W, int32_t H, const float *src, float *out);
+    void och_blend_math(int mode, size_t n, const float *in, void *out);
 
 #ifdef __cplusplus
 }

@@ -751,6 +751,35 @@ extern "C"
                            uint64_t *id_out, float *weight_out, ochip_color_corr *corr_out, uint64_t corr_capacity,
                            uint64_t *n_corr, uint32_t *knn_out);
 
+    /* ---- blended full-resolution orthomosaic (src/ortho/ortho.cpp:1665-1990, src/ortho/blending.cpp;
+     * opencalibration_amd/csrc/ortho_blend.hpp) ----
+     * One node id the layers may name, the table sorted by id, ids unique: cam, its row in cams (0xFFFFFFFF: none, the
+     * sample keeps black and weight 0), and its colour balance (has_color 0: no entry, no correction).  64 bytes. */
+    typedef struct ochip_blend_id
+    {
+        uint64_t id;
+        uint32_t cam, has_color;
+        double lab_offset[3], brdf, slope[2];
+    } ochip_blend_id;
+    /* Rows [row0, row0 + rows) of the blended orthomosaic `cols` wide, whole tile rows from a tile row (the raster's last
+     * may be partial); raster3 = {min_x, max_y, gsd}; config4 = {num_layers (1..8), tile_size (1..4096), pyramid_levels,
+     * blend_transition_radius (>= 1)}.  Inputs as ochip_ortho_layers writes them: bgra [L][rows][cols][4] (valid: alpha
+     * > 0), id [L][rows][cols], and the DSM band dsm [rows][cols]; cams [n_cams][28] as ochip_ortho_layers'.  vig0: the
+     * vignetting coefficients of model id 0 (NULL: no entry), which every sample uses.  rgba_out [rows][cols][4].
+     * bgra, id, dsm and rgba_out are device pointers of this context's GPU when on_device, else host.  Debug outputs
+     * (host, each may be NULL): weight_out [L][rows][cols] the recomputed weight before the falloff, dist_out
+     * [rows][cols] the boundary distance (+inf: no boundary in the tile), lab_out [L][rows][cols][3] the corrected Lab. */
+    int ochip_ortho_blend(ochip_ctx *ctx, const double *raster3, int32_t cols, int64_t row0, int64_t rows,
+                          const int32_t *config4, uint32_t n_cams, const double *cams, uint32_t n_ids,
+                          const ochip_blend_id *ids, const double *vig0, int on_device, const uint8_t *bgra,
+                          const uint64_t *id, const float *dsm, uint8_t *rgba_out, float *weight_out, float *dist_out,
+                          float *lab_out);
+    /* laplacianBlend (src/ortho/blending.cpp) alone on one rows x cols tile (each at most 4096) on the device, the steps
+     * of ochip_ortho_blend: lab [L][rows][cols][3] float Lab, weight [L][rows][cols], host; bgra_out [rows][cols][4]
+     * host, alpha 255. */
+    int ochip_laplacian_blend(ochip_ctx *ctx, int32_t num_layers, int32_t rows, int32_t cols, int32_t pyramid_levels,
+                              const float *lab, const float *weight, uint8_t *bgra_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -36,6 +36,7 @@ EXPORTS = [
     "ochip_rccl_unique_id", "ochip_rccl_comm_create", "ochip_rccl_comm_destroy", "ochip_rccl_comm_stats",
     "ochip_rccl_relax_exchange",
     "ochip_ortho_mesh_create", "ochip_ortho_mesh_destroy", "ochip_ortho_dsm", "ochip_ortho_thumbnail", "ochip_ortho_layers",
+    "ochip_ortho_blend", "ochip_laplacian_blend",
 ]
 
 _lib = None
@@ -104,6 +105,7 @@ def load():
         L.ochip_synth_views_read.argtypes = [vp, vp, u32, i32, i32, vp]
         L.ochip_ortho_mesh_destroy.argtypes = [vp]
         L.ochip_ortho_mesh_destroy.restype = None
+        L.ochip_laplacian_blend.argtypes = [vp, i32, i32, i32, i32, vp, vp, vp]
         _lib = L
     return _lib
 

@@ -246,6 +246,16 @@ def load():
         L.och_ortho_patch_sample.argtypes = [vp, vp, f64, vp, vp, vp, vp]
         L.och_ortho_sample_fields.argtypes = [f64, f64, i32, i32, C.c_float, f64, vp]
         L.och_ortho_sample_fields.restype = None
+        L.och_ortho_blend_render.argtypes = [vp, vp, vp, sz, _f64p, vp, i64, i64, sz, vp, vp, sz, vp, vp, C.c_int, vp, vp, vp,
+                                             vp, vp, vp, vp]
+        L.och_ortho_blend_last_error.restype = C.c_char_p
+        L.och_laplacian_blend.argtypes = [i32, i32, i32, i32, vp, vp, vp]
+        L.och_blend_chamfer.argtypes = [i32, i32, vp, vp]
+        L.och_blend_chamfer.restype = None
+        L.och_blend_pyr.argtypes = [C.c_int, i32, i32, i32, i32, i32, vp, vp]
+        L.och_blend_pyr.restype = None
+        L.och_blend_math.argtypes = [C.c_int, sz, vp, vp]
+        L.och_blend_math.restype = None
         _lib = L
     return _lib
 
@@ -777,6 +787,176 @@ def lab_convert(values, mode):
     m = {"bgr2lab8": 0, "lab82bgr": 1, "bgr2labf": 2}[mode]
     out = np.zeros(v.shape, np.float32 if m == 2 else np.uint8)
     load().och_lab_convert(m, v.ctypes.data, len(v), out.ctypes.data)
+    return out
+
+
+# ---- blended full-resolution orthomosaic (include/oc_host.h; src/ortho/ortho.cpp:1665-1990) ---------------------------
+# OrthoMosaicConfig's defaults for the blend (include/opencalibration/ortho/ortho.hpp)
+BLEND_CONFIG = dict(pyramid_levels=4, blend_transition_radius=64, tile_size=1024)
+
+
+def _blend_config(config, num_layers):
+    cfg = dict(BLEND_CONFIG, **(config or {}))
+    unknown = set(cfg) - set(BLEND_CONFIG) - set(LAYERS_CONFIG)
+    if unknown:
+        raise ValueError(f"unknown blend settings {sorted(unknown)}")
+    return cfg, np.array([num_layers, cfg["tile_size"], cfg["pyramid_levels"], cfg["blend_transition_radius"]], np.int32)
+
+
+def _color_tables(color_balance):
+    """ColorBalanceResult as the C tables: per_image {node id: dict(lab_offset (3), brdf, slope (2))}, per_model
+    {model id: (3 vignetting coefficients)}."""
+    cb = color_balance or {}
+    per_image, per_model = cb.get("per_image", {}), cb.get("per_model", {})
+    ids = np.array(sorted(per_image), np.uint64)
+    six = np.array([[*per_image[int(i)]["lab_offset"], per_image[int(i)]["brdf"], *per_image[int(i)]["slope"]]
+                    for i in ids], np.float64).reshape(-1, 6)
+    mids = np.array(sorted(per_model), np.uint32)
+    vig = np.array([per_model[int(m)] for m in mids], np.float64).reshape(-1, 3)
+    return ids, six, mids, vig
+
+
+def _device_ptr(t, dtype, shape, what, device):
+    if tuple(t.shape) != tuple(shape) or str(t.dtype) != dtype or not t.is_cuda or not t.is_contiguous() or \
+            t.device.index != device:
+        raise ValueError(f"{what} must be a contiguous {dtype} tensor of {tuple(shape)} on device {device}")
+    return t.data_ptr()
+
+
+def ortho_blend(plan, graph, surfaces, layers, dsm, color_balance=None, ctx=None, config=None, out=None, debug=False):
+    """blendLayeredGeoTIFF's pass (src/ortho/ortho.cpp:1665-1990) over one band of `layers` (ortho_layers' result:
+    bgra (L, rows, width, 4), camera_id (L, rows, width), row0) with the DSM band `dsm` (rows x width float32).
+    color_balance: dict(per_image={node id: dict(lab_offset, brdf, slope)}, per_model={model id: 3 coefficients}); None:
+    no correction.  ctx (a capi.Context): on its device, where the layers, dsm and `out` may be CUDA tensors; None: the
+    CPU route (numpy).  config overrides BLEND_CONFIG.  Returns rgba (rows, width, 4) uint8 (`out` when given), with
+    debug (weight (L, rows, width) before the falloff, dist (rows, width), lab (L, rows, width, 3)) as (rgba, dict)."""
+    L = load()
+    bgra, ids = layers["bgra"], layers["camera_id"]
+    nl, rows, w = int(bgra.shape[0]), int(bgra.shape[1]), int(bgra.shape[2])
+    cfg, config4 = _blend_config(config, nl)
+    row0 = int(layers.get("row0", 0))
+    arr, n = _surface_array(surfaces)
+    on_device = not isinstance(bgra, np.ndarray)
+    if on_device:
+        if ctx is None:
+            raise ValueError("device layers need the device route (ctx)")
+        import torch
+
+        dev = ctx.device
+        p_bgra = _device_ptr(bgra, "torch.uint8", (nl, rows, w, 4), "layers['bgra']", dev)
+        p_ids = _device_ptr(ids, "torch.int64", (nl, rows, w), "layers['camera_id']", dev)
+        p_dsm = _device_ptr(dsm, "torch.float32", (rows, w), "dsm", dev)
+        if out is None:
+            out = torch.empty((rows, w, 4), dtype=torch.uint8, device=f"cuda:{dev}")
+        p_out = _device_ptr(out, "torch.uint8", (rows, w, 4), "out", dev)
+        # the kernels run on the context's own stream: torch's queued work on these tensors finishes first
+        torch.cuda.current_stream(out.device).synchronize()
+    else:
+        bgra = np.ascontiguousarray(bgra, np.uint8)
+        ids = np.ascontiguousarray(ids).view(np.uint64) if np.asarray(ids).dtype.itemsize == 8 else None
+        if ids is None or bgra.shape != (nl, rows, w, 4) or ids.shape != (nl, rows, w):
+            raise ValueError("layers must hold bgra (L, rows, width, 4) and 64-bit camera_id (L, rows, width)")
+        dsm = np.ascontiguousarray(dsm, np.float32)
+        if dsm.shape != (rows, w):
+            raise ValueError(f"dsm must be {rows} x {w}")
+        out = np.zeros((rows, w, 4), np.uint8) if out is None else out
+        if out.shape != (rows, w, 4) or out.dtype != np.uint8 or not out.flags.c_contiguous:
+            raise ValueError(f"out must be a contiguous uint8 array of {rows} x {w} x 4")
+        p_bgra, p_ids, p_dsm, p_out = bgra.ctypes.data, ids.ctypes.data, dsm.ctypes.data, out.ctypes.data
+    cids, six, mids, vig = _color_tables(color_balance)
+    dbg = dict(weight=np.zeros((nl, rows, w), np.float32), dist=np.zeros((rows, w), np.float32),
+               lab=np.zeros((nl, rows, w, 3), np.float32)) if debug else None
+    rc = L.och_ortho_blend_render(graph.h, ctx.h if ctx is not None else None, arr, n, _plan_array(plan), config4.ctypes.data,
+                                  row0, rows, len(cids), cids.ctypes.data if len(cids) else None,
+                                  six.ctypes.data if len(cids) else None, len(mids), mids.ctypes.data if len(mids) else None,
+                                  vig.ctypes.data if len(mids) else None, int(on_device), p_bgra, p_ids, p_dsm, p_out,
+                                  *(None if dbg is None else dbg[k].ctypes.data for k in ("weight", "dist", "lab")))
+    if rc != 0:
+        raise capi.OchipError(L.och_ortho_blend_last_error().decode())
+    return (out, dbg) if debug else out
+
+
+def laplacian_blend(lab_layers, weights, pyramid_levels=4, ctx=None):
+    """laplacianBlend (src/ortho/blending.cpp) of float Lab layers (L, rows, cols, 3) with weights (L, rows, cols): BGRA
+    (rows, cols, 4) uint8, alpha 255.  ctx: on its device (ochip_laplacian_blend); None: the CPU route."""
+    lab = np.ascontiguousarray(lab_layers, np.float32)
+    wt = np.ascontiguousarray(weights, np.float32)
+    if lab.ndim != 4 or lab.shape[3] != 3 or wt.shape != lab.shape[:3]:
+        raise ValueError("lab_layers (L, rows, cols, 3) and weights (L, rows, cols)")
+    nl, rows, cols = wt.shape
+    out = np.zeros((rows, cols, 4), np.uint8)
+    if nl == 0:
+        return np.zeros((0, 0, 4), np.uint8)  # laplacianBlend of no layers: an empty Mat
+    if ctx is not None:
+        ctx._check(capi.load().ochip_laplacian_blend(ctx.h, nl, rows, cols, int(pyramid_levels), lab.ctypes.data,
+                                                     wt.ctypes.data, out.ctypes.data), "ochip_laplacian_blend")
+    elif load().och_laplacian_blend(nl, rows, cols, int(pyramid_levels), lab.ctypes.data, wt.ctypes.data, out.ctypes.data):
+        raise ValueError("laplacian_blend: 1..8 layers of at most 4096 x 4096")
+    return out
+
+
+def ortho_mosaic(plan, graph, surfaces, images, mesh=None, config=None, color_balance=None, tile_rows=1, out=None):
+    """The blended full-resolution orthomosaic of `plan` (dsm_plan), band by band of tile_rows output tile rows: DSM ->
+    layers (ortho_layers) -> blend (ortho_blend).  mesh (an OrthoMesh): every step on its device, images as CUDA tensors,
+    into `out` (a (height, width, 4) uint8 CUDA tensor, made when None); None: the CPU route, numpy images, into a host
+    array.  config: LAYERS_CONFIG's and BLEND_CONFIG's keys."""
+    cfg = {**LAYERS_CONFIG, **BLEND_CONFIG, **(config or {})}
+    lcfg = {k: cfg[k] for k in LAYERS_CONFIG}
+    bcfg = {k: cfg[k] for k in BLEND_CONFIG}
+    h, w, t, nl = plan["height"], plan["width"], cfg["tile_size"], cfg["num_layers"]
+    if mesh is None:
+        out = np.zeros((h, w, 4), np.uint8) if out is None else out
+    else:
+        import torch
+
+        dev = f"cuda:{mesh.ctx.device}"
+        out = torch.empty((h, w, 4), dtype=torch.uint8, device=dev) if out is None else out
+    for row0 in range(0, h, tile_rows * t):
+        rows = min(tile_rows * t, h - row0)
+        if mesh is None:
+            dsm = dsm_render(plan, surfaces, row0=row0, rows=rows)
+            layers = ortho_layers(plan, graph, surfaces, images, row0=row0, tile_rows=tile_rows, config=lcfg, dsm=dsm)
+            ortho_blend(plan, graph, surfaces, layers, dsm, color_balance, config=bcfg, out=out[row0:row0 + rows])
+        else:
+            dsm = torch.empty((rows, w), dtype=torch.float32, device=dev)
+            dsm_render(plan, surfaces, mesh=mesh, row0=row0, rows=rows, out=dsm)
+            lay = dict(bgra=torch.empty((nl, rows, w, 4), dtype=torch.uint8, device=dev),
+                       camera_id=torch.empty((nl, rows, w), dtype=torch.int64, device=dev))
+            layers = ortho_layers(plan, graph, surfaces, images, mesh=mesh, row0=row0, tile_rows=tile_rows, config=lcfg,
+                                  out=lay)
+            layers["bgra"], layers["camera_id"] = lay["bgra"], lay["camera_id"]
+            ortho_blend(plan, graph, surfaces, layers, dsm, color_balance, ctx=mesh.ctx, config=bcfg, out=out[row0:row0 + rows])
+    return out
+
+
+def blend_chamfer(boundary):
+    """The sequential two-pass 3 x 3 chamfer of a boundary mask, int32 in 1e-4 units."""
+    m = np.ascontiguousarray(boundary, np.uint8)
+    d = np.zeros(m.shape, np.int32)
+    load().och_blend_chamfer(m.shape[0], m.shape[1], m.ctypes.data, d.ctypes.data)
+    return d
+
+
+def blend_pyr(image, up=False, size=None):
+    """pyrDown (to ((w + 1) / 2, (h + 1) / 2)) or pyrUp (to size = (H, W)) of a float32 (h, w) or (h, w, 3) image as the
+    blend defines them."""
+    src = np.ascontiguousarray(image, np.float32)
+    h, w = src.shape[:2]
+    ch = 1 if src.ndim == 2 else src.shape[2]
+    H, W = size if up else ((h + 1) // 2, (w + 1) // 2)
+    out = np.zeros((H, W) + src.shape[2:], np.float32)
+    load().och_blend_pyr(int(up), ch, w, h, W, H, src.ctypes.data, out.ctypes.data)
+    return out
+
+
+def blend_math(values, mode):
+    """The blend's restated functions: mode "exp" (float32 -> float32), "falloff" (N x 2 (steepness, d) -> float32) or
+    "lab2bgr8" (N x 3 float Lab -> uint8 BGR)."""
+    m = {"exp": 0, "falloff": 1, "lab2bgr8": 2}[mode]
+    v = np.ascontiguousarray(values, np.float32)
+    n = v.size if m == 0 else v.size // (2 if m == 1 else 3)
+    out = np.zeros((n, 3), np.uint8) if m == 2 else np.zeros(n, np.float32)
+    load().och_blend_math(m, n, v.ctypes.data, out.ctypes.data)
     return out
 
 
