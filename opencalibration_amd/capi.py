@@ -57,6 +57,47 @@ class RelaxgDesc(C.Structure):
                 ("n_rel", C.c_uint32), ("rel_cam", C.c_void_p), ("rel_pose", C.c_void_p), ("rel_huber_a", C.c_double)]
 
 
+def relaxg_desc(scene):
+    """(RelaxgDesc, arrays it points into) of a scene dict holding the ochip_relaxg_desc fields by name: cam_pos, cam_q,
+    cam_optimize, vert_xy, vert_z, vert_optimize, blk_n, blk_ray_off, blk_tri, ray_cam, ray_dir, down_cam, down_weight,
+    diff_v, diff_weight, anchor_weight, huber_a, model; optional blk_intr, ray_px, smooth_v, smooth_weight, opt_focal,
+    opt_principal, n_radial_free, focal_lo, focal_hi, mono_observations, mono_r_max, rel_cam, rel_pose, rel_huber_a (absent:
+    none / zero)."""
+    d = RelaxgDesc()
+    keep = []
+
+    def arr(name, dtype):
+        if scene.get(name) is None:
+            return None
+        a = np.ascontiguousarray(scene[name], dtype)
+        keep.append(a)
+        return a.ctypes.data
+
+    d.n_cams = len(scene["cam_pos"])
+    d.cam_pos, d.cam_q, d.cam_optimize = arr("cam_pos", np.float64), arr("cam_q", np.float64), arr("cam_optimize", np.uint8)
+    d.n_verts = len(scene["vert_z"])
+    d.vert_xy, d.vert_z, d.vert_optimize = arr("vert_xy", np.float64), arr("vert_z", np.float64), arr("vert_optimize", np.uint8)
+    d.n_blocks = len(scene["blk_n"])
+    d.blk_n, d.blk_ray_off, d.blk_tri = arr("blk_n", np.uint8), arr("blk_ray_off", np.uint32), arr("blk_tri", np.uint32)
+    d.blk_intr, d.ray_px = arr("blk_intr", np.uint8), arr("ray_px", np.float64)
+    d.ray_cam, d.ray_dir = arr("ray_cam", np.uint32), arr("ray_dir", np.float64)
+    d.n_down, d.down_cam, d.down_weight = len(scene["down_cam"]), arr("down_cam", np.uint32), scene["down_weight"]
+    d.n_diff, d.diff_v, d.diff_weight = np.size(scene["diff_v"]) // 2, arr("diff_v", np.uint32), scene["diff_weight"]
+    d.anchor_weight, d.huber_a = scene["anchor_weight"], scene["huber_a"]
+    if scene.get("smooth_v") is not None:
+        d.n_smooth, d.smooth_v, d.smooth_weight = np.size(scene["smooth_v"]) // 4, arr("smooth_v", np.uint32), scene["smooth_weight"]
+    for i, v in enumerate(scene["model"]):
+        d.model[i] = v
+    d.opt_focal, d.opt_principal = int(scene.get("opt_focal", 0)), int(scene.get("opt_principal", 0))
+    d.n_radial_free = int(scene.get("n_radial_free", 0))
+    d.focal_lo, d.focal_hi = scene.get("focal_lo", 100.0), scene.get("focal_hi", 20000.0)
+    d.mono_observations, d.mono_r_max = int(scene.get("mono_observations", 0)), scene.get("mono_r_max", 0.0)
+    if scene.get("rel_cam") is not None:
+        d.n_rel, d.rel_cam, d.rel_pose = np.size(scene["rel_cam"]) // 2, arr("rel_cam", np.uint32), arr("rel_pose", np.float64)
+        d.rel_huber_a = scene["rel_huber_a"]
+    return d, keep
+
+
 class OchipError(RuntimeError):
     pass
 
@@ -359,31 +400,11 @@ class Context:
         return dict(x=x[:n], y=y[:n], L=L, W=W, scal1=s1.value, fail=int(info[0]), order=int(info[1]), slots=int(info[2]),
                     tiles=int(info[3]), claims=int(info[4]), regions=int(info[5]), back=int(info[6]))
 
-    def relaxg_evaluate(self, scene):
+    def relaxg_evaluate(self, scene, structure_only=False):
         """One evaluation of a general-engine relax problem (ochip_relaxg_problem_create, ochip_relaxg_evaluate, destroy):
         (cost, dense J'J, J'r, first unknown per camera / vertex / f / pp / k).  scene: dict of the ochip_relaxg_desc fields
-        (cameras, vertices, 2-ray blocks without intrinsics, priors); what it leaves out is zero."""
-        d = RelaxgDesc()
-        keep = []
-
-        def arr(name, dtype):
-            a = np.ascontiguousarray(scene[name], dtype)
-            keep.append(a)
-            return a.ctypes.data
-
-        d.n_cams = len(scene["cam_pos"])
-        d.cam_pos, d.cam_q, d.cam_optimize = arr("cam_pos", np.float64), arr("cam_q", np.float64), arr("cam_optimize", np.uint8)
-        d.n_verts = len(scene["vert_z"])
-        d.vert_xy, d.vert_z, d.vert_optimize = arr("vert_xy", np.float64), arr("vert_z", np.float64), arr("vert_optimize", np.uint8)
-        d.n_blocks = len(scene["blk_n"])
-        d.blk_n, d.blk_ray_off, d.blk_tri = arr("blk_n", np.uint8), arr("blk_ray_off", np.uint32), arr("blk_tri", np.uint32)
-        d.ray_cam, d.ray_dir = arr("ray_cam", np.uint32), arr("ray_dir", np.float64)
-        d.n_down, d.down_cam, d.down_weight = len(scene["down_cam"]), arr("down_cam", np.uint32), scene["down_weight"]
-        d.n_diff, d.diff_v, d.diff_weight = np.size(scene["diff_v"]) // 2, arr("diff_v", np.uint32), scene["diff_weight"]
-        d.anchor_weight, d.huber_a = scene["anchor_weight"], scene["huber_a"]
-        for i, v in enumerate(scene["model"]):
-            d.model[i] = v
-        d.focal_lo, d.focal_hi = 100.0, 20000.0
+        (relaxg_desc).  An evaluation that reports non-finite blocks raises OchipError."""
+        d, keep = relaxg_desc(scene)
         p = C.c_void_p()
         self.L.ochip_relaxg_problem_create.argtypes = [C.c_void_p, C.POINTER(RelaxgDesc), C.POINTER(C.c_void_p)]
         self.L.ochip_relaxg_problem_destroy.argtypes = [C.c_void_p]
@@ -392,6 +413,9 @@ class Context:
                                                  C.c_void_p]
         self._check(self.L.ochip_relaxg_problem_create(self.h, C.byref(d), C.byref(p)), "ochip_relaxg_problem_create")
         try:
+            if structure_only:
+                self.L.ochip_relaxg_set_structure_only.argtypes = [C.c_void_p, C.c_int]
+                self._check(self.L.ochip_relaxg_set_structure_only(p, 1), "ochip_relaxg_set_structure_only")
             cost, n = C.c_double(), C.c_int()
             order = np.zeros(d.n_cams + d.n_verts + 3, np.int32)
             rc = self.L.ochip_relaxg_evaluate(p, C.byref(cost), C.byref(n), None, None, order.ctypes.data)

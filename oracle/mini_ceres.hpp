@@ -15,7 +15,9 @@
 
 #include <array>
 #include <cmath>
+#include <algorithm>
 #include <functional>
+#include <limits>
 #include <memory>
 #include <string>
 #include <unordered_map>
@@ -83,6 +85,77 @@ template <typename Functor, int kNumResiduals, int... Ns> struct AutoDiffCostFun
     }
 };
 
+// HuberLoss::Evaluate (ceres/loss_function.cc) on a scalar S: rho = (rho(s), rho'(s), rho''(s)) for scale a, b = a * a
+template <typename S> inline void huber_rho(S a, S b, S s, S rho[3])
+{
+    if (s > b)
+    {
+        using std::sqrt;
+        const S r = sqrt(s);
+        rho[0] = S(2.0) * a * r - b;
+        rho[1] = std::max(S(std::numeric_limits<double>::min()), a / r);
+        rho[2] = -rho[1] / (S(2.0) * s);
+    }
+    else
+    {
+        rho[0] = s;
+        rho[1] = S(1.0);
+        rho[2] = S(0.0);
+    }
+}
+
+// Corrector (ceres/corrector.cc) of a block with squared residual norm sq: J -> sqrt_rho1 * (J - alpha_sq_norm * r r'J),
+// r -> residual_scaling * r
+template <typename S> inline void corrector_terms(S sq, const S rho[3], S *sqrt_rho1, S *residual_scaling, S *alpha_sq_norm)
+{
+    using std::sqrt;
+    *sqrt_rho1 = sqrt(rho[1]);
+    if (sq == S(0.0) || rho[2] <= S(0.0))
+    {
+        *residual_scaling = *sqrt_rho1;
+        *alpha_sq_norm = S(0.0);
+    }
+    else
+    {
+        const S D = S(1.0) + S(2.0) * sq * rho[2] / rho[1];
+        const S alpha = S(1.0) - sqrt(D);
+        *residual_scaling = *sqrt_rho1 / (S(1) - alpha);
+        *alpha_sq_norm = alpha / sq;
+    }
+}
+
+// EigenQuaternionManifold (ceres/manifold.cc, Order XYZW) on a scalar S: plus = q_delta * x with
+// q_delta = (sin|d|/|d| d, cos|d|), and its Jacobian at delta = 0 (4 x 3, row-major)
+template <typename S> inline void quat_plus_t(const S *x, const S *delta, S *out)
+{
+    using std::cos;
+    using std::sin;
+    using std::sqrt;
+    const S n2 = delta[0] * delta[0] + delta[1] * delta[1] + delta[2] * delta[2];
+    const S n = sqrt(n2);
+    if (n == S(0.0))
+    {
+        for (int i = 0; i < 4; i++)
+            out[i] = x[i];
+        return;
+    }
+    const S s = sin(n) / n;
+    const S dx = s * delta[0], dy = s * delta[1], dz = s * delta[2], dw = cos(n);
+    const S qx = x[0], qy = x[1], qz = x[2], qw = x[3];
+    // Eigen quaternion product (a = q_delta, b = x)
+    out[3] = dw * qw - dx * qx - dy * qy - dz * qz;
+    out[0] = dw * qx + dx * qw + dy * qz - dz * qy;
+    out[1] = dw * qy + dy * qw + dz * qx - dx * qz;
+    out[2] = dw * qz + dz * qw + dx * qy - dy * qx;
+}
+template <typename S> inline void quat_plus_jacobian_t(const S *x, S *J)
+{
+    const S qx = x[0], qy = x[1], qz = x[2], qw = x[3];
+    const S v[12] = {qw, qz, -qy, -qz, qw, qx, qy, -qx, qw, -qx, -qy, -qz};
+    for (int i = 0; i < 12; i++)
+        J[i] = v[i];
+}
+
 struct LossFunction
 {
     virtual ~LossFunction() = default;
@@ -96,19 +169,7 @@ struct HuberLoss : LossFunction // ceres/loss_function.cc
     }
     void Evaluate(double s, double rho[3]) const override
     {
-        if (s > b)
-        {
-            const double r = std::sqrt(s);
-            rho[0] = 2.0 * a * r - b;
-            rho[1] = std::max(std::numeric_limits<double>::min(), a / r);
-            rho[2] = -rho[1] / (2.0 * s);
-        }
-        else
-        {
-            rho[0] = s;
-            rho[1] = 1.0;
-            rho[2] = 0.0;
-        }
+        huber_rho<double>(a, b, s, rho);
     }
 };
 

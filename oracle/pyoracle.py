@@ -767,3 +767,59 @@ class RxMesh:
 
     def refine_at_point(self, x, y, levels=1):
         return self.L.ocx_rmesh_refine_at_point(self.h, x, y, levels)
+
+
+# ---- one evaluation of the general relax engine's problem (oracle/relax_eval.cpp) ----------------------------------------
+MUT_NONE, MUT_PARTIAL, MUT_NO_CORR_J, MUT_DROP = 0, 1, 2, 3
+
+
+def _relaxg_fns():
+    L = lib()
+    if not getattr(L, "_relaxg_ready", False):
+        vp = C.c_void_p
+        L.oc_relaxg_eval.restype = C.c_int
+        L.oc_relaxg_eval.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+        L.oc_relaxg_fd.restype = C.c_int
+        L.oc_relaxg_fd.argtypes = [vp, C.c_int, C.c_double, vp]
+        L._relaxg_ready = True
+    return L
+
+
+def relaxg_eval(scene, precision=1, raw=False, mutate=MUT_NONE, mutate_arg=-1, delta=None, structure_only=False):
+    """The general engine's problem (a scene dict of ochip_relaxg_desc fields, opencalibration_amd.capi.relaxg_desc) evaluated
+    the way the reference's Problem evaluates it, in long double (precision=1) or double (0).  dict: fail (a block did not
+    evaluate to finite values), n, cost, JtJ (n x n), Jtr, J (rows x n, corrected), r (corrected), row_blk (block of each
+    row), touch (rows x n: 1 where a row structurally depends on a column) and order (n_cams + n_verts + 3: the first
+    canonical column of every camera / vertex / f / pp / k, or -1).  raw: no loss and no corrector.  delta: the state
+    moved by x [+] delta over the canonical unknowns first."""
+    from opencalibration_amd import capi
+
+    L = _relaxg_fns()
+    d, keep = capi.relaxg_desc(scene)
+    n, rows = C.c_int(), C.c_int()
+    dl = None if delta is None else np.ascontiguousarray(delta, np.float64)
+    args = (C.byref(d), int(structure_only), int(precision), int(raw), int(mutate), int(mutate_arg),
+            None if dl is None else dl.ctypes.data)
+    L.oc_relaxg_eval(*args, C.byref(n), C.byref(rows), *([None] * 8))
+    n, m = n.value, rows.value
+    order = np.zeros(d.n_cams + d.n_verts + 3, np.int32)
+    cost = C.c_double()
+    JtJ, Jtr, J, r = np.zeros((n, n)), np.zeros(n), np.zeros((m, n)), np.zeros(m)
+    row_blk, touch = np.zeros(m, np.int32), np.zeros((m, n), np.uint8)
+    fail = L.oc_relaxg_eval(*args, None, None, order.ctypes.data, C.byref(cost), JtJ.ctypes.data, Jtr.ctypes.data,
+                            J.ctypes.data, r.ctypes.data, row_blk.ctypes.data, touch.ctypes.data)
+    return dict(fail=bool(fail), n=n, cost=cost.value, JtJ=JtJ, Jtr=Jtr, J=J, r=r, row_blk=row_blk, touch=touch, order=order)
+
+
+def relaxg_fd(scene, step=1e-4, structure_only=False):
+    """Richardson-extrapolated central differences (long double) of the raw residuals of relaxg_eval over its canonical
+    unknowns: rows x n"""
+    from opencalibration_amd import capi
+
+    L = _relaxg_fns()
+    e = relaxg_eval(scene, raw=True, structure_only=structure_only)
+    d, keep = capi.relaxg_desc(scene)
+    out = np.zeros((len(e["r"]), e["n"]))
+    fail = L.oc_relaxg_fd(C.byref(d), int(structure_only), float(step), out.ctypes.data)
+    assert not fail
+    return out

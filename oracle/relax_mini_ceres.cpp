@@ -81,32 +81,13 @@ std::vector<double *> Problem::GetParameterBlocks() const
 namespace
 {
 
-// EigenQuaternionManifold (ceres/manifold.cc, Order XYZW): plus = q_delta * x, q_delta = (sin|d|/|d| d, cos|d|)
 void quat_plus(const double *x, const double *delta, double *out)
 {
-    const double n2 = delta[0] * delta[0] + delta[1] * delta[1] + delta[2] * delta[2];
-    const double n = std::sqrt(n2);
-    if (n == 0.0)
-    {
-        for (int i = 0; i < 4; i++)
-            out[i] = x[i];
-        return;
-    }
-    const double s = std::sin(n) / n;
-    const double dx = s * delta[0], dy = s * delta[1], dz = s * delta[2], dw = std::cos(n);
-    const double qx = x[0], qy = x[1], qz = x[2], qw = x[3];
-    // Eigen quaternion product (a = q_delta, b = x)
-    out[3] = dw * qw - dx * qx - dy * qy - dz * qz;
-    out[0] = dw * qx + dx * qw + dy * qz - dz * qy;
-    out[1] = dw * qy + dy * qw + dz * qx - dx * qz;
-    out[2] = dw * qz + dz * qw + dx * qy - dy * qx;
+    quat_plus_t<double>(x, delta, out);
 }
 void quat_plus_jacobian(const double *x, double *J /*4x3 row-major*/)
 {
-    const double qx = x[0], qy = x[1], qz = x[2], qw = x[3];
-    const double v[12] = {qw, qz, -qy, -qz, qw, qx, qy, -qx, qw, -qx, -qy, -qz};
-    for (int i = 0; i < 12; i++)
-        J[i] = v[i];
+    quat_plus_jacobian_t<double>(x, J);
 }
 
 struct Program
@@ -222,20 +203,8 @@ bool eval_block(const Program &prog, const ResidualBlock &rb, const std::vector<
     rb.loss->Evaluate(sq, rho);
     *cost = 0.5 * rho[0];
     // Corrector (ceres/corrector.cc)
-    const double sqrt_rho1 = std::sqrt(rho[1]);
-    double residual_scaling, alpha_sq_norm;
-    if (sq == 0.0 || rho[2] <= 0.0)
-    {
-        residual_scaling = sqrt_rho1;
-        alpha_sq_norm = 0.0;
-    }
-    else
-    {
-        const double D = 1.0 + 2.0 * sq * rho[2] / rho[1];
-        const double alpha = 1.0 - std::sqrt(D);
-        residual_scaling = sqrt_rho1 / (1 - alpha);
-        alpha_sq_norm = alpha / sq;
-    }
+    double sqrt_rho1, residual_scaling, alpha_sq_norm;
+    corrector_terms<double>(sq, rho, &sqrt_rho1, &residual_scaling, &alpha_sq_norm);
     if (want_jac)
     {
         if (alpha_sq_norm == 0.0)
