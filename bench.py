@@ -17,8 +17,19 @@ launcher did (under `python -m torch.distributed.run` its RANK / WORLD_SIZE are 
                     one RCCL exchange per evaluation)
 
 Prints ONE JSON line on rank 0.  `roofline` describes the dominant device kernel, timed with HIP events on
-the stream it is launched on; `cpu_baseline` is the CPU restatement (oracle/) timed on this box's usable host
-cores on a bounded sample of the same workload.
+the stream it is launched on.
+
+A plain run does only what the headline needs: set-up, warm-up, the timed steps, --dump-outputs and the line.  --full adds
+everything else the benchmark measures or checks, after the timed region and never part of `value`:
+  roofline.staged and the relax alone on the device   one untimed step with the stages one after the other
+  beside_the_headline                                 N = 1: from host memory (PCIe), 50-camera relax, mesh relax stage,
+                                                      dense guided matching, the reference's schedule of INITIAL_PROCESSING
+  cpu_baseline                                        N = 1: the CPU restatement (oracle/) timed on this box's usable host
+                                                      cores on a bounded sample of the same workload (--no-cpu-baseline: not)
+  strong_scaling (weak mode, N > 1)                   a short run of the strong mode in a child process per rank
+  strong_scaling.general_engine_sharded               --scaling strong --relax sharded: the mesh flavour behind the same
+                                                      exchange, checked against the unsharded solve (in a warm-up step)
+Without --full those fields are null.
 """
 import argparse
 import json
@@ -775,7 +786,7 @@ class StrongRunner:
             self.rctx.synchronize()
             t["relax"] = time.perf_counter() - t1
             res["relax"] = rel
-            if acc is None and "general_engine_sharded" not in self.last:
+            if self.args.full and acc is None and "general_engine_sharded" not in self.last:
                 self.last["general_engine_sharded"] = self._general_engine_sharded()
             g.close()
             self.pending = (threading.Thread(target=lambda: None), res, t)
@@ -865,7 +876,7 @@ def strong_main(args, proc, cfg):
     roofline["kernel"] += f" (rank 0's block of {runner.cnt} images per step)"
     rel = runner.last.get("res", {}).get("relax")
     cpu = None
-    if proc.rank == 0 and proc.world == 1 and not args.no_cpu_baseline:
+    if args.full and proc.rank == 0 and proc.world == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline_leg(ctx, grid, runner.images, runner.shape, proc.threads, runner.start_ori)
     if proc.rank == 0:
         relax_info = {"lm_iters_per_s_in_pipeline": report["lm_iters_per_s_in_pipeline"],
@@ -1069,11 +1080,11 @@ def weak_main(args, proc, cfg):
     n, h, w = shape
     # With the load and link stages overlapped the extraction shares the device with the link kernels during the timed
     # steps, so the in-situ figure understates the extract kernels; one extra step with the stages run one after the
-    # other (same process, after the timed region, HIP events as above) gives the sequence on its own.
+    # other (same process, after the timed region, HIP events as above; --full) gives the sequence on its own.
     roofline = device_rooflines(ctx, capi, args.steps, grid.n_images, acc["extract"] / args.steps, shape, overlap,
                                 last["link_work"], res["edges"])
     staged_relax = None
-    if overlap and rank == 0:
+    if args.full and overlap and rank == 0:
         ctx.profile_reset()
         g2, res2, t2 = pipeline.run(ctx, grid, images, shape, start_ori, overlap=False)
         staged_relax = dict(res2["relax"])
@@ -1105,19 +1116,19 @@ def weak_main(args, proc, cfg):
                   "cameras_left_unconstrained": int(np.sum(err > 0.02))}
 
     extras = {}
-    if rank == 0 and world == 1 and os.environ.get("OCHIP_BENCH_EXTRAS", "1") != "0":
+    if args.full and rank == 0 and world == 1 and os.environ.get("OCHIP_BENCH_EXTRAS", "1") != "0":
         extras = beside_the_headline(ctx, grid, images, shape, start_ori, hot_max / args.steps, rctx if relax_overlap else None)
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:   # the CPU leg is timed at N = 1 only
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:   # the CPU leg is timed at N = 1 only
         cpu = cpu_baseline_leg(ctx, grid, images, shape, proc.threads, start_ori)
 
-    # ---- N > 1: a short run of the strong mode beside the weak headline (ONE survey of this shape over the N ranks), so
-    #      that a scaling run of the default command carries both curves.  A watchdog bounds it: the headline is printed
-    #      even if the strong run cannot finish.
+    # ---- N > 1, --full: a short run of the strong mode beside the weak headline (ONE survey of this shape over the N
+    #      ranks), so that a scaling run carries both curves.  A watchdog bounds it: the headline is printed even if the
+    #      strong run cannot finish.
     strong = None
     ctx.synth_views_free(images)
     images = None
-    if world > 1 and os.environ.get("OCHIP_BENCH_STRONG_BESIDE", "1") != "0":
+    if args.full and world > 1 and os.environ.get("OCHIP_BENCH_STRONG_BESIDE", "1") != "0":
         strong = run_strong_beside(args, proc, cfg)
 
     if rank == 0:
@@ -1139,7 +1150,7 @@ def weak_main(args, proc, cfg):
             # extract k | link k - 1 | relax k - 2 side by side, every new camera bootstrapped by a solve of its own): never `value`
             "images_per_s_reference_schedule": (lambda p: None if not isinstance(p, dict) or "error" in p else p.get("images_per_s"))(
                 (extras or {}).get("incremental_batches")),
-            "value_assumes": "views resident in HBM when the timed region starts (bench contract); PCIe-inclusive rate beside it",
+            "value_assumes": "views resident in HBM when the timed region starts (bench contract); PCIe-inclusive rate beside it (--full)",
             "images_per_s_weak_one_survey_per_gpu": round(value, 3),
             "images_per_s_strong_one_survey_over_all_gpus": (round(value, 3) if world == 1 else
                                                              (strong or {}).get("images_per_s")),
@@ -1189,7 +1200,7 @@ def run_strong_beside(args, proc, cfg):
     env = dict(os.environ, MASTER_PORT=str(port), OCHIP_BENCH_STRONG_BESIDE="0")
     env.pop("OCHIP_BENCH_CPUS", None)                                   # (already pinned: inherited)
     cmd = [sys.executable, os.path.abspath(__file__), "--gpus", str(proc.world), "--scaling", "strong", "--relax", args.relax,
-           "--steps", str(steps), "--warmup", "1", "--config", args.config, "--no-cpu-baseline"]
+           "--steps", str(steps), "--warmup", "1", "--config", args.config, "--no-cpu-baseline", "--full"]
     try:
         done = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, timeout=300.0)
     except subprocess.TimeoutExpired:
@@ -1224,7 +1235,11 @@ def main():
     ap.add_argument("--relax", default="pipelined", choices=["pipelined", "sharded"],
                     help="strong scaling only: pipelined = the relax of survey k runs on rank k mod N in the shadow of the next "
                          "surveys (as at N = 1); sharded = inside the step, residual blocks over all ranks, RCCL exchange")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run what the headline does not need: the staged step, the measurements "
+                         "beside the headline, the CPU baseline (N = 1), the strong mode beside the weak one (N > 1) and the "
+                         "sharded general-engine check (strong mode); without it those fields are null")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps write what the last timed step computed (rank 0's survey: relax result, "
                          "edges, a fixed sample of feature lists and inlier sets) as DIR/<name>.npy, float64, under 64 MB; "

@@ -6,7 +6,7 @@ rm -rf $OUT; mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 # read by the HIP runtime when rocprofv3's preloaded library initialises it, i.e. before python starts
 export HSA_ENABLE_IPC_MODE_LEGACY=0
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- python3 $R/bench.py --steps 6 --warmup 2 --no-cpu-baseline > $OUT/bench.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- python3 $R/bench.py --steps 6 --warmup 2 --no-cpu-baseline --full > $OUT/bench.log 2>&1
 cd $R && python3 - <<'PY'
 import csv, glob, os
 f = max(glob.glob("gpurun_out/prof_pipe/trace/*/*_kernel_stats.csv"), key=os.path.getmtime)

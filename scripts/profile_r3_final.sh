@@ -8,7 +8,7 @@ cd /tmp && export TMPDIR=/tmp
 export HSA_ENABLE_IPC_MODE_LEGACY=0 OCHIP_BENCH_EXTRAS=0
 OCHIP_PIPELINE_OVERLAP=0 OCHIP_EXTRACT_STREAMS=1 OCHIP_LINK_RUNNERS=1 timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/single -- python3 $R/bench.py --config C3 --steps 2 --warmup 1 --no-cpu-baseline > $OUT/single.log 2>&1
 cp $(ls $OUT/single/*/*_kernel_stats.csv | head -1) $R/gpurun_out/r03_final_e2e_single_stream_kernel_stats.csv
-timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/overlap -- python3 $R/bench.py --config C3 --steps 2 --warmup 1 --no-cpu-baseline > $OUT/overlap.log 2>&1
+timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/overlap -- python3 $R/bench.py --config C3 --steps 2 --warmup 1 --no-cpu-baseline --full > $OUT/overlap.log 2>&1
 cp $(ls $OUT/overlap/*/*_kernel_stats.csv | head -1) $R/gpurun_out/r03_final_e2e_kernel_stats.csv
 grep "\"metric\"" $OUT/single.log | tail -n 1 | cut -c1-300
 grep "\"metric\"" $OUT/overlap.log | tail -n 1 > $R/gpurun_out/r03_final_e2e_bench_line.json

@@ -24,7 +24,7 @@ cp $R/gpurun_out/r04d_pmc_counters.json $OUT/r04_describe_pmc.json
 bash $R/scripts/profile_r4_match_pmc.sh r04m > $OUT/match_pmc.txt 2>&1
 cp $R/gpurun_out/r04m_pmc_counters.json $OUT/r04_match_pmc.json
 # 4. the default bench under the tracer: overlapped, then one launch sequence / one link runner / one survey at a time
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/ovl -- python3 $R/bench.py --steps 3 --warmup 1 --no-cpu-baseline > $OUT/r04_e2e_bench_line.json 2> $OUT/ovl.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/ovl -- python3 $R/bench.py --steps 3 --warmup 1 --no-cpu-baseline --full > $OUT/r04_e2e_bench_line.json 2> $OUT/ovl.err
 cp $(ls -t $OUT/ovl/*/*_kernel_stats.csv | head -1) $OUT/r04_e2e_kernel_stats.csv; rm -rf $OUT/ovl
 OCHIP_PIPELINE_OVERLAP=0 OCHIP_EXTRACT_STREAMS=1 OCHIP_LINK_RUNNERS=1 OCHIP_BENCH_EXTRAS=0 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/single -- python3 $R/bench.py --steps 2 --warmup 1 --no-cpu-baseline > $OUT/single.json 2> $OUT/single.err
 cp $(ls -t $OUT/single/*/*_kernel_stats.csv | head -1) $OUT/r04_e2e_single_stream_kernel_stats.csv; rm -rf $OUT/single

@@ -23,7 +23,7 @@ rm -rf $OUT/hbm
 bash $R/scripts/r5_pmc.sh r05s "level_strip_kernel|det_strip_kernel|describe3" > $OUT/strip_pmc.txt 2>&1
 cp $R/gpurun_out/r05s_pmc_counters.json $OUT/r05_strip_describe_pmc.json
 # 4. the default bench under the tracer, and one launch sequence / one link runner / one survey at a time
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/ovl -- python3 $R/bench.py --steps 3 --warmup 1 --no-cpu-baseline > $OUT/r05_e2e_bench_line.json 2> $OUT/ovl.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/ovl -- python3 $R/bench.py --steps 3 --warmup 1 --no-cpu-baseline --full > $OUT/r05_e2e_bench_line.json 2> $OUT/ovl.err
 cp $(ls -t $OUT/ovl/*/*_kernel_stats.csv | head -1) $OUT/r05_e2e_kernel_stats.csv; rm -rf $OUT/ovl
 OCHIP_PIPELINE_OVERLAP=0 OCHIP_EXTRACT_STREAMS=1 OCHIP_LINK_RUNNERS=1 OCHIP_BENCH_EXTRAS=0 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/single -- python3 $R/bench.py --steps 2 --warmup 1 --no-cpu-baseline > $OUT/single.json 2> $OUT/single.err
 cp $(ls -t $OUT/single/*/*_kernel_stats.csv | head -1) $OUT/r05_e2e_single_stream_kernel_stats.csv; rm -rf $OUT/single

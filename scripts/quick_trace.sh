@@ -6,7 +6,7 @@ rm -rf $OUT; mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 # read by the HIP runtime when rocprofv3's preloaded library initialises it, i.e. before python starts
 export HSA_ENABLE_IPC_MODE_LEGACY=0
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/ovl -- python3 $R/bench.py --steps 3 --warmup 1 --no-cpu-baseline > $OUT/ovl.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/ovl -- python3 $R/bench.py --steps 3 --warmup 1 --no-cpu-baseline --full > $OUT/ovl.log 2>&1
 f=$(ls -t $OUT/ovl/*/*_kernel_stats.csv | head -1)
 python3 - "$f" <<'PY'
 import csv, sys

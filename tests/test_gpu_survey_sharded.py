@@ -35,7 +35,7 @@ def test_bench_launches_its_ranks_strong(relax):
     env = dict(os.environ, OCHIP_BENCH_BACKEND="gloo", OCHIP_HOST_THREADS="8")
     env.pop("WORLD_SIZE", None), env.pop("RANK", None)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--scaling", "strong", "--relax", relax, "--config", "C2",
-           "--steps", "2", "--warmup", "1", "--no-cpu-baseline"]
+           "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--full"]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-4000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
@@ -52,11 +52,11 @@ def test_bench_launches_its_ranks_strong(relax):
 
 
 def test_bench_weak_line_carries_the_strong_section():
-    """`bench.py --gpus 2` (the scaling run's command): one weak line, and beside it the strong mode run by a child process per
-    rank (so that nothing it does can take the headline with it)."""
+    """`bench.py --gpus 2 --full` (the scaling run's command): one weak line, and beside it the strong mode run by a child
+    process per rank (so that nothing it does can take the headline with it)."""
     env = dict(os.environ, OCHIP_BENCH_BACKEND="gloo", OCHIP_HOST_THREADS="8")
     env.pop("WORLD_SIZE", None), env.pop("RANK", None)
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--config", "C2", "--steps", "2", "--warmup", "1"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--config", "C2", "--steps", "2", "--warmup", "1", "--full"]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=1200, env=env)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-4000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]

@@ -2,8 +2,8 @@
 ranks, its relaxes sharded, the clustered stage's groups dealt over the ranks - two groups per rank
 (tests/sharded_world4_worker.py).  Two RCCL ranks have never run (1-GPU boxes); this keeps everything around the transport -
 block arithmetic, exchanges, groups dealt over fewer ranks than groups - exercised beyond N = 2.  Four ranks and this
-process stay within the six processes that may hold a shared GPU open at once (`bench.py --gpus N` runs a strong-mode
-child beside every rank, so its launcher form is tested at N = 2, tests/test_gpu_survey_sharded.py)."""
+process stay within the six processes that may hold a shared GPU open at once (`bench.py --gpus N --full` runs a
+strong-mode child beside every rank, so its launcher form is tested at N = 2, tests/test_gpu_survey_sharded.py)."""
 import os
 import subprocess
 import sys
