@@ -470,6 +470,18 @@ extern "C"
     /* cam_q: n_cams x 4; ochip_relax_solve leaves the optimised cameras' quaternions normalised exactly as
      * RelaxProblem::solve does after every Solve (:1410-1413); plane_z: 3 */
     int ochip_relax_get_state(ochip_relax_problem *p, double *cam_q, double *plane_z);
+    /* One evaluation for tests, in the library's unknown order (n unknowns): the cost of the reduced program and, when not
+     * NULL, the dense J'J (n x n; entries outside the stored tiles of the block envelope read as zero) and J'r (n).
+     * route 0: the current state (delta must be NULL); route 1: the candidate x [+] delta the way an accepted LM step
+     * evaluates it, with a Jacobi scale of 1 (the state buffers exchanged, with its Jacobian and the damping's diagonal into
+     * the system's second set; J'J or J'r required);
+     * route 2: the candidate as state 1 of the plain evaluation.  delta (n, or NULL = zero) is applied by the solver's
+     * own candidate kernel; the current state is left as it is.  order_out (n_cams + 3): first unknown of every camera,
+     * then of the three plane heights, or -1.  layout_out (4): n, the first unknown of the dense tail, the number of
+     * regions of the band and the number of separator cameras.  cost NULL (and JtJ, Jtr NULL): n_out, order_out and
+     * layout_out only, nothing evaluated.  Returns 1 for a non-finite block. */
+    int ochip_relax_evaluate(ochip_relax_problem *p, int route, const double *delta, double *cost, int *n_out, double *JtJ,
+                             double *Jtr, int32_t *order_out, int32_t *layout_out);
 
     /* ---- relax, general form: ground mesh, multi-ray tracks, shared intrinsics (replaces ceres::Solver::Solve on the
      *      problems RelaxProblem::setupGroundMeshProblem / setupGroundPlaneProblem build, src/relax/relax_problem.cpp:61-120:

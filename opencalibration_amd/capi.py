@@ -23,7 +23,7 @@ EXPORTS = [
     "ochip_upload_batch", "ochip_host_alloc", "ochip_host_free", "ochip_akaze_batch", "ochip_akaze_batch_dev", "ochip_akaze_features", "ochip_akaze_features_dev", "ochip_feature_lists_from_keypoints",
     "ochip_synth_views_alloc", "ochip_synth_views_free", "ochip_synth_render_views", "ochip_synth_views_read",
     "ochip_relax_problem_create", "ochip_relax_problem_destroy", "ochip_relax_set_cameras_constant",
-    "ochip_relax_solve", "ochip_relax_get_state", "ochip_relax_set_shard",
+    "ochip_relax_solve", "ochip_relax_get_state", "ochip_relax_set_shard", "ochip_relax_evaluate",
     "ochip_plane_setup_create", "ochip_plane_setup_override", "ochip_plane_setup_blocks", "ochip_plane_setup_destroy",
     "ochip_plane_chain_create", "ochip_plane_chain_run", "ochip_plane_chain_destroy",
     "ochip_relaxg_problem_create", "ochip_relaxg_problem_destroy", "ochip_relaxg_set_structure_only", "ochip_relaxg_solve",
@@ -40,6 +40,55 @@ EXPORTS = [
 ]
 
 _lib = None
+
+
+class RelaxDesc(C.Structure):
+    """include/ochip.h: ochip_relax_desc"""
+    _fields_ = [("n_cams", C.c_uint32), ("cam_pos", C.c_void_p), ("cam_q", C.c_void_p), ("cam_optimize", C.c_void_p),
+                ("plane_xy", C.c_double * 6), ("plane_z", C.c_double * 3), ("z_optimize", C.c_uint8 * 3),
+                ("n_blocks", C.c_uint32), ("blk_cam_a", C.c_void_p), ("blk_cam_b", C.c_void_p), ("blk_rays", C.c_void_p),
+                ("n_prior", C.c_uint32), ("prior_cam", C.c_void_p), ("huber_a", C.c_double), ("prior_weight", C.c_double)]
+
+
+class RelaxOptions(C.Structure):
+    """include/ochip.h: ochip_relax_options"""
+    _fields_ = [("max_num_iterations", C.c_int), ("initial_trust_region_radius", C.c_double),
+                ("function_tolerance", C.c_double), ("gradient_tolerance", C.c_double), ("parameter_tolerance", C.c_double)]
+
+
+class RelaxSummary(C.Structure):
+    """include/ochip.h: ochip_relax_summary"""
+    _fields_ = [("termination", C.c_int), ("iterations", C.c_int), ("successful_steps", C.c_int),
+                ("unsuccessful_steps", C.c_int), ("num_parameters", C.c_int), ("num_residual_blocks", C.c_int),
+                ("initial_cost", C.c_double), ("final_cost", C.c_double)]
+
+
+def relax_desc(scene):
+    """(RelaxDesc, arrays it points into) of a dict holding the ochip_relax_desc fields by name: cam_pos, cam_q,
+    cam_optimize, plane_xy (6), plane_z (3), z_optimize (3), blk_cam_a, blk_cam_b, blk_rays (n_blocks x 6), prior_cam,
+    huber_a, prior_weight"""
+    d = RelaxDesc()
+    keep = []
+
+    def arr(name, dtype):
+        a = np.ascontiguousarray(scene[name], dtype).reshape(-1)
+        a = a if a.size else np.zeros(1, dtype)
+        keep.append(a)
+        return a.ctypes.data
+
+    d.n_cams = len(scene["cam_pos"])
+    d.cam_pos, d.cam_q, d.cam_optimize = arr("cam_pos", np.float64), arr("cam_q", np.float64), arr("cam_optimize", np.uint8)
+    for i in range(6):
+        d.plane_xy[i] = float(np.reshape(scene["plane_xy"], -1)[i])
+    for i in range(3):
+        d.plane_z[i] = float(scene["plane_z"][i])
+        d.z_optimize[i] = int(scene["z_optimize"][i])
+    d.n_blocks = len(scene["blk_cam_a"])
+    d.blk_cam_a, d.blk_cam_b = arr("blk_cam_a", np.uint32), arr("blk_cam_b", np.uint32)
+    d.blk_rays = arr("blk_rays", np.float64)
+    d.n_prior, d.prior_cam = len(scene["prior_cam"]), arr("prior_cam", np.uint32)
+    d.huber_a, d.prior_weight = scene["huber_a"], scene["prior_weight"]
+    return d, keep
 
 
 class RelaxgDesc(C.Structure):
@@ -428,6 +477,63 @@ class Context:
         finally:
             self.L.ochip_relaxg_problem_destroy(p)
         return cost.value, JtJ, Jtr, order
+
+    def relax_evaluate(self, scene, route=0, delta=None, cameras_constant=False, iterations=0):
+        """One evaluation of a plane-engine relax problem (ochip_relax_problem_create, ochip_relax_evaluate, destroy).
+        scene: dict of the ochip_relax_desc fields (relax_desc).  iterations > 0: ochip_relax_solve with that many
+        iterations first.  route / delta: as ochip_relax_evaluate (delta in the library's unknown order).
+        cameras_constant: the evaluation between ochip_relax_set_cameras_constant(1) and (0); the evaluation after the
+        undo is returned as well, under "undone".  dict: cost, JtJ, Jtr, order (n_cams + 3), layout (n, tail_begin,
+        regions, separator cameras), cam_q and plane_z (the current state), summary (of the solve, or None).  An
+        evaluation that reports non-finite blocks raises OchipError."""
+        d, keep = relax_desc(scene)
+        p = C.c_void_p()
+        L = self.L
+        L.ochip_relax_problem_create.argtypes = [C.c_void_p, C.POINTER(RelaxDesc), C.POINTER(C.c_void_p)]
+        L.ochip_relax_problem_destroy.argtypes = [C.c_void_p]
+        L.ochip_relax_problem_destroy.restype = None
+        L.ochip_relax_set_cameras_constant.argtypes = [C.c_void_p, C.c_int]
+        L.ochip_relax_solve.argtypes = [C.c_void_p, C.POINTER(RelaxOptions), C.POINTER(RelaxSummary)]
+        L.ochip_relax_get_state.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        L.ochip_relax_evaluate.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int),
+                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+
+        def one(route, delta):
+            cost, n = C.c_double(), C.c_int()
+            order, layout = np.zeros(d.n_cams + 3, np.int32), np.zeros(4, np.int32)
+            self._check(L.ochip_relax_evaluate(p, 0, None, None, C.byref(n), None, None, order.ctypes.data, layout.ctypes.data),
+                        "ochip_relax_evaluate")  # (the layout alone)
+            n = n.value
+            JtJ, Jtr = np.zeros((max(n, 1), max(n, 1))), np.zeros(max(n, 1))
+            dl = None if delta is None else np.ascontiguousarray(delta, np.float64)
+            assert dl is None or dl.shape == (n,), (None if dl is None else dl.shape, n)
+            rc = L.ochip_relax_evaluate(p, int(route), None if dl is None else dl.ctypes.data, C.byref(cost), None,
+                                        JtJ.ctypes.data, Jtr.ctypes.data, None, None)
+            if rc != 0:
+                raise OchipError(f"ochip_relax_evaluate = {rc}: {L.ochip_last_error(self.h).decode()}")
+            q, z = np.zeros((d.n_cams, 4)), np.zeros(3)
+            self._check(L.ochip_relax_get_state(p, q.ctypes.data, z.ctypes.data), "ochip_relax_get_state")
+            return dict(cost=cost.value, JtJ=JtJ[:n, :n], Jtr=Jtr[:n], order=order, layout=layout, cam_q=q, plane_z=z)
+
+        self._check(L.ochip_relax_problem_create(self.h, C.byref(d), C.byref(p)), "ochip_relax_problem_create")
+        try:
+            summary = None
+            if iterations > 0:
+                opt = RelaxOptions(max_num_iterations=int(iterations), initial_trust_region_radius=1.0, function_tolerance=1e-6,
+                                   gradient_tolerance=1e-10, parameter_tolerance=1e-8)
+                s = RelaxSummary()
+                self._check(L.ochip_relax_solve(p, C.byref(opt), C.byref(s)), "ochip_relax_solve")
+                summary = {k: getattr(s, k) for k, _ in RelaxSummary._fields_}
+            if cameras_constant:
+                self._check(L.ochip_relax_set_cameras_constant(p, 1), "ochip_relax_set_cameras_constant")
+            out = one(route, delta)
+            out["summary"] = summary
+            if cameras_constant:
+                self._check(L.ochip_relax_set_cameras_constant(p, 0), "ochip_relax_set_cameras_constant")
+                out["undone"] = one(0, None)
+        finally:
+            L.ochip_relax_problem_destroy(p)
+        return out
 
     def profile_reset(self):
         self._check(self.L.ochip_profile_reset(self.h), "ochip_profile_reset")

@@ -228,7 +228,7 @@ __global__ __launch_bounds__(W) void relax_pair_eval_kernel(relax_dev P, int whi
 // pair the camera is in (~18): one trip to memory for all of them instead of one per pair, then a fixed shuffle tree
 // (a thread per camera walking its pairs took 26 us of an LM iteration).
 __device__ __forceinline__ void scatter_cam(const relax_dev &P, const lm_matrix &A, double *g, int n, const uint8_t *cam_has_prior,
-                                            uint32_t c, int lane)
+                                            uint32_t c, int lane, int which_state)
 {
     if (c >= P.n_cams)
         return;
@@ -262,7 +262,7 @@ __device__ __forceinline__ void scatter_cam(const relax_dev &P, const lm_matrix 
     if (cam_has_prior[c])
     {
         double r, j3[3];
-        downward_prior(P.cam_q + (size_t)c * 4, P.prior_weight, &r, j3);
+        downward_prior((which_state ? P.cam_q2 : P.cam_q) + (size_t)c * 4, P.prior_weight, &r, j3); // (the state evaluated)
         int k = 0;
         for (int i = 0; i < 3; i++)
         {
@@ -331,7 +331,7 @@ __global__ __launch_bounds__(256) void relax_reduce_plane_kernel(relax_dev P, lm
     {
         const uint32_t sb = (uint32_t)(b - groups);
         if (sb < cam_blocks)
-            scatter_cam(P, A, g, n, cam_has_prior, sb * (256 / W) + t / W, t % W);
+            scatter_cam(P, A, g, n, cam_has_prior, sb * (256 / W) + t / W, t % W, which_state);
         else
             scatter_pair(P, A, n, (sb - cam_blocks) * 256 + t);
         // every wavefront's stores have left it before the barrier in front of the arrival (a workgroup barrier alone does not
@@ -351,6 +351,8 @@ __global__ __launch_bounds__(256) void relax_reduce_plane_kernel(relax_dev P, lm
     else
     {
         double v[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0}; // zz (6), gz (3), cost
+        // a pair of constant cameras on constant heights reads no unknown: fixed cost (not in the reduced program)
+        const bool z_free = P.z_t[0] >= 0 || P.z_t[1] >= 0 || P.z_t[2] >= 0;
         for (uint32_t pr = b * 256 + t; pr < P.n_pairs; pr += 256 * groups)
         {
             if (with_jac)
@@ -363,7 +365,8 @@ __global__ __launch_bounds__(256) void relax_reduce_plane_kernel(relax_dev P, lm
                 for (int i = 0; i < 3; i++)
                     v[6 + i] += a[45 + 6 + i];
             }
-            v[9] += P.pair_cost[pr];
+            if (z_free || P.cam_t[P.pair_p[pr]] >= 0 || P.cam_t[P.pair_q[pr]] >= 0)
+                v[9] += P.pair_cost[pr];
         }
         const double *Q = which_state ? P.cam_q2 : P.cam_q;
         for (uint32_t c = b * 256 + t; c < P.n_cams; c += 256 * groups)
@@ -591,6 +594,8 @@ struct ochip_relax_problem
     ochip_relax_exchange_fn exchange = nullptr;
     void *exchange_user = nullptr;
     int32_t *fail_ranks = nullptr;
+    double *eval_scratch = nullptr; // ochip_relax_evaluate: scale, -delta and the candidate's scalars (grown, never per call)
+    size_t eval_scratch_cap = 0;
 };
 
 namespace
@@ -1301,6 +1306,89 @@ int ochip_relax_solve(ochip_relax_problem *p, const ochip_relax_options *opt, oc
         return OCHIP_OK;
     }
     return lm_solve(p->sys, model, opt, sum);
+}
+
+int ochip_relax_evaluate(ochip_relax_problem *p, int route, const double *delta, double *cost, int *n_out, double *JtJ, double *Jtr,
+                         int32_t *order_out, int32_t *layout_out)
+{
+    if (!p || route < 0 || route > 2 || (route == 0 && delta) || (!cost && (JtJ || Jtr)))
+        return OCHIP_EINVAL;
+    ochip_ctx *ctx = p->ctx;
+    OCHIP_HIP(ctx, hipSetDevice(ctx->device));
+    plane_model model(p);
+    const int n = p->n_tangent;
+    if (n_out)
+        *n_out = n;
+    if (order_out)
+    {
+        for (uint32_t c = 0; c < p->n_cams; c++)
+            order_out[c] = p->cam_t[c];
+        for (int i = 0; i < 3; i++)
+            order_out[p->n_cams + i] = p->z_t[i];
+    }
+    if (layout_out)
+    {
+        int active = 0;
+        for (int32_t t : p->cam_t)
+            active += t >= 0;
+        layout_out[0] = n;
+        layout_out[1] = p->sys.env.tail_begin;
+        layout_out[2] = std::max<int>((int)p->sys.env.region_begin.size(), 1);
+        layout_out[3] = active - p->sys.env.tail_begin / 3; // the separator cameras: the active ones in the tail
+    }
+    if (!cost) // (the layout alone)
+        return OCHIP_OK;
+    const bool with_jac = (JtJ || Jtr) && n > 0;
+    int rc;
+    if (route == 0)
+        rc = model.evaluate(with_jac, 0, cost);
+    else
+    {
+        // the candidate x [+] delta through the solver's own kernel: scale 1, y = -delta, alpha 1 (delta NULL: zero)
+        std::vector<double> host(2 * (size_t)std::max(n, 1) + 8, 0.0);
+        for (int i = 0; i < n; i++)
+        {
+            host[i] = 1.0;
+            host[(size_t)n + i] = delta ? -delta[i] : 0.0;
+        }
+        if (host.size() > p->eval_scratch_cap)
+        {
+            const int urc = dev_upload<double>(p, &p->eval_scratch, nullptr, host.size());
+            if (urc != OCHIP_OK)
+                return urc;
+            p->eval_scratch_cap = host.size();
+        }
+        double *buf = p->eval_scratch;
+        OCHIP_HIP(ctx, hipMemcpyAsync(buf, host.data(), host.size() * 8, hipMemcpyHostToDevice, ctx->stream));
+        const double *scale = buf, *y = buf + n;
+        double *scal = buf + 2 * (size_t)n;
+        hipLaunchKernelGGL(plane_candidate_kernel, dim3(1), dim3(LM_TG), 0, ctx->stream, p->dev, scale, y, 1.0, scal);
+        OCHIP_HIP(ctx, hipGetLastError());
+        if (route == 2)
+            rc = model.evaluate(with_jac, 1, cost);
+        else
+        {
+            // the speculative route of an accepted LM step, as the solver launches it (Jacobi scale 1): the candidate as the
+            // current state of a view, into the second set
+            if (!with_jac || !model.speculates())
+                return ochip_fail(ctx, OCHIP_EINVAL, "route 1 evaluates the candidate with its Jacobian into the second set");
+            int mask = 0;
+            rc = model.evaluate_candidate_jac(scale, cost, &mask);
+            rc = rc < 0 ? rc : (mask ? 1 : 0);
+            p->sys.swap_sets();
+        }
+    }
+    if (rc >= 0 && with_jac)
+    {
+        int drc = JtJ ? lm_download_dense(p->sys, JtJ) : OCHIP_OK;
+        if (drc == OCHIP_OK && Jtr && hipMemcpy(Jtr, p->sys.g, (size_t)n * 8, hipMemcpyDeviceToHost) != hipSuccess)
+            drc = ochip_fail(ctx, OCHIP_EHIP, "hipMemcpy failed (gradient)");
+        if (drc)
+            rc = drc;
+    }
+    if (route == 1 && with_jac && p->sys.A2)
+        p->sys.swap_sets();
+    return rc;
 }
 
 } // extern "C"

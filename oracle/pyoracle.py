@@ -779,6 +779,8 @@ def _relaxg_fns():
         vp = C.c_void_p
         L.oc_relaxg_eval.restype = C.c_int
         L.oc_relaxg_eval.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+        L.oc_relaxg_eval_reduced.restype = C.c_int
+        L.oc_relaxg_eval_reduced.argtypes = L.oc_relaxg_eval.argtypes + [vp]
         L.oc_relaxg_fd.restype = C.c_int
         L.oc_relaxg_fd.argtypes = [vp, C.c_int, C.c_double, vp]
         L._relaxg_ready = True
@@ -789,9 +791,10 @@ def relaxg_eval(scene, precision=1, raw=False, mutate=MUT_NONE, mutate_arg=-1, d
     """The general engine's problem (a scene dict of ochip_relaxg_desc fields, opencalibration_amd.capi.relaxg_desc) evaluated
     the way the reference's Problem evaluates it, in long double (precision=1) or double (0).  dict: fail (a block did not
     evaluate to finite values), n, cost, JtJ (n x n), Jtr, J (rows x n, corrected), r (corrected), row_blk (block of each
-    row), touch (rows x n: 1 where a row structurally depends on a column) and order (n_cams + n_verts + 3: the first
-    canonical column of every camera / vertex / f / pp / k, or -1).  raw: no loss and no corrector.  delta: the state
-    moved by x [+] delta over the canonical unknowns first."""
+    row), touch (rows x n: 1 where a row structurally depends on a column), order (n_cams + n_verts + 3: the first
+    canonical column of every camera / vertex / f / pp / k, or -1) and cost_reduced (the blocks that read at least one
+    unknown: Ceres' reduced program).  raw: no loss and no corrector.  delta: the state moved by x [+] delta over the
+    canonical unknowns first."""
     from opencalibration_amd import capi
 
     L = _relaxg_fns()
@@ -803,12 +806,13 @@ def relaxg_eval(scene, precision=1, raw=False, mutate=MUT_NONE, mutate_arg=-1, d
     L.oc_relaxg_eval(*args, C.byref(n), C.byref(rows), *([None] * 8))
     n, m = n.value, rows.value
     order = np.zeros(d.n_cams + d.n_verts + 3, np.int32)
-    cost = C.c_double()
+    cost, cost_reduced = C.c_double(), C.c_double()
     JtJ, Jtr, J, r = np.zeros((n, n)), np.zeros(n), np.zeros((m, n)), np.zeros(m)
     row_blk, touch = np.zeros(m, np.int32), np.zeros((m, n), np.uint8)
-    fail = L.oc_relaxg_eval(*args, None, None, order.ctypes.data, C.byref(cost), JtJ.ctypes.data, Jtr.ctypes.data,
-                            J.ctypes.data, r.ctypes.data, row_blk.ctypes.data, touch.ctypes.data)
-    return dict(fail=bool(fail), n=n, cost=cost.value, JtJ=JtJ, Jtr=Jtr, J=J, r=r, row_blk=row_blk, touch=touch, order=order)
+    fail = L.oc_relaxg_eval_reduced(*args, None, None, order.ctypes.data, C.byref(cost), JtJ.ctypes.data, Jtr.ctypes.data,
+                                    J.ctypes.data, r.ctypes.data, row_blk.ctypes.data, touch.ctypes.data, C.byref(cost_reduced))
+    return dict(fail=bool(fail), n=n, cost=cost.value, JtJ=JtJ, Jtr=Jtr, J=J, r=r, row_blk=row_blk, touch=touch, order=order,
+                cost_reduced=cost_reduced.value)
 
 
 def relaxg_fd(scene, step=1e-4, structure_only=False):

@@ -61,7 +61,7 @@ template <typename S> struct GEval
     std::vector<S> J, r, JtJ, Jtr;
     std::vector<int32_t> row_blk;
     std::vector<uint8_t> touch;
-    S cost = 0;
+    S cost = 0, cost_reduced = 0; // every block / the blocks that read at least one unknown (Ceres' reduced program)
     bool failed = false;
 
     GEval(const ochip_relaxg_desc &d_, bool so) : d(d_), structure_only(so)
@@ -211,6 +211,11 @@ template <typename S> struct GEval
         if (loss && !raw)
             mc::huber_rho<S>(S(loss->a), S(loss->b), sq, rho);
         cost += S(0.5) * rho[0];
+        bool reads_unknown = false;
+        for (const Slot<S> &sl : slots)
+            reads_unknown |= sl.t >= 0;
+        if (reads_unknown)
+            cost_reduced += S(0.5) * rho[0];
         if (loss && !raw)
         {
             S sqrt_rho1, scaling, alpha_sq_norm;
@@ -326,7 +331,7 @@ template <typename S> struct GEval
         J.clear(), r.clear(), row_blk.clear(), touch.clear();
         JtJ.assign((size_t)n * n, S(0));
         Jtr.assign(n, S(0));
-        cost = 0;
+        cost = cost_reduced = 0;
         failed = false;
         const mc::HuberLoss huber(d.huber_a), rel_huber(d.rel_huber_a);
         int b = 0;
@@ -411,7 +416,7 @@ template <typename S> void to_double(const std::vector<S> &v, double *out)
 template <typename S>
 int relaxg_eval(const ochip_relaxg_desc *d, int structure_only, int raw, int mutate, int mutate_arg, const double *delta,
                 int *n_out, int *rows_out, int32_t *order, double *cost, double *JtJ, double *Jtr, double *J, double *r,
-                int32_t *row_blk, uint8_t *touch)
+                int32_t *row_blk, uint8_t *touch, double *cost_reduced)
 {
     GEval<S> e(*d, structure_only != 0);
     e.raw = raw, e.mutate = mutate, e.mutate_arg = mutate_arg;
@@ -436,6 +441,8 @@ int relaxg_eval(const ochip_relaxg_desc *d, int structure_only, int raw, int mut
     }
     if (cost)
         *cost = (double)e.cost;
+    if (cost_reduced)
+        *cost_reduced = (double)e.cost_reduced;
     to_double(e.JtJ, JtJ);
     to_double(e.Jtr, Jtr);
     to_double(e.J, J);
@@ -463,9 +470,22 @@ int oc_relaxg_eval(const ochip_relaxg_desc *d, int structure_only, int precision
 {
     if (precision)
         return oracle::relaxg_eval<long double>(d, structure_only, raw, mutate, mutate_arg, delta, n_out, rows_out, order, cost,
-                                                JtJ, Jtr, J, r, row_blk, touch);
+                                                JtJ, Jtr, J, r, row_blk, touch, nullptr);
     return oracle::relaxg_eval<double>(d, structure_only, raw, mutate, mutate_arg, delta, n_out, rows_out, order, cost, JtJ,
-                                       Jtr, J, r, row_blk, touch);
+                                       Jtr, J, r, row_blk, touch, nullptr);
+}
+
+// oc_relaxg_eval, and the cost of the reduced program: the blocks that read at least one unknown (cost_reduced, may be
+// NULL).  The plane engine and the chain leave the others out, as Ceres' reduced program does; `cost` counts every block.
+int oc_relaxg_eval_reduced(const ochip_relaxg_desc *d, int structure_only, int precision, int raw, int mutate, int mutate_arg,
+                           const double *delta, int *n_out, int *rows_out, int32_t *order, double *cost, double *JtJ, double *Jtr,
+                           double *J, double *r, int32_t *row_blk, uint8_t *touch, double *cost_reduced)
+{
+    if (precision)
+        return oracle::relaxg_eval<long double>(d, structure_only, raw, mutate, mutate_arg, delta, n_out, rows_out, order, cost,
+                                                JtJ, Jtr, J, r, row_blk, touch, cost_reduced);
+    return oracle::relaxg_eval<double>(d, structure_only, raw, mutate, mutate_arg, delta, n_out, rows_out, order, cost, JtJ,
+                                       Jtr, J, r, row_blk, touch, cost_reduced);
 }
 
 // Richardson-extrapolated central differences in long double of the raw residuals over the canonical unknowns:

@@ -224,7 +224,10 @@ def block_stats(ref):
 def bounds(ref, c=C_BOUND):
     """c u-scaled normwise bounds: J'J_ij: sum_b rows_b ||J_b||^2_max over blocks touching i and j; J'r_i: sum_b
     ||J_b||_max ||r_b|| over blocks touching i; cost: relative to sum_b |cost_b| (= the cost: every term >= 0); J_b:
-    ||J_b||_max elementwise"""
+    ||J_b||_max elementwise.  The elementwise J bound has a heavy tail over blocks: an angle residual of a few 1e-6 rad
+    can put one fp64 partial past it (tests/test_plane_eval_oracle.py: four of the first seeds of a 960-block grid did),
+    so a larger fixture may need its seed chosen again; the normwise J'J and J'r bounds stay far inside at the same
+    states.  J'r's bound scales with ||r_b||: a block fitted to a few 1e-6 rad leaves it to rounding (same file)."""
     rows, jmax, rn, T = block_stats(ref)
     return dict(JtJ=c * U * (T.T @ (T * (rows * jmax ** 2)[:, None])), Jtr=c * U * (T.T @ (jmax * rn)),
                 cost=c * U * abs(ref["cost"]), J=c * U * jmax[ref["row_blk"]][:, None] * np.ones((1, ref["n"])))
