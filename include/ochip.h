@@ -69,6 +69,13 @@ extern "C"
      * src/pipeline/link_stage.cpp:41-117) be in flight at once: one host thread per context.  Kernel times of
      * siblings are included in ochip_profile_get(ctx, ...). */
     int ochip_ctx_sibling(ochip_ctx *ctx, uint32_t index, ochip_ctx **out);
+    /* One object that a caller keeps with ctx for the context's life (the host library's extraction slots): made with
+     * make() on the first call - calls from several threads get the same object - and handed to destroy() by
+     * ochip_ctx_destroy before anything of the context is freed. */
+    /* How many chunks of ochip_akaze_* on ctx have passed their first host read-back (the candidate counts: the scale space
+     * and the detector are then behind the sequence).  May be read from another thread while a chunk runs. */
+    uint64_t ochip_akaze_progress(const ochip_ctx *ctx);
+    void *ochip_ctx_attachment(ochip_ctx *ctx, void *(*make)(void), void (*destroy)(void *));
     /* Re-creates the context's compute stream with the highest (high != 0) or lowest stream priority of the device: a
      * latency-bound solve that shares the GPU with throughput kernels of other contexts is scheduled ahead of them.  The
      * context must be idle. */

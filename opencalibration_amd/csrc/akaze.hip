@@ -3922,6 +3922,7 @@ int akaze_run(ochip_ctx *ctx, const uint8_t *images_bgr, bool on_device, uint32_
     std::vector<unsigned int> ncand(B);
     OCHIP_HIP(ctx, hipMemcpyAsync(ncand.data(), d_ncand, B * 4, hipMemcpyDeviceToHost, st));
     OCHIP_HIP(ctx, ochip_stream_wait(ctx, st));
+    ctx->akaze_readbacks.fetch_add(1, std::memory_order_release); // the scale space is behind this sequence (ochip_akaze_progress)
     unsigned int max_n = 0;
     for (uint32_t b = 0; b < B; b++)
     {

@@ -175,8 +175,9 @@ int ochip_ctx_create(int device, ochip_ctx **out)
     }
     if (e == hipSuccess)
         e = hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking);
-    if (e == hipSuccess)
-        e = hipStreamCreateWithFlags(&ctx->copy_stream, hipStreamNonBlocking);
+    // (no copy_stream here: nothing of the hot path copies beside its own kernels, and a process has a handful of hardware
+    // queues that its streams share - a second stream per context, 30 of them with the siblings of a pipelined run, only
+    // made two extraction streams meet on one queue.  Whoever needs it creates it: ochip_copy_stream)
     if (e != hipSuccess)
     {
         int rc = ochip_fail(nullptr, OCHIP_EHIP, "context creation failed: %s", hipGetErrorString(e));
@@ -191,6 +192,9 @@ void ochip_ctx_destroy(ochip_ctx *ctx)
 {
     if (!ctx)
         return;
+    if (ctx->attachment && ctx->attachment_destroy)
+        ctx->attachment_destroy(ctx->attachment);
+    ctx->attachment = nullptr;
     for (ochip_ctx *sib : ctx->siblings)
         ochip_ctx_destroy(sib);
     ctx->siblings.clear();
@@ -279,6 +283,24 @@ int ochip_ctx_sibling(ochip_ctx *ctx, uint32_t index, ochip_ctx **out)
     return OCHIP_OK;
 }
 
+void *ochip_ctx_attachment(ochip_ctx *ctx, void *(*make)(void), void (*destroy)(void *))
+{
+    if (!ctx)
+        return nullptr;
+    std::lock_guard<std::mutex> lock(ctx->siblings_mutex);
+    if (!ctx->attachment && make)
+    {
+        ctx->attachment = make();
+        ctx->attachment_destroy = destroy;
+    }
+    return ctx->attachment;
+}
+
+uint64_t ochip_akaze_progress(const ochip_ctx *ctx)
+{
+    return ctx ? ctx->akaze_readbacks.load(std::memory_order_acquire) : 0;
+}
+
 const char *ochip_last_error(const ochip_ctx *ctx)
 {
     return ctx ? ctx->error.c_str() : g_create_error.c_str();
@@ -303,7 +325,8 @@ int ochip_synchronize(ochip_ctx *ctx)
     if (!ctx)
         return OCHIP_EINVAL;
     OCHIP_HIP(ctx, ochip_stream_wait(ctx, ctx->stream));
-    OCHIP_HIP(ctx, ochip_stream_wait(ctx, ctx->copy_stream));
+    if (ctx->copy_stream)
+        OCHIP_HIP(ctx, ochip_stream_wait(ctx, ctx->copy_stream));
     return OCHIP_OK;
 }
 

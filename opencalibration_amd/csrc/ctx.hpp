@@ -3,6 +3,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include <atomic>
 #include <cstdarg>
 #include <cstdio>
 #include <mutex>
@@ -24,7 +25,7 @@ struct ochip_ctx
 {
     int device = 0;
     hipStream_t stream = nullptr;     // compute stream: every kernel of the hot path is launched here
-    hipStream_t copy_stream = nullptr;
+    hipStream_t copy_stream = nullptr; // created on first use (ochip_copy_stream), not with the context
     std::vector<hipStream_t> retired_streams; // replaced by ochip_ctx_set_priority
     int stream_priority = -1; // what ochip_ctx_set_priority last set (-1: the default stream)
     hipEvent_t sync_event = nullptr;  // ochip_stream_wait: a blocking-sync event (created on first use)
@@ -103,6 +104,14 @@ struct ochip_ctx
     // that independent batches can be in flight at once; owned by this context
     std::vector<ochip_ctx *> siblings;
     std::mutex siblings_mutex; // ochip_ctx_sibling may be called from concurrent runner threads (RelaxStage's group runners)
+
+    // chunks of ochip_akaze_* on this context whose first host read-back (the candidate counts, after the scale space and
+    // the detector) has arrived: ochip_akaze_progress, for a caller that starts its launch sequences out of step
+    std::atomic<uint64_t> akaze_readbacks{0};
+
+    // what the host library keeps with the context (ochip_ctx_attachment: the extraction slots of host/extract_slots.hpp)
+    void *attachment = nullptr;
+    void (*attachment_destroy)(void *) = nullptr;
 };
 
 
@@ -122,6 +131,16 @@ inline hipError_t ochip_stream_wait(ochip_ctx *ctx, hipStream_t st)
     }
     const hipError_t e = hipEventRecord(ctx->sync_event, st);
     return e != hipSuccess ? e : hipEventSynchronize(ctx->sync_event);
+}
+
+// The context's second stream, for a copy that should run beside the context's own kernels: created on first use.
+inline hipError_t ochip_copy_stream(ochip_ctx *ctx, hipStream_t *out)
+{
+    hipError_t e = hipSuccess;
+    if (!ctx->copy_stream)
+        e = hipStreamCreateWithFlags(&ctx->copy_stream, hipStreamNonBlocking);
+    *out = ctx->copy_stream;
+    return e;
 }
 
 int ochip_fail(ochip_ctx *ctx, int code, const char *fmt, ...);

@@ -19,7 +19,10 @@
 //                      branch-free ones for the default scale space's radii; 64 instead of 2 048 list entries in LDS)
 // Other switches (read where they apply): OCHIP_CHAIN_WORKGROUPS (grid of the resident launch; default half the compute units),
 // OCHIP_IP_PRIORITY=0 (och_initial_processing_step: link and relax streams at the default priority), OCHIP_STRIP_MIN_PIXELS
-// (pixels per launch from which a level takes the register-strip kernels), OCHIP_EXTRACT_GATE=0 (two surveys may extract at once)
+// (pixels per launch from which a level takes the register-strip kernels), OCHIP_EXTRACT_GATE=0 (no ordering between the
+// extractions of surveys), OCHIP_EXTRACT_HANDOVER = slot | survey (host/extract_slots.hpp: the extraction contexts pass to the
+// next survey one by one - the default - or all together when the survey before has finished), OCHIP_EXTRACT_STAGGER=1 (a launch
+// sequence waits with its chunk while another one of its survey is in front of its first host read-back)
 #pragma once
 
 #include <cstdlib>

@@ -1,8 +1,10 @@
 #include "../env.hpp"
 #include "extract_features.hpp"
+#include "extract_slots.hpp"
 #include "sort_like_std.hpp"
 
 #include <algorithm>
+#include <chrono>
 #include <cmath>
 #include <condition_variable>
 #include <cstdio>
@@ -334,6 +336,33 @@ struct chunk_buffers
     std::vector<uint32_t> counts;
     uint32_t first = 0, n = 0;
 };
+
+// The slots of a root context live with it (ochip_ctx_attachment): made on the first extraction, destroyed with the context.
+// Their page-locked blocks are the contexts' own (ochip_host_alloc) and go with them.
+extract_slots &slots_of(ochip_ctx *root)
+{
+    void *p = ochip_ctx_attachment(
+        root, []() -> void * { return new extract_slots(); }, [](void *q) { delete static_cast<extract_slots *>(q); });
+    return *static_cast<extract_slots *>(p);
+}
+
+// OCHIP_EXTRACT_HANDOVER = slot (default) | survey; OCHIP_EXTRACT_GATE=0: no ordering between surveys at all
+extract_slots::order handover_order()
+{
+    const char *gate = std::getenv("OCHIP_EXTRACT_GATE");
+    if (gate && gate[0] == '0')
+        return extract_slots::order::none;
+    const char *e = std::getenv("OCHIP_EXTRACT_HANDOVER");
+    if (e && std::strcmp(e, "survey") == 0)
+        return extract_slots::order::survey;
+    return extract_slots::order::slot;
+}
+
+bool stagger_starts()
+{
+    const char *e = std::getenv("OCHIP_EXTRACT_STAGGER");
+    return e && e[0] == '1';
+}
 } // namespace
 
 uint32_t extract_chunk_size()
@@ -366,8 +395,10 @@ std::vector<extracted_features> extract_features_batch(ochip_ctx *ctx, const uin
 bool extract_features_stream(ochip_ctx *ctx, const uint8_t *images_bgr, uint32_t n_images, int width, int height,
                              uint32_t max_keypoints, bool images_on_device, int host_threads,
                              const std::function<void(uint32_t, uint32_t, extracted_features *)> &on_chunk,
-                             std::string *error)
+                             std::string *error, extract_timing *timing)
 {
+    if (timing)
+        *timing = extract_timing{};
     if (n_images == 0)
         return true;
     if (width <= 0 || height <= 0) // image.empty(): {results, 0}, extract_features.cpp:20-23
@@ -390,7 +421,7 @@ bool extract_features_stream(ochip_ctx *ctx, const uint8_t *images_bgr, uint32_t
     // Driver threads (one per device context: the caller's and its siblings) keep the device busy - a chunk's
     // result copies over PCIe, table uploads and launch gaps overlap the kernels of the other context's chunk -
     // while this thread's OpenMP team runs the host tail of the finished chunks.  ochip_akaze_batch is a blocking
-    // call; every driver owns two result buffers.  Four sequences in flight: staged extraction of the 1 000-image grid
+    // call; a driver holds its context's slot and fills the slot's result buffers (extract_slots.hpp).  Four sequences in flight: staged extraction of the 1 000-image grid
     // 0.270 s with three, 0.245 s with four, no gain from five or six (each sequence holds a 6 GB arena of level planes).
     uint32_t n_drivers = images_on_device ? 4 : 5; // (from host memory a fifth sequence keeps the PCIe link busier: 1 416 -> 1 461 images/s)
     if (const char *e = std::getenv("OCHIP_EXTRACT_STREAMS"))
@@ -410,44 +441,46 @@ bool extract_features_stream(ochip_ctx *ctx, const uint8_t *images_bgr, uint32_t
     const bool device_tail = !ochip_test_hook("host_tail");
     const double nms_pixel_radius = 8;
     const bool force_host_nms = ochip_test_hook("host_nms"); // (test knob: the conflict path for every image)
-    const uint32_t n_bufs = 2 * n_drivers;
-    std::vector<chunk_buffers> bufs(n_bufs);
-    std::vector<ochip_ctx *> buf_ctx(n_bufs);
+    // ---- the slots of this root context (extract_slots.hpp): a ticket in arrival order, retired on every return path
+    extract_slots &slots = slots_of(ctx);
+    const extract_slots::order handover = handover_order();
+    const auto t_enter = std::chrono::steady_clock::now();
+    extract_ticket ticket(slots, n_drivers);
+    constexpr int BPS = extract_slots::BUFFERS_PER_SLOT;
+    const uint32_t n_bufs = BPS * n_drivers;
+    std::vector<chunk_buffers> bufs(n_bufs); // this survey's view of buffer b of slot d, at BPS * d + b while it has it
     std::string fail;
-    auto release = [&]() {
-        for (uint32_t i = 0; i < n_bufs; i++)
+    // the page-locked blocks of a slot's buffer in this survey's shape; called by the slot's holder, on the slot's context
+    const size_t rows = (size_t)chunk * max_keypoints;
+    const size_t o_resp = (rows + chunk) * 88, o_slot = o_resp + rows * 4, o_ns = o_slot + rows * 4, o_conf = o_ns + (size_t)chunk * 4;
+    const size_t pad = ((size_t)chunk + 15) / 16 * 16;
+    const size_t o_sub = o_conf + pad, o_nsub = o_sub + (size_t)chunk * OCHIP_SUBSET_CAP * 4, o_sconf = o_nsub + (size_t)chunk * 4;
+    const size_t want[2] = {device_tail ? o_sconf + pad : rows * 6 * sizeof(float), device_tail ? 0 : rows * 8 * sizeof(uint64_t)};
+    auto shape_buffer = [&](ochip_ctx *dctx, extract_slots::buffer &sb, chunk_buffers &b) -> bool {
+        const int layout = device_tail ? 0 : 1;
+        if (sb.layout != layout || sb.bytes[0] < want[0] || sb.bytes[1] < want[1])
         {
-            chunk_buffers &b = bufs[i];
-            if (b.kp)
-                ochip_host_free(buf_ctx[i], b.kp);
-            if (b.desc)
-                ochip_host_free(buf_ctx[i], b.desc);
-            if (b.prepared)
-                ochip_host_free(buf_ctx[i], b.prepared);
-            b.kp = nullptr;
-            b.desc = nullptr;
-            b.prepared = nullptr;
+            for (int k = 0; k < 2; k++)
+            {
+                if (sb.block[k])
+                    ochip_host_free(dctx, sb.block[k]);
+                sb.block[k] = nullptr;
+                sb.bytes[k] = 0;
+            }
+            sb.layout = -1;
+            for (int k = 0; k < 2; k++)
+                if (want[k])
+                {
+                    if (ochip_host_alloc(dctx, want[k], &sb.block[k]) != OCHIP_OK)
+                        return false; // (what was allocated stays with the slot: no layout, replaced by the next holder)
+                    sb.bytes[k] = want[k];
+                }
+            sb.layout = layout;
         }
-    };
-    for (uint32_t i = 0; i < n_bufs; i++)
-    {
-        chunk_buffers &b = bufs[i];
-        buf_ctx[i] = ctxs[i / 2];
-        void *p = nullptr, *q = nullptr;
+        b = chunk_buffers{};
         if (device_tail)
         {
-            const size_t rows = (size_t)chunk * max_keypoints;
-            const size_t o_resp = (rows + chunk) * 88, o_slot = o_resp + rows * 4, o_ns = o_slot + rows * 4, o_conf = o_ns + (size_t)chunk * 4;
-            const size_t pad = ((size_t)chunk + 15) / 16 * 16;
-            const size_t o_sub = o_conf + pad, o_nsub = o_sub + (size_t)chunk * OCHIP_SUBSET_CAP * 4, o_sconf = o_nsub + (size_t)chunk * 4;
-            if (ochip_host_alloc(buf_ctx[i], o_sconf + pad, &p) != OCHIP_OK)
-            {
-                release();
-                if (error)
-                    *error = std::string("ochip_host_alloc: ") + ochip_last_error(buf_ctx[i]);
-                return false;
-            }
-            b.prepared = (uint8_t *)p;
+            b.prepared = (uint8_t *)sb.block[0];
             b.lists.records = b.prepared;
             b.lists.response = (float *)(b.prepared + o_resp);
             b.lists.slot = (uint32_t *)(b.prepared + o_slot);
@@ -458,86 +491,144 @@ bool extract_features_stream(ochip_ctx *ctx, const uint8_t *images_bgr, uint32_t
             b.lists.num_subset = (uint32_t *)(b.prepared + o_nsub);
             b.lists.subset_conflict = b.prepared + o_sconf;
             b.lists.subset_spacing = 40.0;
-            b.counts.resize(chunk);
-            continue;
         }
-        if (ochip_host_alloc(buf_ctx[i], (size_t)chunk * max_keypoints * 6 * sizeof(float), &p) != OCHIP_OK ||
-            ochip_host_alloc(buf_ctx[i], (size_t)chunk * max_keypoints * 8 * sizeof(uint64_t), &q) != OCHIP_OK)
+        else
         {
-            if (p)
-                ochip_host_free(buf_ctx[i], p);
-            release();
-            if (error)
-                *error = std::string("ochip_host_alloc: ") + ochip_last_error(buf_ctx[i]);
-            return false;
+            b.kp = (float *)sb.block[0];
+            b.desc = (uint64_t *)sb.block[1];
         }
-        b.kp = (float *)p;
-        b.desc = (uint64_t *)q;
         b.counts.resize(chunk);
-    }
+        return true;
+    };
     double tail_cpu_seconds = 0;
     std::mutex mu;
     std::condition_variable cv;
     std::deque<int> ready; // filled buffers
-    std::vector<char> buffer_free(n_bufs, 1);
     uint32_t next_chunk = 0, drivers_done = 0;
+    bool started = false;
+    std::chrono::steady_clock::time_point t_first_slot = t_enter;
+    // Start offset (OCHIP_EXTRACT_STAGGER=1): a driver does not start a chunk while another sequence of
+    // this survey is still in front of its first host read-back, so that the sequences do not run the same kernels side by side.
+    const bool stagger = stagger_starts();
+    const bool trace = ochip_verbose("extract");
+    std::vector<uint64_t> progress_at_start(n_drivers, 0);
+    std::vector<char> in_first_phase(n_drivers, 0);
 
     std::vector<double> driver_cpu(n_drivers, 0.0);
     auto driver = [&](uint32_t d) {
         ochip_ctx *dctx = ctxs[d];
-        int which = 2 * (int)d;
         const double cpu0 = thread_cpu_now();
         struct at_exit
         {
             double &out, t0;
             ~at_exit() { out = thread_cpu_now() - t0; }
         } record{driver_cpu[d], cpu0};
-        for (;;)
         {
-            uint32_t c;
+            // (the hold is given back before drivers_done is counted: a driver that finds no chunk left frees its slot at
+            // once, while the survey's other chunks still run)
+            slot_hold hold(slots, ticket.id(), d, handover);
+            if (trace)
+                fprintf(stderr, "[extract] survey %llu driver %u: slot acquired\n", (unsigned long long)ticket.id(), d);
             {
+                std::lock_guard<std::mutex> lk(mu);
+                if (!started)
+                {
+                    started = true;
+                    t_first_slot = std::chrono::steady_clock::now();
+                }
+            }
+            for (;;)
+            {
+                uint32_t c = 0;
+                bool go = false;
+                {
+                    std::unique_lock<std::mutex> lk(mu);
+                    if (stagger)
+                        while (fail.empty() && next_chunk < n_chunks)
+                        {
+                            bool other = false;
+                            for (uint32_t o = 0; o < n_drivers; o++)
+                                if (o != d && in_first_phase[o])
+                                {
+                                    if (ochip_akaze_progress(ctxs[o]) != progress_at_start[o])
+                                        in_first_phase[o] = 0;
+                                    else
+                                        other = true;
+                                }
+                            if (!other)
+                                break;
+                            cv.wait_for(lk, std::chrono::milliseconds(1));
+                        }
+                    if (fail.empty() && next_chunk < n_chunks)
+                    {
+                        c = next_chunk++;
+                        go = true;
+                        if (stagger)
+                        {
+                            progress_at_start[d] = ochip_akaze_progress(dctx);
+                            in_first_phase[d] = 1;
+                        }
+                    }
+                }
+                if (!go)
+                    break; // (nothing left: the slot goes to the survey behind while this survey's other chunks still run)
+                if (c + 1 == n_chunks && handover == extract_slots::order::slot)
+                    ticket.retire(); // the last chunk is handed out: the survey behind may start wherever a slot is free
+                if (trace)
+                    fprintf(stderr, "[extract] survey %llu driver %u: chunk %u of %u\n", (unsigned long long)ticket.id(), d, c, n_chunks);
+                const int sb = slots.take_buffer(d); // (waits for a consumer - this survey's or the one before - if all three are in a tail)
+                const int which = BPS * (int)d + sb;
+                chunk_buffers &b = bufs[which];
+                int rc = OCHIP_OK;
+                if (!shape_buffer(dctx, slots.at(d, sb), b))
+                    rc = OCHIP_ENOMEM;
+                b.first = c * chunk;
+                b.n = std::min(chunk, n_images - b.first);
+                int wh[2];
+                const uint8_t *src = images_bgr + (size_t)b.first * image_bytes;
+                if (rc != OCHIP_OK)
+                    ;
+                else if (device_tail)
+                    rc = images_on_device ? ochip_akaze_features_dev(dctx, src, b.n, width, height, max_keypoints, nms_pixel_radius,
+                                                                     b.counts.data(), &b.lists, wh)
+                                          : ochip_akaze_features(dctx, src, b.n, width, height, max_keypoints, nms_pixel_radius,
+                                                                 b.counts.data(), &b.lists, wh);
+                else
+                    rc = images_on_device ? ochip_akaze_batch_dev(dctx, src, b.n, width, height, max_keypoints, b.kp, b.desc,
+                                                                  b.counts.data(), wh)
+                                          : ochip_akaze_batch(dctx, src, b.n, width, height, max_keypoints, b.kp, b.desc,
+                                                              b.counts.data(), wh);
                 std::unique_lock<std::mutex> lk(mu);
-                cv.wait(lk, [&] { return buffer_free[which] != 0; });
-                if (!fail.empty() || next_chunk >= n_chunks)
+                in_first_phase[d] = 0;
+                if (rc != OCHIP_OK)
+                {
+                    if (fail.empty())
+                        fail = std::string("ochip_akaze_batch: ") + ochip_last_error(dctx);
+                    if (trace)
+                        fprintf(stderr, "[extract] survey %llu driver %u: chunk %u failed (%s)\n", (unsigned long long)ticket.id(), d, c,
+                                ochip_last_error(dctx));
+                    lk.unlock();
+                    cv.notify_all();
+                    slots.return_buffer(d, sb);
+                    ticket.retire(); // no further chunk will be handed out
                     break;
-                c = next_chunk++;
-                buffer_free[which] = 0;
+                }
+                ready.push_back(which);
+                cv.notify_all();
             }
-            chunk_buffers &b = bufs[which];
-            b.first = c * chunk;
-            b.n = std::min(chunk, n_images - b.first);
-            int wh[2];
-            const uint8_t *src = images_bgr + (size_t)b.first * image_bytes;
-            int rc;
-            if (device_tail)
-                rc = images_on_device ? ochip_akaze_features_dev(dctx, src, b.n, width, height, max_keypoints, nms_pixel_radius,
-                                                                 b.counts.data(), &b.lists, wh)
-                                      : ochip_akaze_features(dctx, src, b.n, width, height, max_keypoints, nms_pixel_radius,
-                                                             b.counts.data(), &b.lists, wh);
-            else
-                rc = images_on_device ? ochip_akaze_batch_dev(dctx, src, b.n, width, height, max_keypoints, b.kp, b.desc,
-                                                              b.counts.data(), wh)
-                                      : ochip_akaze_batch(dctx, src, b.n, width, height, max_keypoints, b.kp, b.desc,
-                                                          b.counts.data(), wh);
-            std::unique_lock<std::mutex> lk(mu);
-            if (rc != OCHIP_OK)
-            {
-                if (fail.empty())
-                    fail = std::string("ochip_akaze_batch: ") + ochip_last_error(dctx);
-                buffer_free[which] = 1;
-                break;
-            }
-            ready.push_back(which);
-            cv.notify_all();
-            which = 2 * (int)d + ((which + 1) & 1);
         }
+        if (trace)
+            fprintf(stderr, "[extract] survey %llu driver %u: slot released\n", (unsigned long long)ticket.id(), d);
         std::unique_lock<std::mutex> lk(mu);
         drivers_done++;
         cv.notify_all();
     };
+    // (everything up to here - and in load_link_stream, the link ranges and the runner threads - runs while the survey before
+    // is still extracting; the drivers wait for their slots)
     std::vector<std::thread> drivers;
     for (uint32_t d = 0; d < n_drivers; d++)
         drivers.emplace_back(driver, d);
+    std::chrono::steady_clock::time_point t_last_final = t_enter;
 
     for (;;)
     {
@@ -577,15 +668,18 @@ bool extract_features_stream(ochip_ctx *ctx, const uint8_t *images_bgr, uint32_t
         }
         tail_cpu_seconds += cpu;
         const uint32_t chunk_first = b.first, chunk_n = b.n;
-        {
-            std::unique_lock<std::mutex> lk(mu);
-            buffer_free[which] = 1;
-            cv.notify_all();
-        }
+        slots.return_buffer((uint32_t)(which / BPS), which % BPS);
+        t_last_final = std::chrono::steady_clock::now();
         on_chunk(chunk_first, chunk_n, done.data()); // the device is already busy with the next chunks
     }
     for (auto &t : drivers)
         t.join();
+    ticket.retire(); // (OCHIP_EXTRACT_HANDOVER=survey: only now)
+    if (timing)
+    {
+        timing->wait_seconds = std::chrono::duration<double>(t_first_slot - t_enter).count();
+        timing->extract_seconds = std::chrono::duration<double>(std::max(t_last_final, t_first_slot) - t_first_slot).count();
+    }
     if (ochip_verbose("extract"))
     {
         fprintf(stderr, "[extract] %u images: host tail %.3f thread-seconds of wall time (%.2f ms per image)\n", n_images,
@@ -597,7 +691,6 @@ bool extract_features_stream(ochip_ctx *ctx, const uint8_t *images_bgr, uint32_t
         fprintf(stderr, "[extract] cumulative CPU seconds of the tail: ordering %.3f, NMS %.3f, feature records %.3f, total %.3f; images with tied responses %.0f\n",
                 g_tail_prof[0], g_tail_prof[1], g_tail_prof[2], g_tail_prof[3], g_tail_prof[4]);
     }
-    release();
     if (!fail.empty())
     {
         if (error)

@@ -30,13 +30,23 @@ std::vector<extracted_features> extract_features_batch(ochip_ctx *ctx, const uin
                                                        int width, int height, uint32_t max_keypoints, std::string *error,
                                                        bool images_on_device = false);
 
+// What a survey's extraction took: from entering extract_features_stream to its first slot (the wait for the surveys before
+// it, host/extract_slots.hpp) and from there to its last chunk's features being final.  With the hand-over per slot two
+// surveys' extract_seconds overlap by the hand-over window: their sum can exceed the wall time.
+struct extract_timing
+{
+    double wait_seconds = 0, extract_seconds = 0;
+};
+
 // The same, streaming: `on_chunk(first, count, features)` is called (from the calling thread, chunks in completion
 // order) as soon as the features of images [first, first + count) are final, while later chunks are still on the
 // device; `features` points at the `count` results, which the callback may move from.  host_threads caps the OpenMP
-// team of the host tail (0 = the whole team).  Returns false and sets *error on a device error.
+// team of the host tail (0 = the whole team).  Returns false and sets *error on a device error.  Calls on the same root
+// context from several threads are served in arrival order: the extraction contexts pass from one call to the next one by
+// one (host/extract_slots.hpp; OCHIP_EXTRACT_HANDOVER=survey: all at once, when the call before has finished).
 bool extract_features_stream(ochip_ctx *ctx, const uint8_t *images_bgr, uint32_t n_images, int width, int height,
                              uint32_t max_keypoints, bool images_on_device, int host_threads,
                              const std::function<void(uint32_t, uint32_t, extracted_features *)> &on_chunk,
-                             std::string *error);
+                             std::string *error, extract_timing *timing = nullptr);
 
 } // namespace opencalibration_amd

@@ -58,19 +58,16 @@ std::vector<owned_pair> pair_owners(const std::vector<NodeLinks> &links)
 }
 
 // Surveys in flight.  Two calls may overlap (two host threads, a graph each, the same device context): the second one's
-// extraction starts when the first one's has finished, and runs beside the first one's remaining link ranges - the tail of
-// a survey's link stage (its last ranges can only start once its last images are extracted, and RANSAC is a chain of
-// dependent steps per pair that leaves most of the device idle) then no longer stands alone on the device.  This is the
-// reference's own schedule: its pipeline runs the load runners of one batch beside the link runners of the batch before
-// (Pipeline::Impl::initial_processing, src/pipeline/pipeline.cpp:543-560).  The extraction contexts (ctx and its first
-// siblings) are used by one survey at a time - the gate below -, the link runners of alternating calls use two different
-// sets of sibling contexts.
+// extraction follows the first one's context by context - a launch sequence of the second survey starts on an extraction
+// context as soon as the first survey has no chunk left for it (host/extract_slots.hpp, inside extract_features_stream) - and
+// runs beside the first one's remaining link ranges: the tail of a survey's link stage (its last ranges can only start once
+// its last images are extracted, and RANSAC is a chain of dependent steps per pair that leaves most of the device idle) then
+// no longer stands alone on the device.  This is the reference's own schedule: its pipeline runs the load runners of one
+// batch beside the link runners of the batch before (Pipeline::Impl::initial_processing, src/pipeline/pipeline.cpp:543-560).
+// The link runners of alternating calls use two different sets of sibling contexts.
 namespace
 {
-std::mutex g_extract_gate_mu;
-std::condition_variable g_extract_gate_cv;
-bool g_extract_gate_busy = false;
-thread_local double g_last_gate_wait = 0; // seconds the calling thread's last load_link_stream waited at the gate
+thread_local double g_last_gate_wait = 0; // seconds the calling thread's last load_link_stream waited for its first extraction slot
 // The two sets of link-runner contexts (siblings 4.. and 13.. of ctx): a call OWNS one from its first runner to its last
 // (a free-list, not the parity of a call counter: calls need not finish in the order they started, and a third overlapping
 // call waits here instead of driving a context set that is still in use).
@@ -98,29 +95,6 @@ struct runner_lane
         g_lane_cv.notify_all();
     }
 };
-struct extract_gate
-{
-    bool held = false;
-    void acquire()
-    {
-        std::unique_lock<std::mutex> lk(g_extract_gate_mu);
-        g_extract_gate_cv.wait(lk, [] { return !g_extract_gate_busy; });
-        g_extract_gate_busy = true;
-        held = true;
-    }
-    void release()
-    {
-        if (!held)
-            return;
-        {
-            std::lock_guard<std::mutex> lk(g_extract_gate_mu);
-            g_extract_gate_busy = false;
-        }
-        g_extract_gate_cv.notify_all();
-        held = false;
-    }
-    ~extract_gate() { release(); }
-};
 } // namespace
 
 bool load_link_stream(och_graph *g, ochip_ctx *ctx, LinkStage &link, const std::vector<size_t> &ids, uint32_t first,
@@ -128,21 +102,16 @@ bool load_link_stream(och_graph *g, ochip_ctx *ctx, LinkStage &link, const std::
                       bool images_on_device, const std::vector<owned_pair> &pairs, double *total_out, double *sparse_out,
                       double *t_extract_done)
 {
-    using clk = std::chrono::steady_clock;
-    // (declared before the gate: destroyed after it - and after every runner thread below has been joined)
+    // (destroyed after every runner thread below has been joined)
     runner_lane lane_guard;
     lane_guard.acquire();
     const int lane = lane_guard.lane;
-    extract_gate gate;
-    const auto t_gate = clk::now();
-    // (released when this survey's last chunk is extracted; on every return path by the destructor.  Measured in round 6 for
-    // views that come from HOST memory - bound by the PCIe link, not the device - without the gate, two surveys extracting side
-    // by side: 1 271 / 1 336 images/s against 1 306 / 1 275 with it, nothing in it; OCHIP_EXTRACT_GATE=0 turns it off)
-    const char *gate_env = std::getenv("OCHIP_EXTRACT_GATE");
-    if (!(gate_env && gate_env[0] == '0'))
-        gate.acquire();
-    const auto t_begin = clk::now();
-    g_last_gate_wait = std::chrono::duration<double>(t_begin - t_gate).count();
+    // Nothing waits for the survey before here: the ranges and the runner threads below are set up while it is still
+    // extracting, and extract_features_stream orders the surveys itself.  (Measured in round 6 for views that come from HOST
+    // memory - bound by the PCIe link, not the device - with no ordering, two surveys extracting side by side: 1 271 / 1 336
+    // images/s against 1 306 / 1 275 with the gate of that round, nothing in it; OCHIP_EXTRACT_GATE=0 still turns the
+    // ordering off.)
+    g_last_gate_wait = 0;
     const auto &links = link.links();
     // ---- ranges of links and the images (of this call's block) each one waits for
     std::unordered_map<size_t, uint32_t> image_of; // node id -> image index within the block
@@ -234,6 +203,7 @@ bool load_link_stream(och_graph *g, ochip_ctx *ctx, LinkStage &link, const std::
     // ---- extraction; every finished chunk fills its nodes, prepares their 40 px subsets and releases the ranges
     //      that were only waiting for these images
     double total = 0, sparse = 0;
+    extract_timing timing;
     const bool ok = extract_features_stream(
         ctx, images_bgr, count, width, height, max_keypoints, images_on_device, tail_threads,
         [&](uint32_t chunk_first, uint32_t chunk_count, extracted_features *f) {
@@ -257,10 +227,10 @@ bool load_link_stream(och_graph *g, ochip_ctx *ctx, LinkStage &link, const std::
                         ready.push_back(k);
             cv.notify_all();
         },
-        &g->error);
-    gate.release(); // the next survey may extract while this one's remaining ranges are linked
+        &g->error, &timing);
+    g_last_gate_wait = timing.wait_seconds;
     if (t_extract_done)
-        *t_extract_done = std::chrono::duration<double>(clk::now() - t_begin).count();
+        *t_extract_done = timing.extract_seconds; // first slot acquired -> last chunk's features final
     {
         std::lock_guard<std::mutex> lk(mu);
         no_more = true; // runners drain what is queued, then stop
@@ -363,7 +333,7 @@ extern "C" int och_graph_load_link_images(och_graph *g, ochip_ctx *ctx, const ui
     }
     if (stage_seconds2)
     {
-        stage_seconds2[0] = t_extract_done;            // until the last chunk's features were final
+        stage_seconds2[0] = t_extract_done;            // first extraction slot acquired -> the last chunk's features final
         stage_seconds2[1] = seconds_since(t_begin) - gate_wait; // until the graph was linked (not counting the wait for the survey before to finish extracting)
     }
     return 0;
