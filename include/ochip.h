@@ -302,6 +302,14 @@ extern "C"
                                      const ochip_ransac_match *matches, uint64_t total_matches, uint32_t rounds,
                                      double inlier_threshold, ochip_ransac_result *results, uint8_t *inliers);
 
+    /* Test seam: homography_model::fit (homography_model.cpp:19-50) of n minimal samples through the two device routes that
+     * have no entry of their own.  xy16: per sample four correspondences x {x, y, x', y'}, already divided by z.  route 0: one
+     * wavefront per sample through the wave-cooperative 9 x 9 factorisation (what the RANSAC loop's normal path runs); route 1:
+     * the fast-forward's lane-private fit, 32 samples per wavefront in its LDS layout.  H9 / Hinv9: n x 9 row-major;
+     * degenerate[s] = checkSampleDegeneracy of sample s (the fit runs either way). */
+    int ochip_debug_homography_fit4(ochip_ctx *ctx, int route, const double *xy16, uint32_t n, double *H9, double *Hinv9,
+                                    uint8_t *degenerate);
+
     /* ---- relax: ground-plane bundle adjustment (replaces ceres::Solver::Solve on the problem
      *      RelaxProblem::setupGroundPlaneProblem builds, src/relax/relax_problem.cpp:61-81,1390-1420) ---- */
     typedef struct ochip_relax_problem ochip_relax_problem;

@@ -13,6 +13,11 @@ NO_SECOND = 0xFFFF
 
 PAIR_DTYPE = np.dtype([("image_1", np.uint32), ("image_2", np.uint32)])
 MATCH_DTYPE = np.dtype([("best_k", np.uint32), ("best_count", np.uint16), ("second_count", np.uint16)])
+RANSAC_JOB_DTYPE = np.dtype([("image_1", np.uint32), ("image_2", np.uint32), ("n", np.uint32), ("rng_state", np.uint32),
+                             ("match_offset", np.uint64), ("eval_offset", np.uint64)])
+RANSAC_MATCH_DTYPE = np.dtype([("k1", np.uint32), ("k2", np.uint32), ("count", np.uint16), ("reserved", np.uint16)])
+RANSAC_RESULT_DTYPE = np.dtype([("H", np.float64, (9,)), ("score", np.float64), ("iterations", np.uint32), ("n_inliers", np.uint32),
+                                ("improvements", np.uint32), ("reserved", np.uint32)])
 
 # every symbol include/ochip.h declares; tests check that the built library exports all of them
 EXPORTS = [
@@ -31,7 +36,7 @@ EXPORTS = [
     "ochip_relaxp_problem_create", "ochip_relaxp_problem_destroy", "ochip_relaxp_set_structure_only", "ochip_relaxp_solve",
     "ochip_relaxp_get_state",
     "ochip_profile_reset", "ochip_profile_get", "ochip_match_work", "ochip_relax_work", "ochip_relax_memory", "ochip_work_counters",
-    "ochip_debug_fp64", "ochip_debug_std_sort", "ochip_debug_lm_step", "ochip_match_sort", "ochip_ransac_homography_batch_sorted", "ochip_edge_lists",
+    "ochip_debug_fp64", "ochip_debug_std_sort", "ochip_debug_lm_step", "ochip_debug_homography_fit4", "ochip_match_sort", "ochip_ransac_homography_batch_sorted", "ochip_edge_lists",
     "ochip_dense_index_create", "ochip_dense_index_destroy", "ochip_dense_match", "ochip_dense_link", "ochip_dense_triangulate",
     "ochip_rccl_unique_id", "ochip_rccl_comm_create", "ochip_rccl_comm_destroy", "ochip_rccl_comm_stats",
     "ochip_rccl_relax_exchange",
@@ -185,6 +190,9 @@ def load():
         L.ochip_debug_fp64.argtypes = [vp, i32, vp, vp, C.c_size_t, vp]
         L.ochip_debug_std_sort.argtypes = [vp, vp, vp, vp, u32, vp, vp, vp]
         L.ochip_debug_lm_step.argtypes = [vp, i32, vp, vp, vp, vp, C.c_double, vp, i32, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp]
+        L.ochip_debug_homography_fit4.argtypes = [vp, i32, vp, u32, vp, vp, vp]
+        L.ochip_upload_batch.argtypes = [vp, u32, vp, vp, vp, vp]
+        L.ochip_refit_homography_batch.argtypes = [vp, vp, u32, vp, u64, u32, C.c_double, vp, vp]
         L.ochip_akaze_batch.argtypes = [vp, vp, u32, i32, i32, u32, vp, vp, vp, vp]
         L.ochip_feature_lists_from_keypoints.argtypes = [vp, vp, vp, vp, u32, u32, i32, i32, C.c_double, C.c_double, vp]
         L.ochip_akaze_batch_dev.argtypes = [vp, vp, u32, i32, i32, u32, vp, vp, vp, vp]
@@ -448,6 +456,43 @@ class Context:
                     "ochip_debug_lm_step")
         return dict(x=x[:n], y=y[:n], L=L, W=W, scal1=s1.value, fail=int(info[0]), order=int(info[1]), slots=int(info[2]),
                     tiles=int(info[3]), claims=int(info[4]), regions=int(info[5]), back=int(info[6]))
+
+    def upload_batch(self, counts, desc, xy, models8):
+        """ochip_upload_batch: image i owns counts[i] consecutive rows of desc (x 8 u64) and xy (x 2 f64); models8 n x 8."""
+        counts = np.ascontiguousarray(counts, np.uint32)
+        total = int(counts.sum())
+        desc = np.ascontiguousarray(desc, np.uint64).reshape(-1, 8)
+        xy = np.ascontiguousarray(xy, np.float64).reshape(-1, 2)
+        models8 = np.ascontiguousarray(models8, np.float64).reshape(-1, 8)
+        assert len(desc) == total and len(xy) == total and len(models8) == len(counts)
+        self._check(self.L.ochip_upload_batch(self.h, len(counts), counts.ctypes.data, desc.ctypes.data if total else None,
+                                              xy.ctypes.data if total else None, models8.ctypes.data), "ochip_upload_batch")
+
+    def refit_homography(self, jobs, matches, flags, rounds, threshold):
+        """ochip_refit_homography_batch on uploaded keypoints: `rounds` times fitInliers + evaluate per job, starting from
+        flags.  jobs: RANSAC_JOB_DTYPE, matches: RANSAC_MATCH_DTYPE, flags: one byte per match.  Returns (results
+        [RANSAC_RESULT_DTYPE], the flags of the last evaluate)."""
+        jobs = np.ascontiguousarray(jobs, RANSAC_JOB_DTYPE)
+        matches = np.ascontiguousarray(matches, RANSAC_MATCH_DTYPE)
+        out = np.ascontiguousarray(flags, np.uint8).copy()
+        assert len(out) == len(matches)
+        res = np.zeros(len(jobs), RANSAC_RESULT_DTYPE)
+        total = len(matches)
+        self._check(self.L.ochip_refit_homography_batch(self.h, jobs.ctypes.data, len(jobs), matches.ctypes.data if total else None,
+                                                        total, int(rounds), float(threshold), res.ctypes.data,
+                                                        out.ctypes.data if total else None), "ochip_refit_homography_batch")
+        return res, out
+
+    def debug_homography_fit4(self, xy16, route):
+        """ochip_debug_homography_fit4: homography_model::fit of the minimal samples xy16 (n x 16: four correspondences x
+        (x, y, x', y'), divided by z).  route 0: the wave-cooperative 9 x 9 factorisation, 1: the fast-forward's lane fit.
+        Returns (H [n, 3, 3], Hinv [n, 3, 3], degenerate [n] bool)."""
+        xy16 = np.ascontiguousarray(xy16, np.float64).reshape(-1, 16)
+        n = len(xy16)
+        H, Hi, deg = np.zeros((max(n, 1), 9)), np.zeros((max(n, 1), 9)), np.zeros(max(n, 1), np.uint8)
+        self._check(self.L.ochip_debug_homography_fit4(self.h, int(route), xy16.ctypes.data if n else None, n, H.ctypes.data,
+                                                       Hi.ctypes.data, deg.ctypes.data), "ochip_debug_homography_fit4")
+        return H[:n].reshape(-1, 3, 3), Hi[:n].reshape(-1, 3, 3), deg[:n].astype(bool)
 
     def relaxg_evaluate(self, scene, structure_only=False):
         """One evaluation of a general-engine relax problem (ochip_relaxg_problem_create, ochip_relaxg_evaluate, destroy):

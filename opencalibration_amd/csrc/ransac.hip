@@ -16,7 +16,9 @@
 // scores, inlier sets and H are bit-identical to the CPU restatement; pairs are independent, so the
 // chip is filled with thousands of resident waves.  All arithmetic is fp64 with -ffp-contract=off
 // (the reference is built without FMA); device division and sqrt are correctly rounded
-// (tests/test_gpu_fp64.py).
+// (tests/test_gpu_fp64.py).  The three factorisations (full_piv_lu_solve9, regen_lu_solve9, lane_fit) are held at their
+// edges against the oracle bit for bit and against a long-double restatement through ochip_refit_homography_batch and the
+// seam ochip_debug_homography_fit4 (tests/test_gpu_homography_fit.py).
 //
 // libstdc++ pieces on the result path: std::default_random_engine (= minstd_rand0) and
 // std::uniform_int_distribution<size_t> are re-implemented here exactly (bits/random.tcc,
@@ -1010,6 +1012,23 @@ __device__ __forceinline__ void fit_inliers(const pair_data &pd, uint32_t n_in, 
     model_from_solution(model, sol);
 }
 
+// checkSampleDegeneracy (homography_model.cpp:120-136) on measurement1.hnormalized(): any three of the four points within
+// 1e-10 of a line
+__device__ __forceinline__ bool sample_degenerate(const double (&px)[4], const double (&py)[4])
+{
+    bool degenerate = false;
+    for (int a = 0; a < 4; a++)
+        for (int b = a + 1; b < 4; b++)
+            for (int c = b + 1; c < 4; c++)
+            {
+                const double v1x = px[b] - px[a], v1y = py[b] - py[a];
+                const double v2x = px[c] - px[a], v2y = py[c] - py[a];
+                if (fabs(v1x * v2y - v1y * v2x) < 1e-10)
+                    degenerate = true;
+            }
+    return degenerate;
+}
+
 // four distinct positions of the sampling pool; distinct positions are distinct correspondences because the PROSAC
 // order is a permutation, so the uniqueness test of ransac.cpp:118-150 needs no loaded value and the four
 // sorted_idx reads go out together
@@ -1277,15 +1296,8 @@ __device__ uint32_t fast_forward(const pair_data &pd, const uint32_t *__restrict
             qx[j] = pd.x2[s4[j]];
             qy[j] = pd.y2[s4[j]];
         }
-        for (int a = 0; a < 4; a++)
-            for (int b = a + 1; b < 4; b++)
-                for (int c = b + 1; c < 4; c++)
-                {
-                    const double v1x = px[b] - px[a], v1y = py[b] - py[a];
-                    const double v2x = px[c] - px[a], v2y = py[c] - py[a];
-                    if (fabs(v1x * v2y - v1y * v2x) < 1e-10)
-                        live = false; // degenerate: the iteration ends here
-                }
+        if (sample_degenerate(px, py))
+            live = false; // the iteration ends here
         if (live)
             lane_fit(AQs + lane, px, py, qx, qy, m);
     }
@@ -1521,17 +1533,7 @@ template <int OCC> __global__ __launch_bounds__(W, OCC) __attribute__((amdgpu_nu
             qx[j] = pd.x2[s4[j]];
             qy[j] = pd.y2[s4[j]];
         }
-        bool degenerate = false;
-        for (int a = 0; a < 4; a++)
-            for (int b = a + 1; b < 4; b++)
-                for (int c = b + 1; c < 4; c++)
-                {
-                    const double v1x = px[b] - px[a], v1y = py[b] - py[a];
-                    const double v2x = px[c] - px[a], v2y = py[c] - py[a];
-                    if (fabs(v1x * v2y - v1y * v2x) < 1e-10)
-                        degenerate = true;
-                }
-        if (degenerate)
+        if (sample_degenerate(px, py))
             continue;
 
         // ---- fit (homography_model.cpp:19-50): 9x9 DLT system in LDS
@@ -1714,6 +1716,55 @@ __global__ __launch_bounds__(W, 2) __attribute__((amdgpu_num_vgpr(248))) void re
     res.reserved = 0;
     if (lane == 0)
         results[job_id] = res;
+}
+
+// ---- test seam: homography_model::fit of given minimal samples through the two device routes that have no entry of their
+//      own (include/ochip.h: ochip_debug_homography_fit4, tests/test_gpu_homography_fit.py).  ROUTE 0: one wavefront per
+//      sample, the 9 x 9 system in LDS and the wave-cooperative full_piv_lu_solve9 - the statements of the RANSAC loop's
+//      normal path; ROUTE 1: FB samples per wavefront, lane_fit on the fast-forward's interleaved LDS layout.  The fit runs
+//      whatever checkSampleDegeneracy says (the loop would skip the sample); its answer is returned beside it.
+template <int ROUTE>
+__global__ __launch_bounds__(W) void debug_fit4_kernel(const double *__restrict__ xy16, uint32_t n, double *__restrict__ H9,
+                                                       double *__restrict__ Hinv9, uint8_t *__restrict__ degenerate_out)
+{
+    __shared__ double LDS[ROUTE == 0 ? 81 : 81 * FB];
+    const int lane = threadIdx.x;
+    const uint32_t s = ROUTE == 0 ? blockIdx.x : blockIdx.x * FB + (uint32_t)lane;
+    const bool active = s < n && (ROUTE == 0 || lane < FB);
+    double px[4], py[4], qx[4], qy[4];
+    for (int j = 0; j < 4; j++)
+    {
+        px[j] = active ? xy16[(size_t)s * 16 + 4 * j] : 0.0;
+        py[j] = active ? xy16[(size_t)s * 16 + 4 * j + 1] : 0.0;
+        qx[j] = active ? xy16[(size_t)s * 16 + 4 * j + 2] : 0.0;
+        qy[j] = active ? xy16[(size_t)s * 16 + 4 * j + 3] : 0.0;
+    }
+    const bool degenerate = sample_degenerate(px, py);
+    model_t model;
+    set_nan(model);
+    if (ROUTE == 0)
+    {
+        if (!active) // (wave-uniform: the grid is one block per sample)
+            return;
+        if (lane < 4)
+            write_dlt_rows(LDS, 9, 2 * lane, px[lane], py[lane], qx[lane], qy[lane]);
+        if (lane < 9)
+            LDS[lane * 9 + 8] = lane == 8 ? 1.0 : 0.0;
+        double sol[9];
+        full_piv_lu_solve9(LDS, 9, sol);
+        model_from_solution(model, sol);
+    }
+    else if (active)
+        lane_fit(LDS + lane, px, py, qx, qy, model);
+    if (active && (ROUTE == 1 || lane == 0))
+    {
+        for (int i = 0; i < 9; i++)
+        {
+            H9[(size_t)s * 9 + i] = model.H[i];
+            Hinv9[(size_t)s * 9 + i] = model.Hi[i];
+        }
+        degenerate_out[s] = degenerate ? 1 : 0;
+    }
 }
 
 // ---- a9: the fundamental- and essential-matrix models (src/model_inliers/fundamental_matrix_model.cpp:12-217,
@@ -2966,6 +3017,39 @@ int ochip_refit_homography_batch(ochip_ctx *ctx, const ochip_ransac_job *jobs, u
     return OCHIP_OK;
 }
 
+
+int ochip_debug_homography_fit4(ochip_ctx *ctx, int route, const double *xy16, uint32_t n, double *H9, double *Hinv9,
+                                uint8_t *degenerate)
+{
+    if (!ctx)
+        return OCHIP_EINVAL;
+    if (route != 0 && route != 1)
+        return ochip_fail(ctx, OCHIP_EINVAL, "ochip_debug_homography_fit4: route %d", route);
+    if (n == 0)
+        return OCHIP_OK;
+    if (!xy16 || !H9 || !Hinv9 || !degenerate)
+        return ochip_fail(ctx, OCHIP_EINVAL, "ochip_debug_homography_fit4: NULL argument");
+    OCHIP_HIP(ctx, hipSetDevice(ctx->device));
+    // one allocation: the samples (16 doubles each), H and H^-1 (9 each), the degeneracy flags
+    const size_t in_bytes = (size_t)n * 16 * 8, m_bytes = (size_t)n * 9 * 8;
+    int rc = ochip_ensure(ctx, &ctx->scratch_dev[4], &ctx->scratch_cap[4], in_bytes + 2 * m_bytes + n);
+    if (rc)
+        return rc;
+    double *xy_dev = (double *)ctx->scratch_dev[4], *H_dev = xy_dev + (size_t)n * 16, *Hi_dev = H_dev + (size_t)n * 9;
+    uint8_t *deg_dev = (uint8_t *)(Hi_dev + (size_t)n * 9);
+    OCHIP_HIP(ctx, hipMemcpyAsync(xy_dev, xy16, in_bytes, hipMemcpyHostToDevice, ctx->stream));
+    if (route == 0)
+        hipLaunchKernelGGL(debug_fit4_kernel<0>, dim3(n), dim3(W), 0, ctx->stream, (const double *)xy_dev, n, H_dev, Hi_dev, deg_dev);
+    else
+        hipLaunchKernelGGL(debug_fit4_kernel<1>, dim3((n + FB - 1) / FB), dim3(W), 0, ctx->stream, (const double *)xy_dev, n, H_dev,
+                           Hi_dev, deg_dev);
+    OCHIP_HIP(ctx, hipGetLastError());
+    OCHIP_HIP(ctx, hipMemcpyAsync(H9, H_dev, m_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    OCHIP_HIP(ctx, hipMemcpyAsync(Hinv9, Hi_dev, m_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    OCHIP_HIP(ctx, hipMemcpyAsync(degenerate, deg_dev, n, hipMemcpyDeviceToHost, ctx->stream));
+    OCHIP_HIP(ctx, ochip_stream_wait(ctx, ctx->stream));
+    return OCHIP_OK;
+}
 
 int ochip_ransac_epipolar_batch(ochip_ctx *ctx, int model, const ochip_epipolar_job *jobs, uint32_t n_jobs, const double *corr6,
                                 const uint32_t *sorted_idx, uint64_t total, const uint32_t *eval_order, uint64_t eval_total,

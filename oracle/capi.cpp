@@ -144,6 +144,12 @@ void oc_homography_fit4(const double *corr, size_t M, const uint64_t *idx4, doub
     std::memcpy(Hinv, h.homography_inverse.m, 72);
 }
 
+int oc_homography_check_sample_degeneracy(const double *corr, size_t M, const uint64_t *idx4)
+{
+    auto c = make_corrs(corr, M);
+    return homography_model::checkSampleDegeneracy(c, {idx4[0], idx4[1], idx4[2], idx4[3]}) ? 1 : 0;
+}
+
 void oc_homography_fit_inliers(const double *corr, size_t M, const uint8_t *inl, double *H, double *Hinv)
 {
     auto c = make_corrs(corr, M);

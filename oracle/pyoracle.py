@@ -42,6 +42,8 @@ def lib():
         L.oc_image_to_3d.argtypes = [f64p, C.c_size_t, f64p, f64p]
         L.oc_image_from_3d.argtypes = [f64p, C.c_size_t, f64p, f64p]
         L.oc_homography_fit4.argtypes = [f64p, C.c_size_t, u64p, f64p, f64p]
+        L.oc_homography_check_sample_degeneracy.restype = C.c_int
+        L.oc_homography_check_sample_degeneracy.argtypes = [f64p, C.c_size_t, u64p]
         L.oc_homography_fit_inliers.argtypes = [f64p, C.c_size_t, u8p, f64p, f64p]
         L.oc_homography_evaluate.restype = C.c_double
         L.oc_homography_evaluate.argtypes = [f64p, C.c_size_t, f64p, f64p, u8p, C.c_void_p]
@@ -267,6 +269,10 @@ def fit4(corr, idx4):
     H, Hi = np.zeros((3, 3)), np.zeros((3, 3))
     lib().oc_homography_fit4(corr, len(corr), np.asarray(idx4, np.uint64), H, Hi)
     return H, Hi
+
+
+def check_sample_degeneracy(corr, idx4):
+    return bool(lib().oc_homography_check_sample_degeneracy(corr, len(corr), np.asarray(idx4, np.uint64)))
 
 
 def fit_inliers(corr, inl):
