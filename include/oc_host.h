@@ -461,6 +461,46 @@ extern "C"
     void och_blend_pyr(int up, int32_t channels, int32_t w, int32_t h, int32_t W, int32_t H, const float *src, float *out);
     void och_blend_math(int mode, size_t n, const float *in, void *out);
 
+    /* ---- colour balance between the layered render and the blend (opencalibration_amd/csrc/host/color_balance.cpp;
+     * solveColorBalance, src/ortho/color_balance.cpp, and its caller Pipeline::Impl::color_balance,
+     * src/pipeline/pipeline.cpp:987-1018) ------------------------------------------------------------------------------
+     * och_color_balance_solve: collects the camera and model ids of corr (och_ortho_layers_render's records), solves the
+     * radiometric parameters - ctx != NULL: ochip_color_balance_solve on its device; NULL: the CPU route, same arithmetic
+     * and trust-region rules with a dense Cholesky, at most 4096 unknowns (6 per camera + 3 per model) - and removes the
+     * gauge: over the solved cameras that have a position (the explicit list position_ids / position_xy [n][2] first,
+     * else graph node id -> payload.position x, y; g may be NULL; an id without either is skipped), at least 3 of them,
+     * the least-squares plane a x + b y + c per Lab channel is subtracted from their offsets; the minimum-norm solution
+     * when the positions are collinear (singular values at or below max(n, 3) * 2^-52 * the largest count as zero).
+     * Outputs in ascending id order, the blend's layout: cam_ids_out, color6_out [n][6] = lab_offset 3, brdf, slope 2;
+     * model_ids_out, vig3_out [n][3]; *n_cams / *n_models always receive the counts (a capacity too small: -1).
+     * summary4 = {success, final_cost, num_iterations (summary.iterations.size()), termination (OCHIP_RELAX_*)}.
+     * n_corr == 0: success 0, empty tables, nothing launched.  A correspondence with camera_id_a == camera_id_b is
+     * refused (-1): the reference's Ceres aborts on a duplicate parameter block.  -1 + och_color_balance_last_error().
+     * och_color_balance_evaluate (tests): cost, dense J'J (n x n) and J'r (n), n = 6 n_cams + 3 n_models, at the given
+     * parameters (ids sorted and unique), cam_col / model_col the first unknown of every camera / model; ctx as above.
+     * Returns 0, 1 when a residual is not finite, -1 on an error.
+     * och_color_balance_evaluate_plan (tests): the same evaluation as the DEVICE forms it, run on the host - the plan of
+     * opencalibration_amd/csrc/color_balance_plan.hpp (chunks, the order of the unknowns, the owners' record lists) and
+     * the kernels' own arithmetic in the kernels' order, so the device's result equals it bit for bit; cam_col / model_col
+     * in the plan's order; layout4 (may be NULL) = {tail_begin, regions, separator cameras, chunks}.
+     * och_color_balance_remove_gauge: the gauge step alone on n positions xy [n][2] and offsets3 [n][3] (in place; n < 3:
+     * untouched); returns the rank used. */
+    int och_color_balance_solve(const och_graph *g, ochip_ctx *ctx, const ochip_color_corr *corr, size_t n_corr,
+                                size_t n_positions, const uint64_t *position_ids, const double *position_xy,
+                                size_t cam_capacity, uint64_t *cam_ids_out, double *color6_out, size_t *n_cams,
+                                size_t model_capacity, uint32_t *model_ids_out, double *vig3_out, size_t *n_models,
+                                double *summary4);
+    int och_color_balance_evaluate(ochip_ctx *ctx, const ochip_color_corr *corr, size_t n_corr, size_t n_cams,
+                                   const uint64_t *cam_ids, const double *color6, size_t n_models, const uint32_t *model_ids,
+                                   const double *vig3, double *cost, double *JtJ, double *Jtr, int32_t *cam_col,
+                                   int32_t *model_col);
+    int och_color_balance_evaluate_plan(const ochip_color_corr *corr, size_t n_corr, size_t n_cams, const uint64_t *cam_ids,
+                                        const double *color6, size_t n_models, const uint32_t *model_ids, const double *vig3,
+                                        double *cost, double *JtJ, double *Jtr, int32_t *cam_col, int32_t *model_col,
+                                        int32_t *layout4);
+    int och_color_balance_remove_gauge(size_t n, const double *xy, double *offsets3);
+    const char *och_color_balance_last_error(void);
+
 #ifdef __cplusplus
 }
 #endif

@@ -807,6 +807,30 @@ extern "C"
     int ochip_laplacian_blend(ochip_ctx *ctx, int32_t num_layers, int32_t rows, int32_t cols, int32_t pyramid_levels,
                               const float *lab, const float *weight, uint8_t *bgra_out);
 
+    /* ---- colour balance between the layered render and the blend (solveColorBalance, src/ortho/color_balance.cpp;
+     * opencalibration_amd/csrc/color_balance.hpp) ----
+     * The problem: per camera id lab_offset[3], brdf, slope[2], per model id three vignetting coefficients, all starting
+     * at 0; per correspondence three residuals under HuberLoss(5) (RadiometricMatchCost and its shared-model variant are
+     * one formula), priors of weight 0.1 sqrt(max(1, appearances)) on every unknown; max_num_iterations 20, function /
+     * gradient / parameter tolerance 1e-4 / 1e-6 / 1e-4, initial trust-region radius 1e4, Ceres' defaults otherwise.
+     * corr (host, n_corr > 0): the records ochip_ortho_layers writes; cam_ids, model_ids (host): sorted, unique, holding
+     * every id the correspondences name.  A correspondence whose camera_id_a == camera_id_b is refused with OCHIP_EINVAL:
+     * the reference's ceres::Problem aborts on a residual block that names one parameter block twice.
+     * cam6_out [n_cams][6], vig3_out [n_models][3] in the tables' order, BEFORE the gauge removal (the host library's,
+     * och_color_balance_solve).  summary as ochip_relax_solve's: success = termination != OCHIP_RELAX_FAILURE; a
+     * non-finite observation fails at iteration 0 (iterations 0, the parameters stay 0).  Two solves of one input are
+     * bit-identical. */
+    int ochip_color_balance_solve(ochip_ctx *ctx, const ochip_color_corr *corr, uint64_t n_corr, const uint64_t *cam_ids,
+                                  uint32_t n_cams, const uint32_t *model_ids, uint32_t n_models, double *cam6_out,
+                                  double *vig3_out, ochip_relax_summary *summary);
+    /* One evaluation at the given parameters for tests: total cost, and (when not NULL) the dense J'J (n x n) and J'r (n)
+     * in the library's unknown order, n = 6 n_cams + 3 n_models into *n_out; cam_col [n_cams], model_col [n_models]
+     * receive the first unknown of every camera / model.  Returns 0, 1 when a residual is not finite, or a negative code. */
+    int ochip_color_balance_evaluate(ochip_ctx *ctx, const ochip_color_corr *corr, uint64_t n_corr, const uint64_t *cam_ids,
+                                     uint32_t n_cams, const uint32_t *model_ids, uint32_t n_models, const double *cam6,
+                                     const double *vig3, double *cost, int32_t *n_out, double *JtJ, double *Jtr,
+                                     int32_t *cam_col, int32_t *model_col);
+
 #ifdef __cplusplus
 }
 #endif

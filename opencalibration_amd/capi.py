@@ -42,6 +42,7 @@ EXPORTS = [
     "ochip_rccl_relax_exchange",
     "ochip_ortho_mesh_create", "ochip_ortho_mesh_destroy", "ochip_ortho_dsm", "ochip_ortho_thumbnail", "ochip_ortho_layers",
     "ochip_ortho_blend", "ochip_laplacian_blend",
+    "ochip_color_balance_solve", "ochip_color_balance_evaluate",
 ]
 
 _lib = None
@@ -204,6 +205,8 @@ def load():
         L.ochip_ortho_mesh_destroy.argtypes = [vp]
         L.ochip_ortho_mesh_destroy.restype = None
         L.ochip_laplacian_blend.argtypes = [vp, i32, i32, i32, i32, vp, vp, vp]
+        L.ochip_color_balance_solve.argtypes = [vp, vp, C.c_uint64, vp, u32, vp, u32, vp, vp, vp]
+        L.ochip_color_balance_evaluate.argtypes = [vp, vp, C.c_uint64, vp, u32, vp, u32, vp, vp, vp, vp, vp, vp, vp, vp]
         _lib = L
     return _lib
 

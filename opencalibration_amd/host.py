@@ -256,6 +256,11 @@ def load():
         L.och_blend_pyr.restype = None
         L.och_blend_math.argtypes = [C.c_int, sz, vp, vp]
         L.och_blend_math.restype = None
+        L.och_color_balance_solve.argtypes = [vp, vp, vp, sz, sz, vp, vp, sz, vp, vp, C.POINTER(sz), sz, vp, vp, C.POINTER(sz), vp]
+        L.och_color_balance_evaluate.argtypes = [vp, vp, sz, sz, vp, vp, sz, vp, vp, vp, vp, vp, vp, vp]
+        L.och_color_balance_evaluate_plan.argtypes = [vp, sz, sz, vp, vp, sz, vp, vp, vp, vp, vp, vp, vp, vp]
+        L.och_color_balance_remove_gauge.argtypes = [sz, vp, vp]
+        L.och_color_balance_last_error.restype = C.c_char_p
         _lib = L
     return _lib
 
@@ -895,11 +900,101 @@ def laplacian_blend(lab_layers, weights, pyramid_levels=4, ctx=None):
     return out
 
 
+def _corr_array(correspondences):
+    c = np.ascontiguousarray(correspondences)
+    if c.dtype != CORR_DTYPE or c.ndim != 1:
+        raise ValueError("correspondences are a 1-D array of CORR_DTYPE")
+    return c
+
+
+def color_balance_solve(correspondences, graph=None, positions=None, ctx=None):
+    """solveColorBalance (src/ortho/color_balance.cpp) of ortho_layers' correspondences (CORR_DTYPE; the bands'
+    concatenated): the per-image and per-model radiometric parameters the blend applies.  ctx (a capi.Context): the
+    solve runs on its device; None: the CPU route (small surveys: at most 4096 unknowns, 6 per camera + 3 per model).
+    The gauge plane is removed over the cameras with a position: `positions` ({node id: (x, y)} or rows (id, x, y))
+    first, else the graph's nodes.  Returns dict(per_image={id: dict(lab_offset, brdf, slope)}, per_model={id: 3
+    coefficients}, success, final_cost, num_iterations, termination), which ortho_blend takes as color_balance=."""
+    L = load()
+    corr = _corr_array(correspondences)
+    if positions is None:
+        pos = []
+    elif isinstance(positions, dict):
+        pos = [(int(k), float(v[0]), float(v[1])) for k, v in positions.items()]
+    else:
+        pos = [(int(r[0]), float(r[1]), float(r[2])) for r in positions]
+    pid = np.array([r[0] for r in pos], np.uint64)
+    pxy = np.array([r[1:] for r in pos], np.float64).reshape(-1, 2)
+    ncap = len(np.unique(np.concatenate([corr["camera_id_a"], corr["camera_id_b"]])))
+    mcap = len(np.unique(np.concatenate([corr["model_id_a"], corr["model_id_b"]])))
+    cids, six = np.zeros(max(ncap, 1), np.uint64), np.zeros((max(ncap, 1), 6))
+    mids, vig = np.zeros(max(mcap, 1), np.uint32), np.zeros((max(mcap, 1), 3))
+    nc, nm, summary = C.c_size_t(0), C.c_size_t(0), np.zeros(4)
+    rc = L.och_color_balance_solve(graph.h if graph is not None else None, ctx.h if ctx is not None else None,
+                                   corr.ctypes.data if len(corr) else None, len(corr), len(pid),
+                                   pid.ctypes.data if len(pid) else None, pxy.ctypes.data if len(pid) else None,
+                                   ncap, cids.ctypes.data, six.ctypes.data, C.byref(nc), mcap, mids.ctypes.data,
+                                   vig.ctypes.data, C.byref(nm), summary.ctypes.data)
+    if rc != 0:
+        raise capi.OchipError(L.och_color_balance_last_error().decode())
+    per_image = {int(cids[i]): dict(lab_offset=tuple(float(v) for v in six[i, :3]), brdf=float(six[i, 3]),
+                                    slope=tuple(float(v) for v in six[i, 4:])) for i in range(nc.value)}
+    per_model = {int(mids[i]): tuple(float(v) for v in vig[i]) for i in range(nm.value)}
+    return dict(per_image=per_image, per_model=per_model, success=bool(summary[0]), final_cost=float(summary[1]),
+                num_iterations=int(summary[2]), termination=int(summary[3]))
+
+
+def color_balance_evaluate(correspondences, cam_ids, color6, model_ids, vig3, ctx=None, jacobian=True, plan=False):
+    """Test seam: cost, J'J, J'r of the colour-balance problem at the given parameters (cam_ids, model_ids sorted and
+    unique; color6 (n, 6), vig3 (m, 3)), on ctx's device or by the CPU route; plan=True (no ctx): the device's own
+    evaluation run on the host (its plan, its arithmetic, its order: bit-equal to the device's), with layout = dict(
+    tail_begin, regions, separators, chunks).  Returns dict(cost, failed, JtJ, Jtr, cam_col, model_col): the first
+    unknown of every camera / model in the route's own order."""
+    L = load()
+    corr = _corr_array(correspondences)
+    cam_ids, model_ids = np.ascontiguousarray(cam_ids, np.uint64), np.ascontiguousarray(model_ids, np.uint32)
+    color6 = np.ascontiguousarray(color6, np.float64).reshape(len(cam_ids), 6)
+    vig3 = np.ascontiguousarray(vig3, np.float64).reshape(len(model_ids), 3)
+    n = 6 * len(cam_ids) + 3 * len(model_ids)
+    JtJ, Jtr = (np.zeros((n, n)), np.zeros(n)) if jacobian else (None, None)
+    cam_col, model_col = np.zeros(len(cam_ids), np.int32), np.zeros(len(model_ids), np.int32)
+    cost = np.zeros(1)
+    args = (corr.ctypes.data, len(corr), len(cam_ids), cam_ids.ctypes.data, color6.ctypes.data, len(model_ids),
+            model_ids.ctypes.data, vig3.ctypes.data, cost.ctypes.data, None if JtJ is None else JtJ.ctypes.data,
+            None if Jtr is None else Jtr.ctypes.data, cam_col.ctypes.data, model_col.ctypes.data)
+    layout = np.zeros(4, np.int32)
+    if plan:
+        if ctx is not None:
+            raise ValueError("plan=True is the host's run of the device evaluation: no ctx")
+        rc = L.och_color_balance_evaluate_plan(*args, layout.ctypes.data)
+    else:
+        rc = L.och_color_balance_evaluate(ctx.h if ctx is not None else None, *args)
+    if rc < 0:
+        raise capi.OchipError(L.och_color_balance_last_error().decode())
+    res = dict(cost=float(cost[0]), failed=rc == 1, JtJ=JtJ, Jtr=Jtr, cam_col=cam_col, model_col=model_col)
+    if plan:
+        res["layout"] = dict(zip(("tail_begin", "regions", "separators", "chunks"), map(int, layout)))
+    return res
+
+
+def color_balance_remove_gauge(xy, offsets):
+    """The gauge step of color_balance_solve alone: offsets (n, 3) minus their least-squares plane over xy (n, 2);
+    returns (offsets, rank)."""
+    xy = np.ascontiguousarray(xy, np.float64).reshape(-1, 2)
+    off = np.array(offsets, np.float64).reshape(len(xy), 3)
+    rank = load().och_color_balance_remove_gauge(len(xy), xy.ctypes.data, off.ctypes.data)
+    return off, rank
+
+
 def ortho_mosaic(plan, graph, surfaces, images, mesh=None, config=None, color_balance=None, tile_rows=1, out=None):
     """The blended full-resolution orthomosaic of `plan` (dsm_plan), band by band of tile_rows output tile rows: DSM ->
     layers (ortho_layers) -> blend (ortho_blend).  mesh (an OrthoMesh): every step on its device, images as CUDA tensors,
     into `out` (a (height, width, 4) uint8 CUDA tensor, made when None); None: the CPU route, numpy images, into a host
-    array.  config: LAYERS_CONFIG's and BLEND_CONFIG's keys."""
+    array.  config: LAYERS_CONFIG's and BLEND_CONFIG's keys.
+    color_balance: None (no correction), a dict (ortho_blend's), or "solve": the reference's GENERATE_LAYERS ->
+    COLOR_BALANCE -> BLEND_LAYERS - a first pass over the bands renders the layers for their correspondences alone,
+    color_balance_solve (on the mesh's device, or the CPU route) turns them into the tables, and the second pass
+    RE-RENDERS every band's layers and blends them with the result: a band's layers are never kept beyond its blend, so
+    the memory held stays one band's whatever the raster's size, at the price of the layer pass run twice."""
     cfg = {**LAYERS_CONFIG, **BLEND_CONFIG, **(config or {})}
     lcfg = {k: cfg[k] for k in LAYERS_CONFIG}
     bcfg = {k: cfg[k] for k in BLEND_CONFIG}
@@ -911,12 +1006,14 @@ def ortho_mosaic(plan, graph, surfaces, images, mesh=None, config=None, color_ba
 
         dev = f"cuda:{mesh.ctx.device}"
         out = torch.empty((h, w, 4), dtype=torch.uint8, device=dev) if out is None else out
-    for row0 in range(0, h, tile_rows * t):
+
+    def band(row0, blend):
         rows = min(tile_rows * t, h - row0)
         if mesh is None:
             dsm = dsm_render(plan, surfaces, row0=row0, rows=rows)
             layers = ortho_layers(plan, graph, surfaces, images, row0=row0, tile_rows=tile_rows, config=lcfg, dsm=dsm)
-            ortho_blend(plan, graph, surfaces, layers, dsm, color_balance, config=bcfg, out=out[row0:row0 + rows])
+            if blend:
+                ortho_blend(plan, graph, surfaces, layers, dsm, color_balance, config=bcfg, out=out[row0:row0 + rows])
         else:
             dsm = torch.empty((rows, w), dtype=torch.float32, device=dev)
             dsm_render(plan, surfaces, mesh=mesh, row0=row0, rows=rows, out=dsm)
@@ -925,7 +1022,18 @@ def ortho_mosaic(plan, graph, surfaces, images, mesh=None, config=None, color_ba
             layers = ortho_layers(plan, graph, surfaces, images, mesh=mesh, row0=row0, tile_rows=tile_rows, config=lcfg,
                                   out=lay)
             layers["bgra"], layers["camera_id"] = lay["bgra"], lay["camera_id"]
-            ortho_blend(plan, graph, surfaces, layers, dsm, color_balance, ctx=mesh.ctx, config=bcfg, out=out[row0:row0 + rows])
+            if blend:
+                ortho_blend(plan, graph, surfaces, layers, dsm, color_balance, ctx=mesh.ctx, config=bcfg, out=out[row0:row0 + rows])
+        return layers["correspondences"]
+
+    if isinstance(color_balance, str):
+        if color_balance != "solve":
+            raise ValueError('color_balance is None, a dict of tables or "solve"')
+        corr = [band(row0, False) for row0 in range(0, h, tile_rows * t)]
+        color_balance = color_balance_solve(np.concatenate(corr) if corr else np.zeros(0, CORR_DTYPE), graph=graph,
+                                            ctx=mesh.ctx if mesh is not None else None)
+    for row0 in range(0, h, tile_rows * t):
+        band(row0, True)
     return out
 
 
