@@ -2979,26 +2979,6 @@ area_tab area_table(int ssize, int dsize, double scale)
     return t;
 }
 
-template <typename T>
-int up(ochip_ctx *ctx, std::vector<std::pair<void *, size_t>> &allocs, T **dst, const T *src, size_t n)
-{
-    size_t got = 0;
-    void *d = ochip_pool_get(ctx, (n ? n : 1) * sizeof(T), &got);
-    if (!d)
-        return ochip_fail(ctx, OCHIP_ENOMEM, "device allocation of %zu bytes failed in akaze", n * sizeof(T));
-    allocs.emplace_back(d, got);
-    // on the context's own stream (not the device's default stream, where the uploads of all contexts would queue up
-    // behind each other); the wait keeps the caller's buffer semantics of a synchronous copy
-    if (src && n)
-    {
-        if (hipMemcpyAsync(d, src, n * sizeof(T), hipMemcpyHostToDevice, ctx->stream) != hipSuccess ||
-            ochip_stream_wait(ctx, ctx->stream) != hipSuccess)
-            return ochip_fail(ctx, OCHIP_EHIP, "hipMemcpy failed in akaze");
-    }
-    *dst = (T *)d;
-    return OCHIP_OK;
-}
-
 // ---- synthetic views (test / benchmark DATA, not part of the hot path): a jittered ground lattice of
 // Gaussian blobs on the plane z = a x + b y, seen through a pinhole camera.  Every view of one seed shows
 // the same ground, so features extracted from different views really correspond.
@@ -3362,12 +3342,10 @@ int akaze_run(ochip_ctx *ctx, const uint8_t *images_bgr, bool on_device, uint32_
     const uint32_t B = n_images;
     const uint32_t max_cands = std::max<uint32_t>(max_kp * 4, 1u << 16);
 
-    std::vector<std::pair<void *, size_t>> allocs;
-    auto cleanup = [&]() {
-        (void)ochip_stream_wait(ctx, st);
-        for (auto &a : allocs)
-            ochip_pool_put(ctx, a.first, a.second);
-    };
+    // (uploads on the context's own stream, not the device's default stream, where the uploads of all contexts would queue up
+    // behind each other; the wait keeps the caller's buffer semantics of a synchronous copy)
+    ochip::dev_scratch mem{ctx, "akaze"};
+    constexpr auto WAIT = ochip::copy_mode::enqueue_wait;
     int rc = OCHIP_OK;
 #define AK(call)                                                                                                       \
     do                                                                                                                 \
@@ -3404,42 +3382,42 @@ int akaze_run(ochip_ctx *ctx, const uint8_t *images_bgr, bool on_device, uint32_
     if (on_device)
         d_bgr = const_cast<uint8_t *>(images_bgr);
     else
-        AK(up(ctx, allocs, &d_bgr, images_bgr, (size_t)B * src_px * 3));
-    AK(up<uint8_t>(ctx, allocs, &d_gray, nullptr, (size_t)B * src_px + 4));
-    AK(up<float>(ctx, allocs, &d_img, nullptr, (size_t)B * plane0));
-    AK(up<float>(ctx, allocs, &d_flow, nullptr, (size_t)B * plane0));
-    AK(up<float>(ctx, allocs, &d_ping, nullptr, (size_t)B * plane0));
-    AK(up<unsigned int>(ctx, allocs, &d_pmax, nullptr, (size_t)B * n_tiles0));
-    AK(up<float>(ctx, allocs, &d_Lt, nullptr, (size_t)B * img_stride));
-    AK(up<float2>(ctx, allocs, &d_Lxy, nullptr, (size_t)B * img_stride));
-    AK(up<float2>(ctx, allocs, &d_Fit, nullptr, (size_t)B * img_stride));
-    AK(up<float>(ctx, allocs, &d_Rmax, nullptr, (size_t)B * img_stride));
-    AK(up<float>(ctx, allocs, &d_kc, nullptr, B));
-    AK(up<unsigned int>(ctx, allocs, &d_hmax, nullptr, B));
-    AK(up<unsigned int>(ctx, allocs, &d_hist, nullptr, (size_t)B * 301));
-    AK(up<unsigned int>(ctx, allocs, &d_ncand, nullptr, B));
-    AK(up<cand_t>(ctx, allocs, &d_cands, nullptr, (size_t)B * max_cands));
-    AK(up<unsigned char>(ctx, allocs, &d_dead, nullptr, (size_t)B * max_cands));
-    AK(up<unsigned char>(ctx, allocs, &d_valid, nullptr, (size_t)B * max_cands));
-    AK(up<float>(ctx, allocs, &d_kp, nullptr, (size_t)B * max_cands * 6));
-    AK(up<unsigned long long>(ctx, allocs, &d_desc, nullptr, (size_t)B * max_cands * 8));
-    AK(up<float>(ctx, allocs, &d_kpc, nullptr, (size_t)B * max_kp * 6));
-    AK(up<unsigned long long>(ctx, allocs, &d_descc, nullptr, (size_t)B * max_kp * 8));
-    AK(up<unsigned int>(ctx, allocs, &d_counts, nullptr, B));
-    AK(up<unsigned int>(ctx, allocs, &d_tile_counts, nullptr, (size_t)B * n_tiles));
-    AK(up<unsigned int>(ctx, allocs, &d_tile_base, nullptr, (size_t)B * n_tiles));
-    AK(up<unsigned long long>(ctx, allocs, &d_mask, nullptr, (size_t)B * mask_stride));
-    AK(up<unsigned long long>(ctx, allocs, &d_vmask, nullptr, (size_t)B * mask_stride));
-    AK(up<unsigned long long>(ctx, allocs, &d_kmask, nullptr, (size_t)B * sup_stride));
-    AK(up<unsigned long long>(ctx, allocs, &d_pmask, nullptr, (size_t)B * sup_stride));
-    AK(up<unsigned long long>(ctx, allocs, &d_rmask, nullptr, (size_t)B * sup_stride));
-    AK(up<unsigned int>(ctx, allocs, &d_turns, nullptr, (size_t)B * 2 * max_cands));
-    AK(up<unsigned int>(ctx, allocs, &d_waiting, nullptr, (size_t)B * LV.n));
-    AK(up<unsigned int>(ctx, allocs, &d_level_first, nullptr, (size_t)B * (LV.n + 1)));
-    AK(up<unsigned int>(ctx, allocs, &d_found, nullptr, (size_t)B * max_cands));
-    AK(up<unsigned int>(ctx, allocs, &d_wbase, nullptr, (size_t)B * mask_stride));
-    AK(up<unsigned int>(ctx, allocs, &d_live, nullptr, (size_t)B * max_cands));
-    AK(up<unsigned int>(ctx, allocs, &d_nlive, nullptr, B));
+        AK(mem.upload(&d_bgr, images_bgr, (size_t)B * src_px * 3, WAIT));
+    AK(mem.alloc<uint8_t>(&d_gray, (size_t)B * src_px + 4));
+    AK(mem.alloc<float>(&d_img, (size_t)B * plane0));
+    AK(mem.alloc<float>(&d_flow, (size_t)B * plane0));
+    AK(mem.alloc<float>(&d_ping, (size_t)B * plane0));
+    AK(mem.alloc<unsigned int>(&d_pmax, (size_t)B * n_tiles0));
+    AK(mem.alloc<float>(&d_Lt, (size_t)B * img_stride));
+    AK(mem.alloc<float2>(&d_Lxy, (size_t)B * img_stride));
+    AK(mem.alloc<float2>(&d_Fit, (size_t)B * img_stride));
+    AK(mem.alloc<float>(&d_Rmax, (size_t)B * img_stride));
+    AK(mem.alloc<float>(&d_kc, B));
+    AK(mem.alloc<unsigned int>(&d_hmax, B));
+    AK(mem.alloc<unsigned int>(&d_hist, (size_t)B * 301));
+    AK(mem.alloc<unsigned int>(&d_ncand, B));
+    AK(mem.alloc<cand_t>(&d_cands, (size_t)B * max_cands));
+    AK(mem.alloc<unsigned char>(&d_dead, (size_t)B * max_cands));
+    AK(mem.alloc<unsigned char>(&d_valid, (size_t)B * max_cands));
+    AK(mem.alloc<float>(&d_kp, (size_t)B * max_cands * 6));
+    AK(mem.alloc<unsigned long long>(&d_desc, (size_t)B * max_cands * 8));
+    AK(mem.alloc<float>(&d_kpc, (size_t)B * max_kp * 6));
+    AK(mem.alloc<unsigned long long>(&d_descc, (size_t)B * max_kp * 8));
+    AK(mem.alloc<unsigned int>(&d_counts, B));
+    AK(mem.alloc<unsigned int>(&d_tile_counts, (size_t)B * n_tiles));
+    AK(mem.alloc<unsigned int>(&d_tile_base, (size_t)B * n_tiles));
+    AK(mem.alloc<unsigned long long>(&d_mask, (size_t)B * mask_stride));
+    AK(mem.alloc<unsigned long long>(&d_vmask, (size_t)B * mask_stride));
+    AK(mem.alloc<unsigned long long>(&d_kmask, (size_t)B * sup_stride));
+    AK(mem.alloc<unsigned long long>(&d_pmask, (size_t)B * sup_stride));
+    AK(mem.alloc<unsigned long long>(&d_rmask, (size_t)B * sup_stride));
+    AK(mem.alloc<unsigned int>(&d_turns, (size_t)B * 2 * max_cands));
+    AK(mem.alloc<unsigned int>(&d_waiting, (size_t)B * LV.n));
+    AK(mem.alloc<unsigned int>(&d_level_first, (size_t)B * (LV.n + 1)));
+    AK(mem.alloc<unsigned int>(&d_found, (size_t)B * max_cands));
+    AK(mem.alloc<unsigned int>(&d_wbase, (size_t)B * mask_stride));
+    AK(mem.alloc<unsigned int>(&d_live, (size_t)B * max_cands));
+    AK(mem.alloc<unsigned int>(&d_nlive, B));
     {
         // processing order of the detection tiles: level by level, Morton order inside a level
         std::vector<std::pair<uint64_t, unsigned int>> keyed;
@@ -3466,17 +3444,14 @@ int akaze_run(ochip_ctx *ctx, const uint8_t *images_bgr, bool on_device, uint32_
         std::vector<unsigned int> seq(keyed.size());
         for (size_t i = 0; i < keyed.size(); i++)
             seq[i] = keyed[i].second;
-        AK(up(ctx, allocs, &d_tile_seq, seq.data(), seq.size()));
+        AK(mem.upload(&d_tile_seq, seq.data(), seq.size(), WAIT));
     }
     {
         // the descriptor kernel's tables (built once per process): gather orders, cell chains, bit list
-        AK(up(ctx, allocs, &d_gtab, &host_gather_tab(), 1));
+        AK(mem.upload(&d_gtab, &host_gather_tab(), 1, WAIT));
     }
     if (rc != OCHIP_OK)
-    {
-        cleanup();
-        return rc;
-    }
+    return rc;
     auto grid2 = [&](int w, int h) { return dim3((w + 255) / 256, h, B); };
     auto taps_of = [](const std::vector<float> &k) {
         taps_t t{};
@@ -3487,10 +3462,7 @@ int akaze_run(ochip_ctx *ctx, const uint8_t *images_bgr, bool on_device, uint32_
     };
     const taps_t g1 = taps_of(gaussian_taps(1.0f)), g0 = taps_of(gaussian_taps(soffset));
     if (g1.n != 5 || g0.n != 9)
-    {
-        cleanup();
-        return ochip_fail(ctx, OCHIP_EINVAL, "akaze: unexpected Gaussian kernel sizes %d / %d", g1.n, g0.n);
-    }
+    return ochip_fail(ctx, OCHIP_EINVAL, "akaze: unexpected Gaussian kernel sizes %d / %d", g1.n, g0.n);
     hipEvent_t e0, e1;
     ochip_prof_begin(ctx, OCHIP_K_AKAZE, &e0, &e1);
 
@@ -3539,17 +3511,14 @@ int akaze_run(ochip_ctx *ctx, const uint8_t *images_bgr, bool on_device, uint32_
     {
         int *xo, *xs, *yo, *ys;
         float *xa, *ya;
-        AK(up(ctx, allocs, &xo, tx.off.data(), tx.off.size()));
-        AK(up(ctx, allocs, &xs, tx.si.data(), tx.si.size()));
-        AK(up(ctx, allocs, &xa, tx.alpha.data(), tx.alpha.size()));
-        AK(up(ctx, allocs, &yo, ty.off.data(), ty.off.size()));
-        AK(up(ctx, allocs, &ys, ty.si.data(), ty.si.size()));
-        AK(up(ctx, allocs, &ya, ty.alpha.data(), ty.alpha.size()));
+        AK(mem.upload(&xo, tx.off.data(), tx.off.size(), WAIT));
+        AK(mem.upload(&xs, tx.si.data(), tx.si.size(), WAIT));
+        AK(mem.upload(&xa, tx.alpha.data(), tx.alpha.size(), WAIT));
+        AK(mem.upload(&yo, ty.off.data(), ty.off.size(), WAIT));
+        AK(mem.upload(&ys, ty.si.data(), ty.si.size(), WAIT));
+        AK(mem.upload(&ya, ty.alpha.data(), ty.alpha.size(), WAIT));
         if (rc != OCHIP_OK)
-        {
-            cleanup();
-            return rc;
-        }
+        return rc;
         const dim3 rgrid((W + 255) / 256, (H + RESIZE_ROWS - 1) / RESIZE_ROWS, B);
         int most_taps = 0;
         for (int x = 0; x < W; x++)
@@ -3793,10 +3762,7 @@ int akaze_run(ochip_ctx *ctx, const uint8_t *images_bgr, bool on_device, uint32_
             else if (l.sigma_size == 4)
                 hipLaunchKernelGGL((blur_fused_kernel<BLUR_FLOW_DERIV, 4, 2>), tiles(l.w, l.h), dim3(256), 0, st, a, g1);
             else
-            {
-                cleanup();
-                return ochip_fail(ctx, OCHIP_EINVAL, "akaze: derivative scale %d outside 2..4", l.sigma_size);
-            }
+            return ochip_fail(ctx, OCHIP_EINVAL, "akaze: derivative scale %d outside 2..4", l.sigma_size);
         }
         if (const char *dump = std::getenv("OCHIP_DUMP_PLANES"))
             if (i == 1)
@@ -3863,10 +3829,7 @@ int akaze_run(ochip_ctx *ctx, const uint8_t *images_bgr, bool on_device, uint32_
             else if (l.sigma_size == 4)
                 hipLaunchKernelGGL((blur_fused_kernel<BLUR_DERIV, 4, 0>), tiles(l.w, l.h), dim3(256), 0, st, a, one);
             else
-            {
-                cleanup();
-                return ochip_fail(ctx, OCHIP_EINVAL, "akaze: derivative scale %d outside 2..4", l.sigma_size);
-            }
+            return ochip_fail(ctx, OCHIP_EINVAL, "akaze: derivative scale %d outside 2..4", l.sigma_size);
         }
         {
             const float2 *lxy = d_Lxy + l.off;
@@ -3927,11 +3890,8 @@ int akaze_run(ochip_ctx *ctx, const uint8_t *images_bgr, bool on_device, uint32_
     for (uint32_t b = 0; b < B; b++)
     {
         if (ncand[b] > max_cands)
-        {
-            cleanup();
             return ochip_fail(ctx, OCHIP_ENOMEM, "image %u has %u extrema candidates; raise max_kp (candidate capacity %u)", b,
                               ncand[b], max_cands);
-        }
         max_n = std::max(max_n, ncand[b]);
     }
     const int xcd_remap = 2; // groups of 64 list neighbours per XCD (see xcd_contiguous; 0, 1 and 3 measured slower)
@@ -3944,7 +3904,7 @@ int akaze_run(ochip_ctx *ctx, const uint8_t *images_bgr, bool on_device, uint32_
         unsigned int *d_sup_stats = nullptr;
         if (ochip_verbose("extract"))
         {
-            AK(up<unsigned int>(ctx, allocs, &d_sup_stats, nullptr, (size_t)3 * B * LV.n * 3));
+            AK(mem.alloc<unsigned int>(&d_sup_stats, (size_t)3 * B * LV.n * 3));
             OCHIP_HIP(ctx, hipMemsetAsync(d_sup_stats, 0, (size_t)3 * B * LV.n * 3 * 4, st));
         }
         OCHIP_HIP(ctx, hipMemsetAsync(d_kmask, 0, (size_t)B * sup_stride * 8, st));
@@ -4053,7 +4013,7 @@ int akaze_run(ochip_ctx *ctx, const uint8_t *images_bgr, bool on_device, uint32_
     if (rc == OCHIP_OK && lists)
         // the tail of extract_features prepared on the device (features.hip): records, suppression flags, what the
         // host's sort needs - instead of the raw keypoint arrays
-        rc = ochip::feature_lists_enqueue(ctx, &allocs, B, max_kp, d_kpc, d_descc, d_counts, most, W, H, scale, nms_radius, lists);
+        rc = ochip::feature_lists_enqueue(ctx, mem, B, max_kp, d_kpc, d_descc, d_counts, most, W, H, scale, nms_radius, lists);
     else if (rc == OCHIP_OK && most > 0)
     {
         // one strided copy per array instead of one per image and array (2 x 100 launches per chunk): every image's row is
@@ -4064,7 +4024,8 @@ int akaze_run(ochip_ctx *ctx, const uint8_t *images_bgr, bool on_device, uint32_
     if (rc != OCHIP_OK)
         for (uint32_t b = 0; b < B; b++)
             counts[b] = 0;
-    cleanup();
+    (void)ochip_stream_wait(ctx, st);
+    mem.release();
     return rc;
 #undef AK
 }

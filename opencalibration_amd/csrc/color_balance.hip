@@ -185,7 +185,7 @@ __global__ __launch_bounds__(LM_TG) void cb_candidate_kernel(cb_dev D, const dou
 struct cb_problem
 {
     ochip_ctx *ctx = nullptr;
-    std::vector<std::pair<void *, size_t>> allocs;
+    dev_blocks mem;
     lm_system sys;
     cb_dev dev{};
     cb_owner *owners_dev = nullptr;
@@ -201,15 +201,11 @@ struct cb_problem
             return;
         (void)hipSetDevice(ctx->device);
         (void)ochip_stream_wait(ctx, ctx->stream);
-        for (auto &a : allocs)
-            ochip_pool_put(ctx, a.first, a.second);
+        mem.release();
     }
 };
 
-template <typename T> int up(cb_problem *p, T **dst, const std::vector<T> &v)
-{
-    return lm_dev_upload(p->ctx, &p->allocs, dst, v.data(), v.size());
-}
+constexpr auto BLOCKING = copy_mode::blocking;
 
 int problem_create(ochip_ctx *ctx, const ochip_color_corr *corr, uint64_t n_corr, const uint64_t *cam_ids, uint32_t n_cams,
                    const uint32_t *model_ids, uint32_t n_models, cb_problem *p)
@@ -218,7 +214,8 @@ int problem_create(ochip_ctx *ctx, const ochip_color_corr *corr, uint64_t n_corr
     std::string err;
     if (!cb::build_plan(corr, n_corr, cam_ids, n_cams, model_ids, n_models, &P, &err))
         return ochip_fail(ctx, OCHIP_EINVAL, "%s", err.c_str());
-    p->ctx = ctx;
+    p->ctx = p->mem.ctx = ctx;
+    p->mem.what = "colour balance problem";
     p->n_cams = n_cams, p->n_models = n_models, p->n_corr = n_corr;
     p->cam_t = P.cam_t, p->model_t = P.model_t;
     const int n = P.n;
@@ -243,19 +240,19 @@ int problem_create(ochip_ctx *ctx, const ochip_color_corr *corr, uint64_t n_corr
     cb_obs *obs_dev = nullptr;
     cb_chunk *chunks_dev = nullptr;
     double *weight_dev = nullptr;
-    chk(up(p, &obs_dev, obs));
-    chk(up(p, &chunks_dev, chunks));
-    chk(up(p, &weight_dev, weight));
-    chk(up(p, &p->owners_dev, owners));
-    chk(up(p, &p->items_dev, items));
-    chk(up(p, &p->segments_dev, P.segments));
-    chk(lm_dev_upload<double>(ctx, &p->allocs, &D.partial, nullptr, P.segments.size() * 64));
+    chk(p->mem.upload(&obs_dev, obs, BLOCKING));
+    chk(p->mem.upload(&chunks_dev, chunks, BLOCKING));
+    chk(p->mem.upload(&weight_dev, weight, BLOCKING));
+    chk(p->mem.upload(&p->owners_dev, owners, BLOCKING));
+    chk(p->mem.upload(&p->items_dev, items, BLOCKING));
+    chk(p->mem.upload(&p->segments_dev, P.segments, BLOCKING));
+    chk(p->mem.alloc<double>(&D.partial, P.segments.size() * 64));
     p->n_segments = (uint32_t)P.segments.size();
-    chk(lm_dev_upload<double>(ctx, &p->allocs, &D.x[0], nullptr, (size_t)n));
-    chk(lm_dev_upload<double>(ctx, &p->allocs, &D.x[1], nullptr, (size_t)n));
-    chk(lm_dev_upload<double>(ctx, &p->allocs, &D.rec, nullptr, chunks.size() * cb::REC));
-    chk(lm_dev_upload<double>(ctx, &p->allocs, &D.chunk_cost, nullptr, chunks.size()));
-    chk(lm_dev_upload<int32_t>(ctx, &p->allocs, &D.fail, nullptr, 1));
+    chk(p->mem.alloc<double>(&D.x[0], (size_t)n));
+    chk(p->mem.alloc<double>(&D.x[1], (size_t)n));
+    chk(p->mem.alloc<double>(&D.rec, chunks.size() * cb::REC));
+    chk(p->mem.alloc<double>(&D.chunk_cost, chunks.size()));
+    chk(p->mem.alloc<int32_t>(&D.fail, 1));
     if (rc != OCHIP_OK)
         return rc;
     D.obs = obs_dev, D.chunks = chunks_dev, D.weight = weight_dev;
@@ -268,7 +265,7 @@ int problem_create(ochip_ctx *ctx, const ochip_color_corr *corr, uint64_t n_corr
     OCHIP_HIP(ctx, hipMemsetAsync(D.fail, 0, 4, ctx->stream));
     OCHIP_HIP(ctx, ochip_stream_wait(ctx, ctx->stream));
     p->sys.ctx = ctx;
-    p->sys.allocs = &p->allocs;
+    p->sys.allocs = &p->mem;
     return lm_system_resize(&p->sys, n, env);
 }
 

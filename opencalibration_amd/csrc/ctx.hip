@@ -94,6 +94,53 @@ void ochip_pool_put(ochip_ctx *ctx, void *p, size_t bytes)
     }
 }
 
+namespace ochip
+{
+void *dev_blocks::get(size_t bytes)
+{
+    size_t got = 0;
+    void *d = ochip_pool_get(ctx, bytes < 16 ? 16 : bytes, &got);
+    if (d)
+        held.emplace_back(d, got);
+    else
+        ochip_fail(ctx, OCHIP_ENOMEM, "device allocation of %zu bytes failed in %s", bytes, what);
+    return d;
+}
+
+int dev_blocks::upload_bytes(void **dst, const void *src, size_t bytes, copy_mode m)
+{
+    void *d = get(bytes);
+    if (!d)
+        return OCHIP_ENOMEM;
+    if (src && bytes)
+    {
+        hipError_t e = m == copy_mode::blocking ? hipMemcpy(d, src, bytes, hipMemcpyHostToDevice)
+                                                : hipMemcpyAsync(d, src, bytes, hipMemcpyHostToDevice, ctx->stream);
+        if (e == hipSuccess && m == copy_mode::enqueue_wait)
+            e = ochip_stream_wait(ctx, ctx->stream);
+        if (e != hipSuccess)
+            return ochip_fail(ctx, OCHIP_EHIP, "host-to-device copy of %zu bytes failed in %s: %s", bytes, what, hipGetErrorString(e));
+    }
+    *dst = d;
+    return OCHIP_OK;
+}
+
+void dev_blocks::release()
+{
+    for (auto &b : held)
+        ochip_pool_put(ctx, b.first, b.second);
+    held.clear();
+}
+
+dev_scratch::~dev_scratch()
+{
+    if (held.empty())
+        return;
+    (void)ochip_stream_wait(ctx, ctx->stream);
+    release();
+}
+} // namespace ochip
+
 void ochip_prof_begin(ochip_ctx *ctx, int kid, hipEvent_t *start, hipEvent_t *stop)
 {
     auto &s = ctx->prof[kid];

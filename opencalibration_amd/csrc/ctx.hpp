@@ -160,19 +160,81 @@ void ochip_prof_end(ochip_ctx *ctx, int kid, hipEvent_t start, hipEvent_t stop);
                               __LINE__);                                                                               \
     } while (0)
 
-namespace ochip
-{
-// features.hip: the tail of extract_features prepared on the device for B images whose compacted keypoints lie in HBM
-// (enqueued on the context's stream, results copied into `out`; the caller waits and returns `allocs` to the pool)
-int feature_lists_enqueue(ochip_ctx *ctx, std::vector<std::pair<void *, size_t>> *allocs, uint32_t B, uint32_t max_kp,
-                          const float *d_kp6, const unsigned long long *d_desc, const unsigned int *d_counts, uint32_t most,
-                          int work_w, int work_h, double scale, double nms_radius, const ochip_feature_lists *out);
-} // namespace ochip
+// return a failed step's code (its message is set); with the blocks of a call in a dev_scratch an early return is safe
+#define OCHIP_TRY(call)                                                                                                \
+    do                                                                                                                 \
+    {                                                                                                                  \
+        const int rc__ = (call);                                                                                       \
+        if (rc__ != OCHIP_OK)                                                                                          \
+            return rc__;                                                                                               \
+    } while (0)
 
 namespace ochip
 {
+// How dev_blocks::upload copies into the block it takes: enqueue on ctx->stream and leave the wait to the caller, enqueue and
+// wait (the source may be reused on return), or a blocking hipMemcpy.
+enum class copy_mode
+{
+    enqueue,
+    enqueue_wait,
+    blocking
+};
+
+// Device blocks taken from the context's pool and handed back together.  The only user of ochip_pool_get / ochip_pool_put:
+// an object that keeps device arrays holds one and releases it in its destroy; a call's temporaries use dev_scratch.
+struct dev_blocks
+{
+    ochip_ctx *ctx = nullptr;
+    const char *what = ""; // names the owner in error messages ("akaze", "ochip_dense_link", ...)
+    std::vector<std::pair<void *, size_t>> held;
+
+    dev_blocks() = default;
+    dev_blocks(ochip_ctx *c, const char *w) : ctx(c), what(w) {}
+    dev_blocks(const dev_blocks &) = delete;
+    dev_blocks &operator=(const dev_blocks &) = delete;
+
+    void *get(size_t bytes); // a block of max(bytes, 16); nullptr after ochip_fail(OCHIP_ENOMEM, ...)
+    int upload_bytes(void **dst, const void *src, size_t bytes, copy_mode m);
+    // get + copy of n elements; src == nullptr or n == 0: allocate only.  OCHIP_ENOMEM / OCHIP_EHIP on failure
+    template <class T> int upload(T **dst, const T *src, size_t n, copy_mode m)
+    {
+        void *d = nullptr;
+        const int rc = upload_bytes(&d, src, n * sizeof(T), m);
+        if (rc == OCHIP_OK)
+            *dst = (T *)d;
+        return rc;
+    }
+    template <class T> int upload(T **dst, const std::vector<T> &v, copy_mode m)
+    {
+        return upload(dst, v.data(), v.size(), m);
+    }
+    template <class T> int alloc(T **dst, size_t n)
+    {
+        return upload<T>(dst, nullptr, n, copy_mode::enqueue);
+    }
+    // put everything back now: the caller knows that nothing on the stream can still touch the blocks
+    void release();
+    bool empty() const
+    {
+        return held.empty();
+    }
+};
+
+// Call-scoped blocks.  The normal path waits for the stream where it always did and calls release(); an exit that still
+// holds blocks (an early return) waits for ctx->stream here first, so that no block reaches the pool under a running kernel.
+struct dev_scratch : dev_blocks
+{
+    using dev_blocks::dev_blocks;
+    ~dev_scratch();
+};
+
+// features.hip: the tail of extract_features prepared on the device for B images whose compacted keypoints lie in HBM
+// (enqueued on the context's stream, results copied into `out`; the caller waits and releases `mem`)
+int feature_lists_enqueue(ochip_ctx *ctx, dev_blocks &mem, uint32_t B, uint32_t max_kp, const float *d_kp6,
+                          const unsigned long long *d_desc, const unsigned int *d_counts, uint32_t most, int work_w, int work_h,
+                          double scale, double nms_radius, const ochip_feature_lists *out);
+
 // std_sort.hip: libstdc++'s std::sort (comp(a, b) = high half of a > high half of b) on segments of 64-bit records in HBM
-int std_sort_enqueue(ochip_ctx *ctx, std::vector<std::pair<void *, size_t>> *allocs, unsigned long long *recs, size_t total_len,
-                     const unsigned int *seg_begin, const unsigned int *seg_end, uint32_t n_segs, uint32_t max_len,
-                     unsigned char *fallback);
+int std_sort_enqueue(ochip_ctx *ctx, dev_blocks &mem, unsigned long long *recs, size_t total_len, const unsigned int *seg_begin,
+                     const unsigned int *seg_end, uint32_t n_segs, uint32_t max_len, unsigned char *fallback);
 } // namespace ochip

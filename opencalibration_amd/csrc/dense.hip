@@ -740,7 +740,7 @@ struct ochip_dense_index
     uint32_t n_images = 0;
     uint64_t total_features = 0;
     double cell_size = 0;
-    std::vector<std::pair<void *, size_t>> blocks;
+    ochip::dev_blocks mem;
     dense_image_meta *meta = nullptr;
     uint64_t *desc = nullptr;
     double2 *loc = nullptr;
@@ -762,7 +762,8 @@ int ochip_dense_index_create(ochip_ctx *ctx, uint32_t n_images, const uint64_t *
     ochip_dense_index *ix = new (std::nothrow) ochip_dense_index();
     if (!ix)
         return ochip_fail(ctx, OCHIP_ENOMEM, "out of host memory");
-    ix->ctx = ctx;
+    ix->ctx = ix->mem.ctx = ctx;
+    ix->mem.what = "the dense index";
     ix->n_images = n_images;
     ix->total_features = feat_off[n_images];
     ix->cell_size = cell_size;
@@ -783,30 +784,19 @@ int ochip_dense_index_create(ochip_ctx *ctx, uint32_t n_images, const uint64_t *
                               meta[i].ncx, meta[i].ncy, (unsigned long long)(cell_off[i + 1] - cell_off[i]));
         }
     }
-    auto upload = [&](void **dst, const void *src, size_t bytes) {
-        size_t got = 0;
-        void *d = ochip_pool_get(ctx, bytes ? bytes : 16, &got);
-        if (!d)
-            return ochip_fail(ctx, OCHIP_ENOMEM, "device allocation of %zu bytes failed for the dense index", bytes);
-        ix->blocks.emplace_back(d, got);
-        if (bytes && hipMemcpyAsync(d, src, bytes, hipMemcpyHostToDevice, ctx->stream) != hipSuccess)
-            return ochip_fail(ctx, OCHIP_EHIP, "hipMemcpyAsync failed for the dense index");
-        *dst = d;
-        return (int)OCHIP_OK;
-    };
-    int rc = upload((void **)&ix->meta, meta.data(), meta.size() * sizeof(dense_image_meta));
+    constexpr auto ENQ = ochip::copy_mode::enqueue;
+    int rc = ix->mem.upload(&ix->meta, meta.data(), meta.size(), ENQ);
     if (rc == OCHIP_OK)
-        rc = upload((void **)&ix->desc, desc8, (size_t)ix->total_features * 64);
+        rc = ix->mem.upload(&ix->desc, desc8, (size_t)ix->total_features * 8, ENQ);
     if (rc == OCHIP_OK)
-        rc = upload((void **)&ix->loc, loc2, (size_t)ix->total_features * 16);
+        rc = ix->mem.upload(&ix->loc, (const double2 *)loc2, (size_t)ix->total_features, ENQ);
     if (rc == OCHIP_OK)
-        rc = upload((void **)&ix->cell_start, cell_start, (size_t)cell_off[n_images] * 4);
+        rc = ix->mem.upload(&ix->cell_start, cell_start, (size_t)cell_off[n_images], ENQ);
     if (rc == OCHIP_OK && ochip_stream_wait(ctx, ctx->stream) != hipSuccess)
         rc = ochip_fail(ctx, OCHIP_EHIP, "stream wait failed for the dense index");
     if (rc != OCHIP_OK)
     {
-        for (auto &b : ix->blocks)
-            ochip_pool_put(ctx, b.first, b.second);
+        ix->mem.release();
         delete ix;
         return rc;
     }
@@ -818,8 +808,7 @@ void ochip_dense_index_destroy(ochip_dense_index *ix)
 {
     if (!ix)
         return;
-    for (auto &b : ix->blocks)
-        ochip_pool_put(ix->ctx, b.first, b.second);
+    ix->mem.release();
     delete ix;
 }
 
@@ -839,13 +828,11 @@ int ochip_dense_match(ochip_dense_index *ix, const ochip_dense_query *queries, u
             return ochip_fail(ctx, OCHIP_EINVAL, "ochip_dense_match: query %llu is out of range", (unsigned long long)i);
     // chunks of at most 2^24 queries: bounded scratch, and the copy of chunk k + 1 overlaps nothing worth a second stream
     const uint64_t CHUNK = 1ull << 24;
-    size_t got_q = 0, got_r = 0;
     const uint64_t cap = n_queries < CHUNK ? n_queries : CHUNK;
-    ochip_dense_query *dq = (ochip_dense_query *)ochip_pool_get(ctx, cap * sizeof(ochip_dense_query), &got_q);
-    ochip_dense_result *dr = (ochip_dense_result *)ochip_pool_get(ctx, cap * sizeof(ochip_dense_result), &got_r);
-    int rc = OCHIP_OK;
-    if (!dq || !dr)
-        rc = ochip_fail(ctx, OCHIP_ENOMEM, "device allocation failed for %llu dense queries", (unsigned long long)cap);
+    ochip::dev_scratch mem{ctx, "ochip_dense_match"};
+    ochip_dense_query *dq = (ochip_dense_query *)mem.get(cap * sizeof(ochip_dense_query));
+    ochip_dense_result *dr = (ochip_dense_result *)mem.get(cap * sizeof(ochip_dense_result));
+    int rc = dq && dr ? OCHIP_OK : OCHIP_ENOMEM;
     for (uint64_t at = 0; rc == OCHIP_OK && at < n_queries; at += CHUNK)
     {
         const uint64_t n = n_queries - at < CHUNK ? n_queries - at : CHUNK;
@@ -864,10 +851,8 @@ int ochip_dense_match(ochip_dense_index *ix, const ochip_dense_query *queries, u
             ochip_stream_wait(ctx, ctx->stream) != hipSuccess)
             rc = ochip_fail(ctx, OCHIP_EHIP, "dense match launch failed: %s", hipGetErrorString(hipGetLastError()));
     }
-    if (dq)
-        ochip_pool_put(ctx, dq, got_q);
-    if (dr)
-        ochip_pool_put(ctx, dr, got_r);
+    if (rc == OCHIP_OK) // (every chunk ended with a wait)
+        mem.release();
     return rc;
 }
 
@@ -901,23 +886,7 @@ int ochip_dense_link(ochip_dense_index *ix, const double *cams17, const uint32_t
     }
     OCHIP_HIP(ctx, hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
-    std::vector<std::pair<void *, size_t>> blocks;
-    int rc = OCHIP_OK;
-    auto get = [&](size_t bytes) -> void * {
-        size_t got = 0;
-        void *d = ochip_pool_get(ctx, bytes ? bytes : 16, &got);
-        if (!d)
-            rc = ochip_fail(ctx, OCHIP_ENOMEM, "ochip_dense_link: device allocation of %zu bytes failed", bytes);
-        else
-            blocks.emplace_back(d, got);
-        return d;
-    };
-    auto done = [&](int code) {
-        (void)ochip_stream_wait(ctx, st);
-        for (auto &b : blocks)
-            ochip_pool_put(ctx, b.first, b.second);
-        return code;
-    };
+    ochip::dev_scratch mem{ctx, "ochip_dense_link"};
     // batches of source images: bounded slot arrays (the reference walks its images in batches of OpenMP tasks too).
     // (measured and dropped, round 5: a batch's nearest-camera pass on the context's second stream under the search of the batch
     // before it, two sets of candidate arrays - the device phase stayed at 56.5 ms: the search fills the device by itself)
@@ -937,36 +906,27 @@ int ochip_dense_link(ochip_dense_index *ix, const double *cams17, const uint32_t
     for (uint32_t i = 0; i < n_images; i++)
         max_image_feats = std::max(max_image_feats, feat_base[i + 1] - feat_base[i]);
     // (the camera records and the ids stay with the index: ochip_dense_triangulate reads them)
-    auto keep = [&](size_t bytes) -> void * {
-        size_t got = 0;
-        void *d = ochip_pool_get(ctx, bytes ? bytes : 16, &got);
-        if (!d)
-            rc = ochip_fail(ctx, OCHIP_ENOMEM, "ochip_dense_link: device allocation of %zu bytes failed", bytes);
-        else
-            ix->blocks.emplace_back(d, got);
-        return d;
-    };
     if (!ix->cams)
-        ix->cams = keep((size_t)n_images * sizeof(dense_cam));
+        ix->cams = ix->mem.get((size_t)n_images * sizeof(dense_cam));
     if (!ix->ids)
-        ix->ids = (uint32_t *)keep(total * 4);
+        ix->ids = (uint32_t *)ix->mem.get(total * 4);
     dense_cam *cams = (dense_cam *)ix->cams;
     uint32_t *ids = ix->ids;
-    double *hits = (double *)get(total * 24);
-    uint32_t *parent = (uint32_t *)get(total * 4), *root = (uint32_t *)get(total * 4);
-    uint8_t *matched = (uint8_t *)get(total);
-    uint32_t *cand_img = (uint32_t *)get(max_batch_feats * DENSE_K * 4);
-    double2 *cand_px = (double2 *)get(max_batch_feats * DENSE_K * 16);
-    uint32_t *slot_dst = slot_dst_out ? (uint32_t *)get(max_batch_feats * DENSE_K * 4) : nullptr;
-    unsigned long long *counters = (unsigned long long *)get(2 * DENSE_COUNTERS * 8);
-    if (rc != OCHIP_OK)
-        return done(rc);
+    double *hits = (double *)mem.get(total * 24);
+    uint32_t *parent = (uint32_t *)mem.get(total * 4), *root = (uint32_t *)mem.get(total * 4);
+    uint8_t *matched = (uint8_t *)mem.get(total);
+    uint32_t *cand_img = (uint32_t *)mem.get(max_batch_feats * DENSE_K * 4);
+    double2 *cand_px = (double2 *)mem.get(max_batch_feats * DENSE_K * 16);
+    uint32_t *slot_dst = slot_dst_out ? (uint32_t *)mem.get(max_batch_feats * DENSE_K * 4) : nullptr;
+    unsigned long long *counters = (unsigned long long *)mem.get(2 * DENSE_COUNTERS * 8);
+    if (!cams || !ids || !hits || !parent || !root || !matched || !cand_img || !cand_px || (slot_dst_out && !slot_dst) || !counters)
+        return OCHIP_ENOMEM;
     static_assert(sizeof(dense_cam) == 17 * sizeof(double), "cams17 is the kernel's camera record");
     if (hipMemcpyAsync(cams, cams17, (size_t)n_images * sizeof(dense_cam), hipMemcpyHostToDevice, st) != hipSuccess ||
         hipMemcpyAsync(ids, id_of_pos, total * 4, hipMemcpyHostToDevice, st) != hipSuccess ||
         hipMemcpyAsync(hits, hits3, total * 24, hipMemcpyHostToDevice, st) != hipSuccess ||
         hipMemsetAsync(counters, 0, 2 * DENSE_COUNTERS * 8, st) != hipSuccess)
-        return done(ochip_fail(ctx, OCHIP_EHIP, "ochip_dense_link: upload failed"));
+        return ochip_fail(ctx, OCHIP_EHIP, "ochip_dense_link: upload failed");
     hipLaunchKernelGGL(dense_uf_init_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, parent, matched, total);
     const double inv_bits = 1.0 / (double)descriptor_bits;
     const bool unstaged_hook = ochip_test_hook("dense_predict_unstaged"); // (tests: the route of surveys above PRED_LDS_CAMS cameras)
@@ -993,12 +953,12 @@ int ochip_dense_link(ochip_dense_index *ix, const double *cams17, const uint32_t
                            slot_dst, counters + DENSE_COUNTERS);
         ochip_prof_end(ctx, OCHIP_K_DENSE, e0, e1);
         if (hipGetLastError() != hipSuccess)
-            return done(ochip_fail(ctx, OCHIP_EHIP, "ochip_dense_link: launch failed"));
+            return ochip_fail(ctx, OCHIP_EHIP, "ochip_dense_link: launch failed");
         if (slot_dst_out)
         {
             if (hipMemcpyAsync(slot_dst_out + base * DENSE_K, slot_dst, slots * 4, hipMemcpyDeviceToHost, st) != hipSuccess ||
                 ochip_stream_wait(ctx, st) != hipSuccess)
-                return done(ochip_fail(ctx, OCHIP_EHIP, "ochip_dense_link: reading the slots failed"));
+                return ochip_fail(ctx, OCHIP_EHIP, "ochip_dense_link: reading the slots failed");
         }
     }
     hipLaunchKernelGGL(dense_uf_roots_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, parent, matched, total, root);
@@ -1006,14 +966,15 @@ int ochip_dense_link(ochip_dense_index *ix, const double *cams17, const uint32_t
     if (hipGetLastError() != hipSuccess || hipMemcpyAsync(root_out, root, total * 4, hipMemcpyDeviceToHost, st) != hipSuccess ||
         hipMemcpyAsync(host_counts.data(), counters, 2 * DENSE_COUNTERS * 8, hipMemcpyDeviceToHost, st) != hipSuccess ||
         ochip_stream_wait(ctx, st) != hipSuccess)
-        return done(ochip_fail(ctx, OCHIP_EHIP, "ochip_dense_link: %s", hipGetErrorString(hipGetLastError())));
+        return ochip_fail(ctx, OCHIP_EHIP, "ochip_dense_link: %s", hipGetErrorString(hipGetLastError()));
     counts2[0] = counts2[1] = 0;
     for (int i = 0; i < DENSE_COUNTERS; i++)
     {
         counts2[0] += host_counts[i];
         counts2[1] += host_counts[DENSE_COUNTERS + i];
     }
-    return done(OCHIP_OK);
+    mem.release();
+    return OCHIP_OK;
 }
 
 int ochip_dense_triangulate(ochip_dense_index *ix, const double *cam_q4, uint32_t n_tracks, const uint32_t *track_start,
@@ -1037,38 +998,22 @@ int ochip_dense_triangulate(ochip_dense_index *ix, const double *cam_q4, uint32_
         if (track_member[m] >= total)
             return ochip_fail(ctx, OCHIP_EINVAL, "ochip_dense_triangulate: track member %llu is measurement %u of %llu", (unsigned long long)m,
                               track_member[m], (unsigned long long)total);
-    std::vector<std::pair<void *, size_t>> blocks;
-    int rc = OCHIP_OK;
-    auto get = [&](size_t bytes) -> void * {
-        size_t got = 0;
-        void *d = ochip_pool_get(ctx, bytes ? bytes : 16, &got);
-        if (!d)
-            rc = ochip_fail(ctx, OCHIP_ENOMEM, "ochip_dense_triangulate: device allocation of %zu bytes failed", bytes);
-        else
-            blocks.emplace_back(d, got);
-        return d;
-    };
-    auto done = [&](int code) {
-        (void)ochip_stream_wait(ctx, st);
-        for (auto &b : blocks)
-            ochip_pool_put(ctx, b.first, b.second);
-        return code;
-    };
-    double *q = (double *)get((size_t)ix->n_images * 32);
-    uint32_t *pos_of_id = (uint32_t *)get(total * 4);
-    uint32_t *start = (uint32_t *)get(((size_t)n_tracks + 1) * 4), *members = (uint32_t *)get(n_members * 4);
-    double *points = (double *)get((size_t)n_tracks * 24);
-    uint8_t *valid = (uint8_t *)get(n_tracks);
+    ochip::dev_scratch mem{ctx, "ochip_dense_triangulate"};
+    double *q = (double *)mem.get((size_t)ix->n_images * 32);
+    uint32_t *pos_of_id = (uint32_t *)mem.get(total * 4);
+    uint32_t *start = (uint32_t *)mem.get(((size_t)n_tracks + 1) * 4), *members = (uint32_t *)mem.get(n_members * 4);
+    double *points = (double *)mem.get((size_t)n_tracks * 24);
+    uint8_t *valid = (uint8_t *)mem.get(n_tracks);
     const uint32_t max_large = (uint32_t)(n_members / (TRI_LARGE + 1)) + 1;
-    uint32_t *large = (uint32_t *)get(((size_t)max_large + 1) * 4);
-    if (rc != OCHIP_OK)
-        return done(rc);
+    uint32_t *large = (uint32_t *)mem.get(((size_t)max_large + 1) * 4);
+    if (!q || !pos_of_id || !start || !members || !points || !valid || !large)
+        return OCHIP_ENOMEM;
     if (hipMemsetAsync(large + max_large, 0, 4, st) != hipSuccess)
-        return done(ochip_fail(ctx, OCHIP_EHIP, "ochip_dense_triangulate: memset failed"));
+        return ochip_fail(ctx, OCHIP_EHIP, "ochip_dense_triangulate: memset failed");
     if (hipMemcpyAsync(q, cam_q4, (size_t)ix->n_images * 32, hipMemcpyHostToDevice, st) != hipSuccess ||
         hipMemcpyAsync(start, track_start, ((size_t)n_tracks + 1) * 4, hipMemcpyHostToDevice, st) != hipSuccess ||
         (n_members && hipMemcpyAsync(members, track_member, n_members * 4, hipMemcpyHostToDevice, st) != hipSuccess))
-        return done(ochip_fail(ctx, OCHIP_EHIP, "ochip_dense_triangulate: upload failed"));
+        return ochip_fail(ctx, OCHIP_EHIP, "ochip_dense_triangulate: upload failed");
     hipLaunchKernelGGL(dense_pos_of_id_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, ix->ids, pos_of_id, total);
     dense_tri_args A{};
     A.meta = ix->meta;
@@ -1090,8 +1035,9 @@ int ochip_dense_triangulate(ochip_dense_index *ix, const double *cam_q4, uint32_
     hipLaunchKernelGGL(dense_triangulate_large_kernel, dim3((max_large + 3) / 4), dim3(256), 0, st, A);
     if (hipGetLastError() != hipSuccess || hipMemcpyAsync(points3_out, points, (size_t)n_tracks * 24, hipMemcpyDeviceToHost, st) != hipSuccess ||
         hipMemcpyAsync(valid_out, valid, n_tracks, hipMemcpyDeviceToHost, st) != hipSuccess || ochip_stream_wait(ctx, st) != hipSuccess)
-        return done(ochip_fail(ctx, OCHIP_EHIP, "ochip_dense_triangulate: %s", hipGetErrorString(hipGetLastError())));
-    return done(OCHIP_OK);
+        return ochip_fail(ctx, OCHIP_EHIP, "ochip_dense_triangulate: %s", hipGetErrorString(hipGetLastError()));
+    mem.release();
+    return OCHIP_OK;
 }
 
 } // extern "C"

@@ -395,11 +395,11 @@ namespace ochip
 
 // d_kp6 / d_desc / d_counts: the compacted keypoints of B images (stride max_kp) in detection order, on the device.
 // Enqueues everything on the context's stream and the copies into `out` (host arrays, page-locked ones copy at link
-// speed); the caller waits for the stream.  Device blocks are recorded in `allocs` (returned to the pool by the caller
-// after that wait).  `most`: the longest list of the chunk (rows are copied up to it).
-int feature_lists_enqueue(ochip_ctx *ctx, std::vector<std::pair<void *, size_t>> *allocs, uint32_t B, uint32_t max_kp,
-                          const float *d_kp6, const unsigned long long *d_desc, const unsigned int *d_counts, uint32_t most,
-                          int work_w, int work_h, double scale, double nms_radius, const ochip_feature_lists *out)
+// speed); the caller waits for the stream.  Device blocks are taken through `mem` (released by the caller after that
+// wait).  `most`: the longest list of the chunk (rows are copied up to it).
+int feature_lists_enqueue(ochip_ctx *ctx, dev_blocks &mem, uint32_t B, uint32_t max_kp, const float *d_kp6,
+                          const unsigned long long *d_desc, const unsigned int *d_counts, uint32_t most, int work_w, int work_h,
+                          double scale, double nms_radius, const ochip_feature_lists *out)
 {
     hipStream_t st = ctx->stream;
     if (B == 0)
@@ -426,13 +426,7 @@ int feature_lists_enqueue(ochip_ctx *ctx, std::vector<std::pair<void *, size_t>>
     F.counts = d_counts;
     F.scale = scale;
     const size_t N = (size_t)B * F.S;
-    auto dev = [&](size_t bytes) -> void * {
-        size_t got = 0;
-        void *p = ochip_pool_get(ctx, std::max<size_t>(bytes, 16), &got);
-        if (p)
-            allocs->emplace_back(p, got);
-        return p;
-    };
+    auto dev = [&](size_t bytes) { return mem.get(bytes); };
     // a suppression problem over the working image: cells a little larger than the radius, in the locations' units
     // (original-image pixels = working pixels / scale)
     bool alloc_ok = true;
@@ -476,7 +470,7 @@ int feature_lists_enqueue(ochip_ctx *ctx, std::vector<std::pair<void *, size_t>>
     unsigned char *conflict = (unsigned char *)dev(B), *conflict2 = (unsigned char *)dev(B);
     if (!F.n || !F.recs || !F.seg_begin || !F.seg_end || !F.resp || !F.loc || !F.slot_of_rank || !F.slot || !F.n_sparse || !F.records ||
         !F.sub_recs || !F.sub_begin || !F.sub_end || !F.sub_loc || !F.subset || !F.n_subset || !conflict || !conflict2)
-        return ochip_fail(ctx, OCHIP_ENOMEM, "feature lists: device allocation failed");
+        return OCHIP_ENOMEM; // (mem.get has set the message)
     // the reference's test is nn.distance * scale^2 > radius^2 on locations in original pixels (extract_features.cpp:72)
     nms_dev M8 = make_nms(F.n, F.loc, nms_radius / scale, scale * scale, nms_radius * nms_radius);
     // and nn.distance > spacing^2 for the subset (match_features.cpp:31), over the sparse features
@@ -484,7 +478,7 @@ int feature_lists_enqueue(ochip_ctx *ctx, std::vector<std::pair<void *, size_t>>
     if (want_subset)
         M40 = make_nms(F.n_sparse, F.sub_loc, out->subset_spacing, 1.0, out->subset_spacing * out->subset_spacing);
     if (!alloc_ok)
-        return ochip_fail(ctx, OCHIP_ENOMEM, "feature lists: device allocation failed");
+        return OCHIP_ENOMEM; // (mem.get has set the message)
     const dim3 wide((F.S + 255) / 256, 1, B);
     constexpr int rounds = 6; // (4 measured in round 5: the two launches saved cost the per-image finish more than they took;
                               // per image and suppression the rounds take 2.0, 0.9, 0.5 and then 0.18 us each: a later round with
@@ -509,7 +503,7 @@ int feature_lists_enqueue(ochip_ctx *ctx, std::vector<std::pair<void *, size_t>>
     // the strength order: std::sort by descending response from detection order, as the reference's (std_sort.hip);
     // conflict[b] = that image ran into introsort's depth limit and is the host's
     {
-        const int src = std_sort_enqueue(ctx, allocs, F.recs, N, F.seg_begin, F.seg_end, B, most, conflict);
+        const int src = std_sort_enqueue(ctx, mem, F.recs, N, F.seg_begin, F.seg_end, B, most, conflict);
         if (src != OCHIP_OK)
             return src;
     }
@@ -525,7 +519,7 @@ int feature_lists_enqueue(ochip_ctx *ctx, std::vector<std::pair<void *, size_t>>
         // spatially_subsample_feature_indices over the sparse list: indices std::sorted by strength from list order, then
         // the greedy 40 px pass in that order
         hipLaunchKernelGGL(feat_subset_ties_kernel, dim3(B), dim3(256), 0, st, F);
-        const int src = std_sort_enqueue(ctx, allocs, F.sub_recs, N, F.sub_begin, F.sub_end, B, most, conflict2);
+        const int src = std_sort_enqueue(ctx, mem, F.sub_recs, N, F.sub_begin, F.sub_end, B, most, conflict2);
         if (src != OCHIP_OK)
             return src;
         hipLaunchKernelGGL(feat_subset_loc_kernel, wide, dim3(256), 0, st, F);
@@ -562,12 +556,6 @@ extern "C" int ochip_feature_lists_from_keypoints(ochip_ctx *ctx, const float *k
         return OCHIP_EINVAL;
     OCHIP_HIP(ctx, hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
-    std::vector<std::pair<void *, size_t>> allocs;
-    auto cleanup = [&]() {
-        (void)ochip_stream_wait(ctx, st);
-        for (auto &a : allocs)
-            ochip_pool_put(ctx, a.first, a.second);
-    };
     uint32_t most = 0;
     for (uint32_t b = 0; b < n_images; b++)
     {
@@ -576,26 +564,19 @@ extern "C" int ochip_feature_lists_from_keypoints(ochip_ctx *ctx, const float *k
         most = std::max(most, counts[b]);
     }
     const size_t N = (size_t)n_images * max_kp;
-    size_t g0 = 0, g1 = 0, g2 = 0;
-    float *d_kp = (float *)ochip_pool_get(ctx, std::max<size_t>(N * 24, 16), &g0);
-    unsigned long long *d_desc = (unsigned long long *)ochip_pool_get(ctx, std::max<size_t>(N * 64, 16), &g1);
-    unsigned int *d_counts = (unsigned int *)ochip_pool_get(ctx, std::max<size_t>((size_t)n_images * 4, 16), &g2);
-    if (d_kp)
-        allocs.emplace_back(d_kp, g0);
-    if (d_desc)
-        allocs.emplace_back(d_desc, g1);
-    if (d_counts)
-        allocs.emplace_back(d_counts, g2);
-    int rc = OCHIP_OK;
-    if (!d_kp || !d_desc || !d_counts)
-        rc = ochip_fail(ctx, OCHIP_ENOMEM, "feature lists: device allocation failed");
+    dev_scratch mem{ctx, "ochip_feature_lists_from_keypoints"};
+    float *d_kp = (float *)mem.get(N * 24);
+    unsigned long long *d_desc = (unsigned long long *)mem.get(N * 64);
+    unsigned int *d_counts = (unsigned int *)mem.get((size_t)n_images * 4);
+    int rc = d_kp && d_desc && d_counts ? OCHIP_OK : OCHIP_ENOMEM;
     if (rc == OCHIP_OK && N &&
         (hipMemcpyAsync(d_kp, kp6, N * 24, hipMemcpyHostToDevice, st) != hipSuccess ||
          hipMemcpyAsync(d_desc, desc, N * 64, hipMemcpyHostToDevice, st) != hipSuccess ||
          hipMemcpyAsync(d_counts, counts, (size_t)n_images * 4, hipMemcpyHostToDevice, st) != hipSuccess))
         rc = ochip_fail(ctx, OCHIP_EHIP, "feature lists: upload failed");
     if (rc == OCHIP_OK)
-        rc = feature_lists_enqueue(ctx, &allocs, n_images, max_kp, d_kp, d_desc, d_counts, most, work_w, work_h, scale, nms_radius, out);
-    cleanup();
+        rc = feature_lists_enqueue(ctx, mem, n_images, max_kp, d_kp, d_desc, d_counts, most, work_w, work_h, scale, nms_radius, out);
+    (void)ochip_stream_wait(ctx, st);
+    mem.release();
     return rc;
 }

@@ -93,16 +93,15 @@ extern "C" int ochip_match_sort(ochip_ctx *ctx, const ochip_pair *pairs, uint32_
     hipLaunchKernelGGL(ratio_compact_kernel, dim3((n_pairs + 3) / 4), dim3(256), 0, st, (const ochip_match *)ctx->match_out_dev,
                        (const ochip_pair *)pairs_dev, (const uint32_t *)ctx->img_n_dev, n_pairs, (const unsigned int *)seg_begin, seg_end,
                        (unsigned long long *)ctx->ms_recs_dev);
-    std::vector<std::pair<void *, size_t>> allocs;
-    rc = std_sort_enqueue(ctx, &allocs, (unsigned long long *)ctx->ms_recs_dev, out_total, seg_begin, seg_end, n_pairs, max_n1,
+    dev_scratch mem{ctx, "ochip_match_sort"};
+    rc = std_sort_enqueue(ctx, mem, (unsigned long long *)ctx->ms_recs_dev, out_total, seg_begin, seg_end, n_pairs, max_n1,
                           (unsigned char *)ctx->ms_flag_dev);
     std::vector<unsigned int> end(n_pairs);
     if (rc == OCHIP_OK && (hipMemcpyAsync(end.data(), seg_end, (size_t)n_pairs * 4, hipMemcpyDeviceToHost, st) != hipSuccess ||
                            hipMemcpyAsync(fallback_out, ctx->ms_flag_dev, n_pairs, hipMemcpyDeviceToHost, st) != hipSuccess))
         rc = ochip_fail(ctx, OCHIP_EHIP, "ochip_match_sort: download failed");
     const hipError_t werr = ochip_stream_wait(ctx, st);
-    for (auto &a : allocs)
-        ochip_pool_put(ctx, a.first, a.second);
+    mem.release();
     if (rc == OCHIP_OK && werr != hipSuccess)
         rc = ochip_fail(ctx, OCHIP_EHIP, "ochip_match_sort: %s", hipGetErrorString(werr));
     if (rc == OCHIP_OK)

@@ -23,18 +23,9 @@ using namespace ochip_om;
 namespace
 {
 
-constexpr int TILE = 16;                 // pixels per tile side; one workgroup of 256 threads per tile
 constexpr int KNN = ochip_og::KNN; // context.imageGPSLocations.searchKnn({x, y}, 5) (ortho.cpp:586)
 constexpr int CAM_DOUBLES = 24;          // ochip_ortho_thumbnail's camera record
 constexpr uint32_t CAM_LDS_CHUNK = 1024; // camera XY staged in LDS per trip (16 KiB)
-
-struct raster_args
-{
-    double min_x, max_y, gsd, mean_camera_z;
-    int64_t row0, rows; // rows of this launch, from row0 of the raster
-    int32_t cols;
-    uint32_t tiles_x;
-};
 
 __device__ __forceinline__ bool tile_pixel(const raster_args &R, int *col, int64_t *row)
 {
@@ -170,19 +161,7 @@ __global__ __launch_bounds__(256) void ortho_thumbnail_kernel(mesh_args M, raste
 
 } // namespace
 
-namespace
-{
-
-raster_args make_raster(const double *raster4, int32_t cols, int64_t row0, int64_t rows)
-{
-    raster_args R;
-    R.min_x = raster4[0], R.max_y = raster4[1], R.gsd = raster4[2], R.mean_camera_z = raster4[3];
-    R.row0 = row0, R.rows = rows, R.cols = cols;
-    R.tiles_x = (uint32_t)((cols + TILE - 1) / TILE);
-    return R;
-}
-
-} // namespace
+constexpr auto ENQ = ochip::copy_mode::enqueue; // uploads are enqueued on the context's stream; the caller waits
 
 int ochip_ortho_mesh_create(ochip_ctx *ctx, uint32_t n_surfaces, const uint64_t *tri_off, const double *tri9,
                             ochip_ortho_mesh **out)
@@ -262,21 +241,22 @@ int ochip_ortho_mesh_create(ochip_ctx *ctx, uint32_t n_surfaces, const uint64_t 
     ochip_ortho_mesh *m = new (std::nothrow) ochip_ortho_mesh();
     if (!m)
         return ochip_fail(ctx, OCHIP_ENOMEM, "out of host memory");
-    m->ctx = ctx;
+    m->ctx = m->mem.ctx = ctx;
+    m->mem.what = "ochip_ortho_mesh_create";
     m->n_surfaces = n_surfaces;
     m->n_tris = (uint32_t)tri_off[n_surfaces];
-    int rc = pool_upload(ctx, m->blocks, (void **)&m->surf, surf.data(), surf.size() * sizeof(ortho_surf));
+    int rc = m->mem.upload(&m->surf, surf, ENQ);
     if (rc == OCHIP_OK)
-        rc = pool_upload(ctx, m->blocks, (void **)&m->cell_start, cell_start.data(), cell_start.size() * 4);
+        rc = m->mem.upload(&m->cell_start, cell_start, ENQ);
     if (rc == OCHIP_OK)
-        rc = pool_upload(ctx, m->blocks, (void **)&m->cell_tris, cell_tris.data(), cell_tris.size() * 4);
+        rc = m->mem.upload(&m->cell_tris, cell_tris, ENQ);
     if (rc == OCHIP_OK)
-        rc = pool_upload(ctx, m->blocks, (void **)&m->tris, tri9, (size_t)m->n_tris * 9 * sizeof(double));
+        rc = m->mem.upload(&m->tris, tri9, (size_t)m->n_tris * 9, ENQ);
     if (rc == OCHIP_OK && ochip_stream_wait(ctx, ctx->stream) != hipSuccess)
         rc = ochip_fail(ctx, OCHIP_EHIP, "stream wait failed (ortho mesh)");
     if (rc != OCHIP_OK)
     {
-        pool_release(ctx, m->blocks);
+        m->mem.release();
         delete m;
         return rc;
     }
@@ -288,7 +268,7 @@ void ochip_ortho_mesh_destroy(ochip_ortho_mesh *m)
 {
     if (!m)
         return;
-    pool_release(m->ctx, m->blocks);
+    m->mem.release();
     delete m;
 }
 
@@ -304,47 +284,41 @@ int ochip_ortho_dsm(ochip_ortho_mesh *m, const double *raster4, int32_t cols, in
     // launches of at most ~2^26 pixels: bounded scratch for host outputs, and a grid of at most 2^18 workgroups
     const int64_t tile_rows = std::max<int64_t>(1, (int64_t)(((int64_t)1 << 26) / ((int64_t)cols * TILE)));
     const int64_t chunk = tile_rows * TILE;
-    std::vector<std::pair<void *, size_t>> blocks;
+    ochip::dev_scratch mem{ctx, "ochip_ortho_dsm"};
     float *dev_out = nullptr;
     uint32_t *dev_tri = nullptr;
     double *dev_z64 = nullptr;
-    int rc = OCHIP_OK;
     const size_t chunk_px = (size_t)std::min(chunk, rows) * cols;
     if (!out_on_device)
-        rc = pool_upload(ctx, blocks, (void **)&dev_out, nullptr, chunk_px * sizeof(float));
-    if (rc == OCHIP_OK && tri_out)
-        rc = pool_upload(ctx, blocks, (void **)&dev_tri, nullptr, chunk_px * sizeof(uint32_t));
-    if (rc == OCHIP_OK && z64_out)
-        rc = pool_upload(ctx, blocks, (void **)&dev_z64, nullptr, chunk_px * sizeof(double));
-    for (int64_t r = 0; rc == OCHIP_OK && r < rows; r += chunk)
+        OCHIP_TRY(mem.alloc<float>(&dev_out, chunk_px));
+    if (tri_out)
+        OCHIP_TRY(mem.alloc<uint32_t>(&dev_tri, chunk_px));
+    if (z64_out)
+        OCHIP_TRY(mem.alloc<double>(&dev_z64, chunk_px));
+    for (int64_t r = 0; r < rows; r += chunk)
     {
         const int64_t n = std::min(chunk, rows - r);
         raster_args R = make_raster(raster4, cols, row0 + r, n);
         const uint32_t blocks_n = R.tiles_x * (uint32_t)((n + TILE - 1) / TILE);
-        float *o = out_on_device ? out + (size_t)r * cols : dev_out;
+        const size_t at = (size_t)r * cols, n_px = (size_t)n * cols;
+        float *o = out_on_device ? out + at : dev_out;
         hipLaunchKernelGGL(ortho_dsm_kernel, dim3(blocks_n), dim3(TILE * TILE), 0, ctx->stream, m->args(), R, o, dev_tri, dev_z64);
         if (hipGetLastError() != hipSuccess)
-            rc = ochip_fail(ctx, OCHIP_EHIP, "ortho_dsm_kernel launch failed");
-        if (rc == OCHIP_OK && !out_on_device &&
-            hipMemcpyAsync(out + (size_t)r * cols, dev_out, (size_t)n * cols * sizeof(float), hipMemcpyDeviceToHost,
-                           ctx->stream) != hipSuccess)
-            rc = ochip_fail(ctx, OCHIP_EHIP, "hipMemcpyAsync failed (DSM band)");
-        if (rc == OCHIP_OK && tri_out &&
-            hipMemcpyAsync(tri_out + (size_t)r * cols, dev_tri, (size_t)n * cols * sizeof(uint32_t), hipMemcpyDeviceToHost,
-                           ctx->stream) != hipSuccess)
-            rc = ochip_fail(ctx, OCHIP_EHIP, "hipMemcpyAsync failed (DSM triangles)");
-        if (rc == OCHIP_OK && z64_out &&
-            hipMemcpyAsync(z64_out + (size_t)r * cols, dev_z64, (size_t)n * cols * sizeof(double), hipMemcpyDeviceToHost,
-                           ctx->stream) != hipSuccess)
-            rc = ochip_fail(ctx, OCHIP_EHIP, "hipMemcpyAsync failed (DSM heights)");
-        if (rc == OCHIP_OK && (!out_on_device || tri_out || z64_out) && ochip_stream_wait(ctx, ctx->stream) != hipSuccess)
-            rc = ochip_fail(ctx, OCHIP_EHIP, "stream wait failed (DSM band)");
+            return ochip_fail(ctx, OCHIP_EHIP, "ortho_dsm_kernel launch failed");
+        if (!out_on_device)
+            OCHIP_TRY(copy_back(ctx, out + at, dev_out, n_px * sizeof(float), "DSM band"));
+        if (tri_out)
+            OCHIP_TRY(copy_back(ctx, tri_out + at, dev_tri, n_px * sizeof(uint32_t), "DSM triangles"));
+        if (z64_out)
+            OCHIP_TRY(copy_back(ctx, z64_out + at, dev_z64, n_px * sizeof(double), "DSM heights"));
+        if ((!out_on_device || tri_out || z64_out) && ochip_stream_wait(ctx, ctx->stream) != hipSuccess)
+            return ochip_fail(ctx, OCHIP_EHIP, "stream wait failed (DSM band)");
     }
     // the scratch goes back to the pool only once nothing can still write it
-    if (ochip_stream_wait(ctx, ctx->stream) != hipSuccess && rc == OCHIP_OK)
-        rc = ochip_fail(ctx, OCHIP_EHIP, "stream wait failed (DSM)");
-    pool_release(ctx, blocks);
-    return rc;
+    if (ochip_stream_wait(ctx, ctx->stream) != hipSuccess)
+        return ochip_fail(ctx, OCHIP_EHIP, "stream wait failed (DSM)");
+    mem.release();
+    return OCHIP_OK;
 }
 
 int ochip_ortho_thumbnail(ochip_ortho_mesh *m, const double *raster4, int32_t cols, int32_t rows, uint32_t n_cams,
@@ -366,45 +340,33 @@ int ochip_ortho_thumbnail(ochip_ortho_mesh *m, const double *raster4, int32_t co
     if (px == 0)
         return OCHIP_OK;
     OCHIP_HIP(ctx, hipSetDevice(ctx->device));
-    std::vector<std::pair<void *, size_t>> blocks;
+    ochip::dev_scratch mem{ctx, "ochip_ortho_thumbnail"};
     double *d_cams = nullptr, *d_z = nullptr;
     uint32_t *d_id = nullptr, *d_ids = nullptr, *d_tri = nullptr;
     uint64_t *d_off = nullptr;
     uint8_t *d_thumbs = nullptr, *d_rgba = nullptr;
-    int rc = pool_upload(ctx, blocks, (void **)&d_cams, cams24, (size_t)n_cams * CAM_DOUBLES * sizeof(double));
-    if (rc == OCHIP_OK)
-        rc = pool_upload(ctx, blocks, (void **)&d_id, cam_id, (size_t)n_cams * 4);
-    if (rc == OCHIP_OK)
-        rc = pool_upload(ctx, blocks, (void **)&d_off, thumb_off, (size_t)n_cams * 8);
-    if (rc == OCHIP_OK)
-        rc = pool_upload(ctx, blocks, (void **)&d_thumbs, thumbs, thumb_bytes);
-    if (rc == OCHIP_OK)
-        rc = pool_upload(ctx, blocks, (void **)&d_rgba, nullptr, px * 4);
-    if (rc == OCHIP_OK)
-        rc = pool_upload(ctx, blocks, (void **)&d_ids, nullptr, px * 4);
-    if (rc == OCHIP_OK && z_out)
-        rc = pool_upload(ctx, blocks, (void **)&d_z, nullptr, px * 8);
-    if (rc == OCHIP_OK && tri_out)
-        rc = pool_upload(ctx, blocks, (void **)&d_tri, nullptr, px * 4);
-    if (rc == OCHIP_OK)
-    {
-        raster_args R = make_raster(raster4, cols, 0, rows);
-        const uint32_t blocks_n = R.tiles_x * (uint32_t)((rows + TILE - 1) / TILE);
-        hipLaunchKernelGGL(ortho_thumbnail_kernel, dim3(blocks_n), dim3(TILE * TILE), 0, ctx->stream, m->args(), R, d_cams, n_cams,
-                           d_id, d_off, d_thumbs, d_rgba, d_ids, d_z, d_tri);
-        if (hipGetLastError() != hipSuccess)
-            rc = ochip_fail(ctx, OCHIP_EHIP, "ortho_thumbnail_kernel launch failed");
-    }
-    auto back = [&](void *dst, const void *src, size_t bytes) {
-        if (rc == OCHIP_OK && dst && hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess)
-            rc = ochip_fail(ctx, OCHIP_EHIP, "hipMemcpyAsync failed (thumbnail)");
-    };
-    back(rgba_out, d_rgba, px * 4);
-    back(id_out, d_ids, px * 4);
-    back(z_out, d_z, px * 8);
-    back(tri_out, d_tri, px * 4);
-    if (ochip_stream_wait(ctx, ctx->stream) != hipSuccess && rc == OCHIP_OK)
-        rc = ochip_fail(ctx, OCHIP_EHIP, "stream wait failed (thumbnail)");
-    pool_release(ctx, blocks);
-    return rc;
+    OCHIP_TRY(mem.upload(&d_cams, cams24, (size_t)n_cams * CAM_DOUBLES, ENQ));
+    OCHIP_TRY(mem.upload(&d_id, cam_id, n_cams, ENQ));
+    OCHIP_TRY(mem.upload(&d_off, thumb_off, n_cams, ENQ));
+    OCHIP_TRY(mem.upload(&d_thumbs, thumbs, thumb_bytes, ENQ));
+    OCHIP_TRY(mem.alloc<uint8_t>(&d_rgba, px * 4));
+    OCHIP_TRY(mem.alloc<uint32_t>(&d_ids, px));
+    if (z_out)
+        OCHIP_TRY(mem.alloc<double>(&d_z, px));
+    if (tri_out)
+        OCHIP_TRY(mem.alloc<uint32_t>(&d_tri, px));
+    raster_args R = make_raster(raster4, cols, 0, rows);
+    const uint32_t blocks_n = R.tiles_x * (uint32_t)((rows + TILE - 1) / TILE);
+    hipLaunchKernelGGL(ortho_thumbnail_kernel, dim3(blocks_n), dim3(TILE * TILE), 0, ctx->stream, m->args(), R, d_cams, n_cams, d_id,
+                       d_off, d_thumbs, d_rgba, d_ids, d_z, d_tri);
+    if (hipGetLastError() != hipSuccess)
+        return ochip_fail(ctx, OCHIP_EHIP, "ortho_thumbnail_kernel launch failed");
+    OCHIP_TRY(copy_back(ctx, rgba_out, d_rgba, px * 4, "thumbnail"));
+    OCHIP_TRY(copy_back(ctx, id_out, d_ids, px * 4, "thumbnail"));
+    OCHIP_TRY(copy_back(ctx, z_out, d_z, px * 8, "thumbnail"));
+    OCHIP_TRY(copy_back(ctx, tri_out, d_tri, px * 4, "thumbnail"));
+    if (ochip_stream_wait(ctx, ctx->stream) != hipSuccess)
+        return ochip_fail(ctx, OCHIP_EHIP, "stream wait failed (thumbnail)");
+    mem.release();
+    return OCHIP_OK;
 }

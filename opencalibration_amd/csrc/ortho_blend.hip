@@ -18,8 +18,7 @@
 #include <algorithm>
 #include <vector>
 
-using ochip_om::pool_release;
-using ochip_om::pool_upload;
+using ochip_om::copy_back;
 
 namespace
 {
@@ -242,19 +241,16 @@ void blend_levels(hipStream_t st, const ochip_ob::arena &Ar, const std::vector<o
         level(RECON, lv, 1);
 }
 
-int arena_alloc(ochip_ctx *ctx, std::vector<std::pair<void *, size_t>> &blocks, ochip_ob::arena *Ar)
+constexpr auto ENQ = ochip::copy_mode::enqueue; // uploads are enqueued on the context's stream; the caller waits
+
+int arena_alloc(ochip::dev_blocks &mem, ochip_ob::arena *Ar)
 {
     const size_t n = (size_t)Ar->n, L = (size_t)Ar->L;
-    int rc = pool_upload(ctx, blocks, (void **)&Ar->wr, nullptr, L * n * 4);
-    if (rc == OCHIP_OK)
-        rc = pool_upload(ctx, blocks, (void **)&Ar->wc, nullptr, L * n * 12);
-    if (rc == OCHIP_OK)
-        rc = pool_upload(ctx, blocks, (void **)&Ar->fl, nullptr, L * n * 12);
-    if (rc == OCHIP_OK)
-        rc = pool_upload(ctx, blocks, (void **)&Ar->g, nullptr, L * n * 12);
-    if (rc == OCHIP_OK)
-        rc = pool_upload(ctx, blocks, (void **)&Ar->bl, nullptr, n * 12);
-    return rc;
+    OCHIP_TRY(mem.alloc(&Ar->wr, L * n));
+    OCHIP_TRY(mem.alloc(&Ar->wc, L * n * 3));
+    OCHIP_TRY(mem.alloc(&Ar->fl, L * n * 3));
+    OCHIP_TRY(mem.alloc(&Ar->g, L * n * 3));
+    return mem.alloc(&Ar->bl, n * 3);
 }
 
 } // namespace
@@ -276,37 +272,28 @@ int ochip_laplacian_blend(ochip_ctx *ctx, int32_t num_layers, int32_t rows, int3
     std::vector<ochip_ob::tile_info> tiles;
     ochip_ob::arena Ar{num_layers, 0, nullptr, nullptr, nullptr, nullptr, nullptr};
     Ar.n = ochip_ob::tiles_build(std::max(rows, cols), rows, cols, pyramid_levels, &tiles);
-    std::vector<std::pair<void *, size_t>> blocks;
+    ochip::dev_scratch mem{ctx, "ochip_laplacian_blend"};
     float *d_lab = nullptr, *d_w = nullptr;
     uint8_t *d_out = nullptr;
     ochip_ol::lab_tables *d_tab = nullptr;
     ochip_ob::tile_info *d_tiles = nullptr;
-    int rc = pool_upload(ctx, blocks, (void **)&d_tab, &tables, sizeof tables);
-    if (rc == OCHIP_OK)
-        rc = pool_upload(ctx, blocks, (void **)&d_tiles, tiles.data(), tiles.size() * sizeof(ochip_ob::tile_info));
-    if (rc == OCHIP_OK)
-        rc = pool_upload(ctx, blocks, (void **)&d_lab, lab, (size_t)num_layers * px * 12);
-    if (rc == OCHIP_OK)
-        rc = pool_upload(ctx, blocks, (void **)&d_w, weight, (size_t)num_layers * px * 4);
-    if (rc == OCHIP_OK)
-        rc = pool_upload(ctx, blocks, (void **)&d_out, nullptr, px * 4);
-    if (rc == OCHIP_OK)
-        rc = arena_alloc(ctx, blocks, &Ar);
-    if (rc == OCHIP_OK)
-    {
-        const uint32_t grid = (uint32_t)((px + THREADS - 1) / THREADS);
-        hipLaunchKernelGGL(ortho_blend_seed, dim3(grid), dim3(THREADS), 0, ctx->stream, Ar, (int64_t)px, d_lab, d_w);
-        blend_levels(ctx->stream, Ar, tiles, d_tiles);
-        hipLaunchKernelGGL(ortho_blend_seed_out, dim3(grid), dim3(THREADS), 0, ctx->stream, d_tab, Ar, (int64_t)px, d_out);
-        if (hipGetLastError() != hipSuccess)
-            rc = ochip_fail(ctx, OCHIP_EHIP, "laplacian_blend kernel launch failed");
-    }
-    if (rc == OCHIP_OK && hipMemcpyAsync(bgra_out, d_out, px * 4, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess)
-        rc = ochip_fail(ctx, OCHIP_EHIP, "hipMemcpyAsync failed (laplacian blend)");
-    if (ochip_stream_wait(ctx, ctx->stream) != hipSuccess && rc == OCHIP_OK)
-        rc = ochip_fail(ctx, OCHIP_EHIP, "stream wait failed (laplacian blend)");
-    pool_release(ctx, blocks);
-    return rc;
+    OCHIP_TRY(mem.upload<ochip_ol::lab_tables>(&d_tab, &tables, 1, ENQ));
+    OCHIP_TRY(mem.upload(&d_tiles, tiles, ENQ));
+    OCHIP_TRY(mem.upload(&d_lab, lab, (size_t)num_layers * px * 3, ENQ));
+    OCHIP_TRY(mem.upload(&d_w, weight, (size_t)num_layers * px, ENQ));
+    OCHIP_TRY(mem.alloc(&d_out, px * 4));
+    OCHIP_TRY(arena_alloc(mem, &Ar));
+    const uint32_t grid = (uint32_t)((px + THREADS - 1) / THREADS);
+    hipLaunchKernelGGL(ortho_blend_seed, dim3(grid), dim3(THREADS), 0, ctx->stream, Ar, (int64_t)px, d_lab, d_w);
+    blend_levels(ctx->stream, Ar, tiles, d_tiles);
+    hipLaunchKernelGGL(ortho_blend_seed_out, dim3(grid), dim3(THREADS), 0, ctx->stream, d_tab, Ar, (int64_t)px, d_out);
+    if (hipGetLastError() != hipSuccess)
+        return ochip_fail(ctx, OCHIP_EHIP, "laplacian_blend kernel launch failed");
+    OCHIP_TRY(copy_back(ctx, bgra_out, d_out, px * 4, "laplacian blend"));
+    if (ochip_stream_wait(ctx, ctx->stream) != hipSuccess)
+        return ochip_fail(ctx, OCHIP_EHIP, "stream wait failed (laplacian blend)");
+    mem.release();
+    return OCHIP_OK;
 }
 
 int ochip_ortho_blend(ochip_ctx *ctx, const double *raster3, int32_t cols, int64_t row0, int64_t rows, const int32_t *config4,
@@ -340,13 +327,9 @@ int ochip_ortho_blend(ochip_ctx *ctx, const double *raster3, int32_t cols, int64
     const float steepness = (float)std::log(99.0) / (float)radius;
     const ochip_ob::color_model0 M0{vig0 ? 1 : 0, {vig0 ? vig0[0] : 0, vig0 ? vig0[1] : 0, vig0 ? vig0[2] : 0}};
 
-    std::vector<std::pair<void *, size_t>> blocks;
-    int rc = OCHIP_OK;
-    auto get = [&](void **dst, const void *src, size_t bytes) {
-        if (rc == OCHIP_OK)
-            rc = pool_upload(ctx, blocks, dst, src, bytes);
-    };
     const size_t Lpx = (size_t)L * px;
+    std::vector<int32_t> dist(dist_out ? px : 0); // (outlives the blocks: a copy into it may be in flight on an early return)
+    ochip::dev_scratch mem{ctx, "ochip_ortho_blend"};
     double *d_cams = nullptr;
     ochip_ob::id_entry *d_ids = nullptr;
     ochip_ol::lab_tables *d_lab = nullptr;
@@ -356,65 +339,57 @@ int ochip_ortho_blend(ochip_ctx *ctx, const double *raster3, int32_t cols, int64
     float *d_dsm = nullptr, *d_weight = nullptr, *d_labp = nullptr;
     int32_t *d_dist = nullptr;
     ochip_ob::arena Ar{L, n, nullptr, nullptr, nullptr, nullptr, nullptr};
-    get((void **)&d_cams, cams, (size_t)n_cams * ochip_ol::CAM_DOUBLES * sizeof(double));
-    get((void **)&d_ids, ids, (size_t)n_ids * sizeof(ochip_ob::id_entry));
-    get((void **)&d_lab, &tables, sizeof tables);
-    get((void **)&d_tiles, tiles.data(), tiles.size() * sizeof(ochip_ob::tile_info));
+    OCHIP_TRY(mem.upload(&d_cams, cams, (size_t)n_cams * ochip_ol::CAM_DOUBLES, ENQ));
+    OCHIP_TRY(mem.upload(&d_ids, (const ochip_ob::id_entry *)ids, n_ids, ENQ));
+    OCHIP_TRY(mem.upload<ochip_ol::lab_tables>(&d_lab, &tables, 1, ENQ));
+    OCHIP_TRY(mem.upload(&d_tiles, tiles, ENQ));
     if (!on_device)
     {
-        get((void **)&d_bgra, bgra, Lpx * 4);
-        get((void **)&d_id, id, Lpx * 8);
-        get((void **)&d_dsm, dsm, px * 4);
-        get((void **)&d_rgba, nullptr, px * 4);
+        OCHIP_TRY(mem.upload(&d_bgra, bgra, Lpx * 4, ENQ));
+        OCHIP_TRY(mem.upload(&d_id, id, Lpx, ENQ));
+        OCHIP_TRY(mem.upload(&d_dsm, dsm, px, ENQ));
+        OCHIP_TRY(mem.alloc(&d_rgba, px * 4));
     }
-    get((void **)&d_valid, nullptr, Lpx);
-    get((void **)&d_weight, nullptr, Lpx * 4);
-    get((void **)&d_labp, nullptr, Lpx * 12);
-    get((void **)&d_dist, nullptr, px * 4);
-    if (rc == OCHIP_OK)
-        rc = arena_alloc(ctx, blocks, &Ar);
-    if (rc == OCHIP_OK)
-    {
-        ochip_ob::band_view B{L,
-                              cols,
-                              rows,
-                              row0,
-                              raster3[0],
-                              raster3[1],
-                              raster3[2],
-                              on_device ? bgra : d_bgra,
-                              on_device ? id : d_id,
-                              on_device ? dsm : d_dsm,
-                              d_valid,
-                              d_weight,
-                              d_labp,
-                              d_dist};
-        uint8_t *rgba = on_device ? rgba_out : d_rgba;
-        const uint32_t grid = (uint32_t)((px + THREADS - 1) / THREADS);
-        hipStream_t st = ctx->stream;
-        hipLaunchKernelGGL(ortho_blend_prep, dim3(grid), dim3(THREADS), 0, st, d_lab, B, d_cams, d_ids, n_ids, M0);
-        hipLaunchKernelGGL(ortho_blend_chamfer, dim3(n_tiles), dim3(THREADS), 0, st, B, d_tiles);
-        hipLaunchKernelGGL(ortho_blend_weights, dim3(grid), dim3(THREADS), 0, st, B, Ar, d_tiles, TS, tiles_x, steepness);
-        blend_levels(st, Ar, tiles, d_tiles);
-        hipLaunchKernelGGL(ortho_blend_final, dim3(grid), dim3(THREADS), 0, st, d_lab, B, Ar, d_tiles, TS, tiles_x, rgba);
-        if (hipGetLastError() != hipSuccess)
-            rc = ochip_fail(ctx, OCHIP_EHIP, "ortho_blend kernel launch failed");
-    }
-    auto back = [&](void *dst, const void *src, size_t bytes) {
-        if (rc == OCHIP_OK && dst && bytes && hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess)
-            rc = ochip_fail(ctx, OCHIP_EHIP, "hipMemcpyAsync failed (ortho blend)");
-    };
+    OCHIP_TRY(mem.alloc(&d_valid, Lpx));
+    OCHIP_TRY(mem.alloc(&d_weight, Lpx));
+    OCHIP_TRY(mem.alloc(&d_labp, Lpx * 3));
+    OCHIP_TRY(mem.alloc(&d_dist, px));
+    OCHIP_TRY(arena_alloc(mem, &Ar));
+    ochip_ob::band_view B{L,
+                          cols,
+                          rows,
+                          row0,
+                          raster3[0],
+                          raster3[1],
+                          raster3[2],
+                          on_device ? bgra : d_bgra,
+                          on_device ? id : d_id,
+                          on_device ? dsm : d_dsm,
+                          d_valid,
+                          d_weight,
+                          d_labp,
+                          d_dist};
+    uint8_t *rgba = on_device ? rgba_out : d_rgba;
+    const uint32_t grid = (uint32_t)((px + THREADS - 1) / THREADS);
+    hipStream_t st = ctx->stream;
+    hipLaunchKernelGGL(ortho_blend_prep, dim3(grid), dim3(THREADS), 0, st, d_lab, B, d_cams, d_ids, n_ids, M0);
+    hipLaunchKernelGGL(ortho_blend_chamfer, dim3(n_tiles), dim3(THREADS), 0, st, B, d_tiles);
+    hipLaunchKernelGGL(ortho_blend_weights, dim3(grid), dim3(THREADS), 0, st, B, Ar, d_tiles, TS, tiles_x, steepness);
+    blend_levels(st, Ar, tiles, d_tiles);
+    hipLaunchKernelGGL(ortho_blend_final, dim3(grid), dim3(THREADS), 0, st, d_lab, B, Ar, d_tiles, TS, tiles_x, rgba);
+    if (hipGetLastError() != hipSuccess)
+        return ochip_fail(ctx, OCHIP_EHIP, "ortho_blend kernel launch failed");
+    const char *what = "ortho blend";
     if (!on_device)
-        back(rgba_out, d_rgba, px * 4);
-    back(weight_out, d_weight, Lpx * 4);
-    back(lab_out, d_labp, Lpx * 12);
-    std::vector<int32_t> dist(dist_out ? px : 0);
-    back(dist_out ? dist.data() : nullptr, d_dist, px * 4);
-    if (ochip_stream_wait(ctx, ctx->stream) != hipSuccess && rc == OCHIP_OK)
-        rc = ochip_fail(ctx, OCHIP_EHIP, "stream wait failed (ortho blend)");
-    if (rc == OCHIP_OK && dist_out)
+        OCHIP_TRY(copy_back(ctx, rgba_out, d_rgba, px * 4, what));
+    OCHIP_TRY(copy_back(ctx, weight_out, d_weight, Lpx * 4, what));
+    OCHIP_TRY(copy_back(ctx, lab_out, d_labp, Lpx * 12, what));
+    OCHIP_TRY(copy_back(ctx, dist_out ? dist.data() : nullptr, d_dist, px * 4, what));
+    if (ochip_stream_wait(ctx, st) != hipSuccess)
+        return ochip_fail(ctx, OCHIP_EHIP, "stream wait failed (ortho blend)");
+    mem.release();
+    if (dist_out)
         for (size_t i = 0; i < px; i++)
             dist_out[i] = ochip_ob::dist_float(dist[i]);
-    pool_release(ctx, blocks);
-    return rc;
+    return OCHIP_OK;
 }

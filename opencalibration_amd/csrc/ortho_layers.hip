@@ -26,21 +26,11 @@ using namespace ochip_om;
 namespace
 {
 
-constexpr int TILE = 16;            // pixels per side of a pass-1 workgroup's tile
-constexpr int THREADS = TILE * TILE;
+constexpr int THREADS = TILE * TILE; // a pass-1 workgroup's tile
 constexpr uint32_t CAND_CAP = 1024; // kNN candidates staged in LDS; a tile with more scans every camera
 constexpr int ITEMS = 16;           // pass-2 scan: counts per thread
 constexpr int CHUNK = THREADS * ITEMS;
 constexpr int KNN = ochip_ol::KNN;
-
-struct layer_args
-{
-    double min_x, max_y, gsd, mean_camera_z;
-    int64_t rows; // rows of the band (from the band's first row, row0 of the raster)
-    int64_t row0;
-    int32_t cols;
-    uint32_t tiles_x;
-};
 
 // the 5 smallest of two sorted lists of 5, sorted
 __device__ __forceinline__ void merge5(const double *a, const double *b, double *out)
@@ -53,7 +43,7 @@ __device__ __forceinline__ void merge5(const double *a, const double *b, double 
         out[k] = m[k];
 }
 
-__global__ __launch_bounds__(THREADS) void ortho_layers_pass1(mesh_args M, layer_args R, const double *__restrict__ cams,
+__global__ __launch_bounds__(THREADS) void ortho_layers_pass1(mesh_args M, raster_args R, const double *__restrict__ cams,
                                                               uint32_t n_cams, const uint8_t *const *__restrict__ images,
                                                               const uint64_t *__restrict__ node_ids,
                                                               const ochip_ol::lab_tables *__restrict__ lab,
@@ -323,7 +313,8 @@ int ochip_ortho_layers(ochip_ortho_mesh *m, const double *raster4, int32_t cols,
     ochip_ol::lab_tables_build(&tables);
     const size_t Lpx = (size_t)L * px;
     const uint32_t nb = (uint32_t)((px + CHUNK - 1) / CHUNK);
-    std::vector<std::pair<void *, size_t>> blocks;
+    constexpr auto ENQ = ochip::copy_mode::enqueue;
+    ochip::dev_scratch mem{ctx, "ochip_ortho_layers"};
     double *d_cams = nullptr;
     uint64_t *d_ids = nullptr, *d_images = nullptr, *d_bsum = nullptr, *d_id = nullptr;
     uint32_t *d_models = nullptr, *d_cam = nullptr, *d_knn = nullptr;
@@ -331,86 +322,67 @@ int ochip_ortho_layers(ochip_ortho_mesh *m, const double *raster4, int32_t cols,
     uint8_t *d_nvalid = nullptr, *d_bgra = nullptr, *d_counts = nullptr;
     float *d_fields = nullptr, *d_weight = nullptr;
     ochip_ol::corr_record *d_corr = nullptr;
-    int rc = pool_upload(ctx, blocks, (void **)&d_cams, cams, (size_t)n_cams * ochip_ol::CAM_DOUBLES * sizeof(double));
-    auto get = [&](void **dst, const void *src, size_t bytes) {
-        if (rc == OCHIP_OK)
-            rc = pool_upload(ctx, blocks, dst, src, bytes);
-    };
-    get((void **)&d_ids, node_ids, (size_t)n_cams * 8);
-    get((void **)&d_models, model_ids, (size_t)n_cams * 4);
-    get((void **)&d_images, images, (size_t)n_cams * 8);
-    get((void **)&d_lab, &tables, sizeof tables);
-    get((void **)&d_nvalid, nullptr, px);
-    get((void **)&d_cam, nullptr, Lpx * 4);
-    get((void **)&d_fields, nullptr, Lpx * 16);
-    get((void **)&d_counts, nullptr, px);
-    get((void **)&d_bsum, nullptr, ((size_t)nb + 1) * 8);
+    OCHIP_TRY(mem.upload(&d_cams, cams, (size_t)n_cams * ochip_ol::CAM_DOUBLES, ENQ));
+    OCHIP_TRY(mem.upload(&d_ids, node_ids, n_cams, ENQ));
+    OCHIP_TRY(mem.upload(&d_models, model_ids, n_cams, ENQ));
+    OCHIP_TRY(mem.upload(&d_images, images, n_cams, ENQ));
+    OCHIP_TRY(mem.upload<ochip_ol::lab_tables>(&d_lab, &tables, 1, ENQ));
+    OCHIP_TRY(mem.alloc<uint8_t>(&d_nvalid, px));
+    OCHIP_TRY(mem.alloc<uint32_t>(&d_cam, Lpx));
+    OCHIP_TRY(mem.alloc<float>(&d_fields, Lpx * 4));
+    OCHIP_TRY(mem.alloc<uint8_t>(&d_counts, px));
+    OCHIP_TRY(mem.alloc<uint64_t>(&d_bsum, (size_t)nb + 1));
     if (!out_on_device)
     {
-        get((void **)&d_bgra, nullptr, Lpx * 4);
-        get((void **)&d_id, nullptr, Lpx * 8);
+        OCHIP_TRY(mem.alloc<uint8_t>(&d_bgra, Lpx * 4));
+        OCHIP_TRY(mem.alloc<uint64_t>(&d_id, Lpx));
         if (weight_out)
-            get((void **)&d_weight, nullptr, Lpx * 4);
+            OCHIP_TRY(mem.alloc<float>(&d_weight, Lpx));
     }
     if (knn_out)
-        get((void **)&d_knn, nullptr, px * KNN * 4);
+        OCHIP_TRY(mem.alloc<uint32_t>(&d_knn, px * KNN));
     if (corr_capacity)
-        get((void **)&d_corr, nullptr, (size_t)corr_capacity * sizeof(ochip_ol::corr_record));
-    if (rc == OCHIP_OK)
-    {
-        const ochip_ol::band_planes B{L,
-                                      cols,
-                                      rows,
-                                      d_nvalid,
-                                      d_cam,
-                                      out_on_device ? bgra_out : d_bgra,
-                                      out_on_device ? id_out : d_id,
-                                      out_on_device ? weight_out : d_weight,
-                                      d_fields};
-        layer_args R;
-        R.min_x = raster4[0], R.max_y = raster4[1], R.gsd = raster4[2], R.mean_camera_z = raster4[3];
-        R.rows = rows, R.row0 = row0, R.cols = cols;
-        R.tiles_x = (uint32_t)((cols + TILE - 1) / TILE);
-        const uint64_t tiles = (uint64_t)R.tiles_x * (uint64_t)((rows + TILE - 1) / TILE);
-        if (tiles >= ((uint64_t)1 << 31))
-            rc = ochip_fail(ctx, OCHIP_EINVAL, "ochip_ortho_layers: band too large");
-        if (rc == OCHIP_OK)
-        {
-            hipLaunchKernelGGL(ortho_layers_pass1, dim3((uint32_t)tiles), dim3(THREADS), 0, ctx->stream, m->args(), R, d_cams,
-                               n_cams, (const uint8_t *const *)d_images, d_ids, d_lab, B, d_knn);
-            hipLaunchKernelGGL(ortho_layers_count, dim3((uint32_t)((px + THREADS - 1) / THREADS)), dim3(THREADS), 0,
-                               ctx->stream, B, K, d_counts);
-            hipLaunchKernelGGL(ortho_layers_block_sums, dim3(nb), dim3(THREADS), 0, ctx->stream, d_counts, (int64_t)px, d_bsum);
-            hipLaunchKernelGGL(ortho_layers_scan_top, dim3(1), dim3(THREADS), 0, ctx->stream, d_bsum, nb, d_bsum + nb);
-            hipLaunchKernelGGL(ortho_layers_write, dim3(nb), dim3(THREADS), 0, ctx->stream, d_lab, B, K, d_models, d_counts, d_bsum,
-                               d_corr, corr_capacity);
-            if (hipGetLastError() != hipSuccess)
-                rc = ochip_fail(ctx, OCHIP_EHIP, "ortho_layers kernel launch failed");
-        }
-    }
-    auto back = [&](void *dst, const void *src, size_t bytes) {
-        if (rc == OCHIP_OK && dst && bytes && hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess)
-            rc = ochip_fail(ctx, OCHIP_EHIP, "hipMemcpyAsync failed (ortho layers)");
-    };
+        OCHIP_TRY(mem.alloc<ochip_ol::corr_record>(&d_corr, (size_t)corr_capacity));
+    const ochip_ol::band_planes B{L,
+                                  cols,
+                                  rows,
+                                  d_nvalid,
+                                  d_cam,
+                                  out_on_device ? bgra_out : d_bgra,
+                                  out_on_device ? id_out : d_id,
+                                  out_on_device ? weight_out : d_weight,
+                                  d_fields};
+    const raster_args R = make_raster(raster4, cols, row0, rows);
+    const uint64_t tiles = (uint64_t)R.tiles_x * (uint64_t)((rows + TILE - 1) / TILE);
+    if (tiles >= ((uint64_t)1 << 31))
+        return ochip_fail(ctx, OCHIP_EINVAL, "ochip_ortho_layers: band too large");
+    hipLaunchKernelGGL(ortho_layers_pass1, dim3((uint32_t)tiles), dim3(THREADS), 0, ctx->stream, m->args(), R, d_cams, n_cams,
+                       (const uint8_t *const *)d_images, d_ids, d_lab, B, d_knn);
+    hipLaunchKernelGGL(ortho_layers_count, dim3((uint32_t)((px + THREADS - 1) / THREADS)), dim3(THREADS), 0, ctx->stream, B, K,
+                       d_counts);
+    hipLaunchKernelGGL(ortho_layers_block_sums, dim3(nb), dim3(THREADS), 0, ctx->stream, d_counts, (int64_t)px, d_bsum);
+    hipLaunchKernelGGL(ortho_layers_scan_top, dim3(1), dim3(THREADS), 0, ctx->stream, d_bsum, nb, d_bsum + nb);
+    hipLaunchKernelGGL(ortho_layers_write, dim3(nb), dim3(THREADS), 0, ctx->stream, d_lab, B, K, d_models, d_counts, d_bsum, d_corr,
+                       corr_capacity);
+    if (hipGetLastError() != hipSuccess)
+        return ochip_fail(ctx, OCHIP_EHIP, "ortho_layers kernel launch failed");
+    const char *what = "ortho layers";
     uint64_t total = 0;
-    back(&total, d_bsum + nb, 8);
+    OCHIP_TRY(copy_back(ctx, &total, d_bsum + nb, 8, what));
     if (!out_on_device)
     {
-        back(bgra_out, d_bgra, Lpx * 4);
-        back(id_out, d_id, Lpx * 8);
-        back(weight_out, d_weight, Lpx * 4);
+        OCHIP_TRY(copy_back(ctx, bgra_out, d_bgra, Lpx * 4, what));
+        OCHIP_TRY(copy_back(ctx, id_out, d_id, Lpx * 8, what));
+        OCHIP_TRY(copy_back(ctx, weight_out, d_weight, Lpx * 4, what));
     }
-    back(knn_out, d_knn, px * KNN * 4);
-    if (rc == OCHIP_OK && ochip_stream_wait(ctx, ctx->stream) != hipSuccess)
-        rc = ochip_fail(ctx, OCHIP_EHIP, "stream wait failed (ortho layers)");
-    if (rc == OCHIP_OK)
-    {
-        *n_corr = total;
-        back(corr_out, d_corr, (size_t)std::min<uint64_t>(total, corr_capacity) * sizeof(ochip_ol::corr_record));
-    }
+    OCHIP_TRY(copy_back(ctx, knn_out, d_knn, px * KNN * 4, what));
+    if (ochip_stream_wait(ctx, ctx->stream) != hipSuccess)
+        return ochip_fail(ctx, OCHIP_EHIP, "stream wait failed (ortho layers)");
+    *n_corr = total;
+    OCHIP_TRY(copy_back(ctx, corr_out, d_corr, (size_t)std::min<uint64_t>(total, corr_capacity) * sizeof(ochip_ol::corr_record), what));
     // the scratch goes back to the pool only once nothing can still write it
-    if (ochip_stream_wait(ctx, ctx->stream) != hipSuccess && rc == OCHIP_OK)
-        rc = ochip_fail(ctx, OCHIP_EHIP, "stream wait failed (ortho layers)");
-    pool_release(ctx, blocks);
-    return rc;
+    if (ochip_stream_wait(ctx, ctx->stream) != hipSuccess)
+        return ochip_fail(ctx, OCHIP_EHIP, "stream wait failed (ortho layers)");
+    mem.release();
+    return OCHIP_OK;
 }

@@ -6,8 +6,6 @@
 #include "ortho_geom.hpp"
 
 #include <cmath>
-#include <utility>
-#include <vector>
 
 namespace ochip_om
 {
@@ -51,24 +49,32 @@ __device__ __forceinline__ uint32_t mesh_height(const mesh_args &M, double x, do
     return MISS;
 }
 
-inline int pool_upload(ochip_ctx *ctx, std::vector<std::pair<void *, size_t>> &blocks, void **dst, const void *src, size_t bytes)
+// the rasters' tiling, shared by the preview / DSM kernels and the layered render
+constexpr int TILE = 16; // pixels per tile side; one workgroup of 256 threads per tile
+
+struct raster_args
 {
-    size_t got = 0;
-    void *d = ochip_pool_get(ctx, bytes ? bytes : 16, &got);
-    if (!d)
-        return ochip_fail(ctx, OCHIP_ENOMEM, "device allocation of %zu bytes failed (ortho)", bytes);
-    blocks.emplace_back(d, got);
-    if (src && bytes && hipMemcpyAsync(d, src, bytes, hipMemcpyHostToDevice, ctx->stream) != hipSuccess)
-        return ochip_fail(ctx, OCHIP_EHIP, "hipMemcpyAsync failed (ortho)");
-    *dst = d;
-    return OCHIP_OK;
+    double min_x, max_y, gsd, mean_camera_z;
+    int64_t row0, rows; // rows of this launch (band), from row0 of the raster
+    int32_t cols;
+    uint32_t tiles_x;
+};
+
+inline raster_args make_raster(const double *raster4, int32_t cols, int64_t row0, int64_t rows)
+{
+    raster_args R;
+    R.min_x = raster4[0], R.max_y = raster4[1], R.gsd = raster4[2], R.mean_camera_z = raster4[3];
+    R.row0 = row0, R.rows = rows, R.cols = cols;
+    R.tiles_x = (uint32_t)((cols + TILE - 1) / TILE);
+    return R;
 }
 
-inline void pool_release(ochip_ctx *ctx, std::vector<std::pair<void *, size_t>> &blocks)
+// enqueue the device-to-host copy of an output on the context's stream (dst == nullptr: the caller did not ask for it)
+inline int copy_back(ochip_ctx *ctx, void *dst, const void *src, size_t bytes, const char *what)
 {
-    for (auto &b : blocks)
-        ochip_pool_put(ctx, b.first, b.second);
-    blocks.clear();
+    if (dst && bytes && hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess)
+        return ochip_fail(ctx, OCHIP_EHIP, "hipMemcpyAsync failed (%s)", what);
+    return OCHIP_OK;
 }
 
 } // namespace ochip_om
@@ -80,7 +86,7 @@ struct ochip_ortho_mesh
     ochip_om::ortho_surf *surf = nullptr;
     uint32_t *cell_start = nullptr, *cell_tris = nullptr;
     double *tris = nullptr;
-    std::vector<std::pair<void *, size_t>> blocks;
+    ochip::dev_blocks mem;
     ochip_om::mesh_args args() const
     {
         return ochip_om::mesh_args{surf, cell_start, cell_tris, tris, n_surfaces};

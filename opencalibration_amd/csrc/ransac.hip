@@ -2755,21 +2755,9 @@ int ransac_homography_impl(ochip_ctx *ctx, const ochip_ransac_job *jobs, uint32_
             return rc;
     }
     OCHIP_HIP(ctx, hipMemcpyAsync(ctx->scratch_dev[S_JOBS], jobs, sizes[S_JOBS], hipMemcpyHostToDevice, ctx->stream));
-    std::vector<std::pair<void *, size_t>> allocs; // (std_sort's work space, returned to the pool after the wait below)
-    struct put_back
-    {
-        ochip_ctx *ctx;
-        std::vector<std::pair<void *, size_t>> *allocs;
-        ~put_back()
-        {
-            // an early error return can leave kernels in flight that still touch these blocks: the pool must not hand
-            // them to the next caller before the stream has drained (on the normal path it already has)
-            if (!allocs->empty())
-                (void)ochip_stream_wait(ctx, ctx->stream);
-            for (auto &a : *allocs)
-                ochip_pool_put(ctx, a.first, a.second);
-        }
-    } put_back_guard{ctx, &allocs};
+    // (an early error return can leave kernels in flight that still touch these blocks: dev_scratch waits for the stream before
+    // it hands them back; the normal path releases them after its own wait at the end)
+    ochip::dev_scratch mem{ctx, "ochip_ransac_homography_batch"};
     if (total_matches && !sorted_on_device)
     {
         OCHIP_HIP(ctx, hipMemcpyAsync(ctx->scratch_dev[S_MATCH], matches, (size_t)total_matches * sizeof(ochip_ransac_match),
@@ -2785,23 +2773,16 @@ int ransac_homography_impl(ochip_ctx *ctx, const ochip_ransac_job *jobs, uint32_
         uint32_t max_n = 0;
         for (uint32_t j = 0; j < n_jobs; j++)
             max_n = std::max(max_n, jobs[j].n);
-        size_t g0 = 0, g1 = 0, g2 = 0;
-        unsigned long long *prosac = (unsigned long long *)ochip_pool_get(ctx, (size_t)total_matches * 8, &g0);
-        unsigned int *seg2 = (unsigned int *)ochip_pool_get(ctx, (size_t)n_jobs * 8, &g1);
-        unsigned char *fb2 = (unsigned char *)ochip_pool_get(ctx, std::max<size_t>(n_jobs, 16), &g2);
-        if (prosac)
-            allocs.emplace_back(prosac, g0);
-        if (seg2)
-            allocs.emplace_back(seg2, g1);
-        if (fb2)
-            allocs.emplace_back(fb2, g2);
+        unsigned long long *prosac = (unsigned long long *)mem.get((size_t)total_matches * 8);
+        unsigned int *seg2 = (unsigned int *)mem.get((size_t)n_jobs * 8);
+        unsigned char *fb2 = (unsigned char *)mem.get(n_jobs);
         if (!prosac || !seg2 || !fb2)
-            return ochip_fail(ctx, OCHIP_ENOMEM, "device allocation failed (PROSAC order)");
+            return OCHIP_ENOMEM;
         hipLaunchKernelGGL(sorted_matches_kernel, dim3((max_n + 255) / 256, n_jobs), dim3(256), 0, ctx->stream,
                            (const ochip_ransac_job *)ctx->scratch_dev[S_JOBS], (const unsigned int *)ctx->ms_seg_dev,
                            (const unsigned long long *)ctx->ms_recs_dev, (const ochip_match *)ctx->match_out_dev,
                            (ochip_ransac_match *)ctx->scratch_dev[S_MATCH], prosac, seg2);
-        const int src = ochip::std_sort_enqueue(ctx, &allocs, prosac, total_matches, seg2, seg2 + n_jobs, n_jobs, max_n, fb2);
+        const int src = ochip::std_sort_enqueue(ctx, mem, prosac, total_matches, seg2, seg2 + n_jobs, n_jobs, max_n, fb2);
         if (src != OCHIP_OK)
             return src;
         hipLaunchKernelGGL(prosac_order_kernel, dim3((unsigned)((total_matches + 255) / 256)), dim3(256), 0, ctx->stream,
@@ -2829,11 +2810,9 @@ int ransac_homography_impl(ochip_ctx *ctx, const ochip_ransac_job *jobs, uint32_
         for (uint32_t j = 0; j < n_jobs; j++)
             order[j] = j;
         std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return jobs[a].n > jobs[b].n; });
-        size_t go = 0;
-        order_dev = (uint32_t *)ochip_pool_get(ctx, (size_t)n_jobs * 4, &go);
+        order_dev = (uint32_t *)mem.get((size_t)n_jobs * 4);
         if (!order_dev)
-            return ochip_fail(ctx, OCHIP_ENOMEM, "device allocation failed (launch order)");
-        allocs.emplace_back(order_dev, go);
+            return OCHIP_ENOMEM;
         OCHIP_HIP(ctx, hipMemcpyAsync(order_dev, order.data(), (size_t)n_jobs * 4, hipMemcpyHostToDevice, ctx->stream));
     }
     hipEvent_t e0, e1;
@@ -2869,11 +2848,9 @@ int ransac_homography_impl(ochip_ctx *ctx, const ochip_ransac_job *jobs, uint32_
 #endif
     if (decomp_out)
     {
-        size_t gd = 0;
-        ochip_decomposition *dec_dev = (ochip_decomposition *)ochip_pool_get(ctx, (size_t)n_jobs * sizeof(ochip_decomposition), &gd);
+        ochip_decomposition *dec_dev = (ochip_decomposition *)mem.get((size_t)n_jobs * sizeof(ochip_decomposition));
         if (!dec_dev)
-            return ochip_fail(ctx, OCHIP_ENOMEM, "device allocation failed (decompositions)");
-        allocs.emplace_back(dec_dev, gd);
+            return OCHIP_ENOMEM;
         hipLaunchKernelGGL(decompose_vote_kernel, dim3((n_jobs + 3) / 4), dim3(256), 0, ctx->stream,
                            (const ochip_ransac_job *)ctx->scratch_dev[S_JOBS], n_jobs, (const ochip_ransac_match *)ctx->scratch_dev[S_MATCH],
                            (const ochip_ransac_result *)res_dev, (const uint8_t *)inl_dev, rv, dec_dev);
@@ -2885,6 +2862,7 @@ int ransac_homography_impl(ochip_ctx *ctx, const ochip_ransac_job *jobs, uint32_
     if (total_matches)
         OCHIP_HIP(ctx, hipMemcpyAsync(inliers, inl_dev, (size_t)total_matches, hipMemcpyDeviceToHost, ctx->stream));
     OCHIP_HIP(ctx, ochip_stream_wait(ctx, ctx->stream));
+    mem.release();
     for (uint32_t j = 0; j < n_jobs; j++)
         ctx->ransac_hyp_corr += (uint64_t)results[j].iterations * jobs[j].n;
     return OCHIP_OK;
@@ -2907,21 +2885,12 @@ int ochip_edge_lists(ochip_ctx *ctx, uint32_t n_jobs, uint64_t total_matches, co
         return ochip_fail(ctx, OCHIP_ESTATE, "ochip_edge_lists must follow ochip_ransac_homography_batch_sorted of the same batch");
     OCHIP_HIP(ctx, hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
-    std::vector<std::pair<void *, size_t>> allocs;
-    auto dev = [&](size_t bytes) -> void * {
-        size_t got = 0;
-        void *p = ochip_pool_get(ctx, std::max<size_t>(bytes, 16), &got);
-        if (p)
-            allocs.emplace_back(p, got);
-        return p;
-    };
-    uint32_t *idx_dev = (uint32_t *)dev((size_t)n_keypoints * 4);
-    uint64_t *off_dev = (uint64_t *)dev((size_t)n_jobs * 8);
-    edge_feature_match *fm_dev = (edge_feature_match *)dev((size_t)total_matches * sizeof(edge_feature_match));
-    edge_inlier_match *fmd_dev = (edge_inlier_match *)dev((size_t)total_inliers * sizeof(edge_inlier_match));
-    int rc = OCHIP_OK;
-    if (!idx_dev || !off_dev || !fm_dev || !fmd_dev)
-        rc = ochip_fail(ctx, OCHIP_ENOMEM, "device allocation failed (edge lists)");
+    ochip::dev_scratch mem{ctx, "ochip_edge_lists"};
+    uint32_t *idx_dev = (uint32_t *)mem.get((size_t)n_keypoints * 4);
+    uint64_t *off_dev = (uint64_t *)mem.get((size_t)n_jobs * 8);
+    edge_feature_match *fm_dev = (edge_feature_match *)mem.get((size_t)total_matches * sizeof(edge_feature_match));
+    edge_inlier_match *fmd_dev = (edge_inlier_match *)mem.get((size_t)total_inliers * sizeof(edge_inlier_match));
+    int rc = idx_dev && off_dev && fm_dev && fmd_dev ? OCHIP_OK : OCHIP_ENOMEM;
     if (rc == OCHIP_OK && (hipMemcpyAsync(idx_dev, feature_index, (size_t)n_keypoints * 4, hipMemcpyHostToDevice, st) != hipSuccess ||
                            hipMemcpyAsync(off_dev, inlier_offset, (size_t)n_jobs * 8, hipMemcpyHostToDevice, st) != hipSuccess))
         rc = ochip_fail(ctx, OCHIP_EHIP, "upload failed (edge lists)");
@@ -2940,8 +2909,7 @@ int ochip_edge_lists(ochip_ctx *ctx, uint32_t n_jobs, uint64_t total_matches, co
             rc = ochip_fail(ctx, OCHIP_EHIP, "edge lists: launch or download failed");
     }
     const hipError_t werr = ochip_stream_wait(ctx, st);
-    for (auto &a : allocs)
-        ochip_pool_put(ctx, a.first, a.second);
+    mem.release();
     if (rc == OCHIP_OK && werr != hipSuccess)
         rc = ochip_fail(ctx, OCHIP_EHIP, "edge lists: %s", hipGetErrorString(werr));
     return rc;

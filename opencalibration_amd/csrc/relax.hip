@@ -575,7 +575,7 @@ struct ochip_relax_problem
 {
     ochip_ctx *ctx = nullptr;
     relax_dev dev{};
-    std::vector<std::pair<void *, size_t>> allocs; // device blocks from the context's pool (returned on destroy)
+    dev_blocks mem; // device blocks from the context's pool (released on destroy)
     int n_tangent = 0;
     std::vector<int32_t> cam_t;
     int32_t z_t[3] = {-1, -1, -1};
@@ -600,20 +600,8 @@ struct ochip_relax_problem
 
 namespace
 {
-template <typename T> int dev_upload(ochip_relax_problem *p, T **dst, const T *src, size_t n)
-{
-    size_t got = 0;
-    void *d = ochip_pool_get(p->ctx, (n ? n : 1) * sizeof(T), &got);
-    if (!d)
-        return ochip_fail(p->ctx, OCHIP_ENOMEM, "device allocation of %zu bytes failed in relax problem", n * sizeof(T));
-    p->allocs.emplace_back(d, got);
-    if (n && src) // on the context's stream: the device's default stream is a queue shared with every other context
-        if (hipMemcpyAsync(d, src, n * sizeof(T), hipMemcpyHostToDevice, p->ctx->stream) != hipSuccess ||
-            ochip_stream_wait(p->ctx, p->ctx->stream) != hipSuccess)
-            return ochip_fail(p->ctx, OCHIP_EHIP, "hipMemcpy failed in relax problem");
-    *dst = (T *)d;
-    return OCHIP_OK;
-}
+// uploads go on the context's stream (the device's default stream is a queue shared with every other context) and wait
+constexpr auto WAIT = copy_mode::enqueue_wait;
 
 int assign_tangent(ochip_relax_problem *p)
 {
@@ -847,7 +835,7 @@ int assign_tangent(ochip_relax_problem *p)
         hipMemcpy(p->dev.z_t, p->z_t, 12, hipMemcpyHostToDevice) != hipSuccess)
         return ochip_fail(p->ctx, OCHIP_EHIP, "hipMemcpy failed (tangent map)");
     p->sys.ctx = p->ctx;
-    p->sys.allocs = &p->allocs;
+    p->sys.allocs = &p->mem;
     p->sys.speculative = true; // (the candidate is evaluated with its Jacobian: plane_model::evaluate_candidate_jac)
     const int rrc = lm_system_resize(&p->sys, t, env);
     if (rrc != OCHIP_OK)
@@ -868,7 +856,8 @@ int ochip_relax_problem_create(ochip_ctx *ctx, const ochip_relax_desc *d, ochip_
     auto *p = new (std::nothrow) ochip_relax_problem();
     if (!p)
         return ochip_fail(ctx, OCHIP_ENOMEM, "host allocation failed");
-    p->ctx = ctx;
+    p->ctx = p->mem.ctx = ctx;
+    p->mem.what = "relax problem";
     p->n_cams = d->n_cams;
     for (uint32_t b = 0; b < d->n_blocks; b++)
         if (d->blk_cam_a[b] >= d->n_cams || d->blk_cam_b[b] >= d->n_cams || d->blk_cam_a[b] == d->blk_cam_b[b])
@@ -992,35 +981,35 @@ int ochip_relax_problem_create(ochip_ctx *ctx, const ochip_relax_desc *d, ochip_
         if (rc == OCHIP_OK)
             rc = r;
     };
-    chk(dev_upload(p, &D.cam_pos, d->cam_pos, (size_t)d->n_cams * 3));
-    chk(dev_upload(p, &D.cam_q, d->cam_q, (size_t)d->n_cams * 4));
-    chk(dev_upload(p, &D.cam_q2, d->cam_q, (size_t)d->n_cams * 4));
-    chk(dev_upload<int32_t>(p, &D.cam_t, nullptr, d->n_cams));
-    chk(dev_upload(p, &D.plane, plane, 12));
+    chk(p->mem.upload(&D.cam_pos, d->cam_pos, (size_t)d->n_cams * 3, WAIT));
+    chk(p->mem.upload(&D.cam_q, d->cam_q, (size_t)d->n_cams * 4, WAIT));
+    chk(p->mem.upload(&D.cam_q2, d->cam_q, (size_t)d->n_cams * 4, WAIT));
+    chk(p->mem.alloc<int32_t>(&D.cam_t, d->n_cams));
+    chk(p->mem.upload(&D.plane, plane, 12, WAIT));
     D.zcur = 6;
-    chk(dev_upload<int32_t>(p, &D.z_t, nullptr, 3));
-    chk(dev_upload(p, &D.blk_a, blk_a.data(), blk_a.size()));
-    chk(dev_upload(p, &D.blk_b, blk_b.data(), blk_b.size()));
-    chk(dev_upload(p, &D.blk_rays, (const double *)rays, (size_t)d->n_blocks * 6));
+    chk(p->mem.alloc<int32_t>(&D.z_t, 3));
+    chk(p->mem.upload(&D.blk_a, blk_a.data(), blk_a.size(), WAIT));
+    chk(p->mem.upload(&D.blk_b, blk_b.data(), blk_b.size(), WAIT));
+    chk(p->mem.upload(&D.blk_rays, (const double *)rays, (size_t)d->n_blocks * 6, WAIT));
     ochip_host_free(ctx, rays);
-    chk(dev_upload(p, &D.pair_off, pair_off.data(), pair_off.size()));
+    chk(p->mem.upload(&D.pair_off, pair_off.data(), pair_off.size(), WAIT));
     p->pair_p_h = pair_p;
     p->pair_q_h = pair_q;
-    chk(dev_upload(p, &D.pair_p, pair_p.data(), pair_p.size()));
-    chk(dev_upload(p, &D.pair_q, pair_q.data(), pair_q.size()));
-    chk(dev_upload(p, &D.cam_pair_off, cpo.data(), cpo.size()));
-    chk(dev_upload(p, &D.cam_pair_idx, cpi.data(), cpi.size()));
-    chk(dev_upload<double>(p, &D.pair_acc, nullptr, (size_t)n_pairs * ACC));
-    chk(dev_upload<double>(p, &D.pair_cost, nullptr, n_pairs));
-    chk(dev_upload<int32_t>(p, &p->fail_ranks, nullptr, 1));
+    chk(p->mem.upload(&D.pair_p, pair_p.data(), pair_p.size(), WAIT));
+    chk(p->mem.upload(&D.pair_q, pair_q.data(), pair_q.size(), WAIT));
+    chk(p->mem.upload(&D.cam_pair_off, cpo.data(), cpo.size(), WAIT));
+    chk(p->mem.upload(&D.cam_pair_idx, cpi.data(), cpi.size(), WAIT));
+    chk(p->mem.alloc<double>(&D.pair_acc, (size_t)n_pairs * ACC));
+    chk(p->mem.alloc<double>(&D.pair_cost, n_pairs));
+    chk(p->mem.alloc<int32_t>(&p->fail_ranks, 1));
     if (rc == OCHIP_OK && hipMemsetAsync(p->fail_ranks, 0, 4, ctx->stream) != hipSuccess) // (evaluations expect it clear and leave it clear)
         rc = ochip_fail(ctx, OCHIP_EHIP, "hipMemsetAsync failed in relax problem");
     D.fail = p->fail_ranks;
     D.pair_lo = 0;
     p->pair_hi = n_pairs;
     p->shard_chunk = n_pairs;
-    chk(dev_upload(p, &p->cam_has_prior, p->cam_has_prior_host.data(), p->cam_has_prior_host.size()));
-    chk(dev_upload(p, &p->cam_optimize_dev, p->cam_optimize.data(), p->cam_optimize.size()));
+    chk(p->mem.upload(&p->cam_has_prior, p->cam_has_prior_host.data(), p->cam_has_prior_host.size(), WAIT));
+    chk(p->mem.upload(&p->cam_optimize_dev, p->cam_optimize.data(), p->cam_optimize.size(), WAIT));
     if (rc == OCHIP_OK)
         rc = assign_tangent(p);
     if (rc != OCHIP_OK)
@@ -1038,8 +1027,7 @@ void ochip_relax_problem_destroy(ochip_relax_problem *p)
         return;
     (void)hipSetDevice(p->ctx->device);
     (void)ochip_stream_wait(p->ctx, p->ctx->stream);
-    for (auto &a : p->allocs)
-        ochip_pool_put(p->ctx, a.first, a.second);
+    p->mem.release();
     delete p;
 }
 
@@ -1069,9 +1057,9 @@ int ochip_relax_set_shard(ochip_relax_problem *p, uint32_t rank, uint32_t world,
             rc = r;
     };
     // record arrays padded to world equal slices so that the exchange is a plain in-place all-gather
-    chk(dev_upload<double>(p, &D.pair_acc, nullptr, (size_t)world * chunk * ACC));
-    chk(dev_upload<double>(p, &D.pair_cost, nullptr, (size_t)world * chunk));
-    chk(dev_upload<int32_t>(p, &p->fail_ranks, nullptr, world));
+    chk(p->mem.alloc<double>(&D.pair_acc, (size_t)world * chunk * ACC));
+    chk(p->mem.alloc<double>(&D.pair_cost, (size_t)world * chunk));
+    chk(p->mem.alloc<int32_t>(&p->fail_ranks, world));
     if (rc != OCHIP_OK)
         return rc;
     OCHIP_HIP(ctx, hipMemset(D.pair_acc, 0, (size_t)world * chunk * ACC * 8));
@@ -1197,7 +1185,7 @@ struct plane_model final : lm_model
         }
         if (!p->reduce_partials)
         {
-            const int arc = dev_upload<double>(p, &p->reduce_partials, nullptr, (size_t)REDUCE_GROUPS * 10 + 2);
+            const int arc = p->mem.alloc<double>(&p->reduce_partials, (size_t)REDUCE_GROUPS * 10 + 2);
             if (arc != OCHIP_OK)
                 return arc;
             p->reduce_arrived = reinterpret_cast<unsigned int *>(p->reduce_partials + (size_t)REDUCE_GROUPS * 10);
@@ -1353,7 +1341,7 @@ int ochip_relax_evaluate(ochip_relax_problem *p, int route, const double *delta,
         }
         if (host.size() > p->eval_scratch_cap)
         {
-            const int urc = dev_upload<double>(p, &p->eval_scratch, nullptr, host.size());
+            const int urc = p->mem.alloc<double>(&p->eval_scratch, host.size());
             if (urc != OCHIP_OK)
                 return urc;
             p->eval_scratch_cap = host.size();

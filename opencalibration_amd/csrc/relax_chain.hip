@@ -1978,7 +1978,7 @@ struct ochip_plane_chain
 {
     ochip_ctx *ctx = nullptr;
     chain_dev dev{};
-    std::vector<std::pair<void *, size_t>> allocs;
+    dev_blocks mem;
     unsigned int grid = 1;
     uint32_t n_cams = 0, n_steps = 0;
     chain_ctl *ctl_host = nullptr; // page-locked: the control block, then the abort flag (16 bytes), then the state [n_cams][4]
@@ -2010,8 +2010,7 @@ void ochip_plane_chain_destroy(ochip_plane_chain *c)
         return;
     (void)hipSetDevice(c->ctx->device);
     (void)ochip_stream_wait(c->ctx, c->ctx->stream);
-    for (auto &a : c->allocs)
-        ochip_pool_put(c->ctx, a.first, a.second);
+    c->mem.release();
     if (c->ctl_host)
         ochip_host_free(c->ctx, c->ctl_host);
     delete c;
@@ -2099,20 +2098,15 @@ int ochip_plane_chain_create(ochip_ctx *ctx, const ochip_plane_edge *edges, uint
     auto *c = new (std::nothrow) ochip_plane_chain();
     if (!c)
         return ochip_fail(ctx, OCHIP_ENOMEM, "host allocation failed");
-    c->ctx = ctx;
+    c->ctx = c->mem.ctx = ctx;
+    c->mem.what = "ochip_plane_chain_create";
     c->n_cams = n_cams;
     c->n_steps = n_steps;
     int rc = OCHIP_OK;
     auto dev = [&](size_t bytes) -> void * {
-        size_t got = 0;
-        void *p = ochip_pool_get(ctx, bytes ? bytes : 16, &got);
+        void *p = c->mem.get(bytes);
         if (!p)
-        {
-            if (rc == OCHIP_OK)
-                rc = ochip_fail(ctx, OCHIP_ENOMEM, "ochip_plane_chain_create: device allocation of %zu bytes failed", bytes);
-            return nullptr;
-        }
-        c->allocs.emplace_back(p, got);
+            rc = OCHIP_ENOMEM;
         return p;
     };
     // every input in ONE page-locked block, one copy

@@ -923,7 +923,7 @@ struct ochip_relaxg_problem
 {
     ochip_ctx *ctx = nullptr;
     g_dev dev{};
-    std::vector<std::pair<void *, size_t>> allocs;
+    dev_blocks mem;
     lm_system sys;
     uint32_t n_cams = 0, n_verts = 0, n_vars = 0, n_blocks = 0, n_rec = 0;
     bool structure_only = false;
@@ -972,14 +972,7 @@ constexpr uint32_t TAIL_CHUNK = 1024;  // most records per chunk of a tail owner
 constexpr uint32_t BAND_CHUNK = 512;  // a band owner with more than twice this many records is cut into chunks of this size
 constexpr uint32_t DENSE_VERTS = 8;   // a mesh of at most this many vertices is dense (plane, minimal mesh): tail
 
-template <typename T> int up(ochip_relaxg_problem *p, T **dst, const T *src, size_t n)
-{
-    return lm_dev_upload(p->ctx, &p->allocs, dst, src, n);
-}
-template <typename T> int up(ochip_relaxg_problem *p, T **dst, const std::vector<T> &v)
-{
-    return lm_dev_upload(p->ctx, &p->allocs, dst, v.data(), v.size());
-}
+constexpr auto BLOCKING = copy_mode::blocking;
 
 // Which unknown groups are variable, in which order, with which envelope; and the assembly plan.
 int assign(ochip_relaxg_problem *p)
@@ -1237,7 +1230,7 @@ int assign(ochip_relaxg_problem *p)
         }
     }
     p->sys.ctx = p->ctx;
-    p->sys.allocs = &p->allocs;
+    p->sys.allocs = &p->mem;
     p->sys.speculative = true; // (the candidate is evaluated with its Jacobian into the second set: general_model::evaluate_candidate_jac)
     int rc = lm_system_resize(&p->sys, n, env);
     if (rc != OCHIP_OK)
@@ -1301,15 +1294,15 @@ int assign(ochip_relaxg_problem *p)
         if (rc == OCHIP_OK)
             rc = r;
     };
-    chk(up(p, &p->items_dev, items));
-    chk(up(p, &p->tail_var_dev, tail_var));
-    chk(up(p, &p->tail_first_dev, tail_first));
-    chk(up(p, &p->tail_count_dev, tail_count));
-    chk(up<double>(p, &p->partials_dev, nullptr, (size_t)std::max<uint32_t>(n_partials, 1) * 3 * (T + 1)));
+    chk(p->mem.upload(&p->items_dev, items, BLOCKING));
+    chk(p->mem.upload(&p->tail_var_dev, tail_var, BLOCKING));
+    chk(p->mem.upload(&p->tail_first_dev, tail_first, BLOCKING));
+    chk(p->mem.upload(&p->tail_count_dev, tail_count, BLOCKING));
+    chk(p->mem.alloc<double>(&p->partials_dev, (size_t)std::max<uint32_t>(n_partials, 1) * 3 * (T + 1)));
     p->n_band_owners = (uint32_t)band_owners.size();
-    chk(up(p, &p->band_owners_dev, band_owners));
-    chk(up<double>(p, &p->band_partials_dev, nullptr, (size_t)std::max<int64_t>(band_doubles, 1)));
-    chk(up<double>(p, &p->cost_slices_dev, nullptr, (size_t)p->n_blocks / COST_SLICE + 2));
+    chk(p->mem.upload(&p->band_owners_dev, band_owners, BLOCKING));
+    chk(p->mem.alloc<double>(&p->band_partials_dev, (size_t)std::max<int64_t>(band_doubles, 1)));
+    chk(p->mem.alloc<double>(&p->cost_slices_dev, (size_t)p->n_blocks / COST_SLICE + 2));
     if (rc != OCHIP_OK)
         return rc;
     if (hipMemcpy(p->dev.var_t, p->var_t.data(), p->n_vars * 4, hipMemcpyHostToDevice) != hipSuccess ||
@@ -1562,7 +1555,8 @@ int ochip_relaxg_problem_create(ochip_ctx *ctx, const ochip_relaxg_desc *d, ochi
     auto *p = new (std::nothrow) ochip_relaxg_problem();
     if (!p)
         return ochip_fail(ctx, OCHIP_ENOMEM, "host allocation failed");
-    p->ctx = ctx;
+    p->ctx = p->mem.ctx = ctx;
+    p->mem.what = "relax problem";
     const uint32_t nc = d->n_cams, nv = d->n_verts, vf = nc + nv;
     p->n_cams = nc;
     p->n_verts = nv;
@@ -1788,35 +1782,35 @@ int ochip_relaxg_problem_create(ochip_ctx *ctx, const ochip_relaxg_desc *d, ochi
         if (rc == OCHIP_OK)
             rc = r;
     };
-    chk(up(p, &D.cam_pos, d->cam_pos, (size_t)nc * 3));
-    chk(up(p, &D.cam_q, d->cam_q, (size_t)nc * 4));
-    chk(up(p, &D.cam_q2, d->cam_q, (size_t)nc * 4));
-    chk(up(p, &D.vert_xy, d->vert_xy, (size_t)nv * 2));
-    chk(up(p, &D.vert_z, d->vert_z, (size_t)nv));
-    chk(up(p, &D.vert_z2, d->vert_z, (size_t)nv));
-    chk(up(p, &D.vert_z0, d->vert_z, (size_t)nv));
-    chk(up(p, &D.model, d->model, 8));
-    chk(up(p, &D.model2, d->model, 8));
-    chk(up<int32_t>(p, &D.var_t, nullptr, p->n_vars));
-    chk(up<uint8_t>(p, &D.var_ts, nullptr, p->n_vars));
-    chk(up(p, &D.blk_ray_off, blk_ray_off));
-    chk(up(p, &D.ray_cam, ray_cam));
-    chk(up(p, &D.blk_tri, blk_tri));
-    chk(up(p, &D.ray_dir, ray_dir));
-    chk(up(p, &D.ray_px, ray_px));
-    chk(up(p, &D.rec_type, p->rec_type));
-    chk(up(p, &D.rec_off, rec_off));
-    chk(up(p, &D.rec_var, p->rec_var));
-    chk(up<double>(p, &D.rec_data, nullptr, (size_t)rec_off[p->n_rec]));
-    chk(up<double>(p, &D.rec_cost, nullptr, p->n_rec));
-    chk(up<int32_t>(p, &p->fail_ranks, nullptr, world));
-    chk(up(p, &D.down_cam, d->down_cam, d->n_down));
-    chk(up(p, &D.diff_v, d->diff_v, (size_t)d->n_diff * 2));
-    chk(up(p, &D.smooth_v, d->smooth_v, (size_t)d->n_smooth * 4));
-    chk(up(p, &D.rel_cam, d->rel_cam, (size_t)d->n_rel * 2));
-    chk(up(p, &D.rel_pose, d->rel_pose, (size_t)d->n_rel * 32));
-    chk(up(p, &p->var_rec_dev, p->var_rec));
-    chk(up(p, &p->cam_optimize_dev, p->cam_optimize));
+    chk(p->mem.upload(&D.cam_pos, d->cam_pos, (size_t)nc * 3, BLOCKING));
+    chk(p->mem.upload(&D.cam_q, d->cam_q, (size_t)nc * 4, BLOCKING));
+    chk(p->mem.upload(&D.cam_q2, d->cam_q, (size_t)nc * 4, BLOCKING));
+    chk(p->mem.upload(&D.vert_xy, d->vert_xy, (size_t)nv * 2, BLOCKING));
+    chk(p->mem.upload(&D.vert_z, d->vert_z, (size_t)nv, BLOCKING));
+    chk(p->mem.upload(&D.vert_z2, d->vert_z, (size_t)nv, BLOCKING));
+    chk(p->mem.upload(&D.vert_z0, d->vert_z, (size_t)nv, BLOCKING));
+    chk(p->mem.upload(&D.model, d->model, 8, BLOCKING));
+    chk(p->mem.upload(&D.model2, d->model, 8, BLOCKING));
+    chk(p->mem.alloc<int32_t>(&D.var_t, p->n_vars));
+    chk(p->mem.alloc<uint8_t>(&D.var_ts, p->n_vars));
+    chk(p->mem.upload(&D.blk_ray_off, blk_ray_off, BLOCKING));
+    chk(p->mem.upload(&D.ray_cam, ray_cam, BLOCKING));
+    chk(p->mem.upload(&D.blk_tri, blk_tri, BLOCKING));
+    chk(p->mem.upload(&D.ray_dir, ray_dir, BLOCKING));
+    chk(p->mem.upload(&D.ray_px, ray_px, BLOCKING));
+    chk(p->mem.upload(&D.rec_type, p->rec_type, BLOCKING));
+    chk(p->mem.upload(&D.rec_off, rec_off, BLOCKING));
+    chk(p->mem.upload(&D.rec_var, p->rec_var, BLOCKING));
+    chk(p->mem.alloc<double>(&D.rec_data, (size_t)rec_off[p->n_rec]));
+    chk(p->mem.alloc<double>(&D.rec_cost, p->n_rec));
+    chk(p->mem.alloc<int32_t>(&p->fail_ranks, world));
+    chk(p->mem.upload(&D.down_cam, d->down_cam, d->n_down, BLOCKING));
+    chk(p->mem.upload(&D.diff_v, d->diff_v, (size_t)d->n_diff * 2, BLOCKING));
+    chk(p->mem.upload(&D.smooth_v, d->smooth_v, (size_t)d->n_smooth * 4, BLOCKING));
+    chk(p->mem.upload(&D.rel_cam, d->rel_cam, (size_t)d->n_rel * 2, BLOCKING));
+    chk(p->mem.upload(&D.rel_pose, d->rel_pose, (size_t)d->n_rel * 32, BLOCKING));
+    chk(p->mem.upload(&p->var_rec_dev, p->var_rec, BLOCKING));
+    chk(p->mem.upload(&p->cam_optimize_dev, p->cam_optimize, BLOCKING));
     if (rc == OCHIP_OK)
     {
         D.fail = p->fail_ranks + p->shard_rank;
@@ -1851,8 +1845,7 @@ void ochip_relaxg_problem_destroy(ochip_relaxg_problem *p)
         return;
     (void)hipSetDevice(p->ctx->device);
     (void)ochip_stream_wait(p->ctx, p->ctx->stream);
-    for (auto &a : p->allocs)
-        ochip_pool_put(p->ctx, a.first, a.second);
+    p->mem.release();
     delete p;
 }
 

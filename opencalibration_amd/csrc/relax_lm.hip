@@ -895,33 +895,33 @@ int lm_system_resize(lm_system *s, int n_in, const lm_envelope &env)
                 s->box[i] = 0.0;
         }
     }
-    if (lm_dev_upload(ctx, s->allocs, &s->first_col_dev, s->env.first_col.data(), s->env.first_col.size()) != OCHIP_OK)
+    if (s->allocs->upload(&s->first_col_dev, s->env.first_col.data(), s->env.first_col.size(), copy_mode::blocking) != OCHIP_OK)
         return ochip_fail(ctx, OCHIP_ENOMEM, "device allocation failed (envelope)");
     const size_t n = (size_t)std::max(n_in, 1);
     if (n > s->cap_n)
     {
         // (blocks of a smaller earlier size stay with the owner until it is destroyed)
-        if (lm_dev_upload<double>(ctx, s->allocs, &s->g, nullptr, n) != OCHIP_OK ||
-            lm_dev_upload<double>(ctx, s->allocs, &s->gs, nullptr, n) != OCHIP_OK ||
-            lm_dev_upload<double>(ctx, s->allocs, &s->scale, nullptr, n) != OCHIP_OK ||
-            lm_dev_upload<double>(ctx, s->allocs, &s->lm_diag, nullptr, n) != OCHIP_OK ||
-            lm_dev_upload<double>(ctx, s->allocs, &s->diag_tmp, nullptr, n) != OCHIP_OK ||
-            lm_dev_upload<double>(ctx, s->allocs, &s->diagonal, nullptr, n) != OCHIP_OK ||
-            lm_dev_upload<double>(ctx, s->allocs, &s->y, nullptr, n) != OCHIP_OK)
+        if (s->allocs->alloc<double>(&s->g, n) != OCHIP_OK ||
+            s->allocs->alloc<double>(&s->gs, n) != OCHIP_OK ||
+            s->allocs->alloc<double>(&s->scale, n) != OCHIP_OK ||
+            s->allocs->alloc<double>(&s->lm_diag, n) != OCHIP_OK ||
+            s->allocs->alloc<double>(&s->diag_tmp, n) != OCHIP_OK ||
+            s->allocs->alloc<double>(&s->diagonal, n) != OCHIP_OK ||
+            s->allocs->alloc<double>(&s->y, n) != OCHIP_OK)
             return ochip_fail(ctx, OCHIP_ENOMEM, "device allocation for the vectors of %zu unknowns failed", n);
         s->cap_n = n;
     }
     if (s->speculative && n > s->cap_n2)
     {
-        if (lm_dev_upload<double>(ctx, s->allocs, &s->g2, nullptr, n) != OCHIP_OK ||
-            lm_dev_upload<double>(ctx, s->allocs, &s->diagonal2, nullptr, n) != OCHIP_OK)
+        if (s->allocs->alloc<double>(&s->g2, n) != OCHIP_OK ||
+            s->allocs->alloc<double>(&s->diagonal2, n) != OCHIP_OK)
             return ochip_fail(ctx, OCHIP_ENOMEM, "device allocation for the second set of vectors of %zu unknowns failed", n);
         s->cap_n2 = n;
     }
     s->A2_clean = false;
-    if (!s->scal && lm_dev_upload<double>(ctx, s->allocs, &s->scal, nullptr, 8) != OCHIP_OK)
+    if (!s->scal && s->allocs->alloc<double>(&s->scal, 8) != OCHIP_OK)
         return OCHIP_ENOMEM;
-    if (!s->fail_chol && lm_dev_upload<int>(ctx, s->allocs, &s->fail_chol, nullptr, 1) != OCHIP_OK)
+    if (!s->fail_chol && s->allocs->alloc<int>(&s->fail_chol, 1) != OCHIP_OK)
         return OCHIP_ENOMEM;
 
     // ---- plan of the one-launch factorisation: the block envelope as tiles, their claim order
@@ -1079,14 +1079,14 @@ int lm_system_resize(lm_system *s, int n_in, const lm_envelope &env)
         if ((size_t)n_tiles > s->cap_tiles)
         {
             const size_t doubles = (size_t)std::max(n_tiles, 1) * NB * NB;
-            if (lm_dev_upload<double>(ctx, s->allocs, &s->A, nullptr, doubles) != OCHIP_OK ||
-                lm_dev_upload<double>(ctx, s->allocs, &s->Wm, nullptr, doubles) != OCHIP_OK)
+            if (s->allocs->alloc<double>(&s->A, doubles) != OCHIP_OK ||
+                s->allocs->alloc<double>(&s->Wm, doubles) != OCHIP_OK)
                 return ochip_fail(ctx, OCHIP_ENOMEM, "device allocation for the reduced system failed (%d tiles of 32 KB, twice)", n_tiles);
             s->cap_tiles = (size_t)n_tiles;
         }
         if (s->speculative && (size_t)n_tiles > s->cap_tiles2)
         {
-            if (lm_dev_upload<double>(ctx, s->allocs, &s->A2, nullptr, (size_t)std::max(n_tiles, 1) * NB * NB) != OCHIP_OK)
+            if (s->allocs->alloc<double>(&s->A2, (size_t)std::max(n_tiles, 1) * NB * NB) != OCHIP_OK)
                 return ochip_fail(ctx, OCHIP_ENOMEM, "device allocation for the candidate's reduced system failed (%d tiles of 32 KB)", n_tiles);
             s->cap_tiles2 = (size_t)n_tiles;
         }
@@ -1098,28 +1098,28 @@ int lm_system_resize(lm_system *s, int n_in, const lm_envelope &env)
             ctx->relax_system_dense_bytes = ((uint64_t)nn * nn + (uint64_t)(nn + 1) * nn) * 8; // what rounds 1-2 allocated
         }
         chol_col *cols_dev = nullptr;
-        if (lm_dev_upload(ctx, s->allocs, &s->tile_ij, stored.data(), stored.size()) != OCHIP_OK ||
-            lm_dev_upload(ctx, s->allocs, &cols_dev, cols.data(), cols.size()) != OCHIP_OK ||
-            lm_dev_upload(ctx, s->allocs, &s->chol_kmin, kmin.data(), kmin.size()) != OCHIP_OK ||
-            lm_dev_upload(ctx, s->allocs, &s->chol_tiles, order.data(), std::max<size_t>(order.size(), 1)) != OCHIP_OK ||
-            lm_dev_upload<unsigned int>(ctx, s->allocs, &s->chol_sync, nullptr, s->chol_sync_bytes / 4) != OCHIP_OK)
+        if (s->allocs->upload(&s->tile_ij, stored.data(), stored.size(), copy_mode::blocking) != OCHIP_OK ||
+            s->allocs->upload(&cols_dev, cols.data(), cols.size(), copy_mode::blocking) != OCHIP_OK ||
+            s->allocs->upload(&s->chol_kmin, kmin.data(), kmin.size(), copy_mode::blocking) != OCHIP_OK ||
+            s->allocs->upload(&s->chol_tiles, order.data(), std::max<size_t>(order.size(), 1), copy_mode::blocking) != OCHIP_OK ||
+            s->allocs->alloc<unsigned int>(&s->chol_sync, s->chol_sync_bytes / 4) != OCHIP_OK)
             return ochip_fail(ctx, OCHIP_ENOMEM, "device allocation failed (factorisation plan)");
         s->chol_cols = cols_dev;
         s->chol_korder = nullptr;
         if (s->n_regions > 1)
         {
-            if (lm_dev_upload(ctx, s->allocs, &s->chol_korder, korder.data(), korder.size()) != OCHIP_OK)
+            if (s->allocs->upload(&s->chol_korder, korder.data(), korder.size(), copy_mode::blocking) != OCHIP_OK)
                 return ochip_fail(ctx, OCHIP_ENOMEM, "device allocation failed (factorisation plan)");
         }
         else
             region_bounds = {0, std::min(tb, nbc)}; // one band: the backward substitution's one "region"
         {
             const size_t need = (size_t)s->n_regions * ((size_t)std::max(nn, 1) + 1);
-            if (lm_dev_upload(ctx, s->allocs, &s->region_dev, region_bounds.data(), region_bounds.size()) != OCHIP_OK)
+            if (s->allocs->upload(&s->region_dev, region_bounds.data(), region_bounds.size(), copy_mode::blocking) != OCHIP_OK)
                 return ochip_fail(ctx, OCHIP_ENOMEM, "device allocation failed (regions of the factorisation)");
             if (need > s->back_work_cap)
             {
-                if (lm_dev_upload<double>(ctx, s->allocs, &s->back_work, nullptr, need) != OCHIP_OK)
+                if (s->allocs->alloc<double>(&s->back_work, need) != OCHIP_OK)
                     return ochip_fail(ctx, OCHIP_ENOMEM, "device allocation failed (backward substitution, %d regions)", s->n_regions);
                 s->back_work_cap = need;
             }
@@ -1204,7 +1204,7 @@ int lm_linear_step(lm_system &S, double radius, const lm_step_args &a, bool *can
         {
             S.linv = nullptr;
             S.linv_cap = 0;
-            if (lm_dev_upload<double>(ctx, S.allocs, &S.linv, nullptr, need) != OCHIP_OK)
+            if (S.allocs->alloc<double>(&S.linv, need) != OCHIP_OK)
                 return ochip_fail(ctx, OCHIP_ENOMEM, "device allocation for the diagonal-block inverses failed");
             S.linv_cap = need;
         }
@@ -1243,13 +1243,13 @@ int lm_linear_step(lm_system &S, double radius, const lm_step_args &a, bool *can
     {
         const bool verify = a.verify; // run both on the same system and compare
         double *Wv = nullptr, *linv_v = nullptr;
-        size_t got_w = 0, got_l = 0;
+        dev_scratch verify_mem{ctx, "chol_verify"};
         if (verify)
         {
-            Wv = (double *)ochip_pool_get(ctx, S.matrix_bytes(), &got_w);
-            linv_v = (double *)ochip_pool_get(ctx, (size_t)((n + NB - 1) / NB) * NB * NB * 8, &got_l);
+            Wv = (double *)verify_mem.get(S.matrix_bytes());
+            linv_v = (double *)verify_mem.get((size_t)((n + NB - 1) / NB) * NB * NB * 8);
             if (!Wv || !linv_v)
-                return ochip_fail(ctx, OCHIP_ENOMEM, "chol_verify: device allocation failed");
+                return OCHIP_ENOMEM;
             OCHIP_HIP(ctx, hipMemcpyAsync(Wv, S.Wm, S.matrix_bytes(), hipMemcpyDeviceToDevice, st));
         }
         // operands through LDS in halves (71 KB per workgroup; whole, 104 KB, measured equal alone and slower beside the
@@ -1275,8 +1275,7 @@ int lm_linear_step(lm_system &S, double radius, const lm_step_args &a, bool *can
                 worst = std::max(worst, std::abs(ya[i] - yb[i]));
                 nan = nan || (std::isnan(ya[i]) != std::isnan(yb[i]));
             }
-            ochip_pool_put(ctx, Wv, got_w);
-            ochip_pool_put(ctx, linv_v, got_l);
+            verify_mem.release();
             const bool loud = ochip_verbose("relax");
             if (loud)
                 fprintf(stderr, "[ochip relax] factorisation check: n=%d forward solve differs by %.3g (scale %.3g)\n", n, worst, scale_y);
@@ -1700,22 +1699,10 @@ extern "C" int ochip_debug_lm_step(ochip_ctx *ctx, int n, const double *A, const
     if (n_region_begin > 0)
         env.region_begin.assign(region_begin, region_begin + n_region_begin);
     // the system and everything it allocates go back to the pool on the way out
-    struct owner
-    {
-        ochip_ctx *ctx = nullptr;
-        std::vector<std::pair<void *, size_t>> allocs;
-        lm_system S;
-        ~owner()
-        {
-            (void)ochip_stream_wait(ctx, ctx->stream);
-            for (auto &a : allocs)
-                ochip_pool_put(ctx, a.first, a.second);
-        }
-    } o;
-    o.ctx = ctx;
-    lm_system &S = o.S;
+    dev_scratch mem{ctx, "ochip_debug_lm_step"};
+    lm_system S;
     S.ctx = ctx;
-    S.allocs = &o.allocs;
+    S.allocs = &mem;
     int rc = lm_system_resize(&S, n, env);
     if (rc)
         return rc;
@@ -1749,9 +1736,9 @@ extern "C" int ochip_debug_lm_step(ochip_ctx *ctx, int n, const double *A, const
         OCHIP_HIP(ctx, hipMemcpy(S.g, g, (size_t)n * 8, hipMemcpyHostToDevice));
         OCHIP_HIP(ctx, hipMemcpy(S.scale, scale, (size_t)n * 8, hipMemcpyHostToDevice));
         OCHIP_HIP(ctx, hipMemcpy(S.diagonal, diagonal, (size_t)n * 8, hipMemcpyHostToDevice));
-        if (W_out && lm_dev_upload<double>(ctx, S.allocs, &w_built, nullptr, (size_t)S.chol_n_tiles * NB * NB) != OCHIP_OK)
+        if (W_out && S.allocs->alloc<double>(&w_built, (size_t)S.chol_n_tiles * NB * NB) != OCHIP_OK)
             return OCHIP_ENOMEM;
-        if (lm_dev_upload<double>(ctx, S.allocs, &y_dev, nullptr, (size_t)n) != OCHIP_OK)
+        if (S.allocs->alloc<double>(&y_dev, (size_t)n) != OCHIP_OK)
             return OCHIP_ENOMEM;
     }
     lm_step_args sa;
@@ -1798,5 +1785,6 @@ extern "C" int ochip_debug_lm_step(ochip_ctx *ctx, int n, const double *A, const
     info_out[5] = S.n_regions;
     info_out[6] = n > 0 ? sa.back : 0;
     info_out[7] = 0;
+    mem.release(); // (nothing was enqueued after the wait above)
     return OCHIP_OK;
 }

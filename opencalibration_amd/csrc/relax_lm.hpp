@@ -66,7 +66,7 @@ __device__ __forceinline__ size_t lm_at(const lm_matrix &M, int i, int j)
 struct lm_system
 {
     ochip_ctx *ctx = nullptr;
-    std::vector<std::pair<void *, size_t>> *allocs = nullptr; // device blocks are recorded here (owner returns them to the pool)
+    dev_blocks *allocs = nullptr; // device blocks are taken through this (the owner releases them)
     int n = 0;
     size_t cap_n = 0, linv_cap = 0, cap_tiles = 0;
     double *A = nullptr;       // J'J: packed lower triangle (lm_matrix), chol_n_tiles tiles; entries (i, j <= i), i < n
@@ -355,21 +355,5 @@ int lm_linear_step(lm_system &sys, double radius, const lm_step_args &args, bool
 // Jacobian through the generic route: swap_sets, evaluate(true, 1) with this as before_wait, swap_sets)
 void lm_launch_diag(lm_system &sys, const double *scale, const int32_t *fail_ranks = nullptr, int world = 0, int with_cost = 0,
                     int32_t *clear_after = nullptr);
-
-// shared by the flavours' problem_create: a device block from the context's pool, recorded in `allocs`
-template <typename T>
-inline int lm_dev_upload(ochip_ctx *ctx, std::vector<std::pair<void *, size_t>> *allocs, T **dst, const T *src, size_t n)
-{
-    size_t got = 0;
-    void *d = ochip_pool_get(ctx, (n ? n : 1) * sizeof(T), &got);
-    if (!d)
-        return ochip_fail(ctx, OCHIP_ENOMEM, "device allocation of %zu bytes failed in relax problem", n * sizeof(T));
-    allocs->emplace_back(d, got);
-    if (n && src)
-        if (hipMemcpy(d, src, n * sizeof(T), hipMemcpyHostToDevice) != hipSuccess)
-            return ochip_fail(ctx, OCHIP_EHIP, "hipMemcpy failed in relax problem");
-    *dst = (T *)d;
-    return OCHIP_OK;
-}
 
 } // namespace ochip

@@ -721,7 +721,7 @@ struct ochip_relaxp_problem
 {
     ochip_ctx *ctx = nullptr;
     p_dev dev{};
-    std::vector<std::pair<void *, size_t>> allocs;
+    dev_blocks mem;
     lm_system sys;
     uint32_t n_cams = 0, n_points = 0, n_groups = 0;
     std::vector<uint8_t> cam_optimize;
@@ -738,10 +738,7 @@ struct ochip_relaxp_problem
 namespace
 {
 
-template <typename T> int up(ochip_relaxp_problem *p, T **dst, const T *src, size_t n)
-{
-    return lm_dev_upload(p->ctx, &p->allocs, dst, src, n);
-}
+constexpr auto BLOCKING = copy_mode::blocking;
 
 // which unknowns are variable and where they sit in the reduced system (cameras in index order, then the lens model)
 int assign(ochip_relaxp_problem *p)
@@ -782,7 +779,7 @@ int assign(ochip_relaxp_problem *p)
     env.env_end.assign(nblk, 0);
     env.first_col.assign(nblk, 0);
     p->sys.ctx = p->ctx;
-    p->sys.allocs = &p->allocs;
+    p->sys.allocs = &p->mem;
     return lm_system_resize(&p->sys, t, env);
 }
 
@@ -967,7 +964,8 @@ int ochip_relaxp_problem_create(ochip_ctx *ctx, const ochip_relaxp_desc *d, ochi
     auto *p = new (std::nothrow) ochip_relaxp_problem();
     if (!p)
         return ochip_fail(ctx, OCHIP_ENOMEM, "host allocation failed");
-    p->ctx = ctx;
+    p->ctx = p->mem.ctx = ctx;
+    p->mem.what = "relax problem";
     p->n_cams = d->n_cams;
     p->n_points = d->n_points;
     p->n_groups = d->n_groups;
@@ -1014,32 +1012,32 @@ int ochip_relaxp_problem_create(ochip_ctx *ctx, const ochip_relaxp_desc *d, ochi
             rc = r;
     };
     const size_t np = d->n_points, nobs = 2 * np;
-    chk(up(p, &D.cam_pos, d->cam_pos, (size_t)d->n_cams * 3));
-    chk(up(p, &D.cam_q, d->cam_q, (size_t)d->n_cams * 4));
-    chk(up(p, &D.cam_q2, d->cam_q, (size_t)d->n_cams * 4));
-    chk(up(p, &D.model, d->model, 8));
-    chk(up(p, &D.model2, d->model, 8));
-    chk(up(p, &D.X, d->point_xyz, np * 3));
-    chk(up(p, &D.X2, d->point_xyz, np * 3));
-    chk(up<int32_t>(p, &D.cam_t, nullptr, d->n_cams));
-    chk(up(p, &D.grp_first, d->grp_first, (size_t)d->n_groups + 1));
-    chk(up(p, &D.grp_cam, d->grp_cam, (size_t)d->n_groups * 2));
-    chk(up(p, &D.pt_group, pt_group.data(), np));
-    chk(up(p, &D.obs_px, d->obs_px, nobs * 2));
-    chk(up<double>(p, &D.obs_J, nullptr, nobs * 2 * JW));
-    chk(up<double>(p, &D.obs_r, nullptr, nobs * 2));
-    chk(up<double>(p, &D.obs_cost, nullptr, nobs));
-    chk(up<double>(p, &D.pt_V, nullptr, np * 6));
-    chk(up<double>(p, &D.pt_g, nullptr, np * 3));
-    chk(up<double>(p, &D.pt_scale, nullptr, np * 3));
-    chk(up<double>(p, &D.pt_Vinv, nullptr, np * 6));
-    chk(up<double>(p, &D.pt_d, nullptr, np * 3));
-    chk(up<double>(p, &D.rec, nullptr, (size_t)std::max<uint32_t>(d->n_groups, 1) * RLEN));
-    chk(up<double>(p, &D.mono, nullptr, 16));
-    chk(up<int32_t>(p, &D.fail, nullptr, 1));
-    chk(up(p, &p->cam_grp_off, cam_grp_off.data(), cam_grp_off.size()));
-    chk(up(p, &p->cam_grp, cam_grp.data(), cam_grp.size()));
-    chk(up(p, &p->cam_optimize_dev, p->cam_optimize.data(), p->cam_optimize.size()));
+    chk(p->mem.upload(&D.cam_pos, d->cam_pos, (size_t)d->n_cams * 3, BLOCKING));
+    chk(p->mem.upload(&D.cam_q, d->cam_q, (size_t)d->n_cams * 4, BLOCKING));
+    chk(p->mem.upload(&D.cam_q2, d->cam_q, (size_t)d->n_cams * 4, BLOCKING));
+    chk(p->mem.upload(&D.model, d->model, 8, BLOCKING));
+    chk(p->mem.upload(&D.model2, d->model, 8, BLOCKING));
+    chk(p->mem.upload(&D.X, d->point_xyz, np * 3, BLOCKING));
+    chk(p->mem.upload(&D.X2, d->point_xyz, np * 3, BLOCKING));
+    chk(p->mem.alloc<int32_t>(&D.cam_t, d->n_cams));
+    chk(p->mem.upload(&D.grp_first, d->grp_first, (size_t)d->n_groups + 1, BLOCKING));
+    chk(p->mem.upload(&D.grp_cam, d->grp_cam, (size_t)d->n_groups * 2, BLOCKING));
+    chk(p->mem.upload(&D.pt_group, pt_group.data(), np, BLOCKING));
+    chk(p->mem.upload(&D.obs_px, d->obs_px, nobs * 2, BLOCKING));
+    chk(p->mem.alloc<double>(&D.obs_J, nobs * 2 * JW));
+    chk(p->mem.alloc<double>(&D.obs_r, nobs * 2));
+    chk(p->mem.alloc<double>(&D.obs_cost, nobs));
+    chk(p->mem.alloc<double>(&D.pt_V, np * 6));
+    chk(p->mem.alloc<double>(&D.pt_g, np * 3));
+    chk(p->mem.alloc<double>(&D.pt_scale, np * 3));
+    chk(p->mem.alloc<double>(&D.pt_Vinv, np * 6));
+    chk(p->mem.alloc<double>(&D.pt_d, np * 3));
+    chk(p->mem.alloc<double>(&D.rec, (size_t)std::max<uint32_t>(d->n_groups, 1) * RLEN));
+    chk(p->mem.alloc<double>(&D.mono, 16));
+    chk(p->mem.alloc<int32_t>(&D.fail, 1));
+    chk(p->mem.upload(&p->cam_grp_off, cam_grp_off.data(), cam_grp_off.size(), BLOCKING));
+    chk(p->mem.upload(&p->cam_grp, cam_grp.data(), cam_grp.size(), BLOCKING));
+    chk(p->mem.upload(&p->cam_optimize_dev, p->cam_optimize.data(), p->cam_optimize.size(), BLOCKING));
     if (rc == OCHIP_OK && np && hipMemset(D.pt_d, 0, np * 24) != hipSuccess)
         rc = ochip_fail(ctx, OCHIP_EHIP, "hipMemset failed");
     if (rc == OCHIP_OK)
@@ -1059,8 +1057,7 @@ void ochip_relaxp_problem_destroy(ochip_relaxp_problem *p)
         return;
     (void)hipSetDevice(p->ctx->device);
     (void)ochip_stream_wait(p->ctx, p->ctx->stream);
-    for (auto &a : p->allocs)
-        ochip_pool_put(p->ctx, a.first, a.second);
+    p->mem.release();
     delete p;
 }
 

@@ -224,7 +224,7 @@ struct ochip_plane_setup
     setup_dev dev{};
     uint64_t n_inliers = 0, total = 0;
     bool emitted = false;
-    std::vector<std::pair<void *, size_t>> allocs;
+    ochip::dev_blocks mem;
 };
 
 extern "C"
@@ -235,8 +235,7 @@ void ochip_plane_setup_destroy(ochip_plane_setup *s)
     if (!s)
         return;
     (void)ochip_stream_wait(s->ctx, s->ctx->stream);
-    for (auto &a : s->allocs)
-        ochip_pool_put(s->ctx, a.first, a.second);
+    s->mem.release();
     delete s;
 }
 
@@ -258,20 +257,15 @@ int ochip_plane_setup_create(ochip_ctx *ctx, const ochip_plane_edge *edges, uint
     OCHIP_HIP(ctx, hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
     auto *s = new ochip_plane_setup();
-    s->ctx = ctx;
+    s->ctx = s->mem.ctx = ctx;
+    s->mem.what = "ochip_plane_setup_create";
     s->n_inliers = n_inliers;
     int rc = OCHIP_OK;
-    auto up = [&](const void *src, size_t bytes) -> void * {
-        size_t got = 0;
-        void *p = ochip_pool_get(ctx, bytes ? bytes : 16, &got);
-        if (!p)
-        {
-            rc = ochip_fail(ctx, OCHIP_ENOMEM, "ochip_plane_setup_create: device allocation of %zu bytes failed", bytes);
-            return nullptr;
-        }
-        s->allocs.emplace_back(p, got);
-        if (src && bytes && hipMemcpyAsync(p, src, bytes, hipMemcpyHostToDevice, st) != hipSuccess)
-            rc = ochip_fail(ctx, OCHIP_EHIP, "ochip_plane_setup_create: upload failed");
+    auto up = [&](const void *src, size_t bytes) -> void * { // (enqueued: the wait below covers the pageable sources)
+        void *p = nullptr;
+        const int urc = s->mem.upload_bytes(&p, src, bytes, ochip::copy_mode::enqueue);
+        if (rc == OCHIP_OK)
+            rc = urc;
         return p;
     };
     setup_dev &D = s->dev;

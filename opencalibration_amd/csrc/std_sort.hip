@@ -718,20 +718,13 @@ namespace ochip
 // Sorts the segments [seg_begin[s], seg_end[s]) of recs (device arrays) in place as std::sort with comp(a, b) =
 // key(a) > key(b) would; fallback[s] != 0: the segment needs libstdc++'s heap sort and was left partly sorted (its records
 // are a permutation of the input).  Enqueued on the context's stream.
-int std_sort_enqueue(ochip_ctx *ctx, std::vector<std::pair<void *, size_t>> *allocs, unsigned long long *recs, size_t total_len,
-                     const unsigned int *seg_begin, const unsigned int *seg_end, uint32_t n_segs, uint32_t max_len,
-                     unsigned char *fallback)
+int std_sort_enqueue(ochip_ctx *ctx, dev_blocks &mem, unsigned long long *recs, size_t total_len, const unsigned int *seg_begin,
+                     const unsigned int *seg_end, uint32_t n_segs, uint32_t max_len, unsigned char *fallback)
 {
     hipStream_t st = ctx->stream;
     if (n_segs == 0 || total_len == 0)
         return OCHIP_OK;
-    auto dev = [&](size_t bytes) -> void * {
-        size_t got = 0;
-        void *p = ochip_pool_get(ctx, std::max<size_t>(bytes, 16), &got);
-        if (p)
-            allocs->emplace_back(p, got);
-        return p;
-    };
+    auto dev = [&](size_t bytes) { return mem.get(bytes); };
     sort_dev S{};
     S.A = recs;
     S.cap_queue = (unsigned int)(total_len / (THRESHOLD + 1) + n_segs + 1);
@@ -752,7 +745,7 @@ int std_sort_enqueue(ochip_ctx *ctx, std::vector<std::pair<void *, size_t>> *all
     S.counts = (unsigned int *)dev(16 * 4);
     S.fallback = fallback;
     if (!S.heap || !S.listL || !S.listR || !S.queue[0] || !S.queue[1] || !S.queue[2] || !S.big[0] || !S.big[1] || !S.big[2] || !S.final_ranges || !S.local || !S.counts)
-        return ochip_fail(ctx, OCHIP_ENOMEM, "std_sort: device allocation failed");
+        return OCHIP_ENOMEM; // (mem.get has set the message)
     S.error = S.counts + 8;
     OCHIP_HIP(ctx, hipMemsetAsync(S.counts, 0, 16 * 4, st));
     // a workgroup per segment walks the levels above LOCAL by itself when there are enough segments to fill the device that
@@ -829,37 +822,25 @@ extern "C" int ochip_debug_std_sort(ochip_ctx *ctx, const uint32_t *keys, const 
         se[s] = offsets[s + 1];
         max_len = std::max(max_len, se[s] - sb[s]);
     }
-    std::vector<std::pair<void *, size_t>> allocs;
-    auto cleanup = [&]() {
-        (void)ochip_stream_wait(ctx, st);
-        for (auto &a : allocs)
-            ochip_pool_put(ctx, a.first, a.second);
-    };
-    auto dev = [&](size_t bytes) -> void * {
-        size_t got = 0;
-        void *p = ochip_pool_get(ctx, std::max<size_t>(bytes, 16), &got);
-        if (p)
-            allocs.emplace_back(p, got);
-        return p;
-    };
+    ochip::dev_scratch mem{ctx, "ochip_debug_std_sort"};
+    auto dev = [&](size_t bytes) { return mem.get(bytes); };
     unsigned long long *d_recs = (unsigned long long *)dev(recs.size() * 8);
     unsigned int *d_sb = (unsigned int *)dev((size_t)n_segs * 4), *d_se = (unsigned int *)dev((size_t)n_segs * 4);
     unsigned char *d_fb = (unsigned char *)dev(std::max<uint32_t>(n_segs, 1));
-    int rc = OCHIP_OK;
-    if (!d_recs || !d_sb || !d_se || !d_fb)
-        rc = ochip_fail(ctx, OCHIP_ENOMEM, "std_sort: device allocation failed");
+    int rc = d_recs && d_sb && d_se && d_fb ? OCHIP_OK : OCHIP_ENOMEM;
     if (rc == OCHIP_OK && n_segs &&
         (hipMemcpyAsync(d_recs, recs.data(), recs.size() * 8, hipMemcpyHostToDevice, st) != hipSuccess ||
          hipMemcpyAsync(d_sb, sb.data(), (size_t)n_segs * 4, hipMemcpyHostToDevice, st) != hipSuccess ||
          hipMemcpyAsync(d_se, se.data(), (size_t)n_segs * 4, hipMemcpyHostToDevice, st) != hipSuccess))
         rc = ochip_fail(ctx, OCHIP_EHIP, "std_sort: upload failed");
     if (rc == OCHIP_OK)
-        rc = std_sort_enqueue(ctx, &allocs, d_recs, total, d_sb, d_se, n_segs, max_len, d_fb);
+        rc = std_sort_enqueue(ctx, mem, d_recs, total, d_sb, d_se, n_segs, max_len, d_fb);
     if (rc == OCHIP_OK && n_segs &&
         (hipMemcpyAsync(recs.data(), d_recs, recs.size() * 8, hipMemcpyDeviceToHost, st) != hipSuccess ||
          hipMemcpyAsync(fallback_out, d_fb, n_segs, hipMemcpyDeviceToHost, st) != hipSuccess))
         rc = ochip_fail(ctx, OCHIP_EHIP, "std_sort: download failed");
-    cleanup();
+    (void)ochip_stream_wait(ctx, st);
+    mem.release();
     if (rc == OCHIP_OK)
         for (size_t i = 0; i < total; i++)
         {
