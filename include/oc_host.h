@@ -435,6 +435,59 @@ extern "C"
                                double *pixel2, double *J4);
     void och_ortho_sample_fields(double pixel_x, double pixel_y, int32_t width, int32_t height, float camera_distance,
                                  double cos_view, float *out5);
+    /* ---- the layered render with streamed source images (opencalibration_amd/csrc/host/ortho_stream.cpp,
+     * ortho_residency.hpp; the reference's findTileCameras, LRU image cache and prefetch thread, src/ortho/ortho.cpp:
+     * 1010-1066, 1501-1539) ------------------------------------------------------------------------------------------------
+     * och_ortho_band_cameras: the raster rows x cols (raster4 = {min_x, max_y, gsd, mean_camera_z}) cut into bands of
+     * band_rows rows (a multiple of the tile size; the last may be shorter); used [n_bands][n_cams] = 1 exactly when
+     * camera i (cams [n_cams][28], och_ortho_layers_cameras') is among the 5 nearest in XY (squared distance, then camera
+     * order) of at least one pixel of band b, whatever the pixel's height: a superset of what the band's render reads,
+     * independent of the DSM.  ctx == NULL: the CPU route (brute force), else ochip_ortho_band_cameras.
+     * och_ortho_layers_render_subset: och_ortho_layers_render over the cameras subset [n_subset] alone (ascending, unique
+     * indices into och_ortho_layers_cameras' order, refused otherwise); images and image_hw have n_subset entries.  A
+     * subset that holds the band's set of och_ortho_band_cameras gives the full table's BGRA, ids, weights and
+     * correspondences bit for bit; knn_out names full-table indices.
+     * och_ortho_residency_plan: ortho_residency.hpp's rule over the sets used [n_bands][n_cams] and `capacity` slots.
+     * resident [capacity]: the camera each slot holds before the first band (-1: free), replaced by the state after the
+     * last; load_off [n_bands + 1]; loads3 (may be NULL) [sum of the sets' sizes at most][3] = camera, slot, phase
+     * (0 ahead, 1 late), band k's at [load_off[k], load_off[k + 1]).  -1 when a band reads more than `capacity` images.
+     * och_ortho_stream_*: the render of plan8 in bands of band_tile_rows tile rows from capacity_images slots of the
+     * largest image's size, one block of ctx's pool (ctx and mesh NULL: the CPU route, slots in host memory).  create
+     * computes the bands' sets and the plan; g, mesh and surfaces outlive the object.  band_cameras / loads: a band's
+     * cameras (ascending) and loads3 as above, returning their number (arguments may be NULL).  upload copies involved
+     * camera `camera`'s image (pixels_rows x pixels_cols x 3) into its planned slot on the context's copy stream: it
+     * returns at once and overlaps the band that renders when host_bgr is page-locked and must then stay valid until the
+     * band's render has returned; pageable memory is merely correct.  render: band `band` as och_ortho_layers_render
+     * writes it, after the compute stream has waited for the band's uploads; returns once the band is written.
+     * The order the plan assumes is enforced: bands render ascending; an ahead upload of band k is accepted once
+     * render(k - 2) has returned, a late one once render(k - 1) has; render(k) is refused while a planned load of k is
+     * missing; an upload that is not planned, or made twice, is refused.  rewind (after the last band): a further sweep,
+     * planned from the images the slots hold.  upload_end_ms: when band's last upload finished on the device, in ms since
+     * the sweep began.  -1 + och_ortho_stream_last_error() on failure. */
+    int och_ortho_band_cameras(ochip_ctx *ctx, const double *raster4, int32_t cols, int64_t rows, int64_t band_rows, size_t n_cams,
+                               const double *cams, uint8_t *used);
+    int och_ortho_layers_render_subset(const och_graph *g, ochip_ctx *ctx, ochip_ortho_mesh *dev, const och_surface *const *surfaces,
+                                       size_t n, const double *plan8, const int32_t *config4, int64_t row0, int64_t rows,
+                                       const uint32_t *subset, size_t n_subset, const uint64_t *images, const int64_t *image_hw,
+                                       const float *dsm_in, int out_on_device, uint8_t *bgra, uint64_t *ids, float *weight,
+                                       ochip_color_corr *corr_out, uint64_t corr_capacity, uint64_t *n_corr, uint32_t *knn_out);
+    int och_ortho_residency_plan(const uint8_t *used, size_t n_bands, size_t n_cams, size_t capacity, int32_t *resident,
+                                 size_t *load_off, int32_t *loads3);
+    typedef struct och_ortho_stream och_ortho_stream;
+    int och_ortho_stream_create(const och_graph *g, ochip_ctx *ctx, ochip_ortho_mesh *mesh, const och_surface *const *surfaces,
+                                size_t n, const double *plan8, const int32_t *config4, int64_t band_tile_rows,
+                                size_t capacity_images, och_ortho_stream **out);
+    void och_ortho_stream_destroy(och_ortho_stream *s);
+    size_t och_ortho_stream_num_bands(const och_ortho_stream *s);
+    size_t och_ortho_stream_band_cameras(const och_ortho_stream *s, size_t band, uint32_t *cameras);
+    size_t och_ortho_stream_loads(const och_ortho_stream *s, size_t band, int32_t *loads3);
+    int och_ortho_stream_upload(och_ortho_stream *s, size_t band, uint32_t camera, const uint8_t *host_bgr);
+    int och_ortho_stream_render(och_ortho_stream *s, size_t band, const float *dsm_in, int out_on_device, uint8_t *bgra,
+                                uint64_t *ids, float *weight, ochip_color_corr *corr_out, uint64_t corr_capacity, uint64_t *n_corr,
+                                uint32_t *knn_out);
+    int och_ortho_stream_rewind(och_ortho_stream *s);
+    int och_ortho_stream_upload_end_ms(och_ortho_stream *s, size_t band, double *ms);
+    const char *och_ortho_stream_last_error(void);
     /* ---- blended full-resolution orthomosaic (opencalibration_amd/csrc/host/ortho_blend.cpp; src/ortho/ortho.cpp:
      * 1665-1990, src/ortho/blending.cpp) ------------------------------------------------------------------------------------
      * och_ortho_blend_render: rows [row0, row0 + rows) of plan8 (och_dsm_plan's plan) blended from the layers of

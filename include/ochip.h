@@ -778,6 +778,31 @@ extern "C"
                            uint64_t *id_out, float *weight_out, ochip_color_corr *corr_out, uint64_t corr_capacity,
                            uint64_t *n_corr, uint32_t *knn_out);
 
+    /* The cameras each band of a raster can read: the raster rows x cols (raster4 as ochip_ortho_dsm) cut into bands of
+     * band_rows rows from row 0 (the last may be shorter), n_bands = ceil(rows / band_rows).  used_out (host)
+     * [n_bands][n_cams]: 1 exactly when the camera is among the 5 nearest in XY (squared distance, then camera order;
+     * ochip_ortho_layers' kNN) of at least one pixel of the band, else 0.  Pixels count whatever their height, so the set
+     * needs no mesh and holds every camera ochip_ortho_layers reads for the band.  At most 65535 16-row tile rows in all. */
+    int ochip_ortho_band_cameras(ochip_ctx *ctx, const double *raster4, int32_t cols, int64_t rows, int64_t band_rows,
+                                 uint32_t n_cams, const double *cams, uint8_t *used_out);
+    /* Image slots for a render that streams its source images: n_slots blocks of slot_bytes (rounded up to 256) in one
+     * block of the context's pool, and n_marks events.  ochip_image_slots_upload enqueues a host-to-device copy into a
+     * slot on the context's copy stream and returns at once when `host` is page-locked (pageable memory: correct, not
+     * overlapped); the caller keeps `host` alive until a mark behind the copy has passed.  ochip_image_slots_mark records
+     * mark i behind everything enqueued on the copy stream so far; ochip_image_slots_wait makes the context's compute
+     * stream (on_host != 0: the calling thread) wait for it; ochip_image_slots_elapsed waits for to_mark and gives the
+     * milliseconds between two recorded marks.  ochip_image_slots_address: the slot's device address, 0 when out of range.
+     * Nothing here orders an upload against a kernel that still reads the slot: the caller does (och_ortho_stream_*).
+     * Destroy waits for both streams and hands the block back. */
+    typedef struct ochip_image_slots ochip_image_slots;
+    int ochip_image_slots_create(ochip_ctx *ctx, uint32_t n_slots, uint64_t slot_bytes, uint32_t n_marks, ochip_image_slots **out);
+    void ochip_image_slots_destroy(ochip_image_slots *s);
+    uint64_t ochip_image_slots_address(const ochip_image_slots *s, uint32_t slot);
+    int ochip_image_slots_upload(ochip_image_slots *s, uint32_t slot, const void *host, uint64_t bytes);
+    int ochip_image_slots_mark(ochip_image_slots *s, uint32_t mark);
+    int ochip_image_slots_wait(ochip_image_slots *s, uint32_t mark, int on_host);
+    int ochip_image_slots_elapsed(ochip_image_slots *s, uint32_t from_mark, uint32_t to_mark, float *ms);
+
     /* ---- blended full-resolution orthomosaic (src/ortho/ortho.cpp:1665-1990, src/ortho/blending.cpp;
      * opencalibration_amd/csrc/ortho_blend.hpp) ----
      * One node id the layers may name, the table sorted by id, ids unique: cam, its row in cams (0xFFFFFFFF: none, the

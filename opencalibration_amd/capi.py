@@ -42,6 +42,8 @@ EXPORTS = [
     "ochip_rccl_relax_exchange",
     "ochip_ortho_mesh_create", "ochip_ortho_mesh_destroy", "ochip_ortho_dsm", "ochip_ortho_thumbnail", "ochip_ortho_layers",
     "ochip_ortho_blend", "ochip_laplacian_blend",
+    "ochip_ortho_band_cameras", "ochip_image_slots_create", "ochip_image_slots_destroy", "ochip_image_slots_address",
+    "ochip_image_slots_upload", "ochip_image_slots_mark", "ochip_image_slots_wait", "ochip_image_slots_elapsed",
     "ochip_color_balance_solve", "ochip_color_balance_evaluate",
 ]
 

@@ -140,6 +140,124 @@ bool read_plan8(const double *plan8, ortho::Plan *p)
     return true;
 }
 
+// och_ortho_layers_render (subset == nullptr) and och_ortho_layers_render_subset: `who` names the entry point in errors
+int renderLayers(const char *who, const och_graph *g, ochip_ctx *ctx, ochip_ortho_mesh *dev, const och_surface *const *surfaces,
+                 size_t n, const double *plan8, const int32_t *config4, int64_t row0, int64_t rows, const uint32_t *subset,
+                 size_t n_subset, const uint64_t *images, const int64_t *image_hw, const float *dsm_in, int out_on_device,
+                 uint8_t *bgra, uint64_t *ids, float *weight, ochip_color_corr *corr_out, uint64_t corr_capacity,
+                 uint64_t *n_corr, uint32_t *knn_out)
+{
+    const std::string name = who;
+    ortho::Plan plan;
+    if (!plan8 || !config4 || !n_corr || !read_plan8(plan8, &plan))
+    {
+        layers_error = name + ": bad argument";
+        return -1;
+    }
+    const int L = config4[0], T = config4[1];
+    if (L < 1 || L > ochip_ol::MAX_LAYERS || T < 1 || config4[2] < 0)
+    {
+        layers_error = name + ": num_layers 1..8, tile_size >= 1 and kernel radius >= 0";
+        return -1;
+    }
+    if (row0 < 0 || rows < 0 || row0 % T != 0 || row0 + rows > plan.height || (rows % T != 0 && row0 + rows != plan.height))
+    {
+        layers_error = name + ": a band is whole tile rows from a tile row (the raster's last may be partial)";
+        return -1;
+    }
+    *n_corr = 0;
+    std::vector<const surface_model *> surf;
+    for (size_t i = 0; i < n; i++)
+        surf.push_back(&surfaces[i]->s);
+    LayerCameras cams = layerCameras(ortho::prepareContext(surf, g->graph, false), g->graph);
+    if (subset)
+    {
+        // the subset keeps the cameras' order, so the kNN's tie order among its members is the full table's
+        LayerCameras part;
+        for (size_t j = 0; j < n_subset; j++)
+        {
+            const size_t i = subset[j];
+            if (i >= cams.ids.size() || (j && subset[j] <= subset[j - 1]))
+            {
+                layers_error = name + ": subset entry " + std::to_string(j) + " is out of range (" + std::to_string(cams.ids.size()) +
+                               " involved cameras) or not above the entry before it";
+                return -1;
+            }
+            part.cams.insert(part.cams.end(), cams.cams.begin() + i * ochip_ol::CAM_DOUBLES,
+                             cams.cams.begin() + (i + 1) * ochip_ol::CAM_DOUBLES);
+            part.ids.push_back(cams.ids[i]);
+            part.models.push_back(cams.models[i]);
+            part.hw.insert(part.hw.end(), {cams.hw[2 * i], cams.hw[2 * i + 1]});
+        }
+        cams = std::move(part);
+    }
+    const size_t nc = cams.ids.size();
+    // the kNN lists name rows of the table rendered from: back to och_ortho_layers_cameras' order
+    const auto map_knn = [&]() {
+        if (subset && knn_out)
+            for (size_t i = 0; i < (size_t)rows * (size_t)plan.width * ochip_og::KNN; i++)
+                if (knn_out[i] != ochip_ol::NONE)
+                    knn_out[i] = subset[knn_out[i]];
+    };
+    for (size_t i = 0; i < nc; i++)
+        if (!images || !images[i] || !image_hw || image_hw[2 * i] != cams.hw[2 * i] || image_hw[2 * i + 1] != cams.hw[2 * i + 1])
+        {
+            layers_error = name + ": involved camera " + std::to_string(i) + " (node " + std::to_string(cams.ids[i]) +
+                           ") has no image or one whose size differs from its model's pixels_rows x pixels_cols";
+            return -1;
+        }
+    const size_t px = (size_t)rows * (size_t)plan.width;
+    if (px && (!bgra || !ids))
+    {
+        layers_error = name + ": bgra and ids are required";
+        return -1;
+    }
+    if (dev)
+    {
+        if (!ctx)
+        {
+            layers_error = name + ": the device route needs the mesh's context";
+            return -1;
+        }
+        const double raster4[4] = {plan.bounds.min_x, plan.bounds.max_y, plan.gsd, plan.mean_camera_z};
+        const int rc = ochip_ortho_layers(dev, raster4, plan.width, row0, rows, config4, (uint32_t)nc, cams.cams.data(),
+                                          cams.ids.data(), cams.models.data(), images, out_on_device, bgra, ids, weight, corr_out,
+                                          corr_capacity, n_corr, knn_out);
+        if (rc != OCHIP_OK)
+        {
+            layers_error = std::string("ochip_ortho_layers: ") + ochip_last_error(ctx);
+            return -1;
+        }
+        map_knn();
+        return 0;
+    }
+    if (out_on_device)
+    {
+        layers_error = name + ": the CPU route writes host memory only";
+        return -1;
+    }
+    std::vector<float> z(px);
+    if (dsm_in)
+        std::copy(dsm_in, dsm_in + px, z.begin());
+    else
+    {
+        std::vector<double> z64(px);
+        ortho::heightsCPU(surf, plan, row0, rows, z64.data(), nullptr, nullptr);
+        for (size_t i = 0; i < px; i++)
+            z[i] = (float)z64[i];
+    }
+    std::vector<const uint8_t *> img(nc);
+    for (size_t i = 0; i < nc; i++)
+        img[i] = reinterpret_cast<const uint8_t *>(images[i]);
+    std::vector<ochip_ol::corr_record> corr;
+    layersCPU(plan, cams, img.data(), z.data(), row0, rows, config4, bgra, ids, weight, knn_out, &corr);
+    *n_corr = corr.size();
+    if (corr_out)
+        std::memcpy(corr_out, corr.data(), std::min<size_t>(corr.size(), corr_capacity) * sizeof(ochip_color_corr));
+    map_knn();
+    return 0;
+}
+
 } // namespace
 
 extern "C"
@@ -169,83 +287,80 @@ int och_ortho_layers_render(const och_graph *g, ochip_ctx *ctx, ochip_ortho_mesh
                             uint8_t *bgra, uint64_t *ids, float *weight, ochip_color_corr *corr_out, uint64_t corr_capacity,
                             uint64_t *n_corr, uint32_t *knn_out)
 {
-    ortho::Plan plan;
-    if (!plan8 || !config4 || !n_corr || !read_plan8(plan8, &plan))
+    return renderLayers("och_ortho_layers_render", g, ctx, dev, surfaces, n, plan8, config4, row0, rows, nullptr, 0, images,
+                        image_hw, dsm_in, out_on_device, bgra, ids, weight, corr_out, corr_capacity, n_corr, knn_out);
+}
+
+int och_ortho_layers_render_subset(const och_graph *g, ochip_ctx *ctx, ochip_ortho_mesh *dev, const och_surface *const *surfaces,
+                                   size_t n, const double *plan8, const int32_t *config4, int64_t row0, int64_t rows,
+                                   const uint32_t *subset, size_t n_subset, const uint64_t *images, const int64_t *image_hw,
+                                   const float *dsm_in, int out_on_device, uint8_t *bgra, uint64_t *ids, float *weight,
+                                   ochip_color_corr *corr_out, uint64_t corr_capacity, uint64_t *n_corr, uint32_t *knn_out)
+{
+    static const uint32_t none = 0;
+    return renderLayers("och_ortho_layers_render_subset", g, ctx, dev, surfaces, n, plan8, config4, row0, rows,
+                        subset ? subset : &none, subset ? n_subset : 0, images, image_hw, dsm_in, out_on_device, bgra, ids, weight,
+                        corr_out, corr_capacity, n_corr, knn_out);
+}
+
+int och_ortho_band_cameras(ochip_ctx *ctx, const double *raster4, int32_t cols, int64_t rows, int64_t band_rows, size_t n_cams,
+                           const double *cams, uint8_t *used)
+{
+    if (!raster4 || cols < 0 || rows < 0 || band_rows < 1 || (n_cams && !cams) || n_cams >= ochip_ol::NONE)
     {
-        layers_error = "och_ortho_layers_render: bad argument";
+        layers_error = "och_ortho_band_cameras: bad argument";
         return -1;
     }
-    const int L = config4[0], T = config4[1];
-    if (L < 1 || L > ochip_ol::MAX_LAYERS || T < 1 || config4[2] < 0)
+    const size_t n_bands = (size_t)((rows + band_rows - 1) / band_rows);
+    if (n_bands * n_cams == 0)
+        return 0;
+    if (!used)
     {
-        layers_error = "och_ortho_layers_render: num_layers 1..8, tile_size >= 1 and kernel radius >= 0";
+        layers_error = "och_ortho_band_cameras: bad argument";
         return -1;
     }
-    if (row0 < 0 || rows < 0 || row0 % T != 0 || row0 + rows > plan.height || (rows % T != 0 && row0 + rows != plan.height))
+    if (ctx)
     {
-        layers_error = "och_ortho_layers_render: a band is whole tile rows from a tile row (the raster's last may be partial)";
-        return -1;
-    }
-    *n_corr = 0;
-    std::vector<const surface_model *> surf;
-    for (size_t i = 0; i < n; i++)
-        surf.push_back(&surfaces[i]->s);
-    const LayerCameras cams = layerCameras(ortho::prepareContext(surf, g->graph, false), g->graph);
-    const size_t nc = cams.ids.size();
-    for (size_t i = 0; i < nc; i++)
-        if (!images || !images[i] || !image_hw || image_hw[2 * i] != cams.hw[2 * i] || image_hw[2 * i + 1] != cams.hw[2 * i + 1])
+        if (ochip_ortho_band_cameras(ctx, raster4, cols, rows, band_rows, (uint32_t)n_cams, cams, used) != OCHIP_OK)
         {
-            layers_error = "och_ortho_layers_render: involved camera " + std::to_string(i) + " (node " + std::to_string(cams.ids[i]) +
-                           ") has no image or one whose size differs from its model's pixels_rows x pixels_cols";
-            return -1;
-        }
-    const size_t px = (size_t)rows * (size_t)plan.width;
-    if (px && (!bgra || !ids))
-    {
-        layers_error = "och_ortho_layers_render: bgra and ids are required";
-        return -1;
-    }
-    if (dev)
-    {
-        if (!ctx)
-        {
-            layers_error = "och_ortho_layers_render: the device route needs the mesh's context";
-            return -1;
-        }
-        const double raster4[4] = {plan.bounds.min_x, plan.bounds.max_y, plan.gsd, plan.mean_camera_z};
-        const int rc = ochip_ortho_layers(dev, raster4, plan.width, row0, rows, config4, (uint32_t)nc, cams.cams.data(),
-                                          cams.ids.data(), cams.models.data(), images, out_on_device, bgra, ids, weight, corr_out,
-                                          corr_capacity, n_corr, knn_out);
-        if (rc != OCHIP_OK)
-        {
-            layers_error = std::string("ochip_ortho_layers: ") + ochip_last_error(ctx);
+            layers_error = std::string("ochip_ortho_band_cameras: ") + ochip_last_error(ctx);
             return -1;
         }
         return 0;
     }
-    if (out_on_device)
+    // the CPU route: layersCPU's pixel centres, distances and kNN order, brute force; a row's flags are merged per row
+    std::fill(used, used + n_bands * n_cams, (uint8_t)0);
+    const double min_x = raster4[0], max_y = raster4[1], gsd = raster4[2];
+#pragma omp parallel for schedule(dynamic)
+    for (int64_t row = 0; row < rows; row++)
     {
-        layers_error = "och_ortho_layers_render: the CPU route writes host memory only";
-        return -1;
+        std::vector<uint8_t> mine(n_cams, 0);
+        for (int64_t col = 0; col < cols; col++)
+        {
+            const double x = (int)col * gsd + min_x;
+            const double y = max_y - row * gsd;
+            double bd[ochip_og::KNN];
+            uint32_t bi[ochip_og::KNN];
+            for (int k = 0; k < ochip_og::KNN; k++)
+                bd[k] = INFINITY, bi[k] = ochip_ol::NONE;
+            for (uint32_t i = 0; i < (uint32_t)n_cams; i++)
+            {
+                const double dx = x - cams[(size_t)i * ochip_ol::CAM_DOUBLES];
+                const double dy = y - cams[(size_t)i * ochip_ol::CAM_DOUBLES + 1];
+                ochip_og::knn_offer(dx * dx + dy * dy, i, bd, bi);
+            }
+            for (int k = 0; k < ochip_og::KNN; k++)
+                if (bi[k] != ochip_ol::NONE)
+                    mine[bi[k]] = 1;
+        }
+        uint8_t *band = used + (size_t)(row / band_rows) * n_cams;
+        for (size_t i = 0; i < n_cams; i++)
+            if (mine[i])
+            {
+#pragma omp atomic write
+                band[i] = 1;
+            }
     }
-    std::vector<float> z(px);
-    if (dsm_in)
-        std::copy(dsm_in, dsm_in + px, z.begin());
-    else
-    {
-        std::vector<double> z64(px);
-        ortho::heightsCPU(surf, plan, row0, rows, z64.data(), nullptr, nullptr);
-        for (size_t i = 0; i < px; i++)
-            z[i] = (float)z64[i];
-    }
-    std::vector<const uint8_t *> img(nc);
-    for (size_t i = 0; i < nc; i++)
-        img[i] = reinterpret_cast<const uint8_t *>(images[i]);
-    std::vector<ochip_ol::corr_record> corr;
-    layersCPU(plan, cams, img.data(), z.data(), row0, rows, config4, bgra, ids, weight, knn_out, &corr);
-    *n_corr = corr.size();
-    if (corr_out)
-        std::memcpy(corr_out, corr.data(), std::min<size_t>(corr.size(), corr_capacity) * sizeof(ochip_color_corr));
     return 0;
 }
 

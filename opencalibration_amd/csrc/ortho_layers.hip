@@ -165,6 +165,143 @@ __global__ __launch_bounds__(THREADS) void ortho_layers_pass1(mesh_args M, raste
     ochip_ol::pixel_layers(*lab, C, node_ids, bi, x, y, (float)z, R.gsd, B, o);
 }
 
+// The front half of ortho_layers_pass1 alone, over every band of a raster in one launch: the tile's exact candidate list, each
+// pixel's kNN, and a byte per (band, camera) that some pixel of the band has among its 5 nearest.  A workgroup's tile lies
+// inside one band (blockIdx.y), so a band whose height is no multiple of TILE ends on a partial tile of its own.  The kNN
+// runs over positions in the candidate list (ascending camera order, so the tie order is the cameras'); the members are
+// flagged in LDS and one lane per flagged candidate stores the byte.  Every writer stores the same value: plain stores.
+// This repeats pass 1's candidate-list code instead of sharing it, so that kernel's code object stays what was measured.
+__global__ __launch_bounds__(THREADS) void ortho_band_cameras_kernel(raster_args R, int64_t band_rows, uint32_t tiles_per_band_y,
+                                                                     const double *__restrict__ cams, uint32_t n_cams,
+                                                                     uint8_t *__restrict__ used)
+{
+    __shared__ double2 cand_xy[CAND_CAP];
+    __shared__ uint32_t cand_id[CAND_CAP];
+    __shared__ uint8_t cand_flag[CAND_CAP];
+    __shared__ double far5[THREADS][KNN];
+    __shared__ uint32_t wave_count[THREADS / 64];
+    __shared__ uint32_t n_cand;
+    const uint32_t t = threadIdx.x;
+    const uint32_t tx = blockIdx.x;
+    const uint32_t band = blockIdx.y / tiles_per_band_y, ty = blockIdx.y % tiles_per_band_y;
+    const int c_lo = (int)(tx * TILE), c_hi = min(c_lo + TILE, R.cols) - 1;
+    const int64_t band_lo = (int64_t)band * band_rows, band_hi = min<int64_t>(band_lo + band_rows, R.rows);
+    const int64_t lr_lo = band_lo + (int64_t)ty * TILE, lr_hi = min<int64_t>(lr_lo + TILE, band_hi) - 1;
+    if (lr_lo > lr_hi) // the raster's last band may be shorter than the others: the whole workgroup leaves
+        return;
+    const double x_lo = c_lo * R.gsd + R.min_x, x_hi = c_hi * R.gsd + R.min_x;
+    const double y_hi = R.max_y - lr_lo * R.gsd, y_lo = R.max_y - lr_hi * R.gsd;
+
+    double mine[KNN];
+    for (int k = 0; k < KNN; k++)
+        mine[k] = INFINITY;
+    for (uint32_t i = t; i < n_cams; i += THREADS)
+    {
+        const double cx = cams[(size_t)i * ochip_ol::CAM_DOUBLES], cy = cams[(size_t)i * ochip_ol::CAM_DOUBLES + 1];
+        const double ax = x_lo - cx, bx = x_hi - cx, ay = y_lo - cy, by = y_hi - cy;
+        double d = fmax(ax * ax, bx * bx) + fmax(ay * ay, by * by);
+        for (int k = 0; k < KNN; k++)
+            if (d < mine[k])
+            {
+                const double s = mine[k];
+                mine[k] = d;
+                d = s;
+            }
+    }
+    for (int k = 0; k < KNN; k++)
+        far5[t][k] = mine[k];
+    for (uint32_t half = THREADS / 2; half > 0; half /= 2)
+    {
+        __syncthreads();
+        if (t < half)
+        {
+            double m[KNN];
+            merge5(far5[t], far5[t + half], m);
+            for (int k = 0; k < KNN; k++)
+                far5[t][k] = m[k];
+        }
+    }
+    if (t == 0)
+        n_cand = 0;
+    for (uint32_t k = t; k < CAND_CAP; k += THREADS)
+        cand_flag[k] = 0;
+    __syncthreads();
+    const double thr = far5[0][KNN - 1];
+
+    const uint32_t lane = t % 64, wave = t / 64;
+    for (uint32_t base = 0; base < n_cams; base += THREADS)
+    {
+        const uint32_t i = base + t;
+        bool keep = false;
+        double cx = 0, cy = 0;
+        if (i < n_cams)
+        {
+            cx = cams[(size_t)i * ochip_ol::CAM_DOUBLES], cy = cams[(size_t)i * ochip_ol::CAM_DOUBLES + 1];
+            const double dx = cx < x_lo ? x_lo - cx : cx > x_hi ? x_hi - cx : 0.0;
+            const double dy = cy < y_lo ? y_lo - cy : cy > y_hi ? y_hi - cy : 0.0;
+            keep = dx * dx + dy * dy <= thr;
+        }
+        const uint64_t ballot = __ballot(keep);
+        if (lane == 0)
+            wave_count[wave] = (uint32_t)__popcll(ballot);
+        __syncthreads();
+        uint32_t off = n_cand;
+        for (uint32_t w = 0; w < wave; w++)
+            off += wave_count[w];
+        off += (uint32_t)__popcll(ballot & ((1ull << lane) - 1ull));
+        if (keep && off < CAND_CAP)
+        {
+            cand_xy[off] = make_double2(cx, cy);
+            cand_id[off] = i;
+        }
+        __syncthreads();
+        if (t == 0)
+            for (uint32_t w = 0; w < THREADS / 64; w++)
+                n_cand += wave_count[w];
+        __syncthreads();
+    }
+
+    const int col = c_lo + (int)(t % TILE);
+    const int64_t row = lr_lo + t / TILE;
+    const bool listed = n_cand <= CAND_CAP; // uniform over the workgroup
+    uint8_t *mine_used = used + (size_t)band * n_cams;
+    if (col <= c_hi && row <= lr_hi)
+    {
+        const double x = col * R.gsd + R.min_x;
+        const double y = R.max_y - row * R.gsd;
+        double bd[KNN];
+        uint32_t bi[KNN];
+        for (int k = 0; k < KNN; k++)
+            bd[k] = INFINITY, bi[k] = ochip_ol::NONE;
+        if (listed)
+            for (uint32_t k = 0; k < n_cand; k++)
+            {
+                const double2 c = cand_xy[k];
+                const double dx = x - c.x, dy = y - c.y;
+                ochip_og::knn_offer(dx * dx + dy * dy, k, bd, bi);
+            }
+        else
+            for (uint32_t i = 0; i < n_cams; i++)
+            {
+                const double dx = x - cams[(size_t)i * ochip_ol::CAM_DOUBLES], dy = y - cams[(size_t)i * ochip_ol::CAM_DOUBLES + 1];
+                ochip_og::knn_offer(dx * dx + dy * dy, i, bd, bi);
+            }
+        for (int k = 0; k < KNN; k++)
+            if (bi[k] != ochip_ol::NONE) // fewer than 5 cameras: the padding names no table entry
+            {
+                if (listed)
+                    cand_flag[bi[k]] = 1;
+                else
+                    mine_used[bi[k]] = 1;
+            }
+    }
+    __syncthreads();
+    if (listed)
+        for (uint32_t k = t; k < n_cand; k += THREADS)
+            if (cand_flag[k])
+                mine_used[cand_id[k]] = 1;
+}
+
 // canonical index k of the band -> band-local (r, c): output tiles row-major, then local raster order
 __device__ __forceinline__ void canon_pixel(int64_t k, int T, int32_t W, int64_t rows, int64_t *r, int32_t *c)
 {
@@ -384,5 +521,156 @@ int ochip_ortho_layers(ochip_ortho_mesh *m, const double *raster4, int32_t cols,
     if (ochip_stream_wait(ctx, ctx->stream) != hipSuccess)
         return ochip_fail(ctx, OCHIP_EHIP, "stream wait failed (ortho layers)");
     mem.release();
+    return OCHIP_OK;
+}
+
+int ochip_ortho_band_cameras(ochip_ctx *ctx, const double *raster4, int32_t cols, int64_t rows, int64_t band_rows,
+                             uint32_t n_cams, const double *cams, uint8_t *used_out)
+{
+    if (!ctx)
+        return OCHIP_EINVAL;
+    if (!raster4 || cols < 0 || rows < 0 || band_rows < 1 || (n_cams && !cams))
+        return ochip_fail(ctx, OCHIP_EINVAL, "ochip_ortho_band_cameras: bad argument");
+    const uint64_t n_bands = (uint64_t)((rows + band_rows - 1) / band_rows);
+    const size_t bytes = (size_t)n_bands * n_cams;
+    if (bytes == 0)
+        return OCHIP_OK;
+    if (!used_out)
+        return ochip_fail(ctx, OCHIP_EINVAL, "ochip_ortho_band_cameras: bad argument");
+    if (cols == 0)
+    {
+        std::fill(used_out, used_out + bytes, (uint8_t)0);
+        return OCHIP_OK;
+    }
+    const raster_args R = make_raster(raster4, cols, 0, rows);
+    const uint64_t tiles_per_band_y = (uint64_t)((std::min(band_rows, rows) + TILE - 1) / TILE);
+    if (n_bands * tiles_per_band_y > 65535 || R.tiles_x >= (1u << 31))
+        return ochip_fail(ctx, OCHIP_EINVAL, "ochip_ortho_band_cameras: more than 65535 tile rows in all bands");
+    OCHIP_HIP(ctx, hipSetDevice(ctx->device));
+    ochip::dev_scratch mem{ctx, "ochip_ortho_band_cameras"};
+    double *d_cams = nullptr;
+    uint8_t *d_used = nullptr;
+    OCHIP_TRY(mem.upload(&d_cams, cams, (size_t)n_cams * ochip_ol::CAM_DOUBLES, ochip::copy_mode::enqueue));
+    OCHIP_TRY(mem.alloc<uint8_t>(&d_used, bytes));
+    OCHIP_HIP(ctx, hipMemsetAsync(d_used, 0, bytes, ctx->stream));
+    hipLaunchKernelGGL(ortho_band_cameras_kernel, dim3(R.tiles_x, (uint32_t)(n_bands * tiles_per_band_y)), dim3(THREADS), 0,
+                       ctx->stream, R, band_rows, (uint32_t)tiles_per_band_y, d_cams, n_cams, d_used);
+    if (hipGetLastError() != hipSuccess)
+        return ochip_fail(ctx, OCHIP_EHIP, "ortho_band_cameras kernel launch failed");
+    OCHIP_TRY(copy_back(ctx, used_out, d_used, bytes, "band cameras"));
+    if (ochip_stream_wait(ctx, ctx->stream) != hipSuccess)
+        return ochip_fail(ctx, OCHIP_EHIP, "stream wait failed (band cameras)");
+    mem.release();
+    return OCHIP_OK;
+}
+
+// The image slots of a streamed render: one block of the context's pool, n_slots x slot_bytes, filled on the context's copy
+// stream; marks are events on that stream which the compute stream can be made to wait for.
+struct ochip_image_slots
+{
+    ochip_ctx *ctx = nullptr;
+    ochip::dev_blocks mem;
+    uint8_t *base = nullptr;
+    uint32_t n_slots = 0;
+    uint64_t slot_bytes = 0;
+    std::vector<hipEvent_t> marks;
+};
+
+int ochip_image_slots_create(ochip_ctx *ctx, uint32_t n_slots, uint64_t slot_bytes, uint32_t n_marks, ochip_image_slots **out)
+{
+    if (!ctx)
+        return OCHIP_EINVAL;
+    if (!out || n_slots == 0 || slot_bytes == 0)
+        return ochip_fail(ctx, OCHIP_EINVAL, "ochip_image_slots_create: bad argument");
+    *out = nullptr;
+    OCHIP_HIP(ctx, hipSetDevice(ctx->device));
+    hipStream_t copy;
+    OCHIP_HIP(ctx, ochip_copy_stream(ctx, &copy));
+    auto *s = new ochip_image_slots;
+    s->ctx = ctx, s->mem.ctx = ctx, s->mem.what = "ochip_image_slots";
+    s->n_slots = n_slots, s->slot_bytes = (slot_bytes + 255) / 256 * 256;
+    s->base = (uint8_t *)s->mem.get((size_t)s->n_slots * s->slot_bytes);
+    if (!s->base)
+    {
+        delete s;
+        return OCHIP_ENOMEM;
+    }
+    for (uint32_t i = 0; i < n_marks; i++)
+    {
+        hipEvent_t e;
+        if (hipEventCreate(&e) != hipSuccess)
+        {
+            ochip_image_slots_destroy(s);
+            return ochip_fail(ctx, OCHIP_EHIP, "ochip_image_slots_create: hipEventCreate failed");
+        }
+        s->marks.push_back(e);
+    }
+    *out = s;
+    return OCHIP_OK;
+}
+
+void ochip_image_slots_destroy(ochip_image_slots *s)
+{
+    if (!s)
+        return;
+    // nothing may still write the block when it goes back to the pool
+    if (s->ctx->copy_stream)
+        (void)ochip_stream_wait(s->ctx, s->ctx->copy_stream);
+    (void)ochip_stream_wait(s->ctx, s->ctx->stream);
+    for (hipEvent_t e : s->marks)
+        (void)hipEventDestroy(e);
+    s->mem.release();
+    delete s;
+}
+
+uint64_t ochip_image_slots_address(const ochip_image_slots *s, uint32_t slot)
+{
+    return s && slot < s->n_slots ? (uint64_t)(uintptr_t)(s->base + (size_t)slot * s->slot_bytes) : 0;
+}
+
+int ochip_image_slots_upload(ochip_image_slots *s, uint32_t slot, const void *host, uint64_t bytes)
+{
+    if (!s)
+        return OCHIP_EINVAL;
+    if (slot >= s->n_slots || !host || bytes > s->slot_bytes)
+        return ochip_fail(s->ctx, OCHIP_EINVAL, "ochip_image_slots_upload: slot %u of %u, %llu bytes into %llu", slot, s->n_slots,
+                          (unsigned long long)bytes, (unsigned long long)s->slot_bytes);
+    OCHIP_HIP(s->ctx, hipSetDevice(s->ctx->device));
+    OCHIP_HIP(s->ctx, hipMemcpyAsync(s->base + (size_t)slot * s->slot_bytes, host, (size_t)bytes, hipMemcpyHostToDevice,
+                                     s->ctx->copy_stream));
+    return OCHIP_OK;
+}
+
+int ochip_image_slots_mark(ochip_image_slots *s, uint32_t mark)
+{
+    if (!s)
+        return OCHIP_EINVAL;
+    if (mark >= s->marks.size())
+        return ochip_fail(s->ctx, OCHIP_EINVAL, "ochip_image_slots_mark: mark %u of %zu", mark, s->marks.size());
+    OCHIP_HIP(s->ctx, hipEventRecord(s->marks[mark], s->ctx->copy_stream));
+    return OCHIP_OK;
+}
+
+int ochip_image_slots_wait(ochip_image_slots *s, uint32_t mark, int on_host)
+{
+    if (!s)
+        return OCHIP_EINVAL;
+    if (mark >= s->marks.size())
+        return ochip_fail(s->ctx, OCHIP_EINVAL, "ochip_image_slots_wait: mark %u of %zu", mark, s->marks.size());
+    if (on_host)
+        OCHIP_HIP(s->ctx, hipEventSynchronize(s->marks[mark]));
+    else
+        OCHIP_HIP(s->ctx, hipStreamWaitEvent(s->ctx->stream, s->marks[mark], 0));
+    return OCHIP_OK;
+}
+
+int ochip_image_slots_elapsed(ochip_image_slots *s, uint32_t from_mark, uint32_t to_mark, float *ms)
+{
+    if (!s)
+        return OCHIP_EINVAL;
+    if (from_mark >= s->marks.size() || to_mark >= s->marks.size() || !ms)
+        return ochip_fail(s->ctx, OCHIP_EINVAL, "ochip_image_slots_elapsed: bad argument");
+    OCHIP_HIP(s->ctx, hipEventSynchronize(s->marks[to_mark]));
+    OCHIP_HIP(s->ctx, hipEventElapsedTime(ms, s->marks[from_mark], s->marks[to_mark]));
     return OCHIP_OK;
 }

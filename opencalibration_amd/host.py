@@ -241,6 +241,23 @@ def load():
         L.och_ortho_layers_render.argtypes = [vp, vp, vp, vp, sz, _f64p, vp, i64, i64, vp, vp, vp, C.c_int, vp, vp, vp, vp, u64,
                                               C.POINTER(u64), vp]
         L.och_ortho_layers_last_error.restype = C.c_char_p
+        L.och_ortho_band_cameras.argtypes = [vp, _f64p, i32, i64, i64, sz, vp, vp]
+        L.och_ortho_layers_render_subset.argtypes = [vp, vp, vp, vp, sz, _f64p, vp, i64, i64, vp, sz, vp, vp, vp, C.c_int, vp, vp,
+                                                     vp, vp, u64, C.POINTER(u64), vp]
+        L.och_ortho_residency_plan.argtypes = [vp, sz, sz, sz, vp, vp, vp]
+        L.och_ortho_stream_create.argtypes = [vp, vp, vp, vp, sz, _f64p, vp, i64, sz, C.POINTER(vp)]
+        L.och_ortho_stream_destroy.argtypes = [vp]
+        L.och_ortho_stream_destroy.restype = None
+        L.och_ortho_stream_num_bands.argtypes = [vp]
+        L.och_ortho_stream_num_bands.restype = sz
+        for fn in (L.och_ortho_stream_band_cameras, L.och_ortho_stream_loads):
+            fn.argtypes = [vp, sz, vp]
+            fn.restype = sz
+        L.och_ortho_stream_upload.argtypes = [vp, sz, u32, vp]
+        L.och_ortho_stream_render.argtypes = [vp, sz, vp, C.c_int, vp, vp, vp, vp, u64, C.POINTER(u64), vp]
+        L.och_ortho_stream_rewind.argtypes = [vp]
+        L.och_ortho_stream_upload_end_ms.argtypes = [vp, sz, C.POINTER(f64)]
+        L.och_ortho_stream_last_error.restype = C.c_char_p
         L.och_lab_convert.argtypes = [C.c_int, vp, sz, vp]
         L.och_lab_convert.restype = None
         L.och_ortho_patch_sample.argtypes = [vp, vp, f64, vp, vp, vp, vp]
@@ -680,7 +697,7 @@ def _corr_bound(rows, width, cfg):
 
 
 def ortho_layers(plan, graph, surfaces, images, mesh=None, row0=0, tile_rows=None, config=None, out=None, dsm=None,
-                 debug_knn=False):
+                 debug_knn=False, subset=None):
     """Rows of tile rows [row0 / tile_size, + tile_rows) of the layered full-resolution orthomosaic (processLayeredTile,
     src/ortho/ortho.cpp:1206-1429) over `plan` (dsm_plan).  images: one BGR uint8 array per involved node
     (ortho_layers_cameras' order), pixels_rows x pixels_cols x 3: numpy arrays for the CPU route, CUDA tensors (or raw
@@ -688,6 +705,8 @@ def ortho_layers(plan, graph, surfaces, images, mesh=None, row0=0, tile_rows=Non
     are `dsm` (float32, rows x width) when given.  config overrides OrthoMosaicConfig's defaults (LAYERS_CONFIG).
     out (device route): dict of CUDA tensors bgra (L, rows, width, 4) uint8, camera_id (L, rows, width) int64 (the uint64
     ids' bits) and optionally weight (L, rows, width) float32, written in place.
+    subset (ascending indices into ortho_layers_cameras' order): render from these cameras alone, images[j] belonging to
+    camera subset[j]; with the band's set of ortho_band_cameras (or more) the result equals the full table's bit for bit.
     Returns dict(bgra, camera_id, weight, correspondences (CORR_DTYPE), row0, rows[, knn])."""
     L = load()
     cfg, config4 = _layers_config(config)
@@ -722,11 +741,41 @@ def ortho_layers(plan, graph, surfaces, images, mesh=None, row0=0, tile_rows=Non
             tensor_images = True
         hw.append(tuple(im.shape[:2]))
     cams = ortho_layers_cameras(graph, surfaces)
-    if len(ptrs) != len(cams["node_ids"]):
-        raise ValueError(f"{len(ptrs)} images for {len(cams['node_ids'])} involved nodes")
-    # raw pointers carry the model's size: the caller vouches for it
-    hw = np.array([h if h is not None else tuple(cams["image_hw"][i]) for i, h in enumerate(hw)], np.int64).reshape(-1, 2)
+    if subset is None:
+        which = range(len(cams["node_ids"]))
+        if len(ptrs) != len(cams["node_ids"]):
+            raise ValueError(f"{len(ptrs)} images for {len(cams['node_ids'])} involved nodes")
+    else:
+        subset = np.ascontiguousarray(subset, np.uint32).reshape(-1)
+        if len(ptrs) != len(subset):
+            raise ValueError(f"{len(ptrs)} images for a subset of {len(subset)} cameras")
+        which = subset.tolist()
+    # raw pointers carry the model's size: the caller vouches for it (a camera out of range is the library's to refuse)
+    sizes = cams["image_hw"]
+    hw = np.array([h if h is not None else tuple(sizes[i]) if i < len(sizes) else (0, 0) for i, h in zip(which, hw)],
+                  np.int64).reshape(-1, 2)
     ptr_arr = np.array(ptrs, np.uint64)
+    if tensor_images and not on_device:
+        import torch
+
+        torch.cuda.current_stream(mesh.ctx.device).synchronize()  # the images' uploads finish first
+    h_ctx, h_mesh = (mesh.ctx.h, mesh.h) if mesh is not None else (None, None)
+    images_p, hw_p = ptr_arr.ctypes.data if len(ptr_arr) else None, hw.ctypes.data if len(hw) else None
+
+    def call(*outputs):
+        if subset is None:
+            return L.och_ortho_layers_render(graph.h, h_ctx, h_mesh, arr, n, _plan_array(plan), config4.ctypes.data, int(row0),
+                                             int(rows), images_p, hw_p, *outputs)
+        return L.och_ortho_layers_render_subset(graph.h, h_ctx, h_mesh, arr, n, _plan_array(plan), config4.ctypes.data, int(row0),
+                                                int(rows), subset.ctypes.data, len(subset), images_p, hw_p, *outputs)
+
+    return _layers_band(call, L.och_ortho_layers_last_error, cfg, w, row0, rows, mesh, out, dsm, debug_knn)
+
+
+def _layers_band(call, last_error, cfg, w, row0, rows, mesh, out, dsm, debug_knn):
+    """The outputs of one band of the layered render, shared by ortho_layers and OrthoStream.render: call(dsm, on_device,
+    bgra, ids, weight, corr, capacity, n_corr, knn) is the entry point with everything before those arguments bound."""
+    nl, on_device = cfg["num_layers"], out is not None
     if on_device:
         if mesh is None:
             raise ValueError("device outputs need the device route (mesh)")
@@ -746,10 +795,6 @@ def ortho_layers(plan, graph, surfaces, images, mesh=None, row0=0, tile_rows=Non
     else:
         bgra, ids, weight = np.zeros((nl, rows, w, 4), np.uint8), np.zeros((nl, rows, w), np.uint64), np.zeros((nl, rows, w), np.float32)
         p_bgra, p_ids, p_w = bgra.ctypes.data, ids.ctypes.data, weight.ctypes.data
-    if tensor_images and not on_device:
-        import torch
-
-        torch.cuda.current_stream(mesh.ctx.device).synchronize()  # the images' uploads finish first
     dsm_p = None
     if dsm is not None:
         if mesh is not None:
@@ -762,13 +807,10 @@ def ortho_layers(plan, graph, surfaces, images, mesh=None, row0=0, tile_rows=Non
     corr = np.zeros(max(cap, 1), CORR_DTYPE)
     knn = np.zeros((rows, w, 5), np.uint32) if debug_knn else None
     n_corr = C.c_uint64(0)
-    rc = L.och_ortho_layers_render(graph.h, mesh.ctx.h if mesh is not None else None, mesh.h if mesh is not None else None,
-                                   arr, n, _plan_array(plan), config4.ctypes.data, int(row0), int(rows),
-                                   ptr_arr.ctypes.data if len(ptr_arr) else None, hw.ctypes.data if len(hw) else None,
-                                   dsm_p, int(on_device), p_bgra, p_ids, p_w, corr.ctypes.data, cap, C.byref(n_corr),
-                                   None if knn is None else knn.ctypes.data)
+    rc = call(dsm_p, int(on_device), p_bgra, p_ids, p_w, corr.ctypes.data, cap, C.byref(n_corr),
+              None if knn is None else knn.ctypes.data)
     if rc != 0:
-        raise capi.OchipError(L.och_ortho_layers_last_error().decode())
+        raise capi.OchipError(last_error().decode())
     if n_corr.value > cap:
         raise capi.OchipError(f"{n_corr.value} correspondences exceed their bound {cap}")
     res = dict(bgra=bgra, camera_id=ids, weight=weight, correspondences=corr[:n_corr.value], row0=row0, rows=rows)
@@ -783,6 +825,142 @@ def ortho_layers_bands(plan, graph, surfaces, images, mesh=None, tile_rows=1, co
     cfg, _ = _layers_config(config)
     for row0 in range(0, plan["height"], tile_rows * cfg["tile_size"]):
         yield ortho_layers(plan, graph, surfaces, images, mesh=mesh, row0=row0, tile_rows=tile_rows, config=config)
+
+
+# ---- the layered render with streamed source images (csrc/host/ortho_stream.cpp, ortho_residency.hpp) ------------------
+def ortho_band_cameras(plan, graph, surfaces, tile_rows=1, config=None, ctx=None):
+    """The cameras each band of tile_rows output tile rows can read: a bool array (n_bands, n_cameras) over
+    ortho_layers_cameras' order, True where the camera is among the 5 nearest in XY of at least one pixel of the band
+    (whatever the pixel's height: no mesh is needed).  ctx (a capi.Context): on its device; None: the CPU route."""
+    L = load()
+    cfg, _ = _layers_config(config)
+    cams = ortho_layers_cameras(graph, surfaces)["cams"]
+    band_rows = tile_rows * cfg["tile_size"]
+    n_bands = -(-plan["height"] // band_rows)
+    used = np.zeros((n_bands, len(cams)), np.uint8)
+    raster4 = np.array([plan["min_x"], plan["max_y"], plan["gsd"], plan["mean_camera_z"]])
+    rc = L.och_ortho_band_cameras(ctx.h if ctx is not None else None, raster4, plan["width"], plan["height"], band_rows, len(cams),
+                                  cams.ctypes.data, used.ctypes.data)
+    if rc != 0:
+        raise capi.OchipError(L.och_ortho_layers_last_error().decode())
+    return used.astype(bool)
+
+
+LOAD_AHEAD, LOAD_LATE = 0, 1
+
+
+def ortho_residency_plan(used, capacity, resident=None):
+    """The loads of a streamed render (ortho_residency.hpp's rule) for the bands' sets used (n_bands, n_cameras) and
+    `capacity` image slots, from the slots' state resident (camera per slot, -1 free; None: all free).  Returns (per band a
+    list of (camera, slot, phase) with phase LOAD_AHEAD or LOAD_LATE, the slots' state after the last band)."""
+    L = load()
+    used = np.ascontiguousarray(np.asarray(used).astype(bool), np.uint8)
+    if used.ndim != 2:
+        raise ValueError("used is (n_bands, n_cameras)")
+    state = np.full(max(int(capacity), 0), -1, np.int32) if resident is None else np.array(resident, np.int32)
+    if len(state) != capacity:
+        raise ValueError(f"resident names {len(state)} slots, the capacity is {capacity}")
+    off = np.zeros(used.shape[0] + 1, np.uint64)
+    loads = np.zeros((max(int(used.sum()), 1), 3), np.int32)
+    if L.och_ortho_residency_plan(used.ctypes.data, used.shape[0], used.shape[1], int(capacity), state.ctypes.data,
+                                  off.ctypes.data, loads.ctypes.data) != 0:
+        raise capi.OchipError(L.och_ortho_stream_last_error().decode())
+    return [[tuple(int(v) for v in l) for l in loads[int(off[k]):int(off[k + 1])]] for k in range(used.shape[0])], state
+
+
+class OrthoStream:
+    """The layered render of `plan` in bands of tile_rows output tile rows, its source images streamed through `capacity`
+    device slots (och_ortho_stream_*).  mesh (an OrthoMesh): on its device, the slots one block of its context's pool;
+    None: the CPU route with the slots in host memory.  The caller drives it: for band k upload(k, camera, image) every
+    load of loads(k) - the ahead ones may go out before render(k - 1), so that they overlap it when the image is
+    page-locked - then render(k); bands ascend, rewind() starts a further sweep from the images the slots hold.  A call
+    out of the plan's order raises OchipError and launches nothing."""
+
+    def __init__(self, plan, graph, surfaces, capacity, mesh=None, tile_rows=1, config=None):
+        self.L, self.plan, self.mesh, self.graph, self.surfaces = load(), dict(plan), mesh, graph, list(surfaces)
+        self.cfg, self.config4 = _layers_config(config)
+        self.tile_rows = tile_rows
+        self.arr, n = _surface_array(self.surfaces)
+        self.h = C.c_void_p()
+        self._keep = []
+        if self.L.och_ortho_stream_create(graph.h, mesh.ctx.h if mesh is not None else None, mesh.h if mesh is not None else None,
+                                          self.arr, n, _plan_array(plan), self.config4.ctypes.data, int(tile_rows), int(capacity),
+                                          C.byref(self.h)) != 0:
+            self.h = None
+            raise capi.OchipError(self._error())
+        self.image_hw = ortho_layers_cameras(graph, surfaces)["image_hw"]
+        self.num_bands = int(self.L.och_ortho_stream_num_bands(self.h))
+
+    def _error(self):
+        return self.L.och_ortho_stream_last_error().decode()
+
+    def close(self):
+        if getattr(self, "h", None):
+            if self.mesh is None or getattr(self.mesh.ctx, "h", None):  # as OrthoMesh.close: the context may be gone
+                self.L.och_ortho_stream_destroy(self.h)
+            self.h = None
+            self._keep = []
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        self.close()
+
+    def band_cameras(self, band):
+        n = self.L.och_ortho_stream_band_cameras(self.h, band, None)
+        cams = np.zeros(n, np.uint32)
+        self.L.och_ortho_stream_band_cameras(self.h, band, cams.ctypes.data)
+        return cams
+
+    def loads(self, band, phase=None):
+        """band's planned loads as (camera, slot, phase), in issue order; phase: those of LOAD_AHEAD or LOAD_LATE alone"""
+        n = self.L.och_ortho_stream_loads(self.h, band, None)
+        l3 = np.zeros((n, 3), np.int32)
+        self.L.och_ortho_stream_loads(self.h, band, l3.ctypes.data)
+        return [tuple(int(v) for v in l) for l in l3 if phase is None or l[2] == phase]
+
+    def upload(self, band, camera, image):
+        """image: involved camera `camera`'s BGR image, a numpy array or a (page-locked) torch CPU tensor; it is kept alive
+        until the band's render has returned"""
+        shape = tuple(self.image_hw[camera]) + (3,) if 0 <= camera < len(self.image_hw) else None
+        if isinstance(image, np.ndarray):
+            ok = image.dtype == np.uint8 and image.shape == shape and image.flags.c_contiguous
+            ptr = image.ctypes.data
+        else:
+            ok = str(image.dtype) == "torch.uint8" and tuple(image.shape) == shape and not image.is_cuda and image.is_contiguous()
+            ptr = image.data_ptr()
+        if shape is not None and not ok:
+            raise ValueError(f"camera {camera}'s image is a contiguous uint8 host array of {shape}")
+        if self.L.och_ortho_stream_upload(self.h, band, camera, ptr) != 0:
+            raise capi.OchipError(self._error())
+        self._keep.append((band, image))
+
+    def render(self, band, out=None, dsm=None, debug_knn=False):
+        """band `band` as ortho_layers returns it (out, dsm, debug_knn as there)"""
+        t, h = self.cfg["tile_size"], self.plan["height"]
+        row0 = band * self.tile_rows * t
+        rows = max(0, min(self.tile_rows * t, h - row0))
+
+        def call(*outputs):
+            return self.L.och_ortho_stream_render(self.h, band, *outputs)
+
+        res = _layers_band(call, self.L.och_ortho_stream_last_error, self.cfg, self.plan["width"], row0, rows, self.mesh, out, dsm,
+                           debug_knn)
+        self._keep = [(b, im) for b, im in self._keep if b > band]
+        return res
+
+    def rewind(self):
+        if self.L.och_ortho_stream_rewind(self.h) != 0:
+            raise capi.OchipError(self._error())
+
+    def upload_end_ms(self, band):
+        """when band's last upload finished on the device, ms since the sweep began (None: the band loaded nothing)"""
+        ms = C.c_double(0)
+        return float(ms.value) if self.L.och_ortho_stream_upload_end_ms(self.h, band, C.byref(ms)) == 0 else None
 
 
 def lab_convert(values, mode):
@@ -1034,6 +1212,56 @@ def ortho_mosaic(plan, graph, surfaces, images, mesh=None, config=None, color_ba
                                             ctx=mesh.ctx if mesh is not None else None)
     for row0 in range(0, h, tile_rows * t):
         band(row0, True)
+    return out
+
+
+def ortho_mosaic_streamed(plan, graph, surfaces, fetch, mesh, capacity, config=None, color_balance=None, tile_rows=1, out=None):
+    """ortho_mosaic on mesh's device without the source images resident: fetch(i) returns involved camera i's BGR image
+    (ortho_layers_cameras' order) as a numpy array or a page-locked torch CPU tensor, and at most `capacity` images are on
+    the device at a time (OrthoStream).  Band k + 1's ahead uploads are issued before band k renders, so that they run
+    beside it when the images are page-locked.  color_balance as ortho_mosaic's; "solve" renders the layers twice, the
+    second sweep starting from the images the first one left on the device.  Returns the (height, width, 4) RGBA tensor."""
+    import torch
+
+    cfg = {**LAYERS_CONFIG, **BLEND_CONFIG, **(config or {})}
+    lcfg = {k: cfg[k] for k in LAYERS_CONFIG}
+    bcfg = {k: cfg[k] for k in BLEND_CONFIG}
+    h, w, t, nl = plan["height"], plan["width"], cfg["tile_size"], cfg["num_layers"]
+    dev = f"cuda:{mesh.ctx.device}"
+    out = torch.empty((h, w, 4), dtype=torch.uint8, device=dev) if out is None else out
+    if isinstance(color_balance, str) and color_balance != "solve":
+        raise ValueError('color_balance is None, a dict of tables or "solve"')
+    with OrthoStream(plan, graph, surfaces, capacity, mesh=mesh, tile_rows=tile_rows, config=lcfg) as stream:
+        def sweep(balance, blend):
+            corr = []
+            for k in range(stream.num_bands):
+                if k == 0:
+                    for cam, _, _ in stream.loads(0):
+                        stream.upload(0, cam, fetch(cam))
+                else:
+                    for cam, _, _ in stream.loads(k, LOAD_LATE):
+                        stream.upload(k, cam, fetch(cam))
+                if k + 1 < stream.num_bands:
+                    for cam, _, _ in stream.loads(k + 1, LOAD_AHEAD):
+                        stream.upload(k + 1, cam, fetch(cam))
+                row0 = k * tile_rows * t
+                rows = min(tile_rows * t, h - row0)
+                dsm = torch.empty((rows, w), dtype=torch.float32, device=dev)
+                dsm_render(plan, surfaces, mesh=mesh, row0=row0, rows=rows, out=dsm)
+                lay = dict(bgra=torch.empty((nl, rows, w, 4), dtype=torch.uint8, device=dev),
+                           camera_id=torch.empty((nl, rows, w), dtype=torch.int64, device=dev))
+                layers = stream.render(k, out=lay)
+                if blend:
+                    ortho_blend(plan, graph, surfaces, layers, dsm, balance, ctx=mesh.ctx, config=bcfg, out=out[row0:row0 + rows])
+                corr.append(layers["correspondences"])
+            return corr
+
+        if color_balance == "solve":
+            corr = sweep(None, False)
+            color_balance = color_balance_solve(np.concatenate(corr) if corr else np.zeros(0, CORR_DTYPE), graph=graph,
+                                                ctx=mesh.ctx)
+            stream.rewind()
+        sweep(color_balance, True)
     return out
 
 
