@@ -373,13 +373,7 @@ void colourCPU(const Plan &plan, const Cameras &cams, const double *z, uint8_t *
                 continue;
             double bd[ochip_og::KNN];
             uint32_t bi[ochip_og::KNN];
-            for (int k = 0; k < ochip_og::KNN; k++)
-                bd[k] = INFINITY, bi[k] = MISS;
-            for (size_t i = 0; i < n_cams; i++)
-            {
-                const double dx = x - cams.cams24[24 * i], dy = y - cams.cams24[24 * i + 1];
-                ochip_og::knn_offer(dx * dx + dy * dy, (uint32_t)i, bd, bi);
-            }
+            ochip_og::knn_brute(cams.cams24.data(), 24, n_cams, x, y, MISS, bd, bi);
             for (int k = 0; k < ochip_og::KNN && bi[k] != MISS; k++)
             {
                 const double *c = &cams.cams24[24 * (size_t)bi[k]];

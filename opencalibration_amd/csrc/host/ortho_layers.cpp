@@ -98,14 +98,7 @@ void layersCPU(const ortho::Plan &plan, const LayerCameras &cams, const uint8_t 
             const double y = plan.bounds.max_y - row * plan.gsd;
             double bd[ochip_og::KNN];
             uint32_t bi[ochip_og::KNN];
-            for (int k = 0; k < ochip_og::KNN; k++)
-                bd[k] = INFINITY, bi[k] = ochip_ol::NONE;
-            for (uint32_t i = 0; i < n_cams; i++)
-            {
-                const double dx = x - cams.cams[(size_t)i * ochip_ol::CAM_DOUBLES];
-                const double dy = y - cams.cams[(size_t)i * ochip_ol::CAM_DOUBLES + 1];
-                ochip_og::knn_offer(dx * dx + dy * dy, i, bd, bi);
-            }
+            ochip_og::knn_brute(cams.cams.data(), ochip_ol::CAM_DOUBLES, n_cams, x, y, ochip_ol::NONE, bd, bi);
             const size_t i = (size_t)r * W + col;
             if (knn_out)
                 std::copy(bi, bi + ochip_og::KNN, knn_out + i * ochip_og::KNN);
@@ -341,14 +334,7 @@ int och_ortho_band_cameras(ochip_ctx *ctx, const double *raster4, int32_t cols, 
             const double y = max_y - row * gsd;
             double bd[ochip_og::KNN];
             uint32_t bi[ochip_og::KNN];
-            for (int k = 0; k < ochip_og::KNN; k++)
-                bd[k] = INFINITY, bi[k] = ochip_ol::NONE;
-            for (uint32_t i = 0; i < (uint32_t)n_cams; i++)
-            {
-                const double dx = x - cams[(size_t)i * ochip_ol::CAM_DOUBLES];
-                const double dy = y - cams[(size_t)i * ochip_ol::CAM_DOUBLES + 1];
-                ochip_og::knn_offer(dx * dx + dy * dy, i, bd, bi);
-            }
+            ochip_og::knn_brute(cams, ochip_ol::CAM_DOUBLES, n_cams, x, y, ochip_ol::NONE, bd, bi);
             for (int k = 0; k < ochip_og::KNN; k++)
                 if (bi[k] != ochip_ol::NONE)
                     mine[bi[k]] = 1;

@@ -111,6 +111,26 @@ OCHIP_OG void knn_offer(double d, uint32_t id, double bd[KNN], uint32_t bi[KNN])
         }
 }
 
+// a kNN list before the first offer: no distance, every entry `none` (the caller's "no camera" sentinel)
+OCHIP_OG void knn_init(uint32_t none, double bd[KNN], uint32_t bi[KNN])
+{
+    for (int k = 0; k < KNN; k++)
+        bd[k] = INFINITY, bi[k] = none;
+}
+
+// The brute-force search every pruned one is held to: the list of (x, y) over cameras 0 .. n - 1 of a table of `stride`
+// doubles per record (x, y first), offered in ascending order.  Fewer than 5 cameras leave `none` entries at the end.
+OCHIP_OG void knn_brute(const double *cams, size_t stride, size_t n, double x, double y, uint32_t none, double bd[KNN],
+                        uint32_t bi[KNN])
+{
+    knn_init(none, bd, bi);
+    for (size_t i = 0; i < n; i++)
+    {
+        const double dx = x - cams[i * stride], dy = y - cams[i * stride + 1];
+        knn_offer(dx * dx + dy * dy, (uint32_t)i, bd, bi);
+    }
+}
+
 // ortho.cpp:601-611 for one camera's projection `pixel` (cam: the 24-double record): times thumb_scale, truncated, strictly
 // inside the thumbnail.  (int)v > 0 && (int)v < n is v >= 1 && v < n, which also rejects NaN and needs no out-of-range
 // conversion.

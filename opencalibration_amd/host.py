@@ -1173,46 +1173,7 @@ def ortho_mosaic(plan, graph, surfaces, images, mesh=None, config=None, color_ba
     color_balance_solve (on the mesh's device, or the CPU route) turns them into the tables, and the second pass
     RE-RENDERS every band's layers and blends them with the result: a band's layers are never kept beyond its blend, so
     the memory held stays one band's whatever the raster's size, at the price of the layer pass run twice."""
-    cfg = {**LAYERS_CONFIG, **BLEND_CONFIG, **(config or {})}
-    lcfg = {k: cfg[k] for k in LAYERS_CONFIG}
-    bcfg = {k: cfg[k] for k in BLEND_CONFIG}
-    h, w, t, nl = plan["height"], plan["width"], cfg["tile_size"], cfg["num_layers"]
-    if mesh is None:
-        out = np.zeros((h, w, 4), np.uint8) if out is None else out
-    else:
-        import torch
-
-        dev = f"cuda:{mesh.ctx.device}"
-        out = torch.empty((h, w, 4), dtype=torch.uint8, device=dev) if out is None else out
-
-    def band(row0, blend):
-        rows = min(tile_rows * t, h - row0)
-        if mesh is None:
-            dsm = dsm_render(plan, surfaces, row0=row0, rows=rows)
-            layers = ortho_layers(plan, graph, surfaces, images, row0=row0, tile_rows=tile_rows, config=lcfg, dsm=dsm)
-            if blend:
-                ortho_blend(plan, graph, surfaces, layers, dsm, color_balance, config=bcfg, out=out[row0:row0 + rows])
-        else:
-            dsm = torch.empty((rows, w), dtype=torch.float32, device=dev)
-            dsm_render(plan, surfaces, mesh=mesh, row0=row0, rows=rows, out=dsm)
-            lay = dict(bgra=torch.empty((nl, rows, w, 4), dtype=torch.uint8, device=dev),
-                       camera_id=torch.empty((nl, rows, w), dtype=torch.int64, device=dev))
-            layers = ortho_layers(plan, graph, surfaces, images, mesh=mesh, row0=row0, tile_rows=tile_rows, config=lcfg,
-                                  out=lay)
-            layers["bgra"], layers["camera_id"] = lay["bgra"], lay["camera_id"]
-            if blend:
-                ortho_blend(plan, graph, surfaces, layers, dsm, color_balance, ctx=mesh.ctx, config=bcfg, out=out[row0:row0 + rows])
-        return layers["correspondences"]
-
-    if isinstance(color_balance, str):
-        if color_balance != "solve":
-            raise ValueError('color_balance is None, a dict of tables or "solve"')
-        corr = [band(row0, False) for row0 in range(0, h, tile_rows * t)]
-        color_balance = color_balance_solve(np.concatenate(corr) if corr else np.zeros(0, CORR_DTYPE), graph=graph,
-                                            ctx=mesh.ctx if mesh is not None else None)
-    for row0 in range(0, h, tile_rows * t):
-        band(row0, True)
-    return out
+    return _mosaic(plan, graph, surfaces, mesh, config, color_balance, tile_rows, out, images=images)
 
 
 def ortho_mosaic_streamed(plan, graph, surfaces, fetch, mesh, capacity, config=None, color_balance=None, tile_rows=1, out=None):
@@ -1221,47 +1182,65 @@ def ortho_mosaic_streamed(plan, graph, surfaces, fetch, mesh, capacity, config=N
     the device at a time (OrthoStream).  Band k + 1's ahead uploads are issued before band k renders, so that they run
     beside it when the images are page-locked.  color_balance as ortho_mosaic's; "solve" renders the layers twice, the
     second sweep starting from the images the first one left on the device.  Returns the (height, width, 4) RGBA tensor."""
-    import torch
+    return _mosaic(plan, graph, surfaces, mesh, config, color_balance, tile_rows, out, fetch=fetch, capacity=capacity)
 
+
+def _mosaic(plan, graph, surfaces, mesh, config, color_balance, tile_rows, out, images=None, fetch=None, capacity=None):
+    """The band loop of ortho_mosaic (images) and ortho_mosaic_streamed (fetch, capacity): the two differ in where a band's
+    layers come from, ortho_layers over the resident images or an OrthoStream's render behind the band's uploads."""
     cfg = {**LAYERS_CONFIG, **BLEND_CONFIG, **(config or {})}
     lcfg = {k: cfg[k] for k in LAYERS_CONFIG}
     bcfg = {k: cfg[k] for k in BLEND_CONFIG}
-    h, w, t, nl = plan["height"], plan["width"], cfg["tile_size"], cfg["num_layers"]
-    dev = f"cuda:{mesh.ctx.device}"
-    out = torch.empty((h, w, 4), dtype=torch.uint8, device=dev) if out is None else out
     if isinstance(color_balance, str) and color_balance != "solve":
         raise ValueError('color_balance is None, a dict of tables or "solve"')
-    with OrthoStream(plan, graph, surfaces, capacity, mesh=mesh, tile_rows=tile_rows, config=lcfg) as stream:
-        def sweep(balance, blend):
-            corr = []
-            for k in range(stream.num_bands):
-                if k == 0:
-                    for cam, _, _ in stream.loads(0):
-                        stream.upload(0, cam, fetch(cam))
-                else:
-                    for cam, _, _ in stream.loads(k, LOAD_LATE):
-                        stream.upload(k, cam, fetch(cam))
-                if k + 1 < stream.num_bands:
-                    for cam, _, _ in stream.loads(k + 1, LOAD_AHEAD):
-                        stream.upload(k + 1, cam, fetch(cam))
-                row0 = k * tile_rows * t
-                rows = min(tile_rows * t, h - row0)
-                dsm = torch.empty((rows, w), dtype=torch.float32, device=dev)
-                dsm_render(plan, surfaces, mesh=mesh, row0=row0, rows=rows, out=dsm)
-                lay = dict(bgra=torch.empty((nl, rows, w, 4), dtype=torch.uint8, device=dev),
-                           camera_id=torch.empty((nl, rows, w), dtype=torch.int64, device=dev))
-                layers = stream.render(k, out=lay)
-                if blend:
-                    ortho_blend(plan, graph, surfaces, layers, dsm, balance, ctx=mesh.ctx, config=bcfg, out=out[row0:row0 + rows])
-                corr.append(layers["correspondences"])
-            return corr
+    h, w, nl, band_rows = plan["height"], plan["width"], cfg["num_layers"], tile_rows * cfg["tile_size"]
+    if mesh is None:
+        ctx = None
+        out = np.zeros((h, w, 4), np.uint8) if out is None else out
+    else:
+        import torch
 
+        ctx, dev = mesh.ctx, f"cuda:{mesh.ctx.device}"
+        out = torch.empty((h, w, 4), dtype=torch.uint8, device=dev) if out is None else out
+    stream = OrthoStream(plan, graph, surfaces, capacity, mesh=mesh, tile_rows=tile_rows, config=lcfg) if fetch is not None else None
+
+    def band(k, balance, blend):
+        row0 = k * band_rows
+        rows = min(band_rows, h - row0)
+        if stream is not None:  # before the band's DSM and render: its own loads still missing, then the next band's ahead ones
+            for cam, _, _ in stream.loads(0) if k == 0 else stream.loads(k, LOAD_LATE):
+                stream.upload(k, cam, fetch(cam))
+            if k + 1 < stream.num_bands:
+                for cam, _, _ in stream.loads(k + 1, LOAD_AHEAD):
+                    stream.upload(k + 1, cam, fetch(cam))
+        if mesh is None:
+            dsm, lay = dsm_render(plan, surfaces, row0=row0, rows=rows), None
+        else:
+            dsm = torch.empty((rows, w), dtype=torch.float32, device=dev)
+            dsm_render(plan, surfaces, mesh=mesh, row0=row0, rows=rows, out=dsm)
+            lay = dict(bgra=torch.empty((nl, rows, w, 4), dtype=torch.uint8, device=dev),
+                       camera_id=torch.empty((nl, rows, w), dtype=torch.int64, device=dev))
+        if stream is not None:
+            layers = stream.render(k, out=lay)
+        else:
+            layers = ortho_layers(plan, graph, surfaces, images, mesh=mesh, row0=row0, tile_rows=tile_rows, config=lcfg, out=lay,
+                                  dsm=dsm if mesh is None else None)
+        if blend:
+            ortho_blend(plan, graph, surfaces, layers, dsm, balance, ctx=ctx, config=bcfg, out=out[row0:row0 + rows])
+        return layers["correspondences"]
+
+    try:
+        bands = range(-(-h // band_rows))
         if color_balance == "solve":
-            corr = sweep(None, False)
-            color_balance = color_balance_solve(np.concatenate(corr) if corr else np.zeros(0, CORR_DTYPE), graph=graph,
-                                                ctx=mesh.ctx)
-            stream.rewind()
-        sweep(color_balance, True)
+            corr = [band(k, None, False) for k in bands]
+            color_balance = color_balance_solve(np.concatenate(corr) if corr else np.zeros(0, CORR_DTYPE), graph=graph, ctx=ctx)
+            if stream is not None:
+                stream.rewind()
+        for k in bands:
+            band(k, color_balance, True)
+    finally:
+        if stream is not None:
+            stream.close()
     return out
 
 

@@ -16,6 +16,7 @@ if __name__ == "__main__":
 from layers_fixtures import DISTORTED, expected_layers, knn_agrees, four_camera_scene, noise_images, plan_with_gsd  # noqa: E402
 from ortho_fixtures import (cloud_surface, functional_scene, jittered_cameras, make_graph, perturbed_mesh,  # noqa: E402
                             three_cameras)
+from ortho_stream_fixtures import BAND_SET_SCENES, knn_band_sets, scene_knn_overflow  # noqa: E402
 from opencalibration_amd import capi, host  # noqa: E402
 
 
@@ -139,6 +140,23 @@ def scenario_device_tensor_outputs(ctx):
     g.close()
 
 
+def scenario_knn_on_band_set_scenes(ctx):
+    """pass 1's search and the band kernel's copy of it agree: the render's own kNN lists give the band kernel's sets"""
+    for name, scene in BAND_SET_SCENES.items():
+        g, s, imgs, plan, cfg = scene()
+        dev, _, _ = compare(ctx, g, [s], imgs, plan, config=cfg, knn=True)
+        sets = host.ortho_band_cameras(plan, g, [s], tile_rows=1, config=cfg, ctx=ctx)
+        assert np.array_equal(knn_band_sets(dev["knn"], len(imgs), cfg["tile_size"]), sets), name
+        g.close()
+
+
+def scenario_knn_candidate_overflow(ctx):
+    g, s, imgs, plan, cfg = scene_knn_overflow()
+    dev, _, _ = compare(ctx, g, [s], imgs, plan, config=cfg, knn=True)
+    assert (dev["bgra"][0, ..., 3] == 255).any()
+    g.close()
+
+
 SCENARIOS = {
     "three_camera_fixture_and_functional_scene": scenario_three_camera_fixture_and_functional_scene,
     "distorted_scene_tiles_bands_and_knn": scenario_distorted_scene_tiles_bands_and_knn,
@@ -147,6 +165,8 @@ SCENARIOS = {
     "two_surfaces": scenario_two_surfaces,
     "single_pixel_path_and_radius_cap": scenario_single_pixel_path_and_radius_cap,
     "device_tensor_outputs": scenario_device_tensor_outputs,
+    "knn_on_band_set_scenes": scenario_knn_on_band_set_scenes,
+    "knn_candidate_overflow": scenario_knn_candidate_overflow,
 }
 
 if __name__ == "__main__":

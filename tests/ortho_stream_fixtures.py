@@ -10,14 +10,14 @@ from opencalibration_amd import host
 AHEAD, LATE = host.LOAD_AHEAD, host.LOAD_LATE
 
 
-def _flat_scene(pos, ori, seed):
+def _flat_scene(pos, ori, seed, n_images=None):
     pos = np.asarray(pos, np.float64)
     g = make_graph(pos, ori, DISTORTED)
     lo, hi = pos[:, :2].min(0) - 6, pos[:, :2].max(0) + 6
     pts = cloud_surface([(lo[0], lo[1], 0), (hi[0], lo[1], 0), (hi[0], hi[1], 0), (lo[0], hi[1], 0),
                          ((lo[0] + hi[0]) / 2, (lo[1] + hi[1]) / 2, 0.5)])
     s = host.rebuild_mesh(pos, previous=pts)
-    return g, s, noise_images(len(pos), 120, 160, seed)
+    return g, s, noise_images(len(pos) if n_images is None else n_images, 120, 160, seed)
 
 
 def plan_of(width, height, gsd, min_x, max_y, mean_camera_z=10.0):
@@ -67,6 +67,25 @@ def scene_overflow():
     cams[:, 2] = 10.0 + np.arange(1100) * 0.01
     order = rng.permutation(1100)
     return np.ascontiguousarray(cams[order]), plan_of(50, 40, 0.5, -2.0, 21.0)
+
+
+def scene_knn_overflow():
+    """1 040 cameras jittered inside the rectangle of pixel centres of the 16 x 16 tile (1, 1) of a 50 x 40 raster at gsd
+    0.5, and 40 spread around it: that tile's candidate list exceeds the kernels' 1 024 and its pixels scan the whole table,
+    the other tiles keep their lists.  Every camera shares one image."""
+    rng = np.random.default_rng(13)
+    plan = plan_of(50, 40, 0.5, -2.0, 21.0)
+    x = np.arange(16, 32) * plan["gsd"] + plan["min_x"]
+    y = plan["max_y"] - np.arange(16, 32) * plan["gsd"]
+    inside = np.stack([rng.uniform(x[0] + 0.1, x[-1] - 0.1, 1040), rng.uniform(y[-1] + 0.1, y[0] - 0.1, 1040)], 1)
+    around = np.stack([rng.uniform(-2, 23, 40), rng.uniform(1, 21, 40)], 1)
+    pos = np.concatenate([inside, around])[rng.permutation(1080)]
+    pos = np.concatenate([pos, 10.0 + rng.uniform(-0.3, 0.3, (1080, 1))], 1)
+    held = (pos[:, 0] >= x[0]) & (pos[:, 0] <= x[-1]) & (pos[:, 1] >= y[-1]) & (pos[:, 1] <= y[0])
+    assert held.sum() > 1024 and len(np.unique(pos[held, :2], axis=0)) == held.sum()  # the scene cannot stop overflowing
+    ori = [qmul(quat(rng.normal(size=3), 0.04), DOWN) for _ in pos]
+    g, s, imgs = _flat_scene(pos, ori, 14, n_images=1)
+    return g, s, imgs * len(pos), plan, dict(tile_size=16, correspondence_subsample=5)
 
 
 def strip_scene(seed=3):
