@@ -554,6 +554,21 @@ extern "C"
     int och_color_balance_remove_gauge(size_t n, const double *xy, double *offsets3);
     const char *och_color_balance_last_error(void);
 
+    /* ---- the load stage's image thumbnails (opencalibration_amd/csrc/host/thumbnail.cpp, csrc/thumbnail.hpp;
+     * src/extract/extract_image.cpp:42-52) -----------------------------------------------------------------------------------
+     * och_thumbnail_size: the thumbnail of a width x height image has rint(height * s) rows and rint(width * s) columns, s =
+     * 50 / sqrt(width * height); refused below 2500 pixels and when a side comes out 0.  och_image_thumbnails: a batch of
+     * equally sized BGR images (a device pointer when images_on_device, which needs ctx) -> rgb_out (host) [n][rows][cols][3],
+     * R G B; ctx == NULL: the CPU route, bit for bit what the device computes.  och_graph_make_thumbnails: the same, stored
+     * on the nodes node_ids[i] (ids as och_graph_load_images returns them) for och_orthomosaic_thumbnail.  -1 +
+     * och_thumbnail_last_error() (och_last_error(g) for the graph call) on failure. */
+    int och_thumbnail_size(int width, int height, int32_t *rows, int32_t *cols);
+    int och_image_thumbnails(ochip_ctx *ctx, const uint8_t *images_bgr, uint32_t n_images, int width, int height,
+                             int images_on_device, uint8_t *rgb_out);
+    int och_graph_make_thumbnails(och_graph *g, ochip_ctx *ctx, const uint8_t *images_bgr, uint32_t n_images, int width,
+                                  int height, int images_on_device, const uint64_t *node_ids);
+    const char *och_thumbnail_last_error(void);
+
 #ifdef __cplusplus
 }
 #endif

@@ -856,6 +856,20 @@ extern "C"
                                      const double *vig3, double *cost, int32_t *n_out, double *JtJ, double *Jtr,
                                      int32_t *cam_col, int32_t *model_col);
 
+    /* ---- the load stage's image thumbnails (opencalibration_amd/csrc/thumbnail.hip; src/extract/extract_image.cpp:42-52:
+     *      BGR -> 8-bit Lab, INTER_AREA by 50 / sqrt(pixels), Lab -> BGR, stored R G B) ---- */
+    /* rows = rint(height * scale), cols = rint(width * scale), ties to even.  OCHIP_EINVAL for a side outside 1..65535, an
+     * image of fewer than 2500 pixels (scale > 1) and a thumbnail side of 0.  Needs no device. */
+    int ochip_thumbnail_size(int width, int height, int32_t *rows, int32_t *cols);
+    /* images_bgr: n_images x height x width x 3 bytes, a device pointer when images_on_device; rgb_out (host): n_images x
+     * rows x cols x 3, R G B interleaved - the layout och_graph_set_thumbnail takes.  The first call on a context fills
+     * the context's table of all 2^24 BGR codes' Lab (64 MB of HBM, kept until the context goes). */
+    int ochip_image_thumbnails(ochip_ctx *ctx, const uint8_t *images_bgr, uint32_t n_images, int width, int height,
+                               int images_on_device, uint8_t *rgb_out);
+    /* For tests and probes: out[i] = that table's entry (L | a << 8 | b << 16) of code B | G << 8 | R << 16 = codes[i]
+     * (host arrays; n may be 0); fill_ms (may be NULL): what the one launch that filled the table took. */
+    int ochip_debug_lab_table(ochip_ctx *ctx, const uint32_t *codes, size_t n, uint32_t *out, float *fill_ms);
+
 #ifdef __cplusplus
 }
 #endif

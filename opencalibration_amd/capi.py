@@ -45,6 +45,7 @@ EXPORTS = [
     "ochip_ortho_band_cameras", "ochip_image_slots_create", "ochip_image_slots_destroy", "ochip_image_slots_address",
     "ochip_image_slots_upload", "ochip_image_slots_mark", "ochip_image_slots_wait", "ochip_image_slots_elapsed",
     "ochip_color_balance_solve", "ochip_color_balance_evaluate",
+    "ochip_thumbnail_size", "ochip_image_thumbnails", "ochip_debug_lab_table",
 ]
 
 _lib = None
@@ -209,6 +210,9 @@ def load():
         L.ochip_laplacian_blend.argtypes = [vp, i32, i32, i32, i32, vp, vp, vp]
         L.ochip_color_balance_solve.argtypes = [vp, vp, C.c_uint64, vp, u32, vp, u32, vp, vp, vp]
         L.ochip_color_balance_evaluate.argtypes = [vp, vp, C.c_uint64, vp, u32, vp, u32, vp, vp, vp, vp, vp, vp, vp, vp]
+        L.ochip_thumbnail_size.argtypes = [i32, i32, vp, vp]
+        L.ochip_image_thumbnails.argtypes = [vp, vp, u32, i32, i32, i32, vp]
+        L.ochip_debug_lab_table.argtypes = [vp, vp, C.c_size_t, vp, vp]
         _lib = L
     return _lib
 
@@ -264,6 +268,15 @@ class Context:
     def _check(self, rc, what):
         if rc != 0:
             raise OchipError(f"{what} = {rc}: {self.L.ochip_last_error(self.h).decode()}")
+
+    def lab_table(self, codes):
+        """The thumbnail pass's table of all BGR codes (filled on first use) at `codes` (B | G << 8 | R << 16): the 8-bit Lab as
+        L | a << 8 | b << 16, and the milliseconds its one fill launch took."""
+        codes = np.ascontiguousarray(codes, np.uint32).reshape(-1)
+        out, ms = np.zeros(len(codes), np.uint32), C.c_float(0)
+        self._check(self.L.ochip_debug_lab_table(self.h, codes.ctypes.data, len(codes), out.ctypes.data, C.byref(ms)),
+                    "ochip_debug_lab_table")
+        return out, float(ms.value)
 
     def sibling(self, index):
         """The index-th sibling context (same device, own streams and scratch; owned by this context): independent work

@@ -273,6 +273,11 @@ void ochip_ctx_destroy(ochip_ctx *ctx)
     for (void *b : {ctx->desc_fp4_dev, ctx->desc_negpop_dev, ctx->desc_pop_dev})
         if (b)
             (void)hipFree(b);
+    if (ctx->lab_table_mem)
+    {
+        ctx->lab_table_mem->release();
+        delete ctx->lab_table_mem;
+    }
     for (auto &b : ctx->dev_pool)
         (void)hipFree(b.first);
     for (auto &b : ctx->pinned_pool)

@@ -21,6 +21,11 @@ struct ochip_profile_slot
     double total_ms = 0;
 };
 
+namespace ochip
+{
+struct dev_blocks;
+}
+
 struct ochip_ctx
 {
     int device = 0;
@@ -108,6 +113,13 @@ struct ochip_ctx
     // chunks of ochip_akaze_* on this context whose first host read-back (the candidate counts, after the scale space and
     // the detector) has arrived: ochip_akaze_progress, for a caller that starts its launch sequences out of step
     std::atomic<uint64_t> akaze_readbacks{0};
+
+    // thumbnail.hip: the 8-bit Lab of all 2^24 BGR codes (64 MB, L | a << 8 | b << 16) and the conversion's tables, filled on
+    // the first thumbnail call; lab_table_mem owns both blocks
+    ochip::dev_blocks *lab_table_mem = nullptr;
+    uint32_t *lab_table_dev = nullptr;
+    void *lab_tables_dev = nullptr; // ochip_ol::lab_tables
+    float lab_table_fill_ms = 0;    // the fill kernel's time (ochip_debug_lab_table)
 
     // what the host library keeps with the context (ochip_ctx_attachment: the extraction slots of host/extract_slots.hpp)
     void *attachment = nullptr;

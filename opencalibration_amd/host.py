@@ -278,6 +278,10 @@ def load():
         L.och_color_balance_evaluate_plan.argtypes = [vp, sz, sz, vp, vp, sz, vp, vp, vp, vp, vp, vp, vp, vp]
         L.och_color_balance_remove_gauge.argtypes = [sz, vp, vp]
         L.och_color_balance_last_error.restype = C.c_char_p
+        L.och_thumbnail_size.argtypes = [C.c_int, C.c_int, C.POINTER(i32), C.POINTER(i32)]
+        L.och_image_thumbnails.argtypes = [vp, vp, u32, C.c_int, C.c_int, C.c_int, vp]
+        L.och_graph_make_thumbnails.argtypes = [vp, vp, vp, u32, C.c_int, C.c_int, C.c_int, _u64p]
+        L.och_thumbnail_last_error.restype = C.c_char_p
         _lib = L
     return _lib
 
@@ -304,6 +308,42 @@ def extract_features_batch(ctx, images_bgr, max_keypoints=20000, device_shape=No
     if rc != 0:
         raise capi.OchipError("extract failed: " + L.och_extract_last_error().decode())
     return [(loc[i, :counts[i]].copy(), st[i, :counts[i]].copy(), de[i, :counts[i]].copy(), int(ns[i])) for i in range(n)]
+
+
+def thumbnail_size(width, height):
+    """(rows, cols) of the load stage's thumbnail of a width x height image: both sides scaled by 50 / sqrt(width * height)
+    and rounded, ties to even.  Refused below 2 500 pixels and when a side comes out 0."""
+    L = load()
+    rows, cols = C.c_int32(0), C.c_int32(0)
+    if L.och_thumbnail_size(int(width), int(height), C.byref(rows), C.byref(cols)) != 0:
+        raise ValueError(L.och_thumbnail_last_error().decode())
+    return rows.value, cols.value
+
+
+def _image_batch(images_bgr, device_shape):
+    """(keep-alive, pointer, n, h, w, on_device) of a batch given as extract_features_batch takes it"""
+    if device_shape is None:
+        imgs = np.ascontiguousarray(images_bgr, np.uint8)
+        if imgs.ndim != 4 or imgs.shape[3] != 3:
+            raise ValueError("images are (n, h, w, 3) uint8")
+        n, h, w, _ = imgs.shape
+        return imgs, imgs.ctypes.data, n, h, w, 0
+    n, h, w = device_shape
+    return None, int(images_bgr), n, h, w, 1
+
+
+def image_thumbnails(images_bgr, ctx=None, device_shape=None):
+    """The load stage's thumbnails of a batch of equally sized BGR images (extract_image.cpp:42-52: Lab, INTER_AREA by
+    50 / sqrt(pixels), back, R G B): (n, rows, cols, 3) uint8.  images_bgr: (n, h, w, 3) uint8 host array or, with
+    device_shape=(n, h, w) and a context, a device pointer.  ctx=None: the CPU route, bit for bit the device's."""
+    L = load()
+    keep, src, n, h, w, on_dev = _image_batch(images_bgr, device_shape)
+    rows, cols = thumbnail_size(w, h)
+    out = np.zeros((n, rows, cols, 3), np.uint8)
+    if L.och_image_thumbnails(ctx.h if ctx is not None else None, src, n, w, h, on_dev, out.ctypes.data) != 0:
+        raise capi.OchipError("image_thumbnails failed: " + L.och_thumbnail_last_error().decode())
+    del keep
+    return out
 
 
 RELAX_SUMMARY_NAMES = ["solves", "iterations_total", "last_iterations", "initial_cost", "final_cost", "residual_blocks",
@@ -1510,9 +1550,21 @@ class Graph:
         self.node_ids.append(nid)
         return nid
 
-    def load_images(self, ctx, images_bgr, model, positions, max_keypoints=30000, device_shape=None):
+    def make_thumbnails(self, images_bgr, node_ids, ctx=None, device_shape=None):
+        """image_thumbnails of the batch, stored on the nodes `node_ids` (one id per image) for the orthomosaic preview."""
+        keep, src, n, h, w, on_dev = _image_batch(images_bgr, device_shape)
+        ids = np.ascontiguousarray(node_ids, np.uint64).reshape(-1)
+        if len(ids) != n:
+            raise ValueError("one node id per image")
+        ids = ids if n else np.zeros(1, np.uint64)
+        if self.L.och_graph_make_thumbnails(self.h, ctx.h if ctx is not None else None, src, n, w, h, on_dev, ids) != 0:
+            raise capi.OchipError("make_thumbnails failed: " + self.L.och_last_error(self.h).decode())
+        del keep
+
+    def load_images(self, ctx, images_bgr, model, positions, max_keypoints=30000, device_shape=None, thumbnails=False):
         """The load stage for a batch of equally sized images: extract_features on the device, one node per image.
-        images_bgr: (n, h, w, 3) uint8 host array or, with device_shape=(n, h, w), a device pointer.  Returns
+        images_bgr: (n, h, w, 3) uint8 host array or, with device_shape=(n, h, w), a device pointer.  thumbnails=True:
+        the same buffer's thumbnails (make_thumbnails, on the device) go onto the new nodes after the extraction.  Returns
         (mean features per image, mean sparse features per image)."""
         if device_shape is None:
             imgs = np.ascontiguousarray(images_bgr, np.uint8)
@@ -1527,6 +1579,8 @@ class Graph:
         if rc != 0:
             raise capi.OchipError("load_images failed: " + self.L.och_last_error(self.h).decode())
         self.node_ids += [int(i) for i in ids[:n]]
+        if thumbnails:
+            self.make_thumbnails(images_bgr, ids[:n], ctx, device_shape)
         return totals[0] / max(n, 1), totals[1] / max(n, 1)
 
     def load_link_images(self, ctx, images_bgr, model, positions, orientations=None, max_keypoints=30000, device_shape=None):
