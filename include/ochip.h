@@ -614,6 +614,27 @@ extern "C"
     int ochip_relaxp_solve(ochip_relaxp_problem *p, const ochip_relax_options *opt, ochip_relax_summary *summary);
     /* cam_q: n_cams x 4 (optimised cameras normalised), point_xyz: n_points x 3, model: 8; any may be NULL */
     int ochip_relaxp_get_state(ochip_relaxp_problem *p, double *cam_q, double *point_xyz, double *model);
+    /* Test seams.  ochip_relaxp_evaluate: one evaluation with Jacobians at the current state (the engine's own kernels):
+     * the total cost, n (unknowns of the reduced system), U (n x n, both triangles) and g_c (n) in the library's unknown
+     * order, per point V (6: xx xy xz yy yz zz) and g_p (3), gmax_p = the largest |g| over the point columns; order_out
+     * (n_cams + 8) = the first unknown of every camera, then of f, ppx, ppy, k1, k2, k3, p1, p2, or -1.  Outputs may be
+     * NULL; with all of cost .. gmax_p NULL nothing is evaluated (n and the order only).  Returns 1 when an observation is
+     * not finite.
+     * ochip_relaxp_step: one LM step on the Jacobian of the last ochip_relaxp_evaluate, as lm_solve takes it: the damped,
+     * scaled reduced system with the points' Schur term, its factorisation and back-solve, the candidate state.  scale_in
+     * (n, NULL: the solver's 1 / (1 + sqrt(diag U))) scales the reduced unknowns; the points' scaling is the engine's own,
+     * fixed by the first step after create / solve / set_structure_only.  y_in (n, may be NULL) replaces the solved y
+     * before the candidate is formed.  alpha2 != 0: the candidate is formed a second time, as the line search contracts a
+     * step (the stored point step times alpha2, then the slope kernel); the outputs are then the second candidate's.
+     * Output (any may be NULL): W_out ((n + 1) x n, lower triangle) the reduced system as built, row n its right-hand
+     * side; y_out (n) the solved y; the candidate cam_q2 (n_cams x 4), model2 (8), X2 (n_points x 3); pt_scale (3 per
+     * point), pt_Vinv (6) and pt_d (3, the unscaled full step of the point); scal_out[4] = model cost change, |x -
+     * candidate|^2, |candidate|^2, g_p . d_p; fail_out the factorisation's failure flag.  The current state is untouched. */
+    int ochip_relaxp_evaluate(ochip_relaxp_problem *p, double *cost, int *n_out, double *U, double *g_c, double *V, double *g_p,
+                              double *gmax_p, int32_t *order_out);
+    int ochip_relaxp_step(ochip_relaxp_problem *p, double radius, const double *scale_in, const double *y_in, double alpha2,
+                          double *W_out, double *y_out, double *cam_q2, double *model2, double *X2, double *pt_scale, double *pt_Vinv,
+                          double *pt_d, double *scal_out, int32_t *fail_out);
 
     /* ---- profiling: HIP-event time of every launch of a kernel since the last reset ------------- */
     int ochip_profile_reset(ochip_ctx *ctx);

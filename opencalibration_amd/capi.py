@@ -34,7 +34,7 @@ EXPORTS = [
     "ochip_relaxg_problem_create", "ochip_relaxg_problem_destroy", "ochip_relaxg_set_structure_only", "ochip_relaxg_solve",
     "ochip_relaxg_get_state", "ochip_relaxg_evaluate", "ochip_relaxg_set_exchange",
     "ochip_relaxp_problem_create", "ochip_relaxp_problem_destroy", "ochip_relaxp_set_structure_only", "ochip_relaxp_solve",
-    "ochip_relaxp_get_state",
+    "ochip_relaxp_get_state", "ochip_relaxp_evaluate", "ochip_relaxp_step",
     "ochip_profile_reset", "ochip_profile_get", "ochip_match_work", "ochip_relax_work", "ochip_relax_memory", "ochip_work_counters",
     "ochip_debug_fp64", "ochip_debug_std_sort", "ochip_debug_lm_step", "ochip_debug_homography_fit4", "ochip_match_sort", "ochip_ransac_homography_batch_sorted", "ochip_edge_lists",
     "ochip_dense_index_create", "ochip_dense_index_destroy", "ochip_dense_match", "ochip_dense_link", "ochip_dense_triangulate",
@@ -153,6 +153,45 @@ def relaxg_desc(scene):
     if scene.get("rel_cam") is not None:
         d.n_rel, d.rel_cam, d.rel_pose = np.size(scene["rel_cam"]) // 2, arr("rel_cam", np.uint32), arr("rel_pose", np.float64)
         d.rel_huber_a = scene["rel_huber_a"]
+    return d, keep
+
+
+class RelaxpDesc(C.Structure):
+    """include/ochip.h: ochip_relaxp_desc"""
+    _fields_ = [("n_cams", C.c_uint32), ("cam_pos", C.c_void_p), ("cam_q", C.c_void_p), ("cam_optimize", C.c_void_p),
+                ("n_points", C.c_uint32), ("point_xyz", C.c_void_p), ("n_groups", C.c_uint32), ("grp_first", C.c_void_p),
+                ("grp_cam", C.c_void_p), ("obs_px", C.c_void_p), ("functor", C.c_int), ("model", C.c_double * 8),
+                ("opt_focal", C.c_uint8), ("opt_principal", C.c_uint8), ("n_radial_free", C.c_uint8),
+                ("focal_lo", C.c_double), ("focal_hi", C.c_double), ("huber_a", C.c_double),
+                ("mono_observations", C.c_uint32), ("mono_r_max", C.c_double)]
+
+
+def relaxp_desc(scene):
+    """(RelaxpDesc, arrays it points into) of a scene dict holding the ochip_relaxp_desc fields by name: cam_pos, cam_q,
+    cam_optimize, point_xyz, grp_first (n_groups + 1), grp_cam, obs_px, functor, model, huber_a; optional opt_focal,
+    opt_principal, n_radial_free, focal_lo, focal_hi, mono_observations, mono_r_max (absent: zero / 100, 20000)."""
+    d = RelaxpDesc()
+    keep = []
+
+    def arr(name, dtype):
+        a = np.ascontiguousarray(scene[name], dtype).reshape(-1)
+        a = a if a.size else np.zeros(1, dtype)
+        keep.append(a)
+        return a.ctypes.data
+
+    d.n_cams = len(scene["cam_pos"])
+    d.cam_pos, d.cam_q, d.cam_optimize = arr("cam_pos", np.float64), arr("cam_q", np.float64), arr("cam_optimize", np.uint8)
+    d.n_points, d.point_xyz = np.size(scene["point_xyz"]) // 3, arr("point_xyz", np.float64)
+    d.n_groups = np.size(scene["grp_cam"]) // 2
+    d.grp_first, d.grp_cam, d.obs_px = arr("grp_first", np.uint32), arr("grp_cam", np.uint32), arr("obs_px", np.float64)
+    assert np.size(scene["grp_first"]) == d.n_groups + 1 and np.size(scene["obs_px"]) == 4 * d.n_points
+    d.functor, d.huber_a = int(scene["functor"]), float(scene["huber_a"])
+    for i, v in enumerate(scene["model"]):
+        d.model[i] = v
+    d.opt_focal, d.opt_principal = int(scene.get("opt_focal", 0)), int(scene.get("opt_principal", 0))
+    d.n_radial_free = int(scene.get("n_radial_free", 0))
+    d.focal_lo, d.focal_hi = scene.get("focal_lo", 100.0), scene.get("focal_hi", 20000.0)
+    d.mono_observations, d.mono_r_max = int(scene.get("mono_observations", 0)), scene.get("mono_r_max", 0.0)
     return d, keep
 
 
@@ -597,6 +636,96 @@ class Context:
         finally:
             L.ochip_relax_problem_destroy(p)
         return out
+
+    def _relaxp_open(self, scene, structure_only):
+        L = self.L
+        vp = C.c_void_p
+        L.ochip_relaxp_problem_create.argtypes = [vp, C.POINTER(RelaxpDesc), C.POINTER(vp)]
+        L.ochip_relaxp_problem_destroy.argtypes = [vp]
+        L.ochip_relaxp_problem_destroy.restype = None
+        L.ochip_relaxp_set_structure_only.argtypes = [vp, C.c_int]
+        L.ochip_relaxp_solve.argtypes = [vp, C.POINTER(RelaxOptions), C.POINTER(RelaxSummary)]
+        L.ochip_relaxp_get_state.argtypes = [vp, vp, vp, vp]
+        L.ochip_relaxp_evaluate.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_int), vp, vp, vp, vp, C.POINTER(C.c_double), vp]
+        L.ochip_relaxp_step.argtypes = [vp, C.c_double, vp, vp, C.c_double, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(C.c_int32)]
+        d, keep = relaxp_desc(scene)
+        p = vp()
+        self._check(L.ochip_relaxp_problem_create(self.h, C.byref(d), C.byref(p)), "ochip_relaxp_problem_create")
+        if structure_only:
+            rc = L.ochip_relaxp_set_structure_only(p, 1)
+            if rc:
+                L.ochip_relaxp_problem_destroy(p)
+                self._check(rc, "ochip_relaxp_set_structure_only")
+        return d, keep, p
+
+    def _relaxp_eval(self, d, p):
+        L = self.L
+        cost, n, gmax = C.c_double(), C.c_int(), C.c_double()
+        order = np.zeros(d.n_cams + 8, np.int32)
+        self._check(L.ochip_relaxp_evaluate(p, None, C.byref(n), None, None, None, None, None, order.ctypes.data),
+                    "ochip_relaxp_evaluate")  # (n and the order alone)
+        n, m = n.value, d.n_points
+        U, g_c, V, g_p = np.zeros((max(n, 1), max(n, 1))), np.zeros(max(n, 1)), np.zeros((max(m, 1), 6)), np.zeros((max(m, 1), 3))
+        rc = L.ochip_relaxp_evaluate(p, C.byref(cost), None, U.ctypes.data, g_c.ctypes.data, V.ctypes.data, g_p.ctypes.data,
+                                     C.byref(gmax), None)
+        if rc != 0:
+            raise OchipError(f"ochip_relaxp_evaluate = {rc}: {L.ochip_last_error(self.h).decode()}")
+        q, X, model = np.zeros((d.n_cams, 4)), np.zeros((max(m, 1), 3)), np.zeros(8)
+        self._check(L.ochip_relaxp_get_state(p, q.ctypes.data, X.ctypes.data, model.ctypes.data), "ochip_relaxp_get_state")
+        return dict(cost=cost.value, n=n, U=U[:n, :n], g_c=g_c[:n], V=V[:m], g_p=g_p[:m], gmax_p=gmax.value, order=order,
+                    cam_q=q, point_xyz=X[:m], model=model)
+
+    def relaxp_evaluate(self, scene, structure_only=False, iterations=0, radius=1e4):
+        """One evaluation of a points-engine relax problem (ochip_relaxp_problem_create, ochip_relaxp_evaluate, destroy).
+        scene: dict of the ochip_relaxp_desc fields (relaxp_desc).  iterations > 0: ochip_relaxp_solve with that many
+        iterations (initial trust-region radius `radius`) first.  dict: cost, n, U (n x n), g_c, V (n_points x 6), g_p
+        (n_points x 3), gmax_p, order (n_cams + 8), cam_q, point_xyz and model (the current state), summary (of the solve, or
+        None).  An evaluation that reports a non-finite observation raises OchipError."""
+        d, keep, p = self._relaxp_open(scene, structure_only)
+        try:
+            summary = None
+            if iterations > 0:
+                opt = RelaxOptions(max_num_iterations=int(iterations), initial_trust_region_radius=float(radius),
+                                   function_tolerance=1e-6, gradient_tolerance=1e-10, parameter_tolerance=1e-8)
+                s = RelaxSummary()
+                self._check(self.L.ochip_relaxp_solve(p, C.byref(opt), C.byref(s)), "ochip_relaxp_solve")
+                summary = {k: getattr(s, k) for k, _ in RelaxSummary._fields_}
+            out = self._relaxp_eval(d, p)
+            out["summary"] = summary
+        finally:
+            self.L.ochip_relaxp_problem_destroy(p)
+        return out
+
+    def relaxp_step(self, scene, steps, structure_only=False):
+        """ochip_relaxp_evaluate, then one ochip_relaxp_step per entry of `steps` on the same problem (the first fixes the
+        points' Jacobi scaling, the later ones keep it).  A step is a dict: radius, and optionally scale (n; absent: the
+        solver's own), y_in (n) and alpha2 - or a callable (evaluation, results so far) that returns one.
+        Returns (evaluation as relaxp_evaluate, [dict per step: W ((n + 1) x n, lower triangle, row n the right-hand
+        side), y, cam_q2, model2, X2, pt_scale, pt_Vinv, pt_d, model_cost_change, step_sq, cand_sq, slope_p, fail])."""
+        d, keep, p = self._relaxp_open(scene, structure_only)
+        try:
+            ev = self._relaxp_eval(d, p)
+            n, m = ev["n"], d.n_points
+            outs = []
+            for st in steps:
+                st = st(ev, outs) if callable(st) else st
+                sc = None if st.get("scale") is None else np.ascontiguousarray(st["scale"], np.float64)
+                yi = None if st.get("y_in") is None else np.ascontiguousarray(st["y_in"], np.float64)
+                assert (sc is None or sc.shape == (n,)) and (yi is None or yi.shape == (n,))
+                W, y = np.zeros((n + 1, max(n, 1))), np.zeros(max(n, 1))
+                q2, m2, X2 = np.zeros((d.n_cams, 4)), np.zeros(8), np.zeros((max(m, 1), 3))
+                ps, pv, pd = np.zeros((max(m, 1), 3)), np.zeros((max(m, 1), 6)), np.zeros((max(m, 1), 3))
+                scal, fail = np.zeros(4), C.c_int32()
+                self._check(self.L.ochip_relaxp_step(p, float(st["radius"]), None if sc is None else sc.ctypes.data,
+                                                     None if yi is None else yi.ctypes.data, float(st.get("alpha2", 0.0)),
+                                                     W.ctypes.data, y.ctypes.data, q2.ctypes.data, m2.ctypes.data, X2.ctypes.data,
+                                                     ps.ctypes.data, pv.ctypes.data, pd.ctypes.data, scal.ctypes.data, C.byref(fail)),
+                            "ochip_relaxp_step")
+                outs.append(dict(W=W[:, :n], y=y[:n], cam_q2=q2, model2=m2, X2=X2[:m], pt_scale=ps[:m], pt_Vinv=pv[:m], pt_d=pd[:m],
+                                 model_cost_change=scal[0], step_sq=scal[1], cand_sq=scal[2], slope_p=scal[3], fail=fail.value))
+        finally:
+            self.L.ochip_relaxp_problem_destroy(p)
+        return ev, outs
 
     def profile_reset(self):
         self._check(self.L.ochip_profile_reset(self.h), "ochip_profile_reset")

@@ -1648,11 +1648,6 @@ int lm_solve(lm_system &S, lm_model &M, const ochip_relax_options *opt, ochip_re
     }
 }
 
-} // namespace ochip
-
-// ---- test seam: one LM step's linear algebra on a given system (include/ochip.h: ochip_debug_lm_step) ----------------
-namespace
-{
 // the lower triangle (rows 0 .. rows - 1, columns < n) of a packed matrix as a dense row-major rows x n array; what the
 // envelope does not store is 0
 void lm_unpack_lower(const lm_system &S, const std::vector<double> &tiles, double *out, int rows)
@@ -1679,8 +1674,17 @@ void lm_unpack_lower(const lm_system &S, const std::vector<double> &tiles, doubl
             put(I, t++);
     }
 }
-} // namespace
 
+// the reduced unknowns' share of the model cost change from sys.y as it stands (a test seam that replaces y recomputes it)
+void lm_launch_model_change(lm_system &S)
+{
+    hipLaunchKernelGGL(lm_model_change_kernel, dim3(1), dim3(LM_TG), 0, S.ctx->stream, (const double *)S.lm_diag, (const double *)S.gs,
+                       (const double *)S.y, S.n, S.scal);
+}
+
+} // namespace ochip
+
+// ---- test seam: one LM step's linear algebra on a given system (include/ochip.h: ochip_debug_lm_step) ----------------
 extern "C" int ochip_debug_lm_step(ochip_ctx *ctx, int n, const double *A, const double *g, const double *scale, const double *diagonal,
                                    double radius, const int32_t *env_end, int32_t tail_begin, const int32_t *region_begin,
                                    int32_t n_region_begin, int32_t route, int32_t back, double *x_out, double *y_out, double *L_out,

@@ -145,6 +145,11 @@ struct lm_system
 
 // J'J as a dense symmetric n x n matrix in host memory (tests, ochip_relaxg_evaluate)
 int lm_download_dense(const lm_system &s, double *out);
+// the lower triangle (rows 0 .. rows - 1, columns < n) of a packed matrix downloaded to `tiles` as a dense row-major
+// rows x n array (test seams; rows = n + 1 takes the augmented row along)
+void lm_unpack_lower(const lm_system &s, const std::vector<double> &tiles, double *out, int rows);
+// enqueue lm_model_change_kernel on sys.y: scal[1] = the reduced unknowns' share of the model cost change
+void lm_launch_model_change(lm_system &sys);
 
 // (re)size the buffers for n unknowns and take the envelope; returns OCHIP_OK or a negative code
 int lm_system_resize(lm_system *s, int n, const lm_envelope &env);

@@ -733,6 +733,9 @@ struct ochip_relaxp_problem
     std::vector<int32_t> cam_t;
     uint32_t *cam_grp_off = nullptr, *cam_grp = nullptr;
     uint8_t *cam_optimize_dev = nullptr;
+    // test seams (ochip_relaxp_evaluate / ochip_relaxp_step): the device holds the Jacobian of an evaluation at the current
+    // state; a step of the seam has fixed the points' Jacobi scaling
+    bool seam_jacobian = false, seam_scale_fixed = false;
 };
 
 namespace
@@ -1067,6 +1070,7 @@ int ochip_relaxp_set_structure_only(ochip_relaxp_problem *p, int on)
         return OCHIP_EINVAL;
     OCHIP_HIP(p->ctx, hipSetDevice(p->ctx->device));
     p->structure_only = on != 0;
+    p->seam_jacobian = p->seam_scale_fixed = false;
     return assign(p);
 }
 
@@ -1085,6 +1089,7 @@ int ochip_relaxp_solve(ochip_relaxp_problem *p, const ochip_relax_options *opt, 
         return OCHIP_OK;
     }
     points_model M(p);
+    p->seam_jacobian = p->seam_scale_fixed = false;
     return lm_solve(p->sys, M, opt, sum);
 }
 
@@ -1100,6 +1105,153 @@ int ochip_relaxp_get_state(ochip_relaxp_problem *p, double *cam_q, double *point
         OCHIP_HIP(ctx, hipMemcpy(point_xyz, p->dev.X, (size_t)p->n_points * 24, hipMemcpyDeviceToHost));
     if (model)
         OCHIP_HIP(ctx, hipMemcpy(model, p->dev.model, 64, hipMemcpyDeviceToHost));
+    return OCHIP_OK;
+}
+
+// ---- test seams (include/ochip.h): the engine's own kernels through points_model and lm_linear_step, nothing else ---------
+int ochip_relaxp_evaluate(ochip_relaxp_problem *p, double *cost, int *n_out, double *U, double *g_c, double *V, double *g_p,
+                          double *gmax_p, int32_t *order_out)
+{
+    if (!p)
+        return OCHIP_EINVAL;
+    ochip_ctx *ctx = p->ctx;
+    OCHIP_HIP(ctx, hipSetDevice(ctx->device));
+    const int n = p->n;
+    if (n_out)
+        *n_out = n;
+    if (order_out)
+    {
+        for (uint32_t c = 0; c < p->n_cams; c++)
+            order_out[c] = p->cam_t[c];
+        for (int k = 0; k < KI; k++)
+            order_out[p->n_cams + k] = p->dev.lens_t[k];
+    }
+    if (!cost && !U && !g_c && !V && !g_p && !gmax_p)
+        return OCHIP_OK;
+    points_model model(p);
+    double c = 0;
+    const int rc = model.evaluate(true, 0, &c);
+    if (rc < 0)
+        return rc;
+    p->seam_jacobian = true;
+    if (cost)
+        *cost = c;
+    if (U && n)
+    {
+        const int drc = lm_download_dense(p->sys, U);
+        if (drc)
+            return drc;
+    }
+    if (g_c && n)
+        OCHIP_HIP(ctx, hipMemcpy(g_c, p->sys.g, (size_t)n * 8, hipMemcpyDeviceToHost));
+    if (V && p->n_points)
+        OCHIP_HIP(ctx, hipMemcpy(V, p->dev.pt_V, (size_t)p->n_points * 48, hipMemcpyDeviceToHost));
+    if (g_p && p->n_points)
+        OCHIP_HIP(ctx, hipMemcpy(g_p, p->dev.pt_g, (size_t)p->n_points * 24, hipMemcpyDeviceToHost));
+    if (gmax_p)
+    {
+        const int grc = model.gradient_max_extra(gmax_p);
+        if (grc)
+            return grc;
+    }
+    return rc;
+}
+
+int ochip_relaxp_step(ochip_relaxp_problem *p, double radius, const double *scale_in, const double *y_in, double alpha2,
+                      double *W_out, double *y_out, double *cam_q2, double *model2, double *X2, double *pt_scale, double *pt_Vinv,
+                      double *pt_d, double *scal_out, int32_t *fail_out)
+{
+    if (!p || !(radius > 0.0))
+        return OCHIP_EINVAL;
+    ochip_ctx *ctx = p->ctx;
+    OCHIP_HIP(ctx, hipSetDevice(ctx->device));
+    if (!p->seam_jacobian)
+        return ochip_fail(ctx, OCHIP_EINVAL, "ochip_relaxp_step: no Jacobian of the current state (ochip_relaxp_evaluate first)");
+    hipStream_t st = ctx->stream;
+    lm_system &S = p->sys;
+    const int n = p->n;
+    const size_t np = p->n_points;
+    points_model M(p);
+    M.scale_fixed = p->seam_scale_fixed;
+    if (n > 0)
+    {
+        std::vector<double> scale(n);
+        if (scale_in)
+            scale.assign(scale_in, scale_in + n);
+        else
+        {
+            // lm_solve's Jacobi scaling: 1 / (1 + sqrt(diag U))
+            lm_launch_diag(S, nullptr);
+            OCHIP_HIP(ctx, hipGetLastError());
+            OCHIP_HIP(ctx, ochip_stream_wait(ctx, st));
+            OCHIP_HIP(ctx, hipMemcpy(scale.data(), S.diag_tmp, (size_t)n * 8, hipMemcpyDeviceToHost));
+            for (double &v : scale)
+                v = 1.0 / (1.0 + std::sqrt(v));
+        }
+        OCHIP_HIP(ctx, hipMemcpy(S.scale, scale.data(), (size_t)n * 8, hipMemcpyHostToDevice));
+        lm_launch_diag(S, S.scale); // the clamped diagonal the damping is formed from
+    }
+    dev_scratch mem{ctx, "ochip_relaxp_step"};
+    double *w_built = nullptr;
+    if (W_out && n > 0 && mem.alloc<double>(&w_built, (size_t)S.chol_n_tiles * LM_NB * LM_NB) != OCHIP_OK)
+        return OCHIP_ENOMEM;
+    lm_step_args sa;
+    sa.back = lm_back_default(S, false);
+    sa.model = &M;
+    sa.w_built = w_built;
+    bool launched = false;
+    int rc = lm_linear_step(S, radius, sa, &launched);
+    if (rc)
+        return rc;
+    p->seam_scale_fixed = true;
+    OCHIP_HIP(ctx, hipGetLastError());
+    OCHIP_HIP(ctx, ochip_stream_wait(ctx, st));
+    if (y_out && n > 0)
+        OCHIP_HIP(ctx, hipMemcpy(y_out, S.y, (size_t)n * 8, hipMemcpyDeviceToHost));
+    if (y_in && n > 0)
+    {
+        OCHIP_HIP(ctx, hipMemcpy(S.y, y_in, (size_t)n * 8, hipMemcpyHostToDevice));
+        lm_launch_model_change(S);
+    }
+    M.launch_candidate(S.y, S.scale, 1.0, S.scal);
+    if (alpha2 != 0.0)
+    {
+        // what the projected line search does with a contracted step: the stored full step rescaled, the slope recomputed
+        M.launch_candidate(S.y, S.scale, alpha2, S.scal);
+        double slope = 0;
+        rc = M.slope_extra(false, &slope);
+        if (rc)
+            return rc;
+    }
+    OCHIP_HIP(ctx, hipGetLastError());
+    OCHIP_HIP(ctx, ochip_stream_wait(ctx, st));
+    double scal[8];
+    int fail = 0;
+    OCHIP_HIP(ctx, hipMemcpy(scal, S.scal, sizeof scal, hipMemcpyDeviceToHost));
+    OCHIP_HIP(ctx, hipMemcpy(&fail, S.fail_chol, 4, hipMemcpyDeviceToHost));
+    if (W_out && n > 0)
+    {
+        std::vector<double> tiles((size_t)S.chol_n_tiles * LM_NB * LM_NB);
+        OCHIP_HIP(ctx, hipMemcpy(tiles.data(), w_built, S.matrix_bytes(), hipMemcpyDeviceToHost));
+        lm_unpack_lower(S, tiles, W_out, n + 1);
+    }
+    if (cam_q2 && p->n_cams)
+        OCHIP_HIP(ctx, hipMemcpy(cam_q2, p->dev.cam_q2, (size_t)p->n_cams * 32, hipMemcpyDeviceToHost));
+    if (model2)
+        OCHIP_HIP(ctx, hipMemcpy(model2, p->dev.model2, 64, hipMemcpyDeviceToHost));
+    if (X2 && np)
+        OCHIP_HIP(ctx, hipMemcpy(X2, p->dev.X2, np * 24, hipMemcpyDeviceToHost));
+    if (pt_scale && np)
+        OCHIP_HIP(ctx, hipMemcpy(pt_scale, p->dev.pt_scale, np * 24, hipMemcpyDeviceToHost));
+    if (pt_Vinv && np)
+        OCHIP_HIP(ctx, hipMemcpy(pt_Vinv, p->dev.pt_Vinv, np * 48, hipMemcpyDeviceToHost));
+    if (pt_d && np)
+        OCHIP_HIP(ctx, hipMemcpy(pt_d, p->dev.pt_d, np * 24, hipMemcpyDeviceToHost));
+    if (scal_out)
+        scal_out[0] = scal[1], scal_out[1] = scal[2], scal_out[2] = scal[3], scal_out[3] = scal[6];
+    if (fail_out)
+        *fail_out = fail;
+    mem.release(); // (nothing was enqueued after the wait above)
     return OCHIP_OK;
 }
 

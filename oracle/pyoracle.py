@@ -833,3 +833,96 @@ def relaxg_fd(scene, step=1e-4, structure_only=False):
     fail = L.oc_relaxg_fd(C.byref(d), int(structure_only), float(step), out.ctypes.data)
     assert not fail
     return out
+
+
+# ---- one evaluation and one LM step of the points engine's problem on the full system (oracle/relaxp_eval.cpp) -----------
+PMUT_NONE, PMUT_PARTIAL, PMUT_NO_CORR_J, PMUT_DROP_SCHUR, PMUT_NO_POINT_DAMPING = 0, 1, 2, 3, 4
+
+
+def _relaxp_fns():
+    L = lib()
+    if not getattr(L, "_relaxp_ready", False):
+        vp, ci = C.c_void_p, C.c_int
+        L.oc_relaxp_eval.restype = ci
+        L.oc_relaxp_eval.argtypes = [vp, ci, ci, ci, ci, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+        L.oc_relaxp_step.restype = ci
+        L.oc_relaxp_step.argtypes = [vp, ci, ci, ci, ci, C.c_double] + [vp] * 13
+        L.oc_relaxp_fd.restype = ci
+        L.oc_relaxp_fd.argtypes = [vp, ci, C.c_double, vp]
+        L._relaxp_ready = True
+    return L
+
+
+def relaxp_eval(scene, precision=1, raw=False, mutate=PMUT_NONE, mutate_arg=-1, delta=None, structure_only=False, jacobian=True):
+    """The points engine's problem (a scene dict of ochip_relaxp_desc fields, opencalibration_amd.capi.relaxp_desc) evaluated
+    the way the reference's Problem evaluates it, nothing eliminated, in long double (precision=1) or double (0).  dict: fail
+    (a block did not evaluate to finite values), n (the reduced unknowns: cameras and lens), N = n + 3 n_points, cost, JtJ
+    (N x N), Jtr, J (rows x N, corrected), r (corrected), row_blk (block of each row: observation 2p + side, then the
+    monotonicity block), touch (rows x N: 1 where a row structurally depends on a column), order (n_cams + 8: the first
+    canonical column of every camera and of f ppx ppy k1 k2 k3 p1 p2, or -1).  raw: no loss and no corrector.  delta (N): the
+    state moved by x [+] delta first.  jacobian=False leaves J and touch out (None)."""
+    from opencalibration_amd import capi
+
+    L = _relaxp_fns()
+    d, keep = capi.relaxp_desc(scene)
+    n, N, rows = C.c_int(), C.c_int(), C.c_int()
+    dl = None if delta is None else np.ascontiguousarray(delta, np.float64)
+    args = (C.byref(d), int(structure_only), int(precision), int(raw), int(mutate), int(mutate_arg),
+            None if dl is None else dl.ctypes.data)
+    order = np.zeros(d.n_cams + 8, np.int32)
+    L.oc_relaxp_eval(*args, C.byref(n), C.byref(N), C.byref(rows), order.ctypes.data, *([None] * 7))
+    n, N, m = n.value, N.value, rows.value
+    assert dl is None or dl.shape == (N,)
+    cost = C.c_double()
+    JtJ, Jtr, r, row_blk = np.zeros((N, N)), np.zeros(N), np.zeros(m), np.zeros(m, np.int32)
+    J, touch = (np.zeros((m, N)), np.zeros((m, N), np.uint8)) if jacobian else (None, None)
+    fail = L.oc_relaxp_eval(*args, None, None, None, None, C.byref(cost), JtJ.ctypes.data, Jtr.ctypes.data,
+                            J.ctypes.data if jacobian else None, r.ctypes.data, row_blk.ctypes.data,
+                            touch.ctypes.data if jacobian else None)
+    return dict(fail=bool(fail), n=n, N=N, cost=cost.value, JtJ=JtJ, Jtr=Jtr, J=J, r=r, row_blk=row_blk, touch=touch, order=order)
+
+
+def relaxp_fd(scene, step=1e-6, structure_only=False):
+    """Richardson-extrapolated central differences (long double) of the raw residuals of relaxp_eval over its canonical
+    columns: rows x N"""
+    from opencalibration_amd import capi
+
+    L = _relaxp_fns()
+    e = relaxp_eval(scene, raw=True, structure_only=structure_only, jacobian=False)
+    d, keep = capi.relaxp_desc(scene)
+    out = np.zeros((len(e["r"]), e["N"]))
+    fail = L.oc_relaxp_fd(C.byref(d), int(structure_only), float(step), out.ctypes.data)
+    assert not fail
+    return out
+
+
+def relaxp_step(scene, radius, precision=1, scale_c=None, y_test=None, mutate=PMUT_NONE, mutate_arg=-1, structure_only=False):
+    """One Levenberg-Marquardt step of the points engine's problem from the FULL normal equations (no elimination): Jacobi
+    scaling 1 / (1 + sqrt(diag)) over every column (scale_c, n values, replaces the reduced unknowns' share), D^2 =
+    clamp(diag S^2, 1e-6, 1e32) / radius, M = S J'J S + D^2, b = S J'r, a dense Cholesky solve, delta = -S y.  dict: fail, n,
+    N, scale, D2, y, delta (N each), Sc (n x n: the Schur complement M_cc - M_cp M_pp^-1 M_pc) and rhs_c (n), Mpp (n_points x
+    3 x 3: the damped point blocks), the candidate cam_q2, model2, X2, model_cost_change, step_sq, cand_sq, slope (g . delta),
+    slope_p (the points' share) and backward_error of y_test (N, scaled unknowns; 0 without)."""
+    from opencalibration_amd import capi
+
+    L = _relaxp_fns()
+    d, keep = capi.relaxp_desc(scene)
+    n, N = C.c_int(), C.c_int()
+    L.oc_relaxp_eval(C.byref(d), int(structure_only), 1, 0, 0, -1, None, C.byref(n), C.byref(N), *([None] * 9))
+    n, N, P = n.value, N.value, d.n_points
+    sc = None if scale_c is None else np.ascontiguousarray(scale_c, np.float64)
+    yt = None if y_test is None else np.ascontiguousarray(y_test, np.float64)
+    assert (sc is None or sc.shape == (n,)) and (yt is None or yt.shape == (N,))
+    scale, D2, y, delta = np.zeros(N), np.zeros(N), np.zeros(N), np.zeros(N)
+    Sc, rhs, Mpp = np.zeros((n, n)), np.zeros(n), np.zeros((P, 3, 3))
+    q2, m2, X2, scal = np.zeros((d.n_cams, 4)), np.zeros(8), np.zeros((P, 3)), np.zeros(8)
+
+    def ptr(a):
+        return a.ctypes.data if a.size else None
+
+    fail = L.oc_relaxp_step(C.byref(d), int(structure_only), int(precision), int(mutate), int(mutate_arg), float(radius),
+                            None if sc is None else ptr(sc), None if yt is None else ptr(yt), ptr(scale), ptr(D2), ptr(y),
+                            ptr(delta), ptr(Sc), ptr(rhs), ptr(Mpp), ptr(q2), m2.ctypes.data, ptr(X2), scal.ctypes.data)
+    return dict(fail=bool(fail), n=n, N=N, scale=scale, D2=D2, y=y, delta=delta, Sc=Sc, rhs_c=rhs, Mpp=Mpp, cam_q2=q2, model2=m2,
+                X2=X2, model_cost_change=scal[0], step_sq=scal[1], cand_sq=scal[2], slope=scal[3], slope_p=scal[4],
+                backward_error=scal[5])

@@ -3,9 +3,9 @@ tail assembly with its chunk merges, the cost reduction) against the long-double
 fixtures of tests/relax_eval_fixtures.py: cost, J'J and J'r within the normwise bounds of that file, the same unknowns, and
 a failing block reported as a failure.  The worst error-to-bound ratios are printed (RELAX_EVAL_RATIOS).
 
-The plane engine (relax.hip) is covered the same way by tests/test_gpu_relax_plane_eval.py.  Not covered: the resident
-chain's copy of the plane evaluation (relax_chain.hip) and the points engine (relax_points.hip), which have no evaluation
-seam of their own yet."""
+The plane engine (relax.hip) is covered the same way by tests/test_gpu_relax_plane_eval.py, and the points engine
+(relax_points.hip: its evaluation and its Schur step) by tests/test_gpu_relaxp_eval.py.  Not covered: the resident chain's
+copy of the plane evaluation (relax_chain.hip), which has no evaluation seam of its own yet."""
 import json
 
 import numpy as np
