@@ -3109,6 +3109,22 @@ int ochip_synth_render_views(ochip_ctx *ctx, uint8_t *images_dev, uint32_t first
 
 } // extern "C"
 
+// What a chunk's launches read that depends on the image shape alone: the processing order of the detection tiles, the
+// descriptor kernel's tables and the INTER_AREA tables of the downscale.  A survey's images share their shape, so the
+// context keeps these from chunk to chunk in blocks of its own (outside the call's arena) and akaze_run rebuilds them only
+// when the shape changes.  The key is everything they are computed from.
+struct ochip::akaze_tables
+{
+    ochip::dev_blocks mem;
+    int width = 0, height = 0, W = 0, H = 0, n_levels = 0, n_tiles = 0; // key (0: nothing built)
+    unsigned int *tile_seq = nullptr;
+    void *gtab = nullptr; // gather_tab
+    int *xo = nullptr, *xs = nullptr, *yo = nullptr, *ys = nullptr;
+    float *xa = nullptr, *ya = nullptr;
+    bool staged = false; // can every resize workgroup stage its source window in LDS? (taps per column, window size)
+    int most_taps = 0;
+};
+
 namespace
 {
 
@@ -3232,6 +3248,97 @@ const gather_tab &host_gather_tab()
     return G;
 }
 
+// The context's tables for this shape (built and uploaded with one wait when the context has none or had another shape's;
+// nothing of the context's stream still reads the old ones then: every akaze_run ends with a wait).
+int akaze_tables_for(ochip_ctx *ctx, int width, int height, int W, int H, double scale, const levels_dev &LV, int n_tiles,
+                     const ochip::akaze_tables **out)
+{
+    if (!ctx->akaze_tabs)
+    {
+        ctx->akaze_tabs = new ochip::akaze_tables();
+        ctx->akaze_tabs->mem.ctx = ctx;
+        ctx->akaze_tabs->mem.what = "akaze tables";
+        ctx->akaze_tabs_destroy = [](ochip::akaze_tables *t) {
+            t->mem.release();
+            delete t;
+        };
+    }
+    ochip::akaze_tables &T = *ctx->akaze_tabs;
+    *out = &T;
+    if (T.width == width && T.height == height && T.W == W && T.H == H && T.n_levels == LV.n && T.n_tiles == n_tiles)
+        return OCHIP_OK;
+    T.width = 0; // (a failure below leaves no key)
+    T.mem.release();
+    constexpr auto ENQ = ochip::copy_mode::enqueue; // (one wait for all of them below; their sources live until then)
+    int rc = OCHIP_OK;
+    // processing order of the detection tiles: level by level, Morton order inside a level
+    std::vector<std::pair<uint64_t, unsigned int>> keyed;
+    keyed.reserve(n_tiles);
+    auto spread = [](uint32_t v) {
+        uint64_t x = v;
+        x = (x | (x << 16)) & 0x0000FFFF0000FFFFull;
+        x = (x | (x << 8)) & 0x00FF00FF00FF00FFull;
+        x = (x | (x << 4)) & 0x0F0F0F0F0F0F0F0Full;
+        x = (x | (x << 2)) & 0x3333333333333333ull;
+        x = (x | (x << 1)) & 0x5555555555555555ull;
+        return x;
+    };
+    for (int i = 0; i < LV.n; i++)
+    {
+        const level_info &l = LV.l[i];
+        const int ty_n = (l.h + DT_Y - 1) / DT_Y;
+        for (int ty = 0; ty < ty_n; ty++)
+            for (int tx = 0; tx < l.tiles_x; tx++)
+                keyed.emplace_back(((uint64_t)i << 48) | spread((uint32_t)tx) | (spread((uint32_t)ty) << 1),
+                                   (unsigned int)(l.tile_off + ty * l.tiles_x + tx));
+    }
+    std::sort(keyed.begin(), keyed.end());
+    std::vector<unsigned int> seq(keyed.size());
+    for (size_t i = 0; i < keyed.size(); i++)
+        seq[i] = keyed[i].second;
+    rc = rc != OCHIP_OK ? rc : T.mem.upload(&T.tile_seq, seq, ENQ);
+    // the descriptor kernel's tables (built once per process): gather orders, cell chains, bit list
+    gather_tab *g = nullptr;
+    rc = rc != OCHIP_OK ? rc : T.mem.upload(&g, &host_gather_tab(), 1, ENQ);
+    T.gtab = g;
+    area_tab tx, ty; // (alive until the wait below)
+    T.staged = false;
+    T.most_taps = 0;
+    if (!(W == width && H == height))
+    {
+        tx = area_table(width, W, 1.0 / scale);
+        ty = area_table(height, H, 1.0 / scale);
+        bool staged = width % 4 == 0;
+        for (int x0 = 0; x0 < W && staged; x0 += 256)
+        {
+            const int x1 = std::min(x0 + 256, W);
+            const int c0 = tx.si[tx.off[x0]] & ~3, c1 = tx.si[tx.off[x1] - 1];
+            staged = c1 - c0 + 1 <= RS_PITCH - 3;
+            for (int x = x0; x < x1 && staged; x++)
+                staged = tx.off[x + 1] - tx.off[x] <= RESIZE_MAX_TAPS;
+        }
+        for (int y0 = 0; y0 < H && staged; y0 += RESIZE_ROWS)
+        {
+            const int y1 = std::min(y0 + RESIZE_ROWS, H);
+            staged = ty.si[ty.off[y1] - 1] - ty.si[ty.off[y0]] + 1 <= RS_ROWS;
+        }
+        T.staged = staged;
+        for (int x = 0; x < W; x++)
+            T.most_taps = std::max(T.most_taps, tx.off[x + 1] - tx.off[x]);
+        rc = rc != OCHIP_OK ? rc : T.mem.upload(&T.xo, tx.off, ENQ);
+        rc = rc != OCHIP_OK ? rc : T.mem.upload(&T.xs, tx.si, ENQ);
+        rc = rc != OCHIP_OK ? rc : T.mem.upload(&T.xa, tx.alpha, ENQ);
+        rc = rc != OCHIP_OK ? rc : T.mem.upload(&T.yo, ty.off, ENQ);
+        rc = rc != OCHIP_OK ? rc : T.mem.upload(&T.ys, ty.si, ENQ);
+        rc = rc != OCHIP_OK ? rc : T.mem.upload(&T.ya, ty.alpha, ENQ);
+    }
+    OCHIP_HIP(ctx, ochip_stream_wait(ctx, ctx->stream));
+    if (rc != OCHIP_OK)
+        return rc;
+    T.width = width, T.height = height, T.W = W, T.H = H, T.n_levels = LV.n, T.n_tiles = n_tiles;
+    return OCHIP_OK;
+}
+
 // images: n_images x h x w x 3 BGR bytes (host, or device when on_device).  Working size: the INTER_AREA
 // downscale to max side 1600 of extract_features.cpp:26-27.  Outputs (host): per image up to max_kp keypoints,
 // in unspecified order: kp6 = {x, y, size, angle(rad), response, level} in working-image pixels, desc = 8 x u64,
@@ -3326,7 +3433,7 @@ int akaze_run(ochip_ctx *ctx, const uint8_t *images_bgr, bool on_device, uint32_
     unsigned char *d_dead = nullptr, *d_valid = nullptr;
     unsigned long long *d_desc = nullptr, *d_descc = nullptr;
     float *d_kpc = nullptr;
-    unsigned int *d_counts = nullptr, *d_tile_counts = nullptr, *d_tile_base = nullptr, *d_tile_seq = nullptr;
+    unsigned int *d_counts = nullptr, *d_tile_counts = nullptr, *d_tile_base = nullptr;
     // maxima / valid keypoints; the suppression's masks (8 x 8 pixels per word): keypoints, points waiting for a turn, points
     // with a turn (pass 1: the maxima in this layout)
     unsigned long long *d_mask = nullptr, *d_vmask = nullptr, *d_kmask = nullptr, *d_pmask = nullptr, *d_rmask = nullptr;
@@ -3334,7 +3441,6 @@ int akaze_run(ochip_ctx *ctx, const uint8_t *images_bgr, bool on_device, uint32_
     unsigned int *d_level_first = nullptr;                 // first candidate of every level of every image (+ the list's length)
     unsigned int *d_turns = nullptr, *d_waiting = nullptr; // its two lists of points waiting for their turn, their lengths per (image, level)
     unsigned int *d_wbase = nullptr, *d_live = nullptr, *d_nlive = nullptr;
-    gather_tab *d_gtab = nullptr;
     const size_t src_px = (size_t)width * height;
     // 1-D tile grids padded to a multiple of 8 workgroups (xcd_tile)
     auto tiles = [&](int w, int h) { return dim3(8 * ((((w + BT_X - 1) / BT_X) * ((h + BT_Y - 1) / BT_Y) + 7) / 8), 1, B); };
@@ -3380,40 +3486,13 @@ int akaze_run(ochip_ctx *ctx, const uint8_t *images_bgr, bool on_device, uint32_
     AK(mem.alloc<unsigned int>(&d_wbase, (size_t)B * mask_stride));
     AK(mem.alloc<unsigned int>(&d_live, (size_t)B * max_cands));
     AK(mem.alloc<unsigned int>(&d_nlive, B));
-    {
-        // processing order of the detection tiles: level by level, Morton order inside a level
-        std::vector<std::pair<uint64_t, unsigned int>> keyed;
-        keyed.reserve(n_tiles);
-        auto spread = [](uint32_t v) {
-            uint64_t x = v;
-            x = (x | (x << 16)) & 0x0000FFFF0000FFFFull;
-            x = (x | (x << 8)) & 0x00FF00FF00FF00FFull;
-            x = (x | (x << 4)) & 0x0F0F0F0F0F0F0F0Full;
-            x = (x | (x << 2)) & 0x3333333333333333ull;
-            x = (x | (x << 1)) & 0x5555555555555555ull;
-            return x;
-        };
-        for (int i = 0; i < LV.n; i++)
-        {
-            const level_info &l = LV.l[i];
-            const int ty_n = (l.h + DT_Y - 1) / DT_Y;
-            for (int ty = 0; ty < ty_n; ty++)
-                for (int tx = 0; tx < l.tiles_x; tx++)
-                    keyed.emplace_back(((uint64_t)i << 48) | spread((uint32_t)tx) | (spread((uint32_t)ty) << 1),
-                                       (unsigned int)(l.tile_off + ty * l.tiles_x + tx));
-        }
-        std::sort(keyed.begin(), keyed.end());
-        std::vector<unsigned int> seq(keyed.size());
-        for (size_t i = 0; i < keyed.size(); i++)
-            seq[i] = keyed[i].second;
-        AK(mem.upload(&d_tile_seq, seq.data(), seq.size(), WAIT));
-    }
-    {
-        // the descriptor kernel's tables (built once per process): gather orders, cell chains, bit list
-        AK(mem.upload(&d_gtab, &host_gather_tab(), 1, WAIT));
-    }
+    // the tables of this shape: the context's own, the same from chunk to chunk
+    const ochip::akaze_tables *tabs = nullptr;
+    AK(akaze_tables_for(ctx, width, height, W, H, scale, LV, n_tiles, &tabs));
     if (rc != OCHIP_OK)
     return rc;
+    const unsigned int *d_tile_seq = tabs->tile_seq;
+    const gather_tab *d_gtab = (const gather_tab *)tabs->gtab;
     auto grid2 = [&](int w, int h) { return dim3((w + 255) / 256, h, B); };
     auto taps_of = [](const std::vector<float> &k) {
         taps_t t{};
@@ -3431,27 +3510,7 @@ int akaze_run(ochip_ctx *ctx, const uint8_t *images_bgr, bool on_device, uint32_
     // ---- grey, downscale, float
     const size_t n_px = (size_t)B * src_px;
     const bool resized = !(W == width && H == height);
-    area_tab tx, ty;
-    bool staged = false; // can every resize workgroup stage its source window in LDS? (taps per column, window size)
-    if (resized)
-    {
-        tx = area_table(width, W, 1.0 / scale);
-        ty = area_table(height, H, 1.0 / scale);
-        staged = width % 4 == 0;
-        for (int x0 = 0; x0 < W && staged; x0 += 256)
-        {
-            const int x1 = std::min(x0 + 256, W);
-            const int c0 = tx.si[tx.off[x0]] & ~3, c1 = tx.si[tx.off[x1] - 1];
-            staged = c1 - c0 + 1 <= RS_PITCH - 3;
-            for (int x = x0; x < x1 && staged; x++)
-                staged = tx.off[x + 1] - tx.off[x] <= RESIZE_MAX_TAPS;
-        }
-        for (int y0 = 0; y0 < H && staged; y0 += RESIZE_ROWS)
-        {
-            const int y1 = std::min(y0 + RESIZE_ROWS, H);
-            staged = ty.si[ty.off[y1] - 1] - ty.si[ty.off[y0]] + 1 <= RS_ROWS;
-        }
-    }
+    const bool staged = resized && tabs->staged;
     const bool fused_grey = staged && ((uintptr_t)d_bgr & 3) == 0; // the resize converts BGR itself
     if (!fused_grey)
     {
@@ -3471,20 +3530,10 @@ int akaze_run(ochip_ctx *ctx, const uint8_t *images_bgr, bool on_device, uint32_
                            B * plane0);
     else
     {
-        int *xo, *xs, *yo, *ys;
-        float *xa, *ya;
-        AK(mem.upload(&xo, tx.off.data(), tx.off.size(), WAIT));
-        AK(mem.upload(&xs, tx.si.data(), tx.si.size(), WAIT));
-        AK(mem.upload(&xa, tx.alpha.data(), tx.alpha.size(), WAIT));
-        AK(mem.upload(&yo, ty.off.data(), ty.off.size(), WAIT));
-        AK(mem.upload(&ys, ty.si.data(), ty.si.size(), WAIT));
-        AK(mem.upload(&ya, ty.alpha.data(), ty.alpha.size(), WAIT));
-        if (rc != OCHIP_OK)
-        return rc;
+        const int *xo = tabs->xo, *xs = tabs->xs, *yo = tabs->yo, *ys = tabs->ys;
+        const float *xa = tabs->xa, *ya = tabs->ya;
         const dim3 rgrid((W + 255) / 256, (H + RESIZE_ROWS - 1) / RESIZE_ROWS, B);
-        int most_taps = 0;
-        for (int x = 0; x < W; x++)
-            most_taps = std::max(most_taps, tx.off[x + 1] - tx.off[x]);
+        const int most_taps = tabs->most_taps;
         // a scale of exactly 2 (a 3200-pixel side): cv::resize's integer path - the vector body of ResizeAreaFast rounds
         // (sum + 2) >> 2, sixteen columns at a time (the 16-bit lanes of an AVX2 build; the scalar tail rounds to even like
         // the general path).  Scales of 4 and 8 give the same bytes either way (every operation is exact).

@@ -136,10 +136,32 @@ dev_scratch::~dev_scratch()
 {
     if (held.empty())
         return;
-    (void)ochip_stream_wait(ctx, ctx->stream);
+    if (ctx->stream.opened())
+        (void)ochip_stream_wait(ctx, ctx->stream);
     release();
 }
 } // namespace ochip
+
+void ochip_lazy_stream::open()
+{
+    int current = -1;
+    error = hipGetDevice(&current);
+    if (error == hipSuccess && current != device)
+        error = hipSetDevice(device);
+    if (error == hipSuccess && priority < 0)
+        error = hipStreamCreateWithFlags(&s, hipStreamNonBlocking);
+    else if (error == hipSuccess)
+    {
+        int least = 0, greatest = 0;
+        error = hipDeviceGetStreamPriorityRange(&least, &greatest);
+        if (error == hipSuccess)
+            error = hipStreamCreateWithPriority(&s, hipStreamNonBlocking, priority ? greatest : least);
+    }
+    if (current >= 0 && current != device)
+        (void)hipSetDevice(current);
+    if (error != hipSuccess)
+        s = nullptr;
+}
 
 void ochip_prof_begin(ochip_ctx *ctx, int kid, hipEvent_t *start, hipEvent_t *stop)
 {
@@ -200,7 +222,7 @@ int ochip_ctx_create(int device, ochip_ctx **out)
     ochip_ctx *ctx = new (std::nothrow) ochip_ctx();
     if (!ctx)
         return ochip_fail(nullptr, OCHIP_ENOMEM, "host allocation failed");
-    ctx->device = device;
+    ctx->device = ctx->stream.device = device;
     hipError_t e = hipSetDevice(device);
     const char *bsync = getenv("OCHIP_BLOCKING_SYNC");
     ctx->blocking_wait = !(bsync && bsync[0] == '0');
@@ -220,11 +242,10 @@ int ochip_ctx_create(int device, ochip_ctx **out)
         delete ctx;
         return rc;
     }
-    if (e == hipSuccess)
-        e = hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking);
-    // (no copy_stream here: nothing of the hot path copies beside its own kernels, and a process has a handful of hardware
-    // queues that its streams share - a second stream per context, 30 of them with the siblings of a pipelined run, only
-    // made two extraction streams meet on one queue.  Whoever needs it creates it: ochip_copy_stream)
+    // (no stream here: a process has a handful of hardware queues per stream priority that its streams share, and the runtime
+    // places a stream when it is created - the streams of contexts that never launch anything, 30 of them with the siblings
+    // of a pipelined run, only made two extraction streams meet on one queue.  ctx->stream opens on first use; whoever
+    // needs a copy stream creates it: ochip_copy_stream)
     if (e != hipSuccess)
     {
         int rc = ochip_fail(nullptr, OCHIP_EHIP, "context creation failed: %s", hipGetErrorString(e));
@@ -273,6 +294,9 @@ void ochip_ctx_destroy(ochip_ctx *ctx)
     for (void *b : {ctx->desc_fp4_dev, ctx->desc_negpop_dev, ctx->desc_pop_dev})
         if (b)
             (void)hipFree(b);
+    if (ctx->akaze_tabs && ctx->akaze_tabs_destroy)
+        ctx->akaze_tabs_destroy(ctx->akaze_tabs);
+    ctx->akaze_tabs = nullptr;
     if (ctx->lab_table_mem)
     {
         ctx->lab_table_mem->release();
@@ -288,8 +312,8 @@ void ochip_ctx_destroy(ochip_ctx *ctx)
         (void)hipEventDestroy(ctx->sync_event);
     for (hipStream_t r : ctx->retired_streams)
         (void)hipStreamDestroy(r);
-    if (ctx->stream)
-        (void)hipStreamDestroy(ctx->stream);
+    if (ctx->stream.opened())
+        (void)hipStreamDestroy(ctx->stream.s);
     if (ctx->copy_stream)
         (void)hipStreamDestroy(ctx->copy_stream);
     delete ctx;
@@ -301,15 +325,20 @@ int ochip_ctx_set_priority(ochip_ctx *ctx, int high)
         return OCHIP_EINVAL;
     if (ctx->stream_priority == (high ? 1 : 0))
         return OCHIP_OK; // (asked again by the next survey's runner: the stream stays)
+    if (!ctx->stream.opened())
+    {
+        ctx->stream.priority = ctx->stream_priority = high ? 1 : 0; // (the first use opens it there)
+        return OCHIP_OK;
+    }
     OCHIP_HIP(ctx, hipSetDevice(ctx->device));
     int least = 0, greatest = 0;
     OCHIP_HIP(ctx, hipDeviceGetStreamPriorityRange(&least, &greatest));
     OCHIP_HIP(ctx, hipStreamSynchronize(ctx->stream));
     hipStream_t s = nullptr;
     OCHIP_HIP(ctx, hipStreamCreateWithPriority(&s, hipStreamNonBlocking, high ? greatest : least));
-    ctx->retired_streams.push_back(ctx->stream); // destroyed with the context, not here: tools that trace the process
-    ctx->stream = s;                             // (rocprofv3) keep per-stream state that other threads may still touch
-    ctx->stream_priority = high ? 1 : 0;
+    ctx->retired_streams.push_back(ctx->stream.s); // destroyed with the context, not here: tools that trace the process
+    ctx->stream.s = s;                             // (rocprofv3) keep per-stream state that other threads may still touch
+    ctx->stream.priority = ctx->stream_priority = high ? 1 : 0;
     return OCHIP_OK;
 }
 
@@ -376,7 +405,10 @@ int ochip_synchronize(ochip_ctx *ctx)
 {
     if (!ctx)
         return OCHIP_EINVAL;
-    OCHIP_HIP(ctx, ochip_stream_wait(ctx, ctx->stream));
+    if (ctx->stream.opened())
+        OCHIP_HIP(ctx, ochip_stream_wait(ctx, ctx->stream));
+    else if (ctx->stream.error != hipSuccess)
+        OCHIP_HIP(ctx, ctx->stream.error);
     if (ctx->copy_stream)
         OCHIP_HIP(ctx, ochip_stream_wait(ctx, ctx->copy_stream));
     return OCHIP_OK;
@@ -543,7 +575,8 @@ int ochip_profile_reset(ochip_ctx *ctx)
 {
     if (!ctx)
         return OCHIP_EINVAL;
-    OCHIP_HIP(ctx, ochip_stream_wait(ctx, ctx->stream));
+    if (ctx->stream.opened()) // (a sibling that never launched anything has nothing to wait for, and stays without a stream)
+        OCHIP_HIP(ctx, ochip_stream_wait(ctx, ctx->stream));
     for (int k = 0; k < OCHIP_K_COUNT; k++)
     {
         prof_drain(ctx, k);

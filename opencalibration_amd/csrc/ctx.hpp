@@ -26,10 +26,43 @@ namespace ochip
 struct dev_blocks;
 }
 
+// A context's compute stream, opened by the first use that needs a hipStream_t.  A process has a handful of hardware queues
+// per stream priority and the runtime hands a stream its queue when it is created: a context that only fills a gap of the
+// sibling list, or only owns pools, opens none and takes no share of a queue.  (A context belongs to one thread at a time,
+// so does this.)  If the stream cannot be created the error stays here and ochip_stream_wait - where every call on a
+// context ends - reports it.
+struct ochip_lazy_stream
+{
+    hipStream_t s = nullptr;
+    int device = 0;
+    int priority = -1; // -1: the default priority, 0: the lowest, 1: the highest (ochip_ctx_set_priority)
+    hipError_t error = hipSuccess;
+
+    ochip_lazy_stream() = default;
+    ochip_lazy_stream(const ochip_lazy_stream &) = delete;
+    ochip_lazy_stream &operator=(const ochip_lazy_stream &) = delete;
+    bool opened() const
+    {
+        return s != nullptr;
+    }
+    operator hipStream_t()
+    {
+        if (!s)
+            open();
+        return s;
+    }
+    void open(); // ctx.hip
+};
+
+namespace ochip
+{
+struct akaze_tables;
+}
+
 struct ochip_ctx
 {
     int device = 0;
-    hipStream_t stream = nullptr;     // compute stream: every kernel of the hot path is launched here
+    ochip_lazy_stream stream;         // compute stream: every kernel of the hot path is launched here
     hipStream_t copy_stream = nullptr; // created on first use (ochip_copy_stream), not with the context
     std::vector<hipStream_t> retired_streams; // replaced by ochip_ctx_set_priority
     int stream_priority = -1; // what ochip_ctx_set_priority last set (-1: the default stream)
@@ -121,6 +154,10 @@ struct ochip_ctx
     void *lab_tables_dev = nullptr; // ochip_ol::lab_tables
     float lab_table_fill_ms = 0;    // the fill kernel's time (ochip_debug_lab_table)
 
+    // akaze.hip: the tables a chunk's launches read that depend on the image shape alone, kept from chunk to chunk
+    ochip::akaze_tables *akaze_tabs = nullptr;
+    void (*akaze_tabs_destroy)(ochip::akaze_tables *) = nullptr;
+
     // what the host library keeps with the context (ochip_ctx_attachment: the extraction slots of host/extract_slots.hpp)
     void *attachment = nullptr;
     void (*attachment_destroy)(void *) = nullptr;
@@ -133,6 +170,8 @@ struct ochip_ctx
 // here would otherwise eat the CPU quota the OpenMP teams of the host phases need.
 inline hipError_t ochip_stream_wait(ochip_ctx *ctx, hipStream_t st)
 {
+    if (ctx->stream.error != hipSuccess)
+        return ctx->stream.error;
     if (!ctx->blocking_wait)
         return hipStreamSynchronize(st);
     if (!ctx->sync_event)

@@ -22,7 +22,9 @@
 // (pixels per launch from which a level takes the register-strip kernels), OCHIP_EXTRACT_GATE=0 (no ordering between the
 // extractions of surveys), OCHIP_EXTRACT_HANDOVER = slot | survey (host/extract_slots.hpp: the extraction contexts pass to the
 // next survey one by one - the default - or all together when the survey before has finished), OCHIP_EXTRACT_STAGGER=1 (a launch
-// sequence waits with its chunk while another one of its survey is in front of its first host read-back)
+// sequence waits with its chunk while another one of its survey is in front of its first host read-back), OCHIP_EXTRACT_PRIORITY=0
+// (host/extract_features.cpp: the launch sequences on the root context and its first siblings at the default stream priority
+// instead of sibling contexts of their own whose streams have the lowest)
 #pragma once
 
 #include <cstdlib>

@@ -358,6 +358,14 @@ extract_slots::order handover_order()
     return extract_slots::order::slot;
 }
 
+// OCHIP_EXTRACT_PRIORITY=0: the launch sequences on the root context and its first siblings at the default stream priority,
+// where they share the process's hardware queues with the link runners, the root context's other work and the null stream
+bool own_stream_class()
+{
+    const char *e = std::getenv("OCHIP_EXTRACT_PRIORITY");
+    return !(e && e[0] == '0');
+}
+
 bool stagger_starts()
 {
     const char *e = std::getenv("OCHIP_EXTRACT_STAGGER");
@@ -428,9 +436,17 @@ bool extract_features_stream(ochip_ctx *ctx, const uint8_t *images_bgr, uint32_t
         n_drivers = (uint32_t)std::max(1L, std::min(5L, std::atol(e))); // siblings 4.. belong to the link runners (load_link.cpp)
     const uint32_t n_chunks = (n_images + chunk - 1) / chunk;
     n_drivers = std::min(n_drivers, n_chunks);
+    // The runtime gives a stream its hardware queue from a pool per stream priority.  A slot's context is a sibling that nothing
+    // else uses (FIRST_SLOT_SIBLING + slot: past the link runners' 4..11 and 13..20 and the relax context 12), its stream of the
+    // lowest priority: the sequences get the queues of that pool to themselves, one each, and the link runners' and the relax
+    // solve's short launches, on the pools above, are dispatched ahead of the bulk work.  The slot's arena of level planes and
+    // the tables of its shape live with that context.  (OCHIP_EXTRACT_PRIORITY=0: slot 0 is the root context, slot d its
+    // sibling d - 1, at whatever priority they have.)
+    constexpr uint32_t FIRST_SLOT_SIBLING = 21;
+    const bool own_class = own_stream_class();
     std::vector<ochip_ctx *> ctxs(n_drivers, ctx);
-    for (uint32_t d = 1; d < n_drivers; d++)
-        if (ochip_ctx_sibling(ctx, d - 1, &ctxs[d]) != OCHIP_OK)
+    for (uint32_t d = own_class ? 0 : 1; d < n_drivers; d++)
+        if (ochip_ctx_sibling(ctx, own_class ? FIRST_SLOT_SIBLING + d : d - 1, &ctxs[d]) != OCHIP_OK)
         {
             if (error)
                 *error = std::string("ochip_ctx_sibling: ") + ochip_last_error(ctx);
@@ -536,6 +552,14 @@ bool extract_features_stream(ochip_ctx *ctx, const uint8_t *images_bgr, uint32_t
                     started = true;
                     t_first_slot = std::chrono::steady_clock::now();
                 }
+            }
+            // (by the slot's holder: the context is one thread's at a time; a stream that is already there stays)
+            if (own_class && ochip_ctx_set_priority(dctx, 0) != OCHIP_OK)
+            {
+                std::lock_guard<std::mutex> lk(mu);
+                if (fail.empty())
+                    fail = std::string("ochip_ctx_set_priority: ") + ochip_last_error(dctx);
+                ticket.retire();
             }
             for (;;)
             {

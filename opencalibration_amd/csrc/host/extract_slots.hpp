@@ -1,7 +1,8 @@
 // Hand-over of the extraction contexts from one survey to the next (header-only, plain C++: no device call in here, so
 // tests/test_extract_slots.py drives it from a small program of its own under the thread sanitizer).
 //
-// A root device context extracts with n "slots": slot 0 is the context itself, slot d its sibling d - 1.  A context is
+// A root device context extracts with n "slots": slot d is its sibling 21 + d, a context nothing else uses, with a stream of
+// the lowest priority (OCHIP_EXTRACT_PRIORITY=0: slot 0 is the context itself, slot d its sibling d - 1).  A context is
 // not thread-safe - its stream, device pool, page-locked pool and error string belong to ONE thread at a time - so a
 // slot has one holder.  Surveys (calls of extract_features_stream on the same root context, from any threads) take a
 // ticket on entry.  Driver d of a survey may start on slot d when the slot is free AND every survey with an earlier
