@@ -569,6 +569,25 @@ extern "C"
                                   int height, int images_on_device, const uint64_t *node_ids);
     const char *och_thumbnail_last_error(void);
 
+    /* ---- averaged overview levels of the orthomosaic and the DSM (opencalibration_amd/csrc/host/ortho_overview.cpp,
+     * csrc/ortho_overview.hpp; the reference's three BuildOverviews("AVERAGE", ...) calls, src/ortho/ortho.cpp:944-961,
+     * 1642-1657, 2028-2044) --------------------------------------------------------------------------------------------------
+     * The levels, the two cell rules and the builder of include/ochip.h (ochip_ortho_overviews_*, kind OCHIP_OVERVIEW_RGBA8 /
+     * OCHIP_OVERVIEW_FLOAT32): ctx != NULL builds on its device; ctx == NULL is the CPU route, the same rule in straight
+     * loops with the same builder semantics - host bands, host levels, bit for bit what the device computes.  A binding
+     * that writes the rasters band by band creates its overview levels empty, feeds every finished band and writes the
+     * rows complete_rows newly reports.  The refusals return OCHIP_EINVAL (a failed device call its
+     * code) with the message in och_ortho_overviews_last_error. */
+    typedef struct och_ortho_overviews och_ortho_overviews;
+    int och_ortho_overviews_levels(int64_t width, int64_t height, int64_t *rows_cols);
+    int och_ortho_overviews_create(ochip_ctx *ctx, int kind, int64_t width, int64_t height, void *const *levels, int on_device,
+                                   och_ortho_overviews **out);
+    int och_ortho_overviews_feed(och_ortho_overviews *o, int64_t row0, int64_t rows, const void *band);
+    int64_t och_ortho_overviews_complete_rows(const och_ortho_overviews *o, int level);
+    int och_ortho_overviews_finish(och_ortho_overviews *o);
+    void och_ortho_overviews_destroy(och_ortho_overviews *o);
+    const char *och_ortho_overviews_last_error(void);
+
 #ifdef __cplusplus
 }
 #endif

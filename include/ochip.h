@@ -891,6 +891,38 @@ extern "C"
      * (host arrays; n may be 0); fill_ms (may be NULL): what the one launch that filled the table took. */
     int ochip_debug_lab_table(ochip_ctx *ctx, const uint32_t *codes, size_t n, uint32_t *out, float *fill_ms);
 
+    /* ---- averaged overview levels of the orthomosaic and the DSM (opencalibration_amd/csrc/ortho_overview.hip, the rule in
+     *      csrc/ortho_overview.hpp; the reference's BuildOverviews("AVERAGE", 2, 4, 8, ...), src/ortho/ortho.cpp:944-961,
+     *      1642-1657, 2028-2044) ----
+     * Level 0 is the raster, width x height pixels of 4 bytes; the levels are k = 1, 2, ... for every factor 2^k <
+     * min(width, height), level k of ceil(height / 2^k) rows and ceil(width / 2^k) columns.  Pixel (r, c) of level k comes
+     * from its cell, the pixels (2r .. 2r + 1, 2c .. 2c + 1) of level k - 1 that exist (4, 2 or 1).
+     * OCHIP_OVERVIEW_RGBA8 (alpha is byte 3; BGRA alike): n = cell pixels with alpha > 0, m = all of them; n = 0 gives
+     * (0, 0, 0, 0), else every colour is (sum over the n valid + n / 2) / n and alpha (sum over all m + m / 2) / m in
+     * integers.  OCHIP_OVERVIEW_FLOAT32 (NaN: no data; inputs finite or NaN): the double sum of the cell's non-NaN pixels
+     * in the order top-left, top-right, bottom-left, bottom-right over their count, rounded once to float; NaN when none.
+     * ochip_ortho_overviews_levels: the number of levels (0 for min(width, height) <= 2; OCHIP_EINVAL for a side below 1)
+     * and, when rows_cols is not NULL, {rows, cols} of levels 1, 2, ...  Needs no device.
+     * The builder is fed level 0 band by band and writes into the caller's level buffers (levels[k - 1]: level k, whole;
+     * device pointers of this context's GPU when on_device, else host - then the fed bands are host memory too, and a feed
+     * uploads its band, downloads the rows it completed and waits).  feed: rows [row0, row0 + rows) of level 0, bands in
+     * ascending order and contiguous from row 0, of any row count; with device bands it enqueues on the context's stream
+     * and does not wait.  complete_rows: the rows of level `level` (1 ..) the feeds so far have computed, monotone (0 for a
+     * level that does not exist).  finish: after the last row; waits for the stream, the levels are then the caller's to
+     * read.  Refused with OCHIP_EINVAL and a message that names the rows: a gap, an overlap, rows beyond the raster, a feed
+     * after finish, finish before the last row.  The only state between feeds is one pending level-0 row (a band that ends
+     * on an odd row) in a block of the context's pool; destroy waits for the stream and hands it back. */
+#define OCHIP_OVERVIEW_RGBA8 0
+#define OCHIP_OVERVIEW_FLOAT32 1
+    typedef struct ochip_ortho_overviews ochip_ortho_overviews;
+    int ochip_ortho_overviews_levels(int64_t width, int64_t height, int64_t *rows_cols);
+    int ochip_ortho_overviews_create(ochip_ctx *ctx, int kind, int64_t width, int64_t height, void *const *levels, int on_device,
+                                     ochip_ortho_overviews **out);
+    int ochip_ortho_overviews_feed(ochip_ortho_overviews *o, int64_t row0, int64_t rows, const void *band);
+    int64_t ochip_ortho_overviews_complete_rows(const ochip_ortho_overviews *o, int level);
+    int ochip_ortho_overviews_finish(ochip_ortho_overviews *o);
+    void ochip_ortho_overviews_destroy(ochip_ortho_overviews *o);
+
 #ifdef __cplusplus
 }
 #endif

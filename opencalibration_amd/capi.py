@@ -46,6 +46,8 @@ EXPORTS = [
     "ochip_image_slots_upload", "ochip_image_slots_mark", "ochip_image_slots_wait", "ochip_image_slots_elapsed",
     "ochip_color_balance_solve", "ochip_color_balance_evaluate",
     "ochip_thumbnail_size", "ochip_image_thumbnails", "ochip_debug_lab_table",
+    "ochip_ortho_overviews_levels", "ochip_ortho_overviews_create", "ochip_ortho_overviews_feed",
+    "ochip_ortho_overviews_complete_rows", "ochip_ortho_overviews_finish", "ochip_ortho_overviews_destroy",
 ]
 
 _lib = None
@@ -252,6 +254,14 @@ def load():
         L.ochip_thumbnail_size.argtypes = [i32, i32, vp, vp]
         L.ochip_image_thumbnails.argtypes = [vp, vp, u32, i32, i32, i32, vp]
         L.ochip_debug_lab_table.argtypes = [vp, vp, C.c_size_t, vp, vp]
+        L.ochip_ortho_overviews_levels.argtypes = [C.c_int64, C.c_int64, vp]
+        L.ochip_ortho_overviews_create.argtypes = [vp, i32, C.c_int64, C.c_int64, vp, i32, C.POINTER(vp)]
+        L.ochip_ortho_overviews_feed.argtypes = [vp, C.c_int64, C.c_int64, vp]
+        L.ochip_ortho_overviews_complete_rows.argtypes = [vp, i32]
+        L.ochip_ortho_overviews_complete_rows.restype = C.c_int64
+        L.ochip_ortho_overviews_finish.argtypes = [vp]
+        L.ochip_ortho_overviews_destroy.argtypes = [vp]
+        L.ochip_ortho_overviews_destroy.restype = None
         _lib = L
     return _lib
 

@@ -282,6 +282,15 @@ def load():
         L.och_image_thumbnails.argtypes = [vp, vp, u32, C.c_int, C.c_int, C.c_int, vp]
         L.och_graph_make_thumbnails.argtypes = [vp, vp, vp, u32, C.c_int, C.c_int, C.c_int, _u64p]
         L.och_thumbnail_last_error.restype = C.c_char_p
+        L.och_ortho_overviews_levels.argtypes = [i64, i64, vp]
+        L.och_ortho_overviews_create.argtypes = [vp, C.c_int, i64, i64, vp, C.c_int, C.POINTER(vp)]
+        L.och_ortho_overviews_feed.argtypes = [vp, i64, i64, vp]
+        L.och_ortho_overviews_complete_rows.argtypes = [vp, C.c_int]
+        L.och_ortho_overviews_complete_rows.restype = i64
+        L.och_ortho_overviews_finish.argtypes = [vp]
+        L.och_ortho_overviews_destroy.argtypes = [vp]
+        L.och_ortho_overviews_destroy.restype = None
+        L.och_ortho_overviews_last_error.restype = C.c_char_p
         _lib = L
     return _lib
 
@@ -1203,7 +1212,8 @@ def color_balance_remove_gauge(xy, offsets):
     return off, rank
 
 
-def ortho_mosaic(plan, graph, surfaces, images, mesh=None, config=None, color_balance=None, tile_rows=1, out=None):
+def ortho_mosaic(plan, graph, surfaces, images, mesh=None, config=None, color_balance=None, tile_rows=1, out=None,
+                 overviews=False):
     """The blended full-resolution orthomosaic of `plan` (dsm_plan), band by band of tile_rows output tile rows: DSM ->
     layers (ortho_layers) -> blend (ortho_blend).  mesh (an OrthoMesh): every step on its device, images as CUDA tensors,
     into `out` (a (height, width, 4) uint8 CUDA tensor, made when None); None: the CPU route, numpy images, into a host
@@ -1212,20 +1222,26 @@ def ortho_mosaic(plan, graph, surfaces, images, mesh=None, config=None, color_ba
     COLOR_BALANCE -> BLEND_LAYERS - a first pass over the bands renders the layers for their correspondences alone,
     color_balance_solve (on the mesh's device, or the CPU route) turns them into the tables, and the second pass
     RE-RENDERS every band's layers and blends them with the result: a band's layers are never kept beyond its blend, so
-    the memory held stays one band's whatever the raster's size, at the price of the layer pass run twice."""
-    return _mosaic(plan, graph, surfaces, mesh, config, color_balance, tile_rows, out, images=images)
+    the memory held stays one band's whatever the raster's size, at the price of the layer pass run twice.
+    overviews=True: (out, dict(rgba=[level 1, ...], dsm=[level 1, ...])), the averaged overview levels (OrthoOverviews) of
+    the mosaic and of the DSM, each band fed right after its blend - with "solve" in the second sweep alone."""
+    return _mosaic(plan, graph, surfaces, mesh, config, color_balance, tile_rows, out, images=images, overviews=overviews)
 
 
-def ortho_mosaic_streamed(plan, graph, surfaces, fetch, mesh, capacity, config=None, color_balance=None, tile_rows=1, out=None):
+def ortho_mosaic_streamed(plan, graph, surfaces, fetch, mesh, capacity, config=None, color_balance=None, tile_rows=1, out=None,
+                          overviews=False):
     """ortho_mosaic on mesh's device without the source images resident: fetch(i) returns involved camera i's BGR image
     (ortho_layers_cameras' order) as a numpy array or a page-locked torch CPU tensor, and at most `capacity` images are on
     the device at a time (OrthoStream).  Band k + 1's ahead uploads are issued before band k renders, so that they run
     beside it when the images are page-locked.  color_balance as ortho_mosaic's; "solve" renders the layers twice, the
-    second sweep starting from the images the first one left on the device.  Returns the (height, width, 4) RGBA tensor."""
-    return _mosaic(plan, graph, surfaces, mesh, config, color_balance, tile_rows, out, fetch=fetch, capacity=capacity)
+    second sweep starting from the images the first one left on the device.  Returns the (height, width, 4) RGBA tensor,
+    with overviews=True (tensor, dict(rgba=[...], dsm=[...])) as ortho_mosaic does."""
+    return _mosaic(plan, graph, surfaces, mesh, config, color_balance, tile_rows, out, fetch=fetch, capacity=capacity,
+                   overviews=overviews)
 
 
-def _mosaic(plan, graph, surfaces, mesh, config, color_balance, tile_rows, out, images=None, fetch=None, capacity=None):
+def _mosaic(plan, graph, surfaces, mesh, config, color_balance, tile_rows, out, images=None, fetch=None, capacity=None,
+            overviews=False):
     """The band loop of ortho_mosaic (images) and ortho_mosaic_streamed (fetch, capacity): the two differ in where a band's
     layers come from, ortho_layers over the resident images or an OrthoStream's render behind the band's uploads."""
     cfg = {**LAYERS_CONFIG, **BLEND_CONFIG, **(config or {})}
@@ -1243,6 +1259,8 @@ def _mosaic(plan, graph, surfaces, mesh, config, color_balance, tile_rows, out, 
         ctx, dev = mesh.ctx, f"cuda:{mesh.ctx.device}"
         out = torch.empty((h, w, 4), dtype=torch.uint8, device=dev) if out is None else out
     stream = OrthoStream(plan, graph, surfaces, capacity, mesh=mesh, tile_rows=tile_rows, config=lcfg) if fetch is not None else None
+    builders = [OrthoOverviews(kind, w, h, ctx=ctx, on_device=mesh is not None)
+                for kind in (OVERVIEW_RGBA8, OVERVIEW_FLOAT32)] if overviews else []
 
     def band(k, balance, blend):
         row0 = k * band_rows
@@ -1267,6 +1285,9 @@ def _mosaic(plan, graph, surfaces, mesh, config, color_balance, tile_rows, out, 
                                   dsm=dsm if mesh is None else None)
         if blend:
             ortho_blend(plan, graph, surfaces, layers, dsm, balance, ctx=ctx, config=bcfg, out=out[row0:row0 + rows])
+            if builders:  # behind the blend on the context's stream: no wait of its own
+                builders[0].feed(row0, out[row0:row0 + rows])
+                builders[1].feed(row0, dsm)
         return layers["correspondences"]
 
     try:
@@ -1278,10 +1299,145 @@ def _mosaic(plan, graph, surfaces, mesh, config, color_balance, tile_rows, out, 
                 stream.rewind()
         for k in bands:
             band(k, color_balance, True)
+        if builders:
+            return out, dict(rgba=builders[0].finish(), dsm=builders[1].finish())
     finally:
         if stream is not None:
             stream.close()
+        for b in builders:
+            b.close()
     return out
+
+
+# ---- averaged overview levels of the orthomosaic and the DSM (include/oc_host.h; DESIGN.md §4.13) -----------------------
+OVERVIEW_RGBA8, OVERVIEW_FLOAT32 = 0, 1
+
+
+def overview_levels(width, height):
+    """[(rows, cols), ...] of the overview levels 1, 2, ... of a width x height raster: one level for every factor
+    2^k < min(width, height) - the reference's loop around BuildOverviews - of ceil(height / 2^k) x ceil(width / 2^k)."""
+    L = load()
+    n = L.och_ortho_overviews_levels(int(width), int(height), None)
+    if n < 0:
+        raise ValueError(L.och_ortho_overviews_last_error().decode())
+    sizes = np.zeros((n, 2), np.int64)
+    L.och_ortho_overviews_levels(int(width), int(height), sizes.ctypes.data)
+    return [(int(r), int(c)) for r, c in sizes]
+
+
+def _overview_kind(dtype, shape):
+    """(kind, height, width) of a raster or band given by dtype and shape: (rows, width, 4) uint8 or (rows, width) float32"""
+    name = str(dtype).replace("torch.", "")
+    if name == "uint8" and len(shape) == 3 and shape[2] == 4:
+        return OVERVIEW_RGBA8, int(shape[0]), int(shape[1])
+    if name == "float32" and len(shape) == 2:
+        return OVERVIEW_FLOAT32, int(shape[0]), int(shape[1])
+    raise ValueError("an overview raster is (rows, width, 4) uint8 or (rows, width) float32")
+
+
+class OrthoOverviews:
+    """The averaged overview levels of a raster fed band by band (och_ortho_overviews_*; the rule: DESIGN.md §4.13).
+    kind: OVERVIEW_RGBA8 ((rows, width, 4) uint8 bands, alpha last) or OVERVIEW_FLOAT32 ((rows, width) float32, NaN: no
+    data).  ctx None: the CPU route, numpy bands and levels.  ctx with on_device: CUDA tensors, fed on the context's stream
+    without a host wait - the caller has torch's work on a band finished before feed, as ortho_blend does - and the levels
+    are read after finish().  ctx without on_device: numpy in and out through the device.  levels: the list of level
+    arrays, made here when None.  feed(row0, band): bands ascend and are contiguous from row 0, of any row count;
+    complete_rows(level) is monotone.  A gap, an overlap, a feed after finish and a finish before the last row raise
+    OchipError naming the rows."""
+
+    def __init__(self, kind, width, height, ctx=None, on_device=False, levels=None):
+        self.L, self.kind, self.width, self.height, self.ctx = load(), int(kind), int(width), int(height), ctx
+        self.on_device = bool(on_device)
+        if self.on_device and ctx is None:
+            raise ValueError("levels on the device need the device route (ctx)")
+        self.h = None
+        sizes = overview_levels(width, height)
+        tail = (4,) if self.kind == OVERVIEW_RGBA8 else ()
+        if self.on_device:
+            import torch
+
+            dtype = torch.uint8 if self.kind == OVERVIEW_RGBA8 else torch.float32
+            if levels is None:
+                levels = [torch.empty(s + tail, dtype=dtype, device=f"cuda:{ctx.device}") for s in sizes]
+            ptrs = [_device_ptr(l, str(dtype), s + tail, f"level {k + 1}", ctx.device) for k, (l, s) in enumerate(zip(levels, sizes))]
+        else:
+            dtype = np.uint8 if self.kind == OVERVIEW_RGBA8 else np.float32
+            if levels is None:
+                levels = [np.zeros(s + tail, dtype) for s in sizes]
+            for k, (l, s) in enumerate(zip(levels, sizes)):
+                if not isinstance(l, np.ndarray) or l.shape != s + tail or l.dtype != dtype or not l.flags.c_contiguous:
+                    raise ValueError(f"level {k + 1} must be a contiguous {np.dtype(dtype).name} array of {s + tail}")
+            ptrs = [l.ctypes.data for l in levels]
+        if len(levels) != len(sizes):
+            raise ValueError(f"a {width} x {height} raster has {len(sizes)} overview levels")
+        self.levels = list(levels)
+        arr = (C.c_void_p * max(1, len(ptrs)))(*ptrs)
+        h = C.c_void_p()
+        if self.L.och_ortho_overviews_create(ctx.h if ctx is not None else None, self.kind, self.width, self.height, arr,
+                                             int(self.on_device), C.byref(h)) != 0:
+            raise capi.OchipError(self._error())
+        self.h = h
+        self._keep = None
+
+    def _error(self):
+        return self.L.och_ortho_overviews_last_error().decode()
+
+    def close(self):
+        if getattr(self, "h", None):
+            if self.ctx is None or getattr(self.ctx, "h", None):  # as OrthoStream.close: the context may be gone
+                self.L.och_ortho_overviews_destroy(self.h)
+            self.h = None
+            self._keep = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        self.close()
+
+    def feed(self, row0, band):
+        kind, rows, w = _overview_kind(band.dtype, tuple(band.shape))
+        if kind != self.kind or w != self.width:
+            raise ValueError(f"a band of this builder is {self.width} pixels wide, kind {self.kind}")
+        if self.on_device:
+            shape = (rows, w, 4) if kind == OVERVIEW_RGBA8 else (rows, w)
+            ptr = _device_ptr(band, str(band.dtype), shape, "band", self.ctx.device)
+        else:
+            band = np.ascontiguousarray(band)
+            ptr = band.ctypes.data
+        if self.L.och_ortho_overviews_feed(self.h, int(row0), rows, ptr) != 0:
+            raise capi.OchipError(self._error())
+        self._keep = band  # the kernels may still read it: alive until the next feed, finish or close
+
+    def complete_rows(self, level):
+        return int(self.L.och_ortho_overviews_complete_rows(self.h, int(level)))
+
+    def finish(self):
+        if self.L.och_ortho_overviews_finish(self.h) != 0:
+            raise capi.OchipError(self._error())
+        self._keep = None
+        return self.levels
+
+
+def ortho_overviews(raster, ctx=None):
+    """The overview levels [level 1, level 2, ...] of a whole raster in one feed: (height, width, 4) uint8 RGBA (or BGRA)
+    or (height, width) float32 with NaN as no data; a numpy array (ctx None: the CPU route, else through ctx's device) or
+    a CUDA tensor on ctx's device, the levels then CUDA tensors."""
+    on_device = not isinstance(raster, np.ndarray)
+    kind, h, w = _overview_kind(raster.dtype, tuple(raster.shape))
+    if on_device:
+        if ctx is None:
+            raise ValueError("a device raster needs the device route (ctx)")
+        import torch
+
+        torch.cuda.current_stream(raster.device).synchronize()  # the kernels run on the context's own stream
+    with OrthoOverviews(kind, w, h, ctx=ctx, on_device=on_device) as b:
+        if h > 0:
+            b.feed(0, raster)
+        return b.finish()
 
 
 def blend_chamfer(boundary):
