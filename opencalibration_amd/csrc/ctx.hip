@@ -19,34 +19,49 @@ int ochip_fail(ochip_ctx *ctx, int code, const char *fmt, ...)
     return code;
 }
 
-int ochip_ensure(ochip_ctx *ctx, void **ptr, size_t *cap, size_t bytes)
+int ochip::dev_array_mem::grow(ochip_ctx *ctx, size_t want)
 {
-    if (bytes <= *cap)
-        return OCHIP_OK;
-    if (*ptr)
-        OCHIP_HIP(ctx, hipFree(*ptr));
-    *ptr = nullptr;
-    *cap = 0;
-    size_t want = bytes + bytes / 4 + 4096;
-    if (hipMalloc(ptr, want) != hipSuccess)
+    if (mem)
+        OCHIP_HIP(ctx, hipFree(mem));
+    mem = nullptr;
+    bytes = 0;
+    want += want / 4 + 4096;
+    if (hipMalloc(&mem, want) != hipSuccess)
         return ochip_fail(ctx, OCHIP_ENOMEM, "hipMalloc(%zu) failed", want);
-    *cap = want;
+    bytes = want;
+    if (!listed)
+        ctx->dev_arrays.push_back(this);
+    listed = true;
     return OCHIP_OK;
+}
+
+void ochip::dev_array_mem::release()
+{
+    if (mem)
+        (void)hipFree(mem);
+    mem = nullptr;
+    bytes = 0;
 }
 
 int ochip_ensure_keypoint_store(ochip_ctx *ctx, size_t n_keypoints, size_t n_images)
 {
     const size_t n = n_keypoints ? n_keypoints : 1, m = n_images ? n_images : 1;
-    int rc = ochip_ensure(ctx, (void **)&ctx->kp_xy_dev, &ctx->kp_xy_bytes, n * 16);
-    if (rc == OCHIP_OK)
-        rc = ochip_ensure(ctx, (void **)&ctx->rays_dev, &ctx->rays_bytes, n * 24);
-    if (rc == OCHIP_OK)
-        rc = ochip_ensure(ctx, (void **)&ctx->kp_image_dev, &ctx->kp_image_bytes, n * 4);
-    if (rc == OCHIP_OK)
-        rc = ochip_ensure(ctx, (void **)&ctx->models_dev, &ctx->models_bytes, m * 64);
-    if (rc == OCHIP_OK)
-        ctx->kp_store_ready = true;
-    return rc;
+    OCHIP_TRY(ctx->kp_xy_dev.ensure(ctx, n * 2));
+    OCHIP_TRY(ctx->rays_dev.ensure(ctx, n * 3));
+    OCHIP_TRY(ctx->kp_image_dev.ensure(ctx, n));
+    OCHIP_TRY(ctx->models_dev.ensure(ctx, m * 8));
+    ctx->kp_store_ready = true;
+    return OCHIP_OK;
+}
+
+int ochip_upload_image_tables(ochip_ctx *ctx)
+{
+    if (!ctx->img_tables_dirty)
+        return OCHIP_OK;
+    OCHIP_HIP(ctx, hipMemcpyAsync(ctx->img_off_dev, ctx->img_off.data(), (size_t)ctx->n_images * 8, hipMemcpyHostToDevice, ctx->stream));
+    OCHIP_HIP(ctx, hipMemcpyAsync(ctx->img_n_dev, ctx->img_n.data(), (size_t)ctx->n_images * 4, hipMemcpyHostToDevice, ctx->stream));
+    ctx->img_tables_dirty = false;
+    return OCHIP_OK;
 }
 
 void *ochip_pool_get(ochip_ctx *ctx, size_t bytes, size_t *got)
@@ -278,22 +293,8 @@ void ochip_ctx_destroy(ochip_ctx *ctx)
             (void)hipEventDestroy(p.second);
         }
     }
-    void *bufs[] = {ctx->desc_dev,      ctx->img_off_dev,   ctx->img_n_dev, ctx->pairs_dev,    ctx->out_off_dev,
-                    ctx->match_out_dev, ctx->kp_xy_dev,     ctx->rays_dev,  ctx->kp_image_dev, ctx->models_dev,
-                    ctx->ms_recs_dev,   ctx->ms_seg_dev,    ctx->ms_flag_dev};
-    for (void *b : bufs)
-        if (b)
-            (void)hipFree(b);
-    for (void *b : ctx->scratch_dev)
-        if (b)
-            (void)hipFree(b);
-    if (ctx->sym_jobs_dev)
-        (void)hipFree(ctx->sym_jobs_dev);
-    if (ctx->sym_part_dev)
-        (void)hipFree(ctx->sym_part_dev);
-    for (void *b : {ctx->desc_fp4_dev, ctx->desc_negpop_dev, ctx->desc_pop_dev})
-        if (b)
-            (void)hipFree(b);
+    for (ochip::dev_array_mem *a : ctx->dev_arrays)
+        a->release();
     if (ctx->akaze_tabs && ctx->akaze_tabs_destroy)
         ctx->akaze_tabs_destroy(ctx->akaze_tabs);
     ctx->akaze_tabs = nullptr;
@@ -431,13 +432,9 @@ int ochip_descriptors_reserve(ochip_ctx *ctx, uint32_t n_images, uint64_t total_
     ctx->img_set.assign(n_images, 0);
     ctx->img_tables_dirty = true;
     const size_t n_img = n_images ? n_images : 1;
-    int rc = ochip_ensure(ctx, (void **)&ctx->desc_dev, &ctx->desc_bytes, (size_t)(total_descriptors ? total_descriptors : 1) * 64);
-    if (rc == OCHIP_OK)
-        rc = ochip_ensure(ctx, (void **)&ctx->img_off_dev, &ctx->img_off_bytes, n_img * 8);
-    if (rc == OCHIP_OK)
-        rc = ochip_ensure(ctx, (void **)&ctx->img_n_dev, &ctx->img_n_bytes, n_img * 4);
-    if (rc != OCHIP_OK)
-        return rc;
+    OCHIP_TRY(ctx->desc_dev.ensure(ctx, (size_t)(total_descriptors ? total_descriptors : 1) * 16));
+    OCHIP_TRY(ctx->img_off_dev.ensure(ctx, n_img));
+    OCHIP_TRY(ctx->img_n_dev.ensure(ctx, n_img));
     ctx->desc_capacity = total_descriptors;
     return OCHIP_OK;
 }

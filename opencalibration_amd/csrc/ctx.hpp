@@ -57,7 +57,90 @@ struct ochip_lazy_stream
 namespace ochip
 {
 struct akaze_tables;
-}
+
+// The untyped core of dev_array: one device allocation that only ever grows, and the context's list of them.
+struct dev_array_mem
+{
+    dev_array_mem() = default;
+    dev_array_mem(const dev_array_mem &) = delete;
+    dev_array_mem &operator=(const dev_array_mem &) = delete;
+    void release(); // hipFree, for ochip_ctx_destroy alone (it walks ochip_ctx::dev_arrays)
+
+  protected:
+    void *mem = nullptr;
+    size_t bytes = 0;
+    bool listed = false; // in ctx->dev_arrays, from the first allocation on
+    int grow(ochip_ctx *ctx, size_t want); // ctx.hip
+};
+
+// A device array that lives as long as its context and only ever grows (a reservation reuses it instead of hipFree /
+// hipMalloc, which synchronise the whole device and would stall the other contexts' streams).  ensure(ctx, n) makes room for
+// n elements: nothing when n <= capacity, else the old block is freed and one of n elements plus a quarter plus 4 KB taken.
+// The CONTENTS DO NOT SURVIVE growth: whoever calls ensure fills the array afterwards (fp4_valid = 0 on a reservation, the
+// dirty flags of the image tables and the rays).  Converts to T * for kernel launches and copies; as<U>() is the typed
+// view of a byte array that packs tables or holds a struct private to one file.  Freed by ochip_ctx_destroy, not by a
+// destructor: the context is deleted after its streams, the arrays go before the pools.
+template <class T> struct dev_array : dev_array_mem
+{
+    size_t capacity = 0; // elements
+
+    int ensure(ochip_ctx *ctx, size_t n)
+    {
+        if (n <= capacity)
+            return OCHIP_OK;
+        const int rc = grow(ctx, n * sizeof(T));
+        capacity = bytes / sizeof(T);
+        return rc;
+    }
+    operator T *() const
+    {
+        return static_cast<T *>(mem);
+    }
+    template <class U> U *as() const
+    {
+        return static_cast<U *>(mem);
+    }
+};
+
+// Who filled the RANSAC scratch last: ochip_edge_lists reads what ochip_ransac_homography_batch_sorted left there.
+enum class ransac_writer
+{
+    nothing,
+    homography_batch,
+    homography_batch_sorted,
+    refit,
+    epipolar
+};
+
+// Device state of the RANSAC entries (ransac.hip), T = correspondences of the batch.  The homography routes and the epipolar
+// one keep different structs in `jobs` and `corr`, hence bytes and a typed view at the use.
+struct ransac_scratch
+{
+    dev_array<unsigned char> jobs;  // [n_jobs] ochip_ransac_job, or the epipolar job
+    dev_array<unsigned char> corr;  // [T] ochip_ransac_match, or 6 doubles (the two rays)
+    dev_array<uint32_t> prosac;     // [T] PROSAC order
+    dev_array<uint32_t> eval_order; // [eval_total]
+    dev_array<double> coords;       // [T][8]
+    dev_array<uint8_t> flags;       // [T][2] homography, [T][5] epipolar
+    dev_array<double> lu;           // [n_jobs][81] LU workspaces
+    dev_array<unsigned char> out;   // [n_jobs] ochip_ransac_result, then [T] inlier flags
+    ransac_writer last = ransac_writer::nothing;
+
+    struct outputs
+    {
+        ochip_ransac_result *results;
+        uint8_t *inliers;
+    };
+    outputs outputs_of(uint32_t n_jobs) const
+    {
+        ochip_ransac_result *r = out.as<ochip_ransac_result>();
+        return {r, reinterpret_cast<uint8_t *>(r + n_jobs)};
+    }
+    // Room for a batch of `who`, which becomes the last writer; a refit (flags_per_corr == 0) has no orders and no flags.
+    int ensure(ochip_ctx *ctx, ransac_writer who, uint32_t n_jobs, size_t job_bytes, uint64_t T, size_t corr_bytes, uint64_t eval_total,
+               unsigned flags_per_corr); // ransac.hip
+};
+} // namespace ochip
 
 struct ochip_ctx
 {
@@ -72,53 +155,51 @@ struct ochip_ctx
     hipDeviceProp_t prop{};
 
     // descriptor arena: [total][16] u32, image i at img_off[i] with img_n[i] descriptors
-    uint32_t *desc_dev = nullptr;
+    ochip::dev_array<uint32_t> desc_dev;
     uint64_t desc_capacity = 0, desc_used = 0;
     uint32_t n_images = 0;
     std::vector<uint64_t> img_off;
     std::vector<uint32_t> img_n;
     std::vector<uint8_t> img_set;
-    uint64_t *img_off_dev = nullptr;
-    uint32_t *img_n_dev = nullptr;
-    bool img_tables_dirty = true;
+    ochip::dev_array<uint64_t> img_off_dev;
+    ochip::dev_array<uint32_t> img_n_dev;
+    bool img_tables_dirty = true; // ochip_upload_image_tables
 
     // keypoint store, same indexing as the descriptor arena: pixel xy, owning image, unit rays
-    double *kp_xy_dev = nullptr;
-    double *rays_dev = nullptr;
-    uint32_t *kp_image_dev = nullptr;
-    double *models_dev = nullptr; // [n_images][8]: f, ppx, ppy, k1, k2, k3, p1, p2
+    ochip::dev_array<double> kp_xy_dev, rays_dev;
+    ochip::dev_array<uint32_t> kp_image_dev;
+    ochip::dev_array<double> models_dev; // [n_images][8]: f, ppx, ppy, k1, k2, k3, p1, p2
     std::vector<uint8_t> kp_set;
     bool rays_dirty = false;
     bool kp_store_ready = false; // keypoint buffers sized for the current reservation
-    // capacities (bytes) of the grow-only buffers above: a reservation reuses them instead of hipFree / hipMalloc,
-    // which synchronise the whole device and would stall the other contexts' streams
-    size_t desc_bytes = 0, img_off_bytes = 0, img_n_bytes = 0, kp_xy_bytes = 0, rays_bytes = 0, kp_image_bytes = 0,
-           models_bytes = 0;
 
     // match scratch
-    ochip_pair *pairs_dev = nullptr;
-    uint64_t *out_off_dev = nullptr;
-    size_t pairs_cap = 0;
-    ochip_match *match_out_dev = nullptr;
-    size_t match_out_cap = 0;
+    ochip::dev_array<ochip_pair> pairs_dev;
+    ochip::dev_array<uint64_t> out_off_dev;
+    ochip::dev_array<ochip_match> match_out_dev;
     uint64_t match_out_total = 0;
     // ochip_match_sort (match_sort.hip): per pair the matches that pass the ratio test as (count << 32 | query) records at the
-    // pair's offset, in match_features_subset's output order; the pairs' offsets and match counts
-    void *ms_recs_dev = nullptr, *ms_seg_dev = nullptr, *ms_flag_dev = nullptr;
-    size_t ms_recs_cap = 0, ms_seg_cap = 0, ms_flag_cap = 0;
+    // pair's offset, in match_features_subset's output order; the pairs' offsets and match counts (ms_seg_dev packs three
+    // tables: [n] u32 begin, [n] u32 end, [n] ochip_pair)
+    ochip::dev_array<unsigned long long> ms_recs_dev;
+    ochip::dev_array<unsigned char> ms_seg_dev, ms_flag_dev;
     uint32_t ms_pairs = 0;
-    void *sym_jobs_dev = nullptr, *sym_part_dev = nullptr; // symmetric pairs of a match launch: job table, column partials
-    size_t sym_jobs_cap = 0, sym_part_cap = 0;
+    // symmetric pairs of a match launch: job table (match.hip's sym_job), column partials
+    ochip::dev_array<unsigned char> sym_jobs_dev;
+    ochip::dev_array<uint2> sym_part_dev;
     // operands of the matrix-core matcher (match.hip, hamming_2nn_mfma_kernel), same indexing as the descriptor arena: the
-    // descriptor's 512 bits as FP4 values 0 / 1 (256 bytes), (512 - popcount) * 8192 as a float, the popcount; features
-    // [0, fp4_valid) are expanded, the rest is done by the next match launch
-    void *desc_fp4_dev = nullptr, *desc_negpop_dev = nullptr, *desc_pop_dev = nullptr;
-    size_t desc_fp4_cap = 0, desc_negpop_cap = 0, desc_pop_cap = 0;
+    // descriptor's 512 bits as FP4 values 0 / 1 (256 bytes = 16 uint4), (512 - popcount) * 8192 as a float, the popcount;
+    // features [0, fp4_valid) are expanded, the rest is done by the next match launch
+    ochip::dev_array<uint4> desc_fp4_dev;
+    ochip::dev_array<float> desc_negpop_dev;
+    ochip::dev_array<uint32_t> desc_pop_dev;
     uint64_t fp4_valid = 0;
 
-    // generic scratch for the RANSAC / relax kernels (grown on demand)
-    void *scratch_dev[8] = {nullptr};
-    size_t scratch_cap[8] = {0};
+    // device state of the RANSAC entries, and which of them wrote it last
+    ochip::ransac_scratch ransac;
+
+    // every dev_array above that holds memory (dev_array_mem::grow lists it): what ochip_ctx_destroy frees
+    std::vector<ochip::dev_array_mem *> dev_arrays;
 
     // page-locked host blocks handed out by ochip_host_alloc (live) and recycled ones (pool)
     std::vector<std::pair<void *, size_t>> pinned_live, pinned_pool;
@@ -195,8 +276,8 @@ inline hipError_t ochip_copy_stream(ochip_ctx *ctx, hipStream_t *out)
 }
 
 int ochip_fail(ochip_ctx *ctx, int code, const char *fmt, ...);
-int ochip_ensure(ochip_ctx *ctx, void **ptr, size_t *cap, size_t bytes); // grow-only device buffer
 int ochip_ensure_keypoint_store(ochip_ctx *ctx, size_t n_keypoints, size_t n_images); // kp_xy, rays, kp_image, models
+int ochip_upload_image_tables(ochip_ctx *ctx); // if img_tables_dirty: enqueue the copies of img_off / img_n, clear the flag
 void *ochip_pool_get(ochip_ctx *ctx, size_t bytes, size_t *got);          // device block from the pool (or hipMalloc); nullptr on failure
 void ochip_pool_put(ochip_ctx *ctx, void *p, size_t bytes);              // hand it back (kept for reuse, freed with the context)
 void ochip_prof_begin(ochip_ctx *ctx, int kid, hipEvent_t *start, hipEvent_t *stop);

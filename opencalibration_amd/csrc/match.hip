@@ -675,44 +675,21 @@ int ochip_match_launch(ochip_ctx *ctx, const ochip_pair *pairs, uint32_t n_pairs
     for (const ochip_pair &pr : single_pairs)
         max_n1_single = std::max(max_n1_single, ctx->img_n[pr.image_1]);
 
-    if (ctx->img_tables_dirty)
-    {
-        OCHIP_HIP(ctx, hipMemcpyAsync(ctx->img_off_dev, ctx->img_off.data(), (size_t)ctx->n_images * 8,
-                                      hipMemcpyHostToDevice, ctx->stream));
-        OCHIP_HIP(ctx, hipMemcpyAsync(ctx->img_n_dev, ctx->img_n.data(), (size_t)ctx->n_images * 4,
-                                      hipMemcpyHostToDevice, ctx->stream));
-        ctx->img_tables_dirty = false;
-    }
-    if (n_single + n_mfma > ctx->pairs_cap)
-    {
-        if (ctx->pairs_dev)
-            OCHIP_HIP(ctx, hipFree(ctx->pairs_dev));
-        if (ctx->out_off_dev)
-            OCHIP_HIP(ctx, hipFree(ctx->out_off_dev));
-        ctx->pairs_dev = nullptr;
-        ctx->out_off_dev = nullptr;
-        ctx->pairs_cap = 0;
-        if (hipMalloc((void **)&ctx->pairs_dev, (size_t)(n_single + n_mfma) * sizeof(ochip_pair)) != hipSuccess ||
-            hipMalloc((void **)&ctx->out_off_dev, (size_t)(n_single + n_mfma) * 8) != hipSuccess)
-            return ochip_fail(ctx, OCHIP_ENOMEM, "hipMalloc for the pair table failed");
-        ctx->pairs_cap = n_single + n_mfma;
-    }
+    OCHIP_TRY(ochip_upload_image_tables(ctx));
+    OCHIP_TRY(ctx->pairs_dev.ensure(ctx, n_single + n_mfma));
+    OCHIP_TRY(ctx->out_off_dev.ensure(ctx, n_single + n_mfma));
     if (n_mfma)
     {
         // operands of the matrix-core kernel for the features uploaded since the last launch
-        int rc = ochip_ensure(ctx, &ctx->desc_fp4_dev, &ctx->desc_fp4_cap, (size_t)ctx->desc_capacity * 256);
-        if (rc == OCHIP_OK)
-            rc = ochip_ensure(ctx, &ctx->desc_negpop_dev, &ctx->desc_negpop_cap, (size_t)ctx->desc_capacity * 4);
-        if (rc == OCHIP_OK)
-            rc = ochip_ensure(ctx, &ctx->desc_pop_dev, &ctx->desc_pop_cap, (size_t)ctx->desc_capacity * 4);
-        if (rc)
-            return rc;
+        OCHIP_TRY(ctx->desc_fp4_dev.ensure(ctx, (size_t)ctx->desc_capacity * 16));
+        OCHIP_TRY(ctx->desc_negpop_dev.ensure(ctx, ctx->desc_capacity));
+        OCHIP_TRY(ctx->desc_pop_dev.ensure(ctx, ctx->desc_capacity));
         if (ctx->fp4_valid < ctx->desc_used)
         {
             const uint64_t n_new = ctx->desc_used - ctx->fp4_valid;
+            // (the expansion writes the operand words, the matcher loads them four at a time)
             hipLaunchKernelGGL(expand_fp4_kernel, dim3((uint32_t)((n_new + 3) / 4)), dim3(256), 0, ctx->stream, ctx->desc_dev,
-                               ctx->fp4_valid, n_new, (uint32_t *)ctx->desc_fp4_dev, (float *)ctx->desc_negpop_dev,
-                               (uint32_t *)ctx->desc_pop_dev);
+                               ctx->fp4_valid, n_new, ctx->desc_fp4_dev.as<uint32_t>(), ctx->desc_negpop_dev, ctx->desc_pop_dev);
             ctx->fp4_valid = ctx->desc_used;
         }
         OCHIP_HIP(ctx, hipMemcpyAsync(ctx->pairs_dev + n_single, mfma_pairs.data(), (size_t)n_mfma * sizeof(ochip_pair),
@@ -720,22 +697,11 @@ int ochip_match_launch(ochip_ctx *ctx, const ochip_pair *pairs, uint32_t n_pairs
         OCHIP_HIP(ctx, hipMemcpyAsync(ctx->out_off_dev + n_single, mfma_off.data(), (size_t)n_mfma * 8, hipMemcpyHostToDevice,
                                       ctx->stream));
     }
+    OCHIP_TRY(ctx->match_out_dev.ensure(ctx, out_total ? out_total : 1));
+    if (n_sym)
     {
-        void *p = ctx->match_out_dev;
-        size_t cap = ctx->match_out_cap * sizeof(ochip_match);
-        int rc = ochip_ensure(ctx, &p, &cap, (size_t)(out_total ? out_total : 1) * sizeof(ochip_match));
-        ctx->match_out_dev = (ochip_match *)p;
-        ctx->match_out_cap = cap / sizeof(ochip_match);
-        if (rc)
-            return rc;
-        if (n_sym)
-        {
-            rc = ochip_ensure(ctx, &ctx->sym_jobs_dev, &ctx->sym_jobs_cap, (size_t)n_sym * sizeof(sym_job));
-            if (rc == OCHIP_OK)
-                rc = ochip_ensure(ctx, &ctx->sym_part_dev, &ctx->sym_part_cap, (size_t)part_max * sizeof(uint2));
-            if (rc)
-                return rc;
-        }
+        OCHIP_TRY(ctx->sym_jobs_dev.ensure(ctx, (size_t)n_sym * sizeof(sym_job)));
+        OCHIP_TRY(ctx->sym_part_dev.ensure(ctx, part_max));
     }
     if (n_single)
     {
@@ -763,9 +729,8 @@ int ochip_match_launch(ochip_ctx *ctx, const ochip_pair *pairs, uint32_t n_pairs
     ochip_prof_begin(ctx, OCHIP_K_MATCH, &e0, &e1);
     if (mfma_blocks)
         hipLaunchKernelGGL(hamming_2nn_mfma_kernel, dim3((uint32_t)mfma_blocks), dim3(256), 0, ctx->stream,
-                           (const uint4 *)ctx->desc_fp4_dev, (const float *)ctx->desc_negpop_dev,
-                           (const uint32_t *)ctx->desc_pop_dev, ctx->img_off_dev, ctx->img_n_dev, ctx->pairs_dev + n_single,
-                           ctx->out_off_dev + n_single, ctx->match_out_dev, mfma_chunks);
+                           ctx->desc_fp4_dev, ctx->desc_negpop_dev, ctx->desc_pop_dev, ctx->img_off_dev, ctx->img_n_dev,
+                           ctx->pairs_dev + n_single, ctx->out_off_dev + n_single, ctx->match_out_dev, mfma_chunks);
     auto launch = [&](auto kernel) {
         hipLaunchKernelGGL(kernel, dim3((uint32_t)blocks), dim3(BLOCK), 0, ctx->stream, ctx->desc_dev,
                            ctx->img_off_dev, ctx->img_n_dev, ctx->pairs_dev, ctx->out_off_dev, ctx->match_out_dev,
@@ -779,11 +744,11 @@ int ochip_match_launch(ochip_ctx *ctx, const ochip_pair *pairs, uint32_t n_pairs
         const uint32_t g0 = sym_groups[gi], gn = sym_groups[gi + 1] - g0;
         if (gn == 0)
             continue;
-        const sym_job *jobs = (const sym_job *)ctx->sym_jobs_dev + g0;
+        const sym_job *jobs = ctx->sym_jobs_dev.as<sym_job>() + g0;
         hipLaunchKernelGGL(hamming_2nn_sym_kernel, dim3(sym_chunks * gn), dim3(BLOCK), 0, ctx->stream, ctx->desc_dev, ctx->img_off_dev,
-                           ctx->img_n_dev, jobs, ctx->match_out_dev, (uint2 *)ctx->sym_part_dev, sym_chunks);
+                           ctx->img_n_dev, jobs, ctx->match_out_dev, ctx->sym_part_dev, sym_chunks);
         hipLaunchKernelGGL(sym_merge_kernel, dim3(gn, (sym_max_nb + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, ctx->stream, jobs, ctx->img_n_dev,
-                           (const uint2 *)ctx->sym_part_dev, ctx->match_out_dev);
+                           ctx->sym_part_dev, ctx->match_out_dev);
     }
     ochip_prof_end(ctx, OCHIP_K_MATCH, e0, e1);
     OCHIP_HIP(ctx, hipGetLastError());

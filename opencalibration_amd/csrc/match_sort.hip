@@ -70,15 +70,11 @@ extern "C" int ochip_match_sort(ochip_ctx *ctx, const ochip_pair *pairs, uint32_
         return ochip_fail(ctx, OCHIP_EINVAL, "ochip_match_sort: %llu query records in one batch (limit 2^32)", (unsigned long long)out_total);
     OCHIP_HIP(ctx, hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
-    int rc = ochip_ensure(ctx, &ctx->ms_recs_dev, &ctx->ms_recs_cap, std::max<size_t>(out_total, 1) * 8);
-    if (rc == OCHIP_OK)
-        rc = ochip_ensure(ctx, &ctx->ms_seg_dev, &ctx->ms_seg_cap, (size_t)n_pairs * 16); // begin | end | pairs
-    if (rc == OCHIP_OK)
-        rc = ochip_ensure(ctx, &ctx->ms_flag_dev, &ctx->ms_flag_cap, (size_t)n_pairs);
-    if (rc != OCHIP_OK)
-        return rc;
+    OCHIP_TRY(ctx->ms_recs_dev.ensure(ctx, std::max<size_t>(out_total, 1)));
+    OCHIP_TRY(ctx->ms_seg_dev.ensure(ctx, (size_t)n_pairs * 16)); // begin | end | pairs
+    OCHIP_TRY(ctx->ms_flag_dev.ensure(ctx, n_pairs));
     ctx->ms_pairs = n_pairs;
-    unsigned int *seg_begin = (unsigned int *)ctx->ms_seg_dev, *seg_end = seg_begin + n_pairs;
+    unsigned int *seg_begin = ctx->ms_seg_dev.as<unsigned int>(), *seg_end = seg_begin + n_pairs;
     std::vector<unsigned int> begin(n_pairs);
     uint32_t max_n1 = 0;
     for (uint32_t p = 0; p < n_pairs; p++)
@@ -90,12 +86,10 @@ extern "C" int ochip_match_sort(ochip_ctx *ctx, const ochip_pair *pairs, uint32_
     OCHIP_HIP(ctx, hipMemcpyAsync(seg_begin, begin.data(), (size_t)n_pairs * 4, hipMemcpyHostToDevice, st));
     OCHIP_HIP(ctx, hipMemcpyAsync(pairs_dev, pairs, (size_t)n_pairs * sizeof(ochip_pair), hipMemcpyHostToDevice, st));
     // (ochip_match_launch left the images' counts on the device)
-    hipLaunchKernelGGL(ratio_compact_kernel, dim3((n_pairs + 3) / 4), dim3(256), 0, st, (const ochip_match *)ctx->match_out_dev,
-                       (const ochip_pair *)pairs_dev, (const uint32_t *)ctx->img_n_dev, n_pairs, (const unsigned int *)seg_begin, seg_end,
-                       (unsigned long long *)ctx->ms_recs_dev);
+    hipLaunchKernelGGL(ratio_compact_kernel, dim3((n_pairs + 3) / 4), dim3(256), 0, st, ctx->match_out_dev, pairs_dev,
+                       ctx->img_n_dev, n_pairs, seg_begin, seg_end, ctx->ms_recs_dev);
     dev_scratch mem{ctx, "ochip_match_sort"};
-    rc = std_sort_enqueue(ctx, mem, (unsigned long long *)ctx->ms_recs_dev, out_total, seg_begin, seg_end, n_pairs, max_n1,
-                          (unsigned char *)ctx->ms_flag_dev);
+    int rc = std_sort_enqueue(ctx, mem, ctx->ms_recs_dev, out_total, seg_begin, seg_end, n_pairs, max_n1, ctx->ms_flag_dev);
     std::vector<unsigned int> end(n_pairs);
     if (rc == OCHIP_OK && (hipMemcpyAsync(end.data(), seg_end, (size_t)n_pairs * 4, hipMemcpyDeviceToHost, st) != hipSuccess ||
                            hipMemcpyAsync(fallback_out, ctx->ms_flag_dev, n_pairs, hipMemcpyDeviceToHost, st) != hipSuccess))

@@ -2651,11 +2651,57 @@ __global__ void prosac_order_kernel(const unsigned long long *__restrict__ prosa
         sorted_idx[i] = (uint32_t)prosac[i];
 }
 
+// What the homography entries do before they size the scratch: the jobs against the keypoint store (eval_total == nullptr: the
+// jobs have no evaluation order), the rays if a keypoint or a model changed, the image tables.
+int prepare_homography_jobs(ochip_ctx *ctx, const ochip_ransac_job *jobs, uint32_t n_jobs, uint64_t total_matches, const uint64_t *eval_total)
+{
+    for (uint32_t j = 0; j < n_jobs; j++)
+    {
+        const ochip_ransac_job &jb = jobs[j];
+        if (jb.image_1 >= ctx->n_images || jb.image_2 >= ctx->n_images || !ctx->kp_set[jb.image_1] || !ctx->kp_set[jb.image_2])
+            return ochip_fail(ctx, OCHIP_ESTATE, "job %u references an image without keypoints", j);
+        if (jb.match_offset + jb.n > total_matches || (eval_total && jb.eval_offset + jb.n > *eval_total))
+            return ochip_fail(ctx, OCHIP_EINVAL, "job %u: offsets exceed the arrays", j);
+    }
+    if (ctx->rays_dirty)
+    {
+        const uint64_t n = ctx->desc_used;
+        if (n)
+            hipLaunchKernelGGL(keypoints_to_rays_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, ctx->kp_xy_dev,
+                               ctx->models_dev, ctx->kp_image_dev, ctx->rays_dev, n);
+        OCHIP_HIP(ctx, hipGetLastError());
+        ctx->rays_dirty = false;
+    }
+    return ochip_upload_image_tables(ctx);
+}
+
+const char *writer_name(ochip::ransac_writer w)
+{
+    static const char *const names[] = {"no call", "ochip_ransac_homography_batch", "ochip_ransac_homography_batch_sorted",
+                                        "ochip_refit_homography_batch", "ochip_ransac_epipolar_batch"};
+    return names[(int)w];
+}
+
 int ransac_homography_impl(ochip_ctx *ctx, const ochip_ransac_job *jobs, uint32_t n_jobs, const ochip_ransac_match *matches,
                            const uint32_t *sorted_idx, uint64_t total_matches, const uint32_t *eval_order, uint64_t eval_total,
                            double inlier_threshold, ochip_ransac_result *results, uint8_t *inliers, bool sorted_on_device,
                            ochip_ransac_match *matches_out, uint8_t *fallback_out, ochip_decomposition *decomp_out);
 } // namespace
+
+int ochip::ransac_scratch::ensure(ochip_ctx *ctx, ransac_writer who, uint32_t n_jobs, size_t job_bytes, uint64_t T, size_t corr_bytes,
+                                  uint64_t eval_total, unsigned flags_per_corr)
+{
+    last = who;
+    const bool search = flags_per_corr != 0; // (a refit samples nothing: no orders, no flags of a hypothesis)
+    OCHIP_TRY(jobs.ensure(ctx, n_jobs * job_bytes));
+    OCHIP_TRY(corr.ensure(ctx, T * corr_bytes));
+    OCHIP_TRY(prosac.ensure(ctx, search ? T : 0));
+    OCHIP_TRY(eval_order.ensure(ctx, search ? (eval_total ? eval_total : 1) : 0));
+    OCHIP_TRY(coords.ensure(ctx, T * 8));
+    OCHIP_TRY(flags.ensure(ctx, T * flags_per_corr));
+    OCHIP_TRY(lu.ensure(ctx, (size_t)n_jobs * 81));
+    return out.ensure(ctx, n_jobs * sizeof(ochip_ransac_result) + T);
+}
 
 extern "C"
 {
@@ -2702,68 +2748,22 @@ int ransac_homography_impl(ochip_ctx *ctx, const ochip_ransac_job *jobs, uint32_
     if (!ctx->kp_store_ready)
         return ochip_fail(ctx, OCHIP_ESTATE, "ochip_upload_keypoints has not been called");
     OCHIP_HIP(ctx, hipSetDevice(ctx->device));
-    for (uint32_t j = 0; j < n_jobs; j++)
-    {
-        const ochip_ransac_job &jb = jobs[j];
-        if (jb.image_1 >= ctx->n_images || jb.image_2 >= ctx->n_images || !ctx->kp_set[jb.image_1] ||
-            !ctx->kp_set[jb.image_2])
-            return ochip_fail(ctx, OCHIP_ESTATE, "job %u references an image without keypoints", j);
-        if (jb.match_offset + jb.n > total_matches || jb.eval_offset + jb.n > eval_total)
-            return ochip_fail(ctx, OCHIP_EINVAL, "job %u: offsets exceed the arrays", j);
-    }
-    if (ctx->rays_dirty)
-    {
-        const uint64_t n = ctx->desc_used;
-        if (n)
-            hipLaunchKernelGGL(keypoints_to_rays_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream,
-                               ctx->kp_xy_dev, ctx->models_dev, ctx->kp_image_dev, ctx->rays_dev, n);
-        OCHIP_HIP(ctx, hipGetLastError());
-        ctx->rays_dirty = false;
-    }
-    if (ctx->img_tables_dirty)
-    {
-        OCHIP_HIP(ctx, hipMemcpyAsync(ctx->img_off_dev, ctx->img_off.data(), (size_t)ctx->n_images * 8,
-                                      hipMemcpyHostToDevice, ctx->stream));
-        OCHIP_HIP(ctx, hipMemcpyAsync(ctx->img_n_dev, ctx->img_n.data(), (size_t)ctx->n_images * 4,
-                                      hipMemcpyHostToDevice, ctx->stream));
-        ctx->img_tables_dirty = false;
-    }
+    OCHIP_TRY(prepare_homography_jobs(ctx, jobs, n_jobs, total_matches, &eval_total));
     const uint64_t T = total_matches ? total_matches : 1;
-    enum
-    {
-        S_JOBS,
-        S_MATCH,
-        S_SORTED,
-        S_EVAL,
-        S_COORD,
-        S_FLAGS,
-        S_P,
-        S_OUT
-    };
-    const size_t sizes[8] = {(size_t)n_jobs * sizeof(ochip_ransac_job),
-                             (size_t)T * sizeof(ochip_ransac_match),
-                             (size_t)T * 4,
-                             (size_t)(eval_total ? eval_total : 1) * 4,
-                             (size_t)T * 64,
-                             (size_t)T * 2,
-                             (size_t)n_jobs * 81 * 8,
-                             (size_t)n_jobs * sizeof(ochip_ransac_result) + T};
-    for (int i = 0; i < 8; i++)
-    {
-        int rc = ochip_ensure(ctx, &ctx->scratch_dev[i], &ctx->scratch_cap[i], sizes[i]);
-        if (rc)
-            return rc;
-    }
-    OCHIP_HIP(ctx, hipMemcpyAsync(ctx->scratch_dev[S_JOBS], jobs, sizes[S_JOBS], hipMemcpyHostToDevice, ctx->stream));
+    ochip::ransac_scratch &rs = ctx->ransac;
+    OCHIP_TRY(rs.ensure(ctx, sorted_on_device ? ochip::ransac_writer::homography_batch_sorted : ochip::ransac_writer::homography_batch, n_jobs,
+                        sizeof(ochip_ransac_job), T, sizeof(ochip_ransac_match), eval_total, 2));
+    const ochip_ransac_job *jobs_dev = rs.jobs.as<ochip_ransac_job>();
+    ochip_ransac_match *matches_dev = rs.corr.as<ochip_ransac_match>();
+    OCHIP_HIP(ctx, hipMemcpyAsync(rs.jobs, jobs, (size_t)n_jobs * sizeof(ochip_ransac_job), hipMemcpyHostToDevice, ctx->stream));
     // (an early error return can leave kernels in flight that still touch these blocks: dev_scratch waits for the stream before
     // it hands them back; the normal path releases them after its own wait at the end)
     ochip::dev_scratch mem{ctx, "ochip_ransac_homography_batch"};
     if (total_matches && !sorted_on_device)
     {
-        OCHIP_HIP(ctx, hipMemcpyAsync(ctx->scratch_dev[S_MATCH], matches, (size_t)total_matches * sizeof(ochip_ransac_match),
-                                      hipMemcpyHostToDevice, ctx->stream));
-        OCHIP_HIP(ctx, hipMemcpyAsync(ctx->scratch_dev[S_SORTED], sorted_idx, (size_t)total_matches * 4,
-                                      hipMemcpyHostToDevice, ctx->stream));
+        OCHIP_HIP(ctx, hipMemcpyAsync(matches_dev, matches, (size_t)total_matches * sizeof(ochip_ransac_match), hipMemcpyHostToDevice,
+                                      ctx->stream));
+        OCHIP_HIP(ctx, hipMemcpyAsync(rs.prosac, sorted_idx, (size_t)total_matches * 4, hipMemcpyHostToDevice, ctx->stream));
     }
     else if (total_matches)
     {
@@ -2778,16 +2778,14 @@ int ransac_homography_impl(ochip_ctx *ctx, const ochip_ransac_job *jobs, uint32_
         unsigned char *fb2 = (unsigned char *)mem.get(n_jobs);
         if (!prosac || !seg2 || !fb2)
             return OCHIP_ENOMEM;
-        hipLaunchKernelGGL(sorted_matches_kernel, dim3((max_n + 255) / 256, n_jobs), dim3(256), 0, ctx->stream,
-                           (const ochip_ransac_job *)ctx->scratch_dev[S_JOBS], (const unsigned int *)ctx->ms_seg_dev,
-                           (const unsigned long long *)ctx->ms_recs_dev, (const ochip_match *)ctx->match_out_dev,
-                           (ochip_ransac_match *)ctx->scratch_dev[S_MATCH], prosac, seg2);
+        hipLaunchKernelGGL(sorted_matches_kernel, dim3((max_n + 255) / 256, n_jobs), dim3(256), 0, ctx->stream, jobs_dev,
+                           ctx->ms_seg_dev.as<unsigned int>(), ctx->ms_recs_dev, ctx->match_out_dev, matches_dev, prosac, seg2);
         const int src = ochip::std_sort_enqueue(ctx, mem, prosac, total_matches, seg2, seg2 + n_jobs, n_jobs, max_n, fb2);
         if (src != OCHIP_OK)
             return src;
         hipLaunchKernelGGL(prosac_order_kernel, dim3((unsigned)((total_matches + 255) / 256)), dim3(256), 0, ctx->stream,
-                           (const unsigned long long *)prosac, (uint32_t *)ctx->scratch_dev[S_SORTED], total_matches);
-        OCHIP_HIP(ctx, hipMemcpyAsync(matches_out, ctx->scratch_dev[S_MATCH], (size_t)total_matches * sizeof(ochip_ransac_match),
+                           (const unsigned long long *)prosac, rs.prosac, total_matches);
+        OCHIP_HIP(ctx, hipMemcpyAsync(matches_out, matches_dev, (size_t)total_matches * sizeof(ochip_ransac_match),
                                       hipMemcpyDeviceToHost, ctx->stream));
         OCHIP_HIP(ctx, hipMemcpyAsync(fallback_out, fb2, n_jobs, hipMemcpyDeviceToHost, ctx->stream));
     }
@@ -2795,11 +2793,9 @@ int ransac_homography_impl(ochip_ctx *ctx, const ochip_ransac_job *jobs, uint32_
         for (uint32_t j = 0; j < n_jobs; j++)
             fallback_out[j] = 0;
     if (eval_total)
-        OCHIP_HIP(ctx, hipMemcpyAsync(ctx->scratch_dev[S_EVAL], eval_order, (size_t)eval_total * 4, hipMemcpyHostToDevice,
-                                      ctx->stream));
+        OCHIP_HIP(ctx, hipMemcpyAsync(rs.eval_order, eval_order, (size_t)eval_total * 4, hipMemcpyHostToDevice, ctx->stream));
     rays_view rv{ctx->rays_dev, ctx->img_off_dev};
-    ochip_ransac_result *res_dev = (ochip_ransac_result *)ctx->scratch_dev[S_OUT];
-    uint8_t *inl_dev = (uint8_t *)ctx->scratch_dev[S_OUT] + (size_t)n_jobs * sizeof(ochip_ransac_result);
+    const ochip::ransac_scratch::outputs out = rs.outputs_of(n_jobs);
     // A pair is one wavefront from its first sample to its last evaluation, 2 048 of them at a time, and what a pair costs
     // goes with its matches (every scoring, walk and factorisation is a sweep over them): taken in the caller's order the
     // launch ended with a few long pairs that had started late - 17.3 ms for 9 000 pairs whose work fills the device for
@@ -2821,12 +2817,8 @@ int ransac_homography_impl(ochip_ctx *ctx, const ochip_ransac_job *jobs, uint32_
     // home on gfx950): 2 waves per SIMD leaves it 256 registers, 1 leaves it 512 (measured slower)
     constexpr int occ = 2;
     auto launch = [&](auto kernel) {
-        hipLaunchKernelGGL(kernel, dim3(n_jobs), dim3(W), 0, ctx->stream,
-                           (const ochip_ransac_job *)ctx->scratch_dev[S_JOBS],
-                           (const ochip_ransac_match *)ctx->scratch_dev[S_MATCH],
-                           (const uint32_t *)ctx->scratch_dev[S_SORTED], (const uint32_t *)ctx->scratch_dev[S_EVAL], rv,
-                           (double *)ctx->scratch_dev[S_COORD], (uint8_t *)ctx->scratch_dev[S_FLAGS],
-                           (double *)ctx->scratch_dev[S_P], (uint64_t)T, inlier_threshold, res_dev, inl_dev, (const uint32_t *)order_dev);
+        hipLaunchKernelGGL(kernel, dim3(n_jobs), dim3(W), 0, ctx->stream, jobs_dev, matches_dev, rs.prosac, rs.eval_order, rv, rs.coords,
+                           rs.flags, rs.lu, (uint64_t)T, inlier_threshold, out.results, out.inliers, (const uint32_t *)order_dev);
     };
     static_assert(occ == 2, "the kernel's register cap is written for two wavefronts per SIMD");
     launch(ransac_homography_kernel<2>);
@@ -2851,16 +2843,15 @@ int ransac_homography_impl(ochip_ctx *ctx, const ochip_ransac_job *jobs, uint32_
         ochip_decomposition *dec_dev = (ochip_decomposition *)mem.get((size_t)n_jobs * sizeof(ochip_decomposition));
         if (!dec_dev)
             return OCHIP_ENOMEM;
-        hipLaunchKernelGGL(decompose_vote_kernel, dim3((n_jobs + 3) / 4), dim3(256), 0, ctx->stream,
-                           (const ochip_ransac_job *)ctx->scratch_dev[S_JOBS], n_jobs, (const ochip_ransac_match *)ctx->scratch_dev[S_MATCH],
-                           (const ochip_ransac_result *)res_dev, (const uint8_t *)inl_dev, rv, dec_dev);
+        hipLaunchKernelGGL(decompose_vote_kernel, dim3((n_jobs + 3) / 4), dim3(256), 0, ctx->stream, jobs_dev, n_jobs, matches_dev, out.results,
+                           out.inliers, rv, dec_dev);
         OCHIP_HIP(ctx, hipMemcpyAsync(decomp_out, dec_dev, (size_t)n_jobs * sizeof(ochip_decomposition), hipMemcpyDeviceToHost,
                                       ctx->stream));
     }
-    OCHIP_HIP(ctx, hipMemcpyAsync(results, res_dev, (size_t)n_jobs * sizeof(ochip_ransac_result), hipMemcpyDeviceToHost,
+    OCHIP_HIP(ctx, hipMemcpyAsync(results, out.results, (size_t)n_jobs * sizeof(ochip_ransac_result), hipMemcpyDeviceToHost,
                                   ctx->stream));
     if (total_matches)
-        OCHIP_HIP(ctx, hipMemcpyAsync(inliers, inl_dev, (size_t)total_matches, hipMemcpyDeviceToHost, ctx->stream));
+        OCHIP_HIP(ctx, hipMemcpyAsync(inliers, out.inliers, (size_t)total_matches, hipMemcpyDeviceToHost, ctx->stream));
     OCHIP_HIP(ctx, ochip_stream_wait(ctx, ctx->stream));
     mem.release();
     for (uint32_t j = 0; j < n_jobs; j++)
@@ -2881,6 +2872,11 @@ int ochip_edge_lists(ochip_ctx *ctx, uint32_t n_jobs, uint64_t total_matches, co
         return OCHIP_OK;
     if (!feature_index || !inlier_offset || (total_matches && !feature_match_out) || (total_inliers && !inlier_match_out))
         return ochip_fail(ctx, OCHIP_EINVAL, "NULL argument");
+    // the kernel gathers through the jobs, correspondences and inlier flags that entry left in the scratch: any other RANSAC
+    // call on the context since then has put its own there
+    if (ctx->ransac.last != ochip::ransac_writer::homography_batch_sorted)
+        return ochip_fail(ctx, OCHIP_ESTATE, "ochip_edge_lists must follow ochip_ransac_homography_batch_sorted; the RANSAC scratch was last written by %s",
+                          writer_name(ctx->ransac.last));
     if (n_jobs != ctx->ms_pairs || n_keypoints != ctx->desc_used)
         return ochip_fail(ctx, OCHIP_ESTATE, "ochip_edge_lists must follow ochip_ransac_homography_batch_sorted of the same batch");
     OCHIP_HIP(ctx, hipSetDevice(ctx->device));
@@ -2896,11 +2892,10 @@ int ochip_edge_lists(ochip_ctx *ctx, uint32_t n_jobs, uint64_t total_matches, co
         rc = ochip_fail(ctx, OCHIP_EHIP, "upload failed (edge lists)");
     if (rc == OCHIP_OK)
     {
-        // scratch slots as ochip_ransac_homography_batch left them: 0 jobs, 1 matches, 7 results + inlier flags
-        const uint8_t *inl_dev = (const uint8_t *)ctx->scratch_dev[7] + (size_t)n_jobs * sizeof(ochip_ransac_result);
-        hipLaunchKernelGGL(edge_lists_kernel, dim3((n_jobs + 3) / 4), dim3(256), 0, st, (const ochip_ransac_job *)ctx->scratch_dev[0], n_jobs,
-                           (const ochip_ransac_match *)ctx->scratch_dev[1], inl_dev, (const uint64_t *)ctx->img_off_dev,
-                           (const double *)ctx->kp_xy_dev, (const uint32_t *)idx_dev, (const uint64_t *)off_dev, fm_dev, fmd_dev);
+        const ochip::ransac_scratch &rs = ctx->ransac;
+        hipLaunchKernelGGL(edge_lists_kernel, dim3((n_jobs + 3) / 4), dim3(256), 0, st, rs.jobs.as<ochip_ransac_job>(), n_jobs,
+                           rs.corr.as<ochip_ransac_match>(), rs.outputs_of(n_jobs).inliers, ctx->img_off_dev, ctx->kp_xy_dev, idx_dev, off_dev,
+                           fm_dev, fmd_dev);
         if (hipGetLastError() != hipSuccess ||
             (total_matches && hipMemcpyAsync(feature_match_out, fm_dev, (size_t)total_matches * sizeof(edge_feature_match),
                                              hipMemcpyDeviceToHost, st) != hipSuccess) ||
@@ -2928,59 +2923,25 @@ int ochip_refit_homography_batch(ochip_ctx *ctx, const ochip_ransac_job *jobs, u
     if (!ctx->kp_store_ready)
         return ochip_fail(ctx, OCHIP_ESTATE, "ochip_upload_keypoints has not been called");
     OCHIP_HIP(ctx, hipSetDevice(ctx->device));
-    for (uint32_t j = 0; j < n_jobs; j++)
-    {
-        const ochip_ransac_job &jb = jobs[j];
-        if (jb.image_1 >= ctx->n_images || jb.image_2 >= ctx->n_images || !ctx->kp_set[jb.image_1] || !ctx->kp_set[jb.image_2])
-            return ochip_fail(ctx, OCHIP_ESTATE, "job %u references an image without keypoints", j);
-        if (jb.match_offset + jb.n > total_matches)
-            return ochip_fail(ctx, OCHIP_EINVAL, "job %u: offsets exceed the arrays", j);
-    }
-    if (ctx->rays_dirty)
-    {
-        const uint64_t n = ctx->desc_used;
-        if (n)
-            hipLaunchKernelGGL(keypoints_to_rays_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream,
-                               ctx->kp_xy_dev, ctx->models_dev, ctx->kp_image_dev, ctx->rays_dev, n);
-        OCHIP_HIP(ctx, hipGetLastError());
-        ctx->rays_dirty = false;
-    }
-    if (ctx->img_tables_dirty)
-    {
-        OCHIP_HIP(ctx, hipMemcpyAsync(ctx->img_off_dev, ctx->img_off.data(), (size_t)ctx->n_images * 8, hipMemcpyHostToDevice,
-                                      ctx->stream));
-        OCHIP_HIP(ctx, hipMemcpyAsync(ctx->img_n_dev, ctx->img_n.data(), (size_t)ctx->n_images * 4, hipMemcpyHostToDevice,
-                                      ctx->stream));
-        ctx->img_tables_dirty = false;
-    }
+    OCHIP_TRY(prepare_homography_jobs(ctx, jobs, n_jobs, total_matches, nullptr));
     const uint64_t T = total_matches ? total_matches : 1;
-    // scratch slots as in ochip_ransac_homography_batch: 0 jobs, 1 matches, 4 coordinates, 6 LU workspaces, 7 results + flags
-    const int slot[5] = {0, 1, 4, 6, 7};
-    const size_t sizes[5] = {(size_t)n_jobs * sizeof(ochip_ransac_job), (size_t)T * sizeof(ochip_ransac_match), (size_t)T * 64,
-                             (size_t)n_jobs * 81 * 8, (size_t)n_jobs * sizeof(ochip_ransac_result) + T};
-    for (int i = 0; i < 5; i++)
-    {
-        int rc = ochip_ensure(ctx, &ctx->scratch_dev[slot[i]], &ctx->scratch_cap[slot[i]], sizes[i]);
-        if (rc)
-            return rc;
-    }
-    ochip_ransac_result *res_dev = (ochip_ransac_result *)ctx->scratch_dev[7];
-    uint8_t *inl_dev = (uint8_t *)ctx->scratch_dev[7] + (size_t)n_jobs * sizeof(ochip_ransac_result);
-    OCHIP_HIP(ctx, hipMemcpyAsync(ctx->scratch_dev[0], jobs, sizes[0], hipMemcpyHostToDevice, ctx->stream));
+    ochip::ransac_scratch &rs = ctx->ransac;
+    OCHIP_TRY(rs.ensure(ctx, ochip::ransac_writer::refit, n_jobs, sizeof(ochip_ransac_job), T, sizeof(ochip_ransac_match), 0, 0));
+    const ochip::ransac_scratch::outputs out = rs.outputs_of(n_jobs);
+    OCHIP_HIP(ctx, hipMemcpyAsync(rs.jobs, jobs, (size_t)n_jobs * sizeof(ochip_ransac_job), hipMemcpyHostToDevice, ctx->stream));
     if (total_matches)
     {
-        OCHIP_HIP(ctx, hipMemcpyAsync(ctx->scratch_dev[1], matches, (size_t)total_matches * sizeof(ochip_ransac_match),
-                                      hipMemcpyHostToDevice, ctx->stream));
-        OCHIP_HIP(ctx, hipMemcpyAsync(inl_dev, inliers, (size_t)total_matches, hipMemcpyHostToDevice, ctx->stream));
+        OCHIP_HIP(ctx, hipMemcpyAsync(rs.corr, matches, (size_t)total_matches * sizeof(ochip_ransac_match), hipMemcpyHostToDevice,
+                                      ctx->stream));
+        OCHIP_HIP(ctx, hipMemcpyAsync(out.inliers, inliers, (size_t)total_matches, hipMemcpyHostToDevice, ctx->stream));
     }
     rays_view rv{ctx->rays_dev, ctx->img_off_dev};
-    hipLaunchKernelGGL(refit_homography_kernel, dim3(n_jobs), dim3(W), 0, ctx->stream, (const ochip_ransac_job *)ctx->scratch_dev[0],
-                       (const ochip_ransac_match *)ctx->scratch_dev[1], rv, (double *)ctx->scratch_dev[4],
-                       (double *)ctx->scratch_dev[6], (uint64_t)T, inlier_threshold, rounds, res_dev, inl_dev);
+    hipLaunchKernelGGL(refit_homography_kernel, dim3(n_jobs), dim3(W), 0, ctx->stream, rs.jobs.as<ochip_ransac_job>(),
+                       rs.corr.as<ochip_ransac_match>(), rv, rs.coords, rs.lu, (uint64_t)T, inlier_threshold, rounds, out.results, out.inliers);
     OCHIP_HIP(ctx, hipGetLastError());
-    OCHIP_HIP(ctx, hipMemcpyAsync(results, res_dev, (size_t)n_jobs * sizeof(ochip_ransac_result), hipMemcpyDeviceToHost, ctx->stream));
+    OCHIP_HIP(ctx, hipMemcpyAsync(results, out.results, (size_t)n_jobs * sizeof(ochip_ransac_result), hipMemcpyDeviceToHost, ctx->stream));
     if (total_matches)
-        OCHIP_HIP(ctx, hipMemcpyAsync(inliers, inl_dev, (size_t)total_matches, hipMemcpyDeviceToHost, ctx->stream));
+        OCHIP_HIP(ctx, hipMemcpyAsync(inliers, out.inliers, (size_t)total_matches, hipMemcpyDeviceToHost, ctx->stream));
     OCHIP_HIP(ctx, ochip_stream_wait(ctx, ctx->stream));
     return OCHIP_OK;
 }
@@ -3000,10 +2961,11 @@ int ochip_debug_homography_fit4(ochip_ctx *ctx, int route, const double *xy16, u
     OCHIP_HIP(ctx, hipSetDevice(ctx->device));
     // one allocation: the samples (16 doubles each), H and H^-1 (9 each), the degeneracy flags
     const size_t in_bytes = (size_t)n * 16 * 8, m_bytes = (size_t)n * 9 * 8;
-    int rc = ochip_ensure(ctx, &ctx->scratch_dev[4], &ctx->scratch_cap[4], in_bytes + 2 * m_bytes + n);
-    if (rc)
-        return rc;
-    double *xy_dev = (double *)ctx->scratch_dev[4], *H_dev = xy_dev + (size_t)n * 16, *Hi_dev = H_dev + (size_t)n * 9;
+    ochip::dev_scratch mem{ctx, "ochip_debug_homography_fit4"};
+    double *xy_dev = (double *)mem.get(in_bytes + 2 * m_bytes + n);
+    if (!xy_dev)
+        return OCHIP_ENOMEM;
+    double *H_dev = xy_dev + (size_t)n * 16, *Hi_dev = H_dev + (size_t)n * 9;
     uint8_t *deg_dev = (uint8_t *)(Hi_dev + (size_t)n * 9);
     OCHIP_HIP(ctx, hipMemcpyAsync(xy_dev, xy16, in_bytes, hipMemcpyHostToDevice, ctx->stream));
     if (route == 0)
@@ -3016,6 +2978,7 @@ int ochip_debug_homography_fit4(ochip_ctx *ctx, int route, const double *xy16, u
     OCHIP_HIP(ctx, hipMemcpyAsync(Hinv9, Hi_dev, m_bytes, hipMemcpyDeviceToHost, ctx->stream));
     OCHIP_HIP(ctx, hipMemcpyAsync(degenerate, deg_dev, n, hipMemcpyDeviceToHost, ctx->stream));
     OCHIP_HIP(ctx, ochip_stream_wait(ctx, ctx->stream));
+    mem.release();
     return OCHIP_OK;
 }
 
@@ -3037,38 +3000,23 @@ int ochip_ransac_epipolar_batch(ochip_ctx *ctx, int model, const ochip_epipolar_
         if (jobs[j].corr_offset + jobs[j].n > total || jobs[j].eval_offset + jobs[j].n > eval_total)
             return ochip_fail(ctx, OCHIP_EINVAL, "job %u: offsets exceed the arrays", j);
     const uint64_t T = total ? total : 1;
-    const size_t sizes[8] = {(size_t)n_jobs * sizeof(ochip_epipolar_job),
-                             (size_t)T * 48,
-                             (size_t)T * 4,
-                             (size_t)(eval_total ? eval_total : 1) * 4,
-                             (size_t)T * 64,
-                             (size_t)T * 5,
-                             (size_t)n_jobs * 81 * 8,
-                             (size_t)n_jobs * sizeof(ochip_ransac_result) + T};
-    for (int i = 0; i < 8; i++)
-    {
-        const int rc = ochip_ensure(ctx, &ctx->scratch_dev[i], &ctx->scratch_cap[i], sizes[i]);
-        if (rc)
-            return rc;
-    }
+    ochip::ransac_scratch &rs = ctx->ransac;
+    OCHIP_TRY(rs.ensure(ctx, ochip::ransac_writer::epipolar, n_jobs, sizeof(ochip_epipolar_job), T, 48, eval_total, 5));
     hipStream_t st = ctx->stream;
-    OCHIP_HIP(ctx, hipMemcpyAsync(ctx->scratch_dev[0], jobs, sizes[0], hipMemcpyHostToDevice, st));
+    OCHIP_HIP(ctx, hipMemcpyAsync(rs.jobs, jobs, (size_t)n_jobs * sizeof(ochip_epipolar_job), hipMemcpyHostToDevice, st));
     if (total)
     {
-        OCHIP_HIP(ctx, hipMemcpyAsync(ctx->scratch_dev[1], corr6, (size_t)total * 48, hipMemcpyHostToDevice, st));
-        OCHIP_HIP(ctx, hipMemcpyAsync(ctx->scratch_dev[2], sorted_idx, (size_t)total * 4, hipMemcpyHostToDevice, st));
+        OCHIP_HIP(ctx, hipMemcpyAsync(rs.corr, corr6, (size_t)total * 48, hipMemcpyHostToDevice, st));
+        OCHIP_HIP(ctx, hipMemcpyAsync(rs.prosac, sorted_idx, (size_t)total * 4, hipMemcpyHostToDevice, st));
     }
     if (eval_total)
-        OCHIP_HIP(ctx, hipMemcpyAsync(ctx->scratch_dev[3], eval_order, (size_t)eval_total * 4, hipMemcpyHostToDevice, st));
-    ochip_ransac_result *res_dev = (ochip_ransac_result *)ctx->scratch_dev[7];
-    uint8_t *inl_dev = (uint8_t *)ctx->scratch_dev[7] + (size_t)n_jobs * sizeof(ochip_ransac_result);
+        OCHIP_HIP(ctx, hipMemcpyAsync(rs.eval_order, eval_order, (size_t)eval_total * 4, hipMemcpyHostToDevice, st));
+    const ochip::ransac_scratch::outputs out = rs.outputs_of(n_jobs);
     hipEvent_t e0, e1;
     ochip_prof_begin(ctx, OCHIP_K_RANSAC, &e0, &e1);
     auto launch = [&](auto kernel) {
-        hipLaunchKernelGGL(kernel, dim3(n_jobs), dim3(W), 0, st, (const ochip_epipolar_job_dev *)ctx->scratch_dev[0],
-                           (const double *)ctx->scratch_dev[1], (const uint32_t *)ctx->scratch_dev[2], (const uint32_t *)ctx->scratch_dev[3],
-                           (double *)ctx->scratch_dev[4], (uint8_t *)ctx->scratch_dev[5], (double *)ctx->scratch_dev[6], (uint64_t)T,
-                           inlier_threshold, res_dev, inl_dev);
+        hipLaunchKernelGGL(kernel, dim3(n_jobs), dim3(W), 0, st, rs.jobs.as<ochip_epipolar_job_dev>(), rs.corr.as<double>(), rs.prosac,
+                           rs.eval_order, rs.coords, rs.flags, rs.lu, (uint64_t)T, inlier_threshold, out.results, out.inliers);
     };
     if (model == 0)
         launch(ransac_epipolar_kernel<8, false>);
@@ -3076,9 +3024,9 @@ int ochip_ransac_epipolar_batch(ochip_ctx *ctx, int model, const ochip_epipolar_
         launch(ransac_epipolar_kernel<5, true>);
     ochip_prof_end(ctx, OCHIP_K_RANSAC, e0, e1);
     OCHIP_HIP(ctx, hipGetLastError());
-    OCHIP_HIP(ctx, hipMemcpyAsync(results, res_dev, (size_t)n_jobs * sizeof(ochip_ransac_result), hipMemcpyDeviceToHost, st));
+    OCHIP_HIP(ctx, hipMemcpyAsync(results, out.results, (size_t)n_jobs * sizeof(ochip_ransac_result), hipMemcpyDeviceToHost, st));
     if (total)
-        OCHIP_HIP(ctx, hipMemcpyAsync(inliers, inl_dev, (size_t)total, hipMemcpyDeviceToHost, st));
+        OCHIP_HIP(ctx, hipMemcpyAsync(inliers, out.inliers, (size_t)total, hipMemcpyDeviceToHost, st));
     OCHIP_HIP(ctx, ochip_stream_wait(ctx, st));
     return OCHIP_OK;
 }

@@ -121,3 +121,71 @@ def test_link_and_relax_with_lens_distortion(ctx, oracle):
     assert np.all(2 * np.arccos(np.clip(dots, 0, 1)) < 1e-6)
     assert int(got["residual_blocks"]) == exp["residual_blocks"] > 0
     g.close()
+
+
+def _edge_signature(g):
+    return [(e["source"], e["dest"], e["n_matches"], e["n_inliers"], e["H"].tobytes(), e["f1"].tobytes(), e["f2"].tobytes(),
+             e["poses"].tobytes()) for e in g.edges()]
+
+
+def _two_view_rays(n, seed):
+    """n points in front of two cameras a small rotation and a baseline apart, as unit rays: n x 6"""
+    rng = np.random.default_rng(seed)
+    X = np.concatenate([rng.uniform(-2, 2, (n, 2)), rng.uniform(4, 9, (n, 1))], 1)
+    c, s = np.cos(0.1), np.sin(0.1)
+    Y = (X - (0.7, 0.1, 0.0)) @ np.array([[c, 0, s], [0, 1, 0], [-s, 0, c]]).T
+    return np.concatenate([X / np.linalg.norm(X, axis=1, keepdims=True), Y / np.linalg.norm(Y, axis=1, keepdims=True)], 1)
+
+
+def _linked(ctx, grid):
+    g = host.Graph.from_synthetic(grid)
+    g.link(ctx)
+    return g
+
+
+def _refit(ctx, g, grid):
+    new_model = grid.model.copy()
+    new_model[0] *= 1.02
+    new_model[1] += 7.5
+    g.set_model(0, new_model)
+    g.refit_edges(ctx)
+    return [e["H"].tobytes() for e in g.edges()]
+
+
+@pytest.mark.parametrize("hooks", ["", "host_sort"])
+def test_small_large_small_batches_on_one_context(monkeypatch, hooks):
+    """The context's device arrays only grow, and growth drops their contents: a small survey, a larger one (every array
+    grows), its refit, an epipolar RANSAC (other structs in the RANSAC scratch) and the small survey again on ONE context
+    must give what each gives on a context of its own, byte for byte - with the device's sort and PROSAC order
+    (ochip_ransac_homography_batch_sorted, ochip_edge_lists) and with the host's (ochip_ransac_homography_batch)."""
+    if hooks:
+        monkeypatch.setenv("OCHIP_TEST_HOOKS", hooks)
+    small, large = synth.make_grid(1, 2, feats=200, seed=3), synth.make_grid(2, 3, feats=512, seed=21)
+    rays = _two_view_rays(100, 4)
+    expect = []
+    for grid in (small, large):
+        fresh = capi.Context(0)
+        g = _linked(fresh, grid)
+        expect.append((_edge_signature(g), _refit(fresh, g, grid)))
+        g.close()
+        fresh.close()
+    fresh = capi.Context(0)
+    expect_epipolar = host.ransac_epipolar(fresh, 1, rays)
+    fresh.close()
+    assert len(expect[0][0]) == 2 and len(expect[1][0]) == 30
+
+    ctx = capi.Context(0)
+    g = _linked(ctx, small)
+    assert _edge_signature(g) == expect[0][0]
+    g.close()
+    g = _linked(ctx, large)
+    assert _edge_signature(g) == expect[1][0]
+    assert _refit(ctx, g, large) == expect[1][1]
+    g.close()
+    got = host.ransac_epipolar(ctx, 1, rays)
+    assert got[0] == expect_epipolar[0] and np.array_equal(got[1], expect_epipolar[1], equal_nan=True)
+    assert np.array_equal(got[2], expect_epipolar[2]) and got[3:] == expect_epipolar[3:]
+    g = _linked(ctx, small)
+    assert _edge_signature(g) == expect[0][0]
+    g.close()
+    ctx.close()
