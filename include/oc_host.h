@@ -370,6 +370,39 @@ extern "C"
     void och_surface_locate(const och_surface *s, const double *xy, size_t n, uint64_t *tri3);
     int och_mesh_refinement_run(och_graph *g, ochip_ctx *ctx, och_surface *surface, int max_steps, double *log8);
 
+    /* ---- points per triangle over the flat locate table, and the DENSE_MESH_RELAX state (opencalibration_amd/csrc/host/
+     *      mesh_points.hpp, csrc/mesh_locate.hpp; src/pipeline/pipeline.cpp:844-924) ----------
+     * The two entries above stay as they are; these give the same rows bit for bit by another route: the mesh flattened
+     * into a locate table, every point located by nearest centroid and a walk of at most max_steps triangles (100 where
+     * no argument says otherwise; a point whose steps run out is found by the exhaustive scan on the host), the sums in
+     * point order.  ctx == NULL: that route in host loops (locate under OpenMP); else on the device (ochip_mesh_points_*
+     * of ochip.h), the cloud uploaded once per call or per counter.  och_surface_count_points returns SIZE_MAX and
+     * och_surface_locate_on -1 on a device error, with the text in och_points_last_error() (per thread).
+     * och_point_counter: a cloud (xyz [n][3]) kept for counts against changing meshes - what refineByPointDensity and the
+     * state use between their iterations; count: the rows for the surface's mesh (its own clouds are not read),
+     * exhausted (may be NULL): how many points ran out of steps.  create returns NULL on a device error.
+     * och_surface_locate_table: the flat table of the surface's mesh as arrays - sizes2 = {T, entries of start};
+     * vertex_xy [T][6], neighbours [T][3] (0xFFFFFFFF: none), plane [T][6], cx, cy [T], grid4 = {x0, y0, cell, nx},
+     * start [sizes2[1]], items [T].
+     * och_dense_mesh_relax_run: the DENSE_MESH_RELAX state - gsd and reduced gsd at grid fraction 0.05, one
+     * refineByPointDensity(mesh, cloud, 20, (2 gsd)^2, 1, reduced gsd), repeat while triangles were created, at most 21
+     * runs - repeated until the state is left or max_steps runs were made; surface: in = the densified surface, out = the
+     * refined one (a surface without mesh and cloud stands for an empty surface list).  log6 rows {run, gsd, reduced gsd,
+     * triangles above threshold, triangles created, mesh vertices}.  Returns the steps made, -1 + och_last_error(g) on a
+     * device error.  With a context the cloud crosses to the device once per call. */
+    typedef struct och_point_counter och_point_counter;
+    const char *och_points_last_error(void);
+    size_t och_surface_count_points(const och_surface *s, ochip_ctx *ctx, uint64_t *tri3, double *stats2, size_t cap);
+    int och_surface_locate_on(const och_surface *s, ochip_ctx *ctx, const double *xy, size_t n, int max_steps, uint64_t *tri3);
+    och_point_counter *och_point_counter_create(ochip_ctx *ctx, const double *xyz, size_t n, int max_steps);
+    void och_point_counter_destroy(och_point_counter *c);
+    size_t och_point_counter_count(och_point_counter *c, const och_surface *s, uint64_t *tri3, double *stats2, size_t cap,
+                                   uint64_t *exhausted);
+    void och_surface_locate_table_sizes(const och_surface *s, uint64_t *sizes2);
+    void och_surface_locate_table(const och_surface *s, double *vertex_xy, uint32_t *neighbours, double *plane, double *cx, double *cy,
+                                  double *grid4, uint32_t *start, uint32_t *items);
+    int och_dense_mesh_relax_run(och_graph *g, ochip_ctx *ctx, och_surface *surface, int max_steps, double *log6);
+
     /* ---- orthomosaic preview and DSM raster (opencalibration_amd/csrc/host/ortho.hpp; src/ortho/ortho.cpp:228-964) -------
      * The reference's context: calculateBoundsAndMeanZ (bounds5 = min_x, max_x, min_y, max_y, mean_surface_z; a surface's
      * clouds count only when it has no mesh), calculateGSD over the given nodes in the given order (thumbnail != 0: the

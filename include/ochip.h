@@ -923,6 +923,50 @@ extern "C"
     int ochip_ortho_overviews_finish(ochip_ortho_overviews *o);
     void ochip_ortho_overviews_destroy(ochip_ortho_overviews *o);
 
+    /* ---- points per triangle of a surface mesh (opencalibration_amd/csrc/mesh_points.hip, the rule in
+     *      csrc/mesh_locate.hpp; the reference's countPointsPerTriangle, src/surface/refine_mesh.cpp:713-825, the expensive
+     *      part of the DENSE_MESH_RELAX state) ----
+     * The object holds a cloud, xyz [n][3] fp64 (n < 2^32; n = 0 is valid), uploaded once by create; the mesh changes from
+     * count to count and arrives as a flat locate table (host arrays, built by the host library from a mesh and an edge
+     * order): per located triangle the x, y of its vertices [T][6], its neighbours [T][3] as triangle indices or
+     * OCHIP_LOCATE_NONE, its plane [T][6] (origin, unit normal), its centroid, and the centroids' bucket grid of nx x nx
+     * cells (start: n_start = nx * nx + 1 offsets into items, n_items = T triangle indices).
+     * count: every point is located - nearest centroid, then a walk of at most max_steps triangles - and per triangle come
+     * back the number of its points, the index of its first point (OCHIP_LOCATE_NONE without one), and sum and sum of
+     * squares of the points' signed plane distances added in ascending point index, bit for bit what a sequential host
+     * loop gives.  A point whose steps ran out is in none of these: its index comes back in `exhausted` (ascending;
+     * exhausted_cap entries, n is always enough) and the caller resolves it by scanning the mesh.  Nothing is carried from
+     * one count to the next except the answer of `where`: the last count's per-point result (triangle index,
+     * OCHIP_LOCATE_NONE outside the mesh, OCHIP_LOCATE_EXHAUSTED | the triangle the walk stood on).
+     * The table is checked before anything is launched: OCHIP_EINVAL and a message for a neighbour or an item >= T, a
+     * start that is not monotone from 0 to T, a grid side outside 1 .. 1024, a NULL array.  OCHIP_EINVAL too for a handle
+     * that create did not return or destroy has taken (then the message is ochip_last_error(NULL)'s).  The calls wait for
+     * the context's stream; destroy hands the device blocks back to the context's pool. */
+#define OCHIP_LOCATE_NONE 0xFFFFFFFFu
+#define OCHIP_LOCATE_EXHAUSTED 0x80000000u
+    typedef struct ochip_locate_table
+    {
+        uint32_t n_triangles; /* T */
+        const double *vertex_xy;
+        const uint32_t *neighbours;
+        const double *plane;
+        const double *centroid_x, *centroid_y;
+        double x0, y0, cell;
+        int32_t nx;
+        const uint32_t *start;
+        size_t n_start;
+        const uint32_t *items;
+        size_t n_items;
+    } ochip_locate_table;
+    typedef struct ochip_mesh_points ochip_mesh_points;
+    int ochip_mesh_points_create(ochip_ctx *ctx, const double *xyz, uint64_t n, ochip_mesh_points **out);
+    uint64_t ochip_mesh_points_size(const ochip_mesh_points *m); /* n; 0 for a handle that is not live */
+    int ochip_mesh_points_count(ochip_mesh_points *m, const ochip_locate_table *table, int max_steps, uint32_t *count /* [T] */,
+                                uint32_t *first /* [T] */, double *sum /* [T] */, double *sum_sq /* [T] */, uint32_t *exhausted,
+                                uint64_t exhausted_cap, uint64_t *n_exhausted);
+    int ochip_mesh_points_where(ochip_mesh_points *m, uint32_t *where /* [n] */);
+    void ochip_mesh_points_destroy(ochip_mesh_points *m);
+
 #ifdef __cplusplus
 }
 #endif

@@ -48,6 +48,8 @@ EXPORTS = [
     "ochip_thumbnail_size", "ochip_image_thumbnails", "ochip_debug_lab_table",
     "ochip_ortho_overviews_levels", "ochip_ortho_overviews_create", "ochip_ortho_overviews_feed",
     "ochip_ortho_overviews_complete_rows", "ochip_ortho_overviews_finish", "ochip_ortho_overviews_destroy",
+    "ochip_mesh_points_create", "ochip_mesh_points_size", "ochip_mesh_points_count", "ochip_mesh_points_where",
+    "ochip_mesh_points_destroy",
 ]
 
 _lib = None
@@ -197,6 +199,13 @@ def relaxp_desc(scene):
     return d, keep
 
 
+class LocateTable(C.Structure):
+    """ochip_locate_table (include/ochip.h)."""
+    _fields_ = [("n_triangles", C.c_uint32), ("vertex_xy", C.c_void_p), ("neighbours", C.c_void_p), ("plane", C.c_void_p),
+                ("centroid_x", C.c_void_p), ("centroid_y", C.c_void_p), ("x0", C.c_double), ("y0", C.c_double), ("cell", C.c_double),
+                ("nx", C.c_int32), ("start", C.c_void_p), ("n_start", C.c_size_t), ("items", C.c_void_p), ("n_items", C.c_size_t)]
+
+
 class OchipError(RuntimeError):
     pass
 
@@ -262,6 +271,13 @@ def load():
         L.ochip_ortho_overviews_finish.argtypes = [vp]
         L.ochip_ortho_overviews_destroy.argtypes = [vp]
         L.ochip_ortho_overviews_destroy.restype = None
+        L.ochip_mesh_points_create.argtypes = [vp, vp, u64, C.POINTER(vp)]
+        L.ochip_mesh_points_size.argtypes = [vp]
+        L.ochip_mesh_points_size.restype = u64
+        L.ochip_mesh_points_count.argtypes = [vp, C.POINTER(LocateTable), i32, vp, vp, vp, vp, vp, u64, C.POINTER(u64)]
+        L.ochip_mesh_points_where.argtypes = [vp, vp]
+        L.ochip_mesh_points_destroy.argtypes = [vp]
+        L.ochip_mesh_points_destroy.restype = None
         _lib = L
     return _lib
 
@@ -288,6 +304,44 @@ class RcclComm:
     def close(self):
         if self.h:
             self.ctx.L.ochip_rccl_comm_destroy(self.h)
+            self.h = C.c_void_p()
+
+
+class MeshPoints:
+    """ochip_mesh_points: a cloud on the device, counted against flat locate tables (host.Surface.locate_table())."""
+
+    def __init__(self, ctx, xyz):
+        self.ctx, self.L = ctx, ctx.L
+        xyz = np.ascontiguousarray(xyz, np.float64).reshape(-1, 3)
+        self.n = len(xyz)
+        self.h = C.c_void_p()
+        ctx._check(self.L.ochip_mesh_points_create(ctx.h, xyz.ctypes.data if self.n else None, self.n, C.byref(self.h)),
+                   "ochip_mesh_points_create")
+        self.raw = self.h.value # kept after close(): what a caller that held on to the handle would pass
+
+    def count(self, table, max_steps=100, handle=None):
+        """Per triangle count, first point, sum, sum of squares; the exhausted points; the per-point result."""
+        T = len(table["vertex_xy"])
+        keep = {k: np.ascontiguousarray(table[k]) for k in ("vertex_xy", "neighbours", "plane", "cx", "cy", "start", "items")}
+        ptr = lambda a: a.ctypes.data if a.size else None
+        t = LocateTable(T, ptr(keep["vertex_xy"]), ptr(keep["neighbours"]), ptr(keep["plane"]), ptr(keep["cx"]), ptr(keep["cy"]),
+                        table["x0"], table["y0"], table["cell"], table["nx"], ptr(keep["start"]), len(keep["start"]), ptr(keep["items"]),
+                        len(keep["items"]))
+        count, first = np.zeros(max(T, 1), np.uint32), np.zeros(max(T, 1), np.uint32)
+        s, ss, ex, nex = np.zeros(max(T, 1)), np.zeros(max(T, 1)), np.zeros(max(self.n, 1), np.uint32), C.c_uint64(0)
+        h = self.h if handle is None else C.c_void_p(handle)
+        rc = self.L.ochip_mesh_points_count(h, C.byref(t), max_steps, count.ctypes.data, first.ctypes.data, s.ctypes.data, ss.ctypes.data,
+                                            ex.ctypes.data, len(ex), C.byref(nex))
+        if rc != 0:
+            text = self.L.ochip_last_error(self.ctx.h).decode() + " | " + self.L.ochip_last_error(None).decode()
+            raise OchipError(f"ochip_mesh_points_count = {rc}: {text}")
+        where = np.zeros(max(self.n, 1), np.uint32)
+        self.ctx._check(self.L.ochip_mesh_points_where(h, where.ctypes.data), "ochip_mesh_points_where")
+        return dict(count=count[:T], first=first[:T], sum=s[:T], sum_sq=ss[:T], exhausted=ex[:nex.value], where=where[:self.n])
+
+    def close(self):
+        if self.h:
+            self.L.ochip_mesh_points_destroy(self.h)
             self.h = C.c_void_p()
 
 

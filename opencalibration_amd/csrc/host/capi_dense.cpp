@@ -42,8 +42,11 @@ uint32_t och_hilbert_xy2d(int order, int x, int y)
 
 } // extern "C"
 
-// ---- mesh refinement (refine_mesh.hpp)
+// ---- mesh refinement (refine_mesh.hpp, mesh_points.hpp)
+#include "mesh_points.hpp"
 #include "refine_mesh.hpp"
+
+#include <algorithm>
 
 extern "C"
 {
@@ -126,6 +129,157 @@ int och_mesh_refinement_run(och_graph *g, ochip_ctx *ctx, och_surface *surface, 
     }
     surface->s = surfaces.empty() ? surface_model() : surfaces[0];
     return steps;
+}
+
+/* ---- the flat locate table and its two routes (mesh_points.hpp) */
+namespace
+{
+size_t rows_out(const MeshGraph &mesh, const TrianglePointRows &rows, uint64_t *tri3, double *stats2, size_t cap)
+{
+    TriangleLocator loc(mesh);
+    for (size_t i = 0; i < rows.size() && i < cap; i++)
+    {
+        size_t v[3] = {0, 0, 0};
+        loc.vertices(rows[i].first, v);
+        for (int k = 0; k < 3; k++)
+            tri3[3 * i + k] = v[k];
+        stats2[2 * i] = (double)rows[i].second.count;
+        stats2[2 * i + 1] = rows[i].second.distanceVariance;
+    }
+    return rows.size();
+}
+thread_local std::string g_points_error;
+} // namespace
+
+struct och_point_counter
+{
+    MeshPointsCounter c;
+    och_point_counter(ochip_ctx *ctx, const double *xyz, size_t n, int max_steps) : c(ctx, xyz, n, max_steps) {}
+};
+
+const char *och_points_last_error(void)
+{
+    return g_points_error.c_str();
+}
+
+size_t och_surface_count_points(const och_surface *s, ochip_ctx *ctx, uint64_t *tri3, double *stats2, size_t cap)
+{
+    MeshPointsCounter counter(ctx, s->s.cloud);
+    const auto rows = counter.count(s->s.mesh);
+    if (counter.failed())
+    {
+        g_points_error = counter.error();
+        return SIZE_MAX;
+    }
+    return rows_out(s->s.mesh, rows, tri3, stats2, cap);
+}
+
+int och_surface_locate_on(const och_surface *s, ochip_ctx *ctx, const double *xy, size_t n, int max_steps, uint64_t *tri3)
+{
+    std::vector<double> xyz(3 * n, 0.0);
+    for (size_t i = 0; i < n; i++)
+        xyz[3 * i] = xy[2 * i], xyz[3 * i + 1] = xy[2 * i + 1];
+    MeshPointsCounter counter(ctx, xyz.data(), n, max_steps);
+    std::vector<TriangleId> where;
+    if (!counter.locate(s->s.mesh, &where))
+    {
+        g_points_error = counter.error();
+        return -1;
+    }
+    TriangleLocator loc(s->s.mesh);
+    for (size_t i = 0; i < n; i++)
+    {
+        size_t v[3];
+        const bool ok = where[i].edgeId != MeshEdge::NONE && loc.vertices(where[i], v);
+        for (int k = 0; k < 3; k++)
+            tri3[3 * i + k] = ok ? v[k] : UINT64_MAX;
+    }
+    return 0;
+}
+
+och_point_counter *och_point_counter_create(ochip_ctx *ctx, const double *xyz, size_t n, int max_steps)
+{
+    och_point_counter *c = new och_point_counter(ctx, xyz, n, max_steps);
+    if (!c->c.failed())
+        return c;
+    g_points_error = c->c.error();
+    delete c;
+    return nullptr;
+}
+
+void och_point_counter_destroy(och_point_counter *c)
+{
+    delete c;
+}
+
+size_t och_point_counter_count(och_point_counter *c, const och_surface *s, uint64_t *tri3, double *stats2, size_t cap, uint64_t *exhausted)
+{
+    const auto rows = c->c.count(s->s.mesh);
+    if (c->c.failed())
+    {
+        g_points_error = c->c.error();
+        return SIZE_MAX;
+    }
+    if (exhausted)
+        *exhausted = c->c.last_exhausted();
+    return rows_out(s->s.mesh, rows, tri3, stats2, cap);
+}
+
+void och_surface_locate_table_sizes(const och_surface *s, uint64_t *sizes2)
+{
+    FlatLocateTable tab;
+    TriangleLocator(s->s.mesh).flatten(tab);
+    sizes2[0] = tab.tri.size(), sizes2[1] = tab.start.size();
+}
+
+void och_surface_locate_table(const och_surface *s, double *vertex_xy, uint32_t *neighbours, double *plane, double *cx, double *cy,
+                              double *grid4, uint32_t *start, uint32_t *items)
+{
+    FlatLocateTable tab;
+    TriangleLocator(s->s.mesh).flatten(tab);
+    std::copy(tab.vxy.begin(), tab.vxy.end(), vertex_xy);
+    std::copy(tab.nbr.begin(), tab.nbr.end(), neighbours);
+    std::copy(tab.plane.begin(), tab.plane.end(), plane);
+    std::copy(tab.cx.begin(), tab.cx.end(), cx);
+    std::copy(tab.cy.begin(), tab.cy.end(), cy);
+    grid4[0] = tab.x0, grid4[1] = tab.y0, grid4[2] = tab.cell, grid4[3] = tab.nx;
+    std::copy(tab.start.begin(), tab.start.end(), start);
+    std::copy(tab.items.begin(), tab.items.end(), items);
+}
+
+/* Pipeline::Impl::dense_mesh_relax (src/pipeline/pipeline.cpp:844-924) repeated until it leaves the state or max_steps runs
+ * were made; surface: the pipeline's one surface (a surface without mesh and cloud: an empty surface list). */
+int och_dense_mesh_relax_run(och_graph *g, ochip_ctx *ctx, och_surface *surface, int max_steps, double *log6)
+{
+    std::vector<surface_model> surfaces;
+    if (surface->s.mesh.size_nodes() > 0 || !surface->s.cloud.empty())
+        surfaces.push_back(std::move(surface->s));
+    DenseMeshRelaxState state;
+    int steps = 0;
+    bool ok = true;
+    while (steps < max_steps)
+    {
+        Transition t;
+        std::string why;
+        const uint64_t run = state.run_count;
+        if (!dense_mesh_relax_step(ctx, g->graph, surfaces, state, &t, &why))
+        {
+            g->error = why;
+            ok = false;
+            break;
+        }
+        if (log6)
+        {
+            double *row = log6 + 6 * steps;
+            row[0] = (double)run, row[1] = state.gsd, row[2] = state.reduced_gsd, row[3] = (double)state.triangles_above_threshold;
+            row[4] = (double)state.refined, row[5] = surfaces.empty() ? 0.0 : (double)surfaces[0].mesh.size_nodes();
+        }
+        steps++;
+        if (t == Transition::NEXT)
+            break;
+    }
+    surface->s = surfaces.empty() ? surface_model() : std::move(surfaces[0]);
+    return ok ? steps : -1;
 }
 
 } // extern "C"

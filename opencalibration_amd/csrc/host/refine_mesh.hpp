@@ -10,6 +10,7 @@
 // the edge ids a refinement leaves behind are 0 .. n-1 in iteration order; ids are opaque in the reference).
 #pragma once
 
+#include "../mesh_locate.hpp"
 #include "relax_mesh.hpp"
 #include "relax_stage.hpp"
 
@@ -31,6 +32,19 @@ struct TrianglePointStats // refine_mesh.hpp
     double distanceVariance = 0;
 };
 
+// What a TriangleLocator holds as plain arrays (csrc/mesh_locate.hpp): the table nearest_centroid and walk read on either
+// side.  tri: the located triangles in table order; index_of: 2 * edge id + side -> table index or ochip_ml::NONE.
+struct FlatLocateTable
+{
+    std::vector<TriangleId> tri;
+    std::vector<uint32_t> index_of;
+    std::vector<double> vxy, plane, cx, cy;
+    std::vector<uint32_t> nbr, start, items;
+    double x0 = 0, y0 = 0, cell = 1;
+    int nx = 1;
+    ochip_ml::table view() const;
+};
+
 // TriangleLocator (refine_mesh.cpp:572-711): the triangle under a point - from the triangle with the nearest centroid
 // across the most violated edge, at most 100 steps, then the exhaustive scan.
 class TriangleLocator
@@ -39,9 +53,12 @@ class TriangleLocator
     explicit TriangleLocator(const MeshGraph &m, const std::vector<size_t> *edge_order = nullptr);
     TriangleId find(double x, double y) const;
     bool vertices(const TriangleId &t, size_t v[3]) const;
+    // the exhaustive scan in edge order: what find falls back to when its steps run out
+    TriangleId brute_force(double x, double y) const;
+    // the flat table of this locator: vertices, neighbours as find resolves them, countPointsPerTriangle's planes, the grid
+    void flatten(FlatLocateTable &out) const;
 
   private:
-    TriangleId brute_force(double x, double y) const;
     const MeshGraph &_m;
     std::vector<size_t> _order;
     std::vector<TriangleId> _tri;
@@ -57,11 +74,28 @@ class TriangleLocator
 // reference does with one thread - with more its accumulation order is whatever the threads' finishing order is).
 std::vector<std::pair<TriangleId, TrianglePointStats>> countPointsPerTriangle(const MeshGraph &mesh, const std::vector<point_cloud> &points);
 
+// Who counts for refineByPointDensity: the rows of countPointsPerTriangle for a mesh whose edges are iterated in `order`
+// (ids of live edges).  A counter owns its points - host/mesh_points.hpp's keeps the cloud on the device from one iteration
+// and one run of the state to the next.  A counter that fails returns no rows and says so in failed().
+using TrianglePointRows = std::vector<std::pair<TriangleId, TrianglePointStats>>;
+struct PointCounter
+{
+    virtual ~PointCounter() = default;
+    virtual TrianglePointRows count(const MeshGraph &mesh, const std::vector<size_t> &order) = 0;
+    virtual bool failed() const
+    {
+        return false;
+    }
+};
+
 // refineByPointDensity (:827-909): bisects (longest edge, neighbour first) every triangle with more than
 // maxPointsPerTriangle points whose distance variance exceeds minDistanceVariance and whose longest side is at least
-// minTriangleSizeMeters.  Returns the number of triangles created.
+// minTriangleSizeMeters.  Returns the number of triangles created.  counter == nullptr: `points` counted on the host as
+// ever; else the counter's points (`points` is not read) - an iteration whose count failed ends the loop.  aboveThreshold
+// (diagnostic): the triangles of the first iteration over both thresholds, whatever their size.
 size_t refineByPointDensity(MeshGraph &mesh, const std::vector<point_cloud> &points, size_t maxPointsPerTriangle,
-                            double minDistanceVariance = 0.0, int maxIterations = 10, double minTriangleSizeMeters = 0.0);
+                            double minDistanceVariance = 0.0, int maxIterations = 10, double minTriangleSizeMeters = 0.0,
+                            PointCounter *counter = nullptr, size_t *aboveThreshold = nullptr);
 // refineAtPoint (:452-473): `levels` rounds of refining the triangle under (x, y)
 size_t refineAtPoint(MeshGraph &mesh, double x, double y, int levels = 1);
 
@@ -85,5 +119,27 @@ enum class Transition
 // is the pipeline's surface list; `stage` its RelaxStage (keeps the previous surfaces).  false + error on a device error.
 bool mesh_refinement_step(ochip_ctx *ctx, MeasurementGraph &graph, std::vector<surface_model> &surfaces, RelaxStage &stage,
                           MeshRefinementState &state, Transition *transition, std::string *error);
+
+
+// Pipeline::Impl::dense_mesh_relax (pipeline.cpp:844-924) as a step function: gsd and reduced gsd (grid fraction 0.05) from
+// the surfaces' mean height and the cameras, one refineByPointDensity(mesh, cloud, 20, (2 gsd)^2, 1, reducedGsd) per surface
+// that has nodes; REPEAT while triangles were created, unless this was run 20 (MESH_REFINEMENT_MAX_ITERATIONS) or later.
+struct DenseMeshRelaxState
+{
+    uint64_t run_count = 0; // stateRunCount()
+    // with a context: one counter per surface (host/mesh_points.hpp), made by the state's first run from the surface's
+    // clouds - which the state does not change - and kept, so that a cloud crosses to the device once
+    std::vector<std::unique_ptr<PointCounter>> counters;
+    // diagnostics of the last step (not in the reference)
+    double gsd = 0, reduced_gsd = 0;
+    size_t triangles_above_threshold = 0, refined = 0;
+};
+// The state's gsd block, shared with MESH_REFINEMENT: {gsd, reducedGsd} for a grid fraction (0.01 and 0 without a usable camera)
+void surface_gsd(const MeasurementGraph &graph, const std::vector<surface_model> &surfaces, size_t maxPointsPerTriangle, double gridFraction,
+                 double *gsd, double *reducedGsd);
+// ctx == nullptr: the points are counted on the host as MESH_REFINEMENT counts them; else on the device.  false + error
+// on a device error.
+bool dense_mesh_relax_step(ochip_ctx *ctx, MeasurementGraph &graph, std::vector<surface_model> &surfaces, DenseMeshRelaxState &state,
+                           Transition *transition, std::string *error);
 
 } // namespace opencalibration_amd

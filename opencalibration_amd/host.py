@@ -201,6 +201,21 @@ def load():
         L.och_surface_locate.argtypes = [vp, _f64p, sz, _u64p]
         L.och_surface_locate.restype = None
         L.och_mesh_refinement_run.argtypes = [vp, vp, vp, C.c_int, _f64p]
+        L.och_points_last_error.restype = C.c_char_p
+        L.och_surface_count_points.argtypes = [vp, vp, _u64p, _f64p, sz]
+        L.och_surface_count_points.restype = sz
+        L.och_surface_locate_on.argtypes = [vp, vp, _f64p, sz, C.c_int, _u64p]
+        L.och_point_counter_create.argtypes = [vp, _f64p, sz, C.c_int]
+        L.och_point_counter_create.restype = vp
+        L.och_point_counter_destroy.argtypes = [vp]
+        L.och_point_counter_destroy.restype = None
+        L.och_point_counter_count.argtypes = [vp, vp, _u64p, _f64p, sz, _u64p]
+        L.och_point_counter_count.restype = sz
+        L.och_surface_locate_table_sizes.argtypes = [vp, _u64p]
+        L.och_surface_locate_table_sizes.restype = None
+        L.och_surface_locate_table.argtypes = [vp] + [vp] * 8
+        L.och_surface_locate_table.restype = None
+        L.och_dense_mesh_relax_run.argtypes = [vp, vp, vp, C.c_int, _f64p]
         L.och_shard_block.argtypes = [u32, u32, u32, C.POINTER(u32), C.POINTER(u32)]
         L.och_shard_block.restype = None
         L.och_shard_begin.restype = vp
@@ -459,18 +474,48 @@ class Surface:
     def refine_at_point(self, x, y, levels=1):
         return self.L.och_refine_at_point(self.h, x, y, levels)
 
-    def count_points_per_triangle(self):
-        """countPointsPerTriangle: (vertices n x 3, counts n, distance variances n) in first-point order."""
+    def count_points_per_triangle(self, ctx=None, flat=False):
+        """countPointsPerTriangle: (vertices n x 3, counts n, distance variances n) in first-point order.  flat=True: by
+        the flat locate table in host loops; ctx: by that table on the device - the same rows."""
         cap = 2 * max(len(self.arrays()["edges"]), 1)
         tri, st = np.zeros((cap, 3), np.uint64), np.zeros((cap, 2))
-        n = self.L.och_count_points_per_triangle(self.h, tri, st, cap)
+        if ctx is None and not flat:
+            n = self.L.och_count_points_per_triangle(self.h, tri, st, cap)
+        else:
+            n = self.L.och_surface_count_points(self.h, ctx.h if ctx is not None else None, tri, st, cap)
+            if n == C.c_size_t(-1).value:
+                raise capi.OchipError("count_points_per_triangle failed: " + self.L.och_points_last_error().decode())
         return tri[:n], st[:n, 0].astype(np.int64), st[:n, 1]
 
-    def locate(self, xy):
+    def locate(self, xy, ctx=None, max_steps=None, flat=False):
+        """The triangle under every point (three vertices, 0xFFFFFFFFFFFFFFFF x 3 outside).  flat=True or max_steps: by the
+        flat locate table in host loops, a walk of at most max_steps (100) triangles and then the exhaustive scan; ctx: the
+        same on the device."""
         xy = np.ascontiguousarray(xy, np.float64).reshape(-1, 2)
         tri = np.zeros((max(len(xy), 1), 3), np.uint64)
-        self.L.och_surface_locate(self.h, xy if len(xy) else np.zeros((1, 2)), len(xy), tri)
+        if ctx is None and max_steps is None and not flat:
+            self.L.och_surface_locate(self.h, xy if len(xy) else np.zeros((1, 2)), len(xy), tri)
+        elif self.L.och_surface_locate_on(self.h, ctx.h if ctx is not None else None, xy if len(xy) else np.zeros((1, 2)), len(xy),
+                                          100 if max_steps is None else max_steps, tri) != 0:
+            raise capi.OchipError("locate failed: " + self.L.och_points_last_error().decode())
         return tri[:len(xy)]
+
+    def locate_table(self):
+        """The mesh's flat locate table (csrc/mesh_locate.hpp) as arrays, in capi.MeshPoints.count's layout."""
+        sizes = np.zeros(2, np.uint64)
+        self.L.och_surface_locate_table_sizes(self.h, sizes)
+        T, ns = int(sizes[0]), int(sizes[1])
+        t = dict(vertex_xy=np.zeros((max(T, 1), 6)), neighbours=np.zeros((max(T, 1), 3), np.uint32), plane=np.zeros((max(T, 1), 6)),
+                 cx=np.zeros(max(T, 1)), cy=np.zeros(max(T, 1)), start=np.zeros(max(ns, 1), np.uint32), items=np.zeros(max(T, 1), np.uint32))
+        grid = np.zeros(4)
+        self.L.och_surface_locate_table(self.h, t["vertex_xy"].ctypes.data, t["neighbours"].ctypes.data, t["plane"].ctypes.data,
+                                        t["cx"].ctypes.data, t["cy"].ctypes.data, grid.ctypes.data, t["start"].ctypes.data,
+                                        t["items"].ctypes.data)
+        for k in ("vertex_xy", "neighbours", "plane", "cx", "cy", "items"):
+            t[k] = t[k][:T]
+        t["start"] = t["start"][:ns]
+        t.update(x0=grid[0], y0=grid[1], cell=grid[2], nx=int(grid[3]))
+        return t
 
     def save_ply(self, path):
         """serialize(MeshGraph, ostream) of the reference (ASCII PLY, src/io/serialize_MeshGraph.cpp)."""
@@ -481,6 +526,38 @@ class Surface:
         if self.L.och_surface_load_ply(self.h, str(path).encode()) != 0:
             raise IOError("%s is not a surface PLY of the reference's layout" % path)
         return self
+
+
+class PointCounter:
+    """A cloud kept for counts against changing meshes (host/mesh_points.hpp): on the device with ctx (uploaded once), in
+    host memory without.  count(surface): count_points_per_triangle's rows for the surface's mesh and THIS cloud."""
+
+    def __init__(self, points, ctx=None, max_steps=100):
+        self.L = load()
+        xyz = np.ascontiguousarray(points, np.float64).reshape(-1, 3)
+        self.h = self.L.och_point_counter_create(ctx.h if ctx is not None else None, xyz if len(xyz) else np.zeros((1, 3)), len(xyz),
+                                                 max_steps)
+        if not self.h:
+            raise capi.OchipError("point counter: " + self.L.och_points_last_error().decode())
+        self.exhausted = 0
+
+    def count(self, surface):
+        if not self.h:
+            raise capi.OchipError("the point counter is closed")
+        cap = 2 * max(len(surface.arrays()["edges"]), 1)
+        tri, st, ex = np.zeros((cap, 3), np.uint64), np.zeros((cap, 2)), np.zeros(1, np.uint64)
+        n = self.L.och_point_counter_count(self.h, surface.h, tri, st, cap, ex)
+        if n == C.c_size_t(-1).value:
+            raise capi.OchipError("point counter: " + self.L.och_points_last_error().decode())
+        self.exhausted = int(ex[0])
+        return tri[:n], st[:n, 0].astype(np.int64), st[:n, 1]
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.L.och_point_counter_destroy(self.h)
+            self.h = None
+
+    __del__ = close
 
 
 def validate_checkpoint(path):
@@ -1648,6 +1725,17 @@ class Graph:
         if n < 0:
             raise capi.OchipError("mesh refinement failed: " + self.L.och_last_error(self.h).decode())
         names = ["level", "grid_fraction", "gsd", "above_threshold", "max_points", "created", "vertices", "repeat"]
+        return surface, [dict(zip(names, row)) for row in log[:n].tolist()]
+
+    def dense_mesh_relax(self, surface, ctx=None, max_steps=40):
+        """The pipeline's DENSE_MESH_RELAX state (src/pipeline/pipeline.cpp:844-924) run to its end on `surface` (mesh +
+        the dense cloud): refine by point density at the gsd's thresholds until nothing is created, at most 21 runs.  ctx:
+        the points are counted on the device (the cloud uploaded once), else on the host.  Returns (surface, log)."""
+        log = np.zeros((max(max_steps, 1), 6))
+        n = self.L.och_dense_mesh_relax_run(self.h, ctx.h if ctx is not None else None, surface.h, max_steps, log)
+        if n < 0:
+            raise capi.OchipError("dense mesh relax failed: " + self.L.och_last_error(self.h).decode())
+        names = ["run", "gsd", "reduced_gsd", "above_threshold", "created", "vertices"]
         return surface, [dict(zip(names, row)) for row in log[:n].tolist()]
 
     def node_table(self):
