@@ -621,6 +621,43 @@ extern "C"
     void och_ortho_overviews_destroy(och_ortho_overviews *o);
     const char *och_ortho_overviews_last_error(void);
 
+    /* ---- per-tile progress of the layer and blend passes (opencalibration_amd/csrc/host/ortho_tile_thumbs.cpp,
+     * csrc/ortho_tile_thumbs.hpp; the reference's TileProgressCallback, include/opencalibration/pipeline/progress.hpp:15-34,
+     * src/ortho/ortho.cpp:1553-1614, 1962-2011) -------------------------------------------------------
+     * One record per finished tile, the reference's TileUpdate with the thumbnail as pixels: the tile's rectangle in the
+     * raster, the raster's size, tile_index the 1-based row-major index over the whole raster (the reference's is its
+     * completion count; here bands run in raster order), total_tiles = ceil(width / T) * ceil(height / T), the thumbnail's
+     * size and scale (include/ochip.h), pass 1 (layers) or 2 (blend), and the raster's min_x, max_y and gsd.  72 bytes, no
+     * padding.
+     * The object belongs to one raster (plan8 as och_dsm_plan writes it: width, height, gsd, min_x, max_x, min_y, max_y,
+     * mean_camera_z), one tile size (1..4096) and layer count (1..8).  ctx != NULL: feed enqueues the thumbnail kernel and an
+     * asynchronous copy into a page-locked block of the context's pool behind whatever the context's stream holds - the
+     * band's render - and returns: the device never waits for the host.  pixels / weight as ochip_ortho_tile_thumbs' (device
+     * pointers when on_device).  ctx == NULL: the CPU route, host inputs, computed in feed.  row0 must lie on a tile row,
+     * rows be whole tile rows or end the raster, and the bands of one pass arrive in raster order without gaps (after the
+     * raster's last row a pass may start again at row 0, and seek names the tile row a pass's next band starts at, for a
+     * caller that reports a part of the raster); anything else is refused with the rows named.  pending: the bands
+     * fed and not yet collected.  collect waits for the oldest fed band alone and returns its tiles in tile order: *n
+     * records into updates and n slots of min(T, 128)^2 BGRA pixels into thumbs (host; the thumbnail densely at a slot's
+     * start, the rest zero).  With updates == NULL it only reports that band's tile count in *n; a capacity below it is
+     * refused and the band stays.  The refusals return OCHIP_EINVAL (a failed device call its code) with the message in
+     * och_tile_progress_last_error.  destroy waits for what is still in flight and hands the blocks back. */
+    typedef struct och_tile_update
+    {
+        int32_t pixel_x, pixel_y, pixel_w, pixel_h, total_output_width, total_output_height, tile_index, total_tiles, thumb_w,
+            thumb_h, scale, pass;
+        double bounds_min_x, bounds_max_y, meters_per_pixel;
+    } och_tile_update;
+    typedef struct och_tile_progress och_tile_progress;
+    int och_tile_progress_create(ochip_ctx *ctx, const double *plan8, int32_t tile_size, int32_t num_layers, och_tile_progress **out);
+    int och_tile_progress_feed(och_tile_progress *p, int pass, int64_t row0, int64_t rows, int on_device, const uint8_t *pixels,
+                               const float *weight);
+    int och_tile_progress_seek(och_tile_progress *p, int pass, int64_t row0);
+    int och_tile_progress_pending(const och_tile_progress *p);
+    int och_tile_progress_collect(och_tile_progress *p, och_tile_update *updates, uint8_t *thumbs, uint64_t capacity, uint64_t *n);
+    void och_tile_progress_destroy(och_tile_progress *p);
+    const char *och_tile_progress_last_error(void);
+
 #ifdef __cplusplus
 }
 #endif

@@ -967,6 +967,41 @@ extern "C"
     int ochip_mesh_points_where(ochip_mesh_points *m, uint32_t *where /* [n] */);
     void ochip_mesh_points_destroy(ochip_mesh_points *m);
 
+    /* ---- per-tile progress thumbnails of the layer and blend passes (opencalibration_amd/csrc/ortho_tile_thumbs.hip, the
+     *      arithmetic in csrc/ortho_tile_thumbs.hpp; the reference's TileProgressCallback, src/ortho/ortho.cpp:1553-1614 and
+     *      1962-2011) ----
+     * A band of rows x cols pixels - whole tile rows from a tile row - is cut into tiles of tile_size T (1..4096), counted
+     * row-major; tile (tx, ty) is tw = min(T, cols - tx T) by th = min(T, rows - ty T).  Its thumbnail takes every scale-th
+     * pixel, scale = max(1, (max(tw, th) + 127) / 128), thumb_w = (tw + scale - 1) / scale, thumb_h likewise: thumbnail
+     * pixel (y, x) reads tile pixel (min(y scale, th - 1), min(x scale, tw - 1)).  ochip_ortho_tile_thumb_dims: dims3 =
+     * {scale, thumb_w, thumb_h} of a tw x th tile (each 1..4096); needs no device.
+     * pass OCHIP_TILE_PASS_LAYERS: pixels = bgra [L][rows][cols][4] and weight [L][rows][cols] as ochip_ortho_layers writes
+     * them (num_layers L in 1..8).  Over the layers in ascending order, from best = -1 and colour 0: a sample with alpha > 0
+     * and weight > best (a float compare: a NaN never wins, an equal weight keeps the lower layer) sets best and the colour.
+     * The pixel is (B, G, R, 255) when best >= 0, else the background (0, 0, 0, 51).
+     * pass OCHIP_TILE_PASS_BLEND: pixels = rgba [rows][cols][4] as ochip_ortho_blend writes it (weight is not read, num_layers
+     * still 1..8): alpha > 0 gives (rgba[2], rgba[1], rgba[0], 255), else (0, 0, 0, 0).
+     * thumbs_out (host): per tile, in tile order, a slot of min(T, 128)^2 BGRA pixels; the thumbnail lies densely at the
+     * slot's start, thumb_h rows of thumb_w, the rest of the slot is zero.
+     * ochip_ortho_tile_thumbs is synchronous; pixels and weight are device pointers of this context's GPU when on_device,
+     * else host.  ctx == NULL: the CPU route over host inputs (the message then in ochip_last_error(NULL)'s place).
+     * The asynchronous form: enqueue launches the one kernel and the copy into a page-locked block of the context's pool on
+     * the context's stream, records an event and returns (host inputs are uploaded and free on return); wait sleeps until
+     * that job's event alone has passed and gives the block (bytes: tiles x slot bytes), valid until release, which hands
+     * the blocks back to the pools (and waits first when nobody has).
+     * Refused with OCHIP_EINVAL and a message, before anything is read: a pass that is neither, T or L out of range, cols <= 0,
+     * rows <= 0, a NULL or unaligned array, pass 1 without weights, more than 2^31 - 1 tiles. */
+#define OCHIP_TILE_PASS_LAYERS 1
+#define OCHIP_TILE_PASS_BLEND 2
+    typedef struct ochip_tile_thumbs_job ochip_tile_thumbs_job;
+    int ochip_ortho_tile_thumb_dims(int32_t tw, int32_t th, int32_t *dims3);
+    int ochip_ortho_tile_thumbs(ochip_ctx *ctx, int pass, int32_t cols, int64_t rows, int32_t tile_size, int32_t num_layers,
+                                int on_device, const uint8_t *pixels, const float *weight, uint8_t *thumbs_out);
+    int ochip_ortho_tile_thumbs_enqueue(ochip_ctx *ctx, int pass, int32_t cols, int64_t rows, int32_t tile_size, int32_t num_layers,
+                                        int on_device, const uint8_t *pixels, const float *weight, ochip_tile_thumbs_job **out);
+    int ochip_ortho_tile_thumbs_wait(ochip_tile_thumbs_job *job, const uint8_t **thumbs, uint64_t *bytes);
+    void ochip_ortho_tile_thumbs_release(ochip_tile_thumbs_job *job);
+
 #ifdef __cplusplus
 }
 #endif

@@ -50,6 +50,8 @@ EXPORTS = [
     "ochip_ortho_overviews_complete_rows", "ochip_ortho_overviews_finish", "ochip_ortho_overviews_destroy",
     "ochip_mesh_points_create", "ochip_mesh_points_size", "ochip_mesh_points_count", "ochip_mesh_points_where",
     "ochip_mesh_points_destroy",
+    "ochip_ortho_tile_thumb_dims", "ochip_ortho_tile_thumbs", "ochip_ortho_tile_thumbs_enqueue", "ochip_ortho_tile_thumbs_wait",
+    "ochip_ortho_tile_thumbs_release",
 ]
 
 _lib = None
@@ -278,6 +280,12 @@ def load():
         L.ochip_mesh_points_where.argtypes = [vp, vp]
         L.ochip_mesh_points_destroy.argtypes = [vp]
         L.ochip_mesh_points_destroy.restype = None
+        L.ochip_ortho_tile_thumb_dims.argtypes = [i32, i32, vp]
+        L.ochip_ortho_tile_thumbs.argtypes = [vp, i32, i32, C.c_int64, i32, i32, i32, vp, vp, vp]
+        L.ochip_ortho_tile_thumbs_enqueue.argtypes = [vp, i32, i32, C.c_int64, i32, i32, i32, vp, vp, C.POINTER(vp)]
+        L.ochip_ortho_tile_thumbs_wait.argtypes = [vp, C.POINTER(vp), C.POINTER(u64)]
+        L.ochip_ortho_tile_thumbs_release.argtypes = [vp]
+        L.ochip_ortho_tile_thumbs_release.restype = None
         _lib = L
     return _lib
 

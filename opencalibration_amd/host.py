@@ -306,6 +306,14 @@ def load():
         L.och_ortho_overviews_destroy.argtypes = [vp]
         L.och_ortho_overviews_destroy.restype = None
         L.och_ortho_overviews_last_error.restype = C.c_char_p
+        L.och_tile_progress_create.argtypes = [vp, _f64p, C.c_int32, C.c_int32, C.POINTER(vp)]
+        L.och_tile_progress_feed.argtypes = [vp, C.c_int, i64, i64, C.c_int, vp, vp]
+        L.och_tile_progress_seek.argtypes = [vp, C.c_int, i64]
+        L.och_tile_progress_pending.argtypes = [vp]
+        L.och_tile_progress_collect.argtypes = [vp, vp, vp, C.c_uint64, C.POINTER(C.c_uint64)]
+        L.och_tile_progress_destroy.argtypes = [vp]
+        L.och_tile_progress_destroy.restype = None
+        L.och_tile_progress_last_error.restype = C.c_char_p
         _lib = L
     return _lib
 
@@ -1290,7 +1298,7 @@ def color_balance_remove_gauge(xy, offsets):
 
 
 def ortho_mosaic(plan, graph, surfaces, images, mesh=None, config=None, color_balance=None, tile_rows=1, out=None,
-                 overviews=False):
+                 overviews=False, progress=None, progress_passes=(1, 2)):
     """The blended full-resolution orthomosaic of `plan` (dsm_plan), band by band of tile_rows output tile rows: DSM ->
     layers (ortho_layers) -> blend (ortho_blend).  mesh (an OrthoMesh): every step on its device, images as CUDA tensors,
     into `out` (a (height, width, 4) uint8 CUDA tensor, made when None); None: the CPU route, numpy images, into a host
@@ -1301,24 +1309,32 @@ def ortho_mosaic(plan, graph, surfaces, images, mesh=None, config=None, color_ba
     RE-RENDERS every band's layers and blends them with the result: a band's layers are never kept beyond its blend, so
     the memory held stays one band's whatever the raster's size, at the price of the layer pass run twice.
     overviews=True: (out, dict(rgba=[level 1, ...], dsm=[level 1, ...])), the averaged overview levels (OrthoOverviews) of
-    the mosaic and of the DSM, each band fed right after its blend - with "solve" in the second sweep alone."""
-    return _mosaic(plan, graph, surfaces, mesh, config, color_balance, tile_rows, out, images=images, overviews=overviews)
+    the mosaic and of the DSM, each band fed right after its blend - with "solve" in the second sweep alone.
+    progress: a callable that takes one tile update (TileProgress.collect's dict) per tile and pass of progress_passes (1:
+    the layers, 2: the blend), the reference's TileProgressCallback; within a pass the calls come in tile_index order.
+    With "solve" the first sweep emits pass 1 and the second pass 2, otherwise the single sweep emits a band's pass-1 tiles
+    and then its pass-2 tiles.  Band k's updates are collected after band k + 1 has been enqueued, so the device never
+    waits for the callback; the rest are flushed before the function returns.  An exception from the callback propagates
+    after the stream and the builders are closed.  None: nothing is allocated or launched for it."""
+    return _mosaic(plan, graph, surfaces, mesh, config, color_balance, tile_rows, out, images=images, overviews=overviews,
+                   progress=progress, progress_passes=progress_passes)
 
 
 def ortho_mosaic_streamed(plan, graph, surfaces, fetch, mesh, capacity, config=None, color_balance=None, tile_rows=1, out=None,
-                          overviews=False):
+                          overviews=False, progress=None, progress_passes=(1, 2)):
     """ortho_mosaic on mesh's device without the source images resident: fetch(i) returns involved camera i's BGR image
     (ortho_layers_cameras' order) as a numpy array or a page-locked torch CPU tensor, and at most `capacity` images are on
     the device at a time (OrthoStream).  Band k + 1's ahead uploads are issued before band k renders, so that they run
     beside it when the images are page-locked.  color_balance as ortho_mosaic's; "solve" renders the layers twice, the
     second sweep starting from the images the first one left on the device.  Returns the (height, width, 4) RGBA tensor,
-    with overviews=True (tensor, dict(rgba=[...], dsm=[...])) as ortho_mosaic does."""
+    with overviews=True (tensor, dict(rgba=[...], dsm=[...])) as ortho_mosaic does.  progress, progress_passes: as
+    ortho_mosaic's."""
     return _mosaic(plan, graph, surfaces, mesh, config, color_balance, tile_rows, out, fetch=fetch, capacity=capacity,
-                   overviews=overviews)
+                   overviews=overviews, progress=progress, progress_passes=progress_passes)
 
 
 def _mosaic(plan, graph, surfaces, mesh, config, color_balance, tile_rows, out, images=None, fetch=None, capacity=None,
-            overviews=False):
+            overviews=False, progress=None, progress_passes=(1, 2)):
     """The band loop of ortho_mosaic (images) and ortho_mosaic_streamed (fetch, capacity): the two differ in where a band's
     layers come from, ortho_layers over the resident images or an OrthoStream's render behind the band's uploads."""
     cfg = {**LAYERS_CONFIG, **BLEND_CONFIG, **(config or {})}
@@ -1338,8 +1354,18 @@ def _mosaic(plan, graph, surfaces, mesh, config, color_balance, tile_rows, out, 
     stream = OrthoStream(plan, graph, surfaces, capacity, mesh=mesh, tile_rows=tile_rows, config=lcfg) if fetch is not None else None
     builders = [OrthoOverviews(kind, w, h, ctx=ctx, on_device=mesh is not None)
                 for kind in (OVERVIEW_RGBA8, OVERVIEW_FLOAT32)] if overviews else []
+    passes = {int(p) for p in progress_passes} if progress is not None else set()
+    if passes - {TILE_PASS_LAYERS, TILE_PASS_BLEND}:
+        raise ValueError("progress_passes names 1 (the layers) and 2 (the blend)")
+    tiles = TileProgress(plan, cfg["tile_size"], nl, ctx=ctx) if passes else None
 
-    def band(k, balance, blend):
+    def deliver(keep):
+        """the fed bands' updates to the callback, oldest first, until `keep` bands are pending"""
+        while tiles.pending() > keep:
+            for update in tiles.collect():
+                progress(update)
+
+    def band(k, balance, blend, emit=frozenset()):
         row0 = k * band_rows
         rows = min(band_rows, h - row0)
         if stream is not None:  # before the band's DSM and render: its own loads still missing, then the next band's ahead ones
@@ -1355,27 +1381,41 @@ def _mosaic(plan, graph, surfaces, mesh, config, color_balance, tile_rows, out, 
             dsm_render(plan, surfaces, mesh=mesh, row0=row0, rows=rows, out=dsm)
             lay = dict(bgra=torch.empty((nl, rows, w, 4), dtype=torch.uint8, device=dev),
                        camera_id=torch.empty((nl, rows, w), dtype=torch.int64, device=dev))
+            if TILE_PASS_LAYERS in emit:  # the pick among the layers reads their weights
+                lay["weight"] = torch.empty((nl, rows, w), dtype=torch.float32, device=dev)
         if stream is not None:
             layers = stream.render(k, out=lay)
         else:
             layers = ortho_layers(plan, graph, surfaces, images, mesh=mesh, row0=row0, tile_rows=tile_rows, config=lcfg, out=lay,
                                   dsm=dsm if mesh is None else None)
+        before = tiles.pending() if emit else 0
+        if TILE_PASS_LAYERS in emit:  # behind the render on the context's stream: no wait of its own
+            tiles.feed(TILE_PASS_LAYERS, row0, layers["bgra"], layers["weight"])
         if blend:
             ortho_blend(plan, graph, surfaces, layers, dsm, balance, ctx=ctx, config=bcfg, out=out[row0:row0 + rows])
+            if TILE_PASS_BLEND in emit:
+                tiles.feed(TILE_PASS_BLEND, row0, out[row0:row0 + rows])
             if builders:  # behind the blend on the context's stream: no wait of its own
                 builders[0].feed(row0, out[row0:row0 + rows])
                 builders[1].feed(row0, dsm)
+        if emit:  # this band is enqueued behind the bands before it: their updates are due
+            deliver(tiles.pending() - before)
         return layers["correspondences"]
 
     try:
         bands = range(-(-h // band_rows))
         if color_balance == "solve":
-            corr = [band(k, None, False) for k in bands]
+            corr = [band(k, None, False, passes & {TILE_PASS_LAYERS}) for k in bands]
+            if tiles is not None:
+                deliver(0)
             color_balance = color_balance_solve(np.concatenate(corr) if corr else np.zeros(0, CORR_DTYPE), graph=graph, ctx=ctx)
             if stream is not None:
                 stream.rewind()
+            passes = passes & {TILE_PASS_BLEND}
         for k in bands:
-            band(k, color_balance, True)
+            band(k, color_balance, True, passes)
+        if tiles is not None:
+            deliver(0)
         if builders:
             return out, dict(rgba=builders[0].finish(), dsm=builders[1].finish())
     finally:
@@ -1383,7 +1423,167 @@ def _mosaic(plan, graph, surfaces, mesh, config, color_balance, tile_rows, out, 
             stream.close()
         for b in builders:
             b.close()
+        if tiles is not None:
+            tiles.close()
     return out
+
+
+# ---- per-tile progress of the layer and blend passes (include/oc_host.h) -----------------------------------
+TILE_PASS_LAYERS, TILE_PASS_BLEND = 1, 2
+# och_tile_update: 72 bytes, no padding
+TILE_UPDATE_DTYPE = np.dtype([(k, np.int32) for k in (
+    "pixel_x", "pixel_y", "pixel_w", "pixel_h", "total_output_width", "total_output_height", "tile_index", "total_tiles",
+    "thumb_w", "thumb_h", "scale", "pass")] + [(k, np.float64) for k in ("bounds_min_x", "bounds_max_y", "meters_per_pixel")])
+
+
+def tile_thumb_dims(tw, th):
+    """(scale, thumb_w, thumb_h) of the progress thumbnail of a tw x th tile (each 1..4096): every scale-th pixel, scale =
+    max(1, (max(tw, th) + 127) // 128)."""
+    dims = np.zeros(3, np.int32)
+    if capi.load().ochip_ortho_tile_thumb_dims(int(tw), int(th), dims.ctypes.data) != 0:
+        raise ValueError(f"a tile of {tw} x {th}")
+    return tuple(int(v) for v in dims)
+
+
+def _tile_band(pass_, pixels, weight, device):
+    """(num_layers, rows, width, on_device, pixels' pointer, weights' pointer, what to keep alive) of a band fed to the tile
+    thumbnails: pass 1 bgra (L, rows, width, 4) uint8 with weight (L, rows, width) float32, pass 2 rgba (rows, width, 4)"""
+    on_device = not isinstance(pixels, np.ndarray)
+    lead = 1 if pass_ == TILE_PASS_LAYERS else 0
+    if len(pixels.shape) != 3 + lead or pixels.shape[-1] != 4:
+        raise ValueError("a band is bgra (L, rows, width, 4) for pass 1, rgba (rows, width, 4) otherwise")
+    shape = tuple(int(v) for v in pixels.shape)
+    nl, rows, w = (shape[0] if lead else 1), shape[lead], shape[lead + 1]
+    if weight is not None and (isinstance(weight, np.ndarray) == on_device):
+        raise ValueError("pixels and weight are both numpy arrays or both CUDA tensors")
+    if on_device:
+        if device is None:
+            raise ValueError("a device band needs the device route (ctx)")
+        p = _device_ptr(pixels, "torch.uint8", shape, "pixels", device)
+        pw = None if weight is None else _device_ptr(weight, "torch.float32", shape[:-1], "weight", device)
+    else:
+        if pixels.dtype != np.uint8:
+            raise ValueError("the pixels are uint8")
+        pixels = np.ascontiguousarray(pixels)
+        if weight is not None:
+            weight = np.ascontiguousarray(weight, np.float32)
+            if weight.shape != shape[:-1]:
+                raise ValueError(f"weight must be {shape[:-1]}")
+        p, pw = pixels.ctypes.data, None if weight is None else weight.ctypes.data
+    return nl, rows, w, on_device, p, pw, (pixels, weight)
+
+
+def ortho_tile_thumbs(pixels, pass_, tile_size=None, weight=None, ctx=None):
+    """The raw thumbnail slots of one band (ochip_ortho_tile_thumbs): (tiles, min(T, 128)^2, 4) uint8 BGRA in tile order, the
+    thumbnail densely at each slot's start and zeros behind it.  pixels / weight: numpy arrays (ctx None: the CPU route,
+    else through ctx's device) or CUDA tensors on ctx's device."""
+    t = int(BLEND_CONFIG["tile_size"] if tile_size is None else tile_size)
+    nl, rows, w, on_device, p, pw, _keep = _tile_band(pass_, pixels, weight, None if ctx is None else ctx.device)
+    if on_device:
+        import torch
+
+        torch.cuda.current_stream(pixels.device).synchronize()  # the kernel runs on the context's own stream
+    side = min(max(t, 1), 128)
+    out = np.zeros((max(-(-w // max(t, 1)) * -(-rows // max(t, 1)), 0), side * side, 4), np.uint8)
+    L = capi.load()
+    if L.ochip_ortho_tile_thumbs(ctx.h if ctx is not None else None, int(pass_), w, rows, t, nl, int(on_device), p, pw,
+                                 out.ctypes.data) != 0:
+        raise capi.OchipError(L.ochip_last_error(ctx.h if ctx is not None else None).decode())
+    return out
+
+
+class TileProgress:
+    """The per-tile updates of a raster's layer and blend passes, band by band (och_tile_progress_*).
+    plan: the raster (dsm_plan); ctx None: the CPU route, numpy bands; ctx: numpy bands through its device, or CUDA tensors,
+    fed on the context's stream without a host wait - the caller has torch's work on a band finished before feed, as
+    ortho_blend does.  feed(pass_, row0, pixels, weight): pass 1 takes bgra (L, rows, width, 4) and weight (L, rows,
+    width), pass 2 rgba (rows, width, 4); row0 lies on a tile row and a pass's bands arrive in raster order without gaps.
+    collect(): waits for the oldest fed band alone and returns its tiles in tile order as dicts of TILE_UPDATE_DTYPE's
+    fields plus thumbnail, a (thumb_h, thumb_w, 4) uint8 BGRA array; raw=True: (records, slots) as the library wrote them."""
+
+    def __init__(self, plan, tile_size=None, num_layers=None, ctx=None):
+        self.L, self.ctx, self.plan = load(), ctx, dict(plan)
+        self.tile_size = int(BLEND_CONFIG["tile_size"] if tile_size is None else tile_size)
+        self.num_layers = int(LAYERS_CONFIG["num_layers"] if num_layers is None else num_layers)
+        self.h = None
+        self._keep = []
+        h = C.c_void_p()
+        if self.L.och_tile_progress_create(ctx.h if ctx is not None else None, _plan_array(plan), self.tile_size, self.num_layers,
+                                           C.byref(h)) != 0:
+            raise capi.OchipError(self._error())
+        self.h = h
+
+    def _error(self):
+        return self.L.och_tile_progress_last_error().decode()
+
+    def close(self):
+        if getattr(self, "h", None):
+            if self.ctx is None or getattr(self.ctx, "h", None):  # as OrthoStream.close: the context may be gone
+                self.L.och_tile_progress_destroy(self.h)
+            self.h = None
+            self._keep = []
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        self.close()
+
+    def feed(self, pass_, row0, pixels, weight=None):
+        nl, rows, w, on_device, p, pw, keep = _tile_band(pass_, pixels, weight, None if self.ctx is None else self.ctx.device)
+        if w != self.plan["width"] or (pass_ == TILE_PASS_LAYERS and nl != self.num_layers):
+            raise ValueError(f"a band of this raster is {self.plan['width']} pixels wide, of {self.num_layers} layers")
+        if self.L.och_tile_progress_feed(self.h, int(pass_), int(row0), rows, int(on_device), p, pw) != 0:
+            raise capi.OchipError(self._error())
+        self._keep.append(keep if on_device else None)  # the kernel may still read a device band: alive until collected
+
+    def seek(self, pass_, row0):
+        """pass_'s next band starts at row0, a tile row: for a caller that reports a part of the raster"""
+        if self.L.och_tile_progress_seek(self.h, int(pass_), int(row0)) != 0:
+            raise capi.OchipError(self._error())
+
+    def pending(self):
+        return int(self.L.och_tile_progress_pending(self.h))
+
+    def collect(self, raw=False):
+        n = C.c_uint64(0)
+        if self.L.och_tile_progress_collect(self.h, None, None, 0, C.byref(n)) != 0:
+            raise capi.OchipError(self._error())
+        side = min(self.tile_size, 128)
+        records = np.zeros(n.value, TILE_UPDATE_DTYPE)
+        slots = np.zeros((n.value, side * side, 4), np.uint8)
+        if self.L.och_tile_progress_collect(self.h, records.ctypes.data, slots.ctypes.data, n.value, C.byref(n)) != 0:
+            raise capi.OchipError(self._error())
+        self._keep.pop(0)
+        if raw:
+            return records, slots
+        updates = []
+        for r, slot in zip(records, slots):
+            u = {k: (float(r[k]) if r.dtype[k] == np.float64 else int(r[k])) for k in TILE_UPDATE_DTYPE.names}
+            u["thumbnail"] = slot[:u["thumb_w"] * u["thumb_h"]].reshape(u["thumb_h"], u["thumb_w"], 4).copy()
+            updates.append(u)
+        return updates
+
+
+def ortho_tile_updates(plan, pixels, pass_, row0=0, tile_size=None, weight=None, ctx=None):
+    """The tile updates of one band of `plan`'s raster from row0 on (TileProgress in one feed): a list of dicts, per tile
+    in tile order pixel_x, pixel_y, pixel_w, pixel_h, total_output_width, total_output_height, tile_index (1-based, row-major
+    over the whole raster), total_tiles, thumb_w, thumb_h, scale, pass, bounds_min_x, bounds_max_y, meters_per_pixel and
+    thumbnail, a (thumb_h, thumb_w, 4) uint8 BGRA array.  pass_ 1: pixels = the layers' bgra (L, rows, width, 4) and weight
+    (L, rows, width); the best-weighted valid layer, (0, 0, 0, 51) where none is.  pass_ 2: pixels = the blended rgba (rows,
+    width, 4); (0, 0, 0, 0) where alpha is 0.  numpy arrays (ctx None: the CPU route) or CUDA tensors on ctx's device."""
+    nl = int(pixels.shape[0]) if pass_ == TILE_PASS_LAYERS and len(pixels.shape) == 4 else 1
+    if not isinstance(pixels, np.ndarray):
+        import torch
+
+        torch.cuda.current_stream(pixels.device).synchronize()  # the kernel runs on the context's own stream
+    with TileProgress(plan, tile_size, nl, ctx=ctx) as t:
+        t.seek(pass_, row0)  # a band in the middle of the raster: the pass's order starts where it does
+        t.feed(pass_, row0, pixels, weight)
+        return t.collect()
 
 
 # ---- averaged overview levels of the orthomosaic and the DSM (include/oc_host.h; DESIGN.md §4.13) -----------------------
