@@ -403,6 +403,36 @@ extern "C"
                                   double *grid4, uint32_t *start, uint32_t *items);
     int och_dense_mesh_relax_run(och_graph *g, ochip_ctx *ctx, och_surface *surface, int max_steps, double *log6);
 
+    /* ---- the filtered point cloud file and the textured OBJ (opencalibration_amd/csrc/host/xyz_export.hpp, .cpp;
+     *      csrc/xyz_export.hpp; the runner's deliverables after COMPLETE, app/pipeline_runner.cpp:351-395; DESIGN.md
+     *      section 4.16) ----------
+     * The cloud is all clouds of all surfaces in surface, cloud, point order.  och_cloud_outlier_bounds: filterOutliers
+     * (src/io/saveXYZ.cpp:50-105), bounds6 = {x first, x second, y first, y second, z first, z second}; a coordinate that
+     * is not finite or not below 2^63 in magnitude is refused.  och_cloud_to_xyz: the bytes of toXYZ (:6-48) for that box
+     * (bounds6 == NULL: no filter), malloc'd and NUL-terminated (och_free), *len its length, *kept (may be NULL) its lines;
+     * och_cloud_save_xyz: the same into a file.  ctx == NULL: host loops under OpenMP; else the device route
+     * (ochip_xyz_export_* of ochip.h) - the same bytes; the route never changes by size.  och_xyz_*: the same for a
+     * flat array xyz [n][3].  0 = ok; -1 or NULL + och_export_last_error() (per thread) otherwise.
+     * och_format_g6: per value 16 bytes of text (zero-padded) and the length of `ostream << double` - the integer
+     * formatter of csrc/xyz_export.hpp, which gives length 0 for |v| outside [1e-5, 2^63) and not 0; with_fallback != 0:
+     * those through snprintf("%g"), as the exports do.
+     * och_textured_obj: the OBJ and MTL text of generateTexturedOBJ (src/ortho/ortho.cpp:2125-2255) over an orthomosaic
+     * of width x height pixels whose top-left corner is (min_x, max_y) at gsd_x, gsd_y metres per pixel: per surface with
+     * edges its vertices `v x y z` and `vt u v` in ascending node id, then the faces the PLY writer lists, in its order,
+     * as `f a/a b/b c/c` with 1-based indices past the surfaces before.  Both texts malloc'd (och_free). */
+    const char *och_export_last_error(void);
+    int och_cloud_outlier_bounds(const och_surface *const *surfaces, size_t n_surfaces, ochip_ctx *ctx, int64_t *bounds6);
+    char *och_cloud_to_xyz(const och_surface *const *surfaces, size_t n_surfaces, ochip_ctx *ctx, const int64_t *bounds6,
+                           size_t *len, uint64_t *kept);
+    int och_cloud_save_xyz(const och_surface *const *surfaces, size_t n_surfaces, ochip_ctx *ctx, const int64_t *bounds6,
+                           const char *path);
+    int och_xyz_outlier_bounds(const double *xyz, size_t n, ochip_ctx *ctx, int64_t *bounds6);
+    char *och_xyz_to_text(const double *xyz, size_t n, ochip_ctx *ctx, const int64_t *bounds6, size_t *len, uint64_t *kept);
+    void och_format_g6(const double *values, size_t n, int with_fallback, char *text16, uint8_t *len);
+    int och_textured_obj(const och_surface *const *surfaces, size_t n_surfaces, int64_t width, int64_t height, double min_x,
+                         double max_y, double gsd_x, double gsd_y, const char *mtl_name, const char *jpg_name, char **obj_out,
+                         size_t *obj_len, char **mtl_out, size_t *mtl_len);
+
     /* ---- orthomosaic preview and DSM raster (opencalibration_amd/csrc/host/ortho.hpp; src/ortho/ortho.cpp:228-964) -------
      * The reference's context: calculateBoundsAndMeanZ (bounds5 = min_x, max_x, min_y, max_y, mean_surface_z; a surface's
      * clouds count only when it has no mesh), calculateGSD over the given nodes in the given order (thumbnail != 0: the

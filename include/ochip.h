@@ -1002,6 +1002,36 @@ extern "C"
     int ochip_ortho_tile_thumbs_wait(ochip_tile_thumbs_job *job, const uint8_t **thumbs, uint64_t *bytes);
     void ochip_ortho_tile_thumbs_release(ochip_tile_thumbs_job *job);
 
+    /* ---- the point cloud file (opencalibration_amd/csrc/xyz_export.hip, the rules in csrc/xyz_export.hpp; the reference's
+     *      filterOutliers and toXYZ, src/io/saveXYZ.cpp) ----
+     * The object holds one flat cloud, xyz [n][3] fp64 (n < 2^32; n = 0 is valid): create uploads it from host memory,
+     * create_from_points copies the clouds of live ochip_mesh_points objects of the same context, in the given order, on
+     * the device (the objects are only read and stay as they are).
+     * bounds: bounds6 = {x first, x second, y first, y second, z first, z second}, filterOutliers' box - per axis the
+     * number of points in every integer cell static_cast<int64_t>(v), exact for any span of cells, then the reference's walk
+     * over the sorted (cell, count) rows.  A coordinate that is not finite or not below 2^63 in magnitude has no cell:
+     * OCHIP_EINVAL.
+     * text_size, then text: the bytes toXYZ writes, a line "x,y,z\n" per point inside the box in point order, every number
+     * as `ostream << double` prints it ("%g").  bounds6 == NULL: no filter (the box {0, 0} x 3 means the same, as in the
+     * reference).  text_size gives the file's size and its number of lines and keeps the lines on the device; text writes the
+     * bytes of the last text_size into out (cap >= bytes; no terminator) and may be called again.  text before any
+     * text_size is OCHIP_ESTATE.
+     * OCHIP_EINVAL and a message, before anything is launched, for a NULL array, cap < bytes and a handle that create did
+     * not return or destroy has taken (then the message is ochip_last_error(NULL)'s).  The calls wait for the context's
+     * stream; destroy hands the device blocks back to the context's pool.
+     * ochip_debug_format_g6: the device's number formatter alone - per value 16 bytes of text (zero-padded) and the length,
+     * 0 where the integer formatter declines (|v| outside [1e-5, 2^63) and not 0) and the library formats on the host. */
+    typedef struct ochip_xyz_export ochip_xyz_export;
+    int ochip_xyz_export_create(ochip_ctx *ctx, const double *xyz, uint64_t n, ochip_xyz_export **out);
+    int ochip_xyz_export_create_from_points(ochip_ctx *ctx, const ochip_mesh_points *const *clouds, uint64_t n_clouds,
+                                            ochip_xyz_export **out);
+    uint64_t ochip_xyz_export_size(const ochip_xyz_export *e); /* n; 0 for a handle that is not live */
+    int ochip_xyz_export_bounds(ochip_xyz_export *e, int64_t *bounds6);
+    int ochip_xyz_export_text_size(ochip_xyz_export *e, const int64_t *bounds6 /* or NULL */, uint64_t *bytes, uint64_t *kept);
+    int ochip_xyz_export_text(ochip_xyz_export *e, char *out, uint64_t cap);
+    void ochip_xyz_export_destroy(ochip_xyz_export *e);
+    int ochip_debug_format_g6(ochip_ctx *ctx, const double *values, uint64_t n, char *text16 /* [n][16] */, uint8_t *len /* [n] */);
+
 #ifdef __cplusplus
 }
 #endif

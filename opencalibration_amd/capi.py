@@ -52,6 +52,8 @@ EXPORTS = [
     "ochip_mesh_points_destroy",
     "ochip_ortho_tile_thumb_dims", "ochip_ortho_tile_thumbs", "ochip_ortho_tile_thumbs_enqueue", "ochip_ortho_tile_thumbs_wait",
     "ochip_ortho_tile_thumbs_release",
+    "ochip_xyz_export_create", "ochip_xyz_export_create_from_points", "ochip_xyz_export_size", "ochip_xyz_export_bounds",
+    "ochip_xyz_export_text_size", "ochip_xyz_export_text", "ochip_xyz_export_destroy", "ochip_debug_format_g6",
 ]
 
 _lib = None
@@ -286,6 +288,16 @@ def load():
         L.ochip_ortho_tile_thumbs_wait.argtypes = [vp, C.POINTER(vp), C.POINTER(u64)]
         L.ochip_ortho_tile_thumbs_release.argtypes = [vp]
         L.ochip_ortho_tile_thumbs_release.restype = None
+        L.ochip_xyz_export_create.argtypes = [vp, vp, u64, C.POINTER(vp)]
+        L.ochip_xyz_export_create_from_points.argtypes = [vp, vp, u64, C.POINTER(vp)]
+        L.ochip_xyz_export_size.argtypes = [vp]
+        L.ochip_xyz_export_size.restype = u64
+        L.ochip_xyz_export_bounds.argtypes = [vp, vp]
+        L.ochip_xyz_export_text_size.argtypes = [vp, vp, C.POINTER(u64), C.POINTER(u64)]
+        L.ochip_xyz_export_text.argtypes = [vp, vp, u64]
+        L.ochip_xyz_export_destroy.argtypes = [vp]
+        L.ochip_xyz_export_destroy.restype = None
+        L.ochip_debug_format_g6.argtypes = [vp, vp, u64, vp, vp]
         _lib = L
     return _lib
 
@@ -353,6 +365,74 @@ class MeshPoints:
             self.h = C.c_void_p()
 
 
+def bounds6(bounds):
+    """A box ((lo, hi),) * 3 as the int64 array of ochip_xyz_export_text_size; None stays None (no filter)."""
+    if bounds is None:
+        return None
+    b = np.ascontiguousarray(bounds, np.int64).reshape(-1)
+    if b.size != 6:
+        raise ValueError("bounds: three (first, second) pairs")
+    return b
+
+
+class XyzExport:
+    """ochip_xyz_export: a flat cloud on the device, written out as the reference's point cloud file (DESIGN.md section
+    4.16).  bounds(): filterOutliers' box as ((lo, hi),) * 3; text(bounds): toXYZ's bytes for a box (None: no filter)."""
+
+    def __init__(self, ctx, xyz, _points=None):
+        self.ctx, self.L = ctx, ctx.L
+        self.h = C.c_void_p()
+        if _points is None:
+            xyz = np.ascontiguousarray(xyz, np.float64).reshape(-1, 3)
+            ctx._check(self.L.ochip_xyz_export_create(ctx.h, xyz.ctypes.data if len(xyz) else None, len(xyz), C.byref(self.h)),
+                       "ochip_xyz_export_create")
+        else:
+            arr = (C.c_void_p * max(len(_points), 1))(*_points)
+            ctx._check(self.L.ochip_xyz_export_create_from_points(ctx.h, arr, len(_points), C.byref(self.h)),
+                       "ochip_xyz_export_create_from_points")
+        self.raw = self.h.value  # kept after close(): what a caller that held on to the handle would pass
+        self.n = self.L.ochip_xyz_export_size(self.h)
+        self.kept = 0
+
+    @classmethod
+    def from_points(cls, ctx, points):
+        """The clouds of live MeshPoints objects (or raw handles) in the given order, copied on the device."""
+        return cls(ctx, None, _points=[p.h.value if isinstance(p, MeshPoints) else p for p in points])
+
+    def _call(self, rc, what):
+        if rc != 0:
+            text = self.L.ochip_last_error(self.ctx.h).decode() + " | " + self.L.ochip_last_error(None).decode()
+            raise OchipError(f"{what} = {rc}: {text}")
+
+    def bounds(self, handle=None):
+        b = np.zeros(6, np.int64)
+        h = self.h if handle is None else C.c_void_p(handle)
+        self._call(self.L.ochip_xyz_export_bounds(h, b.ctypes.data), "ochip_xyz_export_bounds")
+        return tuple((int(b[2 * a]), int(b[2 * a + 1])) for a in range(3))
+
+    def text_size(self, bounds=None, handle=None):
+        b = bounds6(bounds)
+        nbytes, kept = C.c_uint64(0), C.c_uint64(0)
+        h = self.h if handle is None else C.c_void_p(handle)
+        self._call(self.L.ochip_xyz_export_text_size(h, b.ctypes.data if b is not None else None, C.byref(nbytes), C.byref(kept)),
+                   "ochip_xyz_export_text_size")
+        self.kept = kept.value
+        return nbytes.value, kept.value
+
+    def text(self, bounds=None, cap=None):
+        """The file's bytes; cap: the room offered to ochip_xyz_export_text (default: exactly what text_size said)."""
+        nbytes, _ = self.text_size(bounds)
+        cap = nbytes if cap is None else cap
+        out = np.zeros(max(cap, 1), np.uint8)
+        self._call(self.L.ochip_xyz_export_text(self.h, out.ctypes.data, cap), "ochip_xyz_export_text")
+        return out[:nbytes].tobytes()
+
+    def close(self):
+        if self.h:
+            self.L.ochip_xyz_export_destroy(self.h)
+            self.h = C.c_void_p()
+
+
 class Context:
     """Owns one ochip_ctx (one GPU)."""
 
@@ -388,6 +468,14 @@ class Context:
         self._check(self.L.ochip_debug_lab_table(self.h, codes.ctypes.data, len(codes), out.ctypes.data, C.byref(ms)),
                     "ochip_debug_lab_table")
         return out, float(ms.value)
+
+    def format_g6(self, values):
+        """The device's number formatter alone (ochip_debug_format_g6): (text [n] of S16, lengths [n]; 0 = declined)."""
+        v = np.ascontiguousarray(values, np.float64).reshape(-1)
+        text, ln = np.zeros((max(len(v), 1), 16), np.uint8), np.zeros(max(len(v), 1), np.uint8)
+        self._check(self.L.ochip_debug_format_g6(self.h, v.ctypes.data if len(v) else None, len(v), text.ctypes.data, ln.ctypes.data),
+                    "ochip_debug_format_g6")
+        return text[:len(v)].view("S16").reshape(-1), ln[:len(v)]
 
     def sibling(self, index):
         """The index-th sibling context (same device, own streams and scratch; owned by this context): independent work

@@ -366,6 +366,9 @@ int feature_lists_enqueue(ochip_ctx *ctx, dev_blocks &mem, uint32_t B, uint32_t 
                           const unsigned long long *d_desc, const unsigned int *d_counts, uint32_t most, int work_w, int work_h,
                           double scale, double nms_radius, const ochip_feature_lists *out);
 
+// mesh_points.hip: the device cloud of a live ochip_mesh_points object (xyz [n][3]) and its context; false otherwise
+bool mesh_points_view(const ochip_mesh_points *m, ochip_ctx **ctx, const double **xyz, uint32_t *n);
+
 // std_sort.hip: libstdc++'s std::sort (comp(a, b) = high half of a > high half of b) on segments of 64-bit records in HBM
 int std_sort_enqueue(ochip_ctx *ctx, dev_blocks &mem, unsigned long long *recs, size_t total_len, const unsigned int *seg_begin,
                      const unsigned int *seg_end, uint32_t n_segs, uint32_t max_len, unsigned char *fallback);

@@ -1304,15 +1304,10 @@ bool deserialize(const std::string &json, MeasurementGraph &graph, std::string *
 }
 
 // ---- MeshGraph as PLY ------------------------------------------------------------------------------------------------
-bool serialize(const MeshGraph &graph, std::ostream &out)
+// every edge contributes the triangle(s) it borders; a triangle's corners sorted by id, the first two swapped when
+// that order is anticlockwise (geometry/utils.hpp:10-14: cross z < 0), each triangle once (:55-85)
+std::set<std::array<size_t, 3>> mesh_faces(const MeshGraph &graph)
 {
-    const char nl = '\n';
-    out << "ply" << nl << "format ascii 1.0" << nl << "comment exported from OpenCalibration" << nl;
-    out << "element vertex " << graph.size_nodes() << nl;
-    out << "property double x" << nl << "property double y" << nl << "property double z" << nl << "property int nodeIndex" << nl;
-
-    // every edge contributes the triangle(s) it borders; a triangle's corners sorted by id, the first two swapped when
-    // that order is anticlockwise (geometry/utils.hpp:10-14: cross z < 0), each triangle once (:55-85)
     std::set<std::array<size_t, 3>> faces;
     for (const MeshEdge &e : graph.edges)
     {
@@ -1329,6 +1324,17 @@ bool serialize(const MeshGraph &graph, std::ostream &out)
         if (!e.border)
             add_face(e.triangleOppositeNodes[1]);
     }
+    return faces;
+}
+
+bool serialize(const MeshGraph &graph, std::ostream &out)
+{
+    const char nl = '\n';
+    out << "ply" << nl << "format ascii 1.0" << nl << "comment exported from OpenCalibration" << nl;
+    out << "element vertex " << graph.size_nodes() << nl;
+    out << "property double x" << nl << "property double y" << nl << "property double z" << nl << "property int nodeIndex" << nl;
+
+    const std::set<std::array<size_t, 3>> faces = mesh_faces(graph);
     out << "element face " << faces.size() << nl;
     out << "property list uchar int vertex_index" << nl;
     out << "element edge " << graph.size_edges() << nl;

@@ -7,7 +7,9 @@
 
 #include "relax_mesh.hpp"
 
+#include <array>
 #include <iosfwd>
+#include <set>
 
 namespace opencalibration_amd
 {
@@ -25,6 +27,9 @@ bool deserialize(const std::string &json, MeasurementGraph &graph, std::string *
 // digits) exactly as in the reference.
 bool serialize(const MeshGraph &graph, std::ostream &out);
 bool deserialize(std::istream &ply, MeshGraph &graph);
+// The faces the PLY writer lists, in its order (std::set order = the reference's std::sort of the faces): the textured OBJ
+// of xyz_export.cpp writes the same.
+std::set<std::array<size_t, 3>> mesh_faces(const MeshGraph &graph);
 
 struct CheckpointData // io/checkpoint.hpp:12-20; the pipeline state by its name (types/pipeline_state.hpp:25-55)
 {

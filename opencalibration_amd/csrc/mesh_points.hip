@@ -174,6 +174,16 @@ bool live(const ochip_mesh_points *m)
 }
 } // namespace
 
+// The cloud of a live object for another entry of the library that reads it where it lies (xyz_export.hip): read-only, the
+// object is not changed.  False for a handle that is not live.
+bool ochip::mesh_points_view(const ochip_mesh_points *m, ochip_ctx **ctx, const double **xyz, uint32_t *n)
+{
+    if (!live(m))
+        return false;
+    *ctx = m->ctx, *xyz = m->xyz, *n = m->n;
+    return true;
+}
+
 extern "C"
 {
 

@@ -216,6 +216,18 @@ def load():
         L.och_surface_locate_table.argtypes = [vp] + [vp] * 8
         L.och_surface_locate_table.restype = None
         L.och_dense_mesh_relax_run.argtypes = [vp, vp, vp, C.c_int, _f64p]
+        L.och_export_last_error.restype = C.c_char_p
+        L.och_cloud_outlier_bounds.argtypes = [vp, sz, vp, vp]
+        L.och_cloud_to_xyz.argtypes = [vp, sz, vp, vp, C.POINTER(sz), C.POINTER(u64)]
+        L.och_cloud_to_xyz.restype = vp
+        L.och_cloud_save_xyz.argtypes = [vp, sz, vp, vp, C.c_char_p]
+        L.och_xyz_outlier_bounds.argtypes = [vp, sz, vp, vp]
+        L.och_xyz_to_text.argtypes = [vp, sz, vp, vp, C.POINTER(sz), C.POINTER(u64)]
+        L.och_xyz_to_text.restype = vp
+        L.och_format_g6.argtypes = [vp, sz, C.c_int, vp, vp]
+        L.och_format_g6.restype = None
+        L.och_textured_obj.argtypes = [vp, sz, C.c_int64, C.c_int64, C.c_double, C.c_double, C.c_double, C.c_double, C.c_char_p,
+                                       C.c_char_p, C.POINTER(vp), C.POINTER(sz), C.POINTER(vp), C.POINTER(sz)]
         L.och_shard_block.argtypes = [u32, u32, u32, C.POINTER(u32), C.POINTER(u32)]
         L.och_shard_block.restype = None
         L.och_shard_begin.restype = vp
@@ -610,6 +622,119 @@ def rebuild_mesh(cam_xyz, previous=None, minimal=False):
     s = Surface()
     s.L.och_rebuild_mesh(cam_xyz, len(cam_xyz), previous.h if previous is not None else None, int(minimal), s.h)
     return s
+
+
+# ---- the filtered point cloud file and the textured OBJ (include/oc_host.h) -----------------------
+def _export_error(what):
+    return capi.OchipError(f"{what}: " + load().och_export_last_error().decode())
+
+
+def _cloud_source(surfaces):
+    """(entry prefix, first arguments): a list of Surface objects, or a flat array xyz [n][3]."""
+    if isinstance(surfaces, np.ndarray):
+        xyz = np.ascontiguousarray(surfaces, np.float64).reshape(-1, 3)
+        return "och_xyz", (xyz.ctypes.data if len(xyz) else None, len(xyz)), xyz
+    arr, n = _surface_array(surfaces)
+    return "och_cloud", (arr, n), surfaces
+
+
+def _take_text(L, p, n):
+    try:
+        return C.string_at(p, n)
+    finally:
+        L.och_free(p)
+
+
+def cloud_outlier_bounds(surfaces, ctx=None):
+    """filterOutliers (src/io/saveXYZ.cpp:50-105) over all clouds of the surfaces (or a flat array [n][3]): the box as
+    ((first, second),) * 3.  ctx: counted on the device, else in host loops - the same box."""
+    L = load()
+    prefix, args, keep = _cloud_source(surfaces)
+    b = np.zeros(6, np.int64)
+    fn = L.och_xyz_outlier_bounds if prefix == "och_xyz" else L.och_cloud_outlier_bounds
+    if fn(*args, ctx.h if ctx is not None else None, b.ctypes.data) != 0:
+        raise _export_error("cloud_outlier_bounds")
+    return tuple((int(b[2 * a]), int(b[2 * a + 1])) for a in range(3))
+
+
+def cloud_to_xyz(surfaces, bounds="filter", ctx=None, want_kept=False):
+    """toXYZ (src/io/saveXYZ.cpp:6-48): the point cloud file's bytes.  bounds: "filter" = cloud_outlier_bounds' box, None =
+    every point, or a box ((first, second),) * 3.  ctx: formatted on the device, else in host loops - the same bytes."""
+    L = load()
+    if isinstance(bounds, str):
+        if bounds != "filter":
+            raise ValueError('bounds: "filter", None or three (first, second) pairs')
+        bounds = cloud_outlier_bounds(surfaces, ctx)
+    b = capi.bounds6(bounds)
+    prefix, args, keep = _cloud_source(surfaces)
+    fn = L.och_xyz_to_text if prefix == "och_xyz" else L.och_cloud_to_xyz
+    n, kept = C.c_size_t(0), C.c_uint64(0)
+    p = fn(*args, ctx.h if ctx is not None else None, b.ctypes.data if b is not None else None, C.byref(n), C.byref(kept))
+    if not p:
+        raise _export_error("cloud_to_xyz")
+    text = _take_text(L, p, n.value)
+    return (text, kept.value) if want_kept else text
+
+
+def save_pointcloud(path, surfaces, ctx=None):
+    """The runner's point cloud file: toXYZ(surfaces, out, filterOutliers(surfaces)).  Returns the box."""
+    L = load()
+    bounds = cloud_outlier_bounds(surfaces, ctx)
+    arr, n = _surface_array(surfaces)
+    if L.och_cloud_save_xyz(arr, n, ctx.h if ctx is not None else None, capi.bounds6(bounds).ctypes.data, str(path).encode()) != 0:
+        raise _export_error("save_pointcloud")
+    return bounds
+
+
+def format_g6(values, fallback=True):
+    """`ostream << double` of every value as bytes.  fallback=False: the integer formatter of csrc/xyz_export.hpp alone, b""
+    where it declines (|v| outside [1e-5, 2^63) and not 0)."""
+    L = load()
+    v = np.ascontiguousarray(values, np.float64).reshape(-1)
+    text, ln = np.zeros((max(len(v), 1), 16), np.uint8), np.zeros(max(len(v), 1), np.uint8)
+    L.och_format_g6(v.ctypes.data, len(v), int(fallback), text.ctypes.data, ln.ctypes.data)
+    return text[:len(v)].view("S16").reshape(-1), ln[:len(v)]
+
+
+def textured_obj(surfaces, plan_or_geometry, name):
+    """The OBJ and MTL text of generateTexturedOBJ (src/ortho/ortho.cpp:2125-2255) for meshes over an orthomosaic: `name`.mtl
+    and `name`.jpg are the names the texts refer to.  plan_or_geometry: the plan the mosaic was rendered with (dsm_plan), or
+    (width, height, min_x, max_y, gsd_x, gsd_y).  Returns (obj_text, mtl_text) as bytes."""
+    L = load()
+    if isinstance(plan_or_geometry, dict):
+        p = plan_or_geometry
+        geometry = (p["width"], p["height"], p["min_x"], p["max_y"], p["gsd"], p["gsd"])
+    else:
+        geometry = tuple(plan_or_geometry)
+    w, h, min_x, max_y, gsd_x, gsd_y = geometry
+    arr, n = _surface_array(surfaces)
+    obj, mtl, no, nm = C.c_void_p(), C.c_void_p(), C.c_size_t(0), C.c_size_t(0)
+    if L.och_textured_obj(arr, n, int(w), int(h), float(min_x), float(max_y), float(gsd_x), float(gsd_y), (name + ".mtl").encode(),
+                          (name + ".jpg").encode(), C.byref(obj), C.byref(no), C.byref(mtl), C.byref(nm)) != 0:
+        raise _export_error("textured_obj")
+    return _take_text(L, obj.value, no.value), _take_text(L, mtl.value, nm.value)
+
+
+def save_textured_obj(path, surfaces, rgba, plan):
+    """The runner's 3-D model: `path`.obj (a trailing .obj is dropped first, as in the reference) and .mtl are written, the
+    texture - the orthomosaic's first three channels, H x W x 3 - is returned for the caller's encoder (JPEG stays outside
+    this package).  path=None: nothing is written, (obj_text, mtl_text, texture) is returned, the names built from "model".
+    rgba: the mosaic ortho_mosaic rendered with `plan`."""
+    rgba = np.asarray(rgba)
+    if rgba.ndim != 3 or rgba.shape[2] < 3 or rgba.shape[:2] != (plan["height"], plan["width"]):
+        raise ValueError(f"rgba {rgba.shape} is not the plan's {plan['height']} x {plan['width']} mosaic")
+    texture = np.ascontiguousarray(rgba[:, :, :3])
+    base = "model" if path is None else str(path)
+    if base.endswith(".obj"):
+        base = base[:-4]
+    obj, mtl = textured_obj(surfaces, plan, os.path.basename(base))
+    if path is None:
+        return obj, mtl, texture
+    with open(base + ".obj", "wb") as f:
+        f.write(obj)
+    with open(base + ".mtl", "wb") as f:
+        f.write(mtl)
+    return texture
 
 
 # ---- orthomosaic preview and DSM raster (include/oc_host.h; src/ortho/ortho.cpp) ---------------------------------------
