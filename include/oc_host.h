@@ -688,6 +688,23 @@ extern "C"
     void och_tile_progress_destroy(och_tile_progress *p);
     const char *och_tile_progress_last_error(void);
 
+    /* ---- the textured OBJ's JPEG texture (opencalibration_amd/csrc/host/jpeg_encode.cpp, csrc/jpeg_encode.hpp; the
+     * reference's cv::imwrite(jpg_path, texture) in generateTexturedOBJ, src/ortho/ortho.cpp:2096-2123; DESIGN.md section
+     * 4.17) ---------------------------------------------------------------------------------------------------------------
+     * The encoder of include/ochip.h (ochip_jpeg_*) over both routes.  ctx != NULL: the device route, as described there.
+     * ctx == NULL: the same rules in host loops - the coefficients under OpenMP over the MCUs, the entropy coder serially -
+     * over host bands, computed in feed; this route never changes by size.  Both give the same bytes.  The refusals
+     * return OCHIP_EINVAL or OCHIP_ESTATE as there (a failed device call its code) with the message in
+     * och_jpeg_last_error; a handle that create did not return or destroy has taken is refused, not followed. */
+    typedef struct och_jpeg och_jpeg;
+    int och_jpeg_create(ochip_ctx *ctx, int64_t width, int64_t height, int quality, och_jpeg **out);
+    int och_jpeg_feed(och_jpeg *e, int64_t row0, int64_t rows, const void *pixels, int pixel_stride, int on_device);
+    int64_t och_jpeg_pending(och_jpeg *e);
+    int och_jpeg_collect(och_jpeg *e, uint8_t *buf /* or NULL */, uint64_t cap, uint64_t *n);
+    int och_jpeg_finish(och_jpeg *e);
+    void och_jpeg_destroy(och_jpeg *e);
+    const char *och_jpeg_last_error(void);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1032,6 +1032,31 @@ extern "C"
     void ochip_xyz_export_destroy(ochip_xyz_export *e);
     int ochip_debug_format_g6(ochip_ctx *ctx, const double *values, uint64_t n, char *text16 /* [n][16] */, uint8_t *len /* [n] */);
 
+    /* ---- the textured OBJ's JPEG texture (opencalibration_amd/csrc/jpeg_encode.hip, the rules in csrc/jpeg_encode.hpp; the
+     *      reference's cv::imwrite(jpg_path, texture), src/ortho/ortho.cpp:2096-2123) ----
+     * Baseline JPEG, YCbCr 4:2:0, the Annex K tables scaled by quality (1..100; cv::imwrite's default is 95), no restart
+     * intervals: the bytes libjpeg-turbo writes for these settings.  An encoder belongs to one raster of width x height
+     * (each 1..65500) on one context.  feed takes rows [row0, row0 + rows) as pixels of pixel_stride 3 or 4 bytes, channels
+     * 0, 1, 2 = R, G, B: a device pointer on the context's device (on_device) or host memory, which goes through a
+     * page-locked block of the context's pool.  Bands ascend and are contiguous from row 0 and have any row count; the
+     * rows behind the last complete 16-row MCU row, 15 at most, stay on the device and precede the next feed.  A feed
+     * enqueues on the context's stream and returns; it waits - for the oldest pass alone - only when four passes (of up to
+     * 32 768 MCUs each) have not been read, and a host band waits for the feed before.  A device band stays the caller's to
+     * keep alive until the next collect or finish.  pending: the bytes collect would deliver now.  collect: *n bytes of the file into buf - the header first,
+     * after a feed the complete bytes so far, after finish the rest with EOI - and buf == NULL only reports *n; cap < *n
+     * is refused and the bytes stay.  finish: after the raster's last row.
+     * OCHIP_EINVAL and a message, before anything is launched, for a side or quality out of range, a NULL band, a stride
+     * that is neither, a gap, an overlap, rows beyond the raster, cap too small and a handle that create did not return or
+     * destroy has taken (then the message is ochip_last_error(NULL)'s); OCHIP_ESTATE for a feed after finish and a finish
+     * before the last row or a second one. */
+    typedef struct ochip_jpeg ochip_jpeg;
+    int ochip_jpeg_create(ochip_ctx *ctx, int64_t width, int64_t height, int quality, ochip_jpeg **out);
+    int ochip_jpeg_feed(ochip_jpeg *e, int64_t row0, int64_t rows, const void *pixels, int pixel_stride, int on_device);
+    int64_t ochip_jpeg_pending(ochip_jpeg *e);
+    int ochip_jpeg_collect(ochip_jpeg *e, uint8_t *buf /* or NULL */, uint64_t cap, uint64_t *n);
+    int ochip_jpeg_finish(ochip_jpeg *e);
+    void ochip_jpeg_destroy(ochip_jpeg *e);
+
 #ifdef __cplusplus
 }
 #endif

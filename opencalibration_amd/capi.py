@@ -54,6 +54,7 @@ EXPORTS = [
     "ochip_ortho_tile_thumbs_release",
     "ochip_xyz_export_create", "ochip_xyz_export_create_from_points", "ochip_xyz_export_size", "ochip_xyz_export_bounds",
     "ochip_xyz_export_text_size", "ochip_xyz_export_text", "ochip_xyz_export_destroy", "ochip_debug_format_g6",
+    "ochip_jpeg_create", "ochip_jpeg_feed", "ochip_jpeg_pending", "ochip_jpeg_collect", "ochip_jpeg_finish", "ochip_jpeg_destroy",
 ]
 
 _lib = None
@@ -298,6 +299,14 @@ def load():
         L.ochip_xyz_export_destroy.argtypes = [vp]
         L.ochip_xyz_export_destroy.restype = None
         L.ochip_debug_format_g6.argtypes = [vp, vp, u64, vp, vp]
+        L.ochip_jpeg_create.argtypes = [vp, C.c_int64, C.c_int64, i32, C.POINTER(vp)]
+        L.ochip_jpeg_feed.argtypes = [vp, C.c_int64, C.c_int64, vp, i32, i32]
+        L.ochip_jpeg_pending.argtypes = [vp]
+        L.ochip_jpeg_pending.restype = C.c_int64
+        L.ochip_jpeg_collect.argtypes = [vp, vp, u64, C.POINTER(u64)]
+        L.ochip_jpeg_finish.argtypes = [vp]
+        L.ochip_jpeg_destroy.argtypes = [vp]
+        L.ochip_jpeg_destroy.restype = None
         _lib = L
     return _lib
 

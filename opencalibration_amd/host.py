@@ -318,6 +318,15 @@ def load():
         L.och_ortho_overviews_destroy.argtypes = [vp]
         L.och_ortho_overviews_destroy.restype = None
         L.och_ortho_overviews_last_error.restype = C.c_char_p
+        L.och_jpeg_create.argtypes = [vp, i64, i64, C.c_int, C.POINTER(vp)]
+        L.och_jpeg_feed.argtypes = [vp, i64, i64, vp, C.c_int, C.c_int]
+        L.och_jpeg_pending.argtypes = [vp]
+        L.och_jpeg_pending.restype = i64
+        L.och_jpeg_collect.argtypes = [vp, vp, C.c_uint64, C.POINTER(C.c_uint64)]
+        L.och_jpeg_finish.argtypes = [vp]
+        L.och_jpeg_destroy.argtypes = [vp]
+        L.och_jpeg_destroy.restype = None
+        L.och_jpeg_last_error.restype = C.c_char_p
         L.och_tile_progress_create.argtypes = [vp, _f64p, C.c_int32, C.c_int32, C.POINTER(vp)]
         L.och_tile_progress_feed.argtypes = [vp, C.c_int, i64, i64, C.c_int, vp, vp]
         L.och_tile_progress_seek.argtypes = [vp, C.c_int, i64]
@@ -715,25 +724,38 @@ def textured_obj(surfaces, plan_or_geometry, name):
     return _take_text(L, obj.value, no.value), _take_text(L, mtl.value, nm.value)
 
 
-def save_textured_obj(path, surfaces, rgba, plan):
+def save_textured_obj(path, surfaces, rgba, plan, jpeg=False, ctx=None, quality=95):
     """The runner's 3-D model: `path`.obj (a trailing .obj is dropped first, as in the reference) and .mtl are written, the
-    texture - the orthomosaic's first three channels, H x W x 3 - is returned for the caller's encoder (JPEG stays outside
-    this package).  path=None: nothing is written, (obj_text, mtl_text, texture) is returned, the names built from "model".
-    rgba: the mosaic ortho_mosaic rendered with `plan`."""
-    rgba = np.asarray(rgba)
-    if rgba.ndim != 3 or rgba.shape[2] < 3 or rgba.shape[:2] != (plan["height"], plan["width"]):
-        raise ValueError(f"rgba {rgba.shape} is not the plan's {plan['height']} x {plan['width']} mosaic")
-    texture = np.ascontiguousarray(rgba[:, :, :3])
+    texture - the orthomosaic's first three channels, H x W x 3 - is returned for the caller's encoder.  path=None: nothing
+    is written, (obj_text, mtl_text, texture) is returned, the names built from "model".
+    rgba: the mosaic ortho_mosaic rendered with `plan`.
+    jpeg=True: `path`.jpg, the name the MTL refers to, is written too (encode_jpeg: ctx None the CPU route, else on ctx's
+    device, where rgba may be a CUDA tensor), and the texture returned - alone, or as the third value with path=None - is the
+    file's bytes instead of the pixels."""
+    if jpeg and not isinstance(rgba, np.ndarray) and hasattr(rgba, "is_cuda"):
+        shape = tuple(int(v) for v in rgba.shape)
+    else:
+        rgba = np.asarray(rgba)
+        shape = rgba.shape
+    if len(shape) != 3 or shape[2] < 3 or shape[:2] != (plan["height"], plan["width"]):
+        raise ValueError(f"rgba {shape} is not the plan's {plan['height']} x {plan['width']} mosaic")
     base = "model" if path is None else str(path)
     if base.endswith(".obj"):
         base = base[:-4]
     obj, mtl = textured_obj(surfaces, plan, os.path.basename(base))
+    if jpeg:
+        texture = encode_jpeg(rgba if shape[2] in (3, 4) else rgba[:, :, :3], ctx=ctx, quality=quality)
+    else:
+        texture = np.ascontiguousarray(rgba[:, :, :3])
     if path is None:
         return obj, mtl, texture
     with open(base + ".obj", "wb") as f:
         f.write(obj)
     with open(base + ".mtl", "wb") as f:
         f.write(mtl)
+    if jpeg:
+        with open(base + ".jpg", "wb") as f:
+            f.write(texture)
     return texture
 
 
@@ -1423,7 +1445,7 @@ def color_balance_remove_gauge(xy, offsets):
 
 
 def ortho_mosaic(plan, graph, surfaces, images, mesh=None, config=None, color_balance=None, tile_rows=1, out=None,
-                 overviews=False, progress=None, progress_passes=(1, 2)):
+                 overviews=False, progress=None, progress_passes=(1, 2), jpeg=None, jpeg_quality=95):
     """The blended full-resolution orthomosaic of `plan` (dsm_plan), band by band of tile_rows output tile rows: DSM ->
     layers (ortho_layers) -> blend (ortho_blend).  mesh (an OrthoMesh): every step on its device, images as CUDA tensors,
     into `out` (a (height, width, 4) uint8 CUDA tensor, made when None); None: the CPU route, numpy images, into a host
@@ -1440,26 +1462,30 @@ def ortho_mosaic(plan, graph, surfaces, images, mesh=None, config=None, color_ba
     With "solve" the first sweep emits pass 1 and the second pass 2, otherwise the single sweep emits a band's pass-1 tiles
     and then its pass-2 tiles.  Band k's updates are collected after band k + 1 has been enqueued, so the device never
     waits for the callback; the rest are flushed before the function returns.  An exception from the callback propagates
-    after the stream and the builders are closed.  None: nothing is allocated or launched for it."""
+    after the stream and the builders are closed.  None: nothing is allocated or launched for it.
+    jpeg: a path or a binary file object that receives the mosaic as a JPEG of quality jpeg_quality (JpegEncoder, the
+    textured OBJ's texture): each band is fed right after its blend - with "solve" in the second sweep alone - and the bytes
+    are written as they complete; the file is closed (a path) or flushed (an object) before the function returns and on an
+    exception.  None: nothing is allocated or launched for it."""
     return _mosaic(plan, graph, surfaces, mesh, config, color_balance, tile_rows, out, images=images, overviews=overviews,
-                   progress=progress, progress_passes=progress_passes)
+                   progress=progress, progress_passes=progress_passes, jpeg=jpeg, jpeg_quality=jpeg_quality)
 
 
 def ortho_mosaic_streamed(plan, graph, surfaces, fetch, mesh, capacity, config=None, color_balance=None, tile_rows=1, out=None,
-                          overviews=False, progress=None, progress_passes=(1, 2)):
+                          overviews=False, progress=None, progress_passes=(1, 2), jpeg=None, jpeg_quality=95):
     """ortho_mosaic on mesh's device without the source images resident: fetch(i) returns involved camera i's BGR image
     (ortho_layers_cameras' order) as a numpy array or a page-locked torch CPU tensor, and at most `capacity` images are on
     the device at a time (OrthoStream).  Band k + 1's ahead uploads are issued before band k renders, so that they run
     beside it when the images are page-locked.  color_balance as ortho_mosaic's; "solve" renders the layers twice, the
     second sweep starting from the images the first one left on the device.  Returns the (height, width, 4) RGBA tensor,
-    with overviews=True (tensor, dict(rgba=[...], dsm=[...])) as ortho_mosaic does.  progress, progress_passes: as
-    ortho_mosaic's."""
+    with overviews=True (tensor, dict(rgba=[...], dsm=[...])) as ortho_mosaic does.  progress, progress_passes, jpeg,
+    jpeg_quality: as ortho_mosaic's."""
     return _mosaic(plan, graph, surfaces, mesh, config, color_balance, tile_rows, out, fetch=fetch, capacity=capacity,
-                   overviews=overviews, progress=progress, progress_passes=progress_passes)
+                   overviews=overviews, progress=progress, progress_passes=progress_passes, jpeg=jpeg, jpeg_quality=jpeg_quality)
 
 
 def _mosaic(plan, graph, surfaces, mesh, config, color_balance, tile_rows, out, images=None, fetch=None, capacity=None,
-            overviews=False, progress=None, progress_passes=(1, 2)):
+            overviews=False, progress=None, progress_passes=(1, 2), jpeg=None, jpeg_quality=95):
     """The band loop of ortho_mosaic (images) and ortho_mosaic_streamed (fetch, capacity): the two differ in where a band's
     layers come from, ortho_layers over the resident images or an OrthoStream's render behind the band's uploads."""
     cfg = {**LAYERS_CONFIG, **BLEND_CONFIG, **(config or {})}
@@ -1483,6 +1509,7 @@ def _mosaic(plan, graph, surfaces, mesh, config, color_balance, tile_rows, out, 
     if passes - {TILE_PASS_LAYERS, TILE_PASS_BLEND}:
         raise ValueError("progress_passes names 1 (the layers) and 2 (the blend)")
     tiles = TileProgress(plan, cfg["tile_size"], nl, ctx=ctx) if passes else None
+    texture = None
 
     def deliver(keep):
         """the fed bands' updates to the callback, oldest first, until `keep` bands are pending"""
@@ -1523,11 +1550,15 @@ def _mosaic(plan, graph, surfaces, mesh, config, color_balance, tile_rows, out, 
             if builders:  # behind the blend on the context's stream: no wait of its own
                 builders[0].feed(row0, out[row0:row0 + rows])
                 builders[1].feed(row0, dsm)
+            if texture is not None:  # behind the blend on the context's stream as well
+                texture.feed(row0, out[row0:row0 + rows])
         if emit:  # this band is enqueued behind the bands before it: their updates are due
             deliver(tiles.pending() - before)
         return layers["correspondences"]
 
     try:
+        if jpeg is not None:
+            texture = _JpegSink(jpeg, w, h, ctx, jpeg_quality, mesh is not None)
         bands = range(-(-h // band_rows))
         if color_balance == "solve":
             corr = [band(k, None, False, passes & {TILE_PASS_LAYERS}) for k in bands]
@@ -1541,9 +1572,13 @@ def _mosaic(plan, graph, surfaces, mesh, config, color_balance, tile_rows, out, 
             band(k, color_balance, True, passes)
         if tiles is not None:
             deliver(0)
+        if texture is not None:
+            texture.finish()
         if builders:
             return out, dict(rgba=builders[0].finish(), dsm=builders[1].finish())
     finally:
+        if texture is not None:
+            texture.close()
         if stream is not None:
             stream.close()
         for b in builders:
@@ -1709,6 +1744,130 @@ def ortho_tile_updates(plan, pixels, pass_, row0=0, tile_size=None, weight=None,
         t.seek(pass_, row0)  # a band in the middle of the raster: the pass's order starts where it does
         t.feed(pass_, row0, pixels, weight)
         return t.collect()
+
+
+# ---- the textured OBJ's JPEG texture (include/oc_host.h) ------------------------------------------------
+class JpegEncoder:
+    """A baseline JPEG (YCbCr 4:2:0, cv::imwrite's settings) of a width x height raster fed band by band (och_jpeg_*; the
+    rules: DESIGN.md §4.17).  ctx None: the CPU route, numpy bands.  ctx with on_device: CUDA tensors on ctx's device, fed
+    on the context's stream - the caller has torch's work on a band finished before feed, as ortho_blend does.  ctx
+    without on_device: numpy bands through the device.  feed(row0, band): band is (rows, width, 3) or (rows, width, 4) uint8,
+    channels R, G, B first; bands ascend and are contiguous from row 0, of any row count.  collect(): the file's bytes
+    that are complete and not collected yet (the header first).  finish(): the rest, EOI included.  A gap, an overlap, a
+    feed after finish and a finish before the last row raise OchipError naming the rows."""
+
+    def __init__(self, width, height, ctx=None, quality=95, on_device=False):
+        self.L, self.width, self.height, self.ctx = load(), int(width), int(height), ctx
+        self.on_device = bool(on_device)
+        if self.on_device and ctx is None:
+            raise ValueError("bands on the device need the device route (ctx)")
+        self.h = None
+        self._keep = []
+        h = C.c_void_p()
+        if self.L.och_jpeg_create(ctx.h if ctx is not None else None, self.width, self.height, int(quality), C.byref(h)) != 0:
+            raise capi.OchipError(self._error())
+        self.h = h
+
+    def _error(self):
+        return self.L.och_jpeg_last_error().decode()
+
+    def close(self):
+        if getattr(self, "h", None):
+            if self.ctx is None or getattr(self.ctx, "h", None):  # as OrthoStream.close: the context may be gone
+                self.L.och_jpeg_destroy(self.h)
+            self.h = None
+            self._keep = []
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        self.close()
+
+    def feed(self, row0, band):
+        shape = tuple(int(v) for v in band.shape)
+        if len(shape) != 3 or shape[1] != self.width or shape[2] not in (3, 4) or str(band.dtype).replace("torch.", "") != "uint8":
+            raise ValueError(f"a band of this encoder is (rows, {self.width}, 3 or 4) uint8")
+        if self.on_device:
+            ptr = _device_ptr(band, "torch.uint8", shape, "band", self.ctx.device)
+            self._keep.append(band)  # the kernels may still read it: alive until collect, finish or close
+        else:
+            band = np.ascontiguousarray(band)
+            ptr = band.ctypes.data
+        if shape[0] > 0 and self.L.och_jpeg_feed(self.h, int(row0), shape[0], ptr, shape[2], int(self.on_device)) != 0:
+            raise capi.OchipError(self._error())
+
+    def pending(self):
+        """the bytes collect() would return now"""
+        return int(self.L.och_jpeg_pending(self.h))
+
+    def collect(self, cap=None):
+        """cap: the room offered (default: exactly what is ready)"""
+        return self._collect(cap).tobytes()
+
+    def _collect(self, cap=None):
+        """collect() as a uint8 array, for a writer that takes the buffer as it is"""
+        n = C.c_uint64(0)
+        if self.L.och_jpeg_collect(self.h, None, 0, C.byref(n)) != 0:
+            raise capi.OchipError(self._error())
+        self._keep = []  # collect has waited for the kernels
+        buf = np.empty(max(int(n.value if cap is None else cap), 1), np.uint8)
+        if self.L.och_jpeg_collect(self.h, buf.ctypes.data, int(n.value if cap is None else cap), C.byref(n)) != 0:
+            raise capi.OchipError(self._error())
+        return buf[:n.value]
+
+    def finish(self):
+        if self.L.och_jpeg_finish(self.h) != 0:
+            raise capi.OchipError(self._error())
+        return self.collect()
+
+
+def encode_jpeg(raster, ctx=None, quality=95):
+    """The JPEG file (bytes) of a whole (height, width, 3 or 4) uint8 raster, channels R, G, B first, in one feed: a numpy
+    array (ctx None: the CPU route, else through ctx's device) or a CUDA tensor on ctx's device."""
+    on_device = not isinstance(raster, np.ndarray)
+    if len(raster.shape) != 3:
+        raise ValueError("a raster is (height, width, 3 or 4) uint8")
+    if on_device:
+        if ctx is None:
+            raise ValueError("a device raster needs the device route (ctx)")
+        import torch
+
+        torch.cuda.current_stream(raster.device).synchronize()  # the kernels run on the context's own stream
+    with JpegEncoder(int(raster.shape[1]), int(raster.shape[0]), ctx=ctx, quality=quality, on_device=on_device) as e:
+        e.feed(0, raster)
+        return e.collect() + e.finish()
+
+
+class _JpegSink:
+    """_mosaic's jpeg argument: a path (opened here, closed on close) or a binary file object (flushed on close)"""
+
+    def __init__(self, target, width, height, ctx, quality, on_device):
+        self.own = isinstance(target, (str, bytes, os.PathLike))
+        self.f = open(target, "wb") if self.own else target
+        try:
+            self.enc = JpegEncoder(width, height, ctx=ctx, quality=quality, on_device=on_device)
+        except Exception:
+            if self.own:
+                self.f.close()
+            raise
+
+    def feed(self, row0, band):
+        self.f.write(self.enc._collect())  # what the bands before completed: waits for them alone, not for this band's render
+        self.enc.feed(row0, band)
+
+    def finish(self):
+        self.f.write(self.enc.finish())
+
+    def close(self):
+        self.enc.close()
+        if self.own:
+            self.f.close()
+        else:
+            self.f.flush()
 
 
 # ---- averaged overview levels of the orthomosaic and the DSM (include/oc_host.h; DESIGN.md §4.13) -----------------------
