@@ -705,6 +705,23 @@ extern "C"
     void och_jpeg_destroy(och_jpeg *e);
     const char *och_jpeg_last_error(void);
 
+    /* ---- baseline JPEG decoding of the load stage (opencalibration_amd/csrc/host/jpeg_decode.cpp, csrc/jpeg_decode.hpp;
+     *      the reference's cv::imread(path), src/extract/extract_image.cpp:18-21) ----
+     * och_jpeg_info: the headers of one file - size (oriented when apply_orientation), components, sampling, restart
+     * interval, orientation, status (OCHIP_JPEG_*) - without a context; -1 only for NULL arguments.
+     * The decoder of include/ochip.h (ochip_jpeg_decoder_*) over both routes.  ctx != NULL: the device route, out is a device
+     * pointer.  ctx == NULL: the same pixels computed here in loops, OpenMP over the images, out is host memory.  -1 + a
+     * message in och_jpeg_decode_last_error; a handle that create did not return or destroy has taken is refused, not
+     * followed. */
+    int och_jpeg_info(const uint8_t *data, uint64_t size, int apply_orientation, ochip_jpeg_file_info *out);
+    typedef struct och_jpeg_decoder och_jpeg_decoder;
+    int och_jpeg_decoder_create(ochip_ctx *ctx, int subsequence_bits, och_jpeg_decoder **out);
+    int och_jpeg_decoder_decode(och_jpeg_decoder *d, int64_t n, const uint8_t *const *files, const uint64_t *sizes,
+                                int apply_orientation, void *out, uint64_t out_cap, const uint64_t *offsets /* or NULL */,
+                                ochip_jpeg_file_info *info /* [n] */, int32_t *rounds /* [2] or NULL */);
+    void och_jpeg_decoder_destroy(och_jpeg_decoder *d);
+    const char *och_jpeg_decode_last_error(void);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1057,6 +1057,47 @@ extern "C"
     int ochip_jpeg_finish(ochip_jpeg *e);
     void ochip_jpeg_destroy(ochip_jpeg *e);
 
+    /* ---- baseline JPEG decoding of the load stage (opencalibration_amd/csrc/jpeg_decode.hip, the rules in
+     *      csrc/jpeg_decode.hpp; the reference's cv::imread(path), src/extract/extract_image.cpp:18-21; DESIGN.md section
+     *      4.18) ----
+     * The pixels libjpeg-turbo's default decode gives (islow inverse DCT, triangle chroma upsampling, B G R order) with the
+     * EXIF orientation applied, for a batch of files per call.  The host reads the headers only; the entropy-coded bytes go
+     * to the device once and every step from them to the pixels is a kernel on the context's stream.  Taken: SOF0 / SOF1
+     * with Huffman coding, 8 bits, one component or Y Cb Cr with luma 1x1, 2x1 or 2x2, one interleaved scan, any DHT, 8-bit
+     * DQT, DRI / RSTn.  status per file: OCHIP_JPEG_OK, OCHIP_JPEG_UNSUPPORTED (progressive, arithmetic, 12 bits, four
+     * components, other samplings, several scans, 16-bit DQT, RGB files) or OCHIP_JPEG_CORRUPT (truncated, not decodable:
+     * no picture is written where libjpeg would warn and deliver a partly grey one).
+     * create: subsequence_bits is the length of the pieces the scan is decoded in, a multiple of 32 from 32 on; 0: the
+     * default.  decode: files[i] / sizes[i] are host memory; out is a device pointer of out_cap bytes on the context's
+     * device; image i goes to out + offsets[i] as [height][width][3] uint8 (offsets == NULL: back to back), width and height
+     * as info[i] reports them: with apply_orientation the oriented ones, and info[i].offset says where it went.  A file
+     * whose status is not OK writes nothing and leaves its neighbours alone; one whose headers are refused takes no room,
+     * one whose scan turns out corrupt keeps the room its headers asked for.  At most 65 535 files a call.  A header that
+     * promises more blocks than its scan has bits for two each is corrupt; bytes of a scan behind its last block are not
+     * read.  rounds (or NULL): [0] the launches of the synchronisation kernel, [1] the most rounds a
+     * workgroup ran inside one.  The call returns when the pixels are there.
+     * OCHIP_EINVAL and a message, before anything is launched, for a NULL or dead handle (then the message is
+     * ochip_last_error(NULL)'s), subsequence_bits out of range, NULL arguments and an output that is too small. */
+#define OCHIP_JPEG_OK 0
+#define OCHIP_JPEG_UNSUPPORTED 1
+#define OCHIP_JPEG_CORRUPT 2
+    typedef struct ochip_jpeg_file_info
+    {
+        int32_t width, height;   /* as decoded: oriented when the orientation was applied */
+        int32_t components;      /* 1 or 3 */
+        int32_t h_samp, v_samp;  /* luma sampling factors */
+        int32_t restart_interval;
+        int32_t orientation;     /* EXIF tag 0x0112, 1 .. 8; 1 when absent */
+        int32_t status;
+        uint64_t offset;         /* decode: the image's first byte in out; ~0: its headers were refused, it took no room */
+    } ochip_jpeg_file_info;
+    typedef struct ochip_jpeg_decoder ochip_jpeg_decoder;
+    int ochip_jpeg_decoder_create(ochip_ctx *ctx, int subsequence_bits, ochip_jpeg_decoder **out);
+    int ochip_jpeg_decoder_decode(ochip_jpeg_decoder *d, int64_t n, const uint8_t *const *files, const uint64_t *sizes,
+                                  int apply_orientation, void *out, uint64_t out_cap, const uint64_t *offsets /* or NULL */,
+                                  ochip_jpeg_file_info *info /* [n] */, int32_t *rounds /* [2] or NULL */);
+    void ochip_jpeg_decoder_destroy(ochip_jpeg_decoder *d);
+
 #ifdef __cplusplus
 }
 #endif

@@ -55,6 +55,7 @@ EXPORTS = [
     "ochip_xyz_export_create", "ochip_xyz_export_create_from_points", "ochip_xyz_export_size", "ochip_xyz_export_bounds",
     "ochip_xyz_export_text_size", "ochip_xyz_export_text", "ochip_xyz_export_destroy", "ochip_debug_format_g6",
     "ochip_jpeg_create", "ochip_jpeg_feed", "ochip_jpeg_pending", "ochip_jpeg_collect", "ochip_jpeg_finish", "ochip_jpeg_destroy",
+    "ochip_jpeg_decoder_create", "ochip_jpeg_decoder_decode", "ochip_jpeg_decoder_destroy",
 ]
 
 _lib = None
@@ -307,6 +308,10 @@ def load():
         L.ochip_jpeg_finish.argtypes = [vp]
         L.ochip_jpeg_destroy.argtypes = [vp]
         L.ochip_jpeg_destroy.restype = None
+        L.ochip_jpeg_decoder_create.argtypes = [vp, i32, C.POINTER(vp)]
+        L.ochip_jpeg_decoder_decode.argtypes = [vp, C.c_int64, vp, vp, i32, vp, u64, vp, vp, vp]
+        L.ochip_jpeg_decoder_destroy.argtypes = [vp]
+        L.ochip_jpeg_decoder_destroy.restype = None
         _lib = L
     return _lib
 

@@ -327,6 +327,12 @@ def load():
         L.och_jpeg_destroy.argtypes = [vp]
         L.och_jpeg_destroy.restype = None
         L.och_jpeg_last_error.restype = C.c_char_p
+        L.och_jpeg_info.argtypes = [vp, C.c_uint64, C.c_int, vp]
+        L.och_jpeg_decoder_create.argtypes = [vp, C.c_int, C.POINTER(vp)]
+        L.och_jpeg_decoder_decode.argtypes = [vp, i64, vp, vp, C.c_int, vp, C.c_uint64, vp, vp, vp]
+        L.och_jpeg_decoder_destroy.argtypes = [vp]
+        L.och_jpeg_decoder_destroy.restype = None
+        L.och_jpeg_decode_last_error.restype = C.c_char_p
         L.och_tile_progress_create.argtypes = [vp, _f64p, C.c_int32, C.c_int32, C.POINTER(vp)]
         L.och_tile_progress_feed.argtypes = [vp, C.c_int, i64, i64, C.c_int, vp, vp]
         L.och_tile_progress_seek.argtypes = [vp, C.c_int, i64]
@@ -1842,6 +1848,142 @@ def encode_jpeg(raster, ctx=None, quality=95):
         return e.collect() + e.finish()
 
 
+# ---- baseline JPEG decoding of the load stage (include/oc_host.h) -----------------------------------------
+JPEG_STATUS = ("ok", "unsupported", "corrupt")
+JPEG_INFO_DTYPE = np.dtype([("width", "<i4"), ("height", "<i4"), ("components", "<i4"), ("h_samp", "<i4"), ("v_samp", "<i4"),
+                            ("restart_interval", "<i4"), ("orientation", "<i4"), ("status", "<i4"), ("offset", "<u8")])
+JPEG_LOAD_PIXEL_BUDGET = 1 << 28  # Graph.load_jpegs decodes chunks of at most this many pixels
+
+
+def _jpeg_bytes(f):
+    """a file of the decoder: bytes-like as it is, anything else a path"""
+    if isinstance(f, (bytes, bytearray, memoryview)):
+        return bytes(f)
+    with open(f, "rb") as fh:
+        return fh.read()
+
+
+def _jpeg_info_dict(rec):
+    d = {k: int(rec[k]) for k in JPEG_INFO_DTYPE.names if k != "offset"}
+    d["sampling"] = (d.pop("h_samp"), d.pop("v_samp"))
+    d["status"] = JPEG_STATUS[d["status"]]
+    return d
+
+
+def jpeg_info(data, apply_orientation=True):
+    """The headers of a JPEG file (bytes or a path): dict(width, height, components, sampling=(h, v) of the luma,
+    restart_interval, orientation, status "ok" / "unsupported" / "corrupt").  width and height are the oriented ones when
+    apply_orientation.  Reads no entropy-coded bit, needs no context."""
+    data = _jpeg_bytes(data)
+    rec = np.zeros(1, JPEG_INFO_DTYPE)
+    buf = np.frombuffer(data, np.uint8) if len(data) else np.zeros(1, np.uint8)
+    if load().och_jpeg_info(buf.ctypes.data, len(data), int(bool(apply_orientation)), rec.ctypes.data) != 0:
+        raise capi.OchipError(load().och_jpeg_decode_last_error().decode())
+    return _jpeg_info_dict(rec[0])
+
+
+class JpegBatch:
+    """What JpegDecoder.decode returns: status (a name per file), info (jpeg_info's dict per file), shapes ((height, width)
+    per file, None where the file was refused), offsets (the image's first byte in pixels, None likewise), pixels (flat
+    uint8: a CUDA tensor on the device route, a numpy array on the CPU route) and rounds ((launches of the synchronisation
+    kernel, most rounds inside one); (0, 0) on the CPU route).  image(i): the (height, width, 3) B G R view of file i."""
+
+    def __init__(self, info, offsets, pixels, rounds):
+        self.info, self.offsets, self.pixels, self.rounds = info, offsets, pixels, rounds
+        self.status = [d["status"] for d in info]
+        self.shapes = [(d["height"], d["width"]) if d["status"] == "ok" else None for d in info]
+
+    def image(self, i):
+        if self.shapes[i] is None:
+            raise ValueError(f"file {i} is {self.status[i]}")
+        h, w = self.shapes[i]
+        return self.pixels[self.offsets[i]:self.offsets[i] + h * w * 3].reshape(h, w, 3)
+
+
+class JpegDecoder:
+    """Baseline JPEG files to B G R pixels, a batch per call (och_jpeg_decoder_*; the rules: DESIGN.md §4.18): what
+    cv::imread gives - libjpeg-turbo's default decode with the EXIF orientation applied.  ctx: the device route, the pixels
+    stay on ctx's device; ctx None: the host loops.  subsequence_bits: the length of the pieces a scan is decoded in on the
+    device, a multiple of 32; 0: the default."""
+
+    def __init__(self, ctx=None, subsequence_bits=0):
+        self.L, self.ctx, self.h = load(), ctx, None
+        h = C.c_void_p()
+        if self.L.och_jpeg_decoder_create(ctx.h if ctx is not None else None, int(subsequence_bits), C.byref(h)) != 0:
+            raise capi.OchipError(self._error())
+        self.h = h
+
+    def _error(self):
+        return self.L.och_jpeg_decode_last_error().decode()
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.L.och_jpeg_decoder_destroy(self.h)
+            self.h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        self.close()
+
+    def decode(self, files, out=None, apply_orientation=True):
+        """files: bytes objects or paths.  out: where the pixels go - a flat uint8 CUDA tensor on ctx's device (numpy array on
+        the CPU route) with room for the images back to back; None: the headers are read once more to size one.  A file
+        whose headers are refused takes no room; one whose scan turns out corrupt keeps the room its headers asked for
+        and writes nothing.  Either leaves the others alone.  Returns a JpegBatch."""
+        datas = [_jpeg_bytes(f) for f in files]
+        n = len(datas)
+        bufs = [np.frombuffer(d, np.uint8) if len(d) else np.zeros(1, np.uint8) for d in datas]
+        ptrs = np.array([b.ctypes.data for b in bufs] + [0], np.uint64)
+        sizes = np.array([len(d) for d in datas] + [0], np.uint64)
+        rec = np.zeros(n + 1, JPEG_INFO_DTYPE)
+        apply = int(bool(apply_orientation))
+        if out is None:
+            total = 0
+            for i in range(n):
+                if self.L.och_jpeg_info(int(ptrs[i]), int(sizes[i]), apply, rec[i:].ctypes.data) != 0:
+                    raise capi.OchipError(self._error())
+                total += int(rec[i]["width"]) * int(rec[i]["height"]) * 3 if rec[i]["status"] == 0 else 0
+        if self.ctx is not None:
+            import torch
+
+            if out is not None and not hasattr(out, "is_cuda"):
+                raise ValueError("out must be a flat uint8 CUDA tensor on the context's device")
+            if out is None:
+                out = torch.empty(max(total, 1), dtype=torch.uint8, device=f"cuda:{self.ctx.device}")
+                torch.cuda.current_stream(out.device).synchronize()
+            cap = int(out.numel())
+            ptr = _device_ptr(out, "torch.uint8", (cap,), "out", self.ctx.device)
+        else:
+            if out is None:
+                out = np.empty(max(total, 1), np.uint8)
+            if not isinstance(out, np.ndarray) or out.dtype != np.uint8 or out.ndim != 1 or not out.flags.c_contiguous:
+                raise ValueError("out of the CPU route is a flat contiguous uint8 array")
+            cap, ptr = out.size, out.ctypes.data
+        rounds = np.zeros(2, np.int32)
+        if self.L.och_jpeg_decoder_decode(self.h, n, ptrs.ctypes.data, sizes.ctypes.data, apply, ptr, cap, None, rec.ctypes.data,
+                                          rounds.ctypes.data) != 0:
+            raise capi.OchipError(self._error())
+        info = [_jpeg_info_dict(r) for r in rec[:n]]
+        offsets = [int(r["offset"]) if d["status"] == "ok" else None for r, d in zip(rec[:n], info)]
+        return JpegBatch(info, offsets, out, (int(rounds[0]), int(rounds[1])))
+
+
+def decode_jpeg(data, ctx=None, apply_orientation=True):
+    """The (height, width, 3) B G R uint8 array of one JPEG file (bytes or a path), as cv::imread returns it.  ctx None: the
+    host loops; else decoded on ctx's device and fetched.  A refused file raises OchipError with its status."""
+    with JpegDecoder(ctx) as d:
+        b = d.decode([data], apply_orientation=apply_orientation)
+    if b.status[0] != "ok":
+        raise capi.OchipError(f"decode_jpeg: the file is {b.status[0]}")
+    img = b.image(0)
+    return img if isinstance(img, np.ndarray) else img.cpu().numpy()
+
+
 class _JpegSink:
     """_mosaic's jpeg argument: a path (opened here, closed on close) or a binary file object (flushed on close)"""
 
@@ -2310,6 +2452,55 @@ class Graph:
         if thumbnails:
             self.make_thumbnails(images_bgr, ids[:n], ctx, device_shape)
         return totals[0] / max(n, 1), totals[1] / max(n, 1)
+
+    def load_jpegs(self, ctx, files, model, positions, max_keypoints=30000, thumbnails=False, chunk=None):
+        """load_images from JPEG files (bytes objects or paths), all of one decoded size: decoded on ctx's device in chunks
+        of `chunk` images (None: as many as JPEG_LOAD_PIXEL_BUDGET pixels hold) and extracted from the same buffer, which
+        also gives the thumbnails.  A file the decoder refuses raises OchipError naming the file and its status before
+        anything of its chunk is loaded.  Returns load_images' means over all files."""
+        files = list(files)
+        n = len(files)
+        pos = np.ascontiguousarray(positions, np.float64).reshape(-1, 3)
+        if len(pos) != n:
+            raise ValueError("one position per file")
+
+        def name(i):
+            return f"file {i}" if isinstance(files[i], (bytes, bytearray, memoryview)) else f"file {i} ({os.fspath(files[i])})"
+
+        import torch
+
+        shape, at, sums, pixels = None, 0, np.zeros(2), None
+        with JpegDecoder(ctx) as dec:
+            while at < n:
+                if shape is None:
+                    first = jpeg_info(files[at])
+                    if first["status"] != "ok":
+                        raise capi.OchipError(f"load_jpegs: {name(at)} is {first['status']}")
+                    shape = (first["height"], first["width"])
+                step = int(chunk) if chunk else max(1, JPEG_LOAD_PIXEL_BUDGET // (shape[0] * shape[1]))
+                m = min(step, n - at)
+                if pixels is None or pixels.numel() < m * shape[0] * shape[1] * 3:
+                    pixels = torch.empty(m * shape[0] * shape[1] * 3, dtype=torch.uint8, device=f"cuda:{ctx.device}")
+                    torch.cuda.current_stream(pixels.device).synchronize()
+                try:
+                    batch = dec.decode(files[at:at + step], out=pixels)  # one pass over each file's bytes
+                except capi.OchipError as e:
+                    if "the output holds" not in str(e):
+                        raise
+                    batch = dec.decode(files[at:at + step])  # a file of another size: decoded apart so it can be named
+                m = len(batch.status)
+                for i in range(m):
+                    if batch.status[i] != "ok":
+                        raise capi.OchipError(f"load_jpegs: {name(at + i)} is {batch.status[i]}")
+                    if batch.shapes[i] != shape:
+                        raise capi.OchipError(f"load_jpegs: {name(at + i)} is {batch.shapes[i][1]} x {batch.shapes[i][0]}, "
+                                              f"the first file {shape[1]} x {shape[0]}")
+                f, s = self.load_images(ctx, batch.pixels.data_ptr(), model, pos[at:at + m], max_keypoints,
+                                        device_shape=(m, shape[0], shape[1]), thumbnails=thumbnails)
+                sums += (f * m, s * m)
+                del batch
+                at += m
+        return sums[0] / max(n, 1), sums[1] / max(n, 1)
 
     def load_link_images(self, ctx, images_bgr, model, positions, orientations=None, max_keypoints=30000, device_shape=None):
         """Load and link overlapped (och_graph_load_link_images): extraction streams in chunks and ranges of links run
