@@ -466,42 +466,7 @@ __device__ __forceinline__ void plane_candidate_body(const relax_dev &P, const d
     const int t = threadIdx.x;
     // candidate state
     double sn = 0, xn = 0;
-    for (uint32_t c = t; c < P.n_cams; c += LM_TG)
-    {
-        const int tc = P.cam_t[c];
-        const double *q = P.cam_q + (size_t)c * 4;
-        double *o = P.cam_q2 + (size_t)c * 4;
-        if (tc < 0)
-        {
-            for (int k = 0; k < 4; k++)
-                o[k] = q[k];
-            continue;
-        }
-        double d[3];
-        for (int k = 0; k < 3; k++)
-            d[k] = alpha * (-y[tc + k] * scale[tc + k]);
-        const double nrm = sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
-        if (nrm == 0.0)
-        {
-            for (int k = 0; k < 4; k++)
-                o[k] = q[k];
-        }
-        else
-        {
-            const double s = sin(nrm) / nrm;
-            const double dx = s * d[0], dy = s * d[1], dz = s * d[2], dw = cos(nrm);
-            const double qx = q[0], qy = q[1], qz = q[2], qw = q[3];
-            o[3] = dw * qw - dx * qx - dy * qy - dz * qz;
-            o[0] = dw * qx + dx * qw + dy * qz - dz * qy;
-            o[1] = dw * qy + dy * qw + dz * qx - dx * qz;
-            o[2] = dw * qz + dz * qw + dx * qy - dy * qx;
-        }
-        for (int k = 0; k < 4; k++)
-        {
-            sn += (q[k] - o[k]) * (q[k] - o[k]);
-            xn += o[k] * o[k];
-        }
-    }
+    lm_candidate_cams<LM_TG>(P.n_cams, P.cam_t, P.cam_q, P.cam_q2, y, scale, alpha, &sn, &xn);
     if (t < 3)
     {
         const int tz = P.z_t[t];
@@ -517,16 +482,9 @@ __device__ __forceinline__ void plane_candidate_body(const relax_dev &P, const d
     __syncthreads();
     for (int q = 0; q < 2; q++)
     {
-        sh[t] = q == 0 ? sn : xn;
-        __syncthreads();
-        for (int s = LM_TG / 2; s > 0; s >>= 1)
-        {
-            if (t < s)
-                sh[t] += sh[t + s];
-            __syncthreads();
-        }
+        const double sum = lm_block_sum<LM_TG>(q == 0 ? sn : xn, sh);
         if (t == 0)
-            scal[2 + q] = sh[0];
+            scal[2 + q] = sum;
         __syncthreads();
     }
 }
@@ -556,18 +514,6 @@ __global__ void lm_accept_kernel(relax_dev P)
         P.plane[P.zcur + i] = P.plane[15 - P.zcur + i];
 }
 
-// p.second->orientation.normalize() for every node of _nodes_to_optimize (relax_problem.cpp:1410-1413)
-__global__ void normalize_kernel(relax_dev P, const uint8_t *cam_optimize)
-{
-    const uint32_t c = blockIdx.x * blockDim.x + threadIdx.x;
-    if (c >= P.n_cams || !cam_optimize[c])
-        return;
-    double *q = P.cam_q + (size_t)c * 4;
-    const double n = sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
-    for (int k = 0; k < 4; k++)
-        q[k] = q[k] / n;
-}
-
 } // namespace
 
 // ---------------------------------------------------------------------------------------------------
@@ -590,10 +536,8 @@ struct ochip_relax_problem
     uint32_t n_cams = 0;
     std::vector<uint32_t> cam_pair_count;
     // sharded evaluation (ochip_relax_set_shard): this rank evaluates pairs [pair_lo, pair_hi)
-    uint32_t shard_rank = 0, shard_world = 1, shard_chunk = 0, pair_hi = 0;
-    ochip_relax_exchange_fn exchange = nullptr;
-    void *exchange_user = nullptr;
-    int32_t *fail_ranks = nullptr;
+    uint32_t pair_hi = 0;
+    lm_shard shard;
     double *eval_scratch = nullptr; // ochip_relax_evaluate: scale, -delta and the candidate's scalars (grown, never per call)
     size_t eval_scratch_cap = 0;
 };
@@ -1001,13 +945,13 @@ int ochip_relax_problem_create(ochip_ctx *ctx, const ochip_relax_desc *d, ochip_
     chk(p->mem.upload(&D.cam_pair_idx, cpi.data(), cpi.size(), WAIT));
     chk(p->mem.alloc<double>(&D.pair_acc, (size_t)n_pairs * ACC));
     chk(p->mem.alloc<double>(&D.pair_cost, n_pairs));
-    chk(p->mem.alloc<int32_t>(&p->fail_ranks, 1));
-    if (rc == OCHIP_OK && hipMemsetAsync(p->fail_ranks, 0, 4, ctx->stream) != hipSuccess) // (evaluations expect it clear and leave it clear)
+    chk(p->mem.alloc<int32_t>(&p->shard.fail_ranks, 1));
+    if (rc == OCHIP_OK && hipMemsetAsync(p->shard.fail_ranks, 0, 4, ctx->stream) != hipSuccess) // (evaluations expect it clear and leave it clear)
         rc = ochip_fail(ctx, OCHIP_EHIP, "hipMemsetAsync failed in relax problem");
-    D.fail = p->fail_ranks;
+    D.fail = p->shard.fail_ranks;
     D.pair_lo = 0;
     p->pair_hi = n_pairs;
-    p->shard_chunk = n_pairs;
+    p->shard.chunk = n_pairs;
     chk(p->mem.upload(&p->cam_has_prior, p->cam_has_prior_host.data(), p->cam_has_prior_host.size(), WAIT));
     chk(p->mem.upload(&p->cam_optimize_dev, p->cam_optimize.data(), p->cam_optimize.size(), WAIT));
     if (rc == OCHIP_OK)
@@ -1059,20 +1003,20 @@ int ochip_relax_set_shard(ochip_relax_problem *p, uint32_t rank, uint32_t world,
     // record arrays padded to world equal slices so that the exchange is a plain in-place all-gather
     chk(p->mem.alloc<double>(&D.pair_acc, (size_t)world * chunk * ACC));
     chk(p->mem.alloc<double>(&D.pair_cost, (size_t)world * chunk));
-    chk(p->mem.alloc<int32_t>(&p->fail_ranks, world));
+    chk(p->mem.alloc<int32_t>(&p->shard.fail_ranks, world));
     if (rc != OCHIP_OK)
         return rc;
     OCHIP_HIP(ctx, hipMemset(D.pair_acc, 0, (size_t)world * chunk * ACC * 8));
     OCHIP_HIP(ctx, hipMemset(D.pair_cost, 0, (size_t)world * chunk * 8));
-    OCHIP_HIP(ctx, hipMemset(p->fail_ranks, 0, (size_t)world * 4));
+    OCHIP_HIP(ctx, hipMemset(p->shard.fail_ranks, 0, (size_t)world * 4));
     D.pair_lo = std::min(rank * chunk, n_pairs);
     p->pair_hi = std::min((rank + 1) * chunk, n_pairs);
-    D.fail = p->fail_ranks + rank;
-    p->shard_rank = rank;
-    p->shard_world = world;
-    p->shard_chunk = chunk;
-    p->exchange = fn;
-    p->exchange_user = user;
+    D.fail = p->shard.fail_ranks + rank;
+    p->shard.rank = rank;
+    p->shard.world = world;
+    p->shard.chunk = chunk;
+    p->shard.exchange = fn;
+    p->shard.exchange_user = user;
     return OCHIP_OK;
 }
 
@@ -1158,20 +1102,11 @@ struct plane_model final : lm_model
         }
         ochip_prof_end(ctx, OCHIP_K_RELAX_EVAL, e0, e1);
         (with_jac ? ctx->relax_blocks_jac : ctx->relax_blocks_cost) += D.n_blocks ? (uint64_t)D.n_blocks * my_pairs / std::max(D.n_pairs, 1u) : 0;
-        if (p->exchange)
-        {
-            // the ranks' pair records (and failure flags) are all-gathered in place; from here on every rank holds
-            // the same arrays and runs the same deterministic assembly.  A failed exchange is a hard error: the ranks
-            // would otherwise leave the solve on different schedules and the next collective would hang.
-            // (the native transport enqueues its all-gathers on this stream: stream order is all it needs; a callback
-            // transport reads the arrays from outside the stream and gets them complete)
-            if (p->exchange != ochip_rccl_relax_exchange)
-                OCHIP_HIP(ctx, ochip_stream_wait(ctx, st));
-            const int xrc = p->exchange(p->exchange_user, D.pair_acc, with_jac ? (uint64_t)p->shard_chunk * ACC * 8 : 0,
-                                        D.pair_cost, (uint64_t)p->shard_chunk * 8, p->fail_ranks, 4);
-            if (xrc != 0)
-                return ochip_fail(ctx, OCHIP_EHIP, "relax exchange callback failed (%d)", xrc);
-        }
+        // the ranks' pair records (and failure flags), all-gathered in place
+        const int xrc = lm_exchange_records(ctx, p->shard, D.pair_acc, with_jac ? (uint64_t)p->shard.chunk * ACC * 8 : 0, D.pair_cost,
+                                            (uint64_t)p->shard.chunk * 8);
+        if (xrc)
+            return xrc;
         if (with_jac)
         {
             // the entries of A that the scatter and the reduction write are the same from one evaluation to the next (fixed
@@ -1194,41 +1129,19 @@ struct plane_model final : lm_model
         const bool mailed = mails_results();
         lm_mail mail{};
         if (mailed)
-            mail = lm_mail{p->sys.box, p->sys.scal, p->sys.fail_chol, p->fail_ranks, (int)p->shard_world, 1, nullptr};
+            mail = lm_mail{p->sys.box, p->sys.scal, p->sys.fail_chol, p->shard.fail_ranks, (int)p->shard.world, 1, nullptr};
         // (with the Jacobian: the scatter of the pair records into A and g rides in the same launch)
         const uint32_t cam_blocks = with_jac ? (D.n_cams + 3) / 4 : 0, pair_blocks = with_jac ? (D.n_pairs + 255) / 256 : 0;
         hipLaunchKernelGGL(relax_reduce_plane_kernel, dim3(REDUCE_GROUPS + cam_blocks + pair_blocks), dim3(256), 0, st, D, Am, gv, n,
                            p->cam_has_prior, p->sys.scal, with_jac ? 1 : 0, which, p->reduce_partials, p->reduce_arrived, mail, diag_scale,
                            second_set ? p->sys.diagonal2 : p->sys.diagonal, cam_blocks, cam_blocks + pair_blocks);
         OCHIP_HIP(ctx, hipGetLastError());
-        // (read-backs into the system's page-locked block: a copy to pageable memory would make the host wait for it)
-        std::vector<int32_t> hfails_pageable;
-        double *const h0 = p->sys.box + lm_system::BOX_COST;
-        int32_t *hfails = reinterpret_cast<int32_t *>(p->sys.box + lm_system::BOX_FAILS);
-        if (p->shard_world > 2 * (lm_system::BOX_VECTORS - lm_system::BOX_FAILS))
-        {
-            hfails_pageable.assign(p->shard_world, 0);
-            hfails = hfails_pageable.data();
-        }
-        if (!mailed)
-        {
-            OCHIP_HIP(ctx, hipMemcpyAsync(h0, p->sys.scal, 8, hipMemcpyDeviceToHost, st));
-            OCHIP_HIP(ctx, hipMemcpyAsync(hfails, p->fail_ranks, (size_t)p->shard_world * 4, hipMemcpyDeviceToHost, st));
-            OCHIP_HIP(ctx, hipMemsetAsync(D.fail, 0, 4, st)); // this rank's flag, clear for the next evaluation
-        }
-        if (before_wait)
-            before_wait();
-        OCHIP_HIP(ctx, ochip_stream_wait(ctx, st));
-        *cost = *h0;
-        int hfail = 0;
-        for (int r = 0; r < (int)p->shard_world; r++)
-            hfail |= hfails[r];
-        *fail_mask = hfail;
-        return OCHIP_OK;
+        // (not mailed: this rank's flag is cleared behind the copies, for the next evaluation)
+        return lm_finish_evaluation(p->sys, p->shard, mailed, D.fail, before_wait, cost, fail_mask);
     }
     bool mails_results() override
     {
-        return p->shard_world <= (uint32_t)(2 * (lm_system::BOX_VECTORS - lm_system::BOX_FAILS)) && p->sys.box != nullptr;
+        return p->shard.flags_fit_box() && p->sys.box != nullptr;
     }
     void launch_candidate(const double *y, const double *scale, double alpha, double *scal) override
     {
@@ -1240,9 +1153,7 @@ struct plane_model final : lm_model
     }
     void launch_normalize() override
     {
-        if (p->dev.n_cams)
-            hipLaunchKernelGGL(normalize_kernel, dim3((p->dev.n_cams + 255) / 256), dim3(256), 0, p->ctx->stream, p->dev,
-                               p->cam_optimize_dev);
+        lm_launch_normalize(p->ctx, p->dev.cam_q, p->dev.n_cams, p->cam_optimize_dev);
     }
     int x_norm(double *out) override
     {

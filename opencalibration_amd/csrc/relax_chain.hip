@@ -23,6 +23,7 @@
 // continues from the last finished camera with the host loop (csrc/host/relax.cpp).
 #include "ctx.hpp"
 #include "dual.hpp"
+#include "relax_lm_rules.hpp"
 #include "undistort.hpp"
 
 #include <algorithm>
@@ -79,12 +80,13 @@ struct chain_ctl
     int n, n_active, nz, nbc, nbr, n_claims;
     int n_blocks, n_prior, n_live;
     int lm_first;
-    int iter, invalid, iterations, successful, unsuccessful;
+    int iter, iterations, successful, unsuccessful;
     int eval_state, eval_set, eval_cams;
     int fail_bits, chol_fail;
     int steps_done, solves, iterations_total, last_iterations, last_blocks, last_termination;
     int syncs;
-    double radius, decrease, x_cost, x_norm, gmax, mcc, step_norm2, cand_norm2;
+    lm_trust trust; // the solve under way
+    double x_cost, x_norm, gmax, mcc, step_norm2, cand_norm2;
     double initial_cost, last_initial_cost, last_final_cost;
     double plane_xy[6];
     double z[2][3];
@@ -1037,30 +1039,14 @@ struct epi
     __device__ double reduce_sum(double v)
     {
         __syncthreads();
-        sh[t] = v;
-        __syncthreads();
-        for (int s = TG / 2; s > 0; s >>= 1)
-        {
-            if (t < s)
-                sh[t] += sh[t + s];
-            __syncthreads();
-        }
-        const double r = sh[0];
+        const double r = lm_block_sum<TG>(v, sh);
         __syncthreads();
         return r;
     }
     __device__ double reduce_max(double v)
     {
         __syncthreads();
-        sh[t] = v;
-        __syncthreads();
-        for (int s = TG / 2; s > 0; s >>= 1)
-        {
-            if (t < s)
-                sh[t] = fmax(sh[t], sh[t + s]);
-            __syncthreads();
-        }
-        const double r = sh[0];
+        const double r = lm_block_max<TG>(v, sh);
         __syncthreads();
         return r;
     }
@@ -1323,9 +1309,7 @@ struct epi
         {
             C.lm_first = 1;
             C.iter = 0;
-            C.invalid = 0;
-            C.radius = 1.0; // initial_trust_region_radius, relax_problem.cpp:36
-            C.decrease = 2.0;
+            C.trust.start(lm_reference_options().initial_trust_region_radius);
             C.eval_state = C.cur;
             C.eval_set = C.cur;
             C.eval_cams = which;
@@ -1343,12 +1327,7 @@ struct epi
         double *Q = D.q[C.cur];
         for (uint32_t c = t; c < D.n_cams; c += TG)
             if (optimised(c))
-            {
-                double *q = Q + 4 * (size_t)c;
-                const double nrm = sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
-                for (int k = 0; k < 4; k++)
-                    q[k] = q[k] / nrm;
-            }
+                lm_quat_normalize(Q + 4 * (size_t)c);
         if (t == 0)
         {
             C.last_termination = arg_termination;
@@ -1469,6 +1448,7 @@ struct epi
                 g[zt + i] = sh[6 + i];
         }
         const int fail_bits = C.fail_bits, n = C.n, first = C.lm_first;
+        const ochip_relax_options opt = lm_reference_options();
         __syncthreads();
         if (t == 0)
             C.fail_bits = 0;
@@ -1481,11 +1461,9 @@ struct epi
             for (int i = t; i < n; i += TG)
             {
                 const double d = A[at(i, i)];
-                const double s = 1.0 / (1.0 + sqrt(d));
+                const double s = lm_jacobi_scale(d);
                 D.scale[i] = s;
-                const double v = d * s * s;
-                const double lo = v < 1e-6 ? 1e-6 : v;
-                D.diagonal[set][i] = 1e32 < lo ? 1e32 : lo;
+                D.diagonal[set][i] = lm_clamp_diagonal(d * s * s);
                 m = fmax(m, fabs(g[i]));
             }
             const double gmax = reduce_max(m);
@@ -1510,7 +1488,7 @@ struct epi
                 C.lm_first = 0;
             }
             __syncthreads();
-            if (gmax <= 1e-10)
+            if (gmax <= opt.gradient_tolerance)
                 return finish_with(OCHIP_RELAX_CONVERGENCE_GRADIENT, true);
             return ACT_START_ITERATION;
         }
@@ -1519,40 +1497,37 @@ struct epi
         for (int i = t; i < n; i += TG)
         {
             const double d = A[at(i, i)];
-            const double v = d * D.scale[i] * D.scale[i];
-            const double lo = v < 1e-6 ? 1e-6 : v;
-            D.diagonal[set][i] = 1e32 < lo ? 1e32 : lo;
+            D.diagonal[set][i] = lm_clamp_diagonal(d * D.scale[i] * D.scale[i]);
             m = fmax(m, fabs(g[i]));
         }
         const double gmax2 = reduce_max(m);
-        const double mcc = C.mcc, x_cost = C.x_cost, x_norm = C.x_norm, radius = C.radius, decrease = C.decrease;
+        // the trust-region logic of lm_solve (relax_lm.hip): every thread takes the same decisions, thread 0 keeps the state
+        const double mcc = C.mcc, x_cost = C.x_cost, x_norm = C.x_norm;
         const double step_norm = sqrt(C.step_norm2), cand_norm = sqrt(C.cand_norm2);
-        const int chol_fail = C.chol_fail, invalid = C.invalid;
+        const int chol_fail = C.chol_fail;
+        lm_trust trust = C.trust;
         __syncthreads();
-        const bool valid = !chol_fail && isfinite(mcc) && mcc > 0.0;
-        if (!valid)
+        // (the factorisation's flag is tested on its own, ahead of the rule that tests it again: folded into one condition
+        // with the rule's other two tests, this kernel's register allocation costs 16 more bytes of scratch per lane)
+        if (chol_fail || !lm_trust::step_is_valid(chol_fail, mcc))
         {
+            const bool failed = trust.on_invalid();
             if (t == 0)
-            {
-                C.invalid = invalid + 1;
-                C.radius = radius * 0.5;
-            }
+                C.trust = trust;
             __syncthreads();
-            if (invalid + 1 >= 5)
-                return finish_with(OCHIP_RELAX_FAILURE, true);
-            return ACT_START_ITERATION;
+            return failed ? finish_with(OCHIP_RELAX_FAILURE, true) : ACT_START_ITERATION;
         }
         const double cand_cost = (fail_bits & 1) ? 1.7976931348623157e308 : cost;
         if (t == 0)
-            C.invalid = 0;
+            C.trust.on_valid();
         __syncthreads();
-        if (step_norm <= 1e-8 * (x_norm + 1e-8))
+        if (lm_trust::parameter_converged(step_norm, x_norm, opt.parameter_tolerance))
             return finish_with(OCHIP_RELAX_CONVERGENCE_PARAMETER, true);
         const double cost_change = x_cost - cand_cost;
-        if (fabs(cost_change) <= 1e-6 * x_cost)
+        if (lm_trust::function_converged(cost_change, x_cost, opt.function_tolerance))
             return finish_with(OCHIP_RELAX_CONVERGENCE_FUNCTION, true);
         const double rho = cost_change / mcc;
-        if (rho > 1e-3)
+        if (lm_trust::accepts(rho))
         {
             if (t == 0)
             {
@@ -1560,22 +1535,19 @@ struct epi
                 C.x_norm = cand_norm;
                 C.x_cost = cost;
                 C.gmax = gmax2;
-                const double tt = 2.0 * rho - 1.0;
-                C.radius = fmin(1e16, radius / fmax(1.0 / 3.0, 1.0 - tt * tt * tt));
-                C.decrease = 2.0;
+                C.trust.on_accept(rho);
                 C.successful++;
             }
             __syncthreads();
             if (fail_bits & 2)
                 return finish_with(OCHIP_RELAX_FAILURE, true);
-            if (gmax2 <= 1e-10)
+            if (gmax2 <= opt.gradient_tolerance)
                 return finish_with(OCHIP_RELAX_CONVERGENCE_GRADIENT, true);
             return ACT_START_ITERATION;
         }
         if (t == 0)
         {
-            C.radius = radius / decrease;
-            C.decrease = decrease * 2.0;
+            C.trust.on_reject();
             C.unsuccessful++;
         }
         __syncthreads();
@@ -1586,11 +1558,12 @@ struct epi
     {
         __syncthreads();
         const int iter = C.iter, n = C.n, cur = C.cur;
-        const double radius = C.radius;
+        const lm_trust trust = C.trust;
+        const double radius = trust.radius;
         __syncthreads();
-        if (iter >= 100) // max_num_iterations, relax_problem.cpp:32
+        if (iter >= lm_reference_options().max_num_iterations)
             return finish_with(OCHIP_RELAX_NO_CONVERGENCE, true);
-        if (radius <= 1e-32)
+        if (trust.radius_exhausted())
             return finish_with(OCHIP_RELAX_CONVERGENCE_RADIUS, true);
         if (t == 0)
         {
@@ -1610,8 +1583,7 @@ struct epi
             const double *g = D.g[cur], *diagonal = D.diagonal[cur];
             for (int i = t; i < n; i += TG)
             {
-                const double dd = sqrt(diagonal[i] / radius);
-                D.lm_diag[i] = dd * dd;
+                D.lm_diag[i] = lm_damping(diagonal[i], radius);
                 D.gs[i] = g[i] * D.scale[i];
             }
             const int tiles = tile_of(C.nbr, 0) + 4;
@@ -1644,8 +1616,7 @@ struct epi
             {
                 for (int j = 0; j <= i; j++)
                     Wm[i][j] = sm[i * n + j] * scale[i] * scale[j];
-                const double dd = sqrt(diagonal[i] / radius);
-                lm[i] = dd * dd;
+                lm[i] = lm_damping(diagonal[i], radius);
                 Wm[i][i] += lm[i];
                 gs[i] = g[i] * scale[i];
             }
@@ -1762,7 +1733,8 @@ struct epi
         return ACT_CANDIDATE;
     }
 
-    // candidate = x (+) (-y scale): relax.hip's plane_candidate_body; then its evaluation, with the Jacobian, into the other set
+    // candidate = x (+) (-y scale), the cameras by lm_candidate_cams like relax.hip's plane_candidate_body; then its evaluation,
+    // with the Jacobian, into the other set
     __device__ int candidate()
     {
         __syncthreads();
@@ -1770,42 +1742,7 @@ struct epi
         const double *Q = D.q[cur];
         double *O = D.q[cur ^ 1];
         double sn = 0, xn = 0;
-        for (uint32_t c = t; c < D.n_cams; c += TG)
-        {
-            const int tc = D.cam_t[c];
-            const double *q = Q + (size_t)c * 4;
-            double *o = O + (size_t)c * 4;
-            if (tc < 0)
-            {
-                for (int k = 0; k < 4; k++)
-                    o[k] = q[k];
-                continue;
-            }
-            double d[3];
-            for (int k = 0; k < 3; k++)
-                d[k] = 1.0 * (-xs[tc + k] * D.scale[tc + k]);
-            const double nrm = sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
-            if (nrm == 0.0)
-            {
-                for (int k = 0; k < 4; k++)
-                    o[k] = q[k];
-            }
-            else
-            {
-                const double s = sin(nrm) / nrm;
-                const double dx = s * d[0], dy = s * d[1], dz = s * d[2], dw = cos(nrm);
-                const double qx = q[0], qy = q[1], qz = q[2], qw = q[3];
-                o[3] = dw * qw - dx * qx - dy * qy - dz * qz;
-                o[0] = dw * qx + dx * qw + dy * qz - dz * qy;
-                o[1] = dw * qy + dy * qw + dz * qx - dx * qz;
-                o[2] = dw * qz + dz * qw + dx * qy - dy * qx;
-            }
-            for (int k = 0; k < 4; k++)
-            {
-                sn += (q[k] - o[k]) * (q[k] - o[k]);
-                xn += o[k] * o[k];
-            }
-        }
+        lm_candidate_cams<TG>(D.n_cams, D.cam_t, Q, O, xs, D.scale, 1.0, &sn, &xn);
         double z1 = 0;
         if (t < 3)
         {

@@ -527,16 +527,9 @@ __global__ __launch_bounds__(LM_TG) void cost_slices_kernel(const double *rec_co
     double v = 0;
     for (uint32_t i = lo + t; i < hi; i += LM_TG)
         v += rec_cost[i];
-    sh[t] = v;
-    __syncthreads();
-    for (int s = LM_TG / 2; s > 0; s >>= 1)
-    {
-        if (t < s)
-            sh[t] += sh[t + s];
-        __syncthreads();
-    }
+    const double sum = lm_block_sum<LM_TG>(v, sh);
     if (t == 0)
-        slice_sum[blockIdx.x] = sh[0];
+        slice_sum[blockIdx.x] = sum;
 }
 __global__ __launch_bounds__(LM_TG) void cost_reduce_kernel(const double *rec_cost, const double *slice_sum, uint32_t n_slices,
                                                            uint32_t prior_base, uint32_t n_prior, double *scal)
@@ -548,16 +541,9 @@ __global__ __launch_bounds__(LM_TG) void cost_reduce_kernel(const double *rec_co
         v += slice_sum[i];
     for (uint32_t i = t; i < n_prior; i += LM_TG)
         v += rec_cost[prior_base + i];
-    sh[t] = v;
-    __syncthreads();
-    for (int s = LM_TG / 2; s > 0; s >>= 1)
-    {
-        if (t < s)
-            sh[t] += sh[t + s];
-        __syncthreads();
-    }
+    const double sum = lm_block_sum<LM_TG>(v, sh);
     if (t == 0)
-        scal[0] = sh[0];
+        scal[0] = sum;
 }
 
 // ---- assembly ------------------------------------------------------------------------------------------------------
@@ -797,42 +783,7 @@ __global__ __launch_bounds__(LM_TG) void general_candidate_kernel(g_dev P, const
     __shared__ double sh[LM_TG];
     const int t = threadIdx.x;
     double sn = 0, xn = 0;
-    for (uint32_t c = t; c < P.n_cams; c += LM_TG)
-    {
-        const int tc = P.var_t[c];
-        const double *q = P.cam_q + (size_t)c * 4;
-        double *o = P.cam_q2 + (size_t)c * 4;
-        if (tc < 0)
-        {
-            for (int k = 0; k < 4; k++)
-                o[k] = q[k];
-            continue;
-        }
-        double d[3];
-        for (int k = 0; k < 3; k++)
-            d[k] = alpha * (-y[tc + k] * scale[tc + k]);
-        const double nrm = sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
-        if (nrm == 0.0)
-        {
-            for (int k = 0; k < 4; k++)
-                o[k] = q[k];
-        }
-        else
-        {
-            const double s = sin(nrm) / nrm;
-            const double dx = s * d[0], dy = s * d[1], dz = s * d[2], dw = cos(nrm);
-            const double qx = q[0], qy = q[1], qz = q[2], qw = q[3];
-            o[3] = dw * qw - dx * qx - dy * qy - dz * qz;
-            o[0] = dw * qx + dx * qw + dy * qz - dz * qy;
-            o[1] = dw * qy + dy * qw + dz * qx - dx * qz;
-            o[2] = dw * qz + dz * qw + dx * qy - dy * qx;
-        }
-        for (int k = 0; k < 4; k++)
-        {
-            sn += (q[k] - o[k]) * (q[k] - o[k]);
-            xn += o[k] * o[k];
-        }
-    }
+    lm_candidate_cams<LM_TG>(P.n_cams, P.var_t, P.cam_q, P.cam_q2, y, scale, alpha, &sn, &xn);
     for (uint32_t v = t; v < P.n_verts; v += LM_TG)
     {
         const int tz = P.var_t[P.n_cams + v];
@@ -879,16 +830,9 @@ __global__ __launch_bounds__(LM_TG) void general_candidate_kernel(g_dev P, const
     }
     for (int q = 0; q < 2; q++)
     {
-        sh[t] = q == 0 ? sn : xn;
-        __syncthreads();
-        for (int s = LM_TG / 2; s > 0; s >>= 1)
-        {
-            if (t < s)
-                sh[t] += sh[t + s];
-            __syncthreads();
-        }
+        const double sum = lm_block_sum<LM_TG>(q == 0 ? sn : xn, sh);
         if (t == 0)
-            scal[2 + q] = sh[0];
+            scal[2 + q] = sum;
         __syncthreads();
     }
 }
@@ -902,18 +846,6 @@ __global__ void general_accept_kernel(g_dev P)
         P.vert_z[i] = P.vert_z2[i];
     if (i < 8)
         P.model[i] = P.model2[i];
-}
-
-// p.second->orientation.normalize() for every node of _nodes_to_optimize (relax_problem.cpp:1410-1413)
-__global__ void general_normalize_kernel(g_dev P, const uint8_t *cam_optimize)
-{
-    const uint32_t c = blockIdx.x * blockDim.x + threadIdx.x;
-    if (c >= P.n_cams || !cam_optimize[c])
-        return;
-    double *q = P.cam_q + (size_t)c * 4;
-    const double n = sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
-    for (int k = 0; k < 4; k++)
-        q[k] = q[k] / n;
 }
 
 } // namespace
@@ -956,11 +888,9 @@ struct ochip_relaxg_problem
     uint8_t *cam_optimize_dev = nullptr;
     // sharded evaluation (ochip_relaxg_desc.shard_world > 1): this rank evaluates the ray blocks [shard_lo, shard_hi); the
     // record data of rank r lies at r * shard_stride doubles, its costs at r * shard_chunk
-    uint32_t shard_rank = 0, shard_world = 1, shard_chunk = 0, shard_lo = 0, shard_hi = 0;
+    uint32_t shard_lo = 0, shard_hi = 0;
+    lm_shard shard;
     uint64_t shard_stride = 0;
-    int32_t *fail_ranks = nullptr;
-    ochip_relax_exchange_fn exchange = nullptr;
-    void *exchange_user = nullptr;
 };
 
 namespace
@@ -1346,7 +1276,7 @@ struct general_model final : lm_model
         // any other evaluation leaves it to this memset)
         if (!fail_is_clear)
             OCHIP_HIP(ctx, hipMemsetAsync(D.fail, 0, 4, st));
-        const bool mailed = mail_by_diag && p->shard_world <= (uint32_t)(2 * (lm_system::BOX_VECTORS - lm_system::BOX_FAILS));
+        const bool mailed = mail_by_diag && p->shard.flags_fit_box();
         fail_is_clear = mailed;
         hipEvent_t e0, e1;
         ochip_prof_begin(ctx, OCHIP_K_RELAX_EVAL, &e0, &e1);
@@ -1380,18 +1310,11 @@ struct general_model final : lm_model
         if (n_prior)
             hipLaunchKernelGGL(prior_kernel, dim3((n_prior + 255) / 256), dim3(256), 0, st, D, which, with_jac ? 1 : 0);
         ochip_prof_end(ctx, OCHIP_K_RELAX_EVAL, e0, e1);
-        if (p->exchange)
-        {
-            // the ranks' records (costs, failure flags) are all-gathered in place; from here on every rank holds the same
-            // arrays and runs the same deterministic assembly.  A failed exchange is a hard error: the ranks would
-            // otherwise leave the solve on different schedules and the next collective would hang.
-            if (p->exchange != ochip_rccl_relax_exchange) // (the native transport is stream-ordered)
-                OCHIP_HIP(ctx, ochip_stream_wait(ctx, st));
-            const int xrc = p->exchange(p->exchange_user, D.rec_data, with_jac ? p->shard_stride * 8 : 0, D.rec_cost,
-                                        (uint64_t)p->shard_chunk * 8, p->fail_ranks, 4);
-            if (xrc != 0)
-                return ochip_fail(ctx, OCHIP_EHIP, "relax exchange callback failed (%d)", xrc);
-        }
+        // the ranks' records (costs, failure flags), all-gathered in place
+        const int xrc = lm_exchange_records(ctx, p->shard, D.rec_data, with_jac ? p->shard_stride * 8 : 0, D.rec_cost,
+                                            (uint64_t)p->shard.chunk * 8);
+        if (xrc)
+            return xrc;
         if (with_jac)
         {
             // the assembly ASSIGNS the same entries of A and g at every evaluation (fixed by the layout) and nothing else
@@ -1420,28 +1343,10 @@ struct general_model final : lm_model
         hipLaunchKernelGGL(cost_reduce_kernel, dim3(1), dim3(LM_TG), 0, st, (const double *)D.rec_cost, (const double *)p->cost_slices_dev,
                            n_slices, D.prior_base, n_prior, p->sys.scal);
         OCHIP_HIP(ctx, hipGetLastError());
-        // (read-backs into the system's page-locked block: a copy to pageable memory would make the host wait for it)
-        std::vector<int32_t> hfails_pageable;
-        double *const h0 = p->sys.box + lm_system::BOX_COST;
-        int32_t *hfails = reinterpret_cast<int32_t *>(p->sys.box + lm_system::BOX_FAILS);
-        if (p->shard_world > 2 * (lm_system::BOX_VECTORS - lm_system::BOX_FAILS))
-        {
-            hfails_pageable.assign(p->shard_world, 0);
-            hfails = hfails_pageable.data();
-        }
-        if (!mailed) // (mailed: the solver's diagonal kernel, enqueued by before_wait, posts the cost and the flags too)
-        {
-            OCHIP_HIP(ctx, hipMemcpyAsync(h0, p->sys.scal, 8, hipMemcpyDeviceToHost, st));
-            OCHIP_HIP(ctx, hipMemcpyAsync(hfails, p->fail_ranks, (size_t)p->shard_world * 4, hipMemcpyDeviceToHost, st));
-        }
-        if (before_wait)
-            before_wait();
-        OCHIP_HIP(ctx, ochip_stream_wait(ctx, st));
-        *cost = *h0;
+        // (mailed: the solver's diagonal kernel, enqueued by before_wait, posts the cost and the flags too)
         int hfail = 0;
-        for (int r = 0; r < (int)p->shard_world; r++)
-            hfail |= hfails[r];
-        return hfail ? 1 : 0;
+        const int frc = lm_finish_evaluation(p->sys, p->shard, mailed, nullptr, before_wait, cost, &hfail);
+        return frc ? frc : (hfail ? 1 : 0);
     }
     void launch_candidate(const double *y, const double *scale, double alpha, double *scal) override
     {
@@ -1461,7 +1366,7 @@ struct general_model final : lm_model
         lm_system &S = p->sys;
         S.swap_sets();
         ochip_relaxg_problem *const prob = p;
-        before_wait = [&S, scale, prob]() { lm_launch_diag(S, scale, prob->fail_ranks, (int)prob->shard_world, 1, prob->dev.fail); };
+        before_wait = [&S, scale, prob]() { lm_launch_diag(S, scale, prob->shard.fail_ranks, (int)prob->shard.world, 1, prob->dev.fail); };
         mail_by_diag = true;
         const int rc = evaluate(true, 1, cost);
         mail_by_diag = false;
@@ -1481,9 +1386,7 @@ struct general_model final : lm_model
     }
     void launch_normalize() override
     {
-        if (p->n_cams)
-            hipLaunchKernelGGL(general_normalize_kernel, dim3((p->n_cams + 255) / 256), dim3(256), 0, p->ctx->stream, p->dev,
-                               p->cam_optimize_dev);
+        lm_launch_normalize(p->ctx, p->dev.cam_q, p->n_cams, p->cam_optimize_dev);
     }
     int x_norm(double *out) override
     {
@@ -1599,9 +1502,9 @@ int ochip_relaxg_problem_create(ochip_ctx *ctx, const ochip_relaxg_desc *d, ochi
     }
     const uint32_t chunk = std::max<uint32_t>(1, (d->n_blocks + world - 1) / world);
     const uint32_t n_ray_pad = world > 1 ? world * chunk : d->n_blocks;
-    p->shard_rank = d->shard_rank;
-    p->shard_world = world;
-    p->shard_chunk = chunk;
+    p->shard.rank = d->shard_rank;
+    p->shard.world = world;
+    p->shard.chunk = chunk;
     p->shard_lo = world > 1 ? std::min(d->shard_rank * chunk, d->n_blocks) : 0;
     p->shard_hi = world > 1 ? std::min((d->shard_rank + 1) * chunk, d->n_blocks) : d->n_blocks;
     p->n_rec = n_ray_pad + d->n_down + d->n_diff + n_anchor + d->n_smooth + n_mono + d->n_rel;
@@ -1803,7 +1706,7 @@ int ochip_relaxg_problem_create(ochip_ctx *ctx, const ochip_relaxg_desc *d, ochi
     chk(p->mem.upload(&D.rec_var, p->rec_var, BLOCKING));
     chk(p->mem.alloc<double>(&D.rec_data, (size_t)rec_off[p->n_rec]));
     chk(p->mem.alloc<double>(&D.rec_cost, p->n_rec));
-    chk(p->mem.alloc<int32_t>(&p->fail_ranks, world));
+    chk(p->mem.alloc<int32_t>(&p->shard.fail_ranks, world));
     chk(p->mem.upload(&D.down_cam, d->down_cam, d->n_down, BLOCKING));
     chk(p->mem.upload(&D.diff_v, d->diff_v, (size_t)d->n_diff * 2, BLOCKING));
     chk(p->mem.upload(&D.smooth_v, d->smooth_v, (size_t)d->n_smooth * 4, BLOCKING));
@@ -1813,8 +1716,8 @@ int ochip_relaxg_problem_create(ochip_ctx *ctx, const ochip_relaxg_desc *d, ochi
     chk(p->mem.upload(&p->cam_optimize_dev, p->cam_optimize, BLOCKING));
     if (rc == OCHIP_OK)
     {
-        D.fail = p->fail_ranks + p->shard_rank;
-        if (hipMemset(p->fail_ranks, 0, (size_t)world * 4) != hipSuccess || hipMemset(D.rec_cost, 0, (size_t)p->n_rec * 8) != hipSuccess)
+        D.fail = p->shard.fail_ranks + p->shard.rank;
+        if (hipMemset(p->shard.fail_ranks, 0, (size_t)world * 4) != hipSuccess || hipMemset(D.rec_cost, 0, (size_t)p->n_rec * 8) != hipSuccess)
             rc = ochip_fail(ctx, OCHIP_EHIP, "hipMemset failed (relax records)");
     }
     if (rc == OCHIP_OK)
@@ -1832,10 +1735,10 @@ int ochip_relaxg_set_exchange(ochip_relaxg_problem *p, ochip_relax_exchange_fn f
 {
     if (!p)
         return OCHIP_EINVAL;
-    if (p->shard_world > 1 && !fn)
-        return ochip_fail(p->ctx, OCHIP_EINVAL, "a problem sharded over %u ranks needs an exchange function", p->shard_world);
-    p->exchange = fn;
-    p->exchange_user = user;
+    if (p->shard.world > 1 && !fn)
+        return ochip_fail(p->ctx, OCHIP_EINVAL, "a problem sharded over %u ranks needs an exchange function", p->shard.world);
+    p->shard.exchange = fn;
+    p->shard.exchange_user = user;
     return OCHIP_OK;
 }
 

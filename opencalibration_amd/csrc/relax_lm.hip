@@ -60,7 +60,7 @@ __global__ __launch_bounds__(256) void lm_build_kernel(lm_matrix A, const unsign
                     v = a[e] * scale[i] * scale[j];
                     if (i == j)
                     {
-                        const double dd = sqrt(diagonal[i] / radius), lm = dd * dd;
+                        const double lm = lm_damping(diagonal[i], radius);
                         lm_diag[i] = lm;
                         v += lm;
                         gs[i] = g[i] * scale[i];
@@ -657,16 +657,9 @@ __global__ __launch_bounds__(LM_TG) void back_solve_kernel(lm_matrix Lm, int n, 
     double part = 0;
     for (int i = t; i < n; i += LM_TG)
         part += x[i] * gs[i] + lm_diag[i] * x[i] * x[i];
-    sh[t] = part;
-    __syncthreads();
-    for (int s = LM_TG / 2; s > 0; s >>= 1)
-    {
-        if (t < s)
-            sh[t] += sh[t + s];
-        __syncthreads();
-    }
+    const double sum = lm_block_sum<LM_TG>(part, sh);
     if (t == 0)
-        scal[1] = 0.5 * sh[0];
+        scal[1] = 0.5 * sum;
 }
 
 // The same substitution when the band falls into regions that are coupled through the tail only (lm_envelope::
@@ -693,16 +686,9 @@ __global__ __launch_bounds__(LM_TG) void lm_model_change_kernel(const double *lm
     double part = 0;
     for (int i = t; i < n; i += LM_TG)
         part += y[i] * gs[i] + lm_diag[i] * y[i] * y[i];
-    sh[t] = part;
-    __syncthreads();
-    for (int s = LM_TG / 2; s > 0; s >>= 1)
-    {
-        if (t < s)
-            sh[t] += sh[t + s];
-        __syncthreads();
-    }
+    const double sum = lm_block_sum<LM_TG>(part, sh);
     if (t == 0)
-        scal[1] = 0.5 * sh[0];
+        scal[1] = 0.5 * sum;
 }
 
 // diag(A) and max|g| -> scal[4] = max|g|; diag_out[i] = A_ii; scale != nullptr: diagonal[i] = clamp(A_ii scale_i^2, 1e-6, 1e32),
@@ -1167,6 +1153,65 @@ void lm_launch_diag(lm_system &S, const double *scale, const int32_t *fail_ranks
                        S.diagonal, mail);
 }
 
+namespace
+{
+__global__ void lm_normalize_kernel(double *cam_q, uint32_t n_cams, const uint8_t *cam_optimize)
+{
+    const uint32_t c = blockIdx.x * blockDim.x + threadIdx.x;
+    if (c < n_cams && cam_optimize[c])
+        lm_quat_normalize(cam_q + (size_t)c * 4);
+}
+} // namespace
+
+void lm_launch_normalize(ochip_ctx *ctx, double *cam_q, uint32_t n_cams, const uint8_t *cam_optimize)
+{
+    if (n_cams)
+        hipLaunchKernelGGL(lm_normalize_kernel, dim3((n_cams + 255) / 256), dim3(256), 0, ctx->stream, cam_q, n_cams, cam_optimize);
+}
+
+int lm_exchange_records(ochip_ctx *ctx, const lm_shard &shard, void *data, uint64_t data_bytes, void *cost, uint64_t cost_bytes)
+{
+    if (!shard.exchange)
+        return OCHIP_OK;
+    if (shard.exchange != ochip_rccl_relax_exchange)
+        OCHIP_HIP(ctx, ochip_stream_wait(ctx, ctx->stream));
+    const int xrc = shard.exchange(shard.exchange_user, data, data_bytes, cost, cost_bytes, shard.fail_ranks, 4);
+    if (xrc != 0)
+        return ochip_fail(ctx, OCHIP_EHIP, "relax exchange callback failed (%d)", xrc);
+    return OCHIP_OK;
+}
+
+int lm_finish_evaluation(lm_system &S, const lm_shard &shard, bool mailed, int32_t *clear_flag, const std::function<void()> &before_wait,
+                         double *cost, int *fail_or)
+{
+    ochip_ctx *ctx = S.ctx;
+    hipStream_t st = ctx->stream;
+    // (read-backs into the system's page-locked block: a copy to pageable memory would make the host wait for it)
+    std::vector<int32_t> hfails_pageable;
+    double *const h0 = S.box + lm_system::BOX_COST;
+    int32_t *hfails = reinterpret_cast<int32_t *>(S.box + lm_system::BOX_FAILS);
+    if (!shard.flags_fit_box())
+    {
+        hfails_pageable.assign(shard.world, 0);
+        hfails = hfails_pageable.data();
+    }
+    if (!mailed)
+    {
+        OCHIP_HIP(ctx, hipMemcpyAsync(h0, S.scal, 8, hipMemcpyDeviceToHost, st));
+        OCHIP_HIP(ctx, hipMemcpyAsync(hfails, shard.fail_ranks, (size_t)shard.world * 4, hipMemcpyDeviceToHost, st));
+        if (clear_flag)
+            OCHIP_HIP(ctx, hipMemsetAsync(clear_flag, 0, 4, st));
+    }
+    if (before_wait)
+        before_wait();
+    OCHIP_HIP(ctx, ochip_stream_wait(ctx, st));
+    *cost = *h0;
+    *fail_or = 0;
+    for (uint32_t r = 0; r < shard.world; r++)
+        *fail_or |= hfails[r];
+    return OCHIP_OK;
+}
+
 int lm_back_default(const lm_system &S, bool x_global)
 {
     // (the per-region kernel also serves the single band, as one region: it is the faster walk - rows of a block split over
@@ -1362,7 +1407,7 @@ int lm_solve(lm_system &S, lm_model &M, const ochip_relax_options *opt, ochip_re
         return rc;
     OCHIP_HIP(ctx, hipMemcpy(diag, S.diag_tmp, (size_t)n * 8, hipMemcpyDeviceToHost));
     for (int i = 0; i < n; i++)
-        scale[i] = 1.0 / (1.0 + std::sqrt(diag[i])); // jacobi scaling, fixed from the first Jacobian
+        scale[i] = lm_jacobi_scale(diag[i]); // fixed from the first Jacobian
     OCHIP_HIP(ctx, hipMemcpy(S.scale, scale.data(), (size_t)n * 8, hipMemcpyHostToDevice));
     rc = grad_and_diag(&gmax, true); // (the damping diagonal of the first iterations, now that the scaling exists)
     if (rc)
@@ -1373,8 +1418,9 @@ int lm_solve(lm_system &S, lm_model &M, const ochip_relax_options *opt, ochip_re
         return rc;
     sum->initial_cost = x_cost;
     sum->iterations = 1; // iteration 0
-    double radius = opt->initial_trust_region_radius, decrease_factor = 2.0;
-    int invalid = 0, iter = 0;
+    lm_trust trust;
+    trust.start(opt->initial_trust_region_radius);
+    int iter = 0;
     auto finish = [&](int term) -> int {
         sum->termination = term;
         sum->final_cost = x_cost;
@@ -1388,7 +1434,7 @@ int lm_solve(lm_system &S, lm_model &M, const ochip_relax_options *opt, ochip_re
     {
         if (iter >= opt->max_num_iterations)
             return finish(OCHIP_RELAX_NO_CONVERGENCE);
-        if (radius <= 1e-32)
+        if (trust.radius_exhausted())
             return finish(OCHIP_RELAX_CONVERGENCE_RADIUS);
         iter++;
         sum->iterations++;
@@ -1398,15 +1444,13 @@ int lm_solve(lm_system &S, lm_model &M, const ochip_relax_options *opt, ochip_re
         ochip_prof_begin(ctx, OCHIP_K_RELAX_SOLVE, &e0, &e1);
         bool candidate_launched = false;
         {
-            constexpr bool chain = false; // (true: the launch chain per block column, the round-2 schedule; chol_verify runs it beside the tiles)
             static const bool verify = ochip_test_hook("chol_verify");              // factor twice, tiles and chain, and compare
             static const bool x_global = ochip_test_hook("back_solve_x_global");    // test knob: x in HBM even when it fits LDS
             lm_step_args sa;
-            sa.route = chain ? LM_ROUTE_CHAIN : LM_ROUTE_TILES;
             sa.back = lm_back_default(S, x_global);
             sa.verify = verify;
             sa.model = &M;
-            const int lrc = lm_linear_step(S, radius, sa, &candidate_launched);
+            const int lrc = lm_linear_step(S, trust.radius, sa, &candidate_launched);
             if (lrc)
                 return lrc;
         }
@@ -1417,7 +1461,6 @@ int lm_solve(lm_system &S, lm_model &M, const ochip_relax_options *opt, ochip_re
         // The candidate is evaluated right away (cost only): the step's own results - model cost change, step norms, the
         // factorisation's failure flag - come back with that evaluation's wait instead of a host round trip of their own.
         // An invalid step (rare) has then cost one evaluation whose result is ignored.
-        constexpr bool separate_waits = false; // (true: a wait per read-back, the round-2 schedule)
         volatile int &cfail = *reinterpret_cast<volatile int *>(S.box + lm_system::BOX_CFAIL);
         cfail = 0;
         double cand_eval = 0;
@@ -1430,15 +1473,7 @@ int lm_solve(lm_system &S, lm_model &M, const ochip_relax_options *opt, ochip_re
             (void)hipMemcpyAsync(h, S.scal, 64, hipMemcpyDeviceToHost, st);
             (void)hipMemcpyAsync(S.box + lm_system::BOX_CFAIL, S.fail_chol, 4, hipMemcpyDeviceToHost, st);
         };
-        if (separate_waits)
-        {
-            read_step();
-            OCHIP_HIP(ctx, ochip_stream_wait(ctx, st));
-            erc = 1;
-            if (!cfail && std::isfinite(h[1]) && h[1] > 0.0)
-                erc = M.evaluate(false, 1, &cand_eval);
-        }
-        else if (spec)
+        if (spec)
         {
             // the candidate with its Jacobian, into the second set: if the step is accepted (nearly always) everything the
             // next iteration needs is there already
@@ -1455,19 +1490,17 @@ int lm_solve(lm_system &S, lm_model &M, const ochip_relax_options *opt, ochip_re
         if (erc < 0)
             return erc;
         const double model_cost_change = h[1];
-        const bool valid = !cfail && std::isfinite(model_cost_change) && model_cost_change > 0.0;
         static const bool verbose = ochip_verbose("relax");
         if (verbose)
             fprintf(stderr, "[ochip relax] n=%d iter=%d cost=%.17g radius=%.6g model=%.17g step_norm=%.6g cfail=%d gmax=%.6g\n",
-                    n, iter, x_cost, radius, model_cost_change, std::sqrt(h[2]), cfail, gmax);
-        if (!valid)
+                    n, iter, x_cost, trust.radius, model_cost_change, std::sqrt(h[2]), cfail, gmax);
+        if (!lm_trust::step_is_valid(cfail, model_cost_change))
         {
-            if (++invalid >= 5)
+            if (trust.on_invalid())
                 return finish(OCHIP_RELAX_FAILURE);
-            radius *= 0.5;
             continue;
         }
-        invalid = 0;
+        trust.on_valid();
         double cand_cost = erc == 0 ? cand_eval : 1.7976931348623157e308;
         double step_norm = std::sqrt(h[2]), cand_norm = std::sqrt(h[3]);
         if (M.is_constrained())
@@ -1477,23 +1510,26 @@ int lm_solve(lm_system &S, lm_model &M, const ochip_relax_options *opt, ochip_re
             // contracted within [1e-3, 0.6] of the last trial, at most 20 trials, by the minimiser of the polynomial
             // through the trials' costs and directional derivatives (a Jacobian evaluation at every trial).
             std::vector<double> gh(n), yh(n);
-            OCHIP_HIP(ctx, hipMemcpy(gh.data(), S.g, (size_t)n * 8, hipMemcpyDeviceToHost));
             OCHIP_HIP(ctx, hipMemcpy(yh.data(), S.y, (size_t)n * 8, hipMemcpyDeviceToHost));
-            double gdd = 0, dmax = 0;
-            for (int i = 0; i < n; i++)
-            {
-                const double d = -yh[i] * scale[i];
-                gdd += gh[i] * d;
-                dmax = std::max(dmax, std::abs(d));
-            }
-            if (eliminated)
-            {
+            // the directional derivative along the full step d = -y scale of the gradient in sys.g (plus the eliminated
+            // columns' share)
+            auto slope_along_step = [&](bool from_candidate, double *slope) -> int {
+                OCHIP_HIP(ctx, hipMemcpy(gh.data(), S.g, (size_t)n * 8, hipMemcpyDeviceToHost));
+                *slope = 0;
+                for (int i = 0; i < n; i++)
+                    *slope += gh[i] * (-yh[i] * scale[i]);
                 double extra = 0;
-                const int src = M.slope_extra(true, &extra);
-                if (src)
-                    return src;
-                gdd += extra;
-            }
+                const int src = eliminated ? M.slope_extra(from_candidate, &extra) : OCHIP_OK;
+                if (eliminated)
+                    *slope += extra;
+                return src;
+            };
+            double gdd = 0, dmax = 0;
+            rc = slope_along_step(true, &gdd);
+            if (rc)
+                return rc;
+            for (int i = 0; i < n; i++)
+                dmax = std::max(dmax, std::abs(-yh[i] * scale[i]));
             ls_sample at0, previous, current;
             at0.x = 0, at0.value = x_cost, at0.slope = gdd, at0.valid = true;
             current.x = 1.0, current.value = cand_cost, current.valid = cand_cost < 1e308;
@@ -1512,19 +1548,9 @@ int lm_solve(lm_system &S, lm_model &M, const ochip_relax_options *opt, ochip_re
                     erc = M.evaluate(true, 1, &c2);
                     if (erc < 0)
                         return erc;
-                    std::vector<double> g1(n);
-                    OCHIP_HIP(ctx, hipMemcpy(g1.data(), S.g, (size_t)n * 8, hipMemcpyDeviceToHost));
-                    current.slope = 0;
-                    for (int i = 0; i < n; i++)
-                        current.slope += g1[i] * (-yh[i] * scale[i]);
-                    if (eliminated)
-                    {
-                        double extra = 0;
-                        const int src = M.slope_extra(false, &extra);
-                        if (src)
-                            return src;
-                        current.slope += extra;
-                    }
+                    rc = slope_along_step(false, &current.slope);
+                    if (rc)
+                        return rc;
                     current.valid = erc == 0 && std::isfinite(current.slope);
                 }
                 contracted = true;
@@ -1540,21 +1566,11 @@ int lm_solve(lm_system &S, lm_model &M, const ochip_relax_options *opt, ochip_re
                 erc = M.evaluate(true, 1, &c2);
                 if (erc < 0)
                     return erc;
-                std::vector<double> g1(n);
-                OCHIP_HIP(ctx, hipMemcpy(g1.data(), S.g, (size_t)n * 8, hipMemcpyDeviceToHost));
                 current.x = next;
                 current.value = c2;
-                current.slope = 0;
-                for (int i = 0; i < n; i++)
-                    current.slope += g1[i] * (-yh[i] * scale[i]);
-                if (eliminated)
-                {
-                    double extra = 0;
-                    const int src = M.slope_extra(false, &extra);
-                    if (src)
-                        return src;
-                    current.slope += extra;
-                }
+                rc = slope_along_step(false, &current.slope);
+                if (rc)
+                    return rc;
                 current.valid = erc == 0 && std::isfinite(c2) && std::isfinite(current.slope);
             }
             if (contracted)
@@ -1577,51 +1593,43 @@ int lm_solve(lm_system &S, lm_model &M, const ochip_relax_options *opt, ochip_re
                     return erc;
             }
         }
-        if (step_norm <= opt->parameter_tolerance * (x_norm + opt->parameter_tolerance))
+        if (lm_trust::parameter_converged(step_norm, x_norm, opt->parameter_tolerance))
             return finish(OCHIP_RELAX_CONVERGENCE_PARAMETER);
         const double cost_change = x_cost - cand_cost;
-        if (std::abs(cost_change) <= opt->function_tolerance * x_cost)
+        if (lm_trust::function_converged(cost_change, x_cost, opt->function_tolerance))
             return finish(OCHIP_RELAX_CONVERGENCE_FUNCTION);
         const double rho = cost_change / model_cost_change;
-        if (rho > 1e-3 && spec)
+        if (!lm_trust::accepts(rho))
         {
+            trust.on_reject();
+            sum->unsuccessful_steps++;
+            continue;
+        }
+        x_norm = cand_norm;
+        if (spec)
+        {
+            // the candidate's Jacobian is in the second set already: it becomes the system
             M.accept_swap();
             S.swap_sets();
-            x_norm = cand_norm;
             x_cost = cand_eval;
             if (fail_mask & 2) // (a derivative at the accepted point is not finite: Ceres' "evaluation failed")
                 return finish(OCHIP_RELAX_FAILURE);
             gmax = h[4];
-            const double t = 2.0 * rho - 1.0;
-            radius = radius / std::max(1.0 / 3.0, 1.0 - t * t * t);
-            radius = std::min(1e16, radius);
-            decrease_factor = 2.0;
-            sum->successful_steps++;
-            if (gmax <= opt->gradient_tolerance)
-                return finish(OCHIP_RELAX_CONVERGENCE_GRADIENT);
         }
-        else if (rho > 1e-3)
+        else
         {
             M.launch_accept();
-            x_norm = cand_norm;
             // (the gradient norm and the diagonal of the new J'J ride on the evaluation's wait)
-            auto read_gradient = [&]() {
+            M.before_wait = [&]() {
                 hipLaunchKernelGGL(lm_diag_kernel, dim3(1), dim3(LM_TG), 0, st, S.matA(), (const double *)S.g, S.diag_tmp, n, S.scal,
                                    (const double *)S.scale, S.diagonal, mail);
             };
-            if (!separate_waits)
-                M.before_wait = read_gradient;
             erc = M.evaluate(true, 0, &x_cost);
             M.before_wait = nullptr;
             if (erc < 0)
                 return erc;
             if (erc != 0)
                 return finish(OCHIP_RELAX_FAILURE);
-            if (separate_waits)
-            {
-                read_gradient();
-                OCHIP_HIP(ctx, ochip_stream_wait(ctx, st));
-            }
             gmax = h[4];
             if (eliminated)
             {
@@ -1631,20 +1639,11 @@ int lm_solve(lm_system &S, lm_model &M, const ochip_relax_options *opt, ochip_re
                     return xrc;
                 gmax = std::max(gmax, extra);
             }
-            const double t = 2.0 * rho - 1.0;
-            radius = radius / std::max(1.0 / 3.0, 1.0 - t * t * t);
-            radius = std::min(1e16, radius);
-            decrease_factor = 2.0;
-            sum->successful_steps++;
-            if (gmax <= opt->gradient_tolerance)
-                return finish(OCHIP_RELAX_CONVERGENCE_GRADIENT);
         }
-        else
-        {
-            radius = radius / decrease_factor;
-            decrease_factor *= 2.0;
-            sum->unsuccessful_steps++;
-        }
+        trust.on_accept(rho);
+        sum->successful_steps++;
+        if (gmax <= opt->gradient_tolerance)
+            return finish(OCHIP_RELAX_CONVERGENCE_GRADIENT);
     }
 }
 

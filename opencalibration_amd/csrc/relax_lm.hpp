@@ -4,11 +4,13 @@
 // reduced normal-equation system held in HBM as the 64 x 64 tiles of its block envelope (lower triangle only; the
 // reference gives the same system to SPARSE_NORMAL_CHOLESKY, relax_problem.cpp:30-37) and factored in place (relax_lm.hip).
 //
-// A problem flavour (ground plane: relax.hip; mesh / intrinsics: relax_general.hip) implements lm_model: it owns the
+// A problem flavour (ground plane: relax.hip; mesh / intrinsics: relax_general.hip; points: relax_points.hip) implements
+// lm_model: it owns the
 // state, evaluates cost / J'J / J'r into the system's buffers, and applies a step to a candidate state.
 #pragma once
 
 #include "ctx.hpp"
+#include "relax_lm_rules.hpp"
 
 #include <functional>
 #include <utility>
@@ -181,22 +183,10 @@ __device__ __forceinline__ double lm_diag_pass(const lm_matrix &A, const double 
         if (diag_out)
             diag_out[i] = d;
         if (scale)
-        {
-            const double v = d * scale[i] * scale[i];
-            const double lo = v < 1e-6 ? 1e-6 : v; // std::max(v, 1e-6), then std::min(.., 1e32): NaN passes through
-            diagonal[i] = 1e32 < lo ? 1e32 : lo;
-        }
+            diagonal[i] = lm_clamp_diagonal(d * scale[i] * scale[i]);
         m = fmax(m, fabs(g[i]));
     }
-    sh[t] = m;
-    __syncthreads();
-    for (int s = TG / 2; s > 0; s >>= 1)
-    {
-        if (t < s)
-            sh[t] = fmax(sh[t], sh[t + s]);
-        __syncthreads();
-    }
-    return sh[0];
+    return lm_block_max<TG>(m, sh);
 }
 __device__ __forceinline__ void lm_mail_post(const lm_mail &m) // one thread, after everything it mails is written
 {
@@ -322,6 +312,35 @@ struct lm_model
 };
 
 int lm_solve(lm_system &sys, lm_model &model, const ochip_relax_options *opt, ochip_relax_summary *sum);
+
+// enqueue lm_normalize_kernel: orientation.normalize() (lm_quat_normalize) for every camera with cam_optimize set - what
+// RelaxProblem::solve does to _nodes_to_optimize after Solve (relax_problem.cpp:1410-1413); an engine's launch_normalize()
+void lm_launch_normalize(ochip_ctx *ctx, double *cam_q, uint32_t n_cams, const uint8_t *cam_optimize);
+
+// ---- the host tail of an engine's evaluation ---------------------------------------------------------------------------
+// Sharded evaluation: this rank evaluates its part of the residual blocks, `exchange` all-gathers the ranks' records
+// (rank r's slice of every array at r * bytes), and every rank runs the same deterministic assembly.
+struct lm_shard
+{
+    uint32_t rank = 0, world = 1, chunk = 0; // chunk: records per rank
+    ochip_relax_exchange_fn exchange = nullptr;
+    void *exchange_user = nullptr;
+    int32_t *fail_ranks = nullptr; // device, [world]: the ranks' evaluation flags
+    bool flags_fit_box() const       // the ranks' flags fit the host block: an evaluation's last kernel can mail them
+    {
+        return world <= (uint32_t)(2 * (lm_system::BOX_VECTORS - lm_system::BOX_FAILS));
+    }
+};
+// All-gather the ranks' records, costs and failure flags in place (nothing to do without an exchange function).  The native
+// transport enqueues its all-gathers on the context's stream: stream order is all it needs; a callback transport reads the
+// arrays from outside the stream, which is waited for first.  A failed exchange is a hard error: the ranks would otherwise
+// leave the solve on different schedules and the next collective would hang.
+int lm_exchange_records(ochip_ctx *ctx, const lm_shard &shard, void *data, uint64_t data_bytes, void *cost, uint64_t cost_bytes);
+// What ends an evaluation: unless its last kernel mails them, the cost (scal[0]) and the ranks' flags are copied into the
+// host block (pageable memory only for more ranks than the block holds) and *clear_flag (this rank's flag, or nullptr) is
+// zeroed behind them; before_wait() enqueues the caller's own reads; one wait.  *cost, *fail_or = OR of the ranks' flags.
+int lm_finish_evaluation(lm_system &sys, const lm_shard &shard, bool mailed, int32_t *clear_flag,
+                         const std::function<void()> &before_wait, double *cost, int *fail_or);
 
 // ---- the linear algebra of one LM step, shared by lm_solve and the test seam ochip_debug_lm_step ------------------------
 enum

@@ -139,19 +139,12 @@ __device__ __forceinline__ void back_solve_regions_body(lm_matrix Lm, int n, con
             x[i] = v;
             part_sum += v * gs[i] + lm_diag[i] * v * v;
         }
-    sh[t] = part_sum;
     // (x[] / X's stores of every wavefront have left it before the barriers in front of thread 0's release and arrival)
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    for (int s = LM_TG / 2; s > 0; s >>= 1)
-    {
-        if (t < s)
-            sh[t] += sh[t + s];
-        __syncthreads();
-    }
+    const double region_sum = lm_block_sum<LM_TG>(part_sum, sh);
     if (t == 0)
     {
-        __hip_atomic_store(&parts[r], sh[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(&parts[r], region_sum, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         s_last = __hip_atomic_fetch_add(arrived, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT) == (unsigned int)(m - 1);

@@ -501,29 +501,14 @@ __global__ __launch_bounds__(LM_TG) void p_reduce_kernel(p_dev P, int with_gmax,
     if (with_gmax)
         for (uint32_t i = t; i < 3 * P.n_points; i += LM_TG)
             m = fmax(m, fabs(P.pt_g[i]));
-    sh[t] = v;
+    const double total = lm_block_sum<LM_TG>(v, sh) + (P.mono_w > 0 ? P.mono[0] : 0.0);
     __syncthreads();
-    for (int s = LM_TG / 2; s > 0; s >>= 1)
-    {
-        if (t < s)
-            sh[t] += sh[t + s];
-        __syncthreads();
-    }
-    const double total = sh[0] + (P.mono_w > 0 ? P.mono[0] : 0.0);
-    __syncthreads();
-    sh[t] = m;
-    __syncthreads();
-    for (int s = LM_TG / 2; s > 0; s >>= 1)
-    {
-        if (t < s)
-            sh[t] = fmax(sh[t], sh[t + s]);
-        __syncthreads();
-    }
+    const double gmax = lm_block_max<LM_TG>(m, sh);
     if (t == 0)
     {
         scal[0] = total;
         if (with_gmax)
-            scal[5] = sh[0];
+            scal[5] = gmax;
     }
 }
 
@@ -536,42 +521,7 @@ __global__ __launch_bounds__(LM_TG) void p_candidate_kernel(p_dev P, const doubl
     __shared__ double sh[LM_TG];
     const int t = threadIdx.x;
     double sn = 0, xn = 0, mc = 0, slope = 0;
-    for (uint32_t c = t; c < P.n_cams; c += LM_TG)
-    {
-        const int tc = P.cam_t[c];
-        const double *q = P.cam_q + (size_t)c * 4;
-        double *o = P.cam_q2 + (size_t)c * 4;
-        if (tc < 0)
-        {
-            for (int k = 0; k < 4; k++)
-                o[k] = q[k];
-            continue;
-        }
-        double d[3];
-        for (int k = 0; k < 3; k++)
-            d[k] = alpha * (-y[tc + k] * scale[tc + k]);
-        const double nrm = sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
-        if (nrm == 0.0)
-        {
-            for (int k = 0; k < 4; k++)
-                o[k] = q[k];
-        }
-        else
-        {
-            const double s = sin(nrm) / nrm;
-            const double dx = s * d[0], dy = s * d[1], dz = s * d[2], dw = cos(nrm);
-            const double qx = q[0], qy = q[1], qz = q[2], qw = q[3];
-            o[3] = dw * qw - dx * qx - dy * qy - dz * qz;
-            o[0] = dw * qx + dx * qw + dy * qz - dz * qy;
-            o[1] = dw * qy + dy * qw + dz * qx - dx * qz;
-            o[2] = dw * qz + dz * qw + dx * qy - dy * qx;
-        }
-        for (int k = 0; k < 4; k++)
-        {
-            sn += (q[k] - o[k]) * (q[k] - o[k]);
-            xn += o[k] * o[k];
-        }
-    }
+    lm_candidate_cams<LM_TG>(P.n_cams, P.cam_t, P.cam_q, P.cam_q2, y, scale, alpha, &sn, &xn);
     if (t == 0)
     {
         // parameter blocks: focal (1, bounded), principal point (2), radial (3, SubsetManifold: trailing constants count
@@ -632,6 +582,7 @@ __global__ __launch_bounds__(LM_TG) void p_candidate_kernel(p_dev P, const doubl
         const double dg[3] = {V[0], V[3], V[5]};
         for (int a = 0; a < 3; a++)
         {
+            // (fmin / fmax drop a NaN where lm_clamp_diagonal passes it on: this site keeps its own form, its results unchanged)
             const double d2 = fmin(fmax(dg[a] * Sp[a] * Sp[a], 1e-6), 1e32) / radius;
             mc += 0.5 * (d2 * dp[a] * dp[a] - P.pt_g[3 * (size_t)p + a] * Sp[a] * dp[a]);
             const double full = Sp[a] * dp[a], x0 = P.X[3 * (size_t)p + a], x1 = x0 + alpha * full;
@@ -646,15 +597,7 @@ __global__ __launch_bounds__(LM_TG) void p_candidate_kernel(p_dev P, const doubl
     const double part[4] = {sn, xn, mc, slope};
     for (int q = 0; q < 4; q++)
     {
-        sh[t] = part[q];
-        __syncthreads();
-        for (int s = LM_TG / 2; s > 0; s >>= 1)
-        {
-            if (t < s)
-                sh[t] += sh[t + s];
-            __syncthreads();
-        }
-        out[q] = sh[0];
+        out[q] = lm_block_sum<LM_TG>(part[q], sh);
         __syncthreads();
     }
     if (t == 0)
@@ -677,16 +620,9 @@ __global__ __launch_bounds__(LM_TG) void p_slope_kernel(p_dev P, double *scal)
     double v = 0;
     for (uint32_t i = t; i < 3 * P.n_points; i += LM_TG)
         v += P.pt_g[i] * P.pt_d[i];
-    sh[t] = v;
-    __syncthreads();
-    for (int s = LM_TG / 2; s > 0; s >>= 1)
-    {
-        if (t < s)
-            sh[t] += sh[t + s];
-        __syncthreads();
-    }
+    const double sum = lm_block_sum<LM_TG>(v, sh);
     if (t == 0)
-        scal[6] = sh[0];
+        scal[6] = sum;
 }
 
 __global__ void p_accept_kernel(p_dev P)
@@ -698,21 +634,6 @@ __global__ void p_accept_kernel(p_dev P)
         P.X[i] = P.X2[i];
     if (i < 8)
         P.model[i] = P.model2[i];
-}
-
-__global__ void p_normalize_kernel(p_dev P, const uint8_t *cam_optimize)
-{
-    const uint32_t c = blockIdx.x * blockDim.x + threadIdx.x;
-    if (c >= P.n_cams || !cam_optimize[c])
-        return;
-    double *q = P.cam_q + 4 * (size_t)c;
-    const double n2 = q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3];
-    if (n2 > 0.0) // Eigen's normalize()
-    {
-        const double nn = sqrt(n2);
-        for (int k = 0; k < 4; k++)
-            q[k] /= nn;
-    }
 }
 
 } // namespace
@@ -900,8 +821,7 @@ struct points_model final : lm_model
     }
     void launch_normalize() override
     {
-        if (p->n_cams)
-            hipLaunchKernelGGL(p_normalize_kernel, dim3((p->n_cams + 255) / 256), dim3(256), 0, p->ctx->stream, p->dev, p->cam_optimize_dev);
+        lm_launch_normalize(p->ctx, p->dev.cam_q, p->n_cams, p->cam_optimize_dev);
     }
     int x_norm(double *out) override
     {

@@ -1,6 +1,7 @@
 """The plane relax engine's evaluation on the device (ochip_relax_evaluate: relax_pair_eval_kernel with its 64-block trips,
 the role columns of a pair, scatter_cam / scatter_pair / relax_reduce_plane_kernel into the tiles of the block envelope,
-the renumbering and the dissection of the camera graph, plane_candidate_kernel's quaternion plus) against the long-double
+the renumbering and the dissection of the camera graph, plane_candidate_kernel's quaternion plus: lm_candidate_cams of
+relax_lm_rules.hpp) against the long-double
 oracle (oracle/relax_eval.cpp) on the problems of tests/plane_eval_fixtures.py: cost (of the reduced program), J'J and J'r
 within the normwise bounds of tests/relax_eval_fixtures.py, the same unknowns (this engine has no padding columns: every
 unknown belongs to an active camera or a free height), and a failing block reported as a failure on every route.  Every
