@@ -722,6 +722,28 @@ extern "C"
     void och_jpeg_decoder_destroy(och_jpeg_decoder *d);
     const char *och_jpeg_decode_last_error(void);
 
+    /* ---- the tiles of the tiled DEFLATE GeoTIFFs (opencalibration_amd/csrc/host/geotiff.cpp, csrc/deflate_rules.hpp;
+     *      DESIGN.md section 4.19) ----
+     * The writer of include/ochip.h (ochip_geotiff_*) over both routes.  ctx != NULL: the device route, as described there.
+     * ctx == NULL: the CPU route, host bands, the same rules in loops (a tile row's tiles under OpenMP) and the same bytes.
+     * The message of a refusal is in och_geotiff_last_error; a handle that create did not return or destroy has taken is
+     * refused, not followed.
+     * och_deflate_code_lengths: the length limiter of the rules alone - lens[s] of at most `limit` bits for n <= 286
+     * counts. */
+#define OCH_GEOTIFF_RGBA8 OCHIP_GEOTIFF_RGBA8
+#define OCH_GEOTIFF_FLOAT32 OCHIP_GEOTIFF_FLOAT32
+#define OCH_GEOTIFF_MAX_SIDE OCHIP_GEOTIFF_MAX_SIDE
+    typedef struct och_geotiff och_geotiff;
+    int och_geotiff_create(ochip_ctx *ctx, int kind, int64_t width, int64_t height, int sparse, och_geotiff **out);
+    int och_geotiff_feed(och_geotiff *e, int64_t row0, int64_t rows, const void *pixels, int on_device);
+    int och_geotiff_payloads(och_geotiff *e, const uint8_t *payloads, int64_t n);
+    int och_geotiff_collect(och_geotiff *e, uint8_t *buf /* or NULL */, uint64_t cap, uint64_t *bytes,
+                            uint64_t *counts /* or NULL */, uint64_t max_tiles, uint64_t *tiles);
+    int och_geotiff_finish(och_geotiff *e);
+    void och_geotiff_destroy(och_geotiff *e);
+    const char *och_geotiff_last_error(void);
+    int och_deflate_code_lengths(const uint32_t *counts, int n, int limit, uint8_t *lens);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1098,6 +1098,37 @@ extern "C"
                                   ochip_jpeg_file_info *info /* [n] */, int32_t *rounds /* [2] or NULL */);
     void ochip_jpeg_decoder_destroy(ochip_jpeg_decoder *d);
 
+    /* ---- the tiles of the tiled DEFLATE GeoTIFFs (opencalibration_amd/csrc/geotiff.hip, the rules in
+     *      csrc/deflate_rules.hpp; the reference's createGeoTIFF / createDSMGeoTIFF, src/ortho/ortho.cpp:655-708 and
+     *      :745-791) ----
+     * A writer belongs to one raster of width x height pixels of 4 bytes: kind 0 R G B A bytes, kind 1 one float32.  It
+     * turns the raster, fed band by band on the context's stream, into the zlib streams of its 512 x 512 tiles: horizontal
+     * predictor, one deflate block per 16 384 bytes, or the stored form when that is not larger; no stream exceeds
+     * 1 048 667 bytes.  The TIFF structure around the streams is the caller's (host.GeoTiffWriter).
+     * feed: bands ascend from row 0 without gaps, of any row count; rows behind the last complete tile row are kept on the
+     *   device (at most 511), a tile row is encoded once complete, the last at the raster's end.  on_device: pixels is a
+     *   device pointer whose producer has run, or is enqueued on the context's stream; the call does not wait for what it
+     *   enqueues.  Otherwise a host pointer that may be reused on return.
+     * payloads: n predicted payloads of 1 048 576 bytes (host memory) straight into the encoder, n at most the raster's
+     *   tiles across; their streams are collected like a tile row's.
+     * collect: the streams of the tiles complete so far, in tile order, back to back in buf, counts[k] the bytes of the
+     *   k-th (0: an all-zero RGBA tile of a sparse writer, nothing is kept for it).  buf and counts NULL: only *bytes and
+     *   *tiles, what a collect would need now.  Waits for the encoded tile rows alone.
+     * finish: every row has been fed.  OCHIP_EINVAL and a message, before anything is launched, for a kind or side out of
+     * range, a NULL band, a gap, an overlap, rows beyond the raster, too little room, and a handle that create did not
+     * return or destroy has taken; OCHIP_ESTATE for a feed after finish and a finish before the last row. */
+#define OCHIP_GEOTIFF_RGBA8 0
+#define OCHIP_GEOTIFF_FLOAT32 1
+#define OCHIP_GEOTIFF_MAX_SIDE 1048576
+    typedef struct ochip_geotiff ochip_geotiff;
+    int ochip_geotiff_create(ochip_ctx *ctx, int kind, int64_t width, int64_t height, int sparse, ochip_geotiff **out);
+    int ochip_geotiff_feed(ochip_geotiff *e, int64_t row0, int64_t rows, const void *pixels, int on_device);
+    int ochip_geotiff_payloads(ochip_geotiff *e, const uint8_t *payloads, int64_t n);
+    int ochip_geotiff_collect(ochip_geotiff *e, uint8_t *buf /* or NULL */, uint64_t cap, uint64_t *bytes,
+                              uint64_t *counts /* or NULL */, uint64_t max_tiles, uint64_t *tiles);
+    int ochip_geotiff_finish(ochip_geotiff *e);
+    void ochip_geotiff_destroy(ochip_geotiff *e);
+
 #ifdef __cplusplus
 }
 #endif

@@ -56,6 +56,8 @@ EXPORTS = [
     "ochip_xyz_export_text_size", "ochip_xyz_export_text", "ochip_xyz_export_destroy", "ochip_debug_format_g6",
     "ochip_jpeg_create", "ochip_jpeg_feed", "ochip_jpeg_pending", "ochip_jpeg_collect", "ochip_jpeg_finish", "ochip_jpeg_destroy",
     "ochip_jpeg_decoder_create", "ochip_jpeg_decoder_decode", "ochip_jpeg_decoder_destroy",
+    "ochip_geotiff_create", "ochip_geotiff_feed", "ochip_geotiff_payloads", "ochip_geotiff_collect", "ochip_geotiff_finish",
+    "ochip_geotiff_destroy",
 ]
 
 _lib = None
@@ -312,6 +314,13 @@ def load():
         L.ochip_jpeg_decoder_decode.argtypes = [vp, C.c_int64, vp, vp, i32, vp, u64, vp, vp, vp]
         L.ochip_jpeg_decoder_destroy.argtypes = [vp]
         L.ochip_jpeg_decoder_destroy.restype = None
+        L.ochip_geotiff_create.argtypes = [vp, i32, C.c_int64, C.c_int64, i32, C.POINTER(vp)]
+        L.ochip_geotiff_feed.argtypes = [vp, C.c_int64, C.c_int64, vp, i32]
+        L.ochip_geotiff_payloads.argtypes = [vp, vp, C.c_int64]
+        L.ochip_geotiff_collect.argtypes = [vp, vp, u64, C.POINTER(u64), vp, u64, C.POINTER(u64)]
+        L.ochip_geotiff_finish.argtypes = [vp]
+        L.ochip_geotiff_destroy.argtypes = [vp]
+        L.ochip_geotiff_destroy.restype = None
         _lib = L
     return _lib
 

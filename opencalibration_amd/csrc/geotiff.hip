@@ -1,0 +1,834 @@
+// The tiles of the tiled DEFLATE GeoTIFFs on the device (the rules: deflate_rules.hpp).  A feed copies
+// its rows into the tile row being filled; a complete tile row is one pass of these launches on the context's stream:
+//   gt_payload     512 x 512 tiles out of the rows: 16-byte loads where the width allows, the horizontal predictor, zeros
+//                  beyond the raster; a tile's any-non-zero flag
+//   gt_parse       a workgroup per 16 384-byte segment: a lane compares its 64 bytes with the pixel to the left and the pixel
+//                  above into two 64-bit masks, the runs come from the masks and the heads of the chunks behind (LDS); the
+//                  greedy parse - a walk from the segment's start - is cut into the lanes' chunks: where a walk that enters
+//                  a chunk at each of its positions leaves it (64 steps a lane, all lanes at once), one lane's hops from
+//                  chunk to chunk (at most 256), then every entered chunk marks and counts its tokens; the segment's
+//                  Adler-32 partial
+//   gt_codes       a wave per block: the counts, the code construction's arrays and the header in LDS, the construction itself
+//                  - sequential by nature - on one lane; the block's bits
+//   (rocPRIM)      exclusive scan of the blocks' bits
+//   gt_tile_sizes  a lane a tile: its bits, deflated or stored or left out, its Adler-32 from the 64 partials
+//   (rocPRIM)      exclusive scan of the tiles' 16-byte-aligned sizes: where each lies in the pass's output
+//   gt_emit        a workgroup per block: a lane sums the bits of the tokens that start in its 64 bytes, a scan over the
+//                  workgroup places them, whole words are stored and the two ragged ones ORed into the zeroed buffer
+//   gt_stored      the stored form of the tiles that did not shrink
+//   gt_finish      78 9C and the Adler-32 of the deflated tiles; offsets and counts for the host
+// and two copies to page-locked memory: the offsets and counts, and as many bytes as the pass before suggests.  A pass writes
+// into one of OUT_SLOTS output slots with an event each; the host reads a slot when a pass needs it again, at collect or at
+// finish - one wait, for the slot's event, and so not for what the caller enqueued on the stream since.
+#include "ctx.hpp"
+#include "deflate_rules.hpp"
+
+#include <rocprim/device/device_scan.hpp>
+#include <rocprim/iterator/transform_iterator.hpp>
+
+#include <deque>
+#include <memory>
+#include <mutex>
+#include <set>
+#include <vector>
+
+namespace
+{
+
+using namespace ochip_df;
+
+constexpr int THREADS = 256, CHUNK = SEGMENT / THREADS; // a lane's 64 bytes of a segment
+constexpr int OUT_SLOTS = 4;
+static_assert(CHUNK == 64, "a lane's bytes are the bits of one 64-bit mask");
+
+// skip: the tile is all zero and the writer sparse
+__device__ bool skipped(const uint32_t *nz, int sparse, int tile)
+{
+    return sparse && nz[tile] == 0;
+}
+
+__global__ __launch_bounds__(THREADS) void gt_payload(const uint32_t *rows, int64_t w, int is_float, int vec, int tiles, uint8_t *payload,
+                                                       uint32_t *nz)
+{
+    const int tile = blockIdx.y, idx = (int)blockIdx.x * THREADS + (int)threadIdx.x;
+    const int r = idx >> 7, q = idx & 127;
+    if (tile >= tiles || r >= TILE)
+        return;
+    const int64_t X0 = (int64_t)tile * TILE + q * 4;
+    const uint32_t *src = rows + (size_t)r * (size_t)w;
+    uint32_t cur[4] = {0, 0, 0, 0};
+    if (vec && X0 + 3 < w)
+    {
+        const uint4 v = *reinterpret_cast<const uint4 *>(src + X0);
+        cur[0] = v.x, cur[1] = v.y, cur[2] = v.z, cur[3] = v.w;
+    }
+    else
+    {
+#pragma unroll
+        for (int j = 0; j < 4; j++)
+            cur[j] = X0 + j < w ? src[X0 + j] : 0;
+    }
+    const uint32_t left = q > 0 && X0 - 1 < w ? src[X0 - 1] : 0;
+    uint4 o;
+    o.x = q == 0 ? cur[0] : predict_word(cur[0], left, is_float != 0);
+    o.y = predict_word(cur[1], cur[0], is_float != 0);
+    o.z = predict_word(cur[2], cur[1], is_float != 0);
+    o.w = predict_word(cur[3], cur[2], is_float != 0);
+    *reinterpret_cast<uint4 *>(payload + (size_t)tile * PAYLOAD + (size_t)r * ROW_BYTES + (size_t)q * 16) = o;
+    const bool any = (cur[0] | cur[1] | cur[2] | cur[3]) != 0;
+    if (__ballot(any) != 0 && (threadIdx.x & 63) == 0)
+        atomicOr(&nz[tile], 1u);
+}
+
+__device__ int ones_from(uint64_t m, int j) // the run of set bits of m from bit j upwards, at most 64 - j
+{
+    const uint64_t x = ~(m >> j);
+    return x ? __builtin_ctzll(x) : 64;
+}
+
+__global__ __launch_bounds__(THREADS) void gt_parse(const uint8_t *payload, const uint32_t *nz, int sparse, int blocks, uint16_t *tok,
+                                                     uint32_t *counts, uint32_t *seg_adler)
+{
+    constexpr uint16_t MARK_OVER = 0x200; // a mark's spare bit, inside this kernel only
+    constexpr int NOT_ENTERED = CHUNK;    // the walk jumps over the chunk
+    __shared__ uint16_t best[SEGMENT];
+    __shared__ uint8_t leave[SEGMENT];
+    __shared__ uint8_t entry[THREADS];
+    __shared__ uint16_t head[2][THREADS];
+    __shared__ uint32_t cnt[NUM_SYMS];
+    __shared__ uint32_t ad1[THREADS], ad2[THREADS];
+    const int b = blockIdx.x, t = threadIdx.x;
+    if (b >= blocks)
+        return;
+    const int tile = b / SEGMENTS, seg = b % SEGMENTS;
+    if (skipped(nz, sparse, tile))
+        return;
+    const uint8_t *a = payload + (size_t)tile * PAYLOAD;
+    const int P0 = seg * SEGMENT + t * CHUNK;
+    const bool has_left = P0 >= DIST_LEFT, has_up = P0 >= DIST_UP;
+    uint32_t prev = has_left ? *reinterpret_cast<const uint32_t *>(a + P0 - DIST_LEFT) : 0;
+    uint64_t m_left = 0, m_up = 0;
+    uint32_t s1 = 0, s2 = 0;
+#pragma unroll
+    for (int i = 0; i < CHUNK / 16; i++)
+    {
+        const uint4 c4 = *reinterpret_cast<const uint4 *>(a + P0 + i * 16);
+        uint4 u4 = make_uint4(0, 0, 0, 0);
+        if (has_up)
+            u4 = *reinterpret_cast<const uint4 *>(a + P0 - DIST_UP + i * 16);
+        const uint32_t c[4] = {c4.x, c4.y, c4.z, c4.w}, u[4] = {u4.x, u4.y, u4.z, u4.w};
+#pragma unroll
+        for (int k = 0; k < 4; k++)
+        {
+            const uint32_t xl = c[k] ^ prev, xu = c[k] ^ u[k];
+#pragma unroll
+            for (int y = 0; y < 4; y++)
+            {
+                const int j = i * 16 + k * 4 + y;
+                const uint32_t byte = (c[k] >> (8 * y)) & 255u;
+                if (((xl >> (8 * y)) & 255u) == 0)
+                    m_left |= 1ull << j;
+                if (((xu >> (8 * y)) & 255u) == 0)
+                    m_up |= 1ull << j;
+                s1 += byte, s2 += (uint32_t)(CHUNK - j) * byte;
+            }
+            prev = c[k];
+        }
+    }
+    if (!has_left) // the tile's first pixel has nothing to its left
+        m_left &= ~0xFull;
+    if (!has_up)
+        m_up = 0;
+    head[0][t] = (uint16_t)ones_from(m_left, 0), head[1][t] = (uint16_t)ones_from(m_up, 0);
+    ad1[t] = 1 + s1, ad2[t] = (CHUNK + s2) % ADLER_MOD;
+    for (int i = t; i < NUM_SYMS; i += THREADS)
+        cnt[i] = 0;
+    __syncthreads();
+    // how far a run that reaches this chunk's end goes on in the chunks behind, the segment's end the limit
+    int more[2] = {0, 0};
+#pragma unroll
+    for (int d = 0; d < 2; d++)
+    {
+        int r = 0;
+        for (int k = t + 1; k < THREADS; k++)
+        {
+            const int h = head[d][k];
+            r += h;
+            if (h < CHUNK || r >= MAX_MATCH)
+                break;
+        }
+        more[d] = r;
+    }
+    for (int j = 0; j < CHUNK; j++)
+    {
+        int rl = ones_from(m_left, j), ru = ones_from(m_up, j);
+        if (rl == CHUNK - j)
+            rl += more[0];
+        if (ru == CHUNK - j)
+            ru += more[1];
+        best[t * CHUNK + j] = choose_match(rl, ru);
+    }
+    // The greedy parse is a walk from the segment's start.  Each lane first finds, for every position of its chunk, how far
+    // behind the chunk's end a walk entering there leaves it (0 .. 257: nine bits, the ninth in the mark's spare bit);
+    // backwards, so a position reads the answer of the one it steps to.  One lane then hops from chunk to chunk - at most
+    // 256 hops instead of 16 384 steps - and every entered chunk marks its own tokens.
+    for (int e = CHUNK - 1; e >= 0; e--)
+    {
+        const uint16_t m = best[t * CHUNK + e];
+        const int len = m & MARK_LEN, n = e + (len ? len : 1);
+        int over;
+        if (n >= CHUNK)
+            over = n - CHUNK;
+        else
+            over = leave[t * CHUNK + n] | ((best[t * CHUNK + n] & MARK_OVER) ? 256 : 0);
+        leave[t * CHUNK + e] = (uint8_t)over;
+        if (over & 256)
+            best[t * CHUNK + e] = m | MARK_OVER;
+    }
+    entry[t] = NOT_ENTERED;
+    __syncthreads();
+    if (t == 0)
+    {
+        for (int c = 0, e = 0; c < THREADS;)
+        {
+            entry[c] = (uint8_t)e;
+            const int at = c * CHUNK + e;
+            const int next = (c + 1) * CHUNK + (leave[at] | ((best[at] & MARK_OVER) ? 256 : 0));
+            c = next / CHUNK, e = next % CHUNK;
+        }
+    }
+    else if (t == 64)
+    {
+        uint32_t a1 = ad1[0], a2 = ad2[0];
+        for (int k = 1; k < THREADS; k++)
+            adler_combine(a1, a2, ad1[k], ad2[k], CHUNK);
+        seg_adler[2 * (size_t)b] = a1, seg_adler[2 * (size_t)b + 1] = a2;
+    }
+    __syncthreads();
+    // the tokens of this lane's chunk, if the walk enters it: marked and counted in one pass
+    for (int j = entry[t]; j < CHUNK;)
+    {
+        const uint16_t m = best[t * CHUNK + j];
+        best[t * CHUNK + j] = m | MARK_START;
+        int ds;
+        const int ls = token_symbols(m, a[P0 + j], ds);
+        atomicAdd(&cnt[ls], 1u);
+        if (ds >= 0)
+            atomicAdd(&cnt[NUM_LIT + ds], 1u);
+        const int len = m & MARK_LEN;
+        j += len ? len : 1;
+    }
+    __syncthreads();
+    uint16_t *out = tok + (size_t)tile * PAYLOAD + (size_t)seg * SEGMENT;
+    for (int i = t; i < SEGMENT; i += THREADS)
+        out[i] = best[i] & (uint16_t)~MARK_OVER;
+    for (int i = t; i < NUM_SYMS; i += THREADS)
+        counts[(size_t)b * NUM_SYMS + i] = cnt[i];
+}
+
+__global__ __launch_bounds__(64) void gt_codes(const uint32_t *counts, const uint32_t *nz, int sparse, int blocks, uint32_t *codes,
+                                                uint32_t *header, uint32_t *header_bits, uint32_t *block_bits)
+{
+    __shared__ block_work W;
+    __shared__ uint32_t c[NUM_SYMS];
+    __shared__ uint32_t h[HEADER_WORDS];
+    __shared__ uint32_t hb;
+    const int b = blockIdx.x, t = threadIdx.x;
+    if (b >= blocks)
+        return;
+    if (skipped(nz, sparse, b / SEGMENTS))
+        return; // block_bits was zeroed
+    for (int i = t; i < NUM_SYMS; i += 64)
+        W.counts[i] = counts[(size_t)b * NUM_SYMS + i];
+    for (int i = t; i < HEADER_WORDS; i += 64)
+        h[i] = 0;
+    __syncthreads();
+    if (t == 0)
+    {
+        uint32_t bits_of_header = 0;
+        block_bits[b] = build_block(W, b % SEGMENTS == SEGMENTS - 1, c, h, bits_of_header);
+        hb = bits_of_header;
+    }
+    __syncthreads();
+    for (int i = t; i < NUM_SYMS; i += 64)
+        codes[(size_t)b * NUM_SYMS + i] = c[i];
+    for (int i = t; i < HEADER_WORDS; i += 64)
+        header[(size_t)b * HEADER_WORDS + i] = h[i];
+    if (t == 0)
+        header_bits[b] = hb;
+}
+
+// state: 0 deflated, 1 stored, 2 left out; count: the stream's bytes; size[tiles] = 0 so that the scan's last output is the total
+__global__ __launch_bounds__(THREADS) void gt_tile_sizes(const unsigned long long *block_off, const uint32_t *seg_adler, const uint32_t *nz,
+                                                          int sparse, int tiles, uint32_t *state, uint32_t *count, uint32_t *size,
+                                                          uint32_t *adler)
+{
+    const int i = (int)blockIdx.x * THREADS + (int)threadIdx.x;
+    if (i > tiles)
+        return;
+    if (i == tiles)
+    {
+        size[i] = 0;
+        return;
+    }
+    if (skipped(nz, sparse, i))
+    {
+        state[i] = 2, count[i] = 0, size[i] = 0, adler[i] = 0;
+        return;
+    }
+    const unsigned long long bits = block_off[(size_t)(i + 1) * SEGMENTS] - block_off[(size_t)i * SEGMENTS];
+    const unsigned long long bytes = 6 + (bits + 7) / 8;
+    const bool stored = bytes >= (unsigned long long)STORED_BYTES;
+    const uint32_t n = stored ? (uint32_t)STORED_BYTES : (uint32_t)bytes;
+    state[i] = stored ? 1 : 0, count[i] = n, size[i] = (n + 15u) & ~15u;
+    uint32_t a1 = seg_adler[2 * (size_t)i * SEGMENTS], a2 = seg_adler[2 * (size_t)i * SEGMENTS + 1];
+    for (int k = 1; k < SEGMENTS; k++)
+        adler_combine(a1, a2, seg_adler[2 * ((size_t)i * SEGMENTS + k)], seg_adler[2 * ((size_t)i * SEGMENTS + k) + 1], SEGMENT);
+    adler[i] = a2 << 16 | a1;
+}
+
+// Bits LSB first from bit `pos` of a tile's words.  A word this lane fills alone is stored; the first word when the lane starts
+// inside it and the last partial one are ORed into the zeroed buffer.  Nothing is written at or beyond cap.
+struct tile_writer
+{
+    uint32_t *words;
+    uint32_t cap, wi;
+    uint64_t acc;
+    int n;
+    bool shared_first;
+    __device__ void put(uint32_t v, int len) // len <= 24
+    {
+        acc |= (uint64_t)v << n, n += len;
+        if (n >= 32)
+        {
+            if (wi < cap)
+            {
+                if (shared_first)
+                    atomicOr(&words[wi], (uint32_t)acc);
+                else
+                    words[wi] = (uint32_t)acc;
+            }
+            shared_first = false;
+            wi++, n -= 32, acc >>= 32;
+        }
+    }
+    __device__ void flush()
+    {
+        if (n > 0 && wi < cap)
+            atomicOr(&words[wi], (uint32_t)acc);
+    }
+};
+
+__global__ __launch_bounds__(THREADS) void gt_emit(const uint8_t *payload, const uint16_t *tok, const uint32_t *codes, const uint32_t *header,
+                                                    const uint32_t *header_bits, const unsigned long long *block_off,
+                                                    const unsigned long long *tile_off, const uint32_t *state, const uint32_t *size,
+                                                    int blocks, uint8_t *out, unsigned long long out_cap)
+{
+    __shared__ uint32_t c[NUM_SYMS];
+    __shared__ uint32_t sc[THREADS];
+    const int b = blockIdx.x, t = threadIdx.x;
+    if (b >= blocks)
+        return;
+    const int tile = b / SEGMENTS, seg = b % SEGMENTS;
+    if (state[tile] != 0 || tile_off[tile] + size[tile] > out_cap)
+        return;
+    for (int i = t; i < NUM_SYMS; i += THREADS)
+        c[i] = codes[(size_t)b * NUM_SYMS + i];
+    __syncthreads();
+    const uint8_t *a = payload + (size_t)tile * PAYLOAD + (size_t)seg * SEGMENT + (size_t)t * CHUNK;
+    const uint16_t *marks = tok + (size_t)tile * PAYLOAD + (size_t)seg * SEGMENT + (size_t)t * CHUNK;
+    const uint32_t hbits = header_bits[b];
+    uint32_t bits = 0;
+    for (int j = 0; j < CHUNK; j++)
+    {
+        const uint16_t m = marks[j];
+        if (m & MARK_START)
+        {
+            int n;
+            (void)token_bits(m, a[j], c, n);
+            bits += (uint32_t)n;
+        }
+    }
+    if (t == 0)
+        bits += hbits;
+    if (t == THREADS - 1)
+        bits += c[EOB] >> 16;
+    sc[t] = bits;
+    __syncthreads();
+    for (int o = 1; o < THREADS; o <<= 1)
+    {
+        const uint32_t v = t >= o ? sc[t - o] : 0;
+        __syncthreads();
+        sc[t] += v;
+        __syncthreads();
+    }
+    const unsigned long long pos = 16 + (block_off[b] - block_off[(size_t)tile * SEGMENTS]) + (sc[t] - bits);
+    tile_writer w;
+    w.words = reinterpret_cast<uint32_t *>(out + tile_off[tile]), w.cap = size[tile] / 4;
+    w.wi = (uint32_t)(pos >> 5), w.acc = 0, w.n = (int)(pos & 31), w.shared_first = w.n != 0;
+    if (t == 0)
+    {
+        const uint32_t *h = header + (size_t)b * HEADER_WORDS;
+        for (uint32_t at = 0; at < hbits && at < HEADER_WORDS * 32; at += 16)
+        {
+            const int n = hbits - at < 16 ? (int)(hbits - at) : 16;
+            w.put((h[at >> 5] >> (at & 31)) & ((1u << n) - 1), n);
+        }
+    }
+    for (int j = 0; j < CHUNK; j++)
+    {
+        const uint16_t m = marks[j];
+        if (m & MARK_START)
+        {
+            int n;
+            const uint64_t v = token_bits(m, a[j], c, n);
+            w.put((uint32_t)(v & 0xFFFFFF), n < 24 ? n : 24);
+            if (n > 24)
+                w.put((uint32_t)(v >> 24), n - 24);
+        }
+    }
+    if (t == THREADS - 1)
+        w.put(c[EOB] & 0xFFFF, (int)(c[EOB] >> 16));
+    w.flush();
+}
+
+__global__ __launch_bounds__(THREADS) void gt_stored(const uint8_t *payload, const unsigned long long *tile_off, const uint32_t *state,
+                                                      const uint32_t *adler, int tiles, uint8_t *out, unsigned long long out_cap)
+{
+    const int tile = blockIdx.y;
+    const uint32_t i = blockIdx.x * THREADS + threadIdx.x;
+    if (tile >= tiles || state[tile] != 1 || i >= (uint32_t)TILE_SLOT / 4 || tile_off[tile] + TILE_SLOT > out_cap)
+        return;
+    const uint8_t *a = payload + (size_t)tile * PAYLOAD;
+    const uint32_t ad = adler[tile];
+    uint32_t word = 0;
+#pragma unroll
+    for (uint32_t k = 0; k < 4; k++)
+    {
+        const uint32_t o = i * 4 + k;
+        if (o < (uint32_t)STORED_BYTES)
+            word |= (uint32_t)stored_byte(o, a, ad) << (8 * k);
+    }
+    reinterpret_cast<uint32_t *>(out + tile_off[tile])[i] = word;
+}
+
+// info: [0, tiles] the tiles' offsets in the slot and the total, [tiles + 1, 2 tiles + 1) their byte counts
+__global__ __launch_bounds__(THREADS) void gt_finish(const unsigned long long *tile_off, const uint32_t *state, const uint32_t *count,
+                                                      const uint32_t *adler, int tiles, uint8_t *out, unsigned long long out_cap,
+                                                      unsigned long long *info)
+{
+    const int i = (int)blockIdx.x * THREADS + (int)threadIdx.x;
+    if (i > tiles)
+        return;
+    info[i] = tile_off[i];
+    if (i == tiles)
+        return;
+    info[tiles + 1 + i] = count[i];
+    if (state[i] != 0 || tile_off[i] + count[i] > out_cap || count[i] < 6)
+        return;
+    uint8_t *p = out + tile_off[i];
+    p[0] = 0x78, p[1] = 0x9C;
+    for (int k = 0; k < 4; k++)
+        p[count[i] - 4 + k] = (uint8_t)(adler[i] >> (8 * (3 - k)));
+}
+
+struct widen
+{
+    __host__ __device__ unsigned long long operator()(uint32_t v) const
+    {
+        return v;
+    }
+};
+
+std::mutex g_live_mutex;
+std::set<const void *> g_live; // the writers that exist: a destroyed handle is refused, not followed
+
+uint32_t blocks_of(size_t n)
+{
+    return (uint32_t)((n + THREADS - 1) / THREADS);
+}
+
+} // namespace
+
+struct ochip_geotiff
+{
+    ochip_ctx *ctx = nullptr;
+    int kind = 0, sparse = 1;
+    int64_t w = 0, h = 0, tiles_x = 0, next_row = 0;
+    bool finished = false;
+    ochip::dev_blocks mem; // everything on the device, held until destroy
+    uint32_t *rows = nullptr;  // the tile row being filled: [512][w] pixels, zeros where nothing was fed
+    uint8_t *payload = nullptr; // [tiles_x][PAYLOAD]
+    uint16_t *tok = nullptr;    // [tiles_x][PAYLOAD]
+    uint32_t *nz = nullptr, *state = nullptr, *count = nullptr, *size = nullptr, *adler = nullptr; // [tiles_x (+ 1)]
+    uint32_t *counts = nullptr, *codes = nullptr;                                                  // [blocks][316]
+    uint32_t *header = nullptr, *header_bits = nullptr, *block_bits = nullptr, *seg_adler = nullptr;
+    unsigned long long *block_off = nullptr, *tile_off = nullptr;
+    void *scan_tmp = nullptr;
+    size_t scan_bytes = 0, slot_cap = 0;
+    struct out_slot
+    {
+        uint8_t *out = nullptr;
+        unsigned long long *info = nullptr;             // [2 tiles_x + 2]
+        void *pin_info = nullptr, *pin_bytes = nullptr; // page-locked blocks of the context's pool
+        size_t pin_bytes_cap = 0;
+        hipEvent_t done = nullptr; // recorded behind the pass's copies
+        bool pending = false;
+        int tiles = 0;
+        size_t guess = 0;
+    } slot[OUT_SLOTS];
+    uint64_t passes = 0, passes_read = 0;
+    double bytes_per_tile = 262144;
+    std::deque<std::vector<uint8_t>> ready; // the streams read from the slots, in tile order; empty: a tile left out
+};
+
+namespace
+{
+
+bool live(const ochip_geotiff *e)
+{
+    std::lock_guard<std::mutex> lock(g_live_mutex);
+    return e && g_live.count(e) != 0;
+}
+
+void release_host_side(ochip_geotiff *e)
+{
+    for (ochip_geotiff::out_slot &o : e->slot)
+    {
+        if (o.done)
+            (void)hipEventDestroy(o.done);
+        ochip_host_free(e->ctx, o.pin_info);
+        ochip_host_free(e->ctx, o.pin_bytes);
+    }
+}
+
+int launched(ochip_ctx *ctx, const char *what)
+{
+    return hipGetLastError() == hipSuccess ? OCHIP_OK : ochip_fail(ctx, OCHIP_EHIP, "%s launch failed", what);
+}
+
+// The oldest pending pass's tiles into the host queue: the one wait
+int drain_oldest(ochip_geotiff *e)
+{
+    ochip_ctx *ctx = e->ctx;
+    ochip_geotiff::out_slot &o = e->slot[e->passes_read % OUT_SLOTS];
+    if (e->passes_read == e->passes || !o.pending)
+        return OCHIP_OK;
+    o.pending = false, e->passes_read++;
+    OCHIP_HIP(ctx, hipEventSynchronize(o.done));
+    const unsigned long long *info = static_cast<const unsigned long long *>(o.pin_info);
+    const size_t tiles = (size_t)o.tiles, total = (size_t)info[tiles];
+    if (total > e->slot_cap)
+        return ochip_fail(ctx, OCHIP_EHIP, "ochip_geotiff: %zu bytes from %zu tiles, the slot holds %zu", total, tiles, e->slot_cap);
+    std::vector<uint8_t> rest;
+    const size_t have = total < o.guess ? total : o.guess;
+    if (total > have) // the guess was short: the rest directly
+    {
+        rest.resize(total - have);
+        OCHIP_HIP(ctx, hipMemcpy(rest.data(), o.out + have, total - have, hipMemcpyDeviceToHost));
+    }
+    const uint8_t *pin = static_cast<const uint8_t *>(o.pin_bytes);
+    for (size_t i = 0; i < tiles; i++)
+    {
+        const size_t at = (size_t)info[i], n = (size_t)info[tiles + 1 + i];
+        if (n > (size_t)STORED_BYTES || at + n > total)
+            return ochip_fail(ctx, OCHIP_EHIP, "ochip_geotiff: tile %zu of a pass has %zu bytes at %zu of %zu", i, n, at, total);
+        std::vector<uint8_t> t(n);
+        const size_t from_pin = at >= have ? 0 : (at + n <= have ? n : have - at);
+        if (from_pin)
+            std::memcpy(t.data(), pin + at, from_pin);
+        if (n > from_pin)
+            std::memcpy(t.data() + from_pin, rest.data() + (at + from_pin - have), n - from_pin);
+        e->ready.push_back(std::move(t));
+    }
+    if (tiles)
+        e->bytes_per_tile = (double)total / (double)tiles;
+    return OCHIP_OK;
+}
+
+int drain(ochip_geotiff *e)
+{
+    while (e->passes_read < e->passes)
+        OCHIP_TRY(drain_oldest(e));
+    return OCHIP_OK;
+}
+
+// One pass over the first `tiles` payloads: everything behind gt_payload, enqueued
+int encode_payloads(ochip_geotiff *e, int tiles)
+{
+    ochip_ctx *ctx = e->ctx;
+    if (tiles < 1 || tiles > e->tiles_x)
+        return ochip_fail(ctx, OCHIP_EINVAL, "ochip_geotiff: a pass of %d tiles, at most %lld", tiles, (long long)e->tiles_x);
+    hipStream_t st = ctx->stream;
+    const int blocks = tiles * SEGMENTS;
+    ochip_geotiff::out_slot &o = e->slot[e->passes % OUT_SLOTS];
+    while (o.pending) // the slot's last pass has not been read: OUT_SLOTS passes back
+        OCHIP_TRY(drain_oldest(e));
+    const size_t out_bytes = (size_t)tiles * TILE_SLOT; // <= slot_cap
+    OCHIP_HIP(ctx, hipMemsetAsync(o.out, 0, out_bytes, st));
+    OCHIP_HIP(ctx, hipMemsetAsync(e->block_bits, 0, ((size_t)blocks + 1) * 4, st));
+    hipLaunchKernelGGL(gt_parse, dim3((uint32_t)blocks), dim3(THREADS), 0, st, e->payload, e->nz, e->sparse, blocks, e->tok, e->counts,
+                       e->seg_adler);
+    OCHIP_TRY(launched(ctx, "gt_parse"));
+    hipLaunchKernelGGL(gt_codes, dim3((uint32_t)blocks), dim3(64), 0, st, e->counts, e->nz, e->sparse, blocks, e->codes, e->header,
+                       e->header_bits, e->block_bits);
+    OCHIP_TRY(launched(ctx, "gt_codes"));
+    size_t need = 0;
+    auto bits64 = rocprim::make_transform_iterator(e->block_bits, widen());
+    OCHIP_HIP(ctx, rocprim::exclusive_scan(nullptr, need, bits64, e->block_off, 0ull, (size_t)blocks + 1, rocprim::plus<unsigned long long>(), st));
+    if (need > e->scan_bytes)
+        return ochip_fail(ctx, OCHIP_EHIP, "ochip_geotiff: the scan of %d blocks wants %zu bytes, %zu are held", blocks + 1, need, e->scan_bytes);
+    OCHIP_HIP(ctx, rocprim::exclusive_scan(e->scan_tmp, need, bits64, e->block_off, 0ull, (size_t)blocks + 1, rocprim::plus<unsigned long long>(), st));
+    hipLaunchKernelGGL(gt_tile_sizes, dim3(blocks_of((size_t)tiles + 1)), dim3(THREADS), 0, st, e->block_off, e->seg_adler, e->nz, e->sparse,
+                       tiles, e->state, e->count, e->size, e->adler);
+    OCHIP_TRY(launched(ctx, "gt_tile_sizes"));
+    auto size64 = rocprim::make_transform_iterator(e->size, widen());
+    OCHIP_HIP(ctx, rocprim::exclusive_scan(nullptr, need, size64, e->tile_off, 0ull, (size_t)tiles + 1, rocprim::plus<unsigned long long>(), st));
+    if (need > e->scan_bytes)
+        return ochip_fail(ctx, OCHIP_EHIP, "ochip_geotiff: the scan of %d tiles wants %zu bytes, %zu are held", tiles + 1, need, e->scan_bytes);
+    OCHIP_HIP(ctx, rocprim::exclusive_scan(e->scan_tmp, need, size64, e->tile_off, 0ull, (size_t)tiles + 1, rocprim::plus<unsigned long long>(), st));
+    hipLaunchKernelGGL(gt_emit, dim3((uint32_t)blocks), dim3(THREADS), 0, st, e->payload, e->tok, e->codes, e->header, e->header_bits,
+                       e->block_off, e->tile_off, e->state, e->size, blocks, o.out, (unsigned long long)out_bytes);
+    OCHIP_TRY(launched(ctx, "gt_emit"));
+    hipLaunchKernelGGL(gt_stored, dim3(blocks_of((size_t)TILE_SLOT / 4), (uint32_t)tiles), dim3(THREADS), 0, st, e->payload, e->tile_off,
+                       e->state, e->adler, tiles, o.out, (unsigned long long)out_bytes);
+    OCHIP_TRY(launched(ctx, "gt_stored"));
+    hipLaunchKernelGGL(gt_finish, dim3(blocks_of((size_t)tiles + 1)), dim3(THREADS), 0, st, e->tile_off, e->state, e->count, e->adler, tiles,
+                       o.out, (unsigned long long)out_bytes, o.info);
+    OCHIP_TRY(launched(ctx, "gt_finish"));
+    // the offsets and counts, and the bytes the pass before suggests
+    size_t guess = (size_t)(e->bytes_per_tile * 1.25 * (double)tiles) + 4096;
+    guess = guess < out_bytes ? guess : out_bytes;
+    if (guess > o.pin_bytes_cap)
+    {
+        ochip_host_free(ctx, o.pin_bytes);
+        o.pin_bytes = nullptr, o.pin_bytes_cap = 0;
+        const size_t room = guess + guess / 4 < e->slot_cap ? guess + guess / 4 : e->slot_cap;
+        OCHIP_TRY(ochip_host_alloc(ctx, room, &o.pin_bytes));
+        o.pin_bytes_cap = room;
+    }
+    OCHIP_HIP(ctx, hipMemcpyAsync(o.pin_info, o.info, (2 * (size_t)tiles + 2) * 8, hipMemcpyDeviceToHost, st));
+    OCHIP_HIP(ctx, hipMemcpyAsync(o.pin_bytes, o.out, guess, hipMemcpyDeviceToHost, st));
+    OCHIP_HIP(ctx, hipEventRecord(o.done, st));
+    o.pending = true, o.tiles = tiles, o.guess = guess;
+    e->passes++;
+    return OCHIP_OK;
+}
+
+int refuse_feed(ochip_geotiff *e, int64_t row0, int64_t rows)
+{
+    ochip_ctx *ctx = e->ctx;
+    if (e->finished)
+        return ochip_fail(ctx, OCHIP_ESTATE, "ochip_geotiff_feed: rows %lld .. %lld after finish", (long long)row0, (long long)(row0 + rows));
+    if (rows < 0 || row0 != e->next_row)
+        return ochip_fail(ctx, OCHIP_EINVAL, "ochip_geotiff_feed: rows %lld .. %lld where row %lld is next (%s)", (long long)row0,
+                          (long long)(row0 + rows), (long long)e->next_row, row0 > e->next_row ? "a gap" : "an overlap");
+    if (row0 + rows > e->h)
+        return ochip_fail(ctx, OCHIP_EINVAL, "ochip_geotiff_feed: rows %lld .. %lld beyond the raster's %lld", (long long)row0,
+                          (long long)(row0 + rows), (long long)e->h);
+    return OCHIP_OK;
+}
+
+} // namespace
+
+extern "C"
+{
+
+int ochip_geotiff_create(ochip_ctx *ctx, int kind, int64_t width, int64_t height, int sparse, ochip_geotiff **out)
+{
+    if (!ctx)
+        return OCHIP_EINVAL;
+    if (!out)
+        return ochip_fail(ctx, OCHIP_EINVAL, "ochip_geotiff_create: out is NULL");
+    *out = nullptr;
+    if ((kind != OCHIP_GEOTIFF_RGBA8 && kind != OCHIP_GEOTIFF_FLOAT32) || width < 1 || height < 1 || width > OCHIP_GEOTIFF_MAX_SIDE ||
+        height > OCHIP_GEOTIFF_MAX_SIDE)
+        return ochip_fail(ctx, OCHIP_EINVAL, "ochip_geotiff_create: kind 0 (RGBA8) or 1 (float32) and sides of 1 .. %d, not kind %d, %lld x %lld",
+                          OCHIP_GEOTIFF_MAX_SIDE, kind, (long long)width, (long long)height);
+    OCHIP_HIP(ctx, hipSetDevice(ctx->device));
+    std::unique_ptr<ochip_geotiff> e(new ochip_geotiff);
+    e->ctx = ctx, e->kind = kind, e->sparse = sparse != 0 && kind == OCHIP_GEOTIFF_RGBA8, e->w = width, e->h = height;
+    e->tiles_x = (width + TILE - 1) / TILE;
+    e->mem.ctx = ctx, e->mem.what = "ochip_geotiff";
+    const size_t tiles = (size_t)e->tiles_x, blocks = tiles * SEGMENTS;
+    e->slot_cap = tiles * TILE_SLOT;
+    size_t a = 0, b = 0;
+    unsigned long long *none = nullptr;
+    OCHIP_HIP(ctx, rocprim::exclusive_scan(nullptr, a, rocprim::make_transform_iterator((uint32_t *)nullptr, widen()), none, 0ull, blocks + 1,
+                                           rocprim::plus<unsigned long long>(), (hipStream_t)ctx->stream));
+    OCHIP_HIP(ctx, rocprim::exclusive_scan(nullptr, b, rocprim::make_transform_iterator((uint32_t *)nullptr, widen()), none, 0ull, tiles + 1,
+                                           rocprim::plus<unsigned long long>(), (hipStream_t)ctx->stream));
+    e->scan_bytes = (a > b ? a : b) + 256;
+    int rc = e->mem.alloc(&e->rows, (size_t)TILE * (size_t)width);
+    if (rc == OCHIP_OK)
+        rc = e->mem.alloc(&e->payload, tiles * PAYLOAD);
+    if (rc == OCHIP_OK)
+        rc = e->mem.alloc(&e->tok, tiles * PAYLOAD);
+    if (rc == OCHIP_OK)
+        rc = e->mem.alloc(&e->nz, tiles);
+    if (rc == OCHIP_OK)
+        rc = e->mem.alloc(&e->state, tiles);
+    if (rc == OCHIP_OK)
+        rc = e->mem.alloc(&e->count, tiles);
+    if (rc == OCHIP_OK)
+        rc = e->mem.alloc(&e->size, tiles + 1);
+    if (rc == OCHIP_OK)
+        rc = e->mem.alloc(&e->adler, tiles);
+    if (rc == OCHIP_OK)
+        rc = e->mem.alloc(&e->counts, blocks * NUM_SYMS);
+    if (rc == OCHIP_OK)
+        rc = e->mem.alloc(&e->codes, blocks * NUM_SYMS);
+    if (rc == OCHIP_OK)
+        rc = e->mem.alloc(&e->header, blocks * HEADER_WORDS);
+    if (rc == OCHIP_OK)
+        rc = e->mem.alloc(&e->header_bits, blocks);
+    if (rc == OCHIP_OK)
+        rc = e->mem.alloc(&e->block_bits, blocks + 1);
+    if (rc == OCHIP_OK)
+        rc = e->mem.alloc(&e->seg_adler, blocks * 2);
+    if (rc == OCHIP_OK)
+        rc = e->mem.alloc(&e->block_off, blocks + 1);
+    if (rc == OCHIP_OK)
+        rc = e->mem.alloc(&e->tile_off, tiles + 1);
+    if (rc == OCHIP_OK)
+        rc = (e->scan_tmp = e->mem.get(e->scan_bytes)) ? OCHIP_OK : OCHIP_ENOMEM;
+    for (int k = 0; k < OUT_SLOTS && rc == OCHIP_OK; k++)
+    {
+        ochip_geotiff::out_slot &o = e->slot[k];
+        rc = e->mem.alloc(&o.out, e->slot_cap);
+        if (rc == OCHIP_OK)
+            rc = e->mem.alloc(&o.info, 2 * tiles + 2);
+        if (rc == OCHIP_OK)
+            rc = ochip_host_alloc(ctx, (2 * tiles + 2) * 8, &o.pin_info);
+        if (rc == OCHIP_OK && hipEventCreateWithFlags(&o.done, hipEventBlockingSync | hipEventDisableTiming) != hipSuccess)
+            rc = ochip_fail(ctx, OCHIP_EHIP, "ochip_geotiff_create: hipEventCreateWithFlags failed");
+    }
+    if (rc == OCHIP_OK && hipMemsetAsync(e->rows, 0, (size_t)TILE * (size_t)width * 4, ctx->stream) != hipSuccess)
+        rc = ochip_fail(ctx, OCHIP_EHIP, "ochip_geotiff_create: hipMemsetAsync failed");
+    if (rc != OCHIP_OK)
+    {
+        if (ctx->stream.opened())
+            (void)ochip_stream_wait(ctx, ctx->stream);
+        release_host_side(e.get());
+        e->mem.release();
+        return rc;
+    }
+    {
+        std::lock_guard<std::mutex> lock(g_live_mutex);
+        g_live.insert(e.get());
+    }
+    *out = e.release();
+    return OCHIP_OK;
+}
+
+int ochip_geotiff_feed(ochip_geotiff *e, int64_t row0, int64_t rows, const void *pixels, int on_device)
+{
+    if (!live(e))
+        return ochip_fail(nullptr, OCHIP_EINVAL, "ochip_geotiff_feed: not a live ochip_geotiff object");
+    ochip_ctx *ctx = e->ctx;
+    if (!pixels)
+        return ochip_fail(ctx, OCHIP_EINVAL, "ochip_geotiff_feed: the band is NULL");
+    OCHIP_TRY(refuse_feed(e, row0, rows));
+    OCHIP_HIP(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    const size_t row_bytes = (size_t)e->w * 4;
+    const uint8_t *band = static_cast<const uint8_t *>(pixels);
+    for (int64_t at = 0; at < rows;)
+    {
+        const int64_t y = row0 + at, in_tile = y % TILE;
+        int64_t n = TILE - in_tile;
+        n = n < rows - at ? n : rows - at;
+        OCHIP_HIP(ctx, hipMemcpyAsync(e->rows + (size_t)in_tile * (size_t)e->w, band + (size_t)at * row_bytes, (size_t)n * row_bytes,
+                                      on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st));
+        at += n, e->next_row = y + n;
+        if (e->next_row % TILE == 0 || e->next_row == e->h)
+        {
+            const int tiles = (int)e->tiles_x;
+            OCHIP_HIP(ctx, hipMemsetAsync(e->nz, 0, (size_t)tiles * 4, st));
+            const int vec = e->w % 4 == 0 && (uintptr_t)e->rows % 16 == 0;
+            hipLaunchKernelGGL(gt_payload, dim3((uint32_t)(TILE * 128 / THREADS), (uint32_t)tiles), dim3(THREADS), 0, st, e->rows, e->w,
+                               e->kind == OCHIP_GEOTIFF_FLOAT32 ? 1 : 0, vec, tiles, e->payload, e->nz);
+            OCHIP_TRY(launched(ctx, "gt_payload"));
+            OCHIP_TRY(encode_payloads(e, tiles));
+            if (e->next_row < e->h && e->h - e->next_row < TILE) // the last tile row is ragged: zeros below the raster
+                OCHIP_HIP(ctx, hipMemsetAsync(e->rows, 0, (size_t)TILE * row_bytes, st));
+        }
+    }
+    if (!on_device) // the caller's array may be reused on return
+        OCHIP_HIP(ctx, ochip_stream_wait(ctx, st));
+    return OCHIP_OK;
+}
+
+int ochip_geotiff_payloads(ochip_geotiff *e, const uint8_t *payloads, int64_t n)
+{
+    if (!live(e))
+        return ochip_fail(nullptr, OCHIP_EINVAL, "ochip_geotiff_payloads: not a live ochip_geotiff object");
+    ochip_ctx *ctx = e->ctx;
+    if (!payloads || n < 1 || n > e->tiles_x)
+        return ochip_fail(ctx, OCHIP_EINVAL, "ochip_geotiff_payloads: %lld payloads at %p, 1 .. %lld fit", (long long)n, (const void *)payloads,
+                          (long long)e->tiles_x);
+    OCHIP_HIP(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    OCHIP_HIP(ctx, hipMemcpyAsync(e->payload, payloads, (size_t)n * PAYLOAD, hipMemcpyHostToDevice, st));
+    OCHIP_HIP(ctx, hipMemsetAsync(e->nz, 1, (size_t)n * 4, st)); // every payload is encoded
+    OCHIP_TRY(encode_payloads(e, (int)n));
+    OCHIP_HIP(ctx, ochip_stream_wait(ctx, st)); // the caller's array may be reused on return
+    return OCHIP_OK;
+}
+
+int ochip_geotiff_collect(ochip_geotiff *e, uint8_t *buf, uint64_t cap, uint64_t *bytes, uint64_t *counts, uint64_t max_tiles, uint64_t *tiles)
+{
+    if (!live(e))
+        return ochip_fail(nullptr, OCHIP_EINVAL, "ochip_geotiff_collect: not a live ochip_geotiff object");
+    ochip_ctx *ctx = e->ctx;
+    if (!bytes || !tiles)
+        return ochip_fail(ctx, OCHIP_EINVAL, "ochip_geotiff_collect: no place for the counts");
+    OCHIP_TRY(drain(e));
+    uint64_t total = 0;
+    for (const auto &t : e->ready)
+        total += t.size();
+    *bytes = total, *tiles = e->ready.size();
+    if (!buf && !counts)
+        return OCHIP_OK;
+    if (!buf || !counts || cap < total || max_tiles < e->ready.size())
+        return ochip_fail(ctx, OCHIP_EINVAL, "ochip_geotiff_collect: room for %llu bytes and %llu tiles, %llu and %zu are ready",
+                          (unsigned long long)cap, (unsigned long long)max_tiles, (unsigned long long)total, e->ready.size());
+    size_t at = 0, k = 0;
+    for (const auto &t : e->ready)
+    {
+        if (!t.empty())
+            std::memcpy(buf + at, t.data(), t.size());
+        counts[k++] = t.size(), at += t.size();
+    }
+    e->ready.clear();
+    return OCHIP_OK;
+}
+
+int ochip_geotiff_finish(ochip_geotiff *e)
+{
+    if (!live(e))
+        return ochip_fail(nullptr, OCHIP_EINVAL, "ochip_geotiff_finish: not a live ochip_geotiff object");
+    if (e->finished)
+        return ochip_fail(e->ctx, OCHIP_ESTATE, "ochip_geotiff_finish: finished already");
+    if (e->next_row != e->h)
+        return ochip_fail(e->ctx, OCHIP_ESTATE, "ochip_geotiff_finish: rows %lld .. %lld were never fed", (long long)e->next_row, (long long)e->h);
+    OCHIP_TRY(drain(e));
+    e->finished = true;
+    return OCHIP_OK;
+}
+
+void ochip_geotiff_destroy(ochip_geotiff *e)
+{
+    {
+        std::lock_guard<std::mutex> lock(g_live_mutex);
+        if (!e || g_live.erase(e) == 0)
+            return;
+    }
+    if (e->ctx->stream.opened()) // nothing may still touch the blocks when they go back to the pools
+        (void)ochip_stream_wait(e->ctx, e->ctx->stream);
+    release_host_side(e);
+    e->mem.release();
+    delete e;
+}
+
+} // extern "C"

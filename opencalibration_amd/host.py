@@ -333,6 +333,15 @@ def load():
         L.och_jpeg_decoder_destroy.argtypes = [vp]
         L.och_jpeg_decoder_destroy.restype = None
         L.och_jpeg_decode_last_error.restype = C.c_char_p
+        L.och_geotiff_create.argtypes = [vp, C.c_int, i64, i64, C.c_int, C.POINTER(vp)]
+        L.och_geotiff_feed.argtypes = [vp, i64, i64, vp, C.c_int]
+        L.och_geotiff_payloads.argtypes = [vp, vp, i64]
+        L.och_geotiff_collect.argtypes = [vp, vp, C.c_uint64, C.POINTER(C.c_uint64), vp, C.c_uint64, C.POINTER(C.c_uint64)]
+        L.och_geotiff_finish.argtypes = [vp]
+        L.och_geotiff_destroy.argtypes = [vp]
+        L.och_geotiff_destroy.restype = None
+        L.och_geotiff_last_error.restype = C.c_char_p
+        L.och_deflate_code_lengths.argtypes = [vp, C.c_int, C.c_int, vp]
         L.och_tile_progress_create.argtypes = [vp, _f64p, C.c_int32, C.c_int32, C.POINTER(vp)]
         L.och_tile_progress_feed.argtypes = [vp, C.c_int, i64, i64, C.c_int, vp, vp]
         L.och_tile_progress_seek.argtypes = [vp, C.c_int, i64]
@@ -1451,7 +1460,8 @@ def color_balance_remove_gauge(xy, offsets):
 
 
 def ortho_mosaic(plan, graph, surfaces, images, mesh=None, config=None, color_balance=None, tile_rows=1, out=None,
-                 overviews=False, progress=None, progress_passes=(1, 2), jpeg=None, jpeg_quality=95):
+                 overviews=False, progress=None, progress_passes=(1, 2), jpeg=None, jpeg_quality=95, geotiff=None,
+                 dsm_geotiff=None, geo=None):
     """The blended full-resolution orthomosaic of `plan` (dsm_plan), band by band of tile_rows output tile rows: DSM ->
     layers (ortho_layers) -> blend (ortho_blend).  mesh (an OrthoMesh): every step on its device, images as CUDA tensors,
     into `out` (a (height, width, 4) uint8 CUDA tensor, made when None); None: the CPU route, numpy images, into a host
@@ -1472,26 +1482,36 @@ def ortho_mosaic(plan, graph, surfaces, images, mesh=None, config=None, color_ba
     jpeg: a path or a binary file object that receives the mosaic as a JPEG of quality jpeg_quality (JpegEncoder, the
     textured OBJ's texture): each band is fed right after its blend - with "solve" in the second sweep alone - and the bytes
     are written as they complete; the file is closed (a path) or flushed (an object) before the function returns and on an
-    exception.  None: nothing is allocated or launched for it."""
+    exception.  None: nothing is allocated or launched for it.
+    geotiff, dsm_geotiff: a path or a seekable binary file object each, the mosaic and the DSM as tiled DEFLATE GeoTIFFs
+    (GeoTiffWriter; the reference's orthomosaic.tif and dsm.tif): each band's RGBA and DSM are fed right behind its blend -
+    with "solve" in the second sweep alone - the overview levels are built for either (as overviews=True does) and become
+    the files' further IFDs, and the files are finished before the function returns and closed on an exception.  geo:
+    dict(min_x, max_y, gsd[, epsg]) for the georeferencing tags; its missing keys are the plan's.  Both None: nothing is
+    allocated or launched for them."""
     return _mosaic(plan, graph, surfaces, mesh, config, color_balance, tile_rows, out, images=images, overviews=overviews,
-                   progress=progress, progress_passes=progress_passes, jpeg=jpeg, jpeg_quality=jpeg_quality)
+                   progress=progress, progress_passes=progress_passes, jpeg=jpeg, jpeg_quality=jpeg_quality,
+                   geotiff=geotiff, dsm_geotiff=dsm_geotiff, geo=geo)
 
 
 def ortho_mosaic_streamed(plan, graph, surfaces, fetch, mesh, capacity, config=None, color_balance=None, tile_rows=1, out=None,
-                          overviews=False, progress=None, progress_passes=(1, 2), jpeg=None, jpeg_quality=95):
+                          overviews=False, progress=None, progress_passes=(1, 2), jpeg=None, jpeg_quality=95, geotiff=None,
+                          dsm_geotiff=None, geo=None):
     """ortho_mosaic on mesh's device without the source images resident: fetch(i) returns involved camera i's BGR image
     (ortho_layers_cameras' order) as a numpy array or a page-locked torch CPU tensor, and at most `capacity` images are on
     the device at a time (OrthoStream).  Band k + 1's ahead uploads are issued before band k renders, so that they run
     beside it when the images are page-locked.  color_balance as ortho_mosaic's; "solve" renders the layers twice, the
     second sweep starting from the images the first one left on the device.  Returns the (height, width, 4) RGBA tensor,
     with overviews=True (tensor, dict(rgba=[...], dsm=[...])) as ortho_mosaic does.  progress, progress_passes, jpeg,
-    jpeg_quality: as ortho_mosaic's."""
+    jpeg_quality, geotiff, dsm_geotiff, geo: as ortho_mosaic's."""
     return _mosaic(plan, graph, surfaces, mesh, config, color_balance, tile_rows, out, fetch=fetch, capacity=capacity,
-                   overviews=overviews, progress=progress, progress_passes=progress_passes, jpeg=jpeg, jpeg_quality=jpeg_quality)
+                   overviews=overviews, progress=progress, progress_passes=progress_passes, jpeg=jpeg, jpeg_quality=jpeg_quality,
+                   geotiff=geotiff, dsm_geotiff=dsm_geotiff, geo=geo)
 
 
 def _mosaic(plan, graph, surfaces, mesh, config, color_balance, tile_rows, out, images=None, fetch=None, capacity=None,
-            overviews=False, progress=None, progress_passes=(1, 2), jpeg=None, jpeg_quality=95):
+            overviews=False, progress=None, progress_passes=(1, 2), jpeg=None, jpeg_quality=95, geotiff=None, dsm_geotiff=None,
+            geo=None):
     """The band loop of ortho_mosaic (images) and ortho_mosaic_streamed (fetch, capacity): the two differ in where a band's
     layers come from, ortho_layers over the resident images or an OrthoStream's render behind the band's uploads."""
     cfg = {**LAYERS_CONFIG, **BLEND_CONFIG, **(config or {})}
@@ -1510,7 +1530,8 @@ def _mosaic(plan, graph, surfaces, mesh, config, color_balance, tile_rows, out, 
         out = torch.empty((h, w, 4), dtype=torch.uint8, device=dev) if out is None else out
     stream = OrthoStream(plan, graph, surfaces, capacity, mesh=mesh, tile_rows=tile_rows, config=lcfg) if fetch is not None else None
     builders = [OrthoOverviews(kind, w, h, ctx=ctx, on_device=mesh is not None)
-                for kind in (OVERVIEW_RGBA8, OVERVIEW_FLOAT32)] if overviews else []
+                for kind in (OVERVIEW_RGBA8, OVERVIEW_FLOAT32)] if overviews or geotiff is not None or dsm_geotiff is not None else []
+    tiffs = [None, None]  # the orthomosaic's and the DSM's GeoTiffWriter
     passes = {int(p) for p in progress_passes} if progress is not None else set()
     if passes - {TILE_PASS_LAYERS, TILE_PASS_BLEND}:
         raise ValueError("progress_passes names 1 (the layers) and 2 (the blend)")
@@ -1558,6 +1579,10 @@ def _mosaic(plan, graph, surfaces, mesh, config, color_balance, tile_rows, out, 
                 builders[1].feed(row0, dsm)
             if texture is not None:  # behind the blend on the context's stream as well
                 texture.feed(row0, out[row0:row0 + rows])
+            if tiffs[0] is not None:
+                tiffs[0].feed(row0, out[row0:row0 + rows])
+            if tiffs[1] is not None:
+                tiffs[1].feed(row0, dsm)
         if emit:  # this band is enqueued behind the bands before it: their updates are due
             deliver(tiles.pending() - before)
         return layers["correspondences"]
@@ -1565,6 +1590,10 @@ def _mosaic(plan, graph, surfaces, mesh, config, color_balance, tile_rows, out, 
     try:
         if jpeg is not None:
             texture = _JpegSink(jpeg, w, h, ctx, jpeg_quality, mesh is not None)
+        for i, (target, kind) in enumerate(((geotiff, OVERVIEW_RGBA8), (dsm_geotiff, OVERVIEW_FLOAT32))):
+            if target is not None:
+                tiffs[i] = GeoTiffWriter(target, kind, w, h, geo={**{k: plan[k] for k in ("min_x", "max_y", "gsd")}, **(geo or {})},
+                                         ctx=ctx, on_device=mesh is not None)
         bands = range(-(-h // band_rows))
         if color_balance == "solve":
             corr = [band(k, None, False, passes & {TILE_PASS_LAYERS}) for k in bands]
@@ -1581,10 +1610,19 @@ def _mosaic(plan, graph, surfaces, mesh, config, color_balance, tile_rows, out, 
         if texture is not None:
             texture.finish()
         if builders:
-            return out, dict(rgba=builders[0].finish(), dsm=builders[1].finish())
+            levels = dict(rgba=builders[0].finish(), dsm=builders[1].finish())
+            if tiffs[0] is not None:
+                tiffs[0].finish(levels["rgba"])
+            if tiffs[1] is not None:
+                tiffs[1].finish(levels["dsm"])
+            if overviews:
+                return out, levels
     finally:
         if texture is not None:
             texture.close()
+        for t in tiffs:
+            if t is not None:
+                t.close()
         if stream is not None:
             stream.close()
         for b in builders:
@@ -2141,6 +2179,290 @@ def ortho_overviews(raster, ctx=None):
         if h > 0:
             b.feed(0, raster)
         return b.finish()
+
+
+# ---- the orthomosaic and the DSM as tiled DEFLATE GeoTIFFs (include/oc_host.h) ----------------------------
+GEOTIFF_TILE, GEOTIFF_PAYLOAD, GEOTIFF_MAX_STREAM = 512, 1 << 20, 1048667
+GEOTIFF_BIGTIFF_ABOVE = 2_000_000_000  # uncompressed bytes of the full level: GDAL's BIGTIFF=IF_SAFER as remembered, unpinned
+
+
+def deflate_code_lengths(counts, limit):
+    """The length limiter of csrc/deflate_rules.hpp alone: code lengths (uint8, 0 for a count of 0) of at most `limit` bits for
+    up to 286 symbol counts."""
+    counts = np.ascontiguousarray(counts, np.uint32)
+    lens = np.zeros(max(len(counts), 1), np.uint8)
+    L = load()
+    if L.och_deflate_code_lengths(counts.ctypes.data, len(counts), int(limit), lens.ctypes.data) != 0:
+        raise capi.OchipError(L.och_geotiff_last_error().decode())
+    return lens[:len(counts)]
+
+
+class _TileEncoder:
+    """och_geotiff_*: a raster's bands, or predicted payloads, to the zlib streams of its 512 x 512 tiles"""
+
+    def __init__(self, kind, width, height, ctx, sparse):
+        self.L, self.ctx, self.h = load(), ctx, None
+        h = C.c_void_p()
+        if self.L.och_geotiff_create(ctx.h if ctx is not None else None, int(kind), int(width), int(height), int(bool(sparse)),
+                                     C.byref(h)) != 0:
+            raise capi.OchipError(self.error())
+        self.h = h
+
+    def error(self):
+        return self.L.och_geotiff_last_error().decode()
+
+    def close(self):
+        if getattr(self, "h", None):
+            if self.ctx is None or getattr(self.ctx, "h", None):  # as OrthoStream.close: the context may be gone
+                self.L.och_geotiff_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        self.close()
+
+    def feed(self, row0, rows, ptr, on_device):
+        if self.L.och_geotiff_feed(self.h, int(row0), int(rows), ptr, int(on_device)) != 0:
+            raise capi.OchipError(self.error())
+
+    def payloads(self, arr):
+        if self.L.och_geotiff_payloads(self.h, arr.ctypes.data, len(arr)) != 0:
+            raise capi.OchipError(self.error())
+
+    def finish(self):
+        if self.L.och_geotiff_finish(self.h) != 0:
+            raise capi.OchipError(self.error())
+
+    def collect(self):
+        """(bytes as a uint8 array, counts): the streams of the tiles complete so far, back to back in tile order.  The bytes
+        lie in a block this object reuses - a fresh one of a band's size costs more in page faults than the copy into it - so
+        they are valid until the next collect."""
+        nb, nt = C.c_uint64(0), C.c_uint64(0)
+        if self.L.och_geotiff_collect(self.h, None, 0, C.byref(nb), None, 0, C.byref(nt)) != 0:
+            raise capi.OchipError(self.error())
+        if getattr(self, "_buf", None) is None or len(self._buf) < nb.value:
+            self._buf = np.empty(max(nb.value + nb.value // 4, 1), np.uint8)
+        buf, counts = self._buf, np.zeros(max(nt.value, 1), np.uint64)
+        if self.L.och_geotiff_collect(self.h, buf.ctypes.data, nb.value, C.byref(nb), counts.ctypes.data, nt.value, C.byref(nt)) != 0:
+            raise capi.OchipError(self.error())
+        return buf[:nb.value], counts[:nt.value]
+
+
+def deflate_tiles(payloads, ctx=None):
+    """The zlib streams (a list of bytes) of (n, 1048576) uint8 predicted tile payloads by the rules of csrc/deflate_rules.hpp:
+    ctx None the CPU route, else on ctx's device - the same bytes."""
+    payloads = np.ascontiguousarray(payloads, np.uint8)
+    if payloads.ndim != 2 or payloads.shape[1] != GEOTIFF_PAYLOAD:
+        raise ValueError(f"payloads are (n, {GEOTIFF_PAYLOAD}) uint8")
+    n, step, out = len(payloads), 4, []
+    if n == 0:
+        return out
+    enc = _TileEncoder(OVERVIEW_RGBA8, GEOTIFF_TILE * min(n, step), 1, ctx, False)
+    try:
+        for at in range(0, n, step):
+            enc.payloads(payloads[at:at + step])
+            buf, counts = enc.collect()
+            ends = np.cumsum(counts)
+            out += [buf[int(e - c):int(e)].tobytes() for c, e in zip(counts, ends)]
+    finally:
+        enc.close()
+    return out
+
+
+class GeoTiffWriter:
+    """A tiled DEFLATE GeoTIFF of a width x height raster fed band by band: the reference's createGeoTIFF (kind
+    OVERVIEW_RGBA8: (rows, width, 4) uint8 bands whose four bytes go out as they stand - ortho_blend writes R, G, B, A
+    (csrc/ortho_blend.hpp, "Lab -> BGR8 -> RGBA") - with ExtraSamples 2) and createDSMGeoTIFF (OVERVIEW_FLOAT32: (rows, width)
+    float32, tag 42113 "nan"): 512 x 512 tiles, Compression 8, Predictor 2, every tile its own zlib stream by the rules of
+    csrc/deflate_rules.hpp.  target: a path or a seekable binary file object.  ctx None: the CPU route,
+    numpy bands.  ctx with on_device: CUDA tensors on ctx's device, fed on the context's stream - the caller has torch's work
+    on a band finished before feed, as ortho_blend does - and a feed never waits for the band it enqueues: it writes the
+    tiles the bands before completed.  ctx without on_device: numpy bands through the device.  The routes write the same
+    bytes.  geo: dict(min_x, max_y, gsd[, epsg]) for tags 33550, 33922 and 34735.  bigtiff: None chooses BigTIFF above
+    2 000 000 000 uncompressed bytes.  sparse: an all-zero RGBA tile gets offset 0 and count 0 and no bytes; DSM tiles are
+    always written.  feed(row0, band): bands ascend and are contiguous from row 0, of any row count.  finish(overviews): the
+    list of overview level arrays or tensors (OrthoOverviews) become further IFDs with NewSubfileType 1; the file is then
+    complete, flushed (an object) or closed (a path).  A gap, an overlap, a wrong kind or width, a feed after finish and a
+    finish before the last row raise OchipError naming the rows."""
+
+    def __init__(self, target, kind, width, height, geo=None, ctx=None, on_device=False, bigtiff=None, sparse=True):
+        self.enc = self.f = None
+        self.kind, self.width, self.height, self.ctx = int(kind), int(width), int(height), ctx
+        self.on_device, self.sparse = bool(on_device), bool(sparse)
+        if self.kind not in (OVERVIEW_RGBA8, OVERVIEW_FLOAT32):
+            raise capi.OchipError("a GeoTIFF's kind is OVERVIEW_RGBA8 or OVERVIEW_FLOAT32")
+        if self.on_device and ctx is None:
+            raise ValueError("bands on the device need the device route (ctx)")
+        self.geo = dict(geo) if geo is not None else None
+        self.big = self.width * self.height * 4 > GEOTIFF_BIGTIFF_ABOVE if bigtiff is None else bool(bigtiff)
+        self.own = isinstance(target, (str, bytes, os.PathLike))
+        if not self.own and not (hasattr(target, "write") and hasattr(target, "seekable") and target.seekable()):
+            raise capi.OchipError("a GeoTIFF's target is a path or a seekable binary file object: the first IFD's offset is "
+                                  "written last")
+        self.enc = _TileEncoder(self.kind, self.width, self.height, ctx, self.sparse)
+        self.f = open(target, "wb") if self.own else target
+        self.base = self.f.tell()
+        self.f.write(b"II+\0\x08\0\0\0" + bytes(8) if self.big else b"II*\0" + bytes(4))
+        self.at = 16 if self.big else 8      # the file's length so far
+        self.link = 8 if self.big else 4     # where the next IFD's offset goes
+        self.tiles = []                      # (offset, count) of the level being written
+        self.finished = False
+        self._keep = []
+
+    def close(self):
+        if self.enc is not None:
+            self.enc.close()
+            self.enc = None
+        if self.f is not None:
+            if self.own:
+                self.f.close()
+            else:
+                self.f.flush()
+            self.f = None
+        self._keep = []
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        self.close()
+
+    def _write(self, data):
+        """at an even offset; returns it"""
+        if self.at & 1:
+            self.f.write(b"\0")
+            self.at += 1
+        at = self.at
+        self.f.write(data)
+        self.at += len(data)
+        if not self.big and self.at >= 1 << 32:
+            raise capi.OchipError("the file outgrows a classic TIFF's 32-bit offsets: bigtiff=True")
+        return at
+
+    def _take(self, enc):
+        buf, counts = enc.collect()
+        at = 0
+        for c in counts:
+            c = int(c)
+            self.tiles.append((self._write(memoryview(buf[at:at + c])), c) if c else (0, 0))
+            at += c
+
+    def feed(self, row0, band):
+        if self.enc is None:
+            raise capi.OchipError("the writer is closed")
+        try:
+            kind, rows, w = _overview_kind(band.dtype, tuple(band.shape))
+        except ValueError:
+            kind, rows, w = -1, 0, 0
+        if kind != self.kind or w != self.width:
+            raise capi.OchipError(f"rows from {int(row0)}: a band of this writer is {self.width} pixels wide, kind {self.kind}")
+        self._take(self.enc)  # what the bands before completed: waits for them alone, not for this band
+        self._keep = []
+        if self.on_device:
+            shape = (rows, w, 4) if kind == OVERVIEW_RGBA8 else (rows, w)
+            ptr = _device_ptr(band, str(band.dtype), shape, "band", self.ctx.device)
+            self._keep.append(band)  # the copy may still read it: alive until the next feed, finish or close
+        else:
+            band = np.ascontiguousarray(band)
+            ptr = band.ctypes.data
+        if rows > 0:
+            self.enc.feed(row0, rows, ptr, self.on_device)
+
+    def _ifd(self, width, height, overview):
+        rgba, big = self.kind == OVERVIEW_RGBA8, self.big
+        n = 4 if rgba else 1
+        S, L, D, A, L8 = 3, 4, 12, 2, 16
+        offsets = np.array([t[0] for t in self.tiles], np.uint64)
+        tags = []
+        if overview:
+            tags.append((254, L, [1]))
+        tags += [(256, L, [width]), (257, L, [height]), (258, S, [8] * 4 if rgba else [32]), (259, S, [8]), (262, S, [2 if rgba else 1]),
+                 (277, S, [n]), (284, S, [1]), (317, S, [2]), (322, S, [GEOTIFF_TILE]), (323, S, [GEOTIFF_TILE]),
+                 (324, L8 if big else L, offsets), (325, L, [t[1] for t in self.tiles])]
+        if rgba:
+            tags.append((338, S, [2]))
+        tags.append((339, S, [1] * 4 if rgba else [3]))
+        if self.geo is not None and not overview:
+            g = self.geo
+            keys = [(1025, 0, 1, 1)]
+            if g.get("epsg") is not None:
+                keys = [(1024, 0, 1, 1), (1025, 0, 1, 1), (3072, 0, 1, int(g["epsg"]))]
+            tags.append((33550, D, [float(g["gsd"]), float(g["gsd"]), 0.0]))
+            tags.append((33922, D, [0.0, 0.0, 0.0, float(g["min_x"]), float(g["max_y"]), 0.0]))
+            tags.append((34735, S, [1, 1, 0, len(keys)] + [v for k in keys for v in k]))
+        if not rgba:
+            tags.append((42113, A, b"nan\0"))
+        dtypes = {S: "<u2", L: "<u4", D: "<f8", L8: "<u8"}
+        inline, entries = 8 if big else 4, []
+        for tag, typ, values in sorted(tags, key=lambda t: t[0]):
+            data = bytes(values) if typ == A else np.asarray(values).astype(dtypes[typ]).tobytes()
+            count = len(values)
+            field = data.ljust(inline, b"\0") if len(data) <= inline else \
+                np.array([self._write(data)], "<u8" if big else "<u4").tobytes()
+            entries.append(np.array([tag, typ], "<u2").tobytes() + np.array([count], "<u8" if big else "<u4").tobytes() + field)
+        head = np.array([len(entries)], "<u8" if big else "<u2").tobytes()
+        at = self._write(head + b"".join(entries) + bytes(inline))
+        self.f.seek(self.base + self.link)
+        self.f.write(np.array([at], "<u8" if big else "<u4").tobytes())
+        self.f.seek(self.base + self.at)
+        self.link = self.at - inline
+        self.tiles = []
+
+    def finish(self, overviews=None):
+        if self.enc is None or self.finished:
+            raise capi.OchipError("the writer is finished or closed")
+        levels = list(overviews) if overviews is not None else []
+        sizes = overview_levels(self.width, self.height) if levels else []
+        if len(levels) != len(sizes):
+            raise capi.OchipError(f"a {self.width} x {self.height} raster has {len(sizes)} overview levels, {len(levels)} came")
+        self.enc.finish()
+        self.finished = True
+        self._take(self.enc)
+        self._keep = []
+        self.enc.close()
+        self.enc = None
+        self._ifd(self.width, self.height, False)
+        for k, (level, (rows, cols)) in enumerate(zip(levels, sizes)):
+            kind, lr, lc = _overview_kind(level.dtype, tuple(level.shape))
+            if kind != self.kind or (lr, lc) != (rows, cols):
+                raise capi.OchipError(f"overview level {k + 1} is {cols} x {rows} of kind {self.kind}")
+            on_device = not isinstance(level, np.ndarray)
+            if on_device and self.ctx is None:
+                raise capi.OchipError("an overview level on the device needs the device route (ctx)")
+            enc = _TileEncoder(self.kind, cols, rows, self.ctx, self.sparse)
+            try:
+                if on_device:
+                    shape = (rows, cols, 4) if kind == OVERVIEW_RGBA8 else (rows, cols)
+                    enc.feed(0, rows, _device_ptr(level, str(level.dtype), shape, f"level {k + 1}", self.ctx.device), True)
+                else:
+                    level = np.ascontiguousarray(level)
+                    enc.feed(0, rows, level.ctypes.data, False)
+                enc.finish()
+                self._take(enc)
+            finally:
+                enc.close()
+            self._ifd(cols, rows, True)
+        self.close()
+
+
+def save_geotiff(target, raster, geo=None, ctx=None, overviews=True, bigtiff=None, sparse=True):
+    """A whole raster - (height, width, 4) uint8 RGBA or (height, width) float32 with NaN as no data; a numpy array (ctx None:
+    the CPU route, else through ctx's device) or a CUDA tensor on ctx's device - as a GeoTiffWriter's file, with its averaged
+    overview levels (ortho_overviews, on the same route) when overviews."""
+    on_device = not isinstance(raster, np.ndarray)
+    kind, h, w = _overview_kind(raster.dtype, tuple(raster.shape))
+    if on_device:
+        if ctx is None:
+            raise ValueError("a device raster needs the device route (ctx)")
+        import torch
+
+        torch.cuda.current_stream(raster.device).synchronize()  # the kernels run on the context's own stream
+    levels = ortho_overviews(raster, ctx=ctx) if overviews else None
+    with GeoTiffWriter(target, kind, w, h, geo=geo, ctx=ctx, on_device=on_device, bigtiff=bigtiff, sparse=sparse) as wr:
+        wr.feed(0, raster)
+        wr.finish(levels)
 
 
 def blend_chamfer(boundary):
