@@ -744,6 +744,48 @@ extern "C"
     const char *och_geotiff_last_error(void);
     int och_deflate_code_lengths(const uint32_t *counts, int n, int limit, uint8_t *lens);
 
+    /* ---- the PNG codec (opencalibration_amd/csrc/host/png.cpp, csrc/png_rules.hpp, csrc/host/png_decode.hpp; DESIGN.md
+     *      section 4.20) ----
+     * The encoder of include/ochip.h (ochip_png_encoder_*) over both routes.  ctx != NULL: the device route, as described
+     * there.  ctx == NULL: the same rules in loops (OpenMP over the rows and segments of all images) and the same bytes; it
+     * never changes route by size.  och_png_bound: the most bytes a file (or its base64) of that shape has, 0 for a shape
+     * that is refused.  och_png_filter: the filtered payload alone, height (1 + width channels) bytes.  The message of a
+     * refusal is in och_png_last_error.
+     * The decoder is host code only.  och_png_info reads the signature and IHDR; och_png_decode gives the picture in the
+     * file's channels (1, 2, 3 or 4), *pixels allocated here and released with och_png_free.  status: OCHIP_PNG_OK,
+     * OCHIP_PNG_UNSUPPORTED (palette, 16 bits, fewer than 8 bits, Adam7: the caller falls back) or OCHIP_PNG_CORRUPT
+     * (anything that does not parse or check: a chunk CRC, the zlib stream, its Adler-32, bytes behind it, a stream that
+     * gives fewer or more bytes than IHDR says, a filter type above 4); *pixels is NULL unless the status is OK.  Both
+     * return OCHIP_OK whatever the status, OCHIP_EINVAL only for a NULL output argument.
+     * och_graph_encode_thumbnails: every node that has thumbnail pixels gets its thumbnail text, the base64 of a colour
+     * type 2 file of the three bytes as stored, all nodes in one batch; returns their number, -1 + och_last_error(g).
+     * och_graph_decode_thumbnails: every node with thumbnail text gets thumbnail pixels of three channels (gray replicated,
+     * alpha dropped); statuses (or NULL): per node index -1 (no text) or the status, a refused node is left as it was;
+     * returns the number decoded.  och_graph_get_thumbnail: the decoded thumbnail's size (0 x 0: none) and, with rgb, its
+     * rows x cols x 3 bytes. */
+#define OCHIP_PNG_OK 0
+#define OCHIP_PNG_UNSUPPORTED 1
+#define OCHIP_PNG_CORRUPT 2
+    typedef struct och_png_file_info
+    {
+        uint32_t width, height;
+        int32_t bit_depth, color_type, interlace, channels, status;
+    } och_png_file_info;
+    typedef struct och_png_encoder och_png_encoder;
+    int och_png_encoder_create(ochip_ctx *ctx, och_png_encoder **out);
+    int och_png_encoder_encode(och_png_encoder *e, int64_t n, const ochip_png_image *images, int on_device, int base64, uint8_t *out,
+                               uint64_t out_cap, uint64_t *offsets /* [n + 1] */);
+    void och_png_encoder_destroy(och_png_encoder *e);
+    const char *och_png_last_error(void);
+    uint64_t och_png_bound(int64_t width, int64_t height, int64_t channels, int base64);
+    int och_png_filter(const ochip_png_image *image, uint8_t *payload, uint64_t cap);
+    int och_png_info(const uint8_t *data, uint64_t size, och_png_file_info *out);
+    int och_png_decode(const uint8_t *data, uint64_t size, och_png_file_info *info, uint8_t **pixels);
+    void och_png_free(uint8_t *pixels);
+    int och_graph_get_thumbnail(och_graph *g, size_t node_index, size_t *rows, size_t *cols, uint8_t *rgb /* or NULL */);
+    int och_graph_encode_thumbnails(och_graph *g, ochip_ctx *ctx);
+    int och_graph_decode_thumbnails(och_graph *g, int32_t *statuses /* [nodes] or NULL */);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1129,6 +1129,31 @@ extern "C"
     int ochip_geotiff_finish(ochip_geotiff *e);
     void ochip_geotiff_destroy(ochip_geotiff *e);
 
+    /* ---- PNG files of thumbnails and previews (opencalibration_amd/csrc/png.hip, the rules in csrc/png_rules.hpp; the
+     *      reference's cv::imencode(".png") of a node's thumbnail, src/io/serialize_MeasurementGraph.cpp:260-267,
+     *      src/ortho/thumbnail_encode.hpp, and thumb.png) ----
+     * A batch of n images (at most 65 535) of mixed sizes to n PNG files per call: 8 bits per sample, 1, 3 or 4 channels
+     * (colour types 0, 2, 6), sides of 1 .. 65 535, non-interlaced, one IDAT.  pixels: [height][width][channels] bytes
+     * without padding; swap_rb exchanges channels 0 and 2 (B G R (A) arrays) before anything else.  on_device: every
+     * pixels is a device pointer on the context's device whose producer has finished; otherwise host memory.  Every row
+     * takes the filter with the smallest sum of min(v, 256 - v), every 16 384 payload bytes one deflate block, and an image
+     * whose stream would not shrink is stored: file i has at most 2 + F + 5 ceil(F / 65535) + 4 + 57 bytes, F = height (1 +
+     * width channels).  out (host, out_cap bytes): the files back to back, file i at offsets[i] .. offsets[i + 1]; with
+     * base64 their RFC 4648 text instead (padded, no line breaks).  The call returns when out is written.
+     * OCHIP_EINVAL and a message, before anything is launched: a handle that create did not return or destroy has taken
+     * (the message is ochip_last_error(NULL)'s), NULL arrays, n out of range, a size or channel count out of range or a
+     * payload from 2^31 bytes on (one refused image refuses the call), out_cap below the sum of the files' bounds. */
+    typedef struct ochip_png_image
+    {
+        const void *pixels;
+        int32_t width, height, channels, swap_rb;
+    } ochip_png_image;
+    typedef struct ochip_png_encoder ochip_png_encoder;
+    int ochip_png_encoder_create(ochip_ctx *ctx, ochip_png_encoder **out);
+    int ochip_png_encoder_encode(ochip_png_encoder *e, int64_t n, const ochip_png_image *images, int on_device, int base64,
+                                 uint8_t *out, uint64_t out_cap, uint64_t *offsets /* [n + 1] */);
+    void ochip_png_encoder_destroy(ochip_png_encoder *e);
+
 #ifdef __cplusplus
 }
 #endif

@@ -58,9 +58,16 @@ EXPORTS = [
     "ochip_jpeg_decoder_create", "ochip_jpeg_decoder_decode", "ochip_jpeg_decoder_destroy",
     "ochip_geotiff_create", "ochip_geotiff_feed", "ochip_geotiff_payloads", "ochip_geotiff_collect", "ochip_geotiff_finish",
     "ochip_geotiff_destroy",
+    "ochip_png_encoder_create", "ochip_png_encoder_encode", "ochip_png_encoder_destroy",
 ]
 
 _lib = None
+
+
+class PngImage(C.Structure):
+    """include/ochip.h: ochip_png_image"""
+    _fields_ = [("pixels", C.c_void_p), ("width", C.c_int32), ("height", C.c_int32), ("channels", C.c_int32),
+                ("swap_rb", C.c_int32)]
 
 
 class RelaxDesc(C.Structure):
@@ -321,6 +328,10 @@ def load():
         L.ochip_geotiff_finish.argtypes = [vp]
         L.ochip_geotiff_destroy.argtypes = [vp]
         L.ochip_geotiff_destroy.restype = None
+        L.ochip_png_encoder_create.argtypes = [vp, C.POINTER(vp)]
+        L.ochip_png_encoder_encode.argtypes = [vp, C.c_int64, vp, i32, i32, vp, u64, vp]
+        L.ochip_png_encoder_destroy.argtypes = [vp]
+        L.ochip_png_encoder_destroy.restype = None
         _lib = L
     return _lib
 

@@ -342,6 +342,21 @@ def load():
         L.och_geotiff_destroy.restype = None
         L.och_geotiff_last_error.restype = C.c_char_p
         L.och_deflate_code_lengths.argtypes = [vp, C.c_int, C.c_int, vp]
+        L.och_png_encoder_create.argtypes = [vp, C.POINTER(vp)]
+        L.och_png_encoder_encode.argtypes = [vp, i64, vp, C.c_int, C.c_int, vp, C.c_uint64, vp]
+        L.och_png_encoder_destroy.argtypes = [vp]
+        L.och_png_encoder_destroy.restype = None
+        L.och_png_last_error.restype = C.c_char_p
+        L.och_png_bound.argtypes = [i64, i64, i64, C.c_int]
+        L.och_png_bound.restype = C.c_uint64
+        L.och_png_filter.argtypes = [vp, vp, C.c_uint64]
+        L.och_png_info.argtypes = [vp, C.c_uint64, vp]
+        L.och_png_decode.argtypes = [vp, C.c_uint64, vp, C.POINTER(vp)]
+        L.och_png_free.argtypes = [vp]
+        L.och_png_free.restype = None
+        L.och_graph_encode_thumbnails.argtypes = [vp, vp]
+        L.och_graph_get_thumbnail.argtypes = [vp, sz, C.POINTER(sz), C.POINTER(sz), vp]
+        L.och_graph_decode_thumbnails.argtypes = [vp, vp]
         L.och_tile_progress_create.argtypes = [vp, _f64p, C.c_int32, C.c_int32, C.POINTER(vp)]
         L.och_tile_progress_feed.argtypes = [vp, C.c_int, i64, i64, C.c_int, vp, vp]
         L.och_tile_progress_seek.argtypes = [vp, C.c_int, i64]
@@ -609,23 +624,30 @@ def validate_checkpoint(path):
     return bool(load().och_checkpoint_validate(str(path).encode()))
 
 
-def save_checkpoint(path, graph, surfaces=(), state="INITIAL_PROCESSING", state_run_count=0, origin=(0.0, 0.0)):
-    """saveCheckpoint (src/io/checkpoint.cpp:155-231): metadata.json, graph.json, surface_<i>.ply, pointcloud_<i>_<j>.xyz."""
+def save_checkpoint(path, graph, surfaces=(), state="INITIAL_PROCESSING", state_run_count=0, origin=(0.0, 0.0),
+                    encode_thumbnails=False, ctx=None):
+    """saveCheckpoint (src/io/checkpoint.cpp:155-231): metadata.json, graph.json, surface_<i>.ply, pointcloud_<i>_<j>.xyz.
+    encode_thumbnails: the nodes' decoded thumbnails go into graph.json as base64 PNGs first (Graph.encode_thumbnails(ctx))."""
     L = load()
+    if encode_thumbnails:
+        graph.encode_thumbnails(ctx)
     arr = (C.c_void_p * max(len(surfaces), 1))(*[s.h for s in surfaces])
     info = np.array([state_run_count, origin[0], origin[1], 0.0])
     if L.och_checkpoint_save(str(path).encode(), graph.h, arr, len(surfaces), state.encode(), info) != 0:
         raise IOError(L.och_last_error(graph.h).decode())
 
 
-def load_checkpoint(path):
-    """loadCheckpoint (src/io/checkpoint.cpp:233-316).  Returns (Graph, [Surface], info dict)."""
+def load_checkpoint(path, decode_thumbnails=False):
+    """loadCheckpoint (src/io/checkpoint.cpp:233-316).  Returns (Graph, [Surface], info dict).  decode_thumbnails: the
+    nodes' base64 PNG thumbnails are decoded for the preview (Graph.decode_thumbnails; a refused one leaves its node bare)."""
     L = load()
     g = Graph()
     cp = L.och_checkpoint_load(str(path).encode(), g.h)
     if not cp:
         raise IOError(L.och_last_error(g.h).decode())
     g._refresh_ids()
+    if decode_thumbnails:
+        g.decode_thumbnails()
     try:
         surfaces = []
         for i in range(L.och_checkpoint_num_surfaces(cp)):
@@ -1461,7 +1483,7 @@ def color_balance_remove_gauge(xy, offsets):
 
 def ortho_mosaic(plan, graph, surfaces, images, mesh=None, config=None, color_balance=None, tile_rows=1, out=None,
                  overviews=False, progress=None, progress_passes=(1, 2), jpeg=None, jpeg_quality=95, geotiff=None,
-                 dsm_geotiff=None, geo=None):
+                 dsm_geotiff=None, geo=None, progress_png=False):
     """The blended full-resolution orthomosaic of `plan` (dsm_plan), band by band of tile_rows output tile rows: DSM ->
     layers (ortho_layers) -> blend (ortho_blend).  mesh (an OrthoMesh): every step on its device, images as CUDA tensors,
     into `out` (a (height, width, 4) uint8 CUDA tensor, made when None); None: the CPU route, numpy images, into a host
@@ -1478,7 +1500,9 @@ def ortho_mosaic(plan, graph, surfaces, images, mesh=None, config=None, color_ba
     With "solve" the first sweep emits pass 1 and the second pass 2, otherwise the single sweep emits a band's pass-1 tiles
     and then its pass-2 tiles.  Band k's updates are collected after band k + 1 has been enqueued, so the device never
     waits for the callback; the rest are flushed before the function returns.  An exception from the callback propagates
-    after the stream and the builders are closed.  None: nothing is allocated or launched for it.
+    after the stream and the builders are closed.  None: nothing is allocated or launched for it.  progress_png: every
+    update also carries png_base64, the reference's TileUpdate text (TileProgress.collect(png=True)), a band's tiles encoded
+    as one batch on the mosaic's route; False: nothing is allocated or launched for it.
     jpeg: a path or a binary file object that receives the mosaic as a JPEG of quality jpeg_quality (JpegEncoder, the
     textured OBJ's texture): each band is fed right after its blend - with "solve" in the second sweep alone - and the bytes
     are written as they complete; the file is closed (a path) or flushed (an object) before the function returns and on an
@@ -1491,27 +1515,27 @@ def ortho_mosaic(plan, graph, surfaces, images, mesh=None, config=None, color_ba
     allocated or launched for them."""
     return _mosaic(plan, graph, surfaces, mesh, config, color_balance, tile_rows, out, images=images, overviews=overviews,
                    progress=progress, progress_passes=progress_passes, jpeg=jpeg, jpeg_quality=jpeg_quality,
-                   geotiff=geotiff, dsm_geotiff=dsm_geotiff, geo=geo)
+                   geotiff=geotiff, dsm_geotiff=dsm_geotiff, geo=geo, progress_png=progress_png)
 
 
 def ortho_mosaic_streamed(plan, graph, surfaces, fetch, mesh, capacity, config=None, color_balance=None, tile_rows=1, out=None,
                           overviews=False, progress=None, progress_passes=(1, 2), jpeg=None, jpeg_quality=95, geotiff=None,
-                          dsm_geotiff=None, geo=None):
+                          dsm_geotiff=None, geo=None, progress_png=False):
     """ortho_mosaic on mesh's device without the source images resident: fetch(i) returns involved camera i's BGR image
     (ortho_layers_cameras' order) as a numpy array or a page-locked torch CPU tensor, and at most `capacity` images are on
     the device at a time (OrthoStream).  Band k + 1's ahead uploads are issued before band k renders, so that they run
     beside it when the images are page-locked.  color_balance as ortho_mosaic's; "solve" renders the layers twice, the
     second sweep starting from the images the first one left on the device.  Returns the (height, width, 4) RGBA tensor,
     with overviews=True (tensor, dict(rgba=[...], dsm=[...])) as ortho_mosaic does.  progress, progress_passes, jpeg,
-    jpeg_quality, geotiff, dsm_geotiff, geo: as ortho_mosaic's."""
+    jpeg_quality, geotiff, dsm_geotiff, geo, progress_png: as ortho_mosaic's."""
     return _mosaic(plan, graph, surfaces, mesh, config, color_balance, tile_rows, out, fetch=fetch, capacity=capacity,
                    overviews=overviews, progress=progress, progress_passes=progress_passes, jpeg=jpeg, jpeg_quality=jpeg_quality,
-                   geotiff=geotiff, dsm_geotiff=dsm_geotiff, geo=geo)
+                   geotiff=geotiff, dsm_geotiff=dsm_geotiff, geo=geo, progress_png=progress_png)
 
 
 def _mosaic(plan, graph, surfaces, mesh, config, color_balance, tile_rows, out, images=None, fetch=None, capacity=None,
             overviews=False, progress=None, progress_passes=(1, 2), jpeg=None, jpeg_quality=95, geotiff=None, dsm_geotiff=None,
-            geo=None):
+            geo=None, progress_png=False):
     """The band loop of ortho_mosaic (images) and ortho_mosaic_streamed (fetch, capacity): the two differ in where a band's
     layers come from, ortho_layers over the resident images or an OrthoStream's render behind the band's uploads."""
     cfg = {**LAYERS_CONFIG, **BLEND_CONFIG, **(config or {})}
@@ -1541,7 +1565,7 @@ def _mosaic(plan, graph, surfaces, mesh, config, color_balance, tile_rows, out, 
     def deliver(keep):
         """the fed bands' updates to the callback, oldest first, until `keep` bands are pending"""
         while tiles.pending() > keep:
-            for update in tiles.collect():
+            for update in tiles.collect(png=bool(progress_png)):
                 progress(update)
 
     def band(k, balance, blend, emit=frozenset()):
@@ -1711,6 +1735,7 @@ class TileProgress:
         self.num_layers = int(LAYERS_CONFIG["num_layers"] if num_layers is None else num_layers)
         self.h = None
         self._keep = []
+        self._png = None  # the PngEncoder of collect(png=True), made by the first such call
         h = C.c_void_p()
         if self.L.och_tile_progress_create(ctx.h if ctx is not None else None, _plan_array(plan), self.tile_size, self.num_layers,
                                            C.byref(h)) != 0:
@@ -1726,6 +1751,9 @@ class TileProgress:
                 self.L.och_tile_progress_destroy(self.h)
             self.h = None
             self._keep = []
+        if getattr(self, "_png", None) is not None:
+            self._png.close()
+            self._png = None
 
     def __enter__(self):
         return self
@@ -1752,7 +1780,9 @@ class TileProgress:
     def pending(self):
         return int(self.L.och_tile_progress_pending(self.h))
 
-    def collect(self, raw=False):
+    def collect(self, raw=False, png=False):
+        """png: every update also has png_base64, the thumbnail as the base64 of a PNG file (B G R A in, R G B A in the
+        file), the band's tiles encoded as one batch on the object's route"""
         n = C.c_uint64(0)
         if self.L.och_tile_progress_collect(self.h, None, None, 0, C.byref(n)) != 0:
             raise capi.OchipError(self._error())
@@ -1769,6 +1799,11 @@ class TileProgress:
             u = {k: (float(r[k]) if r.dtype[k] == np.float64 else int(r[k])) for k in TILE_UPDATE_DTYPE.names}
             u["thumbnail"] = slot[:u["thumb_w"] * u["thumb_h"]].reshape(u["thumb_h"], u["thumb_w"], 4).copy()
             updates.append(u)
+        if png and updates:
+            if self._png is None:
+                self._png = PngEncoder(self.ctx)
+            for u, text in zip(updates, self._png.encode([u["thumbnail"] for u in updates], bgr=True, base64=True)):
+                u["png_base64"] = text
         return updates
 
 
@@ -2465,6 +2500,177 @@ def save_geotiff(target, raster, geo=None, ctx=None, overviews=True, bigtiff=Non
         wr.finish(levels)
 
 
+# ---- the PNG codec (include/oc_host.h) ---------------------------------------------------------------------
+PNG_OK, PNG_UNSUPPORTED, PNG_CORRUPT = 0, 1, 2
+PNG_MAX_BATCH = 65535
+
+
+class PngFileInfo(C.Structure):
+    """include/oc_host.h: och_png_file_info"""
+    _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("bit_depth", C.c_int32), ("color_type", C.c_int32),
+                ("interlace", C.c_int32), ("channels", C.c_int32), ("status", C.c_int32)]
+
+
+class PngError(ValueError):
+    """A PNG the decoder does not give a picture for; status is PNG_UNSUPPORTED (the caller falls back) or PNG_CORRUPT"""
+
+    def __init__(self, status, text):
+        super().__init__(text)
+        self.status = status
+
+
+def _png_image(raster, bgr, device):
+    """(PngImage, what keeps its pixels alive, on_device) of a (h, w), (h, w, 1), (h, w, 3) or (h, w, 4) uint8 array or CUDA
+    tensor; refused before any work"""
+    on_device = not isinstance(raster, np.ndarray)
+    if on_device:
+        import torch
+
+        if not isinstance(raster, torch.Tensor) or not raster.is_cuda or raster.dtype != torch.uint8:
+            raise ValueError("an image is a uint8 numpy array or a uint8 CUDA tensor")
+        if device is None or raster.device.index != device:
+            raise ValueError("a CUDA tensor needs the context of its device")
+        keep = raster.contiguous()
+        ptr = keep.data_ptr()
+    else:
+        if raster.dtype != np.uint8:
+            raise ValueError(f"an image is uint8, not {raster.dtype}")
+        keep = np.ascontiguousarray(raster)
+        ptr = keep.ctypes.data
+    shape = tuple(int(v) for v in keep.shape)
+    if len(shape) == 2:
+        shape = shape + (1,)
+    if len(shape) != 3 or shape[2] not in (1, 3, 4) or not 1 <= shape[0] <= 65535 or not 1 <= shape[1] <= 65535:
+        raise ValueError(f"an image is (h, w), (h, w, 1), (h, w, 3) or (h, w, 4) with sides of 1 .. 65535, not {tuple(raster.shape)}")
+    return capi.PngImage(ptr, shape[1], shape[0], shape[2], int(bool(bgr))), keep, on_device
+
+
+class PngEncoder:
+    """PNG files of batches of images (och_png_encoder_*; the rules: DESIGN.md §4.20).  ctx None: the CPU route; ctx: the
+    device route, numpy arrays through the device or CUDA tensors on ctx's device (torch's work on them finished).  Both
+    give the same bytes.  encode(images, bgr=False, base64=False): a list of uint8 (h, w), (h, w, 3) or (h, w, 4) images of
+    any sizes, at most 65 535 - all numpy or all CUDA - to a list of bytes, or of str with base64; bgr: the arrays are
+    B G R (A), the files R G B (A)."""
+
+    def __init__(self, ctx=None):
+        self.L, self.ctx, self.h = load(), ctx, None
+        h = C.c_void_p()
+        if self.L.och_png_encoder_create(ctx.h if ctx is not None else None, C.byref(h)) != 0:
+            raise capi.OchipError(self._error())
+        self.h = h
+
+    def _error(self):
+        return self.L.och_png_last_error().decode()
+
+    def close(self):
+        if getattr(self, "h", None):
+            if self.ctx is None or getattr(self.ctx, "h", None):
+                self.L.och_png_encoder_destroy(self.h)
+            self.h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        self.close()
+
+    def encode(self, images, bgr=False, base64=False, cap=None):
+        images = list(images)
+        if len(images) > PNG_MAX_BATCH:
+            raise ValueError(f"a batch of {len(images)} images, at most {PNG_MAX_BATCH} are taken")
+        device = None if self.ctx is None else self.ctx.device
+        recs = [_png_image(m, bgr, device) for m in images]
+        if not recs:
+            return []
+        if len({r[2] for r in recs}) != 1:
+            raise ValueError("a batch is all numpy arrays or all CUDA tensors")
+        on_device = recs[0][2]
+        if on_device:
+            import torch
+
+            torch.cuda.current_stream(recs[0][1].device).synchronize()  # the kernels run on the context's own stream
+        arr = (capi.PngImage * len(recs))(*[r[0] for r in recs])
+        need = 0
+        for r in recs:
+            bound = int(self.L.och_png_bound(r[0].width, r[0].height, r[0].channels, int(bool(base64))))
+            if bound == 0:
+                raise ValueError(f"an image of {r[0].width} x {r[0].height} x {r[0].channels} has a payload of 2^31 bytes or more")
+            need += bound
+        out = np.empty(max(need if cap is None else int(cap), 1), np.uint8)
+        offsets = np.zeros(len(recs) + 1, np.uint64)
+        if self.L.och_png_encoder_encode(self.h, len(recs), arr, int(on_device), int(bool(base64)), out.ctypes.data,
+                                         out.size if cap is None else int(cap), offsets.ctypes.data) != 0:
+            raise capi.OchipError(self._error())
+        files = [out[int(offsets[i]):int(offsets[i + 1])].tobytes() for i in range(len(recs))]
+        return [f.decode("ascii") for f in files] if base64 else files
+
+
+def encode_png(raster, ctx=None, bgr=False):
+    """The PNG file of one image (PngEncoder in one call)"""
+    with PngEncoder(ctx) as e:
+        return e.encode([raster], bgr=bgr)[0]
+
+
+def save_png(target, raster, ctx=None, bgr=False):
+    """encode_png into a path or a binary file object; the runner's thumb.png is save_png(path,
+    orthomosaic_thumbnail(...)["rgba"]) (DESIGN.md §4.20 on the channel order)"""
+    data = encode_png(raster, ctx=ctx, bgr=bgr)
+    if hasattr(target, "write"):
+        target.write(data)
+    else:
+        with open(target, "wb") as f:
+            f.write(data)
+    return len(data)
+
+
+def png_filter(raster, bgr=False):
+    """The filtered payload of an image, h rows of the filter type and w * c bytes: what the file's stream inflates to"""
+    rec, keep, on_device = _png_image(raster, bgr, None)
+    if on_device:
+        raise ValueError("png_filter takes a numpy array")
+    out = np.empty(rec.height * (1 + rec.width * rec.channels), np.uint8)
+    L = load()
+    if L.och_png_filter(C.byref(rec), out.ctypes.data, out.size) != 0:
+        raise capi.OchipError(L.och_png_last_error().decode())
+    return out
+
+
+def _png_info_dict(rec):
+    return dict(width=int(rec.width), height=int(rec.height), bit_depth=int(rec.bit_depth), color_type=int(rec.color_type),
+                interlace=int(rec.interlace), channels=int(rec.channels), status=int(rec.status))
+
+
+def png_info(data):
+    """The signature and IHDR of a PNG file: a dict with width, height, bit_depth, color_type, interlace, channels and status
+    (PNG_OK: decode_png takes it, PNG_UNSUPPORTED, PNG_CORRUPT)"""
+    raw = bytes(data) if data is not None else b""
+    rec = PngFileInfo()
+    load().och_png_info(raw if raw else None, len(raw), C.byref(rec))
+    return _png_info_dict(rec)
+
+
+def decode_png(data):
+    """The picture of a PNG file, (h, w) or (h, w, c) uint8 in the file's channels (host code only).  PngError with the
+    status for a file that is not taken: never a wrong or a partial picture."""
+    raw = bytes(data) if data is not None else b""
+    L = load()
+    rec, px = PngFileInfo(), C.c_void_p()
+    if L.och_png_decode(raw if raw else None, len(raw), C.byref(rec), C.byref(px)) != 0:
+        raise capi.OchipError(L.och_png_last_error().decode())
+    if rec.status != PNG_OK:
+        raise PngError(int(rec.status), "an unsupported PNG file (palette, 16 bits, fewer than 8 bits or interlaced)"
+                       if rec.status == PNG_UNSUPPORTED else "a corrupt PNG file")
+    try:
+        n = rec.height * rec.width * rec.channels
+        out = np.ctypeslib.as_array(C.cast(px, C.POINTER(C.c_uint8)), (n,)).copy()
+    finally:
+        L.och_png_free(px)
+    return out.reshape(rec.height, rec.width) if rec.channels == 1 else out.reshape(rec.height, rec.width, rec.channels)
+
+
 def blend_chamfer(boundary):
     """The sequential two-pass 3 x 3 chamfer of a boundary mask, int32 in 1e-4 units."""
     m = np.ascontiguousarray(boundary, np.uint8)
@@ -3047,6 +3253,34 @@ class Graph:
             raise ValueError("a thumbnail is rows x cols x 3")
         if self.L.och_graph_set_thumbnail(self.h, int(index), rgb.shape[0], rgb.shape[1], rgb.ctypes.data) != 0:
             raise ValueError(self.L.och_last_error(self.h).decode())
+
+    def thumbnail(self, index):
+        """The decoded thumbnail of the node at `index` (rows x cols x 3 uint8), or None where it has none"""
+        rows, cols = C.c_size_t(0), C.c_size_t(0)
+        if self.L.och_graph_get_thumbnail(self.h, int(index), C.byref(rows), C.byref(cols), None) != 0:
+            raise ValueError(self.L.och_last_error(self.h).decode())
+        if rows.value == 0:
+            return None
+        out = np.empty((rows.value, cols.value, 3), np.uint8)
+        self.L.och_graph_get_thumbnail(self.h, int(index), C.byref(rows), C.byref(cols), out.ctypes.data)
+        return out
+
+    def encode_thumbnails(self, ctx=None):
+        """Every node's decoded thumbnail to the base64 PNG text graph.json carries (colour type 2, the three bytes as
+        stored), all nodes in one batch; ctx: on that device, None: the CPU route - the same text.  Returns their number."""
+        k = self.L.och_graph_encode_thumbnails(self.h, ctx.h if ctx is not None else None)
+        if k < 0:
+            raise capi.OchipError(self.L.och_last_error(self.h).decode())
+        return int(k)
+
+    def decode_thumbnails(self):
+        """Every node's thumbnail text to the pixels the preview samples (three channels: gray replicated, alpha dropped;
+        host code).  Returns the per-node statuses: -1 no text, PNG_OK, PNG_UNSUPPORTED, PNG_CORRUPT; a refused node is left
+        as it was."""
+        st = np.full(max(len(self.node_ids), 1), -1, np.int32)
+        if self.L.och_graph_decode_thumbnails(self.h, st.ctypes.data) < 0:
+            raise capi.OchipError(self.L.och_last_error(self.h).decode())
+        return [int(v) for v in st[:len(self.node_ids)]]
 
     def edges_flat(self, node_subset=None):
         """The linked edges as flat dicts (src/dst node index, H, inlier pixel pairs, match indices, match
