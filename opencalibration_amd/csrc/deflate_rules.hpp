@@ -1,10 +1,12 @@
-// The zlib stream of one GeoTIFF tile (the reference's GDAL options COMPRESS=DEFLATE, PREDICTOR=2 on
-// 512 x 512 tiles, src/ortho/ortho.cpp:655-708 and :745-791).  A tile is 512 x 512 pixels of 4 bytes - RGBA8 or one float32 -
-// so its predicted payload is 1 MiB.  This header is the rules for both routes: the match candidates and the greedy parse,
-// the length-limited Huffman code with its tie-breaks, the dynamic block header, the choice between the fixed and the dynamic
-// code, the stored fallback and the Adler-32 combination.  csrc/geotiff.hip runs them in kernels, host/geotiff.cpp in loops;
-// it includes nothing of either, so a stand-alone program builds from it.  Any valid stream that inflates to the payload is a
-// correct file; the two routes give the same bytes because every decision below is a function of the payload alone.
+// DEFLATE as this project writes it: the zlib stream of a payload of F bytes, one block per 16 384-byte segment, with two match
+// candidates - a fixed distance to the left and, optionally, a fixed distance up (a pixel and a row back).  This header is the
+// rules for every route and both formats that use them: the match candidates and the greedy parse, the length-limited Huffman
+// code with its tie-breaks, the dynamic block header, the choice between the fixed and the dynamic code, the stored fallback,
+// the Adler-32 combination, and the host encoder that runs them in loops.  The GeoTIFF tiles (its
+// geometry is the last part of this file) and the PNG files (section 4.20, png_rules.hpp) instantiate them; deflate_kernels.hpp
+// runs them in kernels.  It includes nothing of either, so a stand-alone program builds from it.  Any valid stream that
+// inflates to the payload is correct; the routes give the same bytes because every decision below is a function of the payload
+// and the two distances alone.
 #pragma once
 
 #include <cstdint>
@@ -20,25 +22,38 @@
 namespace ochip_df
 {
 
-constexpr int TILE = 512, PIXEL_BYTES = 4, ROW_BYTES = TILE * PIXEL_BYTES;
-constexpr int PAYLOAD = TILE * ROW_BYTES; // 1 048 576
-// One deflate block per segment of the payload: 8 tile rows, 64 blocks a tile, the last with BFINAL
-constexpr int SEGMENT = 16384, SEGMENTS = PAYLOAD / SEGMENT;
-// The stored form: 78 9C, 17 stored blocks of at most 65 535 bytes with 5 bytes of header each, the Adler-32
-constexpr int STORED_BLOCK = 65535, STORED_BLOCKS = (PAYLOAD + STORED_BLOCK - 1) / STORED_BLOCK;
-constexpr int STORED_BYTES = PAYLOAD + STORED_BLOCKS * 5 + 6;
-static_assert(STORED_BLOCKS == 17 && STORED_BYTES == 1048667, "the bound every buffer is sized from");
-constexpr int TILE_SLOT = (STORED_BYTES + 15) / 16 * 16; // a tile's room in a device buffer
-// Match candidates: the pixel to the left and the pixel above.  A position takes the longer run of at least MIN_MATCH bytes,
-// the smaller distance on a tie.
+// One deflate block per segment of the payload, the last with BFINAL
+constexpr int SEGMENT = 16384;
+constexpr int STORED_BLOCK = 65535; // a stored block's most bytes
+// Match candidates: dist_left bytes back and, where there is one, dist_up bytes back.  A position takes the longer run of at
+// least MIN_MATCH bytes, the smaller distance on a tie.
 constexpr int MIN_MATCH = 4, MAX_MATCH = 258;
-constexpr int DIST_LEFT = PIXEL_BYTES, DIST_UP = ROW_BYTES;
+constexpr int NO_UP = 0; // as dist_up: no second candidate
 // A position's mark: the token's length (0: a literal), the distance chosen, and whether the greedy parse starts a token here
 constexpr uint16_t MARK_LEN = 0x1FF, MARK_UP = 0x4000, MARK_START = 0x8000;
 
 constexpr int NUM_LIT = 286, NUM_DIST = 30, NUM_CL = 19, NUM_SYMS = NUM_LIT + NUM_DIST, EOB = 256;
 constexpr int HEADER_WORDS = 144; // 17 + 19 x 3 + 316 x 14 = 4 498 bits at most
 constexpr uint32_t ADLER_MOD = 65521;
+
+OCHIP_DF_HD constexpr uint64_t segments_of(uint64_t F)
+{
+    return (F + SEGMENT - 1) / SEGMENT;
+}
+
+// The stored form: 78 9C, ceil(F / 65 535) stored blocks of 5 bytes of header each, the Adler-32
+OCHIP_DF_HD constexpr uint64_t stored_bytes(uint64_t F)
+{
+    return 2 + F + 5 * ((F + STORED_BLOCK - 1) / STORED_BLOCK) + 4;
+}
+static_assert(stored_bytes(1) == 12 && stored_bytes(65535) == 65535 + 11 && stored_bytes(65536) == 65536 + 16, "the stored form");
+
+// A deflated stream of stream_bits is taken only where it is smaller than the stored form, so no stream is larger than that
+OCHIP_DF_HD bool takes_deflated(uint64_t stream_bits, uint64_t F, uint64_t &bytes)
+{
+    bytes = 2 + (stream_bits + 7) / 8 + 4;
+    return bytes < stored_bytes(F);
+}
 
 OCHIP_DF_HD uint16_t choose_match(int left, int up)
 {
@@ -229,7 +244,7 @@ OCHIP_DF_HD uint32_t fixed_code(int s) // s < 286: literal / length; s >= 286: d
     return 8u << 16 | reverse_bits(0xC0u + (uint32_t)(s - 280), 8);
 }
 
-// Bits LSB first into zeroed 32-bit words (the header of a block; the host's whole stream)
+// Bits LSB first into zeroed 32-bit words: the header of a block
 struct word_bits
 {
     uint32_t *words;
@@ -362,7 +377,7 @@ OCHIP_DF_HD uint32_t build_block(block_work &W, bool final, uint32_t *codes, uin
 }
 
 // The bits of the token a mark starts: a literal `byte`, or a length and distance pair.  At most 48 bits, LSB first.
-OCHIP_DF_HD uint64_t token_bits(uint16_t mark, uint8_t byte, const uint32_t *codes, int &n)
+OCHIP_DF_HD uint64_t token_bits(uint16_t mark, uint8_t byte, const uint32_t *codes, int &n, int dist_left, int dist_up)
 {
     const int len = mark & MARK_LEN;
     if (len == 0)
@@ -373,7 +388,7 @@ OCHIP_DF_HD uint64_t token_bits(uint16_t mark, uint8_t byte, const uint32_t *cod
     }
     int eb, ev, db, dv;
     const uint32_t lc = codes[length_symbol(len, eb, ev)];
-    const uint32_t dc = codes[NUM_LIT + distance_symbol((mark & MARK_UP) ? DIST_UP : DIST_LEFT, db, dv)];
+    const uint32_t dc = codes[NUM_LIT + distance_symbol((mark & MARK_UP) ? dist_up : dist_left, db, dv)];
     uint64_t v = lc & 0xFFFF;
     n = (int)(lc >> 16);
     v |= (uint64_t)ev << n, n += eb;
@@ -383,14 +398,14 @@ OCHIP_DF_HD uint64_t token_bits(uint16_t mark, uint8_t byte, const uint32_t *cod
 }
 
 // The symbols a mark's token counts: the literal / length symbol, and the distance symbol or -1
-OCHIP_DF_HD int token_symbols(uint16_t mark, uint8_t byte, int &dist_sym)
+OCHIP_DF_HD int token_symbols(uint16_t mark, uint8_t byte, int &dist_sym, int dist_left, int dist_up)
 {
     const int len = mark & MARK_LEN;
     dist_sym = -1;
     if (len == 0)
         return byte;
     int eb, ev;
-    dist_sym = distance_symbol((mark & MARK_UP) ? DIST_UP : DIST_LEFT, eb, ev);
+    dist_sym = distance_symbol((mark & MARK_UP) ? dist_up : dist_left, eb, ev);
     return length_symbol(len, eb, ev);
 }
 
@@ -403,31 +418,23 @@ OCHIP_DF_HD void adler_combine(uint32_t &s1, uint32_t &s2, uint32_t s1b, uint32_
     s1 = (a1 + s1b) % m;
 }
 
-// Byte o of the stored form of a payload whose Adler-32 is `adler`; o < STORED_BYTES
-OCHIP_DF_HD uint8_t stored_byte(uint32_t o, const uint8_t *payload, uint32_t adler)
+// Byte o of the stored form of a payload of F bytes whose Adler-32 is `adler`; o < stored_bytes(F)
+OCHIP_DF_HD uint8_t stored_byte(uint64_t o, const uint8_t *payload, uint64_t F, uint32_t adler)
 {
+    const uint64_t S = stored_bytes(F), blocks = (F + STORED_BLOCK - 1) / STORED_BLOCK;
     if (o < 2)
         return o == 0 ? 0x78 : 0x9C;
-    if (o >= (uint32_t)STORED_BYTES - 4)
-        return (uint8_t)(adler >> (8 * ((uint32_t)STORED_BYTES - 1 - o)));
-    const uint32_t k = (o - 2) / (STORED_BLOCK + 5), r = (o - 2) % (STORED_BLOCK + 5);
+    if (o >= S - 4)
+        return (uint8_t)(adler >> (8 * (S - 1 - o)));
+    const uint64_t k = (o - 2) / (STORED_BLOCK + 5), r = (o - 2) % (STORED_BLOCK + 5);
     if (r >= 5)
         return payload[k * STORED_BLOCK + (r - 5)];
-    const uint32_t len = k + 1 < (uint32_t)STORED_BLOCKS ? STORED_BLOCK : PAYLOAD - k * STORED_BLOCK;
-    return r == 0 ? (k + 1 == (uint32_t)STORED_BLOCKS ? 1 : 0) : r == 1 ? (uint8_t)len : r == 2 ? (uint8_t)(len >> 8) : r == 3 ? (uint8_t)~len : (uint8_t)(~len >> 8);
-}
-
-// The predictor over one tile row of 512 pixels: the first pixel stays, RGBA bytes take the byte 4 before them away, a
-// float's 32-bit pattern the pattern before it.  src: the row's pixels as 32-bit words, `valid` of them real, zeros behind.
-OCHIP_DF_HD uint32_t predict_word(uint32_t cur, uint32_t left, bool is_float)
-{
-    if (is_float)
-        return cur - left;
-    return ((cur | 0x80808080u) - (left & 0x7F7F7F7Fu)) ^ ((cur ^ ~left) & 0x80808080u);
+    const uint32_t len = k + 1 < blocks ? (uint32_t)STORED_BLOCK : (uint32_t)(F - k * STORED_BLOCK);
+    return r == 0 ? (k + 1 == blocks ? 1 : 0) : r == 1 ? (uint8_t)len : r == 2 ? (uint8_t)(len >> 8) : r == 3 ? (uint8_t)~len : (uint8_t)(~len >> 8);
 }
 
 #if !defined(__HIP_DEVICE_COMPILE__)
-// ---- the host route's tile encoder: the same rules in loops -------------------------------------------------------------------
+// ---- the host route's encoder: the same rules in loops ------------------------------------------------------------------------
 inline uint32_t adler32(const uint8_t *p, size_t n)
 {
     uint32_t s1 = 1, s2 = 0;
@@ -441,86 +448,157 @@ inline uint32_t adler32(const uint8_t *p, size_t n)
     return s2 << 16 | s1;
 }
 
-// marks[PAYLOAD] of a payload: candidate runs backwards per segment, then the greedy parse from each segment's start
-inline void mark_tile(const uint8_t *a, uint16_t *marks)
+struct block_out
 {
-    for (int seg = 0; seg < SEGMENTS; seg++)
+    uint32_t codes[NUM_SYMS];
+    uint32_t header[HEADER_WORDS];
+    uint32_t header_bits = 0, bits = 0;
+};
+
+// One segment of a payload of F bytes: the candidate runs backwards from its end into marks[lo, hi), the greedy parse from
+// its start, the block's codes.  dist_up: NO_UP or the second candidate's distance.
+inline void segment_block(const uint8_t *a, uint64_t F, uint64_t seg, int dist_left, int dist_up, uint16_t *marks, block_out &B)
+{
+    const int64_t lo = (int64_t)seg * SEGMENT, hi = lo + SEGMENT < (int64_t)F ? lo + SEGMENT : (int64_t)F;
+    int left = 0, up = 0;
+    for (int64_t p = hi - 1; p >= lo; p--)
     {
-        const int lo = seg * SEGMENT, hi = lo + SEGMENT;
-        int left = 0, up = 0;
-        for (int p = hi - 1; p >= lo; p--)
-        {
-            left = p >= DIST_LEFT && a[p] == a[p - DIST_LEFT] ? left + 1 : 0;
-            up = p >= DIST_UP && a[p] == a[p - DIST_UP] ? up + 1 : 0;
-            marks[p] = choose_match(left, up);
-        }
-        for (int p = lo; p < hi;)
-        {
-            marks[p] |= MARK_START;
-            const int len = marks[p] & MARK_LEN;
-            p += len ? len : 1;
-        }
+        left = p >= dist_left && a[p] == a[p - dist_left] ? left + 1 : 0;
+        up = dist_up != NO_UP && p >= dist_up && a[p] == a[p - dist_up] ? up + 1 : 0;
+        marks[p] = choose_match(left, up);
     }
+    block_work W;
+    std::memset(W.counts, 0, sizeof W.counts);
+    for (int64_t p = lo; p < hi;)
+    {
+        marks[p] |= MARK_START;
+        int ds;
+        W.counts[token_symbols(marks[p], a[p], ds, dist_left, dist_up)]++;
+        if (ds >= 0)
+            W.counts[NUM_LIT + ds]++;
+        const int len = marks[p] & MARK_LEN;
+        p += len ? len : 1;
+    }
+    std::memset(B.header, 0, sizeof B.header);
+    B.bits = build_block(W, seg + 1 == segments_of(F), B.codes, B.header, B.header_bits);
 }
 
-// The zlib stream of a payload into out (cleared first); at most STORED_BYTES
-inline void encode_tile(const uint8_t *a, std::vector<uint8_t> &out)
+// Bits LSB first into zeroed bytes, the position 64-bit
+struct bit_sink
 {
-    std::vector<uint16_t> marks(PAYLOAD);
-    mark_tile(a, marks.data());
-    const uint32_t adler = adler32(a, PAYLOAD);
-    std::vector<uint32_t> words((size_t)STORED_BYTES / 4 + HEADER_WORDS + 16, 0);
-    word_bits w{words.data(), (uint32_t)STORED_BYTES * 8, 16};
-    bool fits = true;
-    block_work W;
-    uint32_t codes[NUM_SYMS], header[HEADER_WORDS], header_bits = 0;
-    for (int seg = 0; seg < SEGMENTS && fits; seg++)
+    uint8_t *bytes;
+    uint64_t cap_bits, bits;
+    void put(uint64_t v, int n) // n <= 48
     {
-        const int lo = seg * SEGMENT, hi = lo + SEGMENT;
-        std::memset(W.counts, 0, sizeof W.counts);
-        for (int p = lo; p < hi; p++)
-            if (marks[p] & MARK_START)
-            {
-                int ds;
-                W.counts[token_symbols(marks[p], a[p], ds)]++;
-                if (ds >= 0)
-                    W.counts[NUM_LIT + ds]++;
-            }
-        std::memset(header, 0, sizeof header);
-        const uint32_t bits = build_block(W, seg + 1 == SEGMENTS, codes, header, header_bits);
-        if ((uint64_t)w.bits + bits > (uint64_t)(STORED_BYTES - 4) * 8)
-        {
-            fits = false;
-            break;
-        }
-        for (uint32_t b = 0; b < header_bits; b += 16)
-            w.put((header[b >> 5] >> (b & 31)) & 0xFFFF & ((1u << (header_bits - b < 16 ? header_bits - b : 16)) - 1),
-                  (int)(header_bits - b < 16 ? header_bits - b : 16));
-        for (int p = lo; p < hi; p++)
-            if (marks[p] & MARK_START)
-            {
-                int n;
-                const uint64_t v = token_bits(marks[p], a[p], codes, n);
-                w.put((uint32_t)(v & 0xFFFFFF), n < 24 ? n : 24);
-                if (n > 24)
-                    w.put((uint32_t)(v >> 24), n - 24);
-            }
-        w.put(codes[EOB] & 0xFFFF, (int)(codes[EOB] >> 16));
+        if (n <= 0 || bits + (uint64_t)n > cap_bits)
+            return;
+        uint64_t at = bits >> 3;
+        const int s = (int)(bits & 7);
+        bits += (uint64_t)n;
+        unsigned __int128 w = (unsigned __int128)v << s;
+        for (int left = n + s; left > 0; left -= 8, w >>= 8)
+            bytes[at++] |= (uint8_t)w;
     }
-    const size_t bytes = fits ? 2 + ((size_t)(w.bits - 16) + 7) / 8 + 4 : (size_t)STORED_BYTES;
-    out.clear();
-    if (!fits || bytes >= (size_t)STORED_BYTES)
+};
+
+// A marked and coded segment's block: the header in 16-bit slices, the tokens, the end-of-block symbol
+inline void emit_segment(bit_sink &w, const uint8_t *a, uint64_t F, uint64_t seg, int dist_left, int dist_up, const uint16_t *marks,
+                         const block_out &B)
+{
+    const int64_t lo = (int64_t)seg * SEGMENT, hi = lo + SEGMENT < (int64_t)F ? lo + SEGMENT : (int64_t)F;
+    for (uint32_t b = 0; b < B.header_bits; b += 16)
     {
-        out.resize(STORED_BYTES);
-        for (uint32_t o = 0; o < (uint32_t)STORED_BYTES; o++)
-            out[o] = stored_byte(o, a, adler);
+        const int n = B.header_bits - b < 16 ? (int)(B.header_bits - b) : 16;
+        w.put((B.header[b >> 5] >> (b & 31)) & ((1u << n) - 1), n);
+    }
+    for (int64_t p = lo; p < hi; p++)
+        if (marks[p] & MARK_START)
+        {
+            int n;
+            const uint64_t v = token_bits(marks[p], a[p], B.codes, n, dist_left, dist_up);
+            w.put(v, n);
+        }
+    w.put(B.codes[EOB] & 0xFFFF, (int)(B.codes[EOB] >> 16));
+}
+
+// The bytes of the stream of a payload whose segments are coded, and whether it is the deflated one
+inline uint64_t stream_bytes(const block_out *blocks, uint64_t F, bool &deflated)
+{
+    uint64_t bits = 0, bytes = 0;
+    for (uint64_t k = 0; k < segments_of(F); k++)
+        bits += blocks[k].bits;
+    deflated = takes_deflated(bits, F, bytes);
+    return deflated ? bytes : stored_bytes(F);
+}
+
+// The stream into z[stream_bytes], zeroed: deflated from the marks and blocks, or stored.  The Adler-32 is combined from the
+// segments' partials, as the device combines them.
+inline void write_stream(const uint8_t *a, uint64_t F, int dist_left, int dist_up, const uint16_t *marks, const block_out *blocks,
+                         bool deflated, uint64_t zlen, uint8_t *z)
+{
+    uint32_t a1 = 1, a2 = 0;
+    for (uint64_t lo = 0; lo < F; lo += SEGMENT)
+    {
+        const uint64_t n = F - lo < (uint64_t)SEGMENT ? F - lo : (uint64_t)SEGMENT;
+        const uint32_t ad = adler32(a + lo, (size_t)n);
+        adler_combine(a1, a2, ad & 0xFFFF, ad >> 16, (uint32_t)n);
+    }
+    const uint32_t adler = a2 << 16 | a1;
+    if (!deflated)
+    {
+        for (uint64_t o = 0; o < zlen; o++)
+            z[o] = stored_byte(o, a, F, adler);
         return;
     }
-    out.resize(bytes);
-    std::memcpy(out.data(), words.data(), bytes - 4); // little-endian words: the stream's byte order
-    out[0] = 0x78, out[1] = 0x9C;
+    z[0] = 0x78, z[1] = 0x9C;
+    bit_sink w{z, (zlen - 4) * 8, 16};
+    for (uint64_t k = 0; k < segments_of(F); k++)
+        emit_segment(w, a, F, k, dist_left, dist_up, marks, blocks[k]);
     for (int k = 0; k < 4; k++)
-        out[bytes - 4 + k] = (uint8_t)(adler >> (8 * (3 - k)));
+        z[zlen - 4 + k] = (uint8_t)(adler >> (8 * (3 - k)));
+}
+
+// The zlib stream of a payload of F bytes into out (cleared first), serially; at most stored_bytes(F)
+inline void encode_stream(const uint8_t *a, uint64_t F, int dist_left, int dist_up, std::vector<uint8_t> &out)
+{
+    std::vector<uint16_t> marks((size_t)F);
+    std::vector<block_out> blocks((size_t)segments_of(F));
+    for (uint64_t k = 0; k < segments_of(F); k++)
+        segment_block(a, F, k, dist_left, dist_up, marks.data(), blocks[(size_t)k]);
+    bool deflated = false;
+    const uint64_t zlen = stream_bytes(blocks.data(), F, deflated);
+    out.assign((size_t)zlen, 0);
+    write_stream(a, F, dist_left, dist_up, marks.data(), blocks.data(), deflated, zlen, out.data());
+}
+#endif
+
+// ---- the GeoTIFF tile (the reference's GDAL options COMPRESS=DEFLATE, PREDICTOR=2 on 512 x 512 tiles,
+// src/ortho/ortho.cpp:655-708 and :745-791) -----------------------------------------------------------------------------------
+// A tile is 512 x 512 pixels of 4 bytes - RGBA8 or one float32 - so its predicted payload is 1 MiB: 64 segments of 8 tile
+// rows, the candidates the pixel to the left and the pixel above.
+constexpr int TILE = 512, PIXEL_BYTES = 4, ROW_BYTES = TILE * PIXEL_BYTES;
+constexpr int PAYLOAD = TILE * ROW_BYTES; // 1 048 576
+constexpr int SEGMENTS = PAYLOAD / SEGMENT;
+constexpr int DIST_LEFT = PIXEL_BYTES, DIST_UP = ROW_BYTES;
+constexpr int STORED_BLOCKS = (PAYLOAD + STORED_BLOCK - 1) / STORED_BLOCK;
+constexpr int STORED_BYTES = (int)stored_bytes(PAYLOAD);
+static_assert(STORED_BLOCKS == 17 && STORED_BYTES == 1048667, "the bound every buffer is sized from");
+constexpr int TILE_SLOT = (STORED_BYTES + 15) / 16 * 16; // a tile's room in a device buffer
+
+// The predictor over one tile row of 512 pixels: the first pixel stays, RGBA bytes take the byte 4 before them away, a
+// float's 32-bit pattern the pattern before it.  src: the row's pixels as 32-bit words, `valid` of them real, zeros behind.
+OCHIP_DF_HD uint32_t predict_word(uint32_t cur, uint32_t left, bool is_float)
+{
+    if (is_float)
+        return cur - left;
+    return ((cur | 0x80808080u) - (left & 0x7F7F7F7Fu)) ^ ((cur ^ ~left) & 0x80808080u);
+}
+
+#if !defined(__HIP_DEVICE_COMPILE__)
+// The zlib stream of a tile's payload into out (cleared first); at most STORED_BYTES
+inline void encode_tile(const uint8_t *a, std::vector<uint8_t> &out)
+{
+    encode_stream(a, PAYLOAD, DIST_LEFT, DIST_UP, out);
 }
 #endif
 

@@ -1,30 +1,22 @@
-// The tiles of the tiled DEFLATE GeoTIFFs on the device (the rules: deflate_rules.hpp).  A feed copies
-// its rows into the tile row being filled; a complete tile row is one pass of these launches on the context's stream:
+// The tiles of the tiled DEFLATE GeoTIFFs on the device (the rules: deflate_rules.hpp, the encoder's
+// kernel bodies: deflate_kernels.hpp).  A feed copies its rows into the tile row being filled; a complete tile row is one pass
+// of these launches on the context's stream:
 //   gt_payload     512 x 512 tiles out of the rows: 16-byte loads where the width allows, the horizontal predictor, zeros
 //                  beyond the raster; a tile's any-non-zero flag
 //   gt_parse       a workgroup per 16 384-byte segment: a lane compares its 64 bytes with the pixel to the left and the pixel
-//                  above into two 64-bit masks, the runs come from the masks and the heads of the chunks behind (LDS); the
-//                  greedy parse - a walk from the segment's start - is cut into the lanes' chunks: where a walk that enters
-//                  a chunk at each of its positions leaves it (64 steps a lane, all lanes at once), one lane's hops from
-//                  chunk to chunk (at most 256), then every entered chunk marks and counts its tokens; the segment's
-//                  Adler-32 partial
-//   gt_codes       a wave per block: the counts, the code construction's arrays and the header in LDS, the construction itself
-//                  - sequential by nature - on one lane; the block's bits
+//                  above - compile-time distances 4 and 2 048, aligned 16-byte loads of the row above - into two 64-bit masks,
+//                  then parse_segment
+//   gt_codes       a wave per block: codes_block
 //   (rocPRIM)      exclusive scan of the blocks' bits
 //   gt_tile_sizes  a lane a tile: its bits, deflated or stored or left out, its Adler-32 from the 64 partials
 //   (rocPRIM)      exclusive scan of the tiles' 16-byte-aligned sizes: where each lies in the pass's output
-//   gt_emit        a workgroup per block: a lane sums the bits of the tokens that start in its 64 bytes, a scan over the
-//                  workgroup places them, whole words are stored and the two ragged ones ORed into the zeroed buffer
+//   gt_emit        a workgroup per block of a deflated tile that fits the slot: emit_segment into the tile's words
 //   gt_stored      the stored form of the tiles that did not shrink
 //   gt_finish      78 9C and the Adler-32 of the deflated tiles; offsets and counts for the host
 // and two copies to page-locked memory: the offsets and counts, and as many bytes as the pass before suggests.  A pass writes
 // into one of OUT_SLOTS output slots with an event each; the host reads a slot when a pass needs it again, at collect or at
 // finish - one wait, for the slot's event, and so not for what the caller enqueued on the stream since.
-#include "ctx.hpp"
-#include "deflate_rules.hpp"
-
-#include <rocprim/device/device_scan.hpp>
-#include <rocprim/iterator/transform_iterator.hpp>
+#include "deflate_kernels.hpp"
 
 #include <deque>
 #include <memory>
@@ -35,11 +27,9 @@
 namespace
 {
 
-using namespace ochip_df;
+using namespace ochip_dfk;
 
-constexpr int THREADS = 256, CHUNK = SEGMENT / THREADS; // a lane's 64 bytes of a segment
 constexpr int OUT_SLOTS = 4;
-static_assert(CHUNK == 64, "a lane's bytes are the bits of one 64-bit mask");
 
 // skip: the tile is all zero and the writer sparse
 __device__ bool skipped(const uint32_t *nz, int sparse, int tile)
@@ -80,23 +70,9 @@ __global__ __launch_bounds__(THREADS) void gt_payload(const uint32_t *rows, int6
         atomicOr(&nz[tile], 1u);
 }
 
-__device__ int ones_from(uint64_t m, int j) // the run of set bits of m from bit j upwards, at most 64 - j
-{
-    const uint64_t x = ~(m >> j);
-    return x ? __builtin_ctzll(x) : 64;
-}
-
 __global__ __launch_bounds__(THREADS) void gt_parse(const uint8_t *payload, const uint32_t *nz, int sparse, int blocks, uint16_t *tok,
                                                      uint32_t *counts, uint32_t *seg_adler)
 {
-    constexpr uint16_t MARK_OVER = 0x200; // a mark's spare bit, inside this kernel only
-    constexpr int NOT_ENTERED = CHUNK;    // the walk jumps over the chunk
-    __shared__ uint16_t best[SEGMENT];
-    __shared__ uint8_t leave[SEGMENT];
-    __shared__ uint8_t entry[THREADS];
-    __shared__ uint16_t head[2][THREADS];
-    __shared__ uint32_t cnt[NUM_SYMS];
-    __shared__ uint32_t ad1[THREADS], ad2[THREADS];
     const int b = blockIdx.x, t = threadIdx.x;
     if (b >= blocks)
         return;
@@ -104,6 +80,7 @@ __global__ __launch_bounds__(THREADS) void gt_parse(const uint8_t *payload, cons
     if (skipped(nz, sparse, tile))
         return;
     const uint8_t *a = payload + (size_t)tile * PAYLOAD;
+    // the lane's two masks at the tile's fixed geometry: whole chunks, the row above in aligned 16-byte loads
     const int P0 = seg * SEGMENT + t * CHUNK;
     const bool has_left = P0 >= DIST_LEFT, has_up = P0 >= DIST_UP;
     uint32_t prev = has_left ? *reinterpret_cast<const uint32_t *>(a + P0 - DIST_LEFT) : 0;
@@ -139,123 +116,20 @@ __global__ __launch_bounds__(THREADS) void gt_parse(const uint8_t *payload, cons
         m_left &= ~0xFull;
     if (!has_up)
         m_up = 0;
-    head[0][t] = (uint16_t)ones_from(m_left, 0), head[1][t] = (uint16_t)ones_from(m_up, 0);
-    ad1[t] = 1 + s1, ad2[t] = (CHUNK + s2) % ADLER_MOD;
-    for (int i = t; i < NUM_SYMS; i += THREADS)
-        cnt[i] = 0;
-    __syncthreads();
-    // how far a run that reaches this chunk's end goes on in the chunks behind, the segment's end the limit
-    int more[2] = {0, 0};
-#pragma unroll
-    for (int d = 0; d < 2; d++)
-    {
-        int r = 0;
-        for (int k = t + 1; k < THREADS; k++)
-        {
-            const int h = head[d][k];
-            r += h;
-            if (h < CHUNK || r >= MAX_MATCH)
-                break;
-        }
-        more[d] = r;
-    }
-    for (int j = 0; j < CHUNK; j++)
-    {
-        int rl = ones_from(m_left, j), ru = ones_from(m_up, j);
-        if (rl == CHUNK - j)
-            rl += more[0];
-        if (ru == CHUNK - j)
-            ru += more[1];
-        best[t * CHUNK + j] = choose_match(rl, ru);
-    }
-    // The greedy parse is a walk from the segment's start.  Each lane first finds, for every position of its chunk, how far
-    // behind the chunk's end a walk entering there leaves it (0 .. 257: nine bits, the ninth in the mark's spare bit);
-    // backwards, so a position reads the answer of the one it steps to.  One lane then hops from chunk to chunk - at most
-    // 256 hops instead of 16 384 steps - and every entered chunk marks its own tokens.
-    for (int e = CHUNK - 1; e >= 0; e--)
-    {
-        const uint16_t m = best[t * CHUNK + e];
-        const int len = m & MARK_LEN, n = e + (len ? len : 1);
-        int over;
-        if (n >= CHUNK)
-            over = n - CHUNK;
-        else
-            over = leave[t * CHUNK + n] | ((best[t * CHUNK + n] & MARK_OVER) ? 256 : 0);
-        leave[t * CHUNK + e] = (uint8_t)over;
-        if (over & 256)
-            best[t * CHUNK + e] = m | MARK_OVER;
-    }
-    entry[t] = NOT_ENTERED;
-    __syncthreads();
-    if (t == 0)
-    {
-        for (int c = 0, e = 0; c < THREADS;)
-        {
-            entry[c] = (uint8_t)e;
-            const int at = c * CHUNK + e;
-            const int next = (c + 1) * CHUNK + (leave[at] | ((best[at] & MARK_OVER) ? 256 : 0));
-            c = next / CHUNK, e = next % CHUNK;
-        }
-    }
-    else if (t == 64)
-    {
-        uint32_t a1 = ad1[0], a2 = ad2[0];
-        for (int k = 1; k < THREADS; k++)
-            adler_combine(a1, a2, ad1[k], ad2[k], CHUNK);
-        seg_adler[2 * (size_t)b] = a1, seg_adler[2 * (size_t)b + 1] = a2;
-    }
-    __syncthreads();
-    // the tokens of this lane's chunk, if the walk enters it: marked and counted in one pass
-    for (int j = entry[t]; j < CHUNK;)
-    {
-        const uint16_t m = best[t * CHUNK + j];
-        best[t * CHUNK + j] = m | MARK_START;
-        int ds;
-        const int ls = token_symbols(m, a[P0 + j], ds);
-        atomicAdd(&cnt[ls], 1u);
-        if (ds >= 0)
-            atomicAdd(&cnt[NUM_LIT + ds], 1u);
-        const int len = m & MARK_LEN;
-        j += len ? len : 1;
-    }
-    __syncthreads();
-    uint16_t *out = tok + (size_t)tile * PAYLOAD + (size_t)seg * SEGMENT;
-    for (int i = t; i < SEGMENT; i += THREADS)
-        out[i] = best[i] & (uint16_t)~MARK_OVER;
-    for (int i = t; i < NUM_SYMS; i += THREADS)
-        counts[(size_t)b * NUM_SYMS + i] = cnt[i];
+    parse_segment(m_left, m_up, s1, s2, CHUNK, a, (uint32_t)(seg * SEGMENT), SEGMENT, DIST_LEFT, DIST_UP, tok + (size_t)tile * PAYLOAD,
+                  counts + (size_t)b * NUM_SYMS, seg_adler + 2 * (size_t)b);
 }
 
 __global__ __launch_bounds__(64) void gt_codes(const uint32_t *counts, const uint32_t *nz, int sparse, int blocks, uint32_t *codes,
                                                 uint32_t *header, uint32_t *header_bits, uint32_t *block_bits)
 {
-    __shared__ block_work W;
-    __shared__ uint32_t c[NUM_SYMS];
-    __shared__ uint32_t h[HEADER_WORDS];
-    __shared__ uint32_t hb;
-    const int b = blockIdx.x, t = threadIdx.x;
+    const int b = blockIdx.x;
     if (b >= blocks)
         return;
     if (skipped(nz, sparse, b / SEGMENTS))
         return; // block_bits was zeroed
-    for (int i = t; i < NUM_SYMS; i += 64)
-        W.counts[i] = counts[(size_t)b * NUM_SYMS + i];
-    for (int i = t; i < HEADER_WORDS; i += 64)
-        h[i] = 0;
-    __syncthreads();
-    if (t == 0)
-    {
-        uint32_t bits_of_header = 0;
-        block_bits[b] = build_block(W, b % SEGMENTS == SEGMENTS - 1, c, h, bits_of_header);
-        hb = bits_of_header;
-    }
-    __syncthreads();
-    for (int i = t; i < NUM_SYMS; i += 64)
-        codes[(size_t)b * NUM_SYMS + i] = c[i];
-    for (int i = t; i < HEADER_WORDS; i += 64)
-        header[(size_t)b * HEADER_WORDS + i] = h[i];
-    if (t == 0)
-        header_bits[b] = hb;
+    codes_block(counts + (size_t)b * NUM_SYMS, b % SEGMENTS == SEGMENTS - 1, codes + (size_t)b * NUM_SYMS, header + (size_t)b * HEADER_WORDS,
+                header_bits + b, block_bits + b);
 }
 
 // state: 0 deflated, 1 stored, 2 left out; count: the stream's bytes; size[tiles] = 0 so that the scan's last output is the total
@@ -276,120 +150,28 @@ __global__ __launch_bounds__(THREADS) void gt_tile_sizes(const unsigned long lon
         state[i] = 2, count[i] = 0, size[i] = 0, adler[i] = 0;
         return;
     }
-    const unsigned long long bits = block_off[(size_t)(i + 1) * SEGMENTS] - block_off[(size_t)i * SEGMENTS];
-    const unsigned long long bytes = 6 + (bits + 7) / 8;
-    const bool stored = bytes >= (unsigned long long)STORED_BYTES;
+    uint64_t bytes = 0;
+    const bool stored = !takes_deflated(block_off[(size_t)(i + 1) * SEGMENTS] - block_off[(size_t)i * SEGMENTS], PAYLOAD, bytes);
     const uint32_t n = stored ? (uint32_t)STORED_BYTES : (uint32_t)bytes;
     state[i] = stored ? 1 : 0, count[i] = n, size[i] = (n + 15u) & ~15u;
-    uint32_t a1 = seg_adler[2 * (size_t)i * SEGMENTS], a2 = seg_adler[2 * (size_t)i * SEGMENTS + 1];
-    for (int k = 1; k < SEGMENTS; k++)
-        adler_combine(a1, a2, seg_adler[2 * ((size_t)i * SEGMENTS + k)], seg_adler[2 * ((size_t)i * SEGMENTS + k) + 1], SEGMENT);
-    adler[i] = a2 << 16 | a1;
+    adler[i] = stream_adler(seg_adler + 2 * (size_t)i * SEGMENTS, PAYLOAD);
 }
-
-// Bits LSB first from bit `pos` of a tile's words.  A word this lane fills alone is stored; the first word when the lane starts
-// inside it and the last partial one are ORed into the zeroed buffer.  Nothing is written at or beyond cap.
-struct tile_writer
-{
-    uint32_t *words;
-    uint32_t cap, wi;
-    uint64_t acc;
-    int n;
-    bool shared_first;
-    __device__ void put(uint32_t v, int len) // len <= 24
-    {
-        acc |= (uint64_t)v << n, n += len;
-        if (n >= 32)
-        {
-            if (wi < cap)
-            {
-                if (shared_first)
-                    atomicOr(&words[wi], (uint32_t)acc);
-                else
-                    words[wi] = (uint32_t)acc;
-            }
-            shared_first = false;
-            wi++, n -= 32, acc >>= 32;
-        }
-    }
-    __device__ void flush()
-    {
-        if (n > 0 && wi < cap)
-            atomicOr(&words[wi], (uint32_t)acc);
-    }
-};
 
 __global__ __launch_bounds__(THREADS) void gt_emit(const uint8_t *payload, const uint16_t *tok, const uint32_t *codes, const uint32_t *header,
                                                     const uint32_t *header_bits, const unsigned long long *block_off,
                                                     const unsigned long long *tile_off, const uint32_t *state, const uint32_t *size,
                                                     int blocks, uint8_t *out, unsigned long long out_cap)
 {
-    __shared__ uint32_t c[NUM_SYMS];
-    __shared__ uint32_t sc[THREADS];
-    const int b = blockIdx.x, t = threadIdx.x;
+    const int b = blockIdx.x;
     if (b >= blocks)
         return;
     const int tile = b / SEGMENTS, seg = b % SEGMENTS;
     if (state[tile] != 0 || tile_off[tile] + size[tile] > out_cap)
         return;
-    for (int i = t; i < NUM_SYMS; i += THREADS)
-        c[i] = codes[(size_t)b * NUM_SYMS + i];
-    __syncthreads();
-    const uint8_t *a = payload + (size_t)tile * PAYLOAD + (size_t)seg * SEGMENT + (size_t)t * CHUNK;
-    const uint16_t *marks = tok + (size_t)tile * PAYLOAD + (size_t)seg * SEGMENT + (size_t)t * CHUNK;
-    const uint32_t hbits = header_bits[b];
-    uint32_t bits = 0;
-    for (int j = 0; j < CHUNK; j++)
-    {
-        const uint16_t m = marks[j];
-        if (m & MARK_START)
-        {
-            int n;
-            (void)token_bits(m, a[j], c, n);
-            bits += (uint32_t)n;
-        }
-    }
-    if (t == 0)
-        bits += hbits;
-    if (t == THREADS - 1)
-        bits += c[EOB] >> 16;
-    sc[t] = bits;
-    __syncthreads();
-    for (int o = 1; o < THREADS; o <<= 1)
-    {
-        const uint32_t v = t >= o ? sc[t - o] : 0;
-        __syncthreads();
-        sc[t] += v;
-        __syncthreads();
-    }
-    const unsigned long long pos = 16 + (block_off[b] - block_off[(size_t)tile * SEGMENTS]) + (sc[t] - bits);
-    tile_writer w;
-    w.words = reinterpret_cast<uint32_t *>(out + tile_off[tile]), w.cap = size[tile] / 4;
-    w.wi = (uint32_t)(pos >> 5), w.acc = 0, w.n = (int)(pos & 31), w.shared_first = w.n != 0;
-    if (t == 0)
-    {
-        const uint32_t *h = header + (size_t)b * HEADER_WORDS;
-        for (uint32_t at = 0; at < hbits && at < HEADER_WORDS * 32; at += 16)
-        {
-            const int n = hbits - at < 16 ? (int)(hbits - at) : 16;
-            w.put((h[at >> 5] >> (at & 31)) & ((1u << n) - 1), n);
-        }
-    }
-    for (int j = 0; j < CHUNK; j++)
-    {
-        const uint16_t m = marks[j];
-        if (m & MARK_START)
-        {
-            int n;
-            const uint64_t v = token_bits(m, a[j], c, n);
-            w.put((uint32_t)(v & 0xFFFFFF), n < 24 ? n : 24);
-            if (n > 24)
-                w.put((uint32_t)(v >> 24), n - 24);
-        }
-    }
-    if (t == THREADS - 1)
-        w.put(c[EOB] & 0xFFFF, (int)(c[EOB] >> 16));
-    w.flush();
+    const size_t at = (size_t)tile * PAYLOAD + (size_t)seg * SEGMENT;
+    emit_segment(payload + at, tok + at, CHUNK, codes + (size_t)b * NUM_SYMS, header + (size_t)b * HEADER_WORDS, header_bits[b],
+                 reinterpret_cast<uint32_t *>(out + tile_off[tile]), size[tile] / 4, 16 + (block_off[b] - block_off[(size_t)tile * SEGMENTS]),
+                 DIST_LEFT, DIST_UP);
 }
 
 __global__ __launch_bounds__(THREADS) void gt_stored(const uint8_t *payload, const unsigned long long *tile_off, const uint32_t *state,
@@ -399,17 +181,7 @@ __global__ __launch_bounds__(THREADS) void gt_stored(const uint8_t *payload, con
     const uint32_t i = blockIdx.x * THREADS + threadIdx.x;
     if (tile >= tiles || state[tile] != 1 || i >= (uint32_t)TILE_SLOT / 4 || tile_off[tile] + TILE_SLOT > out_cap)
         return;
-    const uint8_t *a = payload + (size_t)tile * PAYLOAD;
-    const uint32_t ad = adler[tile];
-    uint32_t word = 0;
-#pragma unroll
-    for (uint32_t k = 0; k < 4; k++)
-    {
-        const uint32_t o = i * 4 + k;
-        if (o < (uint32_t)STORED_BYTES)
-            word |= (uint32_t)stored_byte(o, a, ad) << (8 * k);
-    }
-    reinterpret_cast<uint32_t *>(out + tile_off[tile])[i] = word;
+    reinterpret_cast<uint32_t *>(out + tile_off[tile])[i] = stored_word(i, payload + (size_t)tile * PAYLOAD, PAYLOAD, adler[tile]);
 }
 
 // info: [0, tiles] the tiles' offsets in the slot and the total, [tiles + 1, 2 tiles + 1) their byte counts
@@ -432,21 +204,8 @@ __global__ __launch_bounds__(THREADS) void gt_finish(const unsigned long long *t
         p[count[i] - 4 + k] = (uint8_t)(adler[i] >> (8 * (3 - k)));
 }
 
-struct widen
-{
-    __host__ __device__ unsigned long long operator()(uint32_t v) const
-    {
-        return v;
-    }
-};
-
 std::mutex g_live_mutex;
 std::set<const void *> g_live; // the writers that exist: a destroyed handle is refused, not followed
-
-uint32_t blocks_of(size_t n)
-{
-    return (uint32_t)((n + THREADS - 1) / THREADS);
-}
 
 } // namespace
 
@@ -500,11 +259,6 @@ void release_host_side(ochip_geotiff *e)
         ochip_host_free(e->ctx, o.pin_info);
         ochip_host_free(e->ctx, o.pin_bytes);
     }
-}
-
-int launched(ochip_ctx *ctx, const char *what)
-{
-    return hipGetLastError() == hipSuccess ? OCHIP_OK : ochip_fail(ctx, OCHIP_EHIP, "%s launch failed", what);
 }
 
 // The oldest pending pass's tiles into the host queue: the one wait
@@ -573,20 +327,11 @@ int encode_payloads(ochip_geotiff *e, int tiles)
     hipLaunchKernelGGL(gt_codes, dim3((uint32_t)blocks), dim3(64), 0, st, e->counts, e->nz, e->sparse, blocks, e->codes, e->header,
                        e->header_bits, e->block_bits);
     OCHIP_TRY(launched(ctx, "gt_codes"));
-    size_t need = 0;
-    auto bits64 = rocprim::make_transform_iterator(e->block_bits, widen());
-    OCHIP_HIP(ctx, rocprim::exclusive_scan(nullptr, need, bits64, e->block_off, 0ull, (size_t)blocks + 1, rocprim::plus<unsigned long long>(), st));
-    if (need > e->scan_bytes)
-        return ochip_fail(ctx, OCHIP_EHIP, "ochip_geotiff: the scan of %d blocks wants %zu bytes, %zu are held", blocks + 1, need, e->scan_bytes);
-    OCHIP_HIP(ctx, rocprim::exclusive_scan(e->scan_tmp, need, bits64, e->block_off, 0ull, (size_t)blocks + 1, rocprim::plus<unsigned long long>(), st));
+    OCHIP_TRY(scan_offsets(ctx, "ochip_geotiff", e->scan_tmp, e->scan_bytes, e->block_bits, e->block_off, (size_t)blocks + 1, st));
     hipLaunchKernelGGL(gt_tile_sizes, dim3(blocks_of((size_t)tiles + 1)), dim3(THREADS), 0, st, e->block_off, e->seg_adler, e->nz, e->sparse,
                        tiles, e->state, e->count, e->size, e->adler);
     OCHIP_TRY(launched(ctx, "gt_tile_sizes"));
-    auto size64 = rocprim::make_transform_iterator(e->size, widen());
-    OCHIP_HIP(ctx, rocprim::exclusive_scan(nullptr, need, size64, e->tile_off, 0ull, (size_t)tiles + 1, rocprim::plus<unsigned long long>(), st));
-    if (need > e->scan_bytes)
-        return ochip_fail(ctx, OCHIP_EHIP, "ochip_geotiff: the scan of %d tiles wants %zu bytes, %zu are held", tiles + 1, need, e->scan_bytes);
-    OCHIP_HIP(ctx, rocprim::exclusive_scan(e->scan_tmp, need, size64, e->tile_off, 0ull, (size_t)tiles + 1, rocprim::plus<unsigned long long>(), st));
+    OCHIP_TRY(scan_offsets(ctx, "ochip_geotiff", e->scan_tmp, e->scan_bytes, e->size, e->tile_off, (size_t)tiles + 1, st));
     hipLaunchKernelGGL(gt_emit, dim3((uint32_t)blocks), dim3(THREADS), 0, st, e->payload, e->tok, e->codes, e->header, e->header_bits,
                        e->block_off, e->tile_off, e->state, e->size, blocks, o.out, (unsigned long long)out_bytes);
     OCHIP_TRY(launched(ctx, "gt_emit"));
@@ -653,11 +398,8 @@ int ochip_geotiff_create(ochip_ctx *ctx, int kind, int64_t width, int64_t height
     const size_t tiles = (size_t)e->tiles_x, blocks = tiles * SEGMENTS;
     e->slot_cap = tiles * TILE_SLOT;
     size_t a = 0, b = 0;
-    unsigned long long *none = nullptr;
-    OCHIP_HIP(ctx, rocprim::exclusive_scan(nullptr, a, rocprim::make_transform_iterator((uint32_t *)nullptr, widen()), none, 0ull, blocks + 1,
-                                           rocprim::plus<unsigned long long>(), (hipStream_t)ctx->stream));
-    OCHIP_HIP(ctx, rocprim::exclusive_scan(nullptr, b, rocprim::make_transform_iterator((uint32_t *)nullptr, widen()), none, 0ull, tiles + 1,
-                                           rocprim::plus<unsigned long long>(), (hipStream_t)ctx->stream));
+    OCHIP_HIP(ctx, scan_offsets(nullptr, a, nullptr, nullptr, blocks + 1, ctx->stream));
+    OCHIP_HIP(ctx, scan_offsets(nullptr, b, nullptr, nullptr, tiles + 1, ctx->stream));
     e->scan_bytes = (a > b ? a : b) + 256;
     int rc = e->mem.alloc(&e->rows, (size_t)TILE * (size_t)width);
     if (rc == OCHIP_OK)

@@ -92,7 +92,7 @@ void encode_batch(const ochip_png_image *images, const std::vector<shape> &shape
     {
         const size_t i = owner(seg_base, (uint64_t)u);
         const uint32_t k = (uint32_t)((uint64_t)u - seg_base[i]);
-        segment_block(payload[i].data(), shapes[i], k, marks[i].data(), blocks[i][k]);
+        segment_block(payload[i].data(), shapes[i].F, k, shapes[i].dist_left(), shapes[i].dist_up(), marks[i].data(), blocks[i][k]);
     }
     files.resize(n);
 #pragma omp parallel for schedule(dynamic)

@@ -1,16 +1,16 @@
-// PNG files of a batch of images on the device (the rules: png_rules.hpp).  One call is one set of
-// launches on the context's stream, whatever the images' number and sizes: the host lays the images' rows, 16 384-byte
-// segments and output pieces end to end (prefix sums over the batch) and every kernel finds its image by bisection, so a
-// thousand thumbnails and one large preview fill the device the same way.
+// PNG files of a batch of images on the device (the rules: png_rules.hpp, the DEFLATE encoder's kernel
+// bodies: deflate_kernels.hpp).  One call is one set of launches on the context's stream, whatever the images' number and
+// sizes: the host lays the images' rows, 16 384-byte segments and output pieces end to end (prefix sums over the batch) and
+// every kernel finds its image by bisection, so a thousand thumbnails and one large preview fill the device the same way.
 //   png_filter       a wave per row: the five filters' sums by wave reduction, the type byte and the chosen row into the payload
-//   png_parse        a workgroup per segment, 64 bytes a lane: gt_parse's chunked walk with runtime distances - the byte bpp to
-//                    the left out of the lane's own words, the byte a stride above out of aligned words shifted into place -
-//                    and a partial last segment; the segment's Adler-32 partial
-//   png_codes        a wave per block: build_block in LDS, on one lane
+//   png_parse        a workgroup per segment, 64 bytes a lane: the lane's two masks at runtime distances - the byte
+//                    bpp to the left out of the lane's own words, the byte a stride above out of aligned words shifted into
+//                    place - with a partial last segment, then parse_segment, the walk the GeoTIFF tiles take
+//   png_codes        a wave per block: codes_block
 //   (rocPRIM)        exclusive scan of the blocks' bits
 //   png_sizes        a lane an image: deflated or stored, the Adler-32 from the partials, 78 9C and the Adler-32 of a deflated one
 //   (rocPRIM)        exclusive scan of the files' (or their base64's) sizes: where each lies in the output
-//   png_emit         a workgroup per block of a deflated image, as gt_emit
+//   png_emit         a workgroup per block of a deflated image: emit_segment into the image's stream
 //   png_stored       the stored form of the images that did not shrink
 //   png_crc_pieces   a lane per 4 096 bytes of a stream: its CRC-32
 //   png_crc_combine  a workgroup an image: runs of pieces, then pairs of runs, behind "IDAT" by the x^(8 len) mod P rule
@@ -18,11 +18,8 @@
 //                    into a buffer of the files at their bounds
 //   png_base64       a lane per 12 input bytes, into the output
 // and two copies: the offsets, then as many bytes as they say.  Steps that depend on each other are separate launches.
-#include "ctx.hpp"
+#include "deflate_kernels.hpp"
 #include "png_rules.hpp"
-
-#include <rocprim/device/device_scan.hpp>
-#include <rocprim/iterator/transform_iterator.hpp>
 
 #include <memory>
 #include <mutex>
@@ -33,10 +30,9 @@ namespace
 {
 
 using namespace ochip_png;
+using namespace ochip_dfk;
 
-constexpr int THREADS = 256, CHUNK = SEGMENT / THREADS; // a lane's 64 bytes of a segment
 constexpr uint32_t B64_UNIT = 3072; // input bytes a workgroup of png_base64 turns into 4 096 characters
-static_assert(CHUNK == 64, "a lane's bytes are the bits of one 64-bit mask");
 static_assert(CRC_PIECE == THREADS * 16, "png_file moves a piece as 16 bytes a lane");
 static_assert(B64_UNIT == THREADS * 12, "png_base64 takes 4 groups of 3 bytes a lane");
 
@@ -115,46 +111,27 @@ __global__ __launch_bounds__(THREADS) void png_filter(const img_desc *descs, con
     }
 }
 
-__device__ int ones_from(uint64_t m, int j) // the run of set bits of m from bit j upwards, at most 64 - j
+// the lane's count of real bytes in segment [lo, hi)
+__device__ __forceinline__ int valid_of(uint32_t lo, uint32_t hi)
 {
-    const uint64_t x = ~(m >> j);
-    return x ? __builtin_ctzll(x) : 64;
-}
-
-// the bits of `m` whose byte of `x` is zero, at bit positions j0 .. j0 + 3
-__device__ uint64_t zero_bytes(uint32_t x, int j0)
-{
-    uint64_t m = 0;
-#pragma unroll
-    for (int y = 0; y < 4; y++)
-        if (((x >> (8 * y)) & 255u) == 0)
-            m |= 1ull << (j0 + y);
-    return m;
+    const uint32_t P0 = lo + threadIdx.x * CHUNK;
+    return P0 >= hi ? 0 : hi - P0 < (uint32_t)CHUNK ? (int)(hi - P0) : CHUNK;
 }
 
 __global__ __launch_bounds__(THREADS) void png_parse(const img_desc *descs, const uint32_t *seg_base, int n, uint32_t blocks, const uint8_t *payload,
                                                       uint16_t *tok, uint32_t *counts, uint32_t *seg_adler)
 {
-    constexpr uint16_t MARK_OVER = 0x200; // a mark's spare bit, inside this kernel only
-    constexpr int NOT_ENTERED = CHUNK;    // the walk jumps over the chunk
-    __shared__ uint16_t best[SEGMENT];
-    __shared__ uint8_t leave[SEGMENT];
-    __shared__ uint8_t entry[THREADS];
-    __shared__ uint16_t head[2][THREADS];
-    __shared__ uint32_t cnt[NUM_SYMS];
-    __shared__ uint32_t ad1[THREADS], ad2[THREADS];
     const uint32_t b = blockIdx.x;
-    const int t = threadIdx.x;
     if (b >= blocks)
         return;
     const int img = owner_of(seg_base, n, b);
-    const uint32_t seg = b - seg_base[img];
     const uint32_t F = descs[img].F, dl = descs[img].c, du = descs[img].stride;
     const bool use_up = du <= UP_LIMIT;
     const uint8_t *a = payload + descs[img].pay_off;
-    const uint32_t lo = seg * (uint32_t)SEGMENT, hi = F - lo < (uint32_t)SEGMENT ? F : lo + (uint32_t)SEGMENT;
-    const uint32_t P0 = lo + (uint32_t)t * CHUNK;
-    const int valid = P0 >= hi ? 0 : hi - P0 < (uint32_t)CHUNK ? (int)(hi - P0) : CHUNK;
+    const uint32_t lo = (b - seg_base[img]) * (uint32_t)SEGMENT, hi = F - lo < (uint32_t)SEGMENT ? F : lo + (uint32_t)SEGMENT;
+    const uint32_t P0 = lo + threadIdx.x * CHUNK;
+    const int valid = valid_of(lo, hi);
+    // the lane's two masks at runtime distances, over the `valid` real bytes of its chunk
     uint64_t m_left = 0, m_up = 0;
     uint32_t s1 = 0, s2 = 0;
     if (valid > 0)
@@ -220,127 +197,19 @@ __global__ __launch_bounds__(THREADS) void png_parse(const img_desc *descs, cons
                 s1 += byte, s2 += (uint32_t)(valid - j) * byte; // byte = 0 where valid - j would be negative
             }
     }
-    head[0][t] = (uint16_t)ones_from(m_left, 0), head[1][t] = (uint16_t)ones_from(m_up, 0);
-    ad1[t] = 1 + s1, ad2[t] = ((uint32_t)valid + s2) % ADLER_MOD;
-    for (int i = t; i < NUM_SYMS; i += THREADS)
-        cnt[i] = 0;
-    __syncthreads();
-    // how far a run that reaches this chunk's end goes on in the chunks behind, the segment's end the limit
-    int more_l = 0, more_u = 0;
-    for (int k = t + 1; k < THREADS; k++)
-    {
-        const int h = head[0][k];
-        more_l += h;
-        if (h < CHUNK || more_l >= MAX_MATCH)
-            break;
-    }
-    for (int k = t + 1; k < THREADS; k++)
-    {
-        const int h = head[1][k];
-        more_u += h;
-        if (h < CHUNK || more_u >= MAX_MATCH)
-            break;
-    }
-    for (int j = 0; j < CHUNK; j++)
-    {
-        int rl = ones_from(m_left, j), ru = ones_from(m_up, j);
-        if (rl == CHUNK - j)
-            rl += more_l;
-        if (ru == CHUNK - j)
-            ru += more_u;
-        best[t * CHUNK + j] = choose_match(rl, ru);
-    }
-    // The greedy parse is a walk from the segment's start (geotiff.hip, gt_parse): where a walk entering the chunk at each of
-    // its positions leaves it, one lane's hops from chunk to chunk, then every entered chunk marks and counts its tokens.
-    for (int e = CHUNK - 1; e >= 0; e--)
-    {
-        const uint16_t m = best[t * CHUNK + e];
-        const int len = m & MARK_LEN, nx = e + (len ? len : 1);
-        int over;
-        if (nx >= CHUNK)
-            over = nx - CHUNK;
-        else
-            over = leave[t * CHUNK + nx] | ((best[t * CHUNK + nx] & MARK_OVER) ? 256 : 0);
-        leave[t * CHUNK + e] = (uint8_t)over;
-        if (over & 256)
-            best[t * CHUNK + e] = m | MARK_OVER;
-    }
-    entry[t] = NOT_ENTERED;
-    __syncthreads();
-    if (t == 0)
-    {
-        for (int c = 0, e = 0; c < THREADS;)
-        {
-            entry[c] = (uint8_t)e;
-            const int at = c * CHUNK + e;
-            const int next = (c + 1) * CHUNK + (leave[at] | ((best[at] & MARK_OVER) ? 256 : 0));
-            c = next / CHUNK, e = next % CHUNK;
-        }
-    }
-    else if (t == 64)
-    {
-        uint32_t a1 = ad1[0], a2 = ad2[0];
-        for (int k = 1; k < THREADS; k++)
-        {
-            const uint32_t at = lo + (uint32_t)k * CHUNK;
-            const uint32_t len = at >= hi ? 0 : hi - at < (uint32_t)CHUNK ? hi - at : (uint32_t)CHUNK;
-            adler_combine(a1, a2, ad1[k], ad2[k], len);
-        }
-        seg_adler[2 * (size_t)b] = a1, seg_adler[2 * (size_t)b + 1] = a2;
-    }
-    __syncthreads();
-    // the tokens of this lane's chunk, if the walk enters it: marked and counted in one pass.  No match reaches beyond the
-    // segment's end, so the walk steps over the bytes behind it one by one and nothing there is marked.
-    for (int j = entry[t]; j < valid;)
-    {
-        const uint16_t m = best[t * CHUNK + j];
-        best[t * CHUNK + j] = m | MARK_START;
-        int ds;
-        const int ls = token_symbols_at(m, a[P0 + j], ds, (int)dl, (int)du);
-        atomicAdd(&cnt[ls], 1u);
-        if (ds >= 0)
-            atomicAdd(&cnt[NUM_LIT + ds], 1u);
-        const int len = m & MARK_LEN;
-        j += len ? len : 1;
-    }
-    __syncthreads();
-    uint16_t *out = tok + descs[img].pay_off + lo;
-    for (uint32_t i = t; i < hi - lo; i += THREADS)
-        out[i] = best[i] & (uint16_t)~MARK_OVER;
-    for (int i = t; i < NUM_SYMS; i += THREADS)
-        counts[(size_t)b * NUM_SYMS + i] = cnt[i];
+    parse_segment(m_left, m_up, s1, s2, valid, a, lo, hi - lo, (int)dl, (int)du, tok + descs[img].pay_off, counts + (size_t)b * NUM_SYMS,
+                  seg_adler + 2 * (size_t)b);
 }
 
 __global__ __launch_bounds__(64) void png_codes(const img_desc *descs, const uint32_t *seg_base, int n, uint32_t blocks, const uint32_t *counts,
                                                  uint32_t *codes, uint32_t *header, uint32_t *header_bits, uint32_t *block_bits)
 {
-    __shared__ block_work W;
-    __shared__ uint32_t c[NUM_SYMS];
-    __shared__ uint32_t h[HEADER_WORDS];
-    __shared__ uint32_t hb;
     const uint32_t b = blockIdx.x;
-    const int t = threadIdx.x;
     if (b >= blocks)
         return;
-    for (int i = t; i < NUM_SYMS; i += 64)
-        W.counts[i] = counts[(size_t)b * NUM_SYMS + i];
-    for (int i = t; i < HEADER_WORDS; i += 64)
-        h[i] = 0;
-    __syncthreads();
-    if (t == 0)
-    {
-        const int img = owner_of(seg_base, n, b);
-        uint32_t bits_of_header = 0;
-        block_bits[b] = build_block(W, b - seg_base[img] + 1 == descs[img].segs, c, h, bits_of_header);
-        hb = bits_of_header;
-    }
-    __syncthreads();
-    for (int i = t; i < NUM_SYMS; i += 64)
-        codes[(size_t)b * NUM_SYMS + i] = c[i];
-    for (int i = t; i < HEADER_WORDS; i += 64)
-        header[(size_t)b * HEADER_WORDS + i] = h[i];
-    if (t == 0)
-        header_bits[b] = hb;
+    const int img = owner_of(seg_base, n, b);
+    codes_block(counts + (size_t)b * NUM_SYMS, b - seg_base[img] + 1 == descs[img].segs, codes + (size_t)b * NUM_SYMS,
+                header + (size_t)b * HEADER_WORDS, header_bits + b, block_bits + b);
 }
 
 // state: 0 deflated, 1 stored; zlen: the stream's bytes; osize: the file's bytes, or its base64's; osize[n] = 0 so that the
@@ -364,13 +233,7 @@ __global__ __launch_bounds__(THREADS) void png_sizes(const img_desc *descs, cons
     state[i] = deflated ? 0 : 1, zlen[i] = z;
     const unsigned long long file = (unsigned long long)z + FILE_EXTRA;
     osize[i] = (uint32_t)(base64 ? base64_bytes(file) : file);
-    uint32_t a1 = 1, a2 = 0;
-    for (uint32_t k = 0; k < segs; k++)
-    {
-        const uint32_t at = k * (uint32_t)SEGMENT, len = F - at < (uint32_t)SEGMENT ? F - at : (uint32_t)SEGMENT;
-        adler_combine(a1, a2, seg_adler[2 * (size_t)(s0 + k)], seg_adler[2 * (size_t)(s0 + k) + 1], len);
-    }
-    const uint32_t ad = a2 << 16 | a1;
+    const uint32_t ad = stream_adler(seg_adler + 2 * (size_t)s0, F);
     adler[i] = ad;
     if (deflated)
     {
@@ -380,116 +243,24 @@ __global__ __launch_bounds__(THREADS) void png_sizes(const img_desc *descs, cons
     }
 }
 
-// Bits LSB first from bit `pos` of a stream's words.  A word this lane fills alone is stored; the first word when the lane
-// starts inside it and the last partial one are ORed into the zeroed buffer.  Nothing is written at or beyond cap.
-struct stream_writer
-{
-    uint32_t *words;
-    uint32_t cap, wi;
-    uint64_t acc;
-    int n;
-    bool shared_first;
-    __device__ void put(uint32_t v, int len) // len <= 24
-    {
-        acc |= (uint64_t)v << n, n += len;
-        if (n >= 32)
-        {
-            if (wi < cap)
-            {
-                if (shared_first)
-                    atomicOr(&words[wi], (uint32_t)acc);
-                else
-                    words[wi] = (uint32_t)acc;
-            }
-            shared_first = false;
-            wi++, n -= 32, acc >>= 32;
-        }
-    }
-    __device__ void flush()
-    {
-        if (n > 0 && wi < cap)
-            atomicOr(&words[wi], (uint32_t)acc);
-    }
-};
-
 __global__ __launch_bounds__(THREADS) void png_emit(const img_desc *descs, const uint32_t *seg_base, int n, uint32_t blocks, const uint8_t *payload,
                                                      const uint16_t *tok, const uint32_t *codes, const uint32_t *header, const uint32_t *header_bits,
                                                      const unsigned long long *block_off, const uint32_t *state, const uint32_t *zlen,
                                                      uint8_t *zbuf)
 {
-    __shared__ uint32_t c[NUM_SYMS];
-    __shared__ uint32_t sc[THREADS];
     const uint32_t b = blockIdx.x;
-    const int t = threadIdx.x;
     if (b >= blocks)
         return;
     const int img = owner_of(seg_base, n, b);
     if (state[img] != 0)
         return;
-    const uint32_t seg = b - seg_base[img], F = descs[img].F;
-    const int dl = (int)descs[img].c, du = (int)descs[img].stride;
-    for (int i = t; i < NUM_SYMS; i += THREADS)
-        c[i] = codes[(size_t)b * NUM_SYMS + i];
-    __syncthreads();
-    const uint32_t lo = seg * (uint32_t)SEGMENT, hi = F - lo < (uint32_t)SEGMENT ? F : lo + (uint32_t)SEGMENT;
-    const uint32_t P0 = lo + (uint32_t)t * CHUNK;
-    const int valid = P0 >= hi ? 0 : hi - P0 < (uint32_t)CHUNK ? (int)(hi - P0) : CHUNK;
-    const uint8_t *a = payload + descs[img].pay_off + P0;
-    const uint16_t *marks = tok + descs[img].pay_off + P0;
-    const uint32_t hbits = header_bits[b];
-    uint32_t bits = 0;
-    for (int j = 0; j < valid; j++)
-    {
-        const uint16_t m = marks[j];
-        if (m & MARK_START)
-        {
-            int k;
-            (void)token_bits_at(m, a[j], c, k, dl, du);
-            bits += (uint32_t)k;
-        }
-    }
-    if (t == 0)
-        bits += hbits;
-    if (t == THREADS - 1)
-        bits += c[EOB] >> 16;
-    sc[t] = bits;
-    __syncthreads();
-    for (int o = 1; o < THREADS; o <<= 1)
-    {
-        const uint32_t v = t >= o ? sc[t - o] : 0;
-        __syncthreads();
-        sc[t] += v;
-        __syncthreads();
-    }
-    const unsigned long long pos = 16 + (block_off[b] - block_off[seg_base[img]]) + (sc[t] - bits);
-    stream_writer w;
+    const uint32_t F = descs[img].F;
+    const uint32_t lo = (b - seg_base[img]) * (uint32_t)SEGMENT, hi = F - lo < (uint32_t)SEGMENT ? F : lo + (uint32_t)SEGMENT;
     // the words in front of the Adler-32's: the room is the stored form's, a deflated stream is shorter
-    w.words = reinterpret_cast<uint32_t *>(zbuf + descs[img].z_off), w.cap = (zlen[img] + 3) / 4 < descs[img].room / 4 ? (zlen[img] + 3) / 4 : descs[img].room / 4;
-    w.wi = (uint32_t)(pos >> 5), w.acc = 0, w.n = (int)(pos & 31), w.shared_first = w.n != 0;
-    if (t == 0)
-    {
-        const uint32_t *h = header + (size_t)b * HEADER_WORDS;
-        for (uint32_t at = 0; at < hbits && at < HEADER_WORDS * 32; at += 16)
-        {
-            const int k = hbits - at < 16 ? (int)(hbits - at) : 16;
-            w.put((h[at >> 5] >> (at & 31)) & ((1u << k) - 1), k);
-        }
-    }
-    for (int j = 0; j < valid; j++)
-    {
-        const uint16_t m = marks[j];
-        if (m & MARK_START)
-        {
-            int k;
-            const uint64_t v = token_bits_at(m, a[j], c, k, dl, du);
-            w.put((uint32_t)(v & 0xFFFFFF), k < 24 ? k : 24);
-            if (k > 24)
-                w.put((uint32_t)(v >> 24), k - 24);
-        }
-    }
-    if (t == THREADS - 1)
-        w.put(c[EOB] & 0xFFFF, (int)(c[EOB] >> 16));
-    w.flush();
+    const uint32_t cap = (zlen[img] + 3) / 4 < descs[img].room / 4 ? (zlen[img] + 3) / 4 : descs[img].room / 4;
+    emit_segment(payload + descs[img].pay_off + lo, tok + descs[img].pay_off + lo, valid_of(lo, hi), codes + (size_t)b * NUM_SYMS,
+                 header + (size_t)b * HEADER_WORDS, header_bits[b], reinterpret_cast<uint32_t *>(zbuf + descs[img].z_off), cap,
+                 16 + (block_off[b] - block_off[seg_base[img]]), (int)descs[img].c, (int)descs[img].stride);
 }
 
 // a workgroup per segment of a stored image: 4 096 words of its stream's room, the last segment's workgroup the rest as well
@@ -502,24 +273,12 @@ __global__ __launch_bounds__(THREADS) void png_stored(const img_desc *descs, con
     const int img = owner_of(seg_base, n, b);
     if (state[img] != 1)
         return;
-    const uint32_t seg = b - seg_base[img], F = descs[img].F, S = descs[img].S, words = descs[img].room / 4;
+    const uint32_t seg = b - seg_base[img], words = descs[img].room / 4;
     const uint32_t first = seg * (uint32_t)(SEGMENT / 4);
     const uint32_t end = seg + 1 == descs[img].segs ? words : (first + SEGMENT / 4 < words ? first + SEGMENT / 4 : words);
-    const uint8_t *a = payload + descs[img].pay_off;
     uint32_t *out = reinterpret_cast<uint32_t *>(zbuf + descs[img].z_off);
-    const uint32_t ad = adler[img];
     for (uint32_t wd = first + threadIdx.x; wd < end; wd += THREADS)
-    {
-        uint32_t word = 0;
-#pragma unroll
-        for (uint32_t k = 0; k < 4; k++)
-        {
-            const uint32_t o = wd * 4 + k;
-            if (o < S)
-                word |= (uint32_t)stored_byte_of(o, a, F, ad) << (8 * k);
-        }
-        out[wd] = word;
-    }
+        out[wd] = stored_word(wd, payload + descs[img].pay_off, descs[img].F, adler[img]);
 }
 
 __global__ __launch_bounds__(THREADS) void png_crc_pieces(const img_desc *descs, const uint32_t *piece_base, int n, uint32_t pieces,
@@ -645,26 +404,8 @@ __global__ __launch_bounds__(THREADS) void png_base64(const img_desc *descs, con
     }
 }
 
-struct widen
-{
-    __host__ __device__ unsigned long long operator()(uint32_t v) const
-    {
-        return v;
-    }
-};
-
 std::mutex g_live_mutex;
 std::set<const void *> g_live; // the encoders that exist: a destroyed handle is refused, not followed
-
-uint32_t blocks_of(size_t n)
-{
-    return (uint32_t)((n + THREADS - 1) / THREADS);
-}
-
-int launched(ochip_ctx *ctx, const char *what)
-{
-    return hipGetLastError() == hipSuccess ? OCHIP_OK : ochip_fail(ctx, OCHIP_EHIP, "%s launch failed", what);
-}
 
 // A device array of the encoder that only grows: a batch that needs more takes a new block a quarter larger
 struct grown
@@ -787,13 +528,8 @@ int ochip_png_encoder_encode(ochip_png_encoder *e, int64_t n64, const ochip_png_
     // ---- room: a batch that needs more of anything waits for the stream, hands every block back and takes new ones ----
     const size_t blocks = (size_t)segs;
     size_t scan_a = 0, scan_b = 0;
-    {
-        unsigned long long *none = nullptr;
-        OCHIP_HIP(ctx, rocprim::exclusive_scan(nullptr, scan_a, rocprim::make_transform_iterator((uint32_t *)nullptr, widen()), none, 0ull,
-                                               blocks + 1, rocprim::plus<unsigned long long>(), st));
-        OCHIP_HIP(ctx, rocprim::exclusive_scan(nullptr, scan_b, rocprim::make_transform_iterator((uint32_t *)nullptr, widen()), none, 0ull,
-                                               (size_t)n + 1, rocprim::plus<unsigned long long>(), st));
-    }
+    OCHIP_HIP(ctx, scan_offsets(nullptr, scan_a, nullptr, nullptr, blocks + 1, st));
+    OCHIP_HIP(ctx, scan_offsets(nullptr, scan_b, nullptr, nullptr, (size_t)n + 1, st));
     struct want
     {
         grown *g;
@@ -883,15 +619,11 @@ int ochip_png_encoder_encode(ochip_png_encoder *e, int64_t n64, const ochip_png_
     OCHIP_TRY(launched(ctx, "png_parse"));
     hipLaunchKernelGGL(png_codes, dim3(nb), dim3(64), 0, st, d_descs, d_segs, n, nb, counts, codes, header, header_bits, block_bits);
     OCHIP_TRY(launched(ctx, "png_codes"));
-    size_t tmp = e->scan_tmp.bytes;
-    auto bits64 = rocprim::make_transform_iterator(block_bits, widen());
-    OCHIP_HIP(ctx, rocprim::exclusive_scan(e->scan_tmp.p, tmp, bits64, block_off, 0ull, blocks + 1, rocprim::plus<unsigned long long>(), st));
+    OCHIP_TRY(scan_offsets(ctx, "ochip_png_encoder_encode", e->scan_tmp.p, e->scan_tmp.bytes, block_bits, block_off, blocks + 1, st));
     hipLaunchKernelGGL(png_sizes, dim3(blocks_of((size_t)n + 1)), dim3(THREADS), 0, st, d_descs, d_segs, n, block_off, seg_adler, base64 ? 1 : 0, state,
                        zlen, osize, adler, zbuf);
     OCHIP_TRY(launched(ctx, "png_sizes"));
-    tmp = e->scan_tmp.bytes;
-    auto size64 = rocprim::make_transform_iterator(osize, widen());
-    OCHIP_HIP(ctx, rocprim::exclusive_scan(e->scan_tmp.p, tmp, size64, out_off, 0ull, (size_t)n + 1, rocprim::plus<unsigned long long>(), st));
+    OCHIP_TRY(scan_offsets(ctx, "ochip_png_encoder_encode", e->scan_tmp.p, e->scan_tmp.bytes, osize, out_off, (size_t)n + 1, st));
     hipLaunchKernelGGL(png_emit, dim3(nb), dim3(THREADS), 0, st, d_descs, d_segs, n, nb, payload, tok, codes, header, header_bits, block_off, state, zlen,
                        zbuf);
     OCHIP_TRY(launched(ctx, "png_emit"));

@@ -1,10 +1,10 @@
 // The PNG files of the thumbnails and previews (the reference's cv::imencode(".png") of a node's
 // thumbnail, src/io/serialize_MeasurementGraph.cpp:260-267, src/ortho/thumbnail_encode.hpp and the runner's thumb.png).  This
-// header is the rules for both routes: the row filters and their choice, the payload, the match candidates at runtime
-// distances, the block coder of deflate_rules.hpp around them, the stored fallback, the CRC-32 with its combination, the chunk
-// layout and base64.  csrc/png.hip runs them in kernels, host/png.cpp in loops; it includes nothing of either, so a
-// stand-alone program builds from it.  Any valid file that decodes to the pixels is correct; the two routes give the same
-// bytes because every decision below is a function of the pixels alone.
+// header is what is PNG in both routes: the row filters and their choice, the payload, the CRC-32 with its combination, the
+// chunk layout and base64.  The IDAT body is deflate_rules.hpp's zlib stream of the payload, the candidates the byte bpp to
+// the left and - up to a stride of 32 768 - the byte above.  csrc/png.hip runs the rules in kernels, host/png.cpp in loops; the
+// header includes nothing of either, so a stand-alone program builds from it.  Any valid file that decodes to the pixels is
+// correct; the two routes give the same bytes because every decision is a function of the pixels alone.
 #pragma once
 
 #include "deflate_rules.hpp"
@@ -37,17 +37,6 @@ OCHIP_DF_HD constexpr uint64_t payload_bytes(uint64_t w, uint64_t h, uint64_t c)
     return h * stride_of(w, c);
 }
 
-OCHIP_DF_HD constexpr uint64_t segments_of(uint64_t F)
-{
-    return (F + SEGMENT - 1) / SEGMENT;
-}
-
-// The stored form: 78 9C, ceil(F / 65 535) stored blocks of 5 bytes of header each, the Adler-32
-OCHIP_DF_HD constexpr uint64_t stored_bytes(uint64_t F)
-{
-    return 2 + F + 5 * ((F + STORED_BLOCK - 1) / STORED_BLOCK) + 4;
-}
-
 // The bound every buffer is sized from: the whole file around the stored form.  A deflated stream is taken only where it is
 // smaller than the stored one, so no file is larger.
 OCHIP_DF_HD constexpr uint64_t file_bound(uint64_t F)
@@ -60,18 +49,10 @@ OCHIP_DF_HD constexpr uint64_t base64_bytes(uint64_t n)
     return (n + 2) / 3 * 4;
 }
 
-static_assert(stored_bytes(1) == 12 && stored_bytes(65535) == 65535 + 11 && stored_bytes(65536) == 65536 + 16, "the stored form");
 static_assert(file_bound(16384) == 16384 + 11 + 57 && file_bound(300 * 301) == 300 * 301 + 2 + 10 + 4 + 57, "the file's bound");
 static_assert(FILE_EXTRA == 8 + 25 + 12 + 12 && IDAT_AT == 8 + 25 + 8, "the chunk layout");
 static_assert(base64_bytes(1) == 4 && base64_bytes(3) == 4 && base64_bytes(4) == 8, "base64 with padding");
 static_assert(payload_bytes(MAX_SIDE, MAX_SIDE, 4) < (1ull << 35), "sizes are 64-bit; a payload from 2^31 on is refused");
-
-// The largest stream a deflated image may have and still be taken: one byte below the stored form
-OCHIP_DF_HD bool takes_deflated(uint64_t stream_bits, uint64_t F, uint64_t &bytes)
-{
-    bytes = 2 + (stream_bits + 7) / 8 + 4;
-    return bytes < stored_bytes(F);
-}
 
 // ---- the row filters ----------------------------------------------------------------------------------------------------------
 // Byte x of raster row y as the file holds it: channels 0 and 2 exchanged first where swap_rb asks (c >= 3)
@@ -110,53 +91,6 @@ OCHIP_DF_HD int choose_filter(const uint64_t *sums)
         if (sums[t] < sums[best])
             best = t;
     return best;
-}
-
-// ---- tokens at runtime distances ------------------------------------------------------------------------------------------
-OCHIP_DF_HD uint64_t token_bits_at(uint16_t mark, uint8_t byte, const uint32_t *codes, int &n, int dist_left, int dist_up)
-{
-    const int len = mark & MARK_LEN;
-    if (len == 0)
-    {
-        const uint32_t c = codes[byte];
-        n = (int)(c >> 16);
-        return c & 0xFFFF;
-    }
-    int eb, ev, db, dv;
-    const uint32_t lc = codes[length_symbol(len, eb, ev)];
-    const uint32_t dc = codes[NUM_LIT + distance_symbol((mark & MARK_UP) ? dist_up : dist_left, db, dv)];
-    uint64_t v = lc & 0xFFFF;
-    n = (int)(lc >> 16);
-    v |= (uint64_t)ev << n, n += eb;
-    v |= (uint64_t)(dc & 0xFFFF) << n, n += (int)(dc >> 16);
-    v |= (uint64_t)dv << n, n += db;
-    return v;
-}
-
-OCHIP_DF_HD int token_symbols_at(uint16_t mark, uint8_t byte, int &dist_sym, int dist_left, int dist_up)
-{
-    const int len = mark & MARK_LEN;
-    dist_sym = -1;
-    if (len == 0)
-        return byte;
-    int eb, ev;
-    dist_sym = distance_symbol((mark & MARK_UP) ? dist_up : dist_left, eb, ev);
-    return length_symbol(len, eb, ev);
-}
-
-// Byte o of the stored form of a payload of F bytes whose Adler-32 is `adler`; o < stored_bytes(F)
-OCHIP_DF_HD uint8_t stored_byte_of(uint64_t o, const uint8_t *payload, uint64_t F, uint32_t adler)
-{
-    const uint64_t S = stored_bytes(F), blocks = (F + STORED_BLOCK - 1) / STORED_BLOCK;
-    if (o < 2)
-        return o == 0 ? 0x78 : 0x9C;
-    if (o >= S - 4)
-        return (uint8_t)(adler >> (8 * (S - 1 - o)));
-    const uint64_t k = (o - 2) / (STORED_BLOCK + 5), r = (o - 2) % (STORED_BLOCK + 5);
-    if (r >= 5)
-        return payload[k * STORED_BLOCK + (r - 5)];
-    const uint32_t len = k + 1 < blocks ? (uint32_t)STORED_BLOCK : (uint32_t)(F - k * STORED_BLOCK);
-    return r == 0 ? (k + 1 == blocks ? 1 : 0) : r == 1 ? (uint8_t)len : r == 2 ? (uint8_t)(len >> 8) : r == 3 ? (uint8_t)~len : (uint8_t)(~len >> 8);
 }
 
 // ---- CRC-32 (reflected, polynomial 0xEDB88320) ------------------------------------------------------------------------------
@@ -266,6 +200,15 @@ struct shape
     uint32_t w = 0, h = 0, c = 0, stride = 0, segs = 0;
     bool swap_rb = false;
     uint64_t F = 0, S = 0;
+    // the stream's match candidates: a pixel to the left, and the byte above where deflate's window reaches it
+    int dist_left() const
+    {
+        return (int)c;
+    }
+    int dist_up() const
+    {
+        return stride <= UP_LIMIT ? (int)stride : NO_UP;
+    }
 };
 
 // false: not 1 .. 65 535 squared of 1, 3 or 4 channels, or the stored form would reach 2^31 bytes
@@ -310,78 +253,6 @@ inline void filter_row(const uint8_t *pixels, const shape &s, uint32_t y, uint8_
     }
 }
 
-struct block_out
-{
-    uint32_t codes[NUM_SYMS];
-    uint32_t header[HEADER_WORDS];
-    uint32_t header_bits = 0, bits = 0;
-};
-
-// One segment of a payload: the candidate runs backwards from its end, the greedy parse from its start, the block's codes
-inline void segment_block(const uint8_t *a, const shape &s, uint32_t seg, uint16_t *marks, block_out &B)
-{
-    const int64_t lo = (int64_t)seg * SEGMENT, hi = lo + SEGMENT < (int64_t)s.F ? lo + SEGMENT : (int64_t)s.F;
-    const int64_t dl = s.c, du = s.stride;
-    const bool use_up = s.stride <= UP_LIMIT;
-    int left = 0, up = 0;
-    for (int64_t p = hi - 1; p >= lo; p--)
-    {
-        left = p >= dl && a[p] == a[p - dl] ? left + 1 : 0;
-        up = use_up && p >= du && a[p] == a[p - du] ? up + 1 : 0;
-        marks[p] = choose_match(left, up);
-    }
-    block_work W;
-    std::memset(W.counts, 0, sizeof W.counts);
-    for (int64_t p = lo; p < hi;)
-    {
-        marks[p] |= MARK_START;
-        int ds;
-        W.counts[token_symbols_at(marks[p], a[p], ds, (int)dl, (int)du)]++;
-        if (ds >= 0)
-            W.counts[NUM_LIT + ds]++;
-        const int len = marks[p] & MARK_LEN;
-        p += len ? len : 1;
-    }
-    std::memset(B.header, 0, sizeof B.header);
-    B.bits = build_block(W, seg + 1 == s.segs, B.codes, B.header, B.header_bits);
-}
-
-// Bits LSB first into zeroed bytes, the position 64-bit
-struct bit_sink
-{
-    uint8_t *bytes;
-    uint64_t cap_bits, bits;
-    void put(uint64_t v, int n) // n <= 48
-    {
-        if (n <= 0 || bits + (uint64_t)n > cap_bits)
-            return;
-        uint64_t at = bits >> 3;
-        const int s = (int)(bits & 7);
-        bits += (uint64_t)n;
-        unsigned __int128 w = (unsigned __int128)v << s;
-        for (int left = n + s; left > 0; left -= 8, w >>= 8)
-            bytes[at++] |= (uint8_t)w;
-    }
-};
-
-inline void emit_segment(bit_sink &w, const uint8_t *a, const shape &s, uint32_t seg, const uint16_t *marks, const block_out &B)
-{
-    const int64_t lo = (int64_t)seg * SEGMENT, hi = lo + SEGMENT < (int64_t)s.F ? lo + SEGMENT : (int64_t)s.F;
-    for (uint32_t b = 0; b < B.header_bits; b += 16)
-    {
-        const int n = B.header_bits - b < 16 ? (int)(B.header_bits - b) : 16;
-        w.put((B.header[b >> 5] >> (b & 31)) & ((1u << n) - 1), n);
-    }
-    for (int64_t p = lo; p < hi; p++)
-        if (marks[p] & MARK_START)
-        {
-            int n;
-            const uint64_t v = token_bits_at(marks[p], a[p], B.codes, n, (int)s.c, (int)s.stride);
-            w.put(v, n);
-        }
-    w.put(B.codes[EOB] & 0xFFFF, (int)(B.codes[EOB] >> 16));
-}
-
 inline const uint32_t *crc_table()
 {
     static const struct table
@@ -418,38 +289,14 @@ inline uint32_t idat_crc(const uint8_t *stream, uint64_t n)
     return crc;
 }
 
-// The file of a payload whose segments are marked and coded; out is cleared first
+// The file of a payload whose segments are marked and coded (deflate_rules.hpp's segment_block); out is cleared first
 inline void assemble_file(const uint8_t *a, const shape &s, const uint16_t *marks, const block_out *blocks, std::vector<uint8_t> &out)
 {
-    uint64_t bits = 0;
-    for (uint32_t k = 0; k < s.segs; k++)
-        bits += blocks[k].bits;
-    uint64_t zlen = 0;
-    const bool deflated = takes_deflated(bits, s.F, zlen);
-    if (!deflated)
-        zlen = s.S;
-    // the Adler-32 from the segments' partials, as the device combines them
-    uint32_t a1 = 1, a2 = 0;
-    for (uint32_t k = 0; k < s.segs; k++)
-    {
-        const uint64_t lo = (uint64_t)k * SEGMENT, n = s.F - lo < (uint64_t)SEGMENT ? s.F - lo : (uint64_t)SEGMENT;
-        const uint32_t ad = adler32(a + lo, (size_t)n);
-        adler_combine(a1, a2, ad & 0xFFFF, ad >> 16, (uint32_t)n);
-    }
-    const uint32_t adler = a2 << 16 | a1;
+    bool deflated = false;
+    const uint64_t zlen = stream_bytes(blocks, s.F, deflated);
     out.assign((size_t)(zlen + FILE_EXTRA), 0);
     uint8_t *z = out.data() + IDAT_AT;
-    if (deflated)
-    {
-        z[0] = 0x78, z[1] = 0x9C;
-        bit_sink w{z, (zlen - 4) * 8, 16};
-        for (uint32_t k = 0; k < s.segs; k++)
-            emit_segment(w, a, s, k, marks, blocks[k]);
-        put_be32(z + zlen - 4, adler);
-    }
-    else
-        for (uint64_t o = 0; o < zlen; o++)
-            z[o] = stored_byte_of(o, a, s.F, adler);
+    write_stream(a, s.F, s.dist_left(), s.dist_up(), marks, blocks, deflated, zlen, z);
     file_head(s.w, s.h, s.c, (uint32_t)zlen, out.data());
     file_tail(idat_crc(z, zlen), z + zlen);
 }
@@ -463,7 +310,7 @@ inline void encode_image(const uint8_t *pixels, const shape &s, std::vector<uint
     std::vector<uint16_t> marks((size_t)s.F);
     std::vector<block_out> blocks(s.segs);
     for (uint32_t k = 0; k < s.segs; k++)
-        segment_block(payload.data(), s, k, marks.data(), blocks[k]);
+        segment_block(payload.data(), s.F, k, s.dist_left(), s.dist_up(), marks.data(), blocks[k]);
     assemble_file(payload.data(), s, marks.data(), blocks.data(), out);
     if (payload_out)
         payload_out->swap(payload);
