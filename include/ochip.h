@@ -310,6 +310,15 @@ extern "C"
     int ochip_debug_homography_fit4(ochip_ctx *ctx, int route, const double *xy16, uint32_t n, double *H9, double *Hinv9,
                                     uint8_t *degenerate);
 
+    /* Test seam: decompose_vote_kernel, launched as ochip_ransac_homography_batch_sorted launches it, on homographies the
+     * caller gives instead of the RANSAC kernel's results.  jobs / matches / inliers as for ochip_ransac_homography_batch
+     * (rng_state and eval_offset unused); H9: n_jobs x 9 row-major; the rays are the device's image_to_3d of the uploaded
+     * keypoints and models (ochip_upload_keypoints / ochip_upload_batch).  decomp_out: one ochip_decomposition per job.
+     * Refuses NULL arguments, jobs whose images, offsets or keypoint indices exceed the upload.  Leaves the RANSAC scratch
+     * (what ochip_edge_lists reads) alone. */
+    int ochip_debug_decompose_votes(ochip_ctx *ctx, const ochip_ransac_job *jobs, uint32_t n_jobs, const ochip_ransac_match *matches,
+                                    uint64_t total_matches, const double *H9, const uint8_t *inliers, ochip_decomposition *decomp_out);
+
     /* ---- relax: ground-plane bundle adjustment (replaces ceres::Solver::Solve on the problem
      *      RelaxProblem::setupGroundPlaneProblem builds, src/relax/relax_problem.cpp:61-81,1390-1420) ---- */
     typedef struct ochip_relax_problem ochip_relax_problem;

@@ -18,6 +18,7 @@ RANSAC_JOB_DTYPE = np.dtype([("image_1", np.uint32), ("image_2", np.uint32), ("n
 RANSAC_MATCH_DTYPE = np.dtype([("k1", np.uint32), ("k2", np.uint32), ("count", np.uint16), ("reserved", np.uint16)])
 RANSAC_RESULT_DTYPE = np.dtype([("H", np.float64, (9,)), ("score", np.float64), ("iterations", np.uint32), ("n_inliers", np.uint32),
                                 ("improvements", np.uint32), ("reserved", np.uint32)])
+DECOMPOSITION_DTYPE = np.dtype([("pose", np.float64, (4, 8)), ("can_decompose", np.uint32), ("n_inliers", np.uint32)])
 
 # every symbol include/ochip.h declares; tests check that the built library exports all of them
 EXPORTS = [
@@ -36,7 +37,7 @@ EXPORTS = [
     "ochip_relaxp_problem_create", "ochip_relaxp_problem_destroy", "ochip_relaxp_set_structure_only", "ochip_relaxp_solve",
     "ochip_relaxp_get_state", "ochip_relaxp_evaluate", "ochip_relaxp_step",
     "ochip_profile_reset", "ochip_profile_get", "ochip_match_work", "ochip_relax_work", "ochip_relax_memory", "ochip_work_counters",
-    "ochip_debug_fp64", "ochip_debug_std_sort", "ochip_debug_lm_step", "ochip_debug_homography_fit4", "ochip_match_sort", "ochip_ransac_homography_batch_sorted", "ochip_edge_lists",
+    "ochip_debug_fp64", "ochip_debug_std_sort", "ochip_debug_lm_step", "ochip_debug_homography_fit4", "ochip_debug_decompose_votes", "ochip_match_sort", "ochip_ransac_homography_batch_sorted", "ochip_edge_lists",
     "ochip_dense_index_create", "ochip_dense_index_destroy", "ochip_dense_match", "ochip_dense_link", "ochip_dense_triangulate",
     "ochip_rccl_unique_id", "ochip_rccl_comm_create", "ochip_rccl_comm_destroy", "ochip_rccl_comm_stats",
     "ochip_rccl_relax_exchange",
@@ -260,6 +261,7 @@ def load():
         L.ochip_debug_std_sort.argtypes = [vp, vp, vp, vp, u32, vp, vp, vp]
         L.ochip_debug_lm_step.argtypes = [vp, i32, vp, vp, vp, vp, C.c_double, vp, i32, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp]
         L.ochip_debug_homography_fit4.argtypes = [vp, i32, vp, u32, vp, vp, vp]
+        L.ochip_debug_decompose_votes.argtypes = [vp, vp, u32, vp, u64, vp, vp, vp]
         L.ochip_upload_batch.argtypes = [vp, u32, vp, vp, vp, vp]
         L.ochip_refit_homography_batch.argtypes = [vp, vp, u32, vp, u64, u32, C.c_double, vp, vp]
         L.ochip_akaze_batch.argtypes = [vp, vp, u32, i32, i32, u32, vp, vp, vp, vp]
@@ -744,6 +746,22 @@ class Context:
         self._check(self.L.ochip_debug_homography_fit4(self.h, int(route), xy16.ctypes.data if n else None, n, H.ctypes.data,
                                                        Hi.ctypes.data, deg.ctypes.data), "ochip_debug_homography_fit4")
         return H[:n].reshape(-1, 3, 3), Hi[:n].reshape(-1, 3, 3), deg[:n].astype(bool)
+
+    def debug_decompose_votes(self, jobs, matches, H, flags):
+        """ochip_debug_decompose_votes: decompose_vote_kernel on given homographies H (one 3 x 3 per job) over the rays of the
+        uploaded keypoints.  jobs: RANSAC_JOB_DTYPE, matches: RANSAC_MATCH_DTYPE, flags: one byte per match.  Returns one
+        DECOMPOSITION_DTYPE row per job."""
+        jobs = np.ascontiguousarray(jobs, RANSAC_JOB_DTYPE)
+        matches = np.ascontiguousarray(matches, RANSAC_MATCH_DTYPE)
+        flags = np.ascontiguousarray(flags, np.uint8)
+        H = np.ascontiguousarray(H, np.float64).reshape(-1, 9)
+        n, total = len(jobs), len(matches)
+        assert len(H) == n and len(flags) == total
+        out = np.zeros(max(n, 1), DECOMPOSITION_DTYPE)
+        self._check(self.L.ochip_debug_decompose_votes(self.h, jobs.ctypes.data if n else None, n, matches.ctypes.data if total else None,
+                                                       total, H.ctypes.data if n else None, flags.ctypes.data if total else None,
+                                                       out.ctypes.data), "ochip_debug_decompose_votes")
+        return out[:n]
 
     def relaxg_evaluate(self, scene, structure_only=False):
         """One evaluation of a general-engine relax problem (ochip_relaxg_problem_create, ochip_relaxg_evaluate, destroy):

@@ -4,7 +4,9 @@
 //
 // The decomposition is the analytical one of Malis & Vargas (INRIA RR-6303) as implemented by OpenCV's
 // HomographyDecompInria: a third-party algorithm restated from its publication; results are pinned by the reference's
-// test/test_ransac_unit.cpp tolerances (tests/test_oracle_ransac.py) and against the oracle's restatement.
+// test/test_ransac_unit.cpp tolerances (tests/test_oracle_ransac.py), against the oracle's restatement, and against
+// homographies built from known motions (tests/decompose_fixtures.py, tests/test_decompose_oracle.py,
+// tests/test_gpu_decompose.py; order_by_votes and quaternion_from_rotation in tests/decompose_order_driver.cpp).
 #pragma once
 
 #include <cmath>

@@ -18,7 +18,8 @@
 // (the reference is built without FMA); device division and sqrt are correctly rounded
 // (tests/test_gpu_fp64.py).  The three factorisations (full_piv_lu_solve9, regen_lu_solve9, lane_fit) are held at their
 // edges against the oracle bit for bit and against a long-double restatement through ochip_refit_homography_batch and the
-// seam ochip_debug_homography_fit4 (tests/test_gpu_homography_fit.py).
+// seam ochip_debug_homography_fit4 (tests/test_gpu_homography_fit.py); decompose_vote_kernel against the host on homographies
+// of known motions through the seam ochip_debug_decompose_votes (tests/test_gpu_decompose.py).
 //
 // libstdc++ pieces on the result path: std::default_random_engine (= minstd_rand0) and
 // std::uniform_int_distribution<size_t> are re-implemented here exactly (bits/random.tcc,
@@ -2977,6 +2978,59 @@ int ochip_debug_homography_fit4(ochip_ctx *ctx, int route, const double *xy16, u
     OCHIP_HIP(ctx, hipMemcpyAsync(H9, H_dev, m_bytes, hipMemcpyDeviceToHost, ctx->stream));
     OCHIP_HIP(ctx, hipMemcpyAsync(Hinv9, Hi_dev, m_bytes, hipMemcpyDeviceToHost, ctx->stream));
     OCHIP_HIP(ctx, hipMemcpyAsync(degenerate, deg_dev, n, hipMemcpyDeviceToHost, ctx->stream));
+    OCHIP_HIP(ctx, ochip_stream_wait(ctx, ctx->stream));
+    mem.release();
+    return OCHIP_OK;
+}
+
+int ochip_debug_decompose_votes(ochip_ctx *ctx, const ochip_ransac_job *jobs, uint32_t n_jobs, const ochip_ransac_match *matches,
+                                uint64_t total_matches, const double *H9, const uint8_t *inliers, ochip_decomposition *decomp_out)
+{
+    if (!ctx)
+        return OCHIP_EINVAL;
+    if (n_jobs == 0)
+        return OCHIP_OK;
+    if (!jobs || !H9 || !decomp_out || (total_matches && (!matches || !inliers)))
+        return ochip_fail(ctx, OCHIP_EINVAL, "ochip_debug_decompose_votes: NULL argument");
+    if (!ctx->kp_store_ready)
+        return ochip_fail(ctx, OCHIP_ESTATE, "ochip_upload_keypoints has not been called");
+    OCHIP_HIP(ctx, hipSetDevice(ctx->device));
+    OCHIP_TRY(prepare_homography_jobs(ctx, jobs, n_jobs, total_matches, nullptr));
+    // (the kernel gathers the rays through k1 / k2: a keypoint index past its image would read past the rays)
+    for (uint32_t j = 0; j < n_jobs; j++)
+        for (uint32_t i = 0; i < jobs[j].n; i++)
+        {
+            const ochip_ransac_match &m = matches[jobs[j].match_offset + i];
+            if (m.k1 >= ctx->img_n[jobs[j].image_1] || m.k2 >= ctx->img_n[jobs[j].image_2])
+                return ochip_fail(ctx, OCHIP_EINVAL, "ochip_debug_decompose_votes: job %u, match %u: keypoint index past its image", j, i);
+        }
+    // result rows that hold nothing but H, as the RANSAC kernel would have left them for the vote
+    std::vector<ochip_ransac_result> rows(n_jobs);
+    std::memset(rows.data(), 0, (size_t)n_jobs * sizeof(ochip_ransac_result));
+    for (uint32_t j = 0; j < n_jobs; j++)
+        std::memcpy(rows[j].H, H9 + (size_t)j * 9, sizeof rows[j].H);
+    const uint64_t T = total_matches ? total_matches : 1;
+    ochip::dev_scratch mem{ctx, "ochip_debug_decompose_votes"};
+    ochip_ransac_job *jobs_dev = (ochip_ransac_job *)mem.get((size_t)n_jobs * sizeof(ochip_ransac_job));
+    ochip_ransac_match *matches_dev = (ochip_ransac_match *)mem.get((size_t)T * sizeof(ochip_ransac_match));
+    ochip_ransac_result *res_dev = (ochip_ransac_result *)mem.get((size_t)n_jobs * sizeof(ochip_ransac_result));
+    uint8_t *inl_dev = (uint8_t *)mem.get((size_t)T);
+    ochip_decomposition *dec_dev = (ochip_decomposition *)mem.get((size_t)n_jobs * sizeof(ochip_decomposition));
+    if (!jobs_dev || !matches_dev || !res_dev || !inl_dev || !dec_dev)
+        return OCHIP_ENOMEM;
+    OCHIP_HIP(ctx, hipMemcpyAsync(jobs_dev, jobs, (size_t)n_jobs * sizeof(ochip_ransac_job), hipMemcpyHostToDevice, ctx->stream));
+    OCHIP_HIP(ctx, hipMemcpyAsync(res_dev, rows.data(), (size_t)n_jobs * sizeof(ochip_ransac_result), hipMemcpyHostToDevice, ctx->stream));
+    if (total_matches)
+    {
+        OCHIP_HIP(ctx, hipMemcpyAsync(matches_dev, matches, (size_t)total_matches * sizeof(ochip_ransac_match), hipMemcpyHostToDevice,
+                                      ctx->stream));
+        OCHIP_HIP(ctx, hipMemcpyAsync(inl_dev, inliers, (size_t)total_matches, hipMemcpyHostToDevice, ctx->stream));
+    }
+    rays_view rv{ctx->rays_dev, ctx->img_off_dev};
+    hipLaunchKernelGGL(decompose_vote_kernel, dim3((n_jobs + 3) / 4), dim3(256), 0, ctx->stream, (const ochip_ransac_job *)jobs_dev, n_jobs,
+                       (const ochip_ransac_match *)matches_dev, (const ochip_ransac_result *)res_dev, (const uint8_t *)inl_dev, rv, dec_dev);
+    OCHIP_HIP(ctx, hipGetLastError());
+    OCHIP_HIP(ctx, hipMemcpyAsync(decomp_out, dec_dev, (size_t)n_jobs * sizeof(ochip_decomposition), hipMemcpyDeviceToHost, ctx->stream));
     OCHIP_HIP(ctx, ochip_stream_wait(ctx, ctx->stream));
     mem.release();
     return OCHIP_OK;

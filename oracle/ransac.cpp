@@ -183,7 +183,9 @@ static void sym3_eigenvalues_jacobi(const Mat3 &S, double ev[3])
                 if (a[p][q] == 0.0)
                     continue;
                 const double theta = (a[q][q] - a[p][p]) / (2.0 * a[p][q]);
-                const double t = (theta >= 0 ? 1.0 : -1.0) / (std::abs(theta) + std::sqrt(theta * theta + 1.0));
+                // (the sign of theta as csrc/decompose.hpp takes it, -0.0 included: either sign is a Jacobi rotation there, and
+                // with one choice the two restatements are equal to the bit - tests/test_decompose_oracle.py)
+                const double t = std::copysign(1.0, theta) / (std::abs(theta) + std::sqrt(theta * theta + 1.0));
                 const double c = 1.0 / std::sqrt(t * t + 1.0), s = t * c;
                 for (int k = 0; k < 3; k++)
                 {
