@@ -786,6 +786,24 @@ extern "C"
     int och_graph_encode_thumbnails(och_graph *g, ochip_ctx *ctx);
     int och_graph_decode_thumbnails(och_graph *g, int32_t *statuses /* [nodes] or NULL */);
 
+    /* ---- reading tiled DEFLATE GeoTIFFs (opencalibration_amd/csrc/host/geotiff_read.cpp, csrc/inflate_rules.hpp;
+     *      DESIGN.md section 4.21) ----
+     * The reader of include/ochip.h (ochip_geotiff_reader_*) over both routes, with the same arguments.  ctx != NULL: the
+     * device route, as described there.  ctx == NULL: the host route, the same rules in loops, one tile or stream a thread
+     * under OpenMP, host rasters only; it never changes route by size.  The message of a refusal is in
+     * och_geotiff_read_last_error; a handle that create did not return or destroy has taken is refused, not followed. */
+    typedef struct och_geotiff_reader och_geotiff_reader;
+    int och_geotiff_reader_create(ochip_ctx *ctx, int samples, int is_float, int64_t width, int64_t height, int tile_w, int tile_h,
+                                  int predictor, uint64_t scratch_budget, och_geotiff_reader **out);
+    int och_geotiff_reader_inflate(och_geotiff_reader *r, int64_t n, const uint8_t *streams, const uint64_t *offsets /* [n + 1] */,
+                                   const uint64_t *expect /* [n] */, uint8_t *out, uint64_t out_cap, int32_t *status /* [n] */,
+                                   uint64_t *bytes /* [n] */);
+    int och_geotiff_reader_read(och_geotiff_reader *r, int64_t n, const uint8_t *streams, const uint64_t *offsets /* [n + 1] */,
+                                int64_t row0, int64_t rows, void *raster, int on_device, int64_t *bad_tile);
+    int64_t och_geotiff_reader_launches(och_geotiff_reader *r);
+    void och_geotiff_reader_destroy(och_geotiff_reader *r);
+    const char *och_geotiff_read_last_error(void);
+
 #ifdef __cplusplus
 }
 #endif

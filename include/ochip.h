@@ -1163,6 +1163,42 @@ extern "C"
                                  uint8_t *out, uint64_t out_cap, uint64_t *offsets /* [n + 1] */);
     void ochip_png_encoder_destroy(ochip_png_encoder *e);
 
+    /* ---- reading tiled DEFLATE GeoTIFFs: inflate, un-predict, raster (opencalibration_amd/csrc/geotiff_read.hip, the
+     *      rules in csrc/inflate_rules.hpp; the reference reads orthomosaic.tif and dsm.tif through GDAL,
+     *      src/ortho/ortho.cpp:2052-2123 and :1735-1756) ----
+     * A reader belongs to a sample layout (samples 1, 3 or 4 of 8 bits, or is_float with one float32), a raster size, a
+     * tile size (sides multiples of 16, a payload of at most 4 MiB) and a predictor (1 or 2).  The TIFF structure around
+     * the streams is the caller's (host.GeoTiffReader).  scratch_budget: the device bytes (streams plus payloads) one
+     * launch may take, 0 for the default of 1.5 GiB; a call's streams go through as many launches as that needs, a launch
+     * at least one stream.  All work runs on the context's stream.
+     * inflate: n zlib streams (at most 65 535), stream i at streams[offsets[i] .. offsets[i + 1]), each of expect[i] bytes
+     * (at most 2^30), into out (host): payload i begins at the sum of the expects before it, each rounded up to 16
+     * (out_cap: at least where the last payload ends).
+     * status[i]: OCHIP_INFLATE_OK only for a stream that gave exactly expect[i] bytes, ended with a BFINAL block, whose
+     * Adler-32 matched and that has nothing behind it; bytes[i]: what it produced.  A stream that is not OK touches
+     * nothing outside its own payload.
+     * read: the streams of the tiles of the tile rows that cover raster rows [row0, row0 + rows), in tile order (n is
+     * their number; an empty stream is a sparse tile: zeros), un-predicted and placed into raster - rows x width pixels,
+     * host memory or, with on_device, device memory of the context's device.  *bad_tile: -1, or the first tile (an index
+     * into the call's streams) whose stream was not OK; the raster's contents are then unspecified.  The call returns
+     * when raster is written.
+     * OCHIP_EINVAL and a message, before anything is launched: a handle that create did not return or destroy has taken
+     * (the message is ochip_last_error(NULL)'s), NULL arrays, n out of range or not the window's tile count, offsets
+     * that descend, an expect beyond 2^30, out_cap too small, a window outside the raster. */
+#define OCHIP_INFLATE_OK 0
+#define OCHIP_INFLATE_CORRUPT 1
+#define OCHIP_INFLATE_MAX_STREAMS 65535
+    typedef struct ochip_geotiff_reader ochip_geotiff_reader;
+    int ochip_geotiff_reader_create(ochip_ctx *ctx, int samples, int is_float, int64_t width, int64_t height, int tile_w,
+                                    int tile_h, int predictor, uint64_t scratch_budget, ochip_geotiff_reader **out);
+    int ochip_geotiff_reader_inflate(ochip_geotiff_reader *r, int64_t n, const uint8_t *streams, const uint64_t *offsets /* [n + 1] */,
+                                     const uint64_t *expect /* [n] */, uint8_t *out, uint64_t out_cap, int32_t *status /* [n] */,
+                                     uint64_t *bytes /* [n] */);
+    int ochip_geotiff_reader_read(ochip_geotiff_reader *r, int64_t n, const uint8_t *streams, const uint64_t *offsets /* [n + 1] */,
+                                  int64_t row0, int64_t rows, void *raster, int on_device, int64_t *bad_tile);
+    int64_t ochip_geotiff_reader_launches(ochip_geotiff_reader *r); /* the inflate launches so far, -1 for a dead handle */
+    void ochip_geotiff_reader_destroy(ochip_geotiff_reader *r);
+
 #ifdef __cplusplus
 }
 #endif

@@ -59,6 +59,8 @@ EXPORTS = [
     "ochip_jpeg_decoder_create", "ochip_jpeg_decoder_decode", "ochip_jpeg_decoder_destroy",
     "ochip_geotiff_create", "ochip_geotiff_feed", "ochip_geotiff_payloads", "ochip_geotiff_collect", "ochip_geotiff_finish",
     "ochip_geotiff_destroy",
+    "ochip_geotiff_reader_create", "ochip_geotiff_reader_inflate", "ochip_geotiff_reader_read", "ochip_geotiff_reader_launches",
+    "ochip_geotiff_reader_destroy",
     "ochip_png_encoder_create", "ochip_png_encoder_encode", "ochip_png_encoder_destroy",
 ]
 
@@ -330,6 +332,13 @@ def load():
         L.ochip_geotiff_finish.argtypes = [vp]
         L.ochip_geotiff_destroy.argtypes = [vp]
         L.ochip_geotiff_destroy.restype = None
+        L.ochip_geotiff_reader_create.argtypes = [vp, i32, i32, C.c_int64, C.c_int64, i32, i32, i32, u64, C.POINTER(vp)]
+        L.ochip_geotiff_reader_inflate.argtypes = [vp, C.c_int64, vp, vp, vp, vp, u64, vp, vp]
+        L.ochip_geotiff_reader_read.argtypes = [vp, C.c_int64, vp, vp, C.c_int64, C.c_int64, vp, i32, C.POINTER(C.c_int64)]
+        L.ochip_geotiff_reader_launches.argtypes = [vp]
+        L.ochip_geotiff_reader_launches.restype = C.c_int64
+        L.ochip_geotiff_reader_destroy.argtypes = [vp]
+        L.ochip_geotiff_reader_destroy.restype = None
         L.ochip_png_encoder_create.argtypes = [vp, C.POINTER(vp)]
         L.ochip_png_encoder_encode.argtypes = [vp, C.c_int64, vp, i32, i32, vp, u64, vp]
         L.ochip_png_encoder_destroy.argtypes = [vp]

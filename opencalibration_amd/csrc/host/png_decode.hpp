@@ -7,6 +7,7 @@
 // data's end, and nothing is sized from IHDR before the data is known to be able to fill it.
 #pragma once
 
+#include "../inflate_rules.hpp"
 #include "../png_rules.hpp"
 
 #include <cstdlib>
@@ -53,222 +54,16 @@ inline int read_info(const uint8_t *data, uint64_t size, file_info &I)
     return I.status = PNG_OK;
 }
 
-namespace inflate_detail
-{
-struct bits_in
-{
-    const uint8_t *p;
-    size_t n, at = 0;
-    uint64_t acc = 0;
-    int cnt = 0;
-    bool fail = false;
-    uint32_t take(int k) // k <= 16
-    {
-        while (cnt < k)
-        {
-            if (at >= n)
-            {
-                fail = true;
-                return 0;
-            }
-            acc |= (uint64_t)p[at++] << cnt, cnt += 8;
-        }
-        const uint32_t v = (uint32_t)(acc & ((1u << k) - 1));
-        acc >>= k, cnt -= k;
-        return v;
-    }
-    void align()
-    {
-        acc >>= cnt & 7, cnt -= cnt & 7;
-    }
-};
-
-struct huffman
-{
-    uint16_t count[16];
-    uint16_t symbol[288];
-};
-
-// false: over-subscribed, or incomplete in a way inflate refuses (more than a single code of one bit; never for the
-// code-length code)
-inline bool build(huffman &h, const uint8_t *lens, int n, bool may_be_single)
-{
-    for (int i = 0; i < 16; i++)
-        h.count[i] = 0;
-    for (int i = 0; i < n; i++)
-        h.count[lens[i]]++;
-    int left = 1, longest = 0;
-    for (int l = 1; l < 16; l++)
-    {
-        left <<= 1, left -= h.count[l];
-        if (left < 0)
-            return false;
-        if (h.count[l])
-            longest = l;
-    }
-    if (left > 0 && longest != 0 && !(may_be_single && longest == 1))
-        return false;
-    if (longest == 0 && !may_be_single)
-        return false;
-    uint16_t offs[16];
-    offs[1] = 0;
-    for (int l = 1; l < 15; l++)
-        offs[l + 1] = (uint16_t)(offs[l] + h.count[l]);
-    for (int i = 0; i < n; i++)
-        if (lens[i])
-            h.symbol[offs[lens[i]]++] = (uint16_t)i;
-    return true;
-}
-
-inline int decode(bits_in &in, const huffman &h) // -1: no such code, or the data ended
-{
-    int code = 0, first = 0, index = 0;
-    for (int l = 1; l < 16; l++)
-    {
-        code |= (int)in.take(1);
-        if (in.fail)
-            return -1;
-        const int count = h.count[l];
-        if (code - count < first)
-            return h.symbol[index + (code - first)];
-        index += count, first += count, first <<= 1, code <<= 1;
-    }
-    return -1;
-}
-} // namespace inflate_detail
-
 // A zlib stream of exactly `expect` bytes into out (sized here, once the stream is known to be able to fill it).  false: any
-// check fails, the stream gives fewer or more bytes, or bytes follow its Adler-32.
+// check of the project's one inflate (csrc/inflate_rules.hpp) fails, the stream gives fewer or more bytes, or bytes follow
+// its Adler-32.
 inline bool inflate_exact(const uint8_t *z, size_t n, uint64_t expect, std::vector<uint8_t> &out)
 {
-    using namespace inflate_detail;
-    // deflate expands at most 1032 : 1 (258 bytes from a two-bit pair of codes)
-    if (n < 6 || expect > (uint64_t)n * 1032 || expect > ((uint64_t)1 << 40))
-        return false;
-    if ((z[0] & 15) != 8 || (z[0] >> 4) > 7 || ((uint32_t)z[0] << 8 | z[1]) % 31 != 0 || (z[1] & 0x20))
+    if (!ochip_inf::plausible(n, expect))
         return false;
     out.clear();
     out.resize((size_t)expect);
-    uint8_t *o = out.data();
-    uint64_t have = 0;
-    bits_in in{z + 2, n - 2};
-    static const uint16_t len_base[29] = {3, 4, 5, 6, 7, 8, 9, 10, 11, 13, 15, 17, 19, 23, 27, 31, 35, 43, 51, 59, 67, 83, 99, 115, 131, 163, 195, 227, 258};
-    static const uint8_t len_extra[29] = {0, 0, 0, 0, 0, 0, 0, 0, 1, 1, 1, 1, 2, 2, 2, 2, 3, 3, 3, 3, 4, 4, 4, 4, 5, 5, 5, 5, 0};
-    static const uint16_t dist_base[30] = {1, 2, 3, 4, 5, 7, 9, 13, 17, 25, 33, 49, 65, 97, 129, 193, 257, 385, 513, 769, 1025, 1537, 2049, 3073, 4097, 6145, 8193, 12289, 16385, 24577};
-    static const uint8_t dist_extra[30] = {0, 0, 0, 0, 1, 1, 2, 2, 3, 3, 4, 4, 5, 5, 6, 6, 7, 7, 8, 8, 9, 9, 10, 10, 11, 11, 12, 12, 13, 13};
-    static const uint8_t order[19] = {16, 17, 18, 0, 8, 7, 9, 6, 10, 5, 11, 4, 12, 3, 13, 2, 14, 1, 15};
-    huffman lit, dist;
-    uint8_t lens[320];
-    for (bool last = false; !last;)
-    {
-        last = in.take(1) != 0;
-        const uint32_t type = in.take(2);
-        if (in.fail || type == 3)
-            return false;
-        if (type == 0)
-        {
-            in.align();
-            const uint32_t len = in.take(16), nlen = in.take(16);
-            if (in.fail || (len ^ 0xFFFFu) != nlen || have + len > expect)
-                return false;
-            for (uint32_t i = 0; i < len; i++) // the bit buffer holds whole bytes here
-            {
-                o[have++] = (uint8_t)in.take(8);
-                if (in.fail)
-                    return false;
-            }
-            continue;
-        }
-        if (type == 1)
-        {
-            for (int i = 0; i < 288; i++)
-                lens[i] = i < 144 ? 8 : i < 256 ? 9 : i < 280 ? 7 : 8;
-            build(lit, lens, 288, false);
-            for (int i = 0; i < 32; i++) // 30 and 31 complete the code and are refused where they occur
-                lens[i] = 5;
-            build(dist, lens, 32, true);
-        }
-        else
-        {
-            const int hlit = (int)in.take(5) + 257, hdist = (int)in.take(5) + 1, hclen = (int)in.take(4) + 4;
-            if (in.fail || hlit > 286 || hdist > 30)
-                return false;
-            uint8_t cl[19] = {0};
-            for (int i = 0; i < hclen; i++)
-                cl[order[i]] = (uint8_t)in.take(3);
-            if (in.fail)
-                return false;
-            huffman clh;
-            if (!build(clh, cl, 19, false))
-                return false;
-            for (int i = 0; i < hlit + hdist;)
-            {
-                const int s = decode(in, clh);
-                if (s < 0)
-                    return false;
-                if (s < 16)
-                {
-                    lens[i++] = (uint8_t)s;
-                    continue;
-                }
-                int rep, val = 0;
-                if (s == 16)
-                {
-                    if (i == 0)
-                        return false;
-                    val = lens[i - 1], rep = 3 + (int)in.take(2);
-                }
-                else
-                    rep = s == 17 ? 3 + (int)in.take(3) : 11 + (int)in.take(7);
-                if (in.fail || i + rep > hlit + hdist)
-                    return false;
-                while (rep--)
-                    lens[i++] = (uint8_t)val;
-            }
-            if (lens[256] == 0)
-                return false; // no end-of-block code
-            uint8_t dl[30];
-            for (int i = 0; i < hdist; i++)
-                dl[i] = lens[hlit + i];
-            if (!build(lit, lens, hlit, true) || !build(dist, dl, hdist, true))
-                return false;
-        }
-        for (;;)
-        {
-            const int s = decode(in, lit);
-            if (s < 0)
-                return false;
-            if (s < 256)
-            {
-                if (have >= expect)
-                    return false;
-                o[have++] = (uint8_t)s;
-                continue;
-            }
-            if (s == 256)
-                break;
-            if (s > 285)
-                return false;
-            const uint32_t len = len_base[s - 257] + in.take(len_extra[s - 257]);
-            const int ds = decode(in, dist);
-            if (ds < 0 || ds > 29)
-                return false;
-            const uint32_t d = dist_base[ds] + in.take(dist_extra[ds]);
-            if (in.fail || d > have || have + len > expect)
-                return false;
-            for (uint32_t i = 0; i < len; i++, have++)
-                o[have] = o[have - d];
-        }
-    }
-    if (have != expect)
-        return false;
-    in.align();
-    uint32_t adler = 0;
-    for (int i = 0; i < 4; i++)
-        adler = adler << 8 | in.take(8);
-    if (in.fail || in.cnt != 0 || in.at != in.n) // bytes behind the Adler-32: trailing garbage inside the stream
-        return false;
-    return adler == adler32(o, (size_t)expect);
+    return ochip_inf::inflate_stream(z, n, out.data(), expect).status == ochip_inf::INF_OK;
 }
 
 // The picture of a file: width x height x channels bytes, the file's channels.  PNG_OK only with every check passed; pixels

@@ -341,6 +341,14 @@ def load():
         L.och_geotiff_destroy.argtypes = [vp]
         L.och_geotiff_destroy.restype = None
         L.och_geotiff_last_error.restype = C.c_char_p
+        L.och_geotiff_reader_create.argtypes = [vp, C.c_int, C.c_int, i64, i64, C.c_int, C.c_int, C.c_int, C.c_uint64, C.POINTER(vp)]
+        L.och_geotiff_reader_inflate.argtypes = [vp, i64, vp, vp, vp, vp, C.c_uint64, vp, vp]
+        L.och_geotiff_reader_read.argtypes = [vp, i64, vp, vp, i64, i64, vp, C.c_int, C.POINTER(i64)]
+        L.och_geotiff_reader_launches.argtypes = [vp]
+        L.och_geotiff_reader_launches.restype = i64
+        L.och_geotiff_reader_destroy.argtypes = [vp]
+        L.och_geotiff_reader_destroy.restype = None
+        L.och_geotiff_read_last_error.restype = C.c_char_p
         L.och_deflate_code_lengths.argtypes = [vp, C.c_int, C.c_int, vp]
         L.och_png_encoder_create.argtypes = [vp, C.POINTER(vp)]
         L.och_png_encoder_encode.argtypes = [vp, i64, vp, C.c_int, C.c_int, vp, C.c_uint64, vp]
@@ -769,13 +777,18 @@ def save_textured_obj(path, surfaces, rgba, plan, jpeg=False, ctx=None, quality=
     jpeg=True: `path`.jpg, the name the MTL refers to, is written too (encode_jpeg: ctx None the CPU route, else on ctx's
     device, where rgba may be a CUDA tensor), and the texture returned - alone, or as the third value with path=None - is the
     file's bytes instead of the pixels."""
+    return _save_textured_obj(path, surfaces, rgba, plan, plan["width"], plan["height"], jpeg, ctx, quality)
+
+
+def _save_textured_obj(path, surfaces, rgba, plan, pw, ph, jpeg, ctx, quality):
+    """save_textured_obj with the mosaic's size named: plan is the plan or textured_obj's geometry tuple"""
     if jpeg and not isinstance(rgba, np.ndarray) and hasattr(rgba, "is_cuda"):
         shape = tuple(int(v) for v in rgba.shape)
     else:
         rgba = np.asarray(rgba)
         shape = rgba.shape
-    if len(shape) != 3 or shape[2] < 3 or shape[:2] != (plan["height"], plan["width"]):
-        raise ValueError(f"rgba {shape} is not the plan's {plan['height']} x {plan['width']} mosaic")
+    if len(shape) != 3 or shape[2] < 3 or shape[:2] != (ph, pw):
+        raise ValueError(f"rgba {shape} is not the plan's {ph} x {pw} mosaic")
     base = "model" if path is None else str(path)
     if base.endswith(".obj"):
         base = base[:-4]
@@ -2498,6 +2511,393 @@ def save_geotiff(target, raster, geo=None, ctx=None, overviews=True, bigtiff=Non
     with GeoTiffWriter(target, kind, w, h, geo=geo, ctx=ctx, on_device=on_device, bigtiff=bigtiff, sparse=sparse) as wr:
         wr.feed(0, raster)
         wr.finish(levels)
+
+
+# ---- reading tiled DEFLATE GeoTIFFs (include/oc_host.h) -------------------------------------------------------
+INFLATE_OK, INFLATE_CORRUPT = 0, 1
+INFLATE_MAX_STREAMS = 65535
+GEOTIFF_MAX_TILE_BYTES = 4 << 20
+
+
+class GeoTiffError(ValueError):
+    """status: "unsupported" (a file this reader does not take: the reason is the text), "corrupt" (a structure that does not
+    parse or a tile whose stream does not check) or "refused" (the library refused the call)"""
+
+    def __init__(self, status, text):
+        super().__init__(f"{status}: {text}")
+        self.status = status
+
+
+class _TileReader:
+    """och_geotiff_reader_*: zlib streams to payloads, and a layout's tile streams to a raster"""
+
+    def __init__(self, samples, is_float, width, height, tile_w, tile_h, predictor, ctx, budget=0):
+        self.L, self.ctx, self.h = load(), ctx, None
+        h = C.c_void_p()
+        if self.L.och_geotiff_reader_create(ctx.h if ctx is not None else None, int(samples), int(bool(is_float)), int(width), int(height),
+                                            int(tile_w), int(tile_h), int(predictor), int(budget), C.byref(h)) != 0:
+            raise GeoTiffError("refused", self.error())
+        self.h = h
+
+    def error(self):
+        return self.L.och_geotiff_read_last_error().decode()
+
+    def close(self):
+        if getattr(self, "h", None):
+            if self.ctx is None or getattr(self.ctx, "h", None):  # as OrthoStream.close: the context may be gone
+                self.L.och_geotiff_reader_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        self.close()
+
+    def launches(self):
+        return int(self.L.och_geotiff_reader_launches(self.h))
+
+    def inflate(self, packed, offsets, expect):
+        """(payloads as one uint8 array, slot offsets, status, bytes) of the packed streams"""
+        n = len(expect)
+        slots = np.zeros(n + 1, np.uint64)
+        np.cumsum((expect + np.uint64(15)) & ~np.uint64(15), out=slots[1:])
+        out = np.empty(max(int(slots[-1]), 1), np.uint8)
+        status, produced = np.zeros(max(n, 1), np.int32), np.zeros(max(n, 1), np.uint64)
+        if self.L.och_geotiff_reader_inflate(self.h, n, packed.ctypes.data, offsets.ctypes.data, expect.ctypes.data, out.ctypes.data,
+                                             int(slots[-1]), status.ctypes.data, produced.ctypes.data) != 0:
+            raise GeoTiffError("refused", self.error())
+        return out, slots, status[:n], produced[:n]
+
+    def read(self, packed, offsets, row0, rows, ptr, on_device):
+        bad = C.c_int64(-1)
+        if self.L.och_geotiff_reader_read(self.h, len(offsets) - 1, packed.ctypes.data, offsets.ctypes.data, int(row0), int(rows), ptr,
+                                          int(bool(on_device)), C.byref(bad)) != 0:
+            raise GeoTiffError("refused", self.error())
+        return int(bad.value)
+
+
+def _pack_streams(pieces):
+    """(packed uint8 array, offsets uint64 [n + 1]) of a list of bytes-like streams back to back"""
+    offsets = np.zeros(len(pieces) + 1, np.uint64)
+    if pieces:
+        np.cumsum([len(p) for p in pieces], out=offsets[1:])
+    packed = np.empty(max(int(offsets[-1]), 1), np.uint8)
+    for p, at in zip(pieces, offsets[:-1]):
+        if len(p):
+            packed[int(at):int(at) + len(p)] = np.frombuffer(p, np.uint8)
+    return packed, offsets
+
+
+def inflate_report(streams, expect, ctx=None, budget=0):
+    """inflate_streams without the raise: a list of (status, produced, payload) per stream - INFLATE_OK with the payload's
+    bytes, or INFLATE_CORRUPT with None - and `produced`, the bytes the stream gave before it ended or was refused."""
+    streams = list(streams)
+    n = len(streams)
+    expect = np.full(n, expect, np.uint64) if np.ndim(expect) == 0 else np.ascontiguousarray(expect, np.uint64)
+    if len(expect) != n:
+        raise ValueError(f"{n} streams and {len(expect)} sizes")
+    packed, offsets = _pack_streams(streams)
+    rd = _TileReader(1, False, 16, 16, 16, 16, 1, ctx, budget)
+    try:
+        out, slots, status, produced = rd.inflate(packed, offsets, expect)
+    finally:
+        rd.close()
+    return [(int(status[i]), int(produced[i]),
+             out[int(slots[i]):int(slots[i]) + int(expect[i])].tobytes() if status[i] == INFLATE_OK else None) for i in range(n)]
+
+
+def inflate_streams(streams, expect, ctx=None, budget=0):
+    """The counterpart of deflate_tiles: the payloads (a list of bytes) of zlib streams (a list of bytes) of known sizes -
+    `expect`, one size or a list - by the rules of csrc/inflate_rules.hpp: ctx None the host route, else on ctx's device (one
+    wavefront a stream; budget: the device scratch a launch may take, 0 for the default) - the same bytes.  A stream that
+    does not give exactly its size, does not end with a final block, fails its Adler-32 or has bytes behind it raises
+    GeoTiffError("corrupt") naming the stream's index."""
+    report = inflate_report(streams, expect, ctx=ctx, budget=budget)
+    for i, (status, produced, _) in enumerate(report):
+        if status != INFLATE_OK:
+            raise GeoTiffError("corrupt", f"stream {i} of {len(report)}: not a zlib stream of exactly its expected size ({produced} bytes "
+                                          f"produced)")
+    return [payload for _, _, payload in report]
+
+
+_TIFF_TYPES = {1: "u1", 2: "S1", 3: "<u2", 4: "<u4", 5: "<u4", 6: "i1", 7: "u1", 8: "<i2", 9: "<i4", 10: "<i4", 11: "<f4", 12: "<f8",
+               16: "<u8", 17: "<i8", 18: "<u8"}
+
+
+class GeoTiffReader:
+    """A tiled DEFLATE GeoTIFF read back: the file GeoTiffWriter writes, and what GDAL writes with the same options.  source: a
+    path, bytes, or a seekable binary file object.  The structure - header, the IFD chain, the tile arrays - is parsed here;
+    the tiles are inflated, un-predicted and placed by och_geotiff_reader_* (DESIGN.md §4.21): ctx None the host route (one
+    tile a thread), else on ctx's device (one wavefront a tile; the raster stays there with on_device).  It never changes
+    route by size.  Measured on the MI355X (profiles/geotiff_read_probe.json) the device route is the slower
+    one: a 16 384 x 16 384 RGBA file of 1 024 tiles takes 0.27 - 0.52 s on the device and 0.18 s on 16 host threads, a
+    64-tile file 0.12 - 0.25 s against 0.012 s.  Take it for pixels that must end on the device.
+    width, height, samples, kind (OVERVIEW_RGBA8, OVERVIEW_FLOAT32 or None for 1 or 3 samples), levels ([(rows, cols), ...]
+    of the overview IFDs), geo (dict(min_x, max_y, gsd_x, gsd_y, epsg) from tags 33550 / 33922 / 34735, or None) and nodata
+    (tag 42113 as a float, or None).
+    Taken: little-endian classic and BigTIFF, tiles with sides that are multiples of 16 and a payload of at most 4 MiB,
+    Compression 8 and 32946, Predictor 1 and 2, PlanarConfiguration 1, 8-bit unsigned samples 1, 3 or 4 to a pixel, one
+    float32.  Everything else - big-endian files, strips, other compressions (none included), Predictor 3, planar 2, other
+    sample formats or depths - raises GeoTiffError("unsupported") with the reason; offsets or counts outside the file, IFD
+    loops, tile arrays of the wrong length and any tile whose stream does not check raise GeoTiffError("corrupt"), the last
+    naming the level and the tile, and no part of the raster is returned."""
+
+    def __init__(self, source, ctx=None, budget=0):
+        self.ctx, self.budget, self._readers, self._f, self._map = ctx, int(budget), {}, None, None
+        self.buf = None
+        if isinstance(source, (bytes, bytearray, memoryview)):
+            self.buf = np.frombuffer(source, np.uint8)
+        elif isinstance(source, (str, os.PathLike)):
+            import mmap
+
+            self._f = open(source, "rb")
+            if os.fstat(self._f.fileno()).st_size == 0:
+                self.close()
+                raise GeoTiffError("corrupt", "the file is empty")
+            self._map = mmap.mmap(self._f.fileno(), 0, access=mmap.ACCESS_READ)
+            self.buf = np.frombuffer(self._map, np.uint8)
+        elif hasattr(source, "read") and hasattr(source, "seekable") and source.seekable():
+            source.seek(0)  # the file begins at the object's start, wherever a writer left its position
+            self.buf = np.frombuffer(source.read(), np.uint8)
+        else:
+            raise GeoTiffError("refused", "a GeoTIFF's source is a path, bytes or a seekable binary file object")
+        try:
+            self._parse()
+        except BaseException:
+            self.close()
+            raise
+
+    # -- the structure
+    def _at(self, off, n, what):
+        if off < 0 or n < 0 or off + n > len(self.buf):
+            raise GeoTiffError("corrupt", f"{what} at {off} + {n} lies outside the file's {len(self.buf)} bytes")
+        return self.buf[off:off + n]
+
+    def _num(self, off, dtype, what):
+        return int(self._at(off, np.dtype(dtype).itemsize, what).view(dtype)[0])
+
+    def _parse(self):
+        head = bytes(self._at(0, 8, "the header"))
+        if head[:2] == b"MM":
+            raise GeoTiffError("unsupported", "a big-endian file")
+        if head[:2] != b"II" or head[2:4] not in (b"*\0", b"+\0"):
+            raise GeoTiffError("corrupt", "not a TIFF header")
+        self.big = head[2:4] == b"+\0"
+        if self.big:
+            if bytes(self._at(4, 4, "the BigTIFF header")) != b"\x08\0\0\0":
+                raise GeoTiffError("corrupt", "a BigTIFF header's offset size is 8")
+            at = self._num(8, "<u8", "the first IFD's offset")
+        else:
+            at = self._num(4, "<u4", "the first IFD's offset")
+        self._ifds, seen = [], set()
+        while at:
+            if at in seen or len(seen) > 64:
+                raise GeoTiffError("corrupt", f"the IFD chain returns to offset {at}" if at in seen else "more than 64 IFDs")
+            seen.add(at)
+            tags, at = self._read_ifd(at)
+            self._ifds.append(self._layout(tags, len(self._ifds)))
+        if not self._ifds:
+            raise GeoTiffError("corrupt", "no IFD")
+        first = self._ifds[0]
+        self.width, self.height, self.samples, self.is_float = first["width"], first["height"], first["samples"], first["is_float"]
+        self.kind = OVERVIEW_FLOAT32 if self.is_float else OVERVIEW_RGBA8 if self.samples == 4 else None
+        for k, lv in enumerate(self._ifds[1:]):
+            if (lv["samples"], lv["is_float"]) != (self.samples, self.is_float):
+                raise GeoTiffError("unsupported", f"level {k + 1} has another sample layout than the full raster")
+        self.levels = [(lv["height"], lv["width"]) for lv in self._ifds[1:]]
+        tags = first["tags"]
+        self.geo = None
+        if 33550 in tags and 33922 in tags and len(tags[33550]) >= 2 and len(tags[33922]) >= 6:
+            sx, sy = float(tags[33550][0]), float(tags[33550][1])
+            i, j, _, x, y = (float(v) for v in tags[33922][:5])
+            epsg, keys = None, tags.get(34735)
+            if keys is not None and len(keys) >= 4:
+                for q in range(min(int(keys[3]), (len(keys) - 4) // 4)):
+                    key, loc, _, value = (int(v) for v in keys[4 + 4 * q:8 + 4 * q])
+                    if loc == 0 and (key == 3072 or (key == 2048 and epsg is None)):
+                        epsg = value
+            self.geo = dict(min_x=x - i * sx, max_y=y + j * sy, gsd_x=sx, gsd_y=sy, epsg=epsg)
+        self.nodata = None
+        if 42113 in tags:
+            try:
+                self.nodata = float(bytes(tags[42113]).split(b"\0")[0].decode("ascii").strip())
+            except (ValueError, UnicodeDecodeError):
+                self.nodata = None
+
+    def _read_ifd(self, at):
+        big = self.big
+        count = self._num(at, "<u8" if big else "<u2", "an IFD's entry count")
+        esize, inline, body = (20, 8, at + 8) if big else (12, 4, at + 2)
+        if count > 4096:
+            raise GeoTiffError("corrupt", f"an IFD of {count} entries")
+        raw = self._at(body, count * esize + inline, "an IFD")
+        tags = {}
+        for k in range(count):
+            e = raw[k * esize:(k + 1) * esize]
+            tag, typ = int(e[0:2].view("<u2")[0]), int(e[2:4].view("<u2")[0])
+            n = int(e[4:12].view("<u8")[0]) if big else int(e[4:8].view("<u4")[0])
+            if typ not in _TIFF_TYPES:
+                continue
+            dt = np.dtype(_TIFF_TYPES[typ])
+            size = n * dt.itemsize * (2 if typ in (5, 10) else 1)
+            if size > len(self.buf):
+                raise GeoTiffError("corrupt", f"tag {tag} claims {size} bytes")
+            field = e[esize - inline:]
+            data = field[:size] if size <= inline else self._at(int(field.view("<u8" if big else "<u4")[0]), size, f"tag {tag}'s values")
+            tags[tag] = bytes(data) if typ == 2 else np.frombuffer(bytes(data), dt)
+        nxt = raw[count * esize:]
+        return tags, int(nxt.view("<u8" if big else "<u4")[0])
+
+    def _layout(self, tags, index):
+        what = f"level {index}"
+
+        def one(tag, default=None):
+            if tag not in tags or isinstance(tags[tag], bytes) or len(tags[tag]) == 0:
+                if default is None:
+                    raise GeoTiffError("corrupt", f"{what}: tag {tag} is missing")
+                return default
+            return int(tags[tag][0])
+
+        width, height = one(256), one(257)
+        if width < 1 or height < 1 or width > 1048576 or height > 1048576:
+            raise GeoTiffError("corrupt", f"{what}: a raster of {width} x {height}")
+        if 322 not in tags or 323 not in tags or 324 not in tags or 325 not in tags:
+            raise GeoTiffError("unsupported" if 273 in tags else "corrupt", f"{what}: strips, not tiles" if 273 in tags
+                               else f"{what}: no tile tags")
+        comp, planar, pred, samples, fmt = one(259, 1), one(284, 1), one(317, 1), one(277, 1), one(339, 1)
+        bits = [int(v) for v in tags[258]] if 258 in tags and not isinstance(tags[258], bytes) else [1]
+        if comp not in (8, 32946):
+            raise GeoTiffError("unsupported", f"{what}: compression {comp}, not DEFLATE (8 or 32946)")
+        if planar != 1:
+            raise GeoTiffError("unsupported", f"{what}: PlanarConfiguration {planar}")
+        if pred not in (1, 2):
+            raise GeoTiffError("unsupported", f"{what}: Predictor {pred}")
+        is_float = fmt == 3 and bits == [32] and samples == 1
+        if not is_float and not (fmt == 1 and samples in (1, 3, 4) and bits == [8] * samples):
+            raise GeoTiffError("unsupported", f"{what}: {samples} samples of {bits} bits, SampleFormat {fmt}")
+        tw, th = one(322), one(323)
+        bpp = 4 if is_float else samples
+        if tw < 16 or th < 16 or tw % 16 or th % 16 or tw * th * bpp > GEOTIFF_MAX_TILE_BYTES:
+            raise GeoTiffError("unsupported", f"{what}: tiles of {tw} x {th} (sides are multiples of 16, a payload at most 4 MiB)")
+        tiles_x, tiles_y = -(-width // tw), -(-height // th)
+        for tag in (324, 325):
+            if isinstance(tags[tag], bytes) or tags[tag].dtype.kind != "u":
+                raise GeoTiffError("corrupt", f"{what}: tag {tag}'s values are not unsigned integers")
+        offs, cnts = tags[324].astype(np.uint64), tags[325].astype(np.uint64)
+        if len(offs) != tiles_x * tiles_y or len(cnts) != tiles_x * tiles_y:
+            raise GeoTiffError("corrupt", f"{what}: {len(offs)} tile offsets and {len(cnts)} counts for {tiles_x} x {tiles_y} tiles")
+        live = cnts > 0
+        if np.any(offs[live] > len(self.buf)) or np.any(cnts[live] > len(self.buf)) or np.any(offs[live] + cnts[live] > len(self.buf)):
+            k = int(np.flatnonzero(live & ((offs > len(self.buf)) | (cnts > len(self.buf)) | (offs + cnts > len(self.buf))))[0])
+            raise GeoTiffError("corrupt", f"{what}: tile {k} at {int(offs[k])} + {int(cnts[k])} lies outside the file's {len(self.buf)} bytes")
+        return dict(width=width, height=height, samples=samples, is_float=is_float, tile_w=tw, tile_h=th, predictor=pred,
+                    tiles_x=tiles_x, tiles_y=tiles_y, offsets=offs, counts=cnts, tags=tags)
+
+    # -- the pattern of the other classes
+    def close(self):
+        for rd in getattr(self, "_readers", {}).values():
+            rd.close()
+        self._readers = {}
+        self.buf = None
+        if getattr(self, "_map", None) is not None:
+            try:
+                self._map.close()
+            except BufferError:  # an array over the map is still alive: the map goes with it
+                pass
+            self._map = None
+        if getattr(self, "_f", None) is not None:
+            self._f.close()
+            self._f = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        self.close()
+
+    def launches(self, level=0):
+        """the inflate launches of the device route for `level` so far"""
+        return self._readers[level].launches() if level in self._readers else 0
+
+    def read(self, row0=0, rows=None, level=0, out=None, on_device=False):
+        """Rows [row0, row0 + rows) of level `level` (0: the full raster): (rows, width, samples) uint8 or (rows, width)
+        float32, a numpy array, or with on_device a CUDA tensor on ctx's device.  Any row window inside the level is taken;
+        the tile rows that cover it are decoded.  out: the array or tensor to fill."""
+        if self.buf is None:
+            raise GeoTiffError("refused", "the reader is closed")
+        if not 0 <= int(level) < len(self._ifds):
+            raise ValueError(f"level {level} of a file with {len(self._ifds) - 1} overview levels")
+        lv = self._ifds[int(level)]
+        w, h, th = lv["width"], lv["height"], lv["tile_h"]
+        row0 = int(row0)
+        rows = h - row0 if rows is None else int(rows)
+        if row0 < 0 or rows < 0 or row0 + rows > h:
+            raise ValueError(f"rows {row0} .. {row0 + rows} of a level of {h} rows")
+        if on_device and self.ctx is None:
+            raise ValueError("a raster on the device needs the device route (ctx)")
+        shape = (rows, w) if lv["is_float"] else (rows, w, lv["samples"])
+        dtype = "float32" if lv["is_float"] else "uint8"
+        if on_device:
+            import torch
+
+            if out is None:
+                out = torch.empty(shape, dtype=getattr(torch, dtype), device=f"cuda:{self.ctx.device}")
+            torch.cuda.current_stream(out.device).synchronize()  # the kernels run on the context's own stream
+            ptr = _device_ptr(out, "torch." + dtype, shape, "out", self.ctx.device) if rows else None
+        else:
+            if out is None:
+                out = np.empty(shape, dtype)
+            if not isinstance(out, np.ndarray) or out.shape != shape or out.dtype != np.dtype(dtype) or not out.flags.c_contiguous or \
+                    not out.flags.writeable:
+                raise ValueError(f"out must be a writeable C-contiguous {dtype} array of {shape}")
+            ptr = out.ctypes.data
+        if rows == 0:
+            return out
+        ty0, ty1 = row0 // th, -(-(row0 + rows) // th)
+        lo, hi = ty0 * lv["tiles_x"], ty1 * lv["tiles_x"]
+        offs, cnts = lv["offsets"][lo:hi], lv["counts"][lo:hi]
+        offsets = np.zeros(hi - lo + 1, np.uint64)
+        np.cumsum(cnts, out=offsets[1:])
+        packed = np.empty(max(int(offsets[-1]), 1), np.uint8)
+        for o, c, at in zip(offs, cnts, offsets[:-1]):
+            if c:
+                packed[int(at):int(at + c)] = self.buf[int(o):int(o + c)]
+        if level not in self._readers:
+            self._readers[level] = _TileReader(lv["samples"], lv["is_float"], w, h, lv["tile_w"], th, lv["predictor"], self.ctx, self.budget)
+        bad = self._readers[level].read(packed, offsets, row0, rows, ptr, on_device)
+        if bad >= 0:
+            tx, ty = bad % lv["tiles_x"], ty0 + bad // lv["tiles_x"]
+            raise GeoTiffError("corrupt", f"level {level}, tile ({tx}, {ty}): its stream is not a zlib stream of exactly "
+                                          f"{lv['tile_w'] * th * (4 if lv['is_float'] else lv['samples'])} bytes")
+        return out
+
+
+def load_geotiff(source, ctx=None, level=0, on_device=False):
+    """(raster, geo) of a tiled DEFLATE GeoTIFF (GeoTiffReader): level `level` as a numpy array (ctx None: the host route, else
+    through ctx's device) or, with on_device, a CUDA tensor on ctx's device; geo as GeoTiffReader.geo.  Measured on the
+    MI355X the device route is the slower one at 64 and at 1 024 tiles: take it for a raster that must end
+    on the device."""
+    with GeoTiffReader(source, ctx=ctx) as rd:
+        return rd.read(level=level, on_device=on_device), rd.geo
+
+
+def save_textured_obj_from_geotiff(path, surfaces, geotiff, jpeg=True, ctx=None, quality=95):
+    """generateTexturedOBJ(surfaces, geotiff_path, obj_path) (src/ortho/ortho.cpp:2052-2123): save_textured_obj with the
+    orthomosaic read from its file - `geotiff`: what GeoTiffReader takes - the geometry from the file's geotransform (gsd_x
+    and gsd_y as there) and the texture from the first min(samples, 3) samples.  With ctx the pixels go from the reader to
+    the JPEG encoder without leaving the device."""
+    with GeoTiffReader(geotiff, ctx=ctx) as rd:
+        if rd.geo is None:
+            raise GeoTiffError("unsupported", "the file has no geotransform (tags 33550 and 33922)")
+        if rd.is_float:
+            raise GeoTiffError("unsupported", "a float32 raster is not a texture")
+        g = rd.geo
+        geometry = (rd.width, rd.height, g["min_x"], g["max_y"], g["gsd_x"], g["gsd_y"])
+        raster = rd.read(on_device=ctx is not None and bool(jpeg))
+    if raster.shape[2] == 1:
+        raster = raster.expand(-1, -1, 3).contiguous() if hasattr(raster, "is_cuda") else np.repeat(raster, 3, axis=2)
+    return _save_textured_obj(path, surfaces, raster, geometry, geometry[0], geometry[1], jpeg, ctx, quality)
 
 
 # ---- the PNG codec (include/oc_host.h; DESIGN.md §4.20) ---------------------------------------------------------------------
