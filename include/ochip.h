@@ -453,6 +453,20 @@ extern "C"
     /* stepped != 0: one phase per launch (the test route; same code, same numbers).  cam_q_out [n_cams][4]: the state after
      * the last finished step, normalised as RelaxProblem::solve leaves it (:1410-1413). */
     int ochip_plane_chain_run(ochip_plane_chain *chain, int stepped, double *cam_q_out, ochip_plane_chain_result *result);
+    /* The test seam of the chain: runs it as ochip_plane_chain_run does (the same numbers, from an instantiation of the
+     * kernel the product never launches) and records what its serial part computed as events of 8-byte words: a header
+     * (kind, words including the header, index, step) and the payload of the kind - 1: a step's set-up (counts, the state,
+     * blk_cnt, inexact, cam_prior, cam_blocks, the block lists, the keep flags), 2: a finished evaluation (the state, cam_t,
+     * cost, fail bits, J'r, the clamped diagonal, J'J's lower triangle), 3: a linear solve and its candidate (radius, scale,
+     * damping, scaled gradient, the step, the model's cost change; above 12 unknowns also the factor with its augmented
+     * row and the inverses of its diagonal tiles), 4: a finished solve (termination, iterations, costs).  The layouts are
+     * the ones opencalibration_amd/capi.py parses.  Events [first_event, first_event + max_events) are written into
+     * events[capacity] as long as they fit; every event is counted: *n_events, and *n_words of the buffer are filled.
+     * capacity 0 (events may be NULL) only counts.  rays_out: NULL or [n_inliers][6], the camera-frame rays of every
+     * inlier match.  OCHIP_EINVAL, and nothing launched, for a NULL chain, cam_q_out, result, n_events or n_words. */
+    int ochip_plane_chain_trace(ochip_plane_chain *chain, int stepped, uint64_t first_event, uint64_t max_events, double *events,
+                                uint64_t capacity, uint64_t *n_events, uint64_t *n_words, double *rays_out, double *cam_q_out,
+                                ochip_plane_chain_result *result);
     void ochip_plane_chain_destroy(ochip_plane_chain *chain);
 
     /* A problem (this one and the ochip_relaxg_ / ochip_relaxp_ ones below) holds device blocks and a page-locked host

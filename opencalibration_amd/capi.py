@@ -31,7 +31,7 @@ EXPORTS = [
     "ochip_relax_problem_create", "ochip_relax_problem_destroy", "ochip_relax_set_cameras_constant",
     "ochip_relax_solve", "ochip_relax_get_state", "ochip_relax_set_shard", "ochip_relax_evaluate",
     "ochip_plane_setup_create", "ochip_plane_setup_override", "ochip_plane_setup_blocks", "ochip_plane_setup_destroy",
-    "ochip_plane_chain_create", "ochip_plane_chain_run", "ochip_plane_chain_destroy",
+    "ochip_plane_chain_create", "ochip_plane_chain_run", "ochip_plane_chain_trace", "ochip_plane_chain_destroy",
     "ochip_relaxg_problem_create", "ochip_relaxg_problem_destroy", "ochip_relaxg_set_structure_only", "ochip_relaxg_solve",
     "ochip_relaxg_get_state", "ochip_relaxg_evaluate", "ochip_relaxg_set_exchange",
     "ochip_relaxp_problem_create", "ochip_relaxp_problem_destroy", "ochip_relaxp_set_structure_only", "ochip_relaxp_solve",
@@ -478,8 +478,182 @@ class XyzExport:
             self.h = C.c_void_p()
 
 
+PLANE_EDGE_DTYPE = np.dtype([("cam_a", np.uint32), ("cam_b", np.uint32), ("model_a", np.uint32), ("model_b", np.uint32),
+                             ("n_inliers", np.uint32), ("flags", np.uint32), ("inlier_offset", np.uint64), ("H", np.float64, (9,))])
+PLANE_INLIER_DTYPE = np.dtype([("px1", np.float64, (2,)), ("px2", np.float64, (2,)), ("descriptor_score", np.float64)])
+PLANE_CHAIN_STEP_DTYPE = np.dtype([("cam", np.uint32), ("mode", np.uint32), ("n_filter", np.uint32), ("prev_cam", np.int32),
+                                   ("prev_q", np.float64, (4,)), ("tri_xy", np.float64, (6,)), ("z0", np.float64)])
+PLANE_CHAIN_RESULT_DTYPE = np.dtype([("steps_done", np.uint32), ("status", np.int32), ("solves", np.int32),
+                                     ("iterations_total", np.int32), ("last_iterations", np.int32),
+                                     ("last_residual_blocks", np.int32), ("last_initial_cost", np.float64),
+                                     ("last_final_cost", np.float64), ("grid_syncs", np.int32), ("workgroups", np.int32),
+                                     ("plane_z", np.float64, (3,))])
+TR_SETUP, TR_EVAL, TR_SOLVE, TR_FINISH = 1, 2, 3, 4
+
+
+def parse_chain_trace(words):
+    """The events of ochip_plane_chain_trace's buffer (its filled words) as dicts: kind, index, step and the payload of the
+    kind by name (csrc/relax_chain.hip: trace_setup, trace_eval, trace_solve, trace_finish).  Counts are ints, A and L are
+    dense lower triangles (L with the augmented row: (n + 1) x n), blk_idx a list of one array per edge."""
+    w = np.asarray(words, np.float64)
+    out, at = [], 0
+
+    def take(p, k, dtype=np.float64):
+        v = p[take.at:take.at + k]
+        take.at += k
+        return v.copy() if dtype is np.float64 else v.astype(dtype)
+
+    while at < len(w):
+        kind, size, index, step = (int(v) for v in w[at:at + 4])
+        assert size >= 4 and at + size <= len(w), (at, size, len(w))
+        p = w[at + 4:at + size]
+        at += size
+        ev = dict(kind=kind, index=index, step=step)
+        take.at = 0
+        if kind == TR_SETUP:
+            names = ("complete", "mode", "cam", "n_filter", "n_blocks", "n_prior", "n_live", "n_cams", "n_edges", "n_keep", "n_idx",
+                     "cur")
+            ev.update({k: int(v) for k, v in zip(names, take(p, 12))})
+            ev["plane_xy"], ev["z"] = take(p, 6), take(p, 3)
+            nc, ne = ev["n_cams"], ev["n_edges"]
+            ev["q"] = take(p, 4 * nc).reshape(nc, 4)
+            ev["blk_cnt"], ev["inexact"] = take(p, ne, np.int64), take(p, ne, np.uint8)
+            ev["cam_prior"], ev["cam_blocks"] = take(p, nc, np.uint8), take(p, nc, np.uint8)
+            off = take(p, ne + 1, np.int64)
+            idx = take(p, ev["n_idx"], np.int64)
+            ev["blk_idx"] = [idx[off[e]:off[e] + ev["blk_cnt"][e]] for e in range(ne)] if ev["n_idx"] else [idx[:0]] * ne
+            ev["keep"] = take(p, ev["n_keep"], np.uint8)
+        elif kind == TR_EVAL:
+            names = ("which", "first", "state", "set", "n", "n_active", "nz", "n_cams")
+            ev.update({k: int(v) for k, v in zip(names, take(p, 8))})
+            ev["cost"] = float(take(p, 1)[0])
+            ev["fail_bits"], ev["iter"], ev["has_diag"] = (int(v) for v in take(p, 3))
+            ev["z"] = take(p, 3)
+            nc, n = ev["n_cams"], ev["n"]
+            ev["q"], ev["cam_t"] = take(p, 4 * nc).reshape(nc, 4), take(p, nc, np.int64)
+            ev["g"], ev["diagonal"] = take(p, n), take(p, n)
+            ev["A"] = np.zeros((n, n))
+            ev["A"][np.tril_indices(n)] = take(p, n * (n + 1) // 2)
+        elif kind == TR_SOLVE:
+            names = ("which", "iter", "tiles", "n", "n_active", "nz", "n_cams", "cur")
+            ev.update({k: int(v) for k, v in zip(names, take(p, 8))})
+            for k, v in zip(("radius", "mcc"), take(p, 2)):
+                ev[k] = float(v)
+            ev["chol_fail"] = int(take(p, 1)[0])
+            for k, v in zip(("step_norm2", "cand_norm2", "x_norm", "x_cost"), take(p, 4)):
+                ev[k] = float(v)
+            ev["nbc"] = int(take(p, 1)[0])
+            ev["z"] = take(p, 3)
+            nc, n = ev["n_cams"], ev["n"]
+            ev["q"] = take(p, 4 * nc).reshape(nc, 4)
+            ev["scale"], ev["lm_diag"], ev["gs"], ev["x"] = take(p, n), take(p, n), take(p, n), take(p, n)
+            if ev["tiles"]:
+                L = np.zeros((n + 1, n))
+                L[:n][np.tril_indices(n)] = take(p, n * (n + 1) // 2)
+                L[n] = take(p, n)
+                ev["L"], ev["linv"] = L, take(p, ev["nbc"] * 4096).reshape(ev["nbc"], 64, 64)
+        elif kind == TR_FINISH:
+            v = take(p, 8)
+            ev.update(which=int(v[0]), termination=int(v[1]), iterations=int(v[2]), initial_cost=float(v[3]), final_cost=float(v[4]),
+                      successful=int(v[5]), unsuccessful=int(v[6]), radius=float(v[7]))
+        else:
+            raise OchipError(f"ochip_plane_chain_trace: event {index} of unknown kind {kind}")
+        assert take.at == len(p), (kind, take.at, len(p))
+        out.append(ev)
+    return out
+
+
+class PlaneChain:
+    """An ochip_plane_chain (the NaN bootstrap of runGroundPlane as one resident launch).  edges, inliers, steps: arrays of
+    PLANE_EDGE_DTYPE, PLANE_INLIER_DTYPE, PLANE_CHAIN_STEP_DTYPE; models10 [n_models][10]."""
+
+    def __init__(self, ctx, edges, inliers, cam_pos, cam_q, cam_optimize, models10, grid_fraction, huber_a, prior_weight, steps):
+        self.ctx, self.L = ctx, ctx.L
+        L = self.L
+        vp, u32, u64, dbl = C.c_void_p, C.c_uint32, C.c_uint64, C.c_double
+        L.ochip_plane_chain_create.argtypes = [vp, vp, u32, vp, u64, vp, vp, vp, u32, vp, u32, dbl, dbl, dbl, vp, u32, C.POINTER(vp)]
+        L.ochip_plane_chain_run.argtypes = [vp, C.c_int, vp, vp]
+        L.ochip_plane_chain_trace.argtypes = [vp, C.c_int, u64, u64, vp, u64, C.POINTER(u64), C.POINTER(u64), vp, vp, vp]
+        L.ochip_plane_chain_destroy.argtypes = [vp]
+        L.ochip_plane_chain_destroy.restype = None
+        edges = np.ascontiguousarray(edges, PLANE_EDGE_DTYPE)
+        inliers = np.ascontiguousarray(inliers, PLANE_INLIER_DTYPE)
+        steps = np.ascontiguousarray(steps, PLANE_CHAIN_STEP_DTYPE)
+        cam_pos = np.ascontiguousarray(cam_pos, np.float64).reshape(-1, 3)
+        cam_q = np.ascontiguousarray(cam_q, np.float64).reshape(-1, 4)
+        cam_optimize = np.ascontiguousarray(cam_optimize, np.uint8)
+        models10 = np.ascontiguousarray(models10, np.float64).reshape(-1, 10)
+        assert len(cam_q) == len(cam_pos) == len(cam_optimize)
+        self.n_cams, self.n_inliers = len(cam_pos), len(inliers)
+        self.h = vp()
+        ctx._check(L.ochip_plane_chain_create(ctx.h, edges.ctypes.data if len(edges) else None, len(edges),
+                                              inliers.ctypes.data if len(inliers) else None, len(inliers), cam_pos.ctypes.data,
+                                              cam_q.ctypes.data, cam_optimize.ctypes.data, len(cam_pos), models10.ctypes.data,
+                                              len(models10), grid_fraction, huber_a, prior_weight,
+                                              steps.ctypes.data if len(steps) else None, len(steps), C.byref(self.h)),
+                   "ochip_plane_chain_create")
+
+    def run(self, stepped=False):
+        """ochip_plane_chain_run: (cam_q [n_cams][4], the result struct as a numpy record)"""
+        q, res = np.zeros((self.n_cams, 4)), np.zeros(1, PLANE_CHAIN_RESULT_DTYPE)
+        self.ctx._check(self.L.ochip_plane_chain_run(self.h, int(stepped), q.ctypes.data, res.ctypes.data), "ochip_plane_chain_run")
+        return q, res[0]
+
+    def trace(self, stepped=False, first_event=0, max_events=2 ** 62, capacity=1 << 22):
+        """ochip_plane_chain_trace: dict(cam_q, result, n_events, n_words, events = parse_chain_trace of the filled words,
+        rays [n_inliers][6])."""
+        q, res = np.zeros((self.n_cams, 4)), np.zeros(1, PLANE_CHAIN_RESULT_DTYPE)
+        words, rays = np.zeros(max(int(capacity), 1)), np.zeros((max(self.n_inliers, 1), 6))
+        n_events, n_words = C.c_uint64(0), C.c_uint64(0)
+        self.ctx._check(self.L.ochip_plane_chain_trace(self.h, int(stepped), int(first_event), int(max_events),
+                                                       words.ctypes.data if capacity else None, int(capacity), C.byref(n_events),
+                                                       C.byref(n_words), rays.ctypes.data, q.ctypes.data, res.ctypes.data),
+                        "ochip_plane_chain_trace")
+        return dict(cam_q=q, result=res[0], n_events=int(n_events.value), n_words=int(n_words.value),
+                    events=parse_chain_trace(words[:n_words.value]), rays=rays[:self.n_inliers])
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.L.ochip_plane_chain_destroy(self.h)
+            self.h = None
+
+
 class Context:
     """Owns one ochip_ctx (one GPU)."""
+
+    def plane_setup(self, edges, inliers, cam_pos, cam_q, models10, triangle_xy6, grid_fraction):
+        """ochip_plane_setup_create + ochip_plane_setup_blocks + destroy: dict(keep [n_inliers], inexact [n_edges], blk_cam_a,
+        blk_cam_b, blk_rays [n_blocks][6]); the blocks are None when an edge is inexact."""
+        L = self.L
+        vp, u32, u64 = C.c_void_p, C.c_uint32, C.c_uint64
+        L.ochip_plane_setup_create.argtypes = [vp, vp, u32, vp, u64, vp, vp, u32, vp, u32, vp, C.c_double, vp, vp, C.POINTER(vp)]
+        L.ochip_plane_setup_blocks.argtypes = [vp, vp, vp, vp, u64, C.POINTER(u64)]
+        L.ochip_plane_setup_destroy.argtypes = [vp]
+        L.ochip_plane_setup_destroy.restype = None
+        edges = np.ascontiguousarray(edges, PLANE_EDGE_DTYPE)
+        inliers = np.ascontiguousarray(inliers, PLANE_INLIER_DTYPE)
+        cam_pos = np.ascontiguousarray(cam_pos, np.float64).reshape(-1, 3)
+        cam_q = np.ascontiguousarray(cam_q, np.float64).reshape(-1, 4)
+        models10 = np.ascontiguousarray(models10, np.float64).reshape(-1, 10)
+        tri = np.ascontiguousarray(triangle_xy6, np.float64).reshape(6)
+        keep, inexact = np.zeros(max(len(inliers), 1), np.uint8), np.zeros(max(len(edges), 1), np.uint8)
+        h = vp()
+        self._check(L.ochip_plane_setup_create(self.h, edges.ctypes.data, len(edges), inliers.ctypes.data, len(inliers),
+                                               cam_pos.ctypes.data, cam_q.ctypes.data, len(cam_pos), models10.ctypes.data, len(models10),
+                                               tri.ctypes.data, grid_fraction, keep.ctypes.data, inexact.ctypes.data, C.byref(h)),
+                    "ochip_plane_setup_create")
+        out = dict(keep=keep[:len(inliers)], inexact=inexact[:len(edges)], blk_cam_a=None, blk_cam_b=None, blk_rays=None)
+        try:
+            if not inexact.any():
+                n = u64(0)
+                self._check(L.ochip_plane_setup_blocks(h, None, None, None, 0, C.byref(n)), "ochip_plane_setup_blocks")
+                a, b, r = np.zeros(max(n.value, 1), np.uint32), np.zeros(max(n.value, 1), np.uint32), np.zeros((max(n.value, 1), 6))
+                self._check(L.ochip_plane_setup_blocks(h, a.ctypes.data, b.ctypes.data, r.ctypes.data, n.value, C.byref(n)),
+                            "ochip_plane_setup_blocks")
+                out.update(blk_cam_a=a[:n.value], blk_cam_b=b[:n.value], blk_rays=r[:n.value])
+        finally:
+            L.ochip_plane_setup_destroy(h)
+        return out
 
     def __init__(self, device=0):
         self.L = load()

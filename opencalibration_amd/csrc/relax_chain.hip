@@ -31,6 +31,7 @@
 #include <cstring>
 #include <map>
 #include <mutex>
+#include <type_traits>
 #include <vector>
 
 using namespace ochip;
@@ -1005,6 +1006,31 @@ __device__ void phase_chol(const chain_dev &D, unsigned char *lds)
 // workgroup's copy of the control block in LDS (written back before the sync releases the others).  The parts hand each
 // other on through an action code (no recursion: a finished solve may start the next solve, the next step, ... inside the
 // same epilogue); every decision is taken from values all threads read alike, so the control flow is uniform.
+// The trace seam (ochip_plane_chain_trace): the TRACE instantiation of the serial part writes what it has just computed
+// as events of 8-byte words into a caller-sized buffer - plain stores by the workgroup that runs the epilogue, no sync, no
+// spin, no atomic of its own.  An event is a 4-word header (kind, words with the header, index, step) and its payload
+// (the layouts: capi.py, parse_chain_trace); one outside [first_event, first_event + max_events) or one that no longer
+// fits is counted and not written.  The product's instantiation holds none of it.
+enum
+{
+    TR_SETUP = 1,
+    TR_EVAL = 2,
+    TR_SOLVE = 3,
+    TR_FINISH = 4
+};
+
+struct chain_trace_state
+{
+    unsigned long long n_events, n_words;
+};
+
+struct chain_trace
+{
+    double *buf;
+    unsigned long long capacity, first_event, max_events;
+    chain_trace_state *state;
+};
+
 enum
 {
     ACT_NONE = 0,
@@ -1021,7 +1047,19 @@ enum
     ACT_CANDIDATE
 };
 
-struct epi
+template <bool TRACE> struct epi_trace
+{
+};
+template <> struct epi_trace<true> // the buffer and this workgroup's copy of its fill state (LDS)
+{
+    const chain_trace *T = nullptr;
+    chain_trace_state *S = nullptr;
+};
+struct no_trace
+{
+};
+
+template <bool TRACE> struct epi : epi_trace<TRACE>
 {
     const chain_dev &D;
     chain_ctl &C;
@@ -1031,6 +1069,166 @@ struct epi
     // arguments of the next action
     int arg_step = 0, arg_which = 0, arg_termination = 0;
     bool arg_count_cost = false;
+
+    // opens an event of `words` payload words: where they go, or nullptr for an event that is only counted
+    __device__ double *trace_open(int kind, unsigned long long words)
+    {
+        __syncthreads();
+        const unsigned long long idx = this->S->n_events, used = this->S->n_words;
+        const chain_trace &tr = *this->T;
+        const bool in = idx >= tr.first_event && idx - tr.first_event < tr.max_events && used + 4 + words <= tr.capacity;
+        __syncthreads();
+        if (t == 0)
+        {
+            this->S->n_events = idx + 1;
+            if (in)
+                this->S->n_words = used + 4 + words;
+        }
+        if (!in)
+            return nullptr;
+        double *o = tr.buf + used;
+        if (t == 0)
+        {
+            o[0] = (double)kind;
+            o[1] = (double)(4 + words);
+            o[2] = (double)idx;
+            o[3] = (double)C.step;
+        }
+        return o + 4;
+    }
+
+    // what the step's set-up left (complete: 0 where a tie hands the step over before the priors are counted)
+    __device__ void trace_setup(int complete, int n_blocks)
+    {
+        const uint32_t nc = D.n_cams, ne = D.n_edges;
+        const unsigned long long n_keep = C.n_filter > 0 ? D.n_inliers : 0ull, n_idx = C.n_filter > 0 ? D.blk_off[ne] : 0u;
+        double *o = trace_open(TR_SETUP, 21 + 6ull * nc + 3ull * ne + 1 + n_idx + n_keep);
+        if (!o)
+            return;
+        const int cur = C.cur;
+        if (t == 0)
+        {
+            o[0] = complete, o[1] = C.mode, o[2] = C.cam, o[3] = C.n_filter, o[4] = n_blocks, o[5] = C.n_prior;
+            o[6] = C.n_live, o[7] = nc, o[8] = ne, o[9] = (double)n_keep, o[10] = (double)n_idx, o[11] = cur;
+            for (int k = 0; k < 6; k++)
+                o[12 + k] = C.plane_xy[k];
+            for (int k = 0; k < 3; k++)
+                o[18 + k] = C.z[cur][k];
+        }
+        o += 21;
+        for (uint32_t i = t; i < 4 * nc; i += TG)
+            o[i] = D.q[cur][i];
+        o += 4 * nc;
+        for (uint32_t e = t; e < ne; e += TG)
+        {
+            o[e] = (double)D.blk_cnt[e];
+            o[ne + e] = (double)D.inexact[e];
+        }
+        o += 2 * ne;
+        for (uint32_t c = t; c < nc; c += TG)
+        {
+            o[c] = (double)D.cam_prior[c];
+            o[nc + c] = (double)D.cam_blocks[c];
+        }
+        o += 2 * nc;
+        for (uint32_t e = t; e <= ne; e += TG)
+            o[e] = (double)D.blk_off[e];
+        o += ne + 1;
+        for (unsigned long long i = t; i < n_idx; i += TG)
+            o[i] = (double)D.blk_idx[i];
+        o += n_idx;
+        for (unsigned long long i = t; i < n_keep; i += TG)
+            o[i] = (double)D.keep[i];
+    }
+
+    // a finished evaluation: the state it read, J'J's lower triangle, J'r, the cost, the clamped diagonal (has_diag)
+    __device__ void trace_eval(int set, double cost, int fail_bits, int first, int has_diag)
+    {
+        const uint32_t nc = D.n_cams;
+        const int n = C.n, state = C.eval_state;
+        double *o = trace_open(TR_EVAL, 15 + 5ull * nc + 2ull * n + (unsigned long long)n * (n + 1) / 2);
+        if (!o)
+            return;
+        if (t == 0)
+        {
+            o[0] = C.which, o[1] = first, o[2] = state, o[3] = set, o[4] = n, o[5] = C.n_active, o[6] = C.nz, o[7] = nc;
+            o[8] = cost, o[9] = fail_bits, o[10] = C.iter, o[11] = has_diag;
+            for (int k = 0; k < 3; k++)
+                o[12 + k] = C.z[state][k];
+        }
+        o += 15;
+        for (uint32_t i = t; i < 4 * nc; i += TG)
+            o[i] = D.q[state][i];
+        o += 4 * nc;
+        for (uint32_t c = t; c < nc; c += TG)
+            o[c] = (double)D.cam_t[c];
+        o += nc;
+        for (int i = t; i < n; i += TG)
+        {
+            o[i] = D.g[set][i];
+            o[n + i] = has_diag ? D.diagonal[set][i] : 0.0;
+        }
+        o += 2 * n;
+        const double *A = D.A[set];
+        for (int e = t; e < n * n; e += TG)
+        {
+            const int i = e / n, j = e % n;
+            if (j <= i)
+                o[i * (i + 1) / 2 + j] = A[at(i, j)];
+        }
+    }
+
+    // a finished linear solve and the candidate made of it; tile route: the factor with its augmented row, and linv
+    __device__ void trace_solve()
+    {
+        const uint32_t nc = D.n_cams;
+        const int n = C.n, cur = C.cur, tiles = n > N_SMALL ? 1 : 0, nbc = C.nbc;
+        const unsigned long long factor = tiles ? (unsigned long long)n * (n + 1) / 2 + n : 0ull;
+        const unsigned long long inv = tiles ? (unsigned long long)nbc * NB * NB : 0ull;
+        double *o = trace_open(TR_SOLVE, 19 + 4ull * nc + 4ull * n + factor + inv);
+        if (!o)
+            return;
+        if (t == 0)
+        {
+            o[0] = C.which, o[1] = C.iter, o[2] = tiles, o[3] = n, o[4] = C.n_active, o[5] = C.nz, o[6] = nc, o[7] = cur;
+            o[8] = C.trust.radius, o[9] = C.mcc, o[10] = C.chol_fail, o[11] = C.step_norm2, o[12] = C.cand_norm2;
+            o[13] = C.x_norm, o[14] = C.x_cost, o[15] = nbc;
+            for (int k = 0; k < 3; k++)
+                o[16 + k] = C.z[cur][k];
+        }
+        o += 19;
+        for (uint32_t i = t; i < 4 * nc; i += TG)
+            o[i] = D.q[cur][i];
+        o += 4 * nc;
+        for (int i = t; i < n; i += TG)
+        {
+            o[i] = D.scale[i];
+            o[n + i] = D.lm_diag[i];
+            o[2 * n + i] = D.gs[i];
+            o[3 * n + i] = xs[i];
+        }
+        o += 4 * n;
+        if (!tiles)
+            return;
+        for (int e = t; e < (n + 1) * n; e += TG)
+        {
+            const int i = e / n, j = e % n;
+            if (j <= i)
+                o[i < n ? i * (i + 1) / 2 + j : n * (n + 1) / 2 + j] = D.W[at(i, j)];
+        }
+        o += factor;
+        for (unsigned long long i = t; i < inv; i += TG)
+            o[i] = D.linv[i];
+    }
+
+    __device__ void trace_finish()
+    {
+        double *o = trace_open(TR_FINISH, 8);
+        if (!o || t != 0)
+            return;
+        o[0] = C.which, o[1] = C.last_termination, o[2] = C.last_iterations, o[3] = C.last_initial_cost, o[4] = C.last_final_cost;
+        o[5] = C.successful, o[6] = C.unsuccessful, o[7] = C.trust.radius;
+    }
 
     __device__ bool optimised(uint32_t c) const
     {
@@ -1116,6 +1314,8 @@ struct epi
             C.n_prior = (int)n_prior;
         }
         __syncthreads();
+        if constexpr (TRACE)
+            trace_setup(1, 0);
         arg_which = 0;
         return ACT_BEGIN_SOLVE;
     }
@@ -1187,6 +1387,8 @@ struct epi
                 C.phase = PH_DONE;
             }
             __syncthreads();
+            if constexpr (TRACE)
+                trace_setup(0, (int)n_blocks);
             return ACT_NONE;
         }
         // the chunks that hold blocks, ascending: every thread takes a run of chunks, counts, an exclusive scan places them
@@ -1234,6 +1436,8 @@ struct epi
             C.n_prior = (int)n_prior;
         }
         __syncthreads();
+        if constexpr (TRACE)
+            trace_setup(1, (int)n_blocks);
         arg_which = 0;
         return ACT_BEGIN_SOLVE;
     }
@@ -1337,6 +1541,8 @@ struct epi
             C.last_final_cost = arg_count_cost ? C.x_cost : 0.0;
         }
         __syncthreads();
+        if constexpr (TRACE)
+            trace_finish();
         return ACT_AFTER_SOLVE;
     }
 
@@ -1455,7 +1661,11 @@ struct epi
         if (first)
         {
             if (fail_bits)
+            {
+                if constexpr (TRACE)
+                    trace_eval(set, cost, fail_bits, 1, 0);
                 return finish_with(OCHIP_RELAX_FAILURE, false);
+            }
             // jacobi scaling, fixed from the first Jacobian; the damping's clamped diagonal; max |g|
             double m = 0;
             for (int i = t; i < n; i += TG)
@@ -1467,6 +1677,8 @@ struct epi
                 m = fmax(m, fabs(g[i]));
             }
             const double gmax = reduce_max(m);
+            if constexpr (TRACE)
+                trace_eval(set, cost, fail_bits, 1, 1);
             double xn_part = 0;
             {
                 const double *Q = D.q[C.cur];
@@ -1501,6 +1713,8 @@ struct epi
             m = fmax(m, fabs(g[i]));
         }
         const double gmax2 = reduce_max(m);
+        if constexpr (TRACE)
+            trace_eval(set, cost, fail_bits, 0, 1);
         // the trust-region logic of lm_solve (relax_lm.hip): every thread takes the same decisions, thread 0 keeps the state
         const double mcc = C.mcc, x_cost = C.x_cost, x_norm = C.x_norm;
         const double step_norm = sqrt(C.step_norm2), cand_norm = sqrt(C.cand_norm2);
@@ -1656,6 +1870,11 @@ struct epi
             {
                 xs[i] = y[i];
                 part += y[i] * gs[i] + lm[i] * y[i] * y[i];
+                if constexpr (TRACE) // (the tile route's arrays are free on this one)
+                {
+                    D.lm_diag[i] = lm[i];
+                    D.gs[i] = gs[i];
+                }
             }
             C.mcc = 0.5 * part;
             C.chol_fail = bad ? 1 : 0;
@@ -1768,6 +1987,8 @@ struct epi
             C.phase = PH_EVAL;
         }
         __syncthreads();
+        if constexpr (TRACE)
+            trace_solve();
         return (C.n_live == 0 && C.n <= N_SMALL) ? ACT_EVAL_SERIAL : ACT_NONE;
     }
 
@@ -1841,7 +2062,9 @@ struct epi
     }
 };
 
-__global__ __launch_bounds__(TG) void plane_chain_kernel(chain_dev D, int stepped)
+// TRACE: the same chain with the trace seam compiled in (ochip_plane_chain_trace; the product never launches it)
+template <bool TRACE>
+__global__ __launch_bounds__(TG) void plane_chain_kernel(chain_dev D, int stepped, std::conditional_t<TRACE, chain_trace, no_trace> T)
 {
     extern __shared__ __align__(16) unsigned char lds[];
     __shared__ chain_ctl s_ctl;
@@ -1888,8 +2111,26 @@ __global__ __launch_bounds__(TG) void plane_chain_kernel(chain_dev D, int steppe
                 s_ctl.n_phase[phase]++;
             }
             __syncthreads();
-            epi E{D, s_ctl, s_sh, reinterpret_cast<double *>(lds), (int)threadIdx.x};
-            E.advance(phase);
+            epi<TRACE> E{{}, D, s_ctl, s_sh, reinterpret_cast<double *>(lds), (int)threadIdx.x};
+            if constexpr (TRACE)
+            {
+                // the trace's fill state the way the control block travels: through LDS, back before the release
+                __shared__ chain_trace_state s_tr;
+                if (threadIdx.x == 0)
+                {
+                    s_tr.n_events = __hip_atomic_load(&T.state->n_events, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    s_tr.n_words = __hip_atomic_load(&T.state->n_words, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                }
+                __syncthreads();
+                E.T = &T;
+                E.S = &s_tr;
+                E.advance(phase);
+                __syncthreads();
+                if (threadIdx.x == 0)
+                    *T.state = s_tr;
+            }
+            else
+                E.advance(phase);
             __syncthreads();
             if (threadIdx.x == 0)
             {
@@ -1937,6 +2178,75 @@ struct ochip_plane_chain
         return e;
     }
 };
+
+// one run of the chain, resident or one phase per launch; trace: the instantiation with the trace seam
+static int chain_run(ochip_plane_chain *c, int stepped, const chain_trace *trace, double *cam_q_out, ochip_plane_chain_result *result)
+{
+    ochip_ctx *ctx = c->ctx;
+    hipStream_t st = ctx->stream;
+    auto launch = [&](int one_phase) {
+        if (trace)
+            hipLaunchKernelGGL(plane_chain_kernel<true>, dim3(c->grid), dim3(TG), LDS_EVAL, st, c->dev, one_phase, *trace);
+        else
+            hipLaunchKernelGGL(plane_chain_kernel<false>, dim3(c->grid), dim3(TG), LDS_EVAL, st, c->dev, one_phase, no_trace{});
+    };
+    std::memset(result, 0, sizeof *result);
+    {
+        std::lock_guard<std::mutex> lk(g_chain_mutex);
+        if (!stepped)
+        {
+            launch(0);
+            OCHIP_HIP(ctx, hipGetLastError());
+            OCHIP_HIP(ctx, c->read_back(st, true));
+            OCHIP_HIP(ctx, ochip_stream_wait(ctx, st));
+        }
+        else
+        {
+            // the test route: one phase per launch, the control block read back in between
+            for (long launches = 0;; launches++)
+            {
+                launch(1);
+                OCHIP_HIP(ctx, hipGetLastError());
+                OCHIP_HIP(ctx, c->read_back(st, false));
+                OCHIP_HIP(ctx, ochip_stream_wait(ctx, st));
+                if (c->ctl_host->phase == PH_DONE || *c->abort_host() != 0u)
+                    break;
+                if (launches > 50000000)
+                    return ochip_fail(ctx, OCHIP_EHIP, "ochip_plane_chain_run: the stepped chain does not end");
+            }
+            OCHIP_HIP(ctx, c->read_back(st, true));
+            OCHIP_HIP(ctx, ochip_stream_wait(ctx, st));
+        }
+        if (*c->abort_host() != 0u)
+            c->ctl_host->status = CHAIN_ABORTED;
+    }
+    const chain_ctl &C = *c->ctl_host;
+    std::memcpy(cam_q_out, c->q_host(), (size_t)c->n_cams * 32);
+    result->steps_done = (uint32_t)C.steps_done;
+    result->status = C.status == CHAIN_FINISHED ? 0 : (C.status == CHAIN_INEXACT ? 1 : 2);
+    result->solves = C.solves;
+    result->iterations_total = C.iterations_total;
+    result->last_iterations = C.last_iterations;
+    result->last_residual_blocks = C.last_blocks;
+    result->last_initial_cost = C.last_initial_cost;
+    result->last_final_cost = C.last_final_cost;
+    result->grid_syncs = C.syncs;
+    result->workgroups = c->grid;
+    for (int i = 0; i < 3; i++)
+        result->plane_z[i] = C.z[C.cur][i];
+    if (ochip_verbose("relax"))
+    {
+        static const char *names[7] = {"rays", "set-up", "evaluate", "assemble", "factor", "-", "-"};
+        for (int p = 0; p < PH_DONE; p++)
+            if (C.n_phase[p])
+                fprintf(stderr, "[relax chain]   %-9s %7llu times, parallel part + sync %9.3f ms (%6.1f us each), serial part behind it %9.3f ms (%6.1f us each)\n",
+                        names[p], C.n_phase[p], C.t_phase[p] * 1e-5, C.t_phase[p] * 1e-2 / (double)C.n_phase[p], C.t_epilogue[p] * 1e-5,
+                        C.t_epilogue[p] * 1e-2 / (double)C.n_phase[p]);
+    }
+    if (C.status == CHAIN_RUNNING)
+        return ochip_fail(ctx, OCHIP_EHIP, "ochip_plane_chain_run: the chain left its launch unfinished (phase %d, step %d)", C.phase, C.step);
+    return OCHIP_OK;
+}
 
 extern "C"
 {
@@ -2137,7 +2447,7 @@ int ochip_plane_chain_create(ochip_ctx *ctx, const ochip_plane_edge *edges, uint
     // the other seven wave slots of every SIMD, stay with the extraction and the link stage of the batches behind this
     // one); OCHIP_CHAIN_WORKGROUPS overrides (processes that share a device in the tests)
     int per_cu = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, plane_chain_kernel, TG, LDS_EVAL) != hipSuccess || per_cu < 1)
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, plane_chain_kernel<false>, TG, LDS_EVAL) != hipSuccess || per_cu < 1)
         per_cu = 1;
     unsigned int grid = (unsigned int)std::max(1, ctx->prop.multiProcessorCount / 2);
     if (const char *env = std::getenv("OCHIP_CHAIN_WORKGROUPS"))
@@ -2175,7 +2485,7 @@ int ochip_plane_chain_create(ochip_ctx *ctx, const ochip_plane_edge *edges, uint
         if (e == hipSuccess)
             e = hipMemcpyAsync(D.q_commit, D.q[0], (size_t)n_cams * 32, hipMemcpyDeviceToDevice, st);
         if (e == hipSuccess)
-            e = hipFuncSetAttribute(reinterpret_cast<const void *>(plane_chain_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_EVAL);
+            e = hipFuncSetAttribute(reinterpret_cast<const void *>(plane_chain_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_EVAL);
         if (e == hipSuccess)
             e = ochip_stream_wait(ctx, st); // (the staging block goes back to the pool)
         if (e != hipSuccess)
@@ -2196,65 +2506,45 @@ int ochip_plane_chain_run(ochip_plane_chain *c, int stepped, double *cam_q_out, 
 {
     if (!c || !cam_q_out || !result)
         return OCHIP_EINVAL;
+    OCHIP_HIP(c->ctx, hipSetDevice(c->ctx->device));
+    return chain_run(c, stepped, nullptr, cam_q_out, result);
+}
+
+int ochip_plane_chain_trace(ochip_plane_chain *c, int stepped, uint64_t first_event, uint64_t max_events, double *events, uint64_t capacity,
+                            uint64_t *n_events, uint64_t *n_words, double *rays_out, double *cam_q_out, ochip_plane_chain_result *result)
+{
+    if (!c || !cam_q_out || !result || !n_events || !n_words || (capacity && !events))
+        return OCHIP_EINVAL;
     ochip_ctx *ctx = c->ctx;
     OCHIP_HIP(ctx, hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
-    std::memset(result, 0, sizeof *result);
-    {
-        std::lock_guard<std::mutex> lk(g_chain_mutex);
-        if (!stepped)
-        {
-            hipLaunchKernelGGL(plane_chain_kernel, dim3(c->grid), dim3(TG), LDS_EVAL, st, c->dev, 0);
-            OCHIP_HIP(ctx, hipGetLastError());
-            OCHIP_HIP(ctx, c->read_back(st, true));
-            OCHIP_HIP(ctx, ochip_stream_wait(ctx, st));
-        }
-        else
-        {
-            // the test route: one phase per launch, the control block read back in between
-            for (long launches = 0;; launches++)
-            {
-                hipLaunchKernelGGL(plane_chain_kernel, dim3(c->grid), dim3(TG), LDS_EVAL, st, c->dev, 1);
-                OCHIP_HIP(ctx, hipGetLastError());
-                OCHIP_HIP(ctx, c->read_back(st, false));
-                OCHIP_HIP(ctx, ochip_stream_wait(ctx, st));
-                if (c->ctl_host->phase == PH_DONE || *c->abort_host() != 0u)
-                    break;
-                if (launches > 50000000)
-                    return ochip_fail(ctx, OCHIP_EHIP, "ochip_plane_chain_run: the stepped chain does not end");
-            }
-            OCHIP_HIP(ctx, c->read_back(st, true));
-            OCHIP_HIP(ctx, ochip_stream_wait(ctx, st));
-        }
-        if (*c->abort_host() != 0u)
-            c->ctl_host->status = CHAIN_ABORTED;
-    }
-    const chain_ctl &C = *c->ctl_host;
-    std::memcpy(cam_q_out, c->q_host(), (size_t)c->n_cams * 32);
-    result->steps_done = (uint32_t)C.steps_done;
-    result->status = C.status == CHAIN_FINISHED ? 0 : (C.status == CHAIN_INEXACT ? 1 : 2);
-    result->solves = C.solves;
-    result->iterations_total = C.iterations_total;
-    result->last_iterations = C.last_iterations;
-    result->last_residual_blocks = C.last_blocks;
-    result->last_initial_cost = C.last_initial_cost;
-    result->last_final_cost = C.last_final_cost;
-    result->grid_syncs = C.syncs;
-    result->workgroups = c->grid;
-    for (int i = 0; i < 3; i++)
-        result->plane_z[i] = C.z[C.cur][i];
-    if (ochip_verbose("relax"))
-    {
-        static const char *names[7] = {"rays", "set-up", "evaluate", "assemble", "factor", "-", "-"};
-        for (int p = 0; p < PH_DONE; p++)
-            if (C.n_phase[p])
-                fprintf(stderr, "[relax chain]   %-9s %7llu times, parallel part + sync %9.3f ms (%6.1f us each), serial part behind it %9.3f ms (%6.1f us each)\n",
-                        names[p], C.n_phase[p], C.t_phase[p] * 1e-5, C.t_phase[p] * 1e-2 / (double)C.n_phase[p], C.t_epilogue[p] * 1e-5,
-                        C.t_epilogue[p] * 1e-2 / (double)C.n_phase[p]);
-    }
-    if (C.status == CHAIN_RUNNING)
-        return ochip_fail(ctx, OCHIP_EHIP, "ochip_plane_chain_run: the chain left its launch unfinished (phase %d, step %d)", C.phase, C.step);
-    return OCHIP_OK;
+    *n_events = *n_words = 0;
+    chain_trace T{};
+    T.buf = (double *)c->mem.get(std::max<uint64_t>(capacity, 1) * 8);
+    T.state = (chain_trace_state *)c->mem.get(sizeof(chain_trace_state));
+    if (!T.buf || !T.state)
+        return ochip_fail(ctx, OCHIP_ENOMEM, "ochip_plane_chain_trace: no room for %llu words", (unsigned long long)capacity);
+    T.capacity = capacity;
+    T.first_event = first_event;
+    T.max_events = max_events;
+    OCHIP_HIP(ctx, hipMemsetAsync(T.state, 0, sizeof(chain_trace_state), st));
+    OCHIP_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(plane_chain_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                       (int)LDS_EVAL));
+    const int rc = chain_run(c, stepped, &T, cam_q_out, result);
+    chain_trace_state fill{};
+    OCHIP_HIP(ctx, hipMemcpyAsync(&fill, T.state, sizeof fill, hipMemcpyDeviceToHost, st));
+    OCHIP_HIP(ctx, ochip_stream_wait(ctx, st));
+    if (fill.n_words > capacity)
+        return ochip_fail(ctx, OCHIP_EHIP, "ochip_plane_chain_trace: %llu words in a buffer of %llu", (unsigned long long)fill.n_words,
+                          (unsigned long long)capacity);
+    if (fill.n_words)
+        OCHIP_HIP(ctx, hipMemcpyAsync(events, T.buf, fill.n_words * 8, hipMemcpyDeviceToHost, st));
+    if (rays_out && c->dev.n_inliers)
+        OCHIP_HIP(ctx, hipMemcpyAsync(rays_out, c->dev.rays, c->dev.n_inliers * 48, hipMemcpyDeviceToHost, st));
+    OCHIP_HIP(ctx, ochip_stream_wait(ctx, st));
+    *n_events = fill.n_events;
+    *n_words = fill.n_words;
+    return rc;
 }
 
 } // extern "C"

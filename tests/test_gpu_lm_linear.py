@@ -2,8 +2,9 @@
 chain, back_solve_kernel / back_solve_regions_kernel, as lm_solve launches them) against a plain fp64 / longdouble
 reference (tests/lm_fixtures.py): W bit for bit, the factor, the forward and backward solves and the model cost change
 within componentwise bounds, failure flags, repeatability of the dynamically claimed tile factorisation, and the plan's
-claim order.  Not covered here: the resident chain's factorisation (relax_chain.hip) and the Schur elimination of the 3-D
-points (relax_points.hip)."""
+claim order.  The resident chain's factorisations (relax_chain.hip: phase_chol and the one-thread Cholesky of small systems) are
+held to the same bounds through the chain's trace seam by tests/test_gpu_chain_trace.py.  Not covered here: the Schur
+elimination of the 3-D points (relax_points.hip)."""
 import json
 
 import numpy as np

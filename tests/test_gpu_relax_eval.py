@@ -4,8 +4,8 @@ fixtures of tests/relax_eval_fixtures.py: cost, J'J and J'r within the normwise 
 a failing block reported as a failure.  The worst error-to-bound ratios are printed (RELAX_EVAL_RATIOS).
 
 The plane engine (relax.hip) is covered the same way by tests/test_gpu_relax_plane_eval.py, and the points engine
-(relax_points.hip: its evaluation and its Schur step) by tests/test_gpu_relaxp_eval.py.  Not covered: the resident chain's
-copy of the plane evaluation (relax_chain.hip), which has no evaluation seam of its own yet."""
+(relax_points.hip: its evaluation and its Schur step) by tests/test_gpu_relaxp_eval.py.  The resident chain's copy of the
+plane evaluation (relax_chain.hip) is held to the same bounds through its trace seam by tests/test_gpu_chain_trace.py."""
 import json
 
 import numpy as np
