@@ -526,7 +526,21 @@ extern "C"
      * render(k - 2) has returned, a late one once render(k - 1) has; render(k) is refused while a planned load of k is
      * missing; an upload that is not planned, or made twice, is refused.  rewind (after the last band): a further sweep,
      * planned from the images the slots hold.  upload_end_ms: when band's last upload finished on the device, in ms since
-     * the sweep began.  -1 + och_ortho_stream_last_error() on failure. */
+     * the sweep began.  -1 + och_ortho_stream_last_error() on failure.
+     * upload_jpegs (the reference's cv::imread in FullResolutionImageCache::getImage,
+     * src/ortho/image_cache.cpp:37): n planned loads of `band` from baseline JPEG files, files[i] / sizes[i] (host memory)
+     * being involved camera cameras[i]'s, decoded by one och_jpeg_decoder the stream owns - made at the first call, on the
+     * stream's route, destroyed with it - straight into the planned slots: out is the slot block, offsets[i] the slot's
+     * distance from its start, the EXIF orientation applied.  Before a byte is parsed every camera passes upload's checks
+     * (a planned load of the band, not uploaded yet, the ahead / late rule), none appears twice and no file is NULL; then
+     * the headers of all files are read, and the call is refused when one is unsupported or corrupt or decodes to
+     * another size than the camera's pixels_cols x pixels_rows.  A refusal up to here launches nothing and marks nothing;
+     * info (or NULL) [n] is filled from the headers on.  Behind the headers the files count one by one, in decoder batches
+     * of at most 2^28 pixels: a file whose scan turns out corrupt leaves its load pending - upload may still bring that
+     * camera's pixels - while the call's others count as uploaded; the call then returns -1, the message names the
+     * camera and info[i].status the file.  n == 0 does nothing.  The call returns when the pixels are in their slots (the
+     * decoder runs on the context's compute stream and waits for it), so the band's mark, recorded behind the band's last
+     * load whichever way it came, still covers exactly the copies. */
     int och_ortho_band_cameras(ochip_ctx *ctx, const double *raster4, int32_t cols, int64_t rows, int64_t band_rows, size_t n_cams,
                                const double *cams, uint8_t *used);
     int och_ortho_layers_render_subset(const och_graph *g, ochip_ctx *ctx, ochip_ortho_mesh *dev, const och_surface *const *surfaces,
@@ -545,6 +559,9 @@ extern "C"
     size_t och_ortho_stream_band_cameras(const och_ortho_stream *s, size_t band, uint32_t *cameras);
     size_t och_ortho_stream_loads(const och_ortho_stream *s, size_t band, int32_t *loads3);
     int och_ortho_stream_upload(och_ortho_stream *s, size_t band, uint32_t camera, const uint8_t *host_bgr);
+    int och_ortho_stream_upload_jpegs(och_ortho_stream *s, size_t band, size_t n, const uint32_t *cameras,
+                                      const uint8_t *const *files, const uint64_t *sizes,
+                                      ochip_jpeg_file_info *info /* [n] or NULL */);
     int och_ortho_stream_render(och_ortho_stream *s, size_t band, const float *dsm_in, int out_on_device, uint8_t *bgra,
                                 uint64_t *ids, float *weight, ochip_color_corr *corr_out, uint64_t corr_capacity, uint64_t *n_corr,
                                 uint32_t *knn_out);

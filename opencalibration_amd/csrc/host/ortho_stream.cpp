@@ -5,6 +5,7 @@
 // the plan's order does not allow, so that no band renders from a slot that holds another camera's image.
 #include "../../../include/oc_host.h"
 
+#include "../jpeg_decode.hpp"
 #include "ortho_residency.hpp"
 
 #include <algorithm>
@@ -24,6 +25,10 @@ int fail(const std::string &text)
     stream_error = "och_ortho_stream: " + text;
     return -1;
 }
+
+// upload_jpegs cuts a call into decoder batches of at most this many pixels (host.py's JPEG_LOAD_PIXEL_BUDGET, what
+// Graph.load_jpegs decodes at a time) and file bytes (the device route keeps 32-bit byte positions within a batch)
+constexpr uint64_t JPEG_BATCH_PIXELS = 1ull << 28, JPEG_BATCH_BYTES = 1ull << 31;
 } // namespace
 
 struct och_ortho_stream
@@ -51,6 +56,7 @@ struct och_ortho_stream
     ochip_image_slots *slots = nullptr;
     std::vector<uint8_t> host_slots;
     uint64_t slot_bytes = 0;
+    och_jpeg_decoder *decoder = nullptr; // upload_jpegs': made at its first call, on the stream's route
 
     bool replan()
     {
@@ -84,6 +90,42 @@ struct och_ortho_stream
             for (uint32_t c : band_cams[k])
                 band_slot[k].push_back((uint32_t)slot_of[c]);
         }
+    }
+
+    // load j of `band` is in its slot, by copy or by decode: the band's mark goes behind its last one
+    int arrived(size_t band, size_t j, const char *who)
+    {
+        uploaded[j] = 1;
+        if (--pending[band] == 0 && slots)
+        {
+            // the band's event: behind its own uploads, before whatever the caller uploads ahead for the next band
+            if (ochip_image_slots_mark(slots, (uint32_t)band) != OCHIP_OK)
+                return fail(std::string(who) + ": " + ochip_last_error(ctx));
+            marked[band] = 1;
+        }
+        return 0;
+    }
+
+    // the planned load of `camera` for `band` (an index into loads) after upload's checks; false: the refusal is in *why
+    bool acceptable(size_t band, uint32_t camera, size_t *load, std::string *why) const
+    {
+        size_t j = load_off[band];
+        while (j < load_off[band + 1] && (uint32_t)loads[j].camera != camera)
+            j++;
+        if (j == load_off[band + 1])
+            return *why = "camera " + std::to_string(camera) + " is no planned load of band " + std::to_string(band), false;
+        if (uploaded[j])
+            return *why = "camera " + std::to_string(camera) + " of band " + std::to_string(band) + " is uploaded already", false;
+        const ortho_residency::Load &l = loads[j];
+        // an ahead load's slot is free of bands k - 1 and k, a late load's of band k alone: the band before those has returned
+        const int64_t need = (int64_t)band - (l.phase == ortho_residency::AHEAD ? 2 : 1);
+        if (rendered < need)
+            return *why = "the " + std::string(l.phase == ortho_residency::AHEAD ? "ahead" : "late") + " load of camera " +
+                          std::to_string(camera) + " for band " + std::to_string(band) + " waits for render(" + std::to_string(need) +
+                          ") to return; the last band rendered is " + std::to_string(rendered),
+                   false;
+        *load = j;
+        return true;
     }
 
     void start_sweep()
@@ -157,6 +199,7 @@ void och_ortho_stream_destroy(och_ortho_stream *s)
 {
     if (!s)
         return;
+    och_jpeg_decoder_destroy(s->decoder);
     ochip_image_slots_destroy(s->slots);
     delete s;
 }
@@ -190,20 +233,11 @@ int och_ortho_stream_upload(och_ortho_stream *s, size_t band, uint32_t camera, c
 {
     if (band >= s->n_bands || !host_bgr)
         return fail("upload: band " + std::to_string(band) + " of " + std::to_string(s->n_bands) + ", or no image");
-    size_t j = s->load_off[band];
-    while (j < s->load_off[band + 1] && (uint32_t)s->loads[j].camera != camera)
-        j++;
-    if (j == s->load_off[band + 1])
-        return fail("upload: camera " + std::to_string(camera) + " is no planned load of band " + std::to_string(band));
-    if (s->uploaded[j])
-        return fail("upload: camera " + std::to_string(camera) + " of band " + std::to_string(band) + " is uploaded already");
+    size_t j = 0;
+    std::string why;
+    if (!s->acceptable(band, camera, &j, &why))
+        return fail("upload: " + why);
     const ortho_residency::Load &l = s->loads[j];
-    // an ahead load's slot is free of bands k - 1 and k, a late load's of band k alone: the band before those has returned
-    const int64_t need = (int64_t)band - (l.phase == ortho_residency::AHEAD ? 2 : 1);
-    if (s->rendered < need)
-        return fail("upload: the " + std::string(l.phase == ortho_residency::AHEAD ? "ahead" : "late") + " load of camera " +
-                    std::to_string(camera) + " for band " + std::to_string(band) + " waits for render(" + std::to_string(need) +
-                    ") to return; the last band rendered is " + std::to_string(s->rendered));
     const uint64_t bytes = (uint64_t)s->hw[2 * camera] * (uint64_t)s->hw[2 * camera + 1] * 3;
     if (s->slots)
     {
@@ -212,14 +246,92 @@ int och_ortho_stream_upload(och_ortho_stream *s, size_t band, uint32_t camera, c
     }
     else
         std::memcpy(s->host_slots.data() + (size_t)l.slot * s->slot_bytes, host_bgr, bytes);
-    s->uploaded[j] = 1;
-    if (--s->pending[band] == 0 && s->slots)
+    return s->arrived(band, j, "upload");
+}
+
+// n planned loads of `band` from JPEG files, decoded into their slots by the stream's own decoder.
+// Why this needs no event of its own: the decoder's kernels run on the context's compute stream and
+// och_jpeg_decoder_decode returns behind its final status read-back and stream wait, so a slot it wrote is complete when
+// this function returns; the render of the band runs on that same stream afterwards.  The slot it writes is free: a load
+// is accepted only after render(k - 2) / render(k - 1) has returned, render returns behind a stream wait with the band
+// written, and that render had waited for its band's mark, which lies behind every copy ever issued into the slot.  The
+// copies of the same band still go out on the copy stream and are covered by the band's mark, recorded behind the last
+// load whichever way it came.
+int och_ortho_stream_upload_jpegs(och_ortho_stream *s, size_t band, size_t n, const uint32_t *cameras, const uint8_t *const *files,
+                                  const uint64_t *sizes, ochip_jpeg_file_info *info)
+{
+    if (band >= s->n_bands)
+        return fail("upload_jpegs: band " + std::to_string(band) + " of " + std::to_string(s->n_bands));
+    if (n == 0)
+        return 0;
+    if (!cameras || !files || !sizes)
+        return fail("upload_jpegs: a NULL argument");
+    // upload's checks for every camera before a byte of a file is read
+    std::vector<size_t> load(n);
+    std::string why;
+    for (size_t i = 0; i < n; i++)
     {
-        // the band's event: behind its own uploads, before whatever the caller uploads ahead for the next band
-        if (ochip_image_slots_mark(s->slots, (uint32_t)band) != OCHIP_OK)
-            return fail(std::string("upload: ") + ochip_last_error(s->ctx));
-        s->marked[band] = 1;
+        if (!s->acceptable(band, cameras[i], &load[i], &why))
+            return fail("upload_jpegs: " + why);
+        if (std::find(cameras, cameras + i, cameras[i]) != cameras + i)
+            return fail("upload_jpegs: camera " + std::to_string(cameras[i]) + " appears twice in the call");
+        if (!files[i])
+            return fail("upload_jpegs: camera " + std::to_string(cameras[i]) + " has no file");
     }
+    // the headers, oriented as cv::imread orients the pixels, before anything is launched
+    uint8_t *base = s->slots ? reinterpret_cast<uint8_t *>((uintptr_t)ochip_image_slots_address(s->slots, 0)) : s->host_slots.data();
+    const uint64_t stride = s->slots && s->resident.size() > 1 ? ochip_image_slots_address(s->slots, 1) - (uint64_t)(uintptr_t)base
+                                                               : s->slot_bytes;
+    const uint64_t block = (uint64_t)(s->resident.size() - 1) * stride + s->slot_bytes;
+    std::vector<uint64_t> offsets(n);
+    for (size_t i = 0; i < n; i++)
+        offsets[i] = (uint64_t)s->loads[load[i]].slot * stride;
+    std::vector<ochip_jpeg_file_info> own(info ? 0 : n);
+    info = info ? info : own.data();
+    std::vector<ochip_jd::parsed> P;
+    why = ochip_jd::plan_batch((int64_t)n, (int64_t)n, files, sizes, true, base, ~0ull, offsets.data(), info, P);
+    if (!why.empty())
+        return fail("upload_jpegs: " + why);
+    static const char *const status_name[3] = {"ok", "unsupported", "corrupt"};
+    for (size_t i = 0; i < n; i++)
+    {
+        const int64_t rows = s->hw[2 * cameras[i]], cols = s->hw[2 * cameras[i] + 1];
+        if (info[i].status != OCHIP_JPEG_OK)
+            return fail("upload_jpegs: the file of camera " + std::to_string(cameras[i]) + " is " +
+                        status_name[info[i].status == OCHIP_JPEG_UNSUPPORTED ? 1 : 2]);
+        if (info[i].width != cols || info[i].height != rows)
+            return fail("upload_jpegs: the file of camera " + std::to_string(cameras[i]) + " decodes to " + std::to_string(info[i].width) +
+                        " x " + std::to_string(info[i].height) + ", the camera's images are " + std::to_string(cols) + " x " +
+                        std::to_string(rows));
+    }
+    if (!s->decoder && och_jpeg_decoder_create(s->ctx, 0, &s->decoder) != 0)
+        return fail(std::string("upload_jpegs: ") + och_jpeg_decode_last_error());
+    // decoder batches: at most JPEG_BATCH_PIXELS pixels (an image above that alone), the decoder's file count, and file
+    // bytes that keep its 32-bit positions
+    std::string corrupt;
+    for (size_t a = 0; a < n;)
+    {
+        size_t b = a;
+        uint64_t pixels = 0, bytes = 0;
+        while (b < n && (b == a || (pixels + (uint64_t)info[b].width * (uint64_t)info[b].height <= JPEG_BATCH_PIXELS &&
+                                    bytes + sizes[b] < JPEG_BATCH_BYTES && (int64_t)(b - a) < ochip_jd::MAX_BATCH_FILES)))
+        {
+            pixels += (uint64_t)info[b].width * (uint64_t)info[b].height, bytes += sizes[b];
+            b++;
+        }
+        if (och_jpeg_decoder_decode(s->decoder, (int64_t)(b - a), files + a, sizes + a, 1, base, block, offsets.data() + a, info + a,
+                                    nullptr) != 0)
+            return fail(std::string("upload_jpegs: ") + och_jpeg_decode_last_error());
+        for (size_t i = a; i < b; i++)
+            if (info[i].status != OCHIP_JPEG_OK) // known only now: the load stays pending, upload may still bring its pixels
+                corrupt += (corrupt.empty() ? "" : ", ") + std::to_string(cameras[i]);
+            else if (s->arrived(band, load[i], "upload_jpegs") != 0)
+                return -1;
+        a = b;
+    }
+    if (!corrupt.empty())
+        return fail("upload_jpegs: the scan of the file of camera " + corrupt + " is corrupt; its load of band " + std::to_string(band) +
+                    " is still pending, the call's other loads are in their slots");
     return 0;
 }
 

@@ -281,6 +281,7 @@ def load():
             fn.argtypes = [vp, sz, vp]
             fn.restype = sz
         L.och_ortho_stream_upload.argtypes = [vp, sz, u32, vp]
+        L.och_ortho_stream_upload_jpegs.argtypes = [vp, sz, sz, vp, vp, vp, vp]
         L.och_ortho_stream_render.argtypes = [vp, sz, vp, C.c_int, vp, vp, vp, vp, u64, C.POINTER(u64), vp]
         L.och_ortho_stream_rewind.argtypes = [vp]
         L.och_ortho_stream_upload_end_ms.argtypes = [vp, sz, C.POINTER(f64)]
@@ -1012,6 +1013,14 @@ def ortho_layers_cameras(graph, surfaces):
     return dict(cams=cams, node_ids=ids, model_ids=models, image_hw=hw)
 
 
+def ortho_image_paths(graph, surfaces):
+    """The involved nodes' image paths in ortho_layers_cameras' order (node_payload(...)["path"] of each): what
+    ortho_mosaic_streamed takes as files= when the graph's nodes carry their paths, as a checkpoint's graph.json does."""
+    index_of = {nid: i for i, nid in enumerate(graph.node_ids)}
+    return [graph.L.och_graph_node_path(graph.h, index_of[int(nid)]).decode("utf-8")
+            for nid in ortho_layers_cameras(graph, surfaces)["node_ids"]]
+
+
 def _corr_bound(rows, width, cfg):
     """At most this many records in a band: every sampled pixel (boundary: (r + c) % s == 0 per tile row, else the
     multiples of s) times C(num_layers, 2)."""
@@ -1214,6 +1223,7 @@ class OrthoStream:
         self.arr, n = _surface_array(self.surfaces)
         self.h = C.c_void_p()
         self._keep = []
+        self.jpeg_status = []  # the status names of the last upload_jpegs call's files, also when it raised
         if self.L.och_ortho_stream_create(graph.h, mesh.ctx.h if mesh is not None else None, mesh.h if mesh is not None else None,
                                           self.arr, n, _plan_array(plan), self.config4.ctypes.data, int(tile_rows), int(capacity),
                                           C.byref(self.h)) != 0:
@@ -1269,6 +1279,31 @@ class OrthoStream:
         if self.L.och_ortho_stream_upload(self.h, band, camera, ptr) != 0:
             raise capi.OchipError(self._error())
         self._keep.append((band, image))
+
+    def upload_jpegs(self, band, cameras, files):
+        """`band`'s planned loads `cameras` from baseline JPEG files (bytes objects or paths, one per camera), decoded into
+        their slots by the stream's own decoder with the EXIF orientation applied (och_ortho_stream_upload_jpegs; DESIGN.md
+        §4.22): what upload(band, camera, decode_jpeg(file)) per camera gives.  Returns the files' status names.  A call
+        the plan's order does not allow, or with a file whose headers are refused or whose size is not the camera's,
+        raises OchipError and launches nothing; a file whose scan turns out corrupt raises it after the call's other
+        loads are in their slots, and upload() may then bring that camera's pixels.  Returns when the pixels are there:
+        nothing is kept alive."""
+        cams = np.array([int(c) for c in cameras] + [0], np.uint32)
+        datas = [None if f is None else _jpeg_bytes(f) for f in files]  # None: a NULL file, which the library refuses
+        n = len(datas)
+        if n != len(cams) - 1:
+            raise ValueError(f"{len(cams) - 1} cameras and {n} files")
+        bufs = [None if d is None else np.frombuffer(d, np.uint8) if len(d) else np.zeros(1, np.uint8) for d in datas]
+        ptrs = np.array([0 if b is None else b.ctypes.data for b in bufs] + [0], np.uint64)
+        sizes = np.array([len(d) if d is not None else 0 for d in datas] + [0], np.uint64)
+        rec = np.zeros(n + 1, JPEG_INFO_DTYPE)
+        rec["status"][:n] = -1
+        rc = self.L.och_ortho_stream_upload_jpegs(self.h, band, n, cams.ctypes.data, ptrs.ctypes.data, sizes.ctypes.data,
+                                                  rec.ctypes.data)
+        self.jpeg_status = [JPEG_STATUS[s] if 0 <= s < 3 else None for s in rec["status"][:n].tolist()]
+        if rc != 0:
+            raise capi.OchipError(self._error())
+        return self.jpeg_status
 
     def render(self, band, out=None, dsm=None, debug_knn=False):
         """band `band` as ortho_layers returns it (out, dsm, debug_knn as there)"""
@@ -1533,24 +1568,31 @@ def ortho_mosaic(plan, graph, surfaces, images, mesh=None, config=None, color_ba
 
 def ortho_mosaic_streamed(plan, graph, surfaces, fetch, mesh, capacity, config=None, color_balance=None, tile_rows=1, out=None,
                           overviews=False, progress=None, progress_passes=(1, 2), jpeg=None, jpeg_quality=95, geotiff=None,
-                          dsm_geotiff=None, geo=None, progress_png=False):
+                          dsm_geotiff=None, geo=None, progress_png=False, files=None):
     """ortho_mosaic on mesh's device without the source images resident: fetch(i) returns involved camera i's BGR image
     (ortho_layers_cameras' order) as a numpy array or a page-locked torch CPU tensor, and at most `capacity` images are on
     the device at a time (OrthoStream).  Band k + 1's ahead uploads are issued before band k renders, so that they run
     beside it when the images are page-locked.  color_balance as ortho_mosaic's; "solve" renders the layers twice, the
     second sweep starting from the images the first one left on the device.  Returns the (height, width, 4) RGBA tensor,
     with overviews=True (tensor, dict(rgba=[...], dsm=[...])) as ortho_mosaic does.  progress, progress_passes, jpeg,
-    jpeg_quality, geotiff, dsm_geotiff, geo, progress_png: as ortho_mosaic's."""
-    return _mosaic(plan, graph, surfaces, mesh, config, color_balance, tile_rows, out, fetch=fetch, capacity=capacity,
+    jpeg_quality, geotiff, dsm_geotiff, geo, progress_png: as ortho_mosaic's.
+    files: files[i] is involved camera i's baseline JPEG file (bytes or a path; ortho_image_paths gives a checkpoint's), None
+    where it has none.  A band's loads that have a file whose headers jpeg_info calls "ok" are decoded into their slots
+    (OrthoStream.upload_jpegs: one call for the band's late loads - all of band 0's - and one for the next band's ahead
+    loads), so only the files cross to the device; the others - no file, an unsupported or corrupt one, a scan that turns
+    out corrupt - come through fetch(i) as before, or raise OchipError naming the camera, the file and its status when fetch
+    is None, which files allows.  files None: nothing changes."""
+    return _mosaic(plan, graph, surfaces, mesh, config, color_balance, tile_rows, out, fetch=fetch, capacity=capacity, files=files,
                    overviews=overviews, progress=progress, progress_passes=progress_passes, jpeg=jpeg, jpeg_quality=jpeg_quality,
                    geotiff=geotiff, dsm_geotiff=dsm_geotiff, geo=geo, progress_png=progress_png)
 
 
 def _mosaic(plan, graph, surfaces, mesh, config, color_balance, tile_rows, out, images=None, fetch=None, capacity=None,
             overviews=False, progress=None, progress_passes=(1, 2), jpeg=None, jpeg_quality=95, geotiff=None, dsm_geotiff=None,
-            geo=None, progress_png=False):
-    """The band loop of ortho_mosaic (images) and ortho_mosaic_streamed (fetch, capacity): the two differ in where a band's
-    layers come from, ortho_layers over the resident images or an OrthoStream's render behind the band's uploads."""
+            geo=None, progress_png=False, files=None):
+    """The band loop of ortho_mosaic (images) and ortho_mosaic_streamed (fetch and / or files, capacity): the two differ in
+    where a band's layers come from, ortho_layers over the resident images or an OrthoStream's render behind the band's
+    uploads."""
     cfg = {**LAYERS_CONFIG, **BLEND_CONFIG, **(config or {})}
     lcfg = {k: cfg[k] for k in LAYERS_CONFIG}
     bcfg = {k: cfg[k] for k in BLEND_CONFIG}
@@ -1565,7 +1607,8 @@ def _mosaic(plan, graph, surfaces, mesh, config, color_balance, tile_rows, out, 
 
         ctx, dev = mesh.ctx, f"cuda:{mesh.ctx.device}"
         out = torch.empty((h, w, 4), dtype=torch.uint8, device=dev) if out is None else out
-    stream = OrthoStream(plan, graph, surfaces, capacity, mesh=mesh, tile_rows=tile_rows, config=lcfg) if fetch is not None else None
+    stream = OrthoStream(plan, graph, surfaces, capacity, mesh=mesh, tile_rows=tile_rows, config=lcfg) \
+        if fetch is not None or files is not None else None
     builders = [OrthoOverviews(kind, w, h, ctx=ctx, on_device=mesh is not None)
                 for kind in (OVERVIEW_RGBA8, OVERVIEW_FLOAT32)] if overviews or geotiff is not None or dsm_geotiff is not None else []
     tiffs = [None, None]  # the orthomosaic's and the DSM's GeoTiffWriter
@@ -1581,15 +1624,40 @@ def _mosaic(plan, graph, surfaces, mesh, config, color_balance, tile_rows, out, 
             for update in tiles.collect(png=bool(progress_png)):
                 progress(update)
 
+    def fill(k, loads):
+        """band k's loads `loads`: one upload_jpegs call for those with a usable file, fetch and upload for the rest"""
+        def pixels(cam, status):
+            if fetch is None:
+                raise capi.OchipError(f"ortho_mosaic_streamed: involved camera {cam} has "
+                                      f"{'no file' if status is None else f'the file {_file_name(files[cam])}, which is {status}'}"
+                                      ", and there is no fetch to ask for its pixels")
+            stream.upload(k, cam, fetch(cam))
+
+        decode = []
+        for cam, _, _ in loads:
+            data = _jpeg_bytes(files[cam]) if files is not None and files[cam] is not None else None
+            status = jpeg_info(data)["status"] if data is not None else None
+            if status == "ok":
+                decode.append((cam, data))
+            else:
+                pixels(cam, status)
+        if decode:
+            try:
+                stream.upload_jpegs(k, [cam for cam, _ in decode], [data for _, data in decode])
+            except capi.OchipError:
+                bad = [(cam, st) for (cam, _), st in zip(decode, stream.jpeg_status) if st == "corrupt"]
+                if not bad or fetch is None:  # a refusal of the whole call, or nobody to ask for a corrupt scan's pixels
+                    raise
+                for cam, st in bad:  # the scans that turned out corrupt: the call's other loads are in their slots
+                    pixels(cam, st)
+
     def band(k, balance, blend, emit=frozenset()):
         row0 = k * band_rows
         rows = min(band_rows, h - row0)
         if stream is not None:  # before the band's DSM and render: its own loads still missing, then the next band's ahead ones
-            for cam, _, _ in stream.loads(0) if k == 0 else stream.loads(k, LOAD_LATE):
-                stream.upload(k, cam, fetch(cam))
+            fill(k, stream.loads(0) if k == 0 else stream.loads(k, LOAD_LATE))
             if k + 1 < stream.num_bands:
-                for cam, _, _ in stream.loads(k + 1, LOAD_AHEAD):
-                    stream.upload(k + 1, cam, fetch(cam))
+                fill(k + 1, stream.loads(k + 1, LOAD_AHEAD))
         if mesh is None:
             dsm, lay = dsm_render(plan, surfaces, row0=row0, rows=rows), None
         else:
@@ -1947,6 +2015,11 @@ def _jpeg_bytes(f):
         return bytes(f)
     with open(f, "rb") as fh:
         return fh.read()
+
+
+def _file_name(f):
+    """a file of the decoder in a message: its path, or its size when it is bytes"""
+    return f"of {len(f)} bytes" if isinstance(f, (bytes, bytearray, memoryview)) else repr(os.fspath(f))
 
 
 def _jpeg_info_dict(rec):
