@@ -3875,15 +3875,19 @@ int akaze_run(ochip_ctx *ctx, const uint8_t *images_bgr, bool on_device, uint32_
     }
     if (const char *dump = std::getenv("OCHIP_DUMP_PLANES"))
     {
-        // debugging aid: the first image's Lt and (Lx, Ly) pyramids as raw float files <prefix>_lt.f32 / _lxy.f32
-        std::vector<float> hl(img_stride), hx(2 * img_stride);
+        // the planes' seam (tests/test_gpu_akaze_planes.py): the first image's Lt and (Lx, Ly) pyramids and its contrast factor
+        // as raw float files <prefix>_lt.f32 / _lxy.f32 / _kc.f32
+        std::vector<float> hl(img_stride), hx(2 * img_stride), hk(1);
         OCHIP_HIP(ctx, ochip_stream_wait(ctx, st));
         OCHIP_HIP(ctx, hipMemcpy(hl.data(), d_Lt, img_stride * 4, hipMemcpyDeviceToHost));
         OCHIP_HIP(ctx, hipMemcpy(hx.data(), d_Lxy, img_stride * 8, hipMemcpyDeviceToHost));
-        for (int which = 0; which < 2; which++)
-            if (FILE *f = std::fopen((std::string(dump) + (which ? "_lxy.f32" : "_lt.f32")).c_str(), "wb"))
+        OCHIP_HIP(ctx, hipMemcpy(hk.data(), d_kc, 4, hipMemcpyDeviceToHost));
+        const std::vector<float> *planes[3] = {&hl, &hx, &hk};
+        const char *suffix[3] = {"_lt.f32", "_lxy.f32", "_kc.f32"};
+        for (int which = 0; which < 3; which++)
+            if (FILE *f = std::fopen((std::string(dump) + suffix[which]).c_str(), "wb"))
             {
-                std::fwrite(which ? hx.data() : hl.data(), 4, which ? hx.size() : hl.size(), f);
+                std::fwrite(planes[which]->data(), 4, planes[which]->size(), f);
                 std::fclose(f);
             }
     }

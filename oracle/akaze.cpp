@@ -1,4 +1,5 @@
-// ORACLE — test infrastructure only.  See akaze.hpp: restated AKAZE + extract_features, PARITY UNPINNED.
+// ORACLE — test infrastructure only.  See akaze.hpp: restated AKAZE + extract_features; parity with cv::AKAZE UNPINNED, the
+// scale space's arithmetic (build_scale_space) PINNED to an fp64 model of its definitions (tests/test_akaze_planes_oracle.py).
 //
 // KNOWN DEPARTURES FROM OpenCV's AKAZE (features2d/src/kaze/AKAZEFeatures.cpp, nldiffusion_functions.cpp [3P: not under
 // /root/reference, absent from this image - what OpenCV does is quoted from its published source, not checked here]).
@@ -1457,6 +1458,43 @@ size_t oc_akaze_level(const uint8_t *gray, int w, int h, int level, int which, f
     *lw = ss.levels[level].width;
     *lh = ss.levels[level].height;
     return src.size();
+}
+
+// every plane of ONE build of the scale space (tests/test_akaze_planes_oracle.py, test_gpu_akaze_planes.py): level i's Lt, Lx,
+// Ly, Ldet follow each other in `planes`, width * height floats each, levels in order; levels6 holds {octave, sublevel, width,
+// height, sigma_size, FED steps} per level, levels2 {esigma, etime}.  Returns the floats `planes` needs; nothing but
+// *n_levels is written when that exceeds planes_cap or the level tables' max_levels rows are too few.
+size_t oc_akaze_planes(const uint8_t *gray, int w, int h, int max_levels, int *n_levels, int *levels6, float *levels2, float *kcontrast,
+                       float *planes, size_t planes_cap)
+{
+    std::vector<float> img((size_t)w * h);
+    for (size_t i = 0; i < img.size(); i++)
+        img[i] = (float)gray[i] * (1.0f / 255.0f);
+    Options o;
+    const ScaleSpace ss = build_scale_space(img, w, h, o);
+    const size_t N = ss.levels.size();
+    size_t need = 0;
+    for (size_t i = 0; i < N; i++)
+        need += 4 * ss.Lt[i].size();
+    *n_levels = (int)N;
+    if (need > planes_cap || N > (size_t)max_levels)
+        return need;
+    *kcontrast = ss.kcontrast;
+    float *out = planes;
+    for (size_t i = 0; i < N; i++)
+    {
+        const Level &l = ss.levels[i];
+        const int row[6] = {l.octave, l.sublevel, l.width, l.height, l.sigma_size, (int)l.tsteps.size()};
+        std::memcpy(levels6 + 6 * i, row, sizeof(row));
+        levels2[2 * i] = l.esigma;
+        levels2[2 * i + 1] = l.etime;
+        for (const std::vector<float> *p : {&ss.Lt[i], &ss.Lx[i], &ss.Ly[i], &ss.Ldet[i]})
+        {
+            std::memcpy(out, p->data(), p->size() * 4);
+            out += p->size();
+        }
+    }
+    return need;
 }
 
 size_t oc_extract_features(const uint8_t *bgr, int w, int h, size_t max_n, double *loc, float *strength, uint64_t *desc,

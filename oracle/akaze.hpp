@@ -10,9 +10,15 @@
 // scale-space extrema + sub-pixel fit, dominant orientation, 3-channel M-LDB over 2x2 + 3x3 + 4x4
 // grids = (6 + 36 + 120) * 3 = 486 bits.
 //
-// PARITY UNPINNED: there is no OpenCV here to compare with and the reference's extract tests need the
-// absent test images and only assert counts (test/test_extract_features.cpp:8-75).  Everything below
-// is therefore a self-consistent definition; the GPU implementation is checked against *this* code.
+// PARITY WITH cv::AKAZE UNPINNED: there is no OpenCV here to compare with and the reference's extract
+// tests need the absent test images and only assert counts (test/test_extract_features.cpp:8-75), so
+// identity with OpenCV's bits is not checked anywhere.  THE SCALE SPACE'S ARITHMETIC IS PINNED: every
+// level's Lt, Lx, Ly, Ldet and the contrast factor are held (tests/test_akaze_planes_oracle.py, through
+// oc_akaze_planes) to an fp64 model written from the stated definitions - level table, Gaussian,
+// contrast histogram, conductivity, FED cycle, half-sampling, scale-s Scharr, determinant - within 4 x
+// the measured float32 round-off (Lt 3e-7, 8.5e-7 at the last 80 x 40 level; Lx, Ly 5e-8; Ldet 3e-8).
+// Detection, orientation and the descriptor remain a self-consistent definition; the GPU
+// implementation is checked against *this* code.
 // Arithmetic is float32 with plain mul/add in the written order (no FMA) so that a device
 // implementation can be bit-identical; every transcendental (Gaussian taps, FED step sizes, the
 // orientation weights) is tabulated on the host in double and handed to both sides.

@@ -75,6 +75,9 @@ def lib():
         L.oc_akaze.argtypes = [u8p, C.c_int, C.c_int, C.c_size_t, f32p_, u64p, vp]
         L.oc_akaze_level.restype = C.c_size_t
         L.oc_akaze_level.argtypes = [u8p, C.c_int, C.c_int, C.c_int, C.c_int, f32p_, vp, vp]
+        L.oc_akaze_planes.restype = C.c_size_t
+        L.oc_akaze_planes.argtypes = [u8p, C.c_int, C.c_int, C.c_int, vp, np.ctypeslib.ndpointer(np.int32, flags="C_CONTIGUOUS"), f32p_, f32p_,
+                                      f32p_, C.c_size_t]
         L.oc_extract_features.restype = C.c_size_t
         L.oc_extract_features.argtypes = [u8p, C.c_int, C.c_int, C.c_size_t, f64p, f32p_, u64p, u64p]
         L.oc_gray_resize.argtypes = [u8p, C.c_int, C.c_int, u8p, C.c_int, C.c_int]
@@ -91,6 +94,29 @@ def akaze(gray, max_kp=50000):
     n = lib().oc_akaze(gray, w, h, max_kp, kp, d, None)
     assert n <= max_kp
     return kp[:n].copy(), d[:n].copy()
+
+
+def akaze_planes(gray):
+    """Every plane of one build of the restated scale space of an 8-bit grey image: {"kcontrast": float32, "levels": a list of
+    dicts with octave, sublevel, width, height, sigma_size, n_steps, esigma, etime and the float32 planes Lt, Lx, Ly, Ldet}."""
+    gray = np.ascontiguousarray(gray, np.uint8)
+    h, w = gray.shape
+    cap = sum(16 * (w >> o) * (h >> o) for o in range(4))
+    ints, flts = np.zeros((16, 6), np.int32), np.zeros((16, 2), np.float32)
+    kc, planes, n = np.zeros(1, np.float32), np.zeros(cap, np.float32), C.c_int(0)
+    need = lib().oc_akaze_planes(gray, w, h, 16, C.byref(n), ints, flts, kc, planes, cap)
+    assert need <= cap and n.value <= 16, (need, cap, n.value)
+    levels, off = [], 0
+    for i in range(n.value):
+        lvl = dict(zip(("octave", "sublevel", "width", "height", "sigma_size", "n_steps"), (int(v) for v in ints[i])))
+        lvl["esigma"], lvl["etime"] = flts[i]
+        px = lvl["width"] * lvl["height"]
+        for name in ("Lt", "Lx", "Ly", "Ldet"):
+            lvl[name] = planes[off:off + px].reshape(lvl["height"], lvl["width"]).copy()
+            off += px
+        levels.append(lvl)
+    assert off == need
+    return {"kcontrast": kc[0], "levels": levels}
 
 
 def extract_features(bgr, max_n=100000):
