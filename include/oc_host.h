@@ -327,6 +327,10 @@ extern "C"
                                double *position3, double *orientation4);
     const char *och_graph_node_path(const och_graph *g, size_t index);
     int och_graph_set_node_path(och_graph *g, size_t index, const char *path);
+    /* a node's "metadata" object as text: set takes any well-formed JSON value (NaN allowed) and keeps it in the
+     * writer's layout, -1 + och_last_error(g) otherwise; "" until one is set or a graph.json brought one */
+    const char *och_graph_node_metadata(const och_graph *g, size_t index);
+    int och_graph_set_node_metadata(och_graph *g, size_t index, const char *json, size_t len);
     size_t och_graph_num_models(const och_graph *g);
     int och_graph_get_model(const och_graph *g, uint32_t index, double *m11); /* och_graph_add_model's ten, then the id */
     int och_surface_save_ply(const och_surface *s, const char *path);
@@ -345,6 +349,40 @@ extern "C"
     const char *och_checkpoint_state(const och_checkpoint *cp);
     void och_checkpoint_info(const och_checkpoint *cp, double *info4);
     int och_checkpoint_get_surface(const och_checkpoint *cp, size_t index, och_surface *out);
+
+    /* ---- a survey from its files alone: image metadata, the local frame, the GeoJSON camera graph.
+     *      Host code only: nothing here touches a device. ---------------------------------------------------------------
+     * och_jpeg_metadata: image_metadata of a JPEG file's bytes (opencalibration_amd/csrc/host/image_metadata.hpp; the
+     * reference's extract_metadata over its EXIF / XMP reader).  numbers14: width, height, focal_length_px, principal x y,
+     * latitude, longitude, altitude, relative_altitude, roll, pitch, yaw, accuracy_xy, accuracy_z (NaN = absent).
+     * strings: make, model, serial_no, lens_make, lens_model, datum, timestamp, datestamp, each NUL-terminated, one after
+     * the other in the caller's `cap` bytes; *needed (may be NULL) is their total length.  Returns OCH_METADATA_OK /
+     * _ABSENT (no Exif, no XMP: the defaults) / _CORRUPT (the defaults), or -1 for a NULL argument or a `cap` below
+     * *needed (nothing but *needed written).  Never reads outside data[0 .. size). */
+#define OCH_METADATA_OK 0
+#define OCH_METADATA_ABSENT 1
+#define OCH_METADATA_CORRUPT 2
+    int och_jpeg_metadata(const uint8_t *data, uint64_t size, double *numbers14, char *strings, uint64_t cap, uint64_t *needed);
+    /* GeoCoord (opencalibration_amd/csrc/host/geo_coord.hpp): Transverse Mercator on WGS84 about the origin, k0 = 1, no
+     * false origin, Krueger's series to n^6 in fp64.  The projection's centre is strtod("%g") of the origin - the
+     * reference writes its WKT with six significant digits - while the origin reported stays unrounded.  create: NULL for
+     * a non-finite origin.  origin4: origin latitude, longitude, then the centre's.  to_local: n x (latitude, longitude,
+     * altitude) -> n x (easting, northing, altitude); to_wgs84: n x (x, y, z) -> n x (longitude, latitude, altitude); a
+     * point that cannot be transformed (non-finite, 90 degrees or more from the central meridian) becomes three NaNs.
+     * wkt: the text into buf[0 .. cap) when it fits (NUL-terminated); returns its length without the NUL. */
+    typedef struct och_geo och_geo;
+    och_geo *och_geo_create(double latitude, double longitude);
+    void och_geo_destroy(och_geo *geo);
+    void och_geo_origin(const och_geo *geo, double *origin4);
+    void och_geo_to_local(const och_geo *geo, size_t n, const double *lat_lon_alt, double *xyz);
+    void och_geo_to_wgs84(const och_geo *geo, size_t n, const double *xyz, double *lon_lat_alt);
+    size_t och_geo_wkt(const och_geo *geo, char *buf, size_t cap);
+    /* toVisualizedGeoJson (src/io/serialize_MeasurementGraph.cpp:62-209): Points of the nodes then LineStrings of the
+     * edges, positions through geo (NULL: the local coordinates as they are).  node_ids / edge_ids NULL: all of them,
+     * sorted by id, else the given ones in the given order.  malloc'd, NUL-terminated (och_free); NULL +
+     * och_last_error(g) for an id the graph does not have. */
+    char *och_graph_geojson(och_graph *g, const och_geo *geo, const uint64_t *node_ids, size_t n_nodes, const uint64_t *edge_ids,
+                            size_t n_edges, size_t *len);
 
     /* ---- dense guided matching (opencalibration_amd/csrc/host/dense_stereo.hpp): densifyMesh(graph, surfaces) of
      *      src/dense/dense_stereo.cpp:66-403 with the surface's mesh as surfaces[0]; the triangulated points are appended

@@ -154,6 +154,26 @@ int och_graph_set_node_path(och_graph *g, size_t index, const char *path)
     g->graph.nodes()[index].payload.path = path;
     return 0;
 }
+const char *och_graph_node_metadata(const och_graph *g, size_t index)
+{
+    return index < g->graph.size_nodes() ? g->graph.nodes()[index].payload.metadata_json.c_str() : "";
+}
+int och_graph_set_node_metadata(och_graph *g, size_t index, const char *json, size_t len)
+{
+    if (index >= g->graph.size_nodes() || !json)
+    {
+        g->error = "set_node_metadata: no such node";
+        return -1;
+    }
+    std::string text;
+    if (!normalise_json(std::string(json, len), text))
+    {
+        g->error = "set_node_metadata: not a well-formed JSON value";
+        return -1;
+    }
+    g->graph.nodes()[index].payload.metadata_json = std::move(text);
+    return 0;
+}
 
 size_t och_graph_num_models(const och_graph *g)
 {

@@ -742,6 +742,97 @@ bool parse_id(const std::string &s, size_t &id) // std::strtoull(name, &end, 10)
 
 } // namespace
 
+bool normalise_json(const std::string &json, std::string &out)
+{
+    out.clear();
+    Cursor c(json.data(), json.data() + json.size());
+    PrettyWriter w(out);
+    if (json.empty() || !copy_value(c, w))
+        return false;
+    return c.peek() == '\0' && c.p == c.end; // nothing but white space may follow
+}
+
+bool visualizeGeoJson(const MeasurementGraph &graph, const std::vector<size_t> &node_ids, const std::vector<size_t> &edge_ids,
+                      const std::function<void(const double *local3, double *global3)> &to_global, std::ostream &out)
+{
+    std::string text;
+    PrettyWriter w(text);
+    const auto coordinates = [&](const double *local) {
+        double wgs84[3];
+        to_global(local, wgs84);
+        w.StartArray();
+        for (int i = 0; i < 3; i++)
+            w.Double(wgs84[i]);
+        w.EndArray();
+    };
+    w.StartObject();
+    w.Key("type");
+    w.String("FeatureCollection");
+    w.Key("features");
+    w.StartArray();
+    for (size_t node_id : node_ids)
+    {
+        const MeasurementGraph::Node *node = graph.getNode(node_id);
+        if (!node)
+            return false;
+        w.StartObject();
+        w.Key("type");
+        w.String("Feature");
+        w.Key("geometry");
+        w.StartObject();
+        w.Key("type");
+        w.String("Point");
+        w.Key("coordinates");
+        coordinates(node->payload.position);
+        w.EndObject();
+        w.Key("properties");
+        w.StartObject();
+        w.Key("path");
+        w.String(node->payload.path);
+        w.Key("id");
+        w.String(std::to_string(node_id));
+        w.EndObject();
+        w.EndObject();
+    }
+    for (size_t edge_id : edge_ids)
+    {
+        const MeasurementGraph::Edge *edge = graph.getEdge(edge_id);
+        const MeasurementGraph::Node *source = edge ? graph.getNode(edge->source) : nullptr;
+        const MeasurementGraph::Node *dest = edge ? graph.getNode(edge->dest) : nullptr;
+        if (!source || !dest)
+            return false;
+        w.StartObject();
+        w.Key("type");
+        w.String("Feature");
+        w.Key("geometry");
+        w.StartObject();
+        w.Key("type");
+        w.String("LineString");
+        w.Key("coordinates");
+        w.StartArray();
+        coordinates(source->payload.position);
+        coordinates(dest->payload.position);
+        w.EndArray();
+        w.EndObject();
+        w.Key("properties");
+        w.StartObject();
+        w.Key("id");
+        w.String(std::to_string(edge_id));
+        w.Key("source_id");
+        w.String(std::to_string(edge->source));
+        w.Key("dest_id");
+        w.String(std::to_string(edge->dest));
+        w.Key("inliers");
+        w.Int64((int64_t)edge->payload.inlier_matches.size());
+        w.EndObject();
+        w.EndObject();
+    }
+    w.EndArray();
+    w.EndObject();
+    out.write(text.data(), (std::streamsize)text.size());
+    return true;
+}
+
 // ---- MeasurementGraph ------------------------------------------------------------------------------------------------
 bool serialize(const MeasurementGraph &graph, std::ostream &out)
 {

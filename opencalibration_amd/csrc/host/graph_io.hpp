@@ -8,6 +8,7 @@
 #include "relax_mesh.hpp"
 
 #include <array>
+#include <functional>
 #include <iosfwd>
 #include <set>
 
@@ -20,6 +21,16 @@ namespace opencalibration_amd
 // The thumbnail (a PNG, OpenCV is not here) and the metadata object are carried as text.
 bool serialize(const MeasurementGraph &graph, std::ostream &out);
 bool deserialize(const std::string &json, MeasurementGraph &graph, std::string *error = nullptr);
+
+// Any JSON value (NaN and Infinity included) re-emitted in the writer's layout: what a node's "metadata" text is kept as.
+// false where the text is not one well-formed value.
+bool normalise_json(const std::string &json, std::string &out);
+
+// io/serialize.hpp's toVisualizedGeoJson (serialize_MeasurementGraph.cpp:62-209): a FeatureCollection of one Point per
+// node of node_ids, then one LineString per edge of edge_ids, in the given order (the reference passes them sorted);
+// to_global: a local position to (longitude, latitude, altitude).  false where an id is not in the graph.
+bool visualizeGeoJson(const MeasurementGraph &graph, const std::vector<size_t> &node_ids, const std::vector<size_t> &edge_ids,
+                      const std::function<void(const double *local3, double *global3)> &to_global, std::ostream &out);
 
 // io/serialize.hpp:15, io/deserialize.hpp:9.  Mesh node and edge ids are insertion indices here (relax_mesh.hpp): the
 // writer uses them as the file's ids, the reader numbers the file's vertices and edges in file order and maps the

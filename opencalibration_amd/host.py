@@ -374,6 +374,24 @@ def load():
         L.och_tile_progress_destroy.argtypes = [vp]
         L.och_tile_progress_destroy.restype = None
         L.och_tile_progress_last_error.restype = C.c_char_p
+        L.och_graph_node_metadata.argtypes = [vp, sz]
+        L.och_graph_node_metadata.restype = C.c_char_p
+        L.och_graph_set_node_metadata.argtypes = [vp, sz, C.c_char_p, sz]
+        L.och_jpeg_metadata.argtypes = [vp, C.c_uint64, _f64p, vp, C.c_uint64, C.POINTER(C.c_uint64)]
+        L.och_geo_create.argtypes = [C.c_double, C.c_double]
+        L.och_geo_create.restype = vp
+        L.och_geo_destroy.argtypes = [vp]
+        L.och_geo_destroy.restype = None
+        L.och_geo_origin.argtypes = [vp, _f64p]
+        L.och_geo_origin.restype = None
+        L.och_geo_to_local.argtypes = [vp, sz, _f64p, _f64p]
+        L.och_geo_to_local.restype = None
+        L.och_geo_to_wgs84.argtypes = [vp, sz, _f64p, _f64p]
+        L.och_geo_to_wgs84.restype = None
+        L.och_geo_wkt.argtypes = [vp, vp, sz]
+        L.och_geo_wkt.restype = sz
+        L.och_graph_geojson.argtypes = [vp, vp, vp, sz, vp, sz, C.POINTER(sz)]
+        L.och_graph_geojson.restype = vp
         _lib = L
     return _lib
 
@@ -2041,6 +2059,97 @@ def jpeg_info(data, apply_orientation=True):
     return _jpeg_info_dict(rec[0])
 
 
+METADATA_STATUS = ["ok", "absent", "corrupt"]
+_METADATA_NUMBERS = ["latitude", "longitude", "altitude", "relative_altitude", "roll", "pitch", "yaw", "accuracy_xy", "accuracy_z"]
+
+
+def jpeg_metadata(data, want_status=False):
+    """image_metadata of a JPEG file (bytes or a path), from its EXIF and XMP (och_jpeg_metadata): a dict
+    in graph.json's layout and key order - camera_info (dimensions, focal_length_px, principal, make, model, serial_no,
+    lens_make, lens_model) and capture_info (latitude ... accuracy_z, datum, timestamp, datestamp).  Absent numbers are NaN,
+    absent strings "".  A file with neither Exif nor XMP ("absent") and one whose structure does not hold ("corrupt") give
+    the defaults; want_status: (dict, status)."""
+    data = _jpeg_bytes(data)
+    buf = np.frombuffer(data, np.uint8) if len(data) else np.zeros(1, np.uint8)
+    numbers, needed, cap = np.zeros(14), C.c_uint64(0), 1024
+    L = load()
+    while True:
+        text = C.create_string_buffer(cap)
+        status = L.och_jpeg_metadata(buf.ctypes.data, len(data), numbers, text, cap, C.byref(needed))
+        if status >= 0:
+            break
+        if needed.value <= cap:
+            raise capi.OchipError("och_jpeg_metadata: bad arguments")
+        cap = int(needed.value)
+    s = [t.decode("utf-8", "replace") for t in text.raw[:needed.value].split(b"\0")[:8]]
+    v = numbers.tolist()
+    camera = dict(dimensions=[int(v[0]), int(v[1])], focal_length_px=v[2], principal=[v[3], v[4]], make=s[0], model=s[1],
+                  serial_no=s[2], lens_make=s[3], lens_model=s[4])
+    capture = dict(zip(_METADATA_NUMBERS, v[5:]))
+    capture.update(datum=s[5], timestamp=s[6], datestamp=s[7])
+    out = dict(camera_info=camera, capture_info=capture)
+    return (out, METADATA_STATUS[status]) if want_status else out
+
+
+class GeoCoord:
+    """The survey's local frame (GeoCoord of the reference; och_geo_*): a Transverse Mercator on WGS84
+    about (lat, lon) with k0 = 1 and no false origin, metres east and north of the origin.  The reference writes the origin
+    into its WKT with six significant digits, so the projection's centre is `centre` = float("%g" % each) while `origin`
+    stays as given; wkt() is that text."""
+
+    def __init__(self, lat, lon):
+        self.L = load()
+        self.h = self.L.och_geo_create(float(lat), float(lon))
+        if not self.h:
+            raise ValueError(f"GeoCoord: ({lat}, {lon}) is no origin")
+        o = np.zeros(4)
+        self.L.och_geo_origin(self.h, o)
+        self.origin, self.centre = (float(o[0]), float(o[1])), (float(o[2]), float(o[3]))
+
+    def __del__(self):
+        if getattr(self, "h", None):
+            self.L.och_geo_destroy(self.h)
+            self.h = None
+
+    def to_local(self, lat, lon, alt=0.0):
+        """(lat, lon, alt), scalars or arrays of one length, to (..., 3) easting, northing, altitude; NaN NaN NaN for a
+        point that is not finite or 90 degrees or more from the central meridian."""
+        lla = np.stack(np.broadcast_arrays(np.asarray(lat, np.float64), np.asarray(lon, np.float64), np.asarray(alt, np.float64)), -1)
+        flat = np.ascontiguousarray(lla.reshape(-1, 3))
+        out = np.zeros_like(flat)
+        if len(flat):
+            self.L.och_geo_to_local(self.h, len(flat), flat, out)
+        return out.reshape(lla.shape)
+
+    def to_wgs84(self, xyz):
+        """(..., 3) local x y z to (..., 3) longitude, latitude, altitude: the order of the reference's toWGS84"""
+        xyz = np.asarray(xyz, np.float64)
+        flat = np.ascontiguousarray(xyz.reshape(-1, 3))
+        out = np.zeros_like(flat)
+        if len(flat):
+            self.L.och_geo_to_wgs84(self.h, len(flat), flat, out)
+        return out.reshape(xyz.shape)
+
+    def wkt(self):
+        n = self.L.och_geo_wkt(self.h, None, 0)
+        buf = C.create_string_buffer(n + 1)
+        self.L.och_geo_wkt(self.h, buf, n + 1)
+        return buf.value.decode()
+
+
+def _geo_coord(geo):
+    """a GeoCoord from what the geo-referenced writers take: one, an (lat, lon) origin, or None"""
+    if geo is None or isinstance(geo, GeoCoord):
+        return geo
+    return GeoCoord(*geo)
+
+
+def save_geojson(path, graph, geo=None):
+    """The camera graph as GeoJSON (Graph.to_geojson) to a file."""
+    with open(path, "w", encoding="utf-8") as f:
+        f.write(graph.to_geojson(geo))
+
+
 class JpegBatch:
     """What JpegDecoder.decode returns: status (a name per file), info (jpeg_info's dict per file), shapes ((height, width)
     per file, None where the file was refused), offsets (the image's first byte in pixels, None likewise), pixels (flat
@@ -2398,7 +2507,8 @@ class GeoTiffWriter:
     numpy bands.  ctx with on_device: CUDA tensors on ctx's device, fed on the context's stream - the caller has torch's work
     on a band finished before feed, as ortho_blend does - and a feed never waits for the band it enqueues: it writes the
     tiles the bands before completed.  ctx without on_device: numpy bands through the device.  The routes write the same
-    bytes.  geo: dict(min_x, max_y, gsd[, epsg]) for tags 33550, 33922 and 34735.  bigtiff: None chooses BigTIFF above
+    bytes.  geo: dict(min_x, max_y, gsd[, epsg]) for tags 33550, 33922 and 34735; instead of epsg, origin=(lat, lon) or
+    coord=GeoCoord writes the local frame's Transverse Mercator as GeoKeys (34735 - 34737).  bigtiff: None chooses BigTIFF above
     2 000 000 000 uncompressed bytes.  sparse: an all-zero RGBA tile gets offset 0 and count 0 and no bytes; DSM tiles are
     always written.  feed(row0, band): bands ascend and are contiguous from row 0, of any row count.  finish(overviews): the
     list of overview level arrays or tensors (OrthoOverviews) become further IFDs with NewSubfileType 1; the file is then
@@ -2414,6 +2524,11 @@ class GeoTiffWriter:
         if self.on_device and ctx is None:
             raise ValueError("bands on the device need the device route (ctx)")
         self.geo = dict(geo) if geo is not None else None
+        self.centre = None  # (lat, lon) of the local frame's projection when geo names one instead of an EPSG code
+        if self.geo is not None and (self.geo.get("coord") is not None or self.geo.get("origin") is not None):
+            if self.geo.get("epsg") is not None:
+                raise ValueError("geo names the local frame (origin / coord) or an epsg code, not both")
+            self.centre = _geo_coord(self.geo["coord"] if self.geo.get("coord") is not None else self.geo["origin"]).centre
         self.big = self.width * self.height * 4 > GEOTIFF_BIGTIFF_ABOVE if bigtiff is None else bool(bigtiff)
         self.own = isinstance(target, (str, bytes, os.PathLike))
         if not self.own and not (hasattr(target, "write") and hasattr(target, "seekable") and target.seekable()):
@@ -2510,9 +2625,20 @@ class GeoTiffWriter:
             keys = [(1025, 0, 1, 1)]
             if g.get("epsg") is not None:
                 keys = [(1024, 0, 1, 1), (1025, 0, 1, 1), (3072, 0, 1, int(g["epsg"]))]
+            doubles, ascii_ = [], b""
+            if self.centre is not None:  # the local frame: a user-defined Transverse Mercator on WGS 84
+                names = [b"Custom Transverse Mercator|", b"WGS 84|"]
+                doubles = [self.centre[1], self.centre[0], 0.0, 0.0, 1.0]
+                ascii_ = b"".join(names) + b"\0"
+                keys = [(1024, 0, 1, 1), (1025, 0, 1, 1), (1026, 34737, len(names[0]), 0), (2048, 0, 1, 4326),
+                        (2049, 34737, len(names[1]), len(names[0])), (2054, 0, 1, 9102), (3072, 0, 1, 32767), (3074, 0, 1, 32767),
+                        (3075, 0, 1, 1), (3076, 0, 1, 9001)] + [(k, 34736, 1, i) for i, k in enumerate((3080, 3081, 3082, 3083, 3092))]
             tags.append((33550, D, [float(g["gsd"]), float(g["gsd"]), 0.0]))
             tags.append((33922, D, [0.0, 0.0, 0.0, float(g["min_x"]), float(g["max_y"]), 0.0]))
             tags.append((34735, S, [1, 1, 0, len(keys)] + [v for k in keys for v in k]))
+            if doubles:
+                tags.append((34736, D, doubles))
+                tags.append((34737, A, ascii_))
         if not rgba:
             tags.append((42113, A, b"nan\0"))
         dtypes = {S: "<u2", L: "<u4", D: "<f8", L8: "<u8"}
@@ -2704,7 +2830,8 @@ class GeoTiffReader:
     one: a 16 384 x 16 384 RGBA file of 1 024 tiles takes 0.27 - 0.52 s on the device and 0.18 s on 16 host threads, a
     64-tile file 0.12 - 0.25 s against 0.012 s.  Take it for pixels that must end on the device.
     width, height, samples, kind (OVERVIEW_RGBA8, OVERVIEW_FLOAT32 or None for 1 or 3 samples), levels ([(rows, cols), ...]
-    of the overview IFDs), geo (dict(min_x, max_y, gsd_x, gsd_y, epsg) from tags 33550 / 33922 / 34735, or None) and nodata
+    of the overview IFDs), geo (dict(min_x, max_y, gsd_x, gsd_y, epsg) from tags 33550 / 33922 / 34735, or None), projection (dict(kind="tmerc", lat0, lon0, k0, false_easting, false_northing) of a
+    user-defined Transverse Mercator in the GeoKeys, or None) and nodata
     (tag 42113 as a float, or None).
     Taken: little-endian classic and BigTIFF, tiles with sides that are multiples of 16 and a payload of at most 4 MiB,
     Compression 8 and 32946, Predictor 1 and 2, PlanarConfiguration 1, 8-bit unsigned samples 1, 3 or 4 to a pixel, one
@@ -2788,12 +2915,32 @@ class GeoTiffReader:
                     if loc == 0 and (key == 3072 or (key == 2048 and epsg is None)):
                         epsg = value
             self.geo = dict(min_x=x - i * sx, max_y=y + j * sy, gsd_x=sx, gsd_y=sy, epsg=epsg)
+        self.projection = self._projection(tags)
         self.nodata = None
         if 42113 in tags:
             try:
                 self.nodata = float(bytes(tags[42113]).split(b"\0")[0].decode("ascii").strip())
             except (ValueError, UnicodeDecodeError):
                 self.nodata = None
+
+    @staticmethod
+    def _projection(tags):
+        """dict(kind="tmerc", lat0, lon0, k0, false_easting, false_northing) of a user-defined Transverse Mercator in the
+        GeoKeys (3075 = 1; its parameters in tag 34736), else None"""
+        keys, doubles = tags.get(34735), tags.get(34736)
+        if keys is None or isinstance(keys, bytes) or len(keys) < 4 or doubles is None or isinstance(doubles, bytes):
+            return None
+        short, real = {}, {}
+        for q in range(min(int(keys[3]), (len(keys) - 4) // 4)):
+            key, loc, count, value = (int(v) for v in keys[4 + 4 * q:8 + 4 * q])
+            if loc == 0:
+                short[key] = value
+            elif loc == 34736 and count >= 1 and value < len(doubles):
+                real[key] = float(doubles[value])
+        if short.get(3075) != 1 or 3080 not in real or 3081 not in real:
+            return None
+        return dict(kind="tmerc", lat0=real[3081], lon0=real[3080], k0=real.get(3092, 1.0), false_easting=real.get(3082, 0.0),
+                    false_northing=real.get(3083, 0.0))
 
     def _read_ifd(self, at):
         big = self.big
@@ -3287,6 +3434,8 @@ class Graph:
         self.L = load()
         self.h = C.c_void_p(self.L.och_graph_create())
         self.node_ids = []
+        self.geo = None             # the local frame's GeoCoord once load_survey (or the caller) has set one
+        self._survey_cameras = {}   # load_survey: camera_info -> model index
 
     def close(self):
         if getattr(self, "h", None):
@@ -3502,6 +3651,113 @@ class Graph:
                 del batch
                 at += m
         return sums[0] / max(n, 1), sums[1] / max(n, 1)
+
+    def load_survey(self, ctx, files, max_keypoints=30000, thumbnails=False, chunk=None, geo=None):
+        """The load stage from JPEG files alone (bytes objects or paths): each file's jpeg_metadata gives
+        its camera and its position.  The local frame is `geo` (a GeoCoord or an (lat, lon) origin), else graph.geo, else
+        one about the first file's position (load_stage.cpp:71-74), and is kept as graph.geo.  Files whose camera_info
+        compare equal (size, make, model, serial number, lens, focal length) share one model: focal length and size from
+        the metadata, the principal point at (cols, rows) / 2, no distortion.  Positions are geo.to_local of latitude,
+        longitude and altitude.  Decode and extraction are load_jpegs', one call per run of consecutive files of one model;
+        each node gets its file's path (when it was one) and its metadata.  A file without latitude / longitude, without a
+        focal length, with a metadata size of 0 or one that differs from the decoded (oriented) size, or one the decoder
+        does not call "ok" raises OchipError naming it before anything is launched or the graph is touched.  Returns
+        load_jpegs' means."""
+        files = list(files)
+        blobs = [_jpeg_bytes(f) for f in files]
+
+        def name(i):
+            return f"file {i}" if isinstance(files[i], (bytes, bytearray, memoryview)) else f"file {i} ({os.fspath(files[i])})"
+
+        metas = []
+        for i, blob in enumerate(blobs):
+            md = jpeg_metadata(blob)
+            cam, cap = md["camera_info"], md["capture_info"]
+            if not (np.isfinite(cap["latitude"]) and np.isfinite(cap["longitude"])):
+                raise capi.OchipError(f"load_survey: {name(i)} has no latitude / longitude")
+            if not np.isfinite(cam["focal_length_px"]):
+                raise capi.OchipError(f"load_survey: {name(i)} has no focal length")
+            w, h = cam["dimensions"]
+            if w == 0 or h == 0:
+                raise capi.OchipError(f"load_survey: {name(i)} has no image size in its metadata")
+            info = jpeg_info(blob)
+            if info["status"] != "ok":
+                raise capi.OchipError(f"load_survey: {name(i)} is {info['status']}")
+            if (info["width"], info["height"]) != (w, h):
+                raise capi.OchipError(f"load_survey: {name(i)} decodes to {info['width']} x {info['height']}, its metadata says "
+                                      f"{w} x {h}")
+            metas.append(md)
+        if ctx is None:
+            raise capi.OchipError("load_survey: the extraction needs a device context")
+        geo = _geo_coord(geo) or self.geo
+        if geo is None and metas:
+            geo = GeoCoord(metas[0]["capture_info"]["latitude"], metas[0]["capture_info"]["longitude"])
+        self.geo = geo
+
+        def camera_key(cam):  # camera_info_t::operator== (types/image_metadata.hpp:22-35): the principal point is not in it
+            return (tuple(cam["dimensions"]), cam["make"], cam["model"], cam["serial_no"], cam["lens_make"], cam["lens_model"],
+                    cam["focal_length_px"])
+
+        models = []
+        for md in metas:
+            cam = md["camera_info"]
+            key = camera_key(cam)
+            if key not in self._survey_cameras:
+                w, h = cam["dimensions"]
+                self._survey_cameras[key] = self.add_model([cam["focal_length_px"], w / 2, h / 2, 0, 0, 0, 0, 0, w, h])
+            models.append(self._survey_cameras[key])
+        cap = [md["capture_info"] for md in metas]
+        pos = geo.to_local([c["latitude"] for c in cap], [c["longitude"] for c in cap], [c["altitude"] for c in cap]) \
+            if metas else np.zeros((0, 3))
+        at, sums, n = 0, np.zeros(2), len(files)
+        while at < n:
+            end = at + 1
+            while end < n and models[end] == models[at]:
+                end += 1
+            first = self.num_nodes
+            f, s = self.load_jpegs(ctx, blobs[at:end], models[at], pos[at:end], max_keypoints, thumbnails, chunk)
+            sums += (f * (end - at), s * (end - at))
+            for i in range(at, end):
+                if not isinstance(files[i], (bytes, bytearray, memoryview)):
+                    self.set_node_path(first + i - at, os.fspath(files[i]))
+                self.set_node_metadata(first + i - at, metas[i])
+            at = end
+        return sums[0] / max(n, 1), sums[1] / max(n, 1)
+
+    def set_node_metadata(self, index, metadata):
+        """The "metadata" object of the index-th node in graph.json: a dict (jpeg_metadata's) or JSON text."""
+        import json
+
+        text = metadata if isinstance(metadata, str) else json.dumps(metadata)
+        raw = text.encode("utf-8")
+        if self.L.och_graph_set_node_metadata(self.h, int(index), raw, len(raw)) != 0:
+            raise ValueError(self.L.och_last_error(self.h).decode())
+
+    def node_metadata(self, index):
+        """The index-th node's metadata as a dict (NaN for absent numbers), or None where the node carries none."""
+        import json
+
+        text = self.L.och_graph_node_metadata(self.h, int(index)).decode("utf-8")
+        return json.loads(text) if text else None
+
+    def to_geojson(self, geo=None, node_ids=None, edge_ids=None):
+        """toVisualizedGeoJson (src/io/serialize_MeasurementGraph.cpp:62-209): a FeatureCollection of one Point per node,
+        then one LineString per edge with its inlier count, coordinates (longitude, latitude, altitude) through `geo` (a
+        GeoCoord or an (lat, lon) origin; None: graph.geo, and without one the local coordinates as they are).  node_ids /
+        edge_ids: None for all of them sorted by id, else those in the given order."""
+        geo = _geo_coord(geo) or self.geo
+        nodes = None if node_ids is None else np.ascontiguousarray(node_ids, np.uint64).reshape(-1)
+        edges = None if edge_ids is None else np.ascontiguousarray(edge_ids, np.uint64).reshape(-1)
+        n = C.c_size_t(0)
+        ptr = self.L.och_graph_geojson(self.h, geo.h if geo is not None else None,
+                                       None if nodes is None else nodes.ctypes.data, 0 if nodes is None else len(nodes),
+                                       None if edges is None else edges.ctypes.data, 0 if edges is None else len(edges), C.byref(n))
+        if not ptr:
+            raise ValueError(self.L.och_last_error(self.h).decode())
+        try:
+            return C.string_at(ptr, n.value).decode("utf-8")
+        finally:
+            self.L.och_free(ptr)
 
     def load_link_images(self, ctx, images_bgr, model, positions, orientations=None, max_keypoints=30000, device_shape=None):
         """Load and link overlapped (och_graph_load_link_images): extraction streams in chunks and ranges of links run
