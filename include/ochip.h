@@ -129,6 +129,23 @@ extern "C"
     int ochip_akaze_batch_dev(ochip_ctx *ctx, const uint8_t *images_bgr_dev, uint32_t n_images, int width, int height,
                               uint32_t max_kp, float *kp6, uint64_t *desc, uint32_t *counts, int *work_wh);
 
+    /* Test seam: the working image alone - what ochip_akaze_batch computes in front of AKAZE (BGR -> grey with cvtColor's
+     * fixed-point weights, cv::resize(INTER_AREA) to a long side of 1600, (float)u8 * (1 / 255f)) through the same function
+     * as the product, and nothing after it.  images_bgr: host, or device when on_device (any alignment); out: n_images x
+     * work_wh[1] x work_wh[0] floats (host); any image size, also ones AKAZE has no levels for.  *route names the kernels
+     * that ran: OCHIP_WI_RESIZE_* | OCHIP_WI_GREY_* << 8. */
+#define OCHIP_WI_RESIZE_NONE 0        /* no side above 1600: to_float_kernel */
+#define OCHIP_WI_RESIZE_FUSED4 1      /* resize_area_lds_kernel<true, 4>: BGR -> LDS -> area, at most 4 horizontal taps */
+#define OCHIP_WI_RESIZE_FUSED8 2      /* resize_area_lds_kernel<true, 8> */
+#define OCHIP_WI_RESIZE_STAGED_GREY 3 /* resize_area_lds_kernel<false, 8> over the grey image */
+#define OCHIP_WI_RESIZE_PER_TAP 4     /* resize_area_kernel over the grey image */
+#define OCHIP_WI_GREY_FUSED 0         /* inside the resize */
+#define OCHIP_WI_GREY_GRAY4 1         /* gray4_kernel */
+#define OCHIP_WI_GREY_GRAY4_TAIL 2    /* gray4_kernel and gray_kernel on the last pixels, fewer than 4 */
+#define OCHIP_WI_GREY_BYTEWISE 3      /* gray_kernel on everything (a source that is not 4-byte aligned) */
+    int ochip_debug_working_image(ochip_ctx *ctx, const uint8_t *images_bgr, int on_device, uint32_t n_images, int width,
+                                  int height, float *out, int *work_wh, int *route);
+
     /* ---- extract_features' tail (src/extract/extract_features.cpp:38-87) on the device ---- */
     /* The reference rescales the keypoints, std::sorts them by response (unstable: libstdc++'s order among equal
      * responses, restated move for move on the device, csrc/std_sort.hip), runs a greedy 8 px suppression in that order

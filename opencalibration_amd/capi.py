@@ -26,7 +26,7 @@ EXPORTS = [
     "ochip_descriptors_reserve", "ochip_upload_descriptors", "ochip_descriptor_count",
     "ochip_match_batch", "ochip_match_launch", "ochip_match_fetch",
     "ochip_upload_keypoints", "ochip_ransac_homography_batch", "ochip_refit_homography_batch", "ochip_ransac_epipolar_batch",
-    "ochip_upload_batch", "ochip_host_alloc", "ochip_host_free", "ochip_akaze_batch", "ochip_akaze_batch_dev", "ochip_akaze_features", "ochip_akaze_features_dev", "ochip_feature_lists_from_keypoints",
+    "ochip_upload_batch", "ochip_host_alloc", "ochip_host_free", "ochip_akaze_batch", "ochip_akaze_batch_dev", "ochip_debug_working_image", "ochip_akaze_features", "ochip_akaze_features_dev", "ochip_feature_lists_from_keypoints",
     "ochip_synth_views_alloc", "ochip_synth_views_free", "ochip_synth_render_views", "ochip_synth_views_read",
     "ochip_relax_problem_create", "ochip_relax_problem_destroy", "ochip_relax_set_cameras_constant",
     "ochip_relax_solve", "ochip_relax_get_state", "ochip_relax_set_shard", "ochip_relax_evaluate",
@@ -269,6 +269,7 @@ def load():
         L.ochip_akaze_batch.argtypes = [vp, vp, u32, i32, i32, u32, vp, vp, vp, vp]
         L.ochip_feature_lists_from_keypoints.argtypes = [vp, vp, vp, vp, u32, u32, i32, i32, C.c_double, C.c_double, vp]
         L.ochip_akaze_batch_dev.argtypes = [vp, vp, u32, i32, i32, u32, vp, vp, vp, vp]
+        L.ochip_debug_working_image.argtypes = [vp, vp, i32, u32, i32, i32, vp, vp, vp]
         L.ochip_synth_views_alloc.argtypes = [vp, u32, i32, i32, C.POINTER(vp)]
         L.ochip_synth_views_free.argtypes = [vp, vp]
         L.ochip_synth_views_free.restype = None
@@ -764,6 +765,24 @@ class Context:
         self._check(self.L.ochip_akaze_batch(self.h, imgs.ctypes.data, n, w, h, max_kp, kp.ctypes.data, desc.ctypes.data,
                                              counts.ctypes.data, wh.ctypes.data), "ochip_akaze_batch")
         return [(kp[i, :counts[i]].copy(), desc[i, :counts[i]].copy()) for i in range(n)], (int(wh[0]), int(wh[1]))
+
+    def working_image(self, images_bgr, device_ptr=None, shape=None):
+        """ochip_debug_working_image: the grey, INTER_AREA-downscaled float image in front of AKAZE and the route taken.
+        images_bgr: (n, h, w, 3) uint8 on the host - or None with device_ptr (an address in device memory, any alignment) and
+        shape = (n, h, w).  Returns (n x H x W float32, (W, H), resize route, grey route): include/ochip.h, OCHIP_WI_*."""
+        if device_ptr is None:
+            imgs = np.ascontiguousarray(images_bgr, np.uint8)
+            n, h, w, _ = imgs.shape
+            src, on_device = imgs.ctypes.data, 0
+        else:
+            (n, h, w), src, on_device = shape, int(device_ptr), 1
+        wh, route = np.zeros(2, np.int32), C.c_int(0)
+        self._check(self.L.ochip_debug_working_image(self.h, src, on_device, 0, w, h, None, wh.ctypes.data, None),
+                    "ochip_debug_working_image")
+        out = np.zeros((n, int(wh[1]), int(wh[0])), np.float32)
+        self._check(self.L.ochip_debug_working_image(self.h, src, on_device, n, w, h, out.ctypes.data, wh.ctypes.data,
+                                                     C.byref(route)), "ochip_debug_working_image")
+        return out, (int(wh[0]), int(wh[1])), route.value & 255, route.value >> 8
 
     def std_sort(self, keys, payload, offsets):
         """ochip_debug_std_sort: (keys, payload, fallback flags) with every segment [offsets[s], offsets[s + 1]) ordered as

@@ -3113,16 +3113,24 @@ int ochip_synth_render_views(ochip_ctx *ctx, uint8_t *images_dev, uint32_t first
 // descriptor kernel's tables and the INTER_AREA tables of the downscale.  A survey's images share their shape, so the
 // context keeps these from chunk to chunk in blocks of its own (outside the call's arena) and akaze_run rebuilds them only
 // when the shape changes.  The key is everything they are computed from.
+// the INTER_AREA tables of one source shape in device memory, with what the host read off them for the dispatch
+namespace ochip
+{
+struct resize_tabs_dev
+{
+    int *xo = nullptr, *xs = nullptr, *yo = nullptr, *ys = nullptr;
+    float *xa = nullptr, *ya = nullptr;
+    bool staged = false; // can every resize workgroup stage its source window in LDS? (taps per column, window size)
+    int most_taps = 0;
+};
+} // namespace ochip
 struct ochip::akaze_tables
 {
     ochip::dev_blocks mem;
     int width = 0, height = 0, W = 0, H = 0, n_levels = 0, n_tiles = 0; // key (0: nothing built)
     unsigned int *tile_seq = nullptr;
     void *gtab = nullptr; // gather_tab
-    int *xo = nullptr, *xs = nullptr, *yo = nullptr, *ys = nullptr;
-    float *xa = nullptr, *ya = nullptr;
-    bool staged = false; // can every resize workgroup stage its source window in LDS? (taps per column, window size)
-    int most_taps = 0;
+    resize_tabs_dev rz;
 };
 
 namespace
@@ -3248,6 +3256,135 @@ const gather_tab &host_gather_tab()
     return G;
 }
 
+// ---- the working image: grey, INTER_AREA downscale to max side 1600, float (extract_features.cpp:25-27).  akaze_run and
+// the test seam ochip_debug_working_image run these three functions; every dispatch decision of the block is in them.
+
+// cv::resize's fx = fy: the FLOAT 1600 / max side (never above 1) widened to a double; dsize = the rint of the product
+struct working_size
+{
+    double scale;
+    int W, H;
+    working_size(int width, int height)
+        : scale(std::min(1.f, float(1600) / (float)std::max(width, height))), W((int)std::lrint(width * scale)),
+          H((int)std::lrint(height * scale))
+    {
+    }
+};
+
+// The downscale's tables on the host (alive until their copies have landed).
+struct resize_plan
+{
+    area_tab tx, ty;
+};
+// Build the tables of a downscale, decide from them whether resize_area_lds_kernel can take it, and enqueue their copies
+// into blocks of `mem` on the context's stream (the caller waits).  An unresized shape has no tables.
+int resize_tables_enqueue(ochip::dev_blocks &mem, int width, int height, int W, int H, double scale, resize_plan *plan,
+                          ochip::resize_tabs_dev *out)
+{
+    constexpr auto ENQ = ochip::copy_mode::enqueue;
+    *out = ochip::resize_tabs_dev{};
+    if (W == width && H == height)
+        return OCHIP_OK;
+    area_tab &tx = plan->tx, &ty = plan->ty;
+    tx = area_table(width, W, 1.0 / scale);
+    ty = area_table(height, H, 1.0 / scale);
+    bool staged = width % 4 == 0;
+    for (int x0 = 0; x0 < W && staged; x0 += 256)
+    {
+        const int x1 = std::min(x0 + 256, W);
+        const int c0 = tx.si[tx.off[x0]] & ~3, c1 = tx.si[tx.off[x1] - 1];
+        staged = c1 - c0 + 1 <= RS_PITCH - 3;
+        for (int x = x0; x < x1 && staged; x++)
+            staged = tx.off[x + 1] - tx.off[x] <= RESIZE_MAX_TAPS;
+    }
+    for (int y0 = 0; y0 < H && staged; y0 += RESIZE_ROWS)
+    {
+        const int y1 = std::min(y0 + RESIZE_ROWS, H);
+        staged = ty.si[ty.off[y1] - 1] - ty.si[ty.off[y0]] + 1 <= RS_ROWS;
+    }
+    out->staged = staged;
+    for (int x = 0; x < W; x++)
+        out->most_taps = std::max(out->most_taps, tx.off[x + 1] - tx.off[x]);
+    int rc = OCHIP_OK;
+    rc = rc != OCHIP_OK ? rc : mem.upload(&out->xo, tx.off, ENQ);
+    rc = rc != OCHIP_OK ? rc : mem.upload(&out->xs, tx.si, ENQ);
+    rc = rc != OCHIP_OK ? rc : mem.upload(&out->xa, tx.alpha, ENQ);
+    rc = rc != OCHIP_OK ? rc : mem.upload(&out->yo, ty.off, ENQ);
+    rc = rc != OCHIP_OK ? rc : mem.upload(&out->ys, ty.si, ENQ);
+    rc = rc != OCHIP_OK ? rc : mem.upload(&out->ya, ty.alpha, ENQ);
+    return rc;
+}
+
+// Enqueue the block's kernels for B images: d_bgr (B x height x width x 3, any alignment) -> d_img (B x H x W floats);
+// d_gray is scratch of B x width x height + 4 bytes.  Returns which kernels it launched:
+// OCHIP_WI_RESIZE_* | OCHIP_WI_GREY_* << 8 (include/ochip.h).
+int working_image_enqueue(hipStream_t st, const uint8_t *d_bgr, uint8_t *d_gray, float *d_img, uint32_t B, int width, int height,
+                          int W, int H, double scale, const ochip::resize_tabs_dev *tabs)
+{
+    const size_t src_px = (size_t)width * height, plane0 = (size_t)W * H;
+    int grey_route = OCHIP_WI_GREY_FUSED, resize_route = OCHIP_WI_RESIZE_NONE;
+    const size_t n_px = (size_t)B * src_px;
+    const bool resized = !(W == width && H == height);
+    const bool staged = resized && tabs->staged;
+    const bool fused_grey = staged && ((uintptr_t)d_bgr & 3) == 0; // the resize converts BGR itself
+    if (!fused_grey)
+    {
+        if (((uintptr_t)d_bgr & 3) == 0)
+        {
+            hipLaunchKernelGGL(gray4_kernel, dim3((unsigned)(((n_px + 3) / 4 + 255) / 256)), dim3(256), 0, st,
+                               (const uint32_t *)d_bgr, (uint32_t *)d_gray, n_px / 4);
+            grey_route = OCHIP_WI_GREY_GRAY4;
+        }
+        if (((uintptr_t)d_bgr & 3) != 0 || (n_px & 3))
+        {
+            // unaligned source or a tail of < 4 pixels: byte-wise
+            const size_t first = ((uintptr_t)d_bgr & 3) ? 0 : (n_px & ~(size_t)3);
+            hipLaunchKernelGGL(gray_kernel, dim3((unsigned)((n_px - first + 255) / 256)), dim3(256), 0, st, d_bgr + 3 * first,
+                               d_gray + first, n_px - first);
+            grey_route = grey_route == OCHIP_WI_GREY_GRAY4 ? OCHIP_WI_GREY_GRAY4_TAIL : OCHIP_WI_GREY_BYTEWISE;
+        }
+    }
+    if (W == width && H == height)
+        hipLaunchKernelGGL(to_float_kernel, dim3((unsigned)((B * plane0 + 255) / 256)), dim3(256), 0, st, d_gray, d_img,
+                           B * plane0);
+    else
+    {
+        const int *xo = tabs->xo, *xs = tabs->xs, *yo = tabs->yo, *ys = tabs->ys;
+        const float *xa = tabs->xa, *ya = tabs->ya;
+        const dim3 rgrid((W + 255) / 256, (H + RESIZE_ROWS - 1) / RESIZE_ROWS, B);
+        const int most_taps = tabs->most_taps;
+        // a scale of exactly 2 (a 3200-pixel side): cv::resize's integer path - the vector body of ResizeAreaFast rounds
+        // (sum + 2) >> 2, sixteen columns at a time (the 16-bit lanes of an AVX2 build; the scalar tail rounds to even like
+        // the general path).  Scales of 4 and 8 give the same bytes either way (every operation is exact).
+        const int half_up_cols = scale == 0.5 ? W - W % 16 : 0;
+        if (fused_grey && most_taps <= 4)
+        {
+            hipLaunchKernelGGL((resize_area_lds_kernel<true, 4>), rgrid, dim3(256), 0, st, (const uint8_t *)d_bgr, width, height, d_img,
+                               W, H, xo, xs, xa, yo, ys, ya, half_up_cols);
+            resize_route = OCHIP_WI_RESIZE_FUSED4;
+        }
+        else if (fused_grey)
+        {
+            hipLaunchKernelGGL((resize_area_lds_kernel<true, RESIZE_MAX_TAPS>), rgrid, dim3(256), 0, st, (const uint8_t *)d_bgr, width, height, d_img,
+                               W, H, xo, xs, xa, yo, ys, ya, half_up_cols);
+            resize_route = OCHIP_WI_RESIZE_FUSED8;
+        }
+        else if (staged)
+        {
+            hipLaunchKernelGGL((resize_area_lds_kernel<false, RESIZE_MAX_TAPS>), rgrid, dim3(256), 0, st, d_gray, width, height, d_img, W, H, xo, xs,
+                               xa, yo, ys, ya, half_up_cols);
+            resize_route = OCHIP_WI_RESIZE_STAGED_GREY;
+        }
+        else
+        {
+            hipLaunchKernelGGL(resize_area_kernel, rgrid, dim3(256), 0, st, d_gray, width, height, d_img, W, H, xo, xs, xa, yo, ys,
+                               ya, half_up_cols);
+            resize_route = OCHIP_WI_RESIZE_PER_TAP;
+        }
+    }
+    return resize_route | (grey_route << 8);
+}
+
 // The context's tables for this shape (built and uploaded with one wait when the context has none or had another shape's;
 // nothing of the context's stream still reads the old ones then: every akaze_run ends with a wait).
 int akaze_tables_for(ochip_ctx *ctx, int width, int height, int W, int H, double scale, const levels_dev &LV, int n_tiles,
@@ -3301,37 +3438,8 @@ int akaze_tables_for(ochip_ctx *ctx, int width, int height, int W, int H, double
     gather_tab *g = nullptr;
     rc = rc != OCHIP_OK ? rc : T.mem.upload(&g, &host_gather_tab(), 1, ENQ);
     T.gtab = g;
-    area_tab tx, ty; // (alive until the wait below)
-    T.staged = false;
-    T.most_taps = 0;
-    if (!(W == width && H == height))
-    {
-        tx = area_table(width, W, 1.0 / scale);
-        ty = area_table(height, H, 1.0 / scale);
-        bool staged = width % 4 == 0;
-        for (int x0 = 0; x0 < W && staged; x0 += 256)
-        {
-            const int x1 = std::min(x0 + 256, W);
-            const int c0 = tx.si[tx.off[x0]] & ~3, c1 = tx.si[tx.off[x1] - 1];
-            staged = c1 - c0 + 1 <= RS_PITCH - 3;
-            for (int x = x0; x < x1 && staged; x++)
-                staged = tx.off[x + 1] - tx.off[x] <= RESIZE_MAX_TAPS;
-        }
-        for (int y0 = 0; y0 < H && staged; y0 += RESIZE_ROWS)
-        {
-            const int y1 = std::min(y0 + RESIZE_ROWS, H);
-            staged = ty.si[ty.off[y1] - 1] - ty.si[ty.off[y0]] + 1 <= RS_ROWS;
-        }
-        T.staged = staged;
-        for (int x = 0; x < W; x++)
-            T.most_taps = std::max(T.most_taps, tx.off[x + 1] - tx.off[x]);
-        rc = rc != OCHIP_OK ? rc : T.mem.upload(&T.xo, tx.off, ENQ);
-        rc = rc != OCHIP_OK ? rc : T.mem.upload(&T.xs, tx.si, ENQ);
-        rc = rc != OCHIP_OK ? rc : T.mem.upload(&T.xa, tx.alpha, ENQ);
-        rc = rc != OCHIP_OK ? rc : T.mem.upload(&T.yo, ty.off, ENQ);
-        rc = rc != OCHIP_OK ? rc : T.mem.upload(&T.ys, ty.si, ENQ);
-        rc = rc != OCHIP_OK ? rc : T.mem.upload(&T.ya, ty.alpha, ENQ);
-    }
+    resize_plan plan; // (alive until the wait below)
+    rc = rc != OCHIP_OK ? rc : resize_tables_enqueue(T.mem, width, height, W, H, scale, &plan, &T.rz);
     OCHIP_HIP(ctx, ochip_stream_wait(ctx, ctx->stream));
     if (rc != OCHIP_OK)
         return rc;
@@ -3353,8 +3461,9 @@ int akaze_run(ochip_ctx *ctx, const uint8_t *images_bgr, bool on_device, uint32_
         return ochip_fail(ctx, OCHIP_EINVAL, "bad image size %d x %d", width, height);
     OCHIP_HIP(ctx, hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
-    const double scale = std::min(1.f, float(1600) / (float)std::max(width, height));
-    const int W = (int)std::lrint(width * scale), H = (int)std::lrint(height * scale);
+    const working_size ws(width, height);
+    const double scale = ws.scale;
+    const int W = ws.W, H = ws.H;
     if (work_wh)
     {
         work_wh[0] = W;
@@ -3508,49 +3617,7 @@ int akaze_run(ochip_ctx *ctx, const uint8_t *images_bgr, bool on_device, uint32_
     ochip_prof_begin(ctx, OCHIP_K_AKAZE, &e0, &e1);
 
     // ---- grey, downscale, float
-    const size_t n_px = (size_t)B * src_px;
-    const bool resized = !(W == width && H == height);
-    const bool staged = resized && tabs->staged;
-    const bool fused_grey = staged && ((uintptr_t)d_bgr & 3) == 0; // the resize converts BGR itself
-    if (!fused_grey)
-    {
-        if (((uintptr_t)d_bgr & 3) == 0)
-            hipLaunchKernelGGL(gray4_kernel, dim3((unsigned)(((n_px + 3) / 4 + 255) / 256)), dim3(256), 0, st,
-                               (const uint32_t *)d_bgr, (uint32_t *)d_gray, n_px / 4);
-        if (((uintptr_t)d_bgr & 3) != 0 || (n_px & 3))
-        {
-            // unaligned source or a tail of < 4 pixels: byte-wise
-            const size_t first = ((uintptr_t)d_bgr & 3) ? 0 : (n_px & ~(size_t)3);
-            hipLaunchKernelGGL(gray_kernel, dim3((unsigned)((n_px - first + 255) / 256)), dim3(256), 0, st, d_bgr + 3 * first,
-                               d_gray + first, n_px - first);
-        }
-    }
-    if (W == width && H == height)
-        hipLaunchKernelGGL(to_float_kernel, dim3((unsigned)((B * plane0 + 255) / 256)), dim3(256), 0, st, d_gray, d_img,
-                           B * plane0);
-    else
-    {
-        const int *xo = tabs->xo, *xs = tabs->xs, *yo = tabs->yo, *ys = tabs->ys;
-        const float *xa = tabs->xa, *ya = tabs->ya;
-        const dim3 rgrid((W + 255) / 256, (H + RESIZE_ROWS - 1) / RESIZE_ROWS, B);
-        const int most_taps = tabs->most_taps;
-        // a scale of exactly 2 (a 3200-pixel side): cv::resize's integer path - the vector body of ResizeAreaFast rounds
-        // (sum + 2) >> 2, sixteen columns at a time (the 16-bit lanes of an AVX2 build; the scalar tail rounds to even like
-        // the general path).  Scales of 4 and 8 give the same bytes either way (every operation is exact).
-        const int half_up_cols = scale == 0.5 ? W - W % 16 : 0;
-        if (fused_grey && most_taps <= 4)
-            hipLaunchKernelGGL((resize_area_lds_kernel<true, 4>), rgrid, dim3(256), 0, st, (const uint8_t *)d_bgr, width, height, d_img,
-                               W, H, xo, xs, xa, yo, ys, ya, half_up_cols);
-        else if (fused_grey)
-            hipLaunchKernelGGL((resize_area_lds_kernel<true, RESIZE_MAX_TAPS>), rgrid, dim3(256), 0, st, (const uint8_t *)d_bgr, width, height, d_img,
-                               W, H, xo, xs, xa, yo, ys, ya, half_up_cols);
-        else if (staged)
-            hipLaunchKernelGGL((resize_area_lds_kernel<false, RESIZE_MAX_TAPS>), rgrid, dim3(256), 0, st, d_gray, width, height, d_img, W, H, xo, xs,
-                               xa, yo, ys, ya, half_up_cols);
-        else
-            hipLaunchKernelGGL(resize_area_kernel, rgrid, dim3(256), 0, st, d_gray, width, height, d_img, W, H, xo, xs, xa, yo, ys,
-                               ya, half_up_cols);
-    }
+    working_image_enqueue(st, d_bgr, d_gray, d_img, B, width, height, W, H, scale, &tabs->rz);
 
     // ---- contrast factor: Gaussian(1) + gradient magnitude + per-tile maxima in one pass, then the histogram
     OCHIP_HIP(ctx, hipMemsetAsync(d_hist, 0, (size_t)B * 301 * 4, st));
@@ -4047,3 +4114,47 @@ int akaze_run(ochip_ctx *ctx, const uint8_t *images_bgr, bool on_device, uint32_
 
 } // namespace
 
+
+// ---- test seam: the working image alone (include/ochip.h: ochip_debug_working_image) ----------------------------------
+extern "C" int ochip_debug_working_image(ochip_ctx *ctx, const uint8_t *images_bgr, int on_device, uint32_t n_images, int width,
+                                         int height, float *out, int *work_wh, int *route)
+{
+    if (!ctx)
+        return OCHIP_EINVAL;
+    if (width <= 0 || height <= 0)
+        return ochip_fail(ctx, OCHIP_EINVAL, "ochip_debug_working_image: bad image size %d x %d", width, height);
+    if (n_images && (!images_bgr || !out))
+        return ochip_fail(ctx, OCHIP_EINVAL, "ochip_debug_working_image: NULL argument");
+    OCHIP_HIP(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    const working_size ws(width, height);
+    if (work_wh)
+        work_wh[0] = ws.W, work_wh[1] = ws.H;
+    if (route)
+        *route = 0;
+    if (n_images == 0)
+        return OCHIP_OK;
+    const size_t src_px = (size_t)width * height, plane0 = (size_t)ws.W * ws.H;
+    ochip::dev_scratch mem{ctx, "ochip_debug_working_image"};
+    uint8_t *d_bgr = nullptr, *d_gray = nullptr;
+    float *d_img = nullptr;
+    if (on_device)
+        d_bgr = const_cast<uint8_t *>(images_bgr);
+    else
+        OCHIP_TRY(mem.upload(&d_bgr, images_bgr, (size_t)n_images * src_px * 3, ochip::copy_mode::enqueue_wait));
+    OCHIP_TRY(mem.alloc<uint8_t>(&d_gray, (size_t)n_images * src_px + 4));
+    OCHIP_TRY(mem.alloc<float>(&d_img, (size_t)n_images * plane0));
+    // (tables of the call's own: the context's belong to a shape AKAZE has levels for)
+    resize_plan plan;
+    ochip::resize_tabs_dev tabs;
+    OCHIP_TRY(resize_tables_enqueue(mem, width, height, ws.W, ws.H, ws.scale, &plan, &tabs));
+    OCHIP_HIP(ctx, ochip_stream_wait(ctx, st));
+    const int r = working_image_enqueue(st, d_bgr, d_gray, d_img, n_images, width, height, ws.W, ws.H, ws.scale, &tabs);
+    OCHIP_HIP(ctx, hipGetLastError());
+    OCHIP_HIP(ctx, hipMemcpyAsync(out, d_img, (size_t)n_images * plane0 * sizeof(float), hipMemcpyDeviceToHost, st));
+    OCHIP_HIP(ctx, ochip_stream_wait(ctx, st));
+    mem.release();
+    if (route)
+        *route = r;
+    return OCHIP_OK;
+}

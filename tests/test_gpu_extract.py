@@ -77,9 +77,13 @@ def test_a_scale_of_exactly_two(ctx, oracle, w, h):
 
 def test_resize_fallback_for_unaligned_width(ctx, oracle):
     """A source width that is not a multiple of 4 cannot be staged by dword loads: the separate grey and per-tap resize
-    kernels run instead and must give the same working image."""
+    kernels run instead and must give the same working image.  Tinted like the image of test_grey_and_area_resize, so that
+    the separate grey kernel's channel order matters too."""
+    rng = np.random.default_rng(6)
     w, h = 2002, 1500
-    img = synth.render_blobs(w, h, 13)
+    base = synth.render_blobs(w, h, 13)
+    tint = rng.integers(0, 40, (h, w, 3), dtype=np.uint8)
+    img = np.clip(base.astype(np.int32) + tint - 20, 0, 255).astype(np.uint8)
     got, (ww, wh) = ctx.akaze_batch(img[None], max_kp=30000)
     small = oracle.gray_resize(img, ww, wh)
     ekp, edesc = oracle.akaze(small)
