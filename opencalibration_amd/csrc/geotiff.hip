@@ -17,11 +17,10 @@
 // into one of OUT_SLOTS output slots with an event each; the host reads a slot when a pass needs it again, at collect or at
 // finish - one wait, for the slot's event, and so not for what the caller enqueued on the stream since.
 #include "deflate_kernels.hpp"
+#include "live_handles.hpp"
 
 #include <deque>
 #include <memory>
-#include <mutex>
-#include <set>
 #include <vector>
 
 namespace
@@ -204,8 +203,7 @@ __global__ __launch_bounds__(THREADS) void gt_finish(const unsigned long long *t
         p[count[i] - 4 + k] = (uint8_t)(adler[i] >> (8 * (3 - k)));
 }
 
-std::mutex g_live_mutex;
-std::set<const void *> g_live; // the writers that exist: a destroyed handle is refused, not followed
+ochip::live_set<ochip_geotiff> g_live; // the writers that exist
 
 } // namespace
 
@@ -243,12 +241,6 @@ struct ochip_geotiff
 
 namespace
 {
-
-bool live(const ochip_geotiff *e)
-{
-    std::lock_guard<std::mutex> lock(g_live_mutex);
-    return e && g_live.count(e) != 0;
-}
 
 void release_host_side(ochip_geotiff *e)
 {
@@ -455,17 +447,14 @@ int ochip_geotiff_create(ochip_ctx *ctx, int kind, int64_t width, int64_t height
         e->mem.release();
         return rc;
     }
-    {
-        std::lock_guard<std::mutex> lock(g_live_mutex);
-        g_live.insert(e.get());
-    }
+    g_live.add(e.get());
     *out = e.release();
     return OCHIP_OK;
 }
 
 int ochip_geotiff_feed(ochip_geotiff *e, int64_t row0, int64_t rows, const void *pixels, int on_device)
 {
-    if (!live(e))
+    if (!g_live.has(e))
         return ochip_fail(nullptr, OCHIP_EINVAL, "ochip_geotiff_feed: not a live ochip_geotiff object");
     ochip_ctx *ctx = e->ctx;
     if (!pixels)
@@ -503,7 +492,7 @@ int ochip_geotiff_feed(ochip_geotiff *e, int64_t row0, int64_t rows, const void 
 
 int ochip_geotiff_payloads(ochip_geotiff *e, const uint8_t *payloads, int64_t n)
 {
-    if (!live(e))
+    if (!g_live.has(e))
         return ochip_fail(nullptr, OCHIP_EINVAL, "ochip_geotiff_payloads: not a live ochip_geotiff object");
     ochip_ctx *ctx = e->ctx;
     if (!payloads || n < 1 || n > e->tiles_x)
@@ -520,7 +509,7 @@ int ochip_geotiff_payloads(ochip_geotiff *e, const uint8_t *payloads, int64_t n)
 
 int ochip_geotiff_collect(ochip_geotiff *e, uint8_t *buf, uint64_t cap, uint64_t *bytes, uint64_t *counts, uint64_t max_tiles, uint64_t *tiles)
 {
-    if (!live(e))
+    if (!g_live.has(e))
         return ochip_fail(nullptr, OCHIP_EINVAL, "ochip_geotiff_collect: not a live ochip_geotiff object");
     ochip_ctx *ctx = e->ctx;
     if (!bytes || !tiles)
@@ -548,7 +537,7 @@ int ochip_geotiff_collect(ochip_geotiff *e, uint8_t *buf, uint64_t cap, uint64_t
 
 int ochip_geotiff_finish(ochip_geotiff *e)
 {
-    if (!live(e))
+    if (!g_live.has(e))
         return ochip_fail(nullptr, OCHIP_EINVAL, "ochip_geotiff_finish: not a live ochip_geotiff object");
     if (e->finished)
         return ochip_fail(e->ctx, OCHIP_ESTATE, "ochip_geotiff_finish: finished already");
@@ -561,11 +550,8 @@ int ochip_geotiff_finish(ochip_geotiff *e)
 
 void ochip_geotiff_destroy(ochip_geotiff *e)
 {
-    {
-        std::lock_guard<std::mutex> lock(g_live_mutex);
-        if (!e || g_live.erase(e) == 0)
-            return;
-    }
+    if (!g_live.remove(e))
+        return;
     if (e->ctx->stream.opened()) // nothing may still touch the blocks when they go back to the pools
         (void)ochip_stream_wait(e->ctx, e->ctx->stream);
     release_host_side(e);

@@ -17,10 +17,9 @@
 //                 raster at the tile's place, clipped at the raster's edges and cropped to the row window.
 #include "ctx.hpp"
 #include "inflate_rules.hpp"
+#include "live_handles.hpp"
 
 #include <memory>
-#include <mutex>
-#include <set>
 #include <vector>
 
 namespace
@@ -387,8 +386,7 @@ __global__ __launch_bounds__(THREADS) void gr_unpredict(const uint8_t *payloads,
     }
 }
 
-std::mutex g_live_mutex;
-std::set<const void *> g_live; // the readers that exist: a destroyed handle is refused, not followed
+ochip::live_set<ochip_geotiff_reader> g_live; // the readers that exist
 
 int launched(ochip_ctx *ctx, const char *what)
 {
@@ -407,12 +405,6 @@ struct ochip_geotiff_reader
 
 namespace
 {
-
-bool live(const ochip_geotiff_reader *r)
-{
-    std::lock_guard<std::mutex> lock(g_live_mutex);
-    return r && g_live.count(r) != 0;
-}
 
 // The streams of a call through the launches the budget allows.  expect: per stream, or nullptr for the reader's tile size.
 // With raster (device memory), every launch's payloads are un-predicted and placed.  status, produced: host arrays of n; out:
@@ -516,10 +508,7 @@ int ochip_geotiff_reader_create(ochip_ctx *ctx, int samples, int is_float, int64
     if (const char *why = refuse_layout(L))
         return ochip_fail(ctx, OCHIP_EINVAL, "ochip_geotiff_reader_create: %s", why);
     r->budget = scratch_budget ? scratch_budget : DEFAULT_BUDGET;
-    {
-        std::lock_guard<std::mutex> lock(g_live_mutex);
-        g_live.insert(r.get());
-    }
+    g_live.add(r.get());
     *out = r.release();
     return OCHIP_OK;
 }
@@ -527,7 +516,7 @@ int ochip_geotiff_reader_create(ochip_ctx *ctx, int samples, int is_float, int64
 int ochip_geotiff_reader_inflate(ochip_geotiff_reader *r, int64_t n, const uint8_t *streams, const uint64_t *offsets, const uint64_t *expect,
                                  uint8_t *out, uint64_t out_cap, int32_t *status, uint64_t *bytes)
 {
-    if (!live(r))
+    if (!g_live.has(r))
         return ochip_fail(nullptr, OCHIP_EINVAL, "ochip_geotiff_reader_inflate: not a live ochip_geotiff_reader object");
     if (const char *why = refuse_inflate(n, streams, offsets, expect, out, out_cap, status, bytes))
         return ochip_fail(r->ctx, OCHIP_EINVAL, "ochip_geotiff_reader_inflate: %s", why);
@@ -541,7 +530,7 @@ int ochip_geotiff_reader_inflate(ochip_geotiff_reader *r, int64_t n, const uint8
 int ochip_geotiff_reader_read(ochip_geotiff_reader *r, int64_t n, const uint8_t *streams, const uint64_t *offsets, int64_t row0, int64_t rows,
                               void *raster, int on_device, int64_t *bad_tile)
 {
-    if (!live(r))
+    if (!g_live.has(r))
         return ochip_fail(nullptr, OCHIP_EINVAL, "ochip_geotiff_reader_read: not a live ochip_geotiff_reader object");
     ochip_ctx *ctx = r->ctx;
     const tile_layout &L = r->L;
@@ -576,16 +565,13 @@ int ochip_geotiff_reader_read(ochip_geotiff_reader *r, int64_t n, const uint8_t 
 
 int64_t ochip_geotiff_reader_launches(ochip_geotiff_reader *r)
 {
-    return live(r) ? r->launches : -1;
+    return g_live.has(r) ? r->launches : -1;
 }
 
 void ochip_geotiff_reader_destroy(ochip_geotiff_reader *r)
 {
-    {
-        std::lock_guard<std::mutex> lock(g_live_mutex);
-        if (!r || g_live.erase(r) == 0)
-            return;
-    }
+    if (!g_live.remove(r))
+        return;
     delete r;
 }
 

@@ -5,11 +5,10 @@
 #include "../../../include/oc_host.h"
 
 #include "../deflate_rules.hpp"
+#include "../live_handles.hpp"
 
 #include <deque>
 #include <memory>
-#include <mutex>
-#include <set>
 #include <string>
 #include <vector>
 
@@ -25,8 +24,7 @@ int fail(int code, const std::string &text)
     return code;
 }
 
-std::mutex g_live_mutex;
-std::set<const void *> g_live; // the writers that exist: a destroyed handle is refused, not followed
+ochip::live_set<och_geotiff> g_live; // the writers that exist
 } // namespace
 
 struct och_geotiff
@@ -43,12 +41,6 @@ struct och_geotiff
 
 namespace
 {
-bool live(const och_geotiff *e)
-{
-    std::lock_guard<std::mutex> lock(g_live_mutex);
-    return e && g_live.count(e) != 0;
-}
-
 // The predicted payload of tile tx of the tile row held in e->rows; returns whether any byte of it is non-zero
 bool tile_payload(const och_geotiff *e, int64_t tx, uint8_t *payload)
 {
@@ -139,17 +131,14 @@ int och_geotiff_create(ochip_ctx *ctx, int kind, int64_t width, int64_t height, 
         e->kind = kind, e->sparse = sparse != 0, e->w = width, e->h = height, e->tiles_x = (width + TILE - 1) / TILE;
         e->rows.assign((size_t)TILE * (size_t)width, 0u);
     }
-    {
-        std::lock_guard<std::mutex> lock(g_live_mutex);
-        g_live.insert(e.get());
-    }
+    g_live.add(e.get());
     *out = e.release();
     return OCHIP_OK;
 }
 
 int och_geotiff_feed(och_geotiff *e, int64_t row0, int64_t rows, const void *pixels, int on_device)
 {
-    if (!live(e))
+    if (!g_live.has(e))
         return fail(OCHIP_EINVAL, "och_geotiff_feed: not a live och_geotiff object");
     if (e->dev)
     {
@@ -177,7 +166,7 @@ int och_geotiff_feed(och_geotiff *e, int64_t row0, int64_t rows, const void *pix
 
 int och_geotiff_payloads(och_geotiff *e, const uint8_t *payloads, int64_t n)
 {
-    if (!live(e))
+    if (!g_live.has(e))
         return fail(OCHIP_EINVAL, "och_geotiff_payloads: not a live och_geotiff object");
     if (e->dev)
     {
@@ -198,7 +187,7 @@ int och_geotiff_payloads(och_geotiff *e, const uint8_t *payloads, int64_t n)
 int och_geotiff_collect(och_geotiff *e, uint8_t *buf, uint64_t cap, uint64_t *bytes, uint64_t *counts, uint64_t max_tiles,
                         uint64_t *tiles)
 {
-    if (!live(e))
+    if (!g_live.has(e))
         return fail(OCHIP_EINVAL, "och_geotiff_collect: not a live och_geotiff object");
     if (!bytes || !tiles)
         return fail(OCHIP_EINVAL, "och_geotiff_collect: no place for the counts");
@@ -229,7 +218,7 @@ int och_geotiff_collect(och_geotiff *e, uint8_t *buf, uint64_t cap, uint64_t *by
 
 int och_geotiff_finish(och_geotiff *e)
 {
-    if (!live(e))
+    if (!g_live.has(e))
         return fail(OCHIP_EINVAL, "och_geotiff_finish: not a live och_geotiff object");
     if (e->dev)
     {
@@ -246,11 +235,8 @@ int och_geotiff_finish(och_geotiff *e)
 
 void och_geotiff_destroy(och_geotiff *e)
 {
-    {
-        std::lock_guard<std::mutex> lock(g_live_mutex);
-        if (!e || g_live.erase(e) == 0)
-            return;
-    }
+    if (!g_live.remove(e))
+        return;
     ochip_geotiff_destroy(e->dev);
     delete e;
 }

@@ -7,10 +7,9 @@
 #include "../../../include/oc_host.h"
 
 #include "../inflate_rules.hpp"
+#include "../live_handles.hpp"
 
 #include <memory>
-#include <mutex>
-#include <set>
 #include <string>
 #include <vector>
 
@@ -26,8 +25,7 @@ int fail(int code, const std::string &text)
     return code;
 }
 
-std::mutex g_live_mutex;
-std::set<const void *> g_live; // the readers that exist: a destroyed handle is refused, not followed
+ochip::live_set<och_geotiff_reader> g_live; // the readers that exist
 } // namespace
 
 struct och_geotiff_reader
@@ -36,15 +34,6 @@ struct och_geotiff_reader
     ochip_geotiff_reader *dev = nullptr; // the device route
     tile_layout L;                       // the host route
 };
-
-namespace
-{
-bool live(const och_geotiff_reader *r)
-{
-    std::lock_guard<std::mutex> lock(g_live_mutex);
-    return r && g_live.count(r) != 0;
-}
-} // namespace
 
 extern "C"
 {
@@ -80,10 +69,7 @@ int och_geotiff_reader_create(ochip_ctx *ctx, int samples, int is_float, int64_t
         if (const char *why = refuse_layout(L))
             return fail(OCHIP_EINVAL, std::string("och_geotiff_reader_create: ") + why);
     }
-    {
-        std::lock_guard<std::mutex> lock(g_live_mutex);
-        g_live.insert(r.get());
-    }
+    g_live.add(r.get());
     *out = r.release();
     return OCHIP_OK;
 }
@@ -91,7 +77,7 @@ int och_geotiff_reader_create(ochip_ctx *ctx, int samples, int is_float, int64_t
 int och_geotiff_reader_inflate(och_geotiff_reader *r, int64_t n, const uint8_t *streams, const uint64_t *offsets, const uint64_t *expect,
                                uint8_t *out, uint64_t out_cap, int32_t *status, uint64_t *bytes)
 {
-    if (!live(r))
+    if (!g_live.has(r))
         return fail(OCHIP_EINVAL, "och_geotiff_reader_inflate: not a live och_geotiff_reader object");
 #ifndef OCHIP_GEOTIFF_READ_STANDALONE
     if (r->dev)
@@ -117,7 +103,7 @@ int och_geotiff_reader_inflate(och_geotiff_reader *r, int64_t n, const uint8_t *
 int och_geotiff_reader_read(och_geotiff_reader *r, int64_t n, const uint8_t *streams, const uint64_t *offsets, int64_t row0, int64_t rows,
                             void *raster, int on_device, int64_t *bad_tile)
 {
-    if (!live(r))
+    if (!g_live.has(r))
         return fail(OCHIP_EINVAL, "och_geotiff_reader_read: not a live och_geotiff_reader object");
 #ifndef OCHIP_GEOTIFF_READ_STANDALONE
     if (r->dev)
@@ -156,7 +142,7 @@ int och_geotiff_reader_read(och_geotiff_reader *r, int64_t n, const uint8_t *str
 
 int64_t och_geotiff_reader_launches(och_geotiff_reader *r)
 {
-    if (!live(r))
+    if (!g_live.has(r))
         return -1;
 #ifndef OCHIP_GEOTIFF_READ_STANDALONE
     if (r->dev)
@@ -167,11 +153,8 @@ int64_t och_geotiff_reader_launches(och_geotiff_reader *r)
 
 void och_geotiff_reader_destroy(och_geotiff_reader *r)
 {
-    {
-        std::lock_guard<std::mutex> lock(g_live_mutex);
-        if (!r || g_live.erase(r) == 0)
-            return;
-    }
+    if (!g_live.remove(r))
+        return;
 #ifndef OCHIP_GEOTIFF_READ_STANDALONE
     ochip_geotiff_reader_destroy(r->dev);
 #endif

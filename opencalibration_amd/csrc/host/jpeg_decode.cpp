@@ -6,10 +6,9 @@
 #include "../../../include/oc_host.h"
 
 #include "../jpeg_decode.hpp"
+#include "../live_handles.hpp"
 
 #include <memory>
-#include <mutex>
-#include <set>
 #include <string>
 #include <vector>
 
@@ -25,8 +24,7 @@ int fail(const std::string &text)
     return -1;
 }
 
-std::mutex g_live_mutex;
-std::set<const void *> g_live; // the decoders that exist: a destroyed handle is refused, not followed
+ochip::live_set<och_jpeg_decoder> g_live; // the decoders that exist
 
 // The coefficients of every block, natural order, in the scan's order; false: the scan is not decodable
 bool decode_scan(const uint8_t *d, const parsed &p, std::vector<int16_t> &coef)
@@ -108,15 +106,6 @@ struct och_jpeg_decoder
     ochip_jpeg_decoder *dev = nullptr;
 };
 
-namespace
-{
-bool live(const och_jpeg_decoder *d)
-{
-    std::lock_guard<std::mutex> lock(g_live_mutex);
-    return d && g_live.count(d) != 0;
-}
-} // namespace
-
 extern "C"
 {
 
@@ -154,10 +143,7 @@ int och_jpeg_decoder_create(ochip_ctx *ctx, int subsequence_bits, och_jpeg_decod
             return fail(ochip_last_error(ctx));
 #endif
     }
-    {
-        std::lock_guard<std::mutex> lock(g_live_mutex);
-        g_live.insert(d.get());
-    }
+    g_live.add(d.get());
     *out = d.release();
     return 0;
 }
@@ -165,7 +151,7 @@ int och_jpeg_decoder_create(ochip_ctx *ctx, int subsequence_bits, och_jpeg_decod
 int och_jpeg_decoder_decode(och_jpeg_decoder *d, int64_t n, const uint8_t *const *files, const uint64_t *sizes, int apply_orientation,
                             void *out, uint64_t out_cap, const uint64_t *offsets, ochip_jpeg_file_info *info, int32_t *rounds)
 {
-    if (!live(d))
+    if (!g_live.has(d))
         return fail("och_jpeg_decoder_decode: not a live och_jpeg_decoder object");
 #ifndef OCHIP_JPEG_DECODE_STANDALONE
     if (d->dev)
@@ -189,11 +175,8 @@ int och_jpeg_decoder_decode(och_jpeg_decoder *d, int64_t n, const uint8_t *const
 
 void och_jpeg_decoder_destroy(och_jpeg_decoder *d)
 {
-    {
-        std::lock_guard<std::mutex> lock(g_live_mutex);
-        if (!d || g_live.erase(d) == 0)
-            return;
-    }
+    if (!g_live.remove(d))
+        return;
 #ifndef OCHIP_JPEG_DECODE_STANDALONE
     ochip_jpeg_decoder_destroy(d->dev);
 #endif

@@ -5,10 +5,9 @@
 #include "../../../include/oc_host.h"
 
 #include "../jpeg_encode.hpp"
+#include "../live_handles.hpp"
 
 #include <memory>
-#include <mutex>
-#include <set>
 #include <string>
 #include <vector>
 
@@ -24,8 +23,7 @@ int fail(int code, const std::string &text)
     return code;
 }
 
-std::mutex g_live_mutex;
-std::set<const void *> g_live; // the encoders that exist: a destroyed handle is refused, not followed
+ochip::live_set<och_jpeg> g_live; // the encoders that exist
 
 // Whole bytes go to the stream with an FF followed by 00; the bits of the last partial byte stay in acc
 struct byte_writer
@@ -113,12 +111,6 @@ struct och_jpeg
 
 namespace
 {
-bool live(const och_jpeg *e)
-{
-    std::lock_guard<std::mutex> lock(g_live_mutex);
-    return e && g_live.count(e) != 0;
-}
-
 void encode_rows(och_jpeg *e, const rows_view &v, int64_t mcu_row0, int64_t mcu_rows)
 {
     const int64_t mw = e->g.mw, n = mcu_rows * mw;
@@ -175,17 +167,14 @@ int och_jpeg_create(ochip_ctx *ctx, int64_t width, int64_t height, int quality, 
         e->carry.resize((size_t)15 * (size_t)width * 3);
         append_header(e->out.bytes, e->g, e->t);
     }
-    {
-        std::lock_guard<std::mutex> lock(g_live_mutex);
-        g_live.insert(e.get());
-    }
+    g_live.add(e.get());
     *out = e.release();
     return OCHIP_OK;
 }
 
 int och_jpeg_feed(och_jpeg *e, int64_t row0, int64_t rows, const void *pixels, int pixel_stride, int on_device)
 {
-    if (!live(e))
+    if (!g_live.has(e))
         return fail(OCHIP_EINVAL, "och_jpeg_feed: not a live och_jpeg object");
     if (e->dev)
     {
@@ -225,14 +214,14 @@ int och_jpeg_feed(och_jpeg *e, int64_t row0, int64_t rows, const void *pixels, i
 
 int64_t och_jpeg_pending(och_jpeg *e)
 {
-    if (!live(e))
+    if (!g_live.has(e))
         return 0;
     return e->dev ? ochip_jpeg_pending(e->dev) : (int64_t)e->out.bytes.size();
 }
 
 int och_jpeg_collect(och_jpeg *e, uint8_t *buf, uint64_t cap, uint64_t *n)
 {
-    if (!live(e))
+    if (!g_live.has(e))
         return fail(OCHIP_EINVAL, "och_jpeg_collect: not a live och_jpeg object");
     if (!n)
         return fail(OCHIP_EINVAL, "och_jpeg_collect: no count");
@@ -247,7 +236,7 @@ int och_jpeg_collect(och_jpeg *e, uint8_t *buf, uint64_t cap, uint64_t *n)
 
 int och_jpeg_finish(och_jpeg *e)
 {
-    if (!live(e))
+    if (!g_live.has(e))
         return fail(OCHIP_EINVAL, "och_jpeg_finish: not a live och_jpeg object");
     if (e->dev)
     {
@@ -263,11 +252,8 @@ int och_jpeg_finish(och_jpeg *e)
 
 void och_jpeg_destroy(och_jpeg *e)
 {
-    {
-        std::lock_guard<std::mutex> lock(g_live_mutex);
-        if (!e || g_live.erase(e) == 0)
-            return;
-    }
+    if (!g_live.remove(e))
+        return;
     ochip_jpeg_destroy(e->dev);
     delete e;
 }

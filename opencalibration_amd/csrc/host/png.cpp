@@ -5,12 +5,11 @@
 // route's tests.
 #include "../../../include/oc_host.h"
 
+#include "../live_handles.hpp"
 #include "capi_graph.hpp"
 #include "png_decode.hpp"
 
 #include <memory>
-#include <mutex>
-#include <set>
 #include <string>
 #include <vector>
 
@@ -28,8 +27,7 @@ int fail(int code, const std::string &text)
     return code;
 }
 
-std::mutex g_live_mutex;
-std::set<const void *> g_live; // the encoders that exist: a destroyed handle is refused, not followed
+ochip::live_set<och_png_encoder> g_live; // the encoders that exist
 
 // "" or why the batch is refused; shapes and the sum of the bounds
 std::string check_batch(int64_t n, const ochip_png_image *images, int base64, const uint8_t *out, uint64_t out_cap, const uint64_t *offsets,
@@ -143,15 +141,6 @@ struct och_png_encoder
     ochip_png_encoder *dev = nullptr; // the device route
 };
 
-namespace
-{
-bool live(const och_png_encoder *e)
-{
-    std::lock_guard<std::mutex> lock(g_live_mutex);
-    return e && g_live.count(e) != 0;
-}
-} // namespace
-
 extern "C"
 {
 
@@ -181,10 +170,7 @@ int och_png_encoder_create(ochip_ctx *ctx, och_png_encoder **out)
         if (rc != OCHIP_OK)
             return fail(rc, ochip_last_error(ctx));
     }
-    {
-        std::lock_guard<std::mutex> lock(g_live_mutex);
-        g_live.insert(e.get());
-    }
+    g_live.add(e.get());
     *out = e.release();
     return OCHIP_OK;
 }
@@ -192,7 +178,7 @@ int och_png_encoder_create(ochip_ctx *ctx, och_png_encoder **out)
 int och_png_encoder_encode(och_png_encoder *e, int64_t n, const ochip_png_image *images, int on_device, int base64, uint8_t *out,
                            uint64_t out_cap, uint64_t *offsets)
 {
-    if (!live(e))
+    if (!g_live.has(e))
         return fail(OCHIP_EINVAL, "och_png_encoder_encode: not a live och_png_encoder object");
     if (e->dev)
     {
@@ -224,11 +210,8 @@ int och_png_encoder_encode(och_png_encoder *e, int64_t n, const ochip_png_image 
 
 void och_png_encoder_destroy(och_png_encoder *e)
 {
-    {
-        std::lock_guard<std::mutex> lock(g_live_mutex);
-        if (!e || g_live.erase(e) == 0)
-            return;
-    }
+    if (!g_live.remove(e))
+        return;
     ochip_png_encoder_destroy(e->dev);
     delete e;
 }

@@ -19,12 +19,11 @@
 // a defined successor, and only jd_write reports errors.
 #include "ctx.hpp"
 #include "jpeg_decode.hpp"
+#include "live_handles.hpp"
 
 #include <rocprim/device/device_scan.hpp>
 
 #include <memory>
-#include <mutex>
-#include <set>
 
 namespace
 {
@@ -354,8 +353,7 @@ __global__ __launch_bounds__(THREADS) void jd_pixels(const batch B)
     px[0] = bgr[0], px[1] = bgr[1], px[2] = bgr[2];
 }
 
-std::mutex g_live_mutex;
-std::set<const void *> g_live; // the decoders that exist: a destroyed handle is refused, not followed
+ochip::live_set<ochip_jpeg_decoder> g_live; // the decoders that exist
 
 uint32_t blocks_of(uint64_t n)
 {
@@ -382,12 +380,6 @@ struct ochip_jpeg_decoder
 
 namespace
 {
-
-bool live(const ochip_jpeg_decoder *d)
-{
-    std::lock_guard<std::mutex> lock(g_live_mutex);
-    return d && g_live.count(d) != 0;
-}
 
 // Everything of a call behind the argument checks; mem holds the device blocks
 int decode_batch(ochip_jpeg_decoder *D, ochip::dev_blocks &mem, int64_t n, const uint8_t *const *files, const std::vector<parsed> &P,
@@ -544,10 +536,7 @@ int ochip_jpeg_decoder_create(ochip_ctx *ctx, int subsequence_bits, ochip_jpeg_d
     std::unique_ptr<ochip_jpeg_decoder> d(new ochip_jpeg_decoder);
     d->ctx = ctx;
     d->sub_bits = subsequence_bits ? (uint32_t)subsequence_bits : (uint32_t)DEFAULT_SUBSEQUENCE_BITS;
-    {
-        std::lock_guard<std::mutex> lock(g_live_mutex);
-        g_live.insert(d.get());
-    }
+    g_live.add(d.get());
     *out = d.release();
     return OCHIP_OK;
 }
@@ -555,7 +544,7 @@ int ochip_jpeg_decoder_create(ochip_ctx *ctx, int subsequence_bits, ochip_jpeg_d
 int ochip_jpeg_decoder_decode(ochip_jpeg_decoder *d, int64_t n, const uint8_t *const *files, const uint64_t *sizes, int apply_orientation,
                               void *out, uint64_t out_cap, const uint64_t *offsets, ochip_jpeg_file_info *info, int32_t *rounds)
 {
-    if (!live(d))
+    if (!g_live.has(d))
         return ochip_fail(nullptr, OCHIP_EINVAL, "ochip_jpeg_decoder_decode: not a live ochip_jpeg_decoder object");
     ochip_ctx *ctx = d->ctx;
     std::vector<parsed> P;
@@ -577,11 +566,8 @@ int ochip_jpeg_decoder_decode(ochip_jpeg_decoder *d, int64_t n, const uint8_t *c
 
 void ochip_jpeg_decoder_destroy(ochip_jpeg_decoder *d)
 {
-    {
-        std::lock_guard<std::mutex> lock(g_live_mutex);
-        if (!d || g_live.erase(d) == 0)
-            return;
-    }
+    if (!g_live.remove(d))
+        return;
     delete d;
 }
 

@@ -19,13 +19,12 @@
 // itself: the mosaic's band loop stays ahead of the device.
 #include "ctx.hpp"
 #include "jpeg_encode.hpp"
+#include "live_handles.hpp"
 
 #include <rocprim/device/device_scan.hpp>
 #include <rocprim/iterator/transform_iterator.hpp>
 
 #include <memory>
-#include <mutex>
-#include <set>
 
 namespace
 {
@@ -360,8 +359,7 @@ struct widen
     }
 };
 
-std::mutex g_live_mutex;
-std::set<const void *> g_live; // the encoders that exist: a destroyed handle is refused, not followed
+ochip::live_set<ochip_jpeg> g_live; // the encoders that exist
 
 size_t blocks_of(size_t n)
 {
@@ -416,12 +414,6 @@ struct ochip_jpeg
 
 namespace
 {
-
-bool live(const ochip_jpeg *e)
-{
-    std::lock_guard<std::mutex> lock(g_live_mutex);
-    return e && g_live.count(e) != 0;
-}
 
 // the events and the page-locked blocks (what was never made is NULL)
 void release_host_side(ochip_jpeg *e)
@@ -677,17 +669,14 @@ int ochip_jpeg_create(ochip_ctx *ctx, int64_t width, int64_t height, int quality
         return rc;
     }
     append_header(e->out.bytes, e->g, e->t);
-    {
-        std::lock_guard<std::mutex> lock(g_live_mutex);
-        g_live.insert(e.get());
-    }
+    g_live.add(e.get());
     *out = e.release();
     return OCHIP_OK;
 }
 
 int ochip_jpeg_feed(ochip_jpeg *e, int64_t row0, int64_t rows, const void *pixels, int pixel_stride, int on_device)
 {
-    if (!live(e))
+    if (!g_live.has(e))
         return ochip_fail(nullptr, OCHIP_EINVAL, "ochip_jpeg_feed: not a live ochip_jpeg object");
     ochip_ctx *ctx = e->ctx;
     if (!pixels)
@@ -712,7 +701,7 @@ int ochip_jpeg_feed(ochip_jpeg *e, int64_t row0, int64_t rows, const void *pixel
 
 int64_t ochip_jpeg_pending(ochip_jpeg *e)
 {
-    if (!live(e))
+    if (!g_live.has(e))
         return 0;
     (void)drain(e);
     return (int64_t)e->out.bytes.size();
@@ -720,7 +709,7 @@ int64_t ochip_jpeg_pending(ochip_jpeg *e)
 
 int ochip_jpeg_collect(ochip_jpeg *e, uint8_t *buf, uint64_t cap, uint64_t *n)
 {
-    if (!live(e))
+    if (!g_live.has(e))
         return ochip_fail(nullptr, OCHIP_EINVAL, "ochip_jpeg_collect: not a live ochip_jpeg object");
     if (!n)
         return ochip_fail(e->ctx, OCHIP_EINVAL, "ochip_jpeg_collect: no count");
@@ -732,7 +721,7 @@ int ochip_jpeg_collect(ochip_jpeg *e, uint8_t *buf, uint64_t cap, uint64_t *n)
 
 int ochip_jpeg_finish(ochip_jpeg *e)
 {
-    if (!live(e))
+    if (!g_live.has(e))
         return ochip_fail(nullptr, OCHIP_EINVAL, "ochip_jpeg_finish: not a live ochip_jpeg object");
     {
         progress probe = e->P;
@@ -748,11 +737,8 @@ int ochip_jpeg_finish(ochip_jpeg *e)
 
 void ochip_jpeg_destroy(ochip_jpeg *e)
 {
-    {
-        std::lock_guard<std::mutex> lock(g_live_mutex);
-        if (!e || g_live.erase(e) == 0)
-            return;
-    }
+    if (!g_live.remove(e))
+        return;
     if (e->ctx->stream.opened()) // nothing may still touch the blocks when they go back to the pools
         (void)ochip_stream_wait(e->ctx, e->ctx->stream);
     release_host_side(e);

@@ -10,14 +10,13 @@
 // No atomics anywhere: neither the counts nor the list of exhausted points (the tail of the sorted keys) need one, so a mesh
 // of two triangles costs what one of ten thousand does, up to the two long add chains.
 #include "ctx.hpp"
+#include "live_handles.hpp"
 #include "mesh_locate.hpp"
 
 #include <rocprim/device/device_radix_sort.hpp>
 
 #include <cstring>
 #include <memory>
-#include <mutex>
-#include <set>
 
 namespace
 {
@@ -129,8 +128,7 @@ __global__ __launch_bounds__(SUMS_THREADS) void segment_sums(const unsigned long
     }
 }
 
-std::mutex g_live_mutex;
-std::set<const void *> g_live; // the objects that exist: a destroyed handle is refused, not followed
+ochip::live_set<ochip_mesh_points> g_live; // the objects that exist
 
 struct pinned // a page-locked block of the context's pool for the length of a call
 {
@@ -165,20 +163,11 @@ struct ochip_mesh_points
     unsigned long long *keys = nullptr, *keys_sorted = nullptr;
 };
 
-namespace
-{
-bool live(const ochip_mesh_points *m)
-{
-    std::lock_guard<std::mutex> lock(g_live_mutex);
-    return m && g_live.count(m) != 0;
-}
-} // namespace
-
 // The cloud of a live object for another entry of the library that reads it where it lies (xyz_export.hip): read-only, the
 // object is not changed.  False for a handle that is not live.
 bool ochip::mesh_points_view(const ochip_mesh_points *m, ochip_ctx **ctx, const double **xyz, uint32_t *n)
 {
-    if (!live(m))
+    if (!g_live.has(m))
         return false;
     *ctx = m->ctx, *xyz = m->xyz, *n = m->n;
     return true;
@@ -235,23 +224,20 @@ int ochip_mesh_points_create(ochip_ctx *ctx, const double *xyz, uint64_t n, ochi
             return rc;
         }
     }
-    {
-        std::lock_guard<std::mutex> lock(g_live_mutex);
-        g_live.insert(m.get());
-    }
+    g_live.add(m.get());
     *out = m.release();
     return OCHIP_OK;
 }
 
 uint64_t ochip_mesh_points_size(const ochip_mesh_points *m)
 {
-    return live(m) ? m->n : 0;
+    return g_live.has(m) ? m->n : 0;
 }
 
 int ochip_mesh_points_count(ochip_mesh_points *m, const ochip_locate_table *tab, int max_steps, uint32_t *count, uint32_t *first,
                             double *sum, double *sum_sq, uint32_t *exhausted, uint64_t exhausted_cap, uint64_t *n_exhausted)
 {
-    if (!live(m))
+    if (!g_live.has(m))
         return ochip_fail(nullptr, OCHIP_EINVAL, "ochip_mesh_points_count: not a live ochip_mesh_points object");
     ochip_ctx *ctx = m->ctx;
     if (!tab || !n_exhausted || max_steps < 0)
@@ -366,7 +352,7 @@ int ochip_mesh_points_count(ochip_mesh_points *m, const ochip_locate_table *tab,
 
 int ochip_mesh_points_where(ochip_mesh_points *m, uint32_t *where)
 {
-    if (!live(m))
+    if (!g_live.has(m))
         return ochip_fail(nullptr, OCHIP_EINVAL, "ochip_mesh_points_where: not a live ochip_mesh_points object");
     ochip_ctx *ctx = m->ctx;
     if (!m->counted)
@@ -383,11 +369,8 @@ int ochip_mesh_points_where(ochip_mesh_points *m, uint32_t *where)
 
 void ochip_mesh_points_destroy(ochip_mesh_points *m)
 {
-    {
-        std::lock_guard<std::mutex> lock(g_live_mutex);
-        if (!m || g_live.erase(m) == 0)
-            return;
-    }
+    if (!g_live.remove(m))
+        return;
     if (!m->mem.empty() && m->ctx->stream.opened()) // nothing may still touch the blocks when they go back to the pool
         (void)ochip_stream_wait(m->ctx, m->ctx->stream);
     m->mem.release();

@@ -19,11 +19,10 @@
 //   png_base64       a lane per 12 input bytes, into the output
 // and two copies: the offsets, then as many bytes as they say.  Steps that depend on each other are separate launches.
 #include "deflate_kernels.hpp"
+#include "live_handles.hpp"
 #include "png_rules.hpp"
 
 #include <memory>
-#include <mutex>
-#include <set>
 #include <vector>
 
 namespace
@@ -404,8 +403,7 @@ __global__ __launch_bounds__(THREADS) void png_base64(const img_desc *descs, con
     }
 }
 
-std::mutex g_live_mutex;
-std::set<const void *> g_live; // the encoders that exist: a destroyed handle is refused, not followed
+ochip::live_set<ochip_png_encoder> g_live; // the encoders that exist
 
 // A device array of the encoder that only grows: a batch that needs more takes a new block a quarter larger
 struct grown
@@ -429,12 +427,6 @@ struct ochip_png_encoder
 
 namespace
 {
-
-bool live(const ochip_png_encoder *e)
-{
-    std::lock_guard<std::mutex> lock(g_live_mutex);
-    return e && g_live.count(e) != 0;
-}
 
 int ensure_pinned(ochip_ctx *ctx, void **p, size_t *have, size_t want)
 {
@@ -464,20 +456,17 @@ int ochip_png_encoder_create(ochip_ctx *ctx, ochip_png_encoder **out)
         return OCHIP_EINVAL;
     if (!out)
         return ochip_fail(ctx, OCHIP_EINVAL, "ochip_png_encoder_create: out is NULL");
-    ochip_png_encoder *e = new ochip_png_encoder;
+    std::unique_ptr<ochip_png_encoder> e(new ochip_png_encoder);
     e->ctx = ctx, e->mem.ctx = ctx, e->mem.what = "ochip_png_encoder";
-    {
-        std::lock_guard<std::mutex> lock(g_live_mutex);
-        g_live.insert(e);
-    }
-    *out = e;
+    g_live.add(e.get());
+    *out = e.release();
     return OCHIP_OK;
 }
 
 int ochip_png_encoder_encode(ochip_png_encoder *e, int64_t n64, const ochip_png_image *images, int on_device, int base64, uint8_t *out,
                              uint64_t out_cap, uint64_t *offsets)
 {
-    if (!live(e))
+    if (!g_live.has(e))
         return ochip_fail(nullptr, OCHIP_EINVAL, "ochip_png_encoder_encode: not a live ochip_png_encoder object");
     ochip_ctx *ctx = e->ctx;
     // ---- everything is checked before anything is enqueued ----
@@ -657,11 +646,8 @@ int ochip_png_encoder_encode(ochip_png_encoder *e, int64_t n64, const ochip_png_
 
 void ochip_png_encoder_destroy(ochip_png_encoder *e)
 {
-    {
-        std::lock_guard<std::mutex> lock(g_live_mutex);
-        if (!e || g_live.erase(e) == 0)
-            return;
-    }
+    if (!g_live.remove(e))
+        return;
     if (e->ctx->stream.opened()) // nothing may still touch the blocks when they go back to the pools
         (void)ochip_stream_wait(e->ctx, e->ctx->stream);
     ochip_host_free(e->ctx, e->pin_in);

@@ -13,6 +13,7 @@
 //                     16-byte words (bytes at the two ragged ends)
 // Point order throughout, no atomics: the same bytes on every run.
 #include "ctx.hpp"
+#include "live_handles.hpp"
 #include "xyz_export.hpp"
 
 #include <rocprim/device/device_radix_sort.hpp>
@@ -23,8 +24,6 @@
 
 #include <cstring>
 #include <memory>
-#include <mutex>
-#include <set>
 #include <vector>
 
 namespace
@@ -169,8 +168,7 @@ __global__ __launch_bounds__(THREADS) void format_numbers(const double *__restri
     text[i] = cells[threadIdx.x];
 }
 
-std::mutex g_live_mutex;
-std::set<const void *> g_live; // the objects that exist: a destroyed handle is refused, not followed
+ochip::live_set<ochip_xyz_export> g_live; // the objects that exist
 
 struct pinned // a page-locked block of the context's pool for the length of a call
 {
@@ -215,12 +213,6 @@ struct ochip_xyz_export
 
 namespace
 {
-bool live(const ochip_xyz_export *e)
-{
-    std::lock_guard<std::mutex> lock(g_live_mutex);
-    return e && g_live.count(e) != 0;
-}
-
 int new_export(ochip_ctx *ctx, uint64_t n, const char *who, std::unique_ptr<ochip_xyz_export> &e)
 {
     if (n >= (1ull << 32))
@@ -236,10 +228,7 @@ int new_export(ochip_ctx *ctx, uint64_t n, const char *who, std::unique_ptr<ochi
 
 int publish(std::unique_ptr<ochip_xyz_export> &e, ochip_xyz_export **out)
 {
-    {
-        std::lock_guard<std::mutex> lock(g_live_mutex);
-        g_live.insert(e.get());
-    }
+    g_live.add(e.get());
     *out = e.release();
     return OCHIP_OK;
 }
@@ -385,12 +374,12 @@ int ochip_xyz_export_create_from_points(ochip_ctx *ctx, const ochip_mesh_points 
 
 uint64_t ochip_xyz_export_size(const ochip_xyz_export *e)
 {
-    return live(e) ? e->n : 0;
+    return g_live.has(e) ? e->n : 0;
 }
 
 int ochip_xyz_export_bounds(ochip_xyz_export *e, int64_t *bounds6)
 {
-    if (!live(e))
+    if (!g_live.has(e))
         return ochip_fail(nullptr, OCHIP_EINVAL, "ochip_xyz_export_bounds: not a live ochip_xyz_export object");
     ochip_ctx *ctx = e->ctx;
     if (!bounds6)
@@ -466,7 +455,7 @@ int ochip_xyz_export_bounds(ochip_xyz_export *e, int64_t *bounds6)
 
 int ochip_xyz_export_text_size(ochip_xyz_export *e, const int64_t *bounds6, uint64_t *bytes, uint64_t *kept)
 {
-    if (!live(e))
+    if (!g_live.has(e))
         return ochip_fail(nullptr, OCHIP_EINVAL, "ochip_xyz_export_text_size: not a live ochip_xyz_export object");
     ochip_ctx *ctx = e->ctx;
     if (!bytes || !kept)
@@ -537,7 +526,7 @@ int ochip_xyz_export_text_size(ochip_xyz_export *e, const int64_t *bounds6, uint
 
 int ochip_xyz_export_text(ochip_xyz_export *e, char *out, uint64_t cap)
 {
-    if (!live(e))
+    if (!g_live.has(e))
         return ochip_fail(nullptr, OCHIP_EINVAL, "ochip_xyz_export_text: not a live ochip_xyz_export object");
     ochip_ctx *ctx = e->ctx;
     if (!e->sized)
@@ -567,11 +556,8 @@ int ochip_xyz_export_text(ochip_xyz_export *e, char *out, uint64_t cap)
 
 void ochip_xyz_export_destroy(ochip_xyz_export *e)
 {
-    {
-        std::lock_guard<std::mutex> lock(g_live_mutex);
-        if (!e || g_live.erase(e) == 0)
-            return;
-    }
+    if (!g_live.remove(e))
+        return;
     if (!e->mem.empty() && e->ctx->stream.opened()) // nothing may still touch the blocks when they go back to the pool
         (void)ochip_stream_wait(e->ctx, e->ctx->stream);
     e->mem.release();

@@ -500,17 +500,60 @@ def relax_options(*names):
     return bits
 
 
-class Surface:
+class _Handle:
+    """A native object of the host library behind `h` (library `L`): closed once, by close(), a with block or the
+    collector, whichever comes first, and also when __init__ raised half-way.  _destroy and _last_error name the
+    family's functions; _check(rc) turns a refused call into the family's exception with the library's text."""
+
+    _destroy = None       # "och_..._destroy"
+    _last_error = None    # "och_..._last_error"; None: the family keeps no text
+    _failure = capi.OchipError
+
+    def _error(self):
+        return getattr(self.L, self._last_error)().decode()
+
+    def _check(self, rc):
+        if rc != 0:
+            raise self._failure(self._error())
+        return rc
+
+    def _context(self):
+        """the context whose pools the object's device blocks came from; None: the CPU route"""
+        return getattr(self, "ctx", None)
+
+    def _destroy_native(self):
+        getattr(self.L, self._destroy)(self.h)
+
+    def _released(self):
+        """after every close: drop what was kept alive for the native object"""
+
+    def close(self):
+        if getattr(self, "h", None):
+            ctx = self._context()
+            # a context closed first has taken the device with it: nothing can be handed back to its pools then
+            if ctx is None or getattr(ctx, "h", None):
+                self._destroy_native()
+        self.h = None
+        self._released()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        self.close()
+
+
+class Surface(_Handle):
     """surface_model of the host library: mesh (vertices, edges {source, dest, border, opposite 0, opposite 1}) + cloud."""
+
+    _destroy = "och_surface_destroy"
 
     def __init__(self):
         self.L = load()
         self.h = self.L.och_surface_create()
-
-    def __del__(self):
-        if getattr(self, "h", None):
-            self.L.och_surface_destroy(self.h)
-            self.h = None
 
     def arrays(self):
         nv, ne, nc = C.c_size_t(0), C.c_size_t(0), C.c_size_t(0)
@@ -614,9 +657,11 @@ class Surface:
         return self
 
 
-class PointCounter:
+class PointCounter(_Handle):
     """A cloud kept for counts against changing meshes (host/mesh_points.hpp): on the device with ctx (uploaded once), in
     host memory without.  count(surface): count_points_per_triangle's rows for the surface's mesh and THIS cloud."""
+
+    _destroy = "och_point_counter_destroy"
 
     def __init__(self, points, ctx=None, max_steps=100):
         self.L = load()
@@ -637,13 +682,6 @@ class PointCounter:
             raise capi.OchipError("point counter: " + self.L.och_points_last_error().decode())
         self.exhausted = int(ex[0])
         return tri[:n], st[:n, 0].astype(np.int64), st[:n, 1]
-
-    def close(self):
-        if getattr(self, "h", None):
-            self.L.och_point_counter_destroy(self.h)
-            self.h = None
-
-    __del__ = close
 
 
 def validate_checkpoint(path):
@@ -930,31 +968,20 @@ def dsm_plan(graph, surfaces, max_output_megapixels=0.0):
     return _plan_dict(plan8)
 
 
-class OrthoMesh:
+class OrthoMesh(_Handle):
     """The surfaces' triangle table on the device (ochip_ortho_mesh), for rendering DSM bands."""
+
+    _last_error = "och_ortho_last_error"
 
     def __init__(self, ctx, surfaces):
         self.L, self.ctx = load(), ctx
         arr, n = _surface_array(surfaces)
         self.h = C.c_void_p()
         if self.L.och_ortho_mesh_upload(ctx.h, arr, n, C.byref(self.h)) != 0:
-            raise capi.OchipError("ortho mesh upload failed: " + self.L.och_ortho_last_error().decode())
+            raise capi.OchipError("ortho mesh upload failed: " + self._error())
 
-    def close(self):
-        if getattr(self, "h", None):
-            # a context closed first has taken the device with it: the table cannot be handed back to its pool then
-            if getattr(self.ctx, "h", None):
-                capi.load().ochip_ortho_mesh_destroy(self.h)
-            self.h = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        self.close()
+    def _destroy_native(self):
+        capi.load().ochip_ortho_mesh_destroy(self.h)  # the table is the device library's own object
 
 
 def dsm_render(plan, surfaces=(), mesh=None, row0=0, rows=None, out=None, debug=False):
@@ -1226,7 +1253,7 @@ def ortho_residency_plan(used, capacity, resident=None):
     return [[tuple(int(v) for v in l) for l in loads[int(off[k]):int(off[k + 1])]] for k in range(used.shape[0])], state
 
 
-class OrthoStream:
+class OrthoStream(_Handle):
     """The layered render of `plan` in bands of tile_rows output tile rows, its source images streamed through `capacity`
     device slots (och_ortho_stream_*).  mesh (an OrthoMesh): on its device, the slots one block of its context's pool;
     None: the CPU route with the slots in host memory.  The caller drives it: for band k upload(k, camera, image) every
@@ -1234,40 +1261,29 @@ class OrthoStream:
     page-locked - then render(k); bands ascend, rewind() starts a further sweep from the images the slots hold.  A call
     out of the plan's order raises OchipError and launches nothing."""
 
+    _destroy, _last_error = "och_ortho_stream_destroy", "och_ortho_stream_last_error"
+
     def __init__(self, plan, graph, surfaces, capacity, mesh=None, tile_rows=1, config=None):
         self.L, self.plan, self.mesh, self.graph, self.surfaces = load(), dict(plan), mesh, graph, list(surfaces)
         self.cfg, self.config4 = _layers_config(config)
         self.tile_rows = tile_rows
         self.arr, n = _surface_array(self.surfaces)
-        self.h = C.c_void_p()
+        self.h = None
         self._keep = []
         self.jpeg_status = []  # the status names of the last upload_jpegs call's files, also when it raised
-        if self.L.och_ortho_stream_create(graph.h, mesh.ctx.h if mesh is not None else None, mesh.h if mesh is not None else None,
-                                          self.arr, n, _plan_array(plan), self.config4.ctypes.data, int(tile_rows), int(capacity),
-                                          C.byref(self.h)) != 0:
-            self.h = None
-            raise capi.OchipError(self._error())
+        h = C.c_void_p()
+        self._check(self.L.och_ortho_stream_create(graph.h, mesh.ctx.h if mesh is not None else None,
+                                                   mesh.h if mesh is not None else None, self.arr, n, _plan_array(plan),
+                                                   self.config4.ctypes.data, int(tile_rows), int(capacity), C.byref(h)))
+        self.h = h
         self.image_hw = ortho_layers_cameras(graph, surfaces)["image_hw"]
         self.num_bands = int(self.L.och_ortho_stream_num_bands(self.h))
 
-    def _error(self):
-        return self.L.och_ortho_stream_last_error().decode()
+    def _context(self):
+        return self.mesh.ctx if self.mesh is not None else None
 
-    def close(self):
-        if getattr(self, "h", None):
-            if self.mesh is None or getattr(self.mesh.ctx, "h", None):  # as OrthoMesh.close: the context may be gone
-                self.L.och_ortho_stream_destroy(self.h)
-            self.h = None
-            self._keep = []
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        self.close()
+    def _released(self):
+        self._keep = []
 
     def band_cameras(self, band):
         n = self.L.och_ortho_stream_band_cameras(self.h, band, None)
@@ -1294,8 +1310,7 @@ class OrthoStream:
             ptr = image.data_ptr()
         if shape is not None and not ok:
             raise ValueError(f"camera {camera}'s image is a contiguous uint8 host array of {shape}")
-        if self.L.och_ortho_stream_upload(self.h, band, camera, ptr) != 0:
-            raise capi.OchipError(self._error())
+        self._check(self.L.och_ortho_stream_upload(self.h, band, camera, ptr))
         self._keep.append((band, image))
 
     def upload_jpegs(self, band, cameras, files):
@@ -1319,8 +1334,7 @@ class OrthoStream:
         rc = self.L.och_ortho_stream_upload_jpegs(self.h, band, n, cams.ctypes.data, ptrs.ctypes.data, sizes.ctypes.data,
                                                   rec.ctypes.data)
         self.jpeg_status = [JPEG_STATUS[s] if 0 <= s < 3 else None for s in rec["status"][:n].tolist()]
-        if rc != 0:
-            raise capi.OchipError(self._error())
+        self._check(rc)
         return self.jpeg_status
 
     def render(self, band, out=None, dsm=None, debug_knn=False):
@@ -1338,8 +1352,7 @@ class OrthoStream:
         return res
 
     def rewind(self):
-        if self.L.och_ortho_stream_rewind(self.h) != 0:
-            raise capi.OchipError(self._error())
+        self._check(self.L.och_ortho_stream_rewind(self.h))
 
     def upload_end_ms(self, band):
         """when band's last upload finished on the device, ms since the sweep began (None: the band loaded nothing)"""
@@ -1819,7 +1832,7 @@ def ortho_tile_thumbs(pixels, pass_, tile_size=None, weight=None, ctx=None):
     return out
 
 
-class TileProgress:
+class TileProgress(_Handle):
     """The per-tile updates of a raster's layer and blend passes, band by band (och_tile_progress_*).
     plan: the raster (dsm_plan); ctx None: the CPU route, numpy bands; ctx: numpy bands through its device, or CUDA tensors,
     fed on the context's stream without a host wait - the caller has torch's work on a band finished before feed, as
@@ -1827,6 +1840,8 @@ class TileProgress:
     width), pass 2 rgba (rows, width, 4); row0 lies on a tile row and a pass's bands arrive in raster order without gaps.
     collect(): waits for the oldest fed band alone and returns its tiles in tile order as dicts of TILE_UPDATE_DTYPE's
     fields plus thumbnail, a (thumb_h, thumb_w, 4) uint8 BGRA array; raw=True: (records, slots) as the library wrote them."""
+
+    _destroy, _last_error = "och_tile_progress_destroy", "och_tile_progress_last_error"
 
     def __init__(self, plan, tile_size=None, num_layers=None, ctx=None):
         self.L, self.ctx, self.plan = load(), ctx, dict(plan)
@@ -1836,45 +1851,26 @@ class TileProgress:
         self._keep = []
         self._png = None  # the PngEncoder of collect(png=True), made by the first such call
         h = C.c_void_p()
-        if self.L.och_tile_progress_create(ctx.h if ctx is not None else None, _plan_array(plan), self.tile_size, self.num_layers,
-                                           C.byref(h)) != 0:
-            raise capi.OchipError(self._error())
+        self._check(self.L.och_tile_progress_create(ctx.h if ctx is not None else None, _plan_array(plan), self.tile_size,
+                                                    self.num_layers, C.byref(h)))
         self.h = h
 
-    def _error(self):
-        return self.L.och_tile_progress_last_error().decode()
-
-    def close(self):
-        if getattr(self, "h", None):
-            if self.ctx is None or getattr(self.ctx, "h", None):  # as OrthoStream.close: the context may be gone
-                self.L.och_tile_progress_destroy(self.h)
-            self.h = None
-            self._keep = []
+    def _released(self):
+        self._keep = []
         if getattr(self, "_png", None) is not None:
             self._png.close()
             self._png = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        self.close()
 
     def feed(self, pass_, row0, pixels, weight=None):
         nl, rows, w, on_device, p, pw, keep = _tile_band(pass_, pixels, weight, None if self.ctx is None else self.ctx.device)
         if w != self.plan["width"] or (pass_ == TILE_PASS_LAYERS and nl != self.num_layers):
             raise ValueError(f"a band of this raster is {self.plan['width']} pixels wide, of {self.num_layers} layers")
-        if self.L.och_tile_progress_feed(self.h, int(pass_), int(row0), rows, int(on_device), p, pw) != 0:
-            raise capi.OchipError(self._error())
+        self._check(self.L.och_tile_progress_feed(self.h, int(pass_), int(row0), rows, int(on_device), p, pw))
         self._keep.append(keep if on_device else None)  # the kernel may still read a device band: alive until collected
 
     def seek(self, pass_, row0):
         """pass_'s next band starts at row0, a tile row: for a caller that reports a part of the raster"""
-        if self.L.och_tile_progress_seek(self.h, int(pass_), int(row0)) != 0:
-            raise capi.OchipError(self._error())
+        self._check(self.L.och_tile_progress_seek(self.h, int(pass_), int(row0)))
 
     def pending(self):
         return int(self.L.och_tile_progress_pending(self.h))
@@ -1883,13 +1879,11 @@ class TileProgress:
         """png: every update also has png_base64, the thumbnail as the base64 of a PNG file (B G R A in, R G B A in the
         file), the band's tiles encoded as one batch on the object's route"""
         n = C.c_uint64(0)
-        if self.L.och_tile_progress_collect(self.h, None, None, 0, C.byref(n)) != 0:
-            raise capi.OchipError(self._error())
+        self._check(self.L.och_tile_progress_collect(self.h, None, None, 0, C.byref(n)))
         side = min(self.tile_size, 128)
         records = np.zeros(n.value, TILE_UPDATE_DTYPE)
         slots = np.zeros((n.value, side * side, 4), np.uint8)
-        if self.L.och_tile_progress_collect(self.h, records.ctypes.data, slots.ctypes.data, n.value, C.byref(n)) != 0:
-            raise capi.OchipError(self._error())
+        self._check(self.L.och_tile_progress_collect(self.h, records.ctypes.data, slots.ctypes.data, n.value, C.byref(n)))
         self._keep.pop(0)
         if raw:
             return records, slots
@@ -1925,7 +1919,7 @@ def ortho_tile_updates(plan, pixels, pass_, row0=0, tile_size=None, weight=None,
 
 
 # ---- the textured OBJ's JPEG texture (include/oc_host.h) ------------------------------------------------
-class JpegEncoder:
+class JpegEncoder(_Handle):
     """A baseline JPEG (YCbCr 4:2:0, cv::imwrite's settings) of a width x height raster fed band by band (och_jpeg_*; the
     rules: DESIGN.md §4.17).  ctx None: the CPU route, numpy bands.  ctx with on_device: CUDA tensors on ctx's device, fed
     on the context's stream - the caller has torch's work on a band finished before feed, as ortho_blend does.  ctx
@@ -1933,6 +1927,8 @@ class JpegEncoder:
     channels R, G, B first; bands ascend and are contiguous from row 0, of any row count.  collect(): the file's bytes
     that are complete and not collected yet (the header first).  finish(): the rest, EOI included.  A gap, an overlap, a
     feed after finish and a finish before the last row raise OchipError naming the rows."""
+
+    _destroy, _last_error = "och_jpeg_destroy", "och_jpeg_last_error"
 
     def __init__(self, width, height, ctx=None, quality=95, on_device=False):
         self.L, self.width, self.height, self.ctx = load(), int(width), int(height), ctx
@@ -1942,28 +1938,11 @@ class JpegEncoder:
         self.h = None
         self._keep = []
         h = C.c_void_p()
-        if self.L.och_jpeg_create(ctx.h if ctx is not None else None, self.width, self.height, int(quality), C.byref(h)) != 0:
-            raise capi.OchipError(self._error())
+        self._check(self.L.och_jpeg_create(ctx.h if ctx is not None else None, self.width, self.height, int(quality), C.byref(h)))
         self.h = h
 
-    def _error(self):
-        return self.L.och_jpeg_last_error().decode()
-
-    def close(self):
-        if getattr(self, "h", None):
-            if self.ctx is None or getattr(self.ctx, "h", None):  # as OrthoStream.close: the context may be gone
-                self.L.och_jpeg_destroy(self.h)
-            self.h = None
-            self._keep = []
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        self.close()
+    def _released(self):
+        self._keep = []
 
     def feed(self, row0, band):
         shape = tuple(int(v) for v in band.shape)
@@ -1975,8 +1954,8 @@ class JpegEncoder:
         else:
             band = np.ascontiguousarray(band)
             ptr = band.ctypes.data
-        if shape[0] > 0 and self.L.och_jpeg_feed(self.h, int(row0), shape[0], ptr, shape[2], int(self.on_device)) != 0:
-            raise capi.OchipError(self._error())
+        if shape[0] > 0:
+            self._check(self.L.och_jpeg_feed(self.h, int(row0), shape[0], ptr, shape[2], int(self.on_device)))
 
     def pending(self):
         """the bytes collect() would return now"""
@@ -1989,17 +1968,14 @@ class JpegEncoder:
     def _collect(self, cap=None):
         """collect() as a uint8 array, for a writer that takes the buffer as it is"""
         n = C.c_uint64(0)
-        if self.L.och_jpeg_collect(self.h, None, 0, C.byref(n)) != 0:
-            raise capi.OchipError(self._error())
+        self._check(self.L.och_jpeg_collect(self.h, None, 0, C.byref(n)))
         self._keep = []  # collect has waited for the kernels
         buf = np.empty(max(int(n.value if cap is None else cap), 1), np.uint8)
-        if self.L.och_jpeg_collect(self.h, buf.ctypes.data, int(n.value if cap is None else cap), C.byref(n)) != 0:
-            raise capi.OchipError(self._error())
+        self._check(self.L.och_jpeg_collect(self.h, buf.ctypes.data, int(n.value if cap is None else cap), C.byref(n)))
         return buf[:n.value]
 
     def finish(self):
-        if self.L.och_jpeg_finish(self.h) != 0:
-            raise capi.OchipError(self._error())
+        self._check(self.L.och_jpeg_finish(self.h))
         return self.collect()
 
 
@@ -2091,11 +2067,13 @@ def jpeg_metadata(data, want_status=False):
     return (out, METADATA_STATUS[status]) if want_status else out
 
 
-class GeoCoord:
+class GeoCoord(_Handle):
     """The survey's local frame (GeoCoord of the reference; och_geo_*): a Transverse Mercator on WGS84
     about (lat, lon) with k0 = 1 and no false origin, metres east and north of the origin.  The reference writes the origin
     into its WKT with six significant digits, so the projection's centre is `centre` = float("%g" % each) while `origin`
     stays as given; wkt() is that text."""
+
+    _destroy = "och_geo_destroy"
 
     def __init__(self, lat, lon):
         self.L = load()
@@ -2105,11 +2083,6 @@ class GeoCoord:
         o = np.zeros(4)
         self.L.och_geo_origin(self.h, o)
         self.origin, self.centre = (float(o[0]), float(o[1])), (float(o[2]), float(o[3]))
-
-    def __del__(self):
-        if getattr(self, "h", None):
-            self.L.och_geo_destroy(self.h)
-            self.h = None
 
     def to_local(self, lat, lon, alt=0.0):
         """(lat, lon, alt), scalars or arrays of one length, to (..., 3) easting, northing, altitude; NaN NaN NaN for a
@@ -2168,35 +2141,19 @@ class JpegBatch:
         return self.pixels[self.offsets[i]:self.offsets[i] + h * w * 3].reshape(h, w, 3)
 
 
-class JpegDecoder:
+class JpegDecoder(_Handle):
     """Baseline JPEG files to B G R pixels, a batch per call (och_jpeg_decoder_*; the rules: DESIGN.md §4.18): what
     cv::imread gives - libjpeg-turbo's default decode with the EXIF orientation applied.  ctx: the device route, the pixels
     stay on ctx's device; ctx None: the host loops.  subsequence_bits: the length of the pieces a scan is decoded in on the
     device, a multiple of 32; 0: the default."""
 
+    _destroy, _last_error = "och_jpeg_decoder_destroy", "och_jpeg_decode_last_error"
+
     def __init__(self, ctx=None, subsequence_bits=0):
         self.L, self.ctx, self.h = load(), ctx, None
         h = C.c_void_p()
-        if self.L.och_jpeg_decoder_create(ctx.h if ctx is not None else None, int(subsequence_bits), C.byref(h)) != 0:
-            raise capi.OchipError(self._error())
+        self._check(self.L.och_jpeg_decoder_create(ctx.h if ctx is not None else None, int(subsequence_bits), C.byref(h)))
         self.h = h
-
-    def _error(self):
-        return self.L.och_jpeg_decode_last_error().decode()
-
-    def close(self):
-        if getattr(self, "h", None):
-            self.L.och_jpeg_decoder_destroy(self.h)
-            self.h = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        self.close()
 
     def decode(self, files, out=None, apply_orientation=True):
         """files: bytes objects or paths.  out: where the pixels go - a flat uint8 CUDA tensor on ctx's device (numpy array on
@@ -2213,8 +2170,7 @@ class JpegDecoder:
         if out is None:
             total = 0
             for i in range(n):
-                if self.L.och_jpeg_info(int(ptrs[i]), int(sizes[i]), apply, rec[i:].ctypes.data) != 0:
-                    raise capi.OchipError(self._error())
+                self._check(self.L.och_jpeg_info(int(ptrs[i]), int(sizes[i]), apply, rec[i:].ctypes.data))
                 total += int(rec[i]["width"]) * int(rec[i]["height"]) * 3 if rec[i]["status"] == 0 else 0
         if self.ctx is not None:
             import torch
@@ -2233,9 +2189,8 @@ class JpegDecoder:
                 raise ValueError("out of the CPU route is a flat contiguous uint8 array")
             cap, ptr = out.size, out.ctypes.data
         rounds = np.zeros(2, np.int32)
-        if self.L.och_jpeg_decoder_decode(self.h, n, ptrs.ctypes.data, sizes.ctypes.data, apply, ptr, cap, None, rec.ctypes.data,
-                                          rounds.ctypes.data) != 0:
-            raise capi.OchipError(self._error())
+        self._check(self.L.och_jpeg_decoder_decode(self.h, n, ptrs.ctypes.data, sizes.ctypes.data, apply, ptr, cap, None, rec.ctypes.data,
+                                                   rounds.ctypes.data))
         info = [_jpeg_info_dict(r) for r in rec[:n]]
         offsets = [int(r["offset"]) if d["status"] == "ok" else None for r, d in zip(rec[:n], info)]
         return JpegBatch(info, offsets, out, (int(rounds[0]), int(rounds[1])))
@@ -2306,7 +2261,7 @@ def _overview_kind(dtype, shape):
     raise ValueError("an overview raster is (rows, width, 4) uint8 or (rows, width) float32")
 
 
-class OrthoOverviews:
+class OrthoOverviews(_Handle):
     """The averaged overview levels of a raster fed band by band (och_ortho_overviews_*; the rule: DESIGN.md §4.13).
     kind: OVERVIEW_RGBA8 ((rows, width, 4) uint8 bands, alpha last) or OVERVIEW_FLOAT32 ((rows, width) float32, NaN: no
     data).  ctx None: the CPU route, numpy bands and levels.  ctx with on_device: CUDA tensors, fed on the context's stream
@@ -2315,6 +2270,8 @@ class OrthoOverviews:
     arrays, made here when None.  feed(row0, band): bands ascend and are contiguous from row 0, of any row count;
     complete_rows(level) is monotone.  A gap, an overlap, a feed after finish and a finish before the last row raise
     OchipError naming the rows."""
+
+    _destroy, _last_error = "och_ortho_overviews_destroy", "och_ortho_overviews_last_error"
 
     def __init__(self, kind, width, height, ctx=None, on_device=False, levels=None):
         self.L, self.kind, self.width, self.height, self.ctx = load(), int(kind), int(width), int(height), ctx
@@ -2344,30 +2301,13 @@ class OrthoOverviews:
         self.levels = list(levels)
         arr = (C.c_void_p * max(1, len(ptrs)))(*ptrs)
         h = C.c_void_p()
-        if self.L.och_ortho_overviews_create(ctx.h if ctx is not None else None, self.kind, self.width, self.height, arr,
-                                             int(self.on_device), C.byref(h)) != 0:
-            raise capi.OchipError(self._error())
+        self._check(self.L.och_ortho_overviews_create(ctx.h if ctx is not None else None, self.kind, self.width, self.height, arr,
+                                                      int(self.on_device), C.byref(h)))
         self.h = h
         self._keep = None
 
-    def _error(self):
-        return self.L.och_ortho_overviews_last_error().decode()
-
-    def close(self):
-        if getattr(self, "h", None):
-            if self.ctx is None or getattr(self.ctx, "h", None):  # as OrthoStream.close: the context may be gone
-                self.L.och_ortho_overviews_destroy(self.h)
-            self.h = None
-            self._keep = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        self.close()
+    def _released(self):
+        self._keep = None  # one band, not a list: the last fed
 
     def feed(self, row0, band):
         kind, rows, w = _overview_kind(band.dtype, tuple(band.shape))
@@ -2379,16 +2319,14 @@ class OrthoOverviews:
         else:
             band = np.ascontiguousarray(band)
             ptr = band.ctypes.data
-        if self.L.och_ortho_overviews_feed(self.h, int(row0), rows, ptr) != 0:
-            raise capi.OchipError(self._error())
+        self._check(self.L.och_ortho_overviews_feed(self.h, int(row0), rows, ptr))
         self._keep = band  # the kernels may still read it: alive until the next feed, finish or close
 
     def complete_rows(self, level):
         return int(self.L.och_ortho_overviews_complete_rows(self.h, int(level)))
 
     def finish(self):
-        if self.L.och_ortho_overviews_finish(self.h) != 0:
-            raise capi.OchipError(self._error())
+        self._check(self.L.och_ortho_overviews_finish(self.h))
         self._keep = None
         return self.levels
 
@@ -2427,53 +2365,37 @@ def deflate_code_lengths(counts, limit):
     return lens[:len(counts)]
 
 
-class _TileEncoder:
+class _TileEncoder(_Handle):
     """och_geotiff_*: a raster's bands, or predicted payloads, to the zlib streams of its 512 x 512 tiles"""
+
+    _destroy, _last_error = "och_geotiff_destroy", "och_geotiff_last_error"
 
     def __init__(self, kind, width, height, ctx, sparse):
         self.L, self.ctx, self.h = load(), ctx, None
         h = C.c_void_p()
-        if self.L.och_geotiff_create(ctx.h if ctx is not None else None, int(kind), int(width), int(height), int(bool(sparse)),
-                                     C.byref(h)) != 0:
-            raise capi.OchipError(self.error())
+        self._check(self.L.och_geotiff_create(ctx.h if ctx is not None else None, int(kind), int(width), int(height), int(bool(sparse)),
+                                              C.byref(h)))
         self.h = h
 
-    def error(self):
-        return self.L.och_geotiff_last_error().decode()
-
-    def close(self):
-        if getattr(self, "h", None):
-            if self.ctx is None or getattr(self.ctx, "h", None):  # as OrthoStream.close: the context may be gone
-                self.L.och_geotiff_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        self.close()
-
     def feed(self, row0, rows, ptr, on_device):
-        if self.L.och_geotiff_feed(self.h, int(row0), int(rows), ptr, int(on_device)) != 0:
-            raise capi.OchipError(self.error())
+        self._check(self.L.och_geotiff_feed(self.h, int(row0), int(rows), ptr, int(on_device)))
 
     def payloads(self, arr):
-        if self.L.och_geotiff_payloads(self.h, arr.ctypes.data, len(arr)) != 0:
-            raise capi.OchipError(self.error())
+        self._check(self.L.och_geotiff_payloads(self.h, arr.ctypes.data, len(arr)))
 
     def finish(self):
-        if self.L.och_geotiff_finish(self.h) != 0:
-            raise capi.OchipError(self.error())
+        self._check(self.L.och_geotiff_finish(self.h))
 
     def collect(self):
         """(bytes as a uint8 array, counts): the streams of the tiles complete so far, back to back in tile order.  The bytes
         lie in a block this object reuses - a fresh one of a band's size costs more in page faults than the copy into it - so
         they are valid until the next collect."""
         nb, nt = C.c_uint64(0), C.c_uint64(0)
-        if self.L.och_geotiff_collect(self.h, None, 0, C.byref(nb), None, 0, C.byref(nt)) != 0:
-            raise capi.OchipError(self.error())
+        self._check(self.L.och_geotiff_collect(self.h, None, 0, C.byref(nb), None, 0, C.byref(nt)))
         if getattr(self, "_buf", None) is None or len(self._buf) < nb.value:
             self._buf = np.empty(max(nb.value + nb.value // 4, 1), np.uint8)
         buf, counts = self._buf, np.zeros(max(nt.value, 1), np.uint64)
-        if self.L.och_geotiff_collect(self.h, buf.ctypes.data, nb.value, C.byref(nb), counts.ctypes.data, nt.value, C.byref(nt)) != 0:
-            raise capi.OchipError(self.error())
+        self._check(self.L.och_geotiff_collect(self.h, buf.ctypes.data, nb.value, C.byref(nb), counts.ctypes.data, nt.value, C.byref(nt)))
         return buf[:nb.value], counts[:nt.value]
 
 
@@ -2727,28 +2649,21 @@ class GeoTiffError(ValueError):
         self.status = status
 
 
-class _TileReader:
+class _TileReader(_Handle):
     """och_geotiff_reader_*: zlib streams to payloads, and a layout's tile streams to a raster"""
+
+    _destroy, _last_error = "och_geotiff_reader_destroy", "och_geotiff_read_last_error"
+
+    @staticmethod
+    def _failure(text):
+        return GeoTiffError("refused", text)
 
     def __init__(self, samples, is_float, width, height, tile_w, tile_h, predictor, ctx, budget=0):
         self.L, self.ctx, self.h = load(), ctx, None
         h = C.c_void_p()
-        if self.L.och_geotiff_reader_create(ctx.h if ctx is not None else None, int(samples), int(bool(is_float)), int(width), int(height),
-                                            int(tile_w), int(tile_h), int(predictor), int(budget), C.byref(h)) != 0:
-            raise GeoTiffError("refused", self.error())
+        self._check(self.L.och_geotiff_reader_create(ctx.h if ctx is not None else None, int(samples), int(bool(is_float)), int(width),
+                                                     int(height), int(tile_w), int(tile_h), int(predictor), int(budget), C.byref(h)))
         self.h = h
-
-    def error(self):
-        return self.L.och_geotiff_read_last_error().decode()
-
-    def close(self):
-        if getattr(self, "h", None):
-            if self.ctx is None or getattr(self.ctx, "h", None):  # as OrthoStream.close: the context may be gone
-                self.L.och_geotiff_reader_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        self.close()
 
     def launches(self):
         return int(self.L.och_geotiff_reader_launches(self.h))
@@ -2760,16 +2675,14 @@ class _TileReader:
         np.cumsum((expect + np.uint64(15)) & ~np.uint64(15), out=slots[1:])
         out = np.empty(max(int(slots[-1]), 1), np.uint8)
         status, produced = np.zeros(max(n, 1), np.int32), np.zeros(max(n, 1), np.uint64)
-        if self.L.och_geotiff_reader_inflate(self.h, n, packed.ctypes.data, offsets.ctypes.data, expect.ctypes.data, out.ctypes.data,
-                                             int(slots[-1]), status.ctypes.data, produced.ctypes.data) != 0:
-            raise GeoTiffError("refused", self.error())
+        self._check(self.L.och_geotiff_reader_inflate(self.h, n, packed.ctypes.data, offsets.ctypes.data, expect.ctypes.data,
+                                                      out.ctypes.data, int(slots[-1]), status.ctypes.data, produced.ctypes.data))
         return out, slots, status[:n], produced[:n]
 
     def read(self, packed, offsets, row0, rows, ptr, on_device):
         bad = C.c_int64(-1)
-        if self.L.och_geotiff_reader_read(self.h, len(offsets) - 1, packed.ctypes.data, offsets.ctypes.data, int(row0), int(rows), ptr,
-                                          int(bool(on_device)), C.byref(bad)) != 0:
-            raise GeoTiffError("refused", self.error())
+        self._check(self.L.och_geotiff_reader_read(self.h, len(offsets) - 1, packed.ctypes.data, offsets.ctypes.data, int(row0), int(rows),
+                                                   ptr, int(bool(on_device)), C.byref(bad)))
         return int(bad.value)
 
 
@@ -3165,37 +3078,20 @@ def _png_image(raster, bgr, device):
     return capi.PngImage(ptr, shape[1], shape[0], shape[2], int(bool(bgr))), keep, on_device
 
 
-class PngEncoder:
+class PngEncoder(_Handle):
     """PNG files of batches of images (och_png_encoder_*; the rules: DESIGN.md §4.20).  ctx None: the CPU route; ctx: the
     device route, numpy arrays through the device or CUDA tensors on ctx's device (torch's work on them finished).  Both
     give the same bytes.  encode(images, bgr=False, base64=False): a list of uint8 (h, w), (h, w, 3) or (h, w, 4) images of
     any sizes, at most 65 535 - all numpy or all CUDA - to a list of bytes, or of str with base64; bgr: the arrays are
     B G R (A), the files R G B (A)."""
 
+    _destroy, _last_error = "och_png_encoder_destroy", "och_png_last_error"
+
     def __init__(self, ctx=None):
         self.L, self.ctx, self.h = load(), ctx, None
         h = C.c_void_p()
-        if self.L.och_png_encoder_create(ctx.h if ctx is not None else None, C.byref(h)) != 0:
-            raise capi.OchipError(self._error())
+        self._check(self.L.och_png_encoder_create(ctx.h if ctx is not None else None, C.byref(h)))
         self.h = h
-
-    def _error(self):
-        return self.L.och_png_last_error().decode()
-
-    def close(self):
-        if getattr(self, "h", None):
-            if self.ctx is None or getattr(self.ctx, "h", None):
-                self.L.och_png_encoder_destroy(self.h)
-            self.h = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        self.close()
 
     def encode(self, images, bgr=False, base64=False, cap=None):
         images = list(images)
@@ -3221,9 +3117,8 @@ class PngEncoder:
             need += bound
         out = np.empty(max(need if cap is None else int(cap), 1), np.uint8)
         offsets = np.zeros(len(recs) + 1, np.uint64)
-        if self.L.och_png_encoder_encode(self.h, len(recs), arr, int(on_device), int(bool(base64)), out.ctypes.data,
-                                         out.size if cap is None else int(cap), offsets.ctypes.data) != 0:
-            raise capi.OchipError(self._error())
+        self._check(self.L.och_png_encoder_encode(self.h, len(recs), arr, int(on_device), int(bool(base64)), out.ctypes.data,
+                                                  out.size if cap is None else int(cap), offsets.ctypes.data))
         files = [out[int(offsets[i]):int(offsets[i + 1])].tobytes() for i in range(len(recs))]
         return [f.decode("ascii") for f in files] if base64 else files
 

@@ -242,7 +242,7 @@ def scenario_refusals(ctx):
                                                                         bad.ctypes.data_as(host.C.POINTER(host.C.c_int64))),
     }
     for text, call in calls.items():
-        assert call() == -1 and text in rd.error(), (text, rd.error())
+        assert call() == -1 and text in rd._error(), (text, rd._error())
     assert rd.launches() == 0
     dead = rd.h
     rd.close()

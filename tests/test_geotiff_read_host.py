@@ -85,9 +85,9 @@ def test_inflate_argument_refusals():
     rd = host._TileReader(1, False, 16, 16, 16, 16, 1, None)
     one = np.zeros(8, np.uint64)
     assert L.och_geotiff_reader_inflate(rd.h, 65536, None, None, None, None, 0, None, None) == -1
-    assert "65535 streams" in rd.error()
+    assert "65535 streams" in rd._error()
     assert L.och_geotiff_reader_inflate(rd.h, 1, one.ctypes.data, None, None, None, 0, None, None) == -1
-    assert "offsets are NULL" in rd.error()
+    assert "offsets are NULL" in rd._error()
     dead = rd.h
     rd.close()
     assert L.och_geotiff_reader_inflate(dead, 0, None, None, None, None, 0, None, None) == -1
