@@ -357,7 +357,8 @@ inline uint64_t cell_key(int i, int j) // gridCellKey, grid_filter.hpp:11-14
 class GroundMeshProblem
 {
   public:
-    GroundMeshProblem(ochip_ctx *ctx, const MeasurementGraph &graph) : _ctx(ctx), _graph(graph)
+    GroundMeshProblem(ochip_ctx *ctx, const MeasurementGraph &graph, std::vector<NodePose> &poses)
+        : _ctx(ctx), _graph(graph), _poses(poses), _cams(graph, poses)
     {
     }
     ~GroundMeshProblem()
@@ -367,9 +368,8 @@ class GroundMeshProblem
     }
 
     // setupGroundMeshProblem (relax_problem.cpp:83-120)
-    bool setup(std::vector<NodePose> &poses, std::vector<std::pair<size_t, CameraModel>> &cam_models,
-               const std::vector<size_t> &edges_to_optimize, const RelaxConfig &config,
-               const std::vector<surface_model> &previous, RelaxMeshStats *stats, std::string *error,
+    bool setup(std::vector<std::pair<size_t, CameraModel>> &cam_models, const std::vector<size_t> &edges_to_optimize,
+               const RelaxConfig &config, const std::vector<surface_model> &previous, RelaxMeshStats *stats, std::string *error,
                const RelaxShard *shard = nullptr)
     {
         const bool verbose = ochip_verbose("relax");
@@ -379,19 +379,9 @@ class GroundMeshProblem
                 fprintf(stderr, "[relax mesh setup] %-28s %.3f ms\n", what, since(tmark) * 1e3);
             tmark = clk::now();
         };
-        _poses = &poses;
         _cam_models = &cam_models;
         _options = config.options;
         _intrinsics = (config.options & (OPT_FOCAL_LENGTH | OPT_PRINCIPAL_POINT | OPT_LENS_DISTORTIONS_RADIAL)) != 0;
-        for (size_t i = 0; i < poses.size(); i++)
-            if (_opt_index.emplace(poses[i].node_id, i).second) // the first pose of a node is the one optimised
-            {
-                _cam_of_node.emplace(poses[i].node_id, (uint32_t)_cam_opt.size());
-                _pose_cam.push_back((uint32_t)_cam_opt.size());
-                push_camera(poses[i].position, poses[i].orientation, true);
-            }
-            else
-                _pose_cam.push_back(UINT32_MAX);
         initialize_mesh(previous, (config.options & OPT_MINIMAL_MESH) != 0);
         const double frac = config.ground_mesh_grid_fraction;
 
@@ -404,8 +394,8 @@ class GroundMeshProblem
             if (e == nullptr)
                 continue;
             edges.push_back(e);
-            src.push_back(lookup(e->source));
-            dst.push_back(lookup(e->dest));
+            src.push_back(_cams.lookup(e->source));
+            dst.push_back(_cams.lookup(e->dest));
         }
         lap("mesh + pose lookup");
         build_tracks(edges, src, dst, frac);
@@ -428,13 +418,14 @@ class GroundMeshProblem
         {
             const double no_triangle[6] = {0, 0, 1, 0, 0, 1}; // (only the plane flavour's block list uses it)
             device_filter df;
-            if (!df.run(_ctx, _graph, edges, src, dst, n_filter, _cam_pos, _cam_q, no_triangle, frac, error))
+            if (!df.run(_ctx, _graph, edges, src, dst, n_filter, _cams, no_triangle, frac, error))
                 return false;
-            for (size_t j = 0, k = 0; j < df.pe.size(); j++, k++)
+            const std::vector<ochip_plane_edge> &pe = df.pk.pe;
+            for (size_t j = 0, k = 0; j < pe.size(); j++, k++)
             {
-                while (edges[k] != df.edge[j]) // (run skips nothing here: every entry of `edges` is an edge)
+                while (edges[k] != df.pk.edge[j]) // (run skips nothing here: every entry of `edges` is an edge)
                     k++;
-                keep[k].assign(df.keep.begin() + df.pe[j].inlier_offset, df.keep.begin() + df.pe[j].inlier_offset + df.pe[j].n_inliers);
+                keep[k].assign(df.keep.begin() + pe[j].inlier_offset, df.keep.begin() + pe[j].inlier_offset + pe[j].n_inliers);
             }
             if (relax_setup_check_on())
             {
@@ -504,10 +495,10 @@ class GroundMeshProblem
             vz[v] = _mesh.nodes[v].location[2];
         }
         ochip_relaxg_desc d{};
-        d.n_cams = (uint32_t)_cam_opt.size();
-        d.cam_pos = _cam_pos.data();
-        d.cam_q = _cam_q.data();
-        d.cam_optimize = _cam_opt.data();
+        d.n_cams = (uint32_t)_cams.size();
+        d.cam_pos = _cams.pos.data();
+        d.cam_q = _cams.q.data();
+        d.cam_optimize = _cams.optimize.data();
         d.n_verts = (uint32_t)_mesh.size_nodes();
         d.vert_xy = vxy.data();
         d.vert_z = vz.data();
@@ -524,24 +515,10 @@ class GroundMeshProblem
         {
             // the one inverse lens model the FocalRadial blocks share (:483-507, :799-853)
             const InverseCameraModel &m = twin_of(_shared_model)->m;
-            d.model[0] = m.focal_length_pixels;
-            d.model[1] = m.principle_point[0], d.model[2] = m.principle_point[1];
-            for (int i = 0; i < 3; i++)
-                d.model[3 + i] = m.radial_distortion[i];
-            d.model[6] = m.tangential_distortion[0], d.model[7] = m.tangential_distortion[1];
+            pack_model8(m, d.model);
             d.opt_focal = (_options & OPT_FOCAL_LENGTH) != 0;
             d.opt_principal = (_options & OPT_PRINCIPAL_POINT) != 0;
-            // SubsetManifold of the radial block (:533-556): Brown k1 / k1 k2 / k1 k2 k3; with no parameterisation chosen -
-            // also when LENS_DISTORTIONS_RADIAL is not among the options at all - the block stays a free Euclidean one
-            const bool radial = (_options & OPT_LENS_DISTORTIONS_RADIAL) != 0;
-            d.n_radial_free = 3;
-            if (radial && !(_options & OPT_LENS_DISTORTIONS_RADIAL_BROWN246_PARAMETERIZATION))
-            {
-                if (_options & OPT_LENS_DISTORTIONS_RADIAL_BROWN24_PARAMETERIZATION)
-                    d.n_radial_free = 2;
-                else if (_options & OPT_LENS_DISTORTIONS_RADIAL_BROWN2_PARAMETERIZATION)
-                    d.n_radial_free = 1;
-            }
+            d.n_radial_free = radial_free_count(_options);
             d.mono_observations = (uint32_t)_mono_count; // addMonotonicityCosts (:1381-1388)
             const double hc = m.pixels_cols / 2.0, hr = m.pixels_rows / 2.0;
             d.mono_r_max = std::sqrt(hc * hc + hr * hr) / _mono_focal;
@@ -579,17 +556,9 @@ class GroundMeshProblem
             d.shard_world = shard->world;
         }
         if (ochip_relaxg_problem_create(_ctx, &d, &_dev) != OCHIP_OK)
-        {
-            if (error)
-                *error = std::string("ochip_relaxg_problem_create: ") + ochip_last_error(_ctx);
-            return false;
-        }
+            return device_fail(_ctx, error, "ochip_relaxg_problem_create");
         if (sharded && ochip_relaxg_set_exchange(_dev, shard->exchange, shard->user) != OCHIP_OK)
-        {
-            if (error)
-                *error = std::string("ochip_relaxg_set_exchange: ") + ochip_last_error(_ctx);
-            return false;
-        }
+            return device_fail(_ctx, error, "ochip_relaxg_set_exchange");
         lap("ochip_relaxg_problem_create");
         return true;
     }
@@ -598,10 +567,10 @@ class GroundMeshProblem
     bool relax_observed_model_only(RelaxTimers *t, RelaxMeshStats *stats, std::string *error)
     {
         if (ochip_relaxg_set_structure_only(_dev, 1) != OCHIP_OK)
-            return fail(error, "ochip_relaxg_set_structure_only");
+            return device_fail(_ctx, error, "ochip_relaxg_set_structure_only");
         const bool ok = solve(t, stats, error);
         if (ochip_relaxg_set_structure_only(_dev, 0) != OCHIP_OK)
-            return fail(error, "ochip_relaxg_set_structure_only");
+            return device_fail(_ctx, error, "ochip_relaxg_set_structure_only");
         return ok;
     }
 
@@ -610,22 +579,14 @@ class GroundMeshProblem
         ochip_relax_options o{100, 1.0, 1e-6, 1e-10, 1e-8}; // relax_problem.cpp:30-37 + Ceres defaults
         ochip_relax_summary s{};
         if (ochip_relaxg_solve(_dev, &o, &s) != OCHIP_OK)
-            return fail(error, "ochip_relaxg_solve");
-        if (t)
-        {
-            t->solves++;
-            t->iterations_total += s.iterations;
-            t->last_iterations = s.iterations;
-            t->last_initial_cost = s.initial_cost;
-            t->last_final_cost = s.final_cost;
-            t->last_residual_blocks = s.num_residual_blocks;
-        }
+            return device_fail(_ctx, error, "ochip_relaxg_solve");
+        note_solve(t, s);
         if (stats)
             stats->unknowns = s.num_parameters;
-        std::vector<double> q(_cam_opt.size() * 4), z(_mesh.size_nodes());
+        std::vector<double> q(_cams.size() * 4), z(_mesh.size_nodes());
         double model[8];
         if (ochip_relaxg_get_state(_dev, q.data(), z.data(), model) != OCHIP_OK)
-            return fail(error, "ochip_relaxg_get_state");
+            return device_fail(_ctx, error, "ochip_relaxg_get_state");
         if (_shared_model != (size_t)-1)
         {
             InverseCameraModel &m = twin_of(_shared_model)->m;
@@ -639,16 +600,7 @@ class GroundMeshProblem
             for (auto &cm : *_cam_models)
                 if (cm.first == t.id)
                     cm.second = convertModel(t.m, t.id);
-        for (size_t i = 0; i < _poses->size(); i++) // p.second->orientation.normalize(), :1410-1413
-        {
-            if (_pose_cam[i] == UINT32_MAX)
-                continue;
-            double *o4 = (*_poses)[i].orientation;
-            const double *s4 = &q[4 * (size_t)_pose_cam[i]];
-            const double n = std::sqrt(s4[0] * s4[0] + s4[1] * s4[1] + s4[2] * s4[2] + s4[3] * s4[3]);
-            for (int k = 0; k < 4; k++)
-                o4[k] = s4[k] / n;
-        }
+        _cams.store_orientations(q.data()); // p.second->orientation.normalize(), :1410-1413
         for (size_t v = 0; v < z.size(); v++)
             _mesh.nodes[v].location[2] = z[v];
         return true;
@@ -731,46 +683,6 @@ class GroundMeshProblem
         size_t views = 0;
     };
 
-    bool fail(std::string *error, const char *what)
-    {
-        if (error)
-            *error = std::string(what) + ": " + ochip_last_error(_ctx);
-        return false;
-    }
-    void push_camera(const double *pos, const double *q, bool optimize)
-    {
-        _cam_pos.insert(_cam_pos.end(), pos, pos + 3);
-        _cam_q.insert(_cam_q.end(), q, q + 4);
-        _cam_opt.push_back(optimize ? 1 : 0);
-    }
-    pose_ref lookup(size_t node_id)
-    {
-        pose_ref po;
-        auto it = _opt_index.find(node_id);
-        if (it != _opt_index.end())
-        {
-            NodePose &np = (*_poses)[it->second];
-            po.optimize = true;
-            po.loc = np.position;
-            po.rot = np.orientation;
-            po.cam = _cam_of_node.at(node_id);
-            return po;
-        }
-        const MeasurementGraph::Node *node = _graph.getNode(node_id);
-        if (node != nullptr && finite4(node->payload.orientation) && finite3(node->payload.position))
-        {
-            po.loc = node->payload.position;
-            po.rot = node->payload.orientation;
-            auto c = _cam_of_node.find(node_id);
-            if (c == _cam_of_node.end())
-            {
-                c = _cam_of_node.emplace(node_id, (uint32_t)_cam_opt.size()).first;
-                push_camera(po.loc, po.rot, false);
-            }
-            po.cam = c->second;
-        }
-        return po;
-    }
     const CameraModel &model_of(size_t node_id) const // the group's copy of the node's model if there is one (:207-229)
     {
         const CameraModel &m = *_graph.getNode(node_id)->payload.model;
@@ -783,9 +695,9 @@ class GroundMeshProblem
     void initialize_mesh(const std::vector<surface_model> &previous, bool minimal) // initializeGroundMesh (:1244-1288)
     {
         point_cloud cams;
-        for (size_t i = 0; i < _poses->size(); i++)
-            if (_pose_cam[i] != UINT32_MAX)
-                cams.push_back({(*_poses)[i].position[0], (*_poses)[i].position[1], (*_poses)[i].position[2]});
+        for (size_t i = 0; i < _poses.size(); i++)
+            if (_cams.pose_cam[i] != UINT32_MAX)
+                cams.push_back({_poses[i].position[0], _poses[i].position[1], _poses[i].position[2]});
         const MeshGraph *prev = nullptr;
         for (const surface_model &s : previous)
             if (s.mesh.size_nodes() > 0)
@@ -949,9 +861,10 @@ class GroundMeshProblem
         std::vector<uint64_t> ray_cell(off.back()); // the grid cell of every ray's pixel in its image
         std::vector<uint32_t> n_rays(n_tracks, 0), n_imgs(n_tracks, 0);
         std::vector<cloud_track> cloud(n_tracks);
-        std::vector<int64_t> pose_of_node(n_nodes, -1); // index into *_poses of the pose that is optimised, per node index
-        for (const auto &kv : _opt_index)
-            pose_of_node[_graph.nodeIndex(kv.first)] = (int64_t)kv.second;
+        std::vector<int64_t> pose_of_node(n_nodes, -1); // index into _poses of the pose that is optimised, per node index
+        for (size_t i = 0; i < _poses.size(); i++)
+            if (_cams.pose_cam[i] != UINT32_MAX)
+                pose_of_node[_graph.nodeIndex(_poses[i].node_id)] = (int64_t)i;
         const auto &gnodes = _graph.nodes();
         // members grouped by track (ascending inside a track), then the tracks in parallel
         std::vector<uint32_t> moff(n_tracks + 1, 0), mlist(M);
@@ -1088,8 +1001,8 @@ class GroundMeshProblem
                 ray_info r;
                 r.v = rays[off[t] + k];
                 const MeasurementGraph::Node &node = gnodes[r.v.node];
-                const NodePose &np = (*_poses)[(size_t)pose_of_node[r.v.node]];
-                r.cam = _cam_of_node.at(node.id);
+                const NodePose &np = _poses[(size_t)pose_of_node[r.v.node]];
+                r.cam = _cams.pose_cam[(size_t)pose_of_node[r.v.node]];
                 r.loc = v3{np.position[0], np.position[1], np.position[2]};
                 double ray[3];
                 image_to_3d(node.payload.features[r.v.feature].location, *node.payload.model, ray);
@@ -1243,12 +1156,10 @@ class GroundMeshProblem
 
     ochip_ctx *_ctx;
     const MeasurementGraph &_graph;
-    std::vector<NodePose> *_poses = nullptr;
+    std::vector<NodePose> &_poses;
+    camera_table _cams;
     std::vector<std::pair<size_t, CameraModel>> *_cam_models = nullptr;
-    std::unordered_map<size_t, size_t> _opt_index;
-    std::unordered_map<size_t, uint32_t> _cam_of_node;
-    std::vector<uint32_t> _pose_cam; // per pose: its camera, or UINT32_MAX for a repeated node
-    std::vector<double> _cam_pos, _cam_q, _ray_dir, _ray_px;
+    std::vector<double> _ray_dir, _ray_px;
     std::vector<uint8_t> _blk_intr;
     std::vector<twin> _twins;
     uint32_t _options = 0;
@@ -1256,7 +1167,7 @@ class GroundMeshProblem
     std::atomic<bool> _views_without_features{false};
     size_t _shared_model = (size_t)-1, _mono_count = 0;
     double _mono_focal = 1;
-    std::vector<uint8_t> _cam_opt, _blk_n;
+    std::vector<uint8_t> _blk_n;
     std::vector<uint32_t> _blk_ray_off{0}, _ray_cam, _blk_tri;
     std::vector<std::unordered_map<uint64_t, char>> _track_measurement, _covered; // per node index: features / cells in track blocks
     std::vector<cloud_track> _tracks_for_cloud;
@@ -1274,8 +1185,8 @@ bool relax(ochip_ctx *ctx, const MeasurementGraph &graph, std::vector<NodePose> 
     if (config.options & OPT_GROUND_MESH) // runGroundMesh (relax.cpp:89-102)
     {
         auto t0 = clk::now();
-        GroundMeshProblem rp(ctx, graph);
-        if (!rp.setup(nodes, cam_models, edges_to_optimize, config, previous, stats, error, shard))
+        GroundMeshProblem rp(ctx, graph, nodes);
+        if (!rp.setup(cam_models, edges_to_optimize, config, previous, stats, error, shard))
             return false;
         if (timers)
             timers->setup_host += since(t0);

@@ -152,7 +152,8 @@ void ray_intersection_refined(const CameraModel &m1, const CameraModel &m2, cons
 class PointsProblem
 {
   public:
-    PointsProblem(ochip_ctx *ctx, const MeasurementGraph &graph) : _ctx(ctx), _graph(graph)
+    PointsProblem(ochip_ctx *ctx, const MeasurementGraph &graph, std::vector<NodePose> &poses)
+        : _ctx(ctx), _graph(graph), _cams(graph, poses)
     {
     }
     ~PointsProblem()
@@ -162,20 +163,11 @@ class PointsProblem
     }
 
     // setup3dPointProblem (relax_problem.cpp:122-145)
-    bool setup(std::vector<NodePose> &poses, std::vector<std::pair<size_t, CameraModel>> &cam_models,
-               const std::vector<size_t> &edges_to_optimize, uint32_t options, std::string *error)
+    bool setup(std::vector<std::pair<size_t, CameraModel>> &cam_models, const std::vector<size_t> &edges_to_optimize,
+               uint32_t options, std::string *error)
     {
-        _poses = &poses;
         _cam_models = &cam_models;
         _options = options;
-        _pose_cam.assign(poses.size(), UINT32_MAX);
-        for (size_t i = 0; i < poses.size(); i++)
-            if (_opt_index.emplace(poses[i].node_id, i).second)
-            {
-                _pose_cam[i] = (uint32_t)_cam_opt.size();
-                _cam_of_node.emplace(poses[i].node_id, _pose_cam[i]);
-                push_camera(poses[i].position, poses[i].orientation, true);
-            }
         // which functor (:1038-1086)
         auto has_any = [&](uint32_t o) { return (options & o) != 0; };
         auto has_all = [&](uint32_t o) { return (options & o) == o; };
@@ -198,8 +190,8 @@ class PointsProblem
             const MeasurementGraph::Edge *e = _graph.getEdge(edges_to_optimize[k]);
             if (e == nullptr)
                 continue;
-            src[k] = lookup(e->source);
-            dst[k] = lookup(e->dest);
+            src[k] = _cams.lookup(e->source);
+            dst[k] = _cams.lookup(e->dest);
             if ((src[k].loc == nullptr || dst[k].loc == nullptr) && n_filter == ne)
                 n_filter = k;
         }
@@ -225,10 +217,10 @@ class PointsProblem
                 used.emplace(edges_to_optimize[k], 1);
         }
         ochip_relaxp_desc d{};
-        d.n_cams = (uint32_t)_cam_opt.size();
-        d.cam_pos = _cam_pos.data();
-        d.cam_q = _cam_q.data();
-        d.cam_optimize = _cam_opt.data();
+        d.n_cams = (uint32_t)_cams.size();
+        d.cam_pos = _cams.pos.data();
+        d.cam_q = _cams.q.data();
+        d.cam_optimize = _cams.optimize.data();
         d.n_points = (uint32_t)(_points.size() / 3);
         d.point_xyz = _points.data();
         d.n_groups = (uint32_t)(_grp_first.size() - 1);
@@ -236,47 +228,30 @@ class PointsProblem
         d.grp_cam = _grp_cam.data();
         d.obs_px = _obs_px.data();
         d.functor = std::max(_functor, 0);
-        const CameraModel *m = _shared_model ? _shared_model : nullptr;
-        if (m)
-        {
-            d.model[0] = m->focal_length_pixels;
-            d.model[1] = m->principle_point[0], d.model[2] = m->principle_point[1];
-            for (int i = 0; i < 3; i++)
-                d.model[3 + i] = m->radial_distortion[i];
-            d.model[6] = m->tangential_distortion[0], d.model[7] = m->tangential_distortion[1];
-        }
+        if (_shared_model)
+            pack_model8(*_shared_model, d.model);
         else
             d.model[0] = 1.0;
         d.opt_focal = has_any(OPT_FOCAL_LENGTH);
         d.opt_principal = has_any(OPT_PRINCIPAL_POINT);
-        d.n_radial_free = 3; // BROWN246 or no parameterisation chosen: a free block (:1160-1180)
-        if (has_all(OPT_LENS_DISTORTIONS_RADIAL) && !has_all(OPT_LENS_DISTORTIONS_RADIAL_BROWN246_PARAMETERIZATION))
-        {
-            if (has_all(OPT_LENS_DISTORTIONS_RADIAL_BROWN24_PARAMETERIZATION))
-                d.n_radial_free = 2;
-            else if (has_all(OPT_LENS_DISTORTIONS_RADIAL_BROWN2_PARAMETERIZATION))
-                d.n_radial_free = 1;
-        }
+        d.n_radial_free = radial_free_count(options);
         d.focal_lo = 100.0;
         d.focal_hi = 20000.0;
         d.huber_a = 10.0; // HuberLoss(10), :128
         d.mono_observations = (uint32_t)_mono_count;
         d.mono_r_max = _mono_r_max;
         if (ochip_relaxp_problem_create(_ctx, &d, &_dev) != OCHIP_OK)
-        {
-            *error = std::string("ochip_relaxp_problem_create: ") + ochip_last_error(_ctx);
-            return false;
-        }
+            return device_fail(_ctx, error, "ochip_relaxp_problem_create");
         return true;
     }
 
     bool relax_observed_model_only(RelaxTimers *t, std::string *error)
     {
         if (ochip_relaxp_set_structure_only(_dev, 1) != OCHIP_OK)
-            return fail(error, "ochip_relaxp_set_structure_only");
+            return device_fail(_ctx, error, "ochip_relaxp_set_structure_only");
         const bool ok = solve(t, error);
         if (ochip_relaxp_set_structure_only(_dev, 0) != OCHIP_OK)
-            return fail(error, "ochip_relaxp_set_structure_only");
+            return device_fail(_ctx, error, "ochip_relaxp_set_structure_only");
         return ok;
     }
 
@@ -287,30 +262,13 @@ class PointsProblem
         ochip_relax_options o{1000, 1.0, 1e-6, 1e-10, 1e-8}; // max_num_iterations = 1000 (:143)
         ochip_relax_summary s{};
         if (ochip_relaxp_solve(_dev, &o, &s) != OCHIP_OK)
-            return fail(error, "ochip_relaxp_solve");
-        if (t)
-        {
-            t->solves++;
-            t->iterations_total += s.iterations;
-            t->last_iterations = s.iterations;
-            t->last_initial_cost = s.initial_cost;
-            t->last_final_cost = s.final_cost;
-            t->last_residual_blocks = s.num_residual_blocks;
-        }
-        std::vector<double> q(_cam_opt.size() * 4);
+            return device_fail(_ctx, error, "ochip_relaxp_solve");
+        note_solve(t, s);
+        std::vector<double> q(_cams.size() * 4);
         double model[8];
         if (ochip_relaxp_get_state(_dev, q.data(), _points.data(), model) != OCHIP_OK)
-            return fail(error, "ochip_relaxp_get_state");
-        for (size_t i = 0; i < _poses->size(); i++) // orientation.normalize(), :1410-1413
-        {
-            if (_pose_cam[i] == UINT32_MAX)
-                continue;
-            double *o4 = (*_poses)[i].orientation;
-            const double *s4 = &q[4 * (size_t)_pose_cam[i]];
-            const double n = std::sqrt(s4[0] * s4[0] + s4[1] * s4[1] + s4[2] * s4[2] + s4[3] * s4[3]);
-            for (int k = 0; k < 4; k++)
-                o4[k] = s4[k] / n;
-        }
+            return device_fail(_ctx, error, "ochip_relaxp_get_state");
+        _cams.store_orientations(q.data()); // orientation.normalize(), :1410-1413
         if (_shared_model && _functor >= 1)
         {
             _shared_model->focal_length_pixels = model[0];
@@ -337,45 +295,6 @@ class PointsProblem
     }
 
   private:
-    bool fail(std::string *error, const char *what)
-    {
-        *error = std::string(what) + ": " + ochip_last_error(_ctx);
-        return false;
-    }
-    void push_camera(const double *pos, const double *q, bool optimize)
-    {
-        _cam_pos.insert(_cam_pos.end(), pos, pos + 3);
-        _cam_q.insert(_cam_q.end(), q, q + 4);
-        _cam_opt.push_back(optimize ? 1 : 0);
-    }
-    pose_ref lookup(size_t node_id) // nodeid2poseopt (:182-232)
-    {
-        pose_ref po;
-        auto it = _opt_index.find(node_id);
-        if (it != _opt_index.end())
-        {
-            NodePose &np = (*_poses)[it->second];
-            po.optimize = true;
-            po.loc = np.position;
-            po.rot = np.orientation;
-            po.cam = _pose_cam[it->second];
-            return po;
-        }
-        const MeasurementGraph::Node *node = _graph.getNode(node_id);
-        if (node != nullptr && finite4(node->payload.orientation) && finite3(node->payload.position))
-        {
-            po.loc = node->payload.position;
-            po.rot = node->payload.orientation;
-            auto c = _cam_of_node.find(node_id);
-            if (c == _cam_of_node.end())
-            {
-                c = _cam_of_node.emplace(node_id, (uint32_t)_cam_opt.size()).first;
-                push_camera(po.loc, po.rot, false);
-            }
-            po.cam = c->second;
-        }
-        return po;
-    }
     CameraModel *model_of(size_t node_id) // the group's copy of the node's model when it holds one, else the node's own
     {
         const MeasurementGraph::Node *node = _graph.getNode(node_id);
@@ -400,7 +319,8 @@ class PointsProblem
             return true; // "No viable bundle options found"
         if (sm != dm || (_shared_model && _shared_model != sm))
         {
-            *error = "relax (3-D points): the device path optimises one shared camera model; this problem holds several";
+            if (error)
+                *error = "relax (3-D points): the device path optimises one shared camera model; this problem holds several";
             return false;
         }
         _shared_model = sm;
@@ -448,16 +368,13 @@ class PointsProblem
 
     ochip_ctx *_ctx;
     const MeasurementGraph &_graph;
-    std::vector<NodePose> *_poses = nullptr;
+    camera_table _cams;
     std::vector<std::pair<size_t, CameraModel>> *_cam_models = nullptr;
     uint32_t _options = 0;
     int _functor = 0;
     CameraModel *_shared_model = nullptr;
-    std::unordered_map<size_t, size_t> _opt_index;
-    std::unordered_map<size_t, uint32_t> _cam_of_node;
-    std::vector<double> _cam_pos, _cam_q, _points, _obs_px;
-    std::vector<uint8_t> _cam_opt;
-    std::vector<uint32_t> _pose_cam, _grp_first, _grp_cam;
+    std::vector<double> _points, _obs_px;
+    std::vector<uint32_t> _grp_first, _grp_cam;
     size_t _mono_count = 0;
     double _mono_r_max = 0;
     ochip_relaxp_problem *_dev = nullptr;
@@ -471,10 +388,10 @@ bool relax_points(ochip_ctx *ctx, const MeasurementGraph &graph, std::vector<Nod
                   std::vector<double> *points_before, std::vector<double> *points_after)
 {
     auto t0 = clk::now();
-    PointsProblem rp(ctx, graph);
+    PointsProblem rp(ctx, graph, nodes);
     std::vector<NodePose> backup = nodes;
     std::vector<std::pair<size_t, CameraModel>> models_backup = cam_models;
-    if (!rp.setup(nodes, cam_models, edges_to_optimize, options, error))
+    if (!rp.setup(cam_models, edges_to_optimize, options, error))
         return false;
     if (timers)
         timers->setup_host += since(t0);

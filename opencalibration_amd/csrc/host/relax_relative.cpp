@@ -18,51 +18,7 @@ bool solve_decomposition_problem(ochip_ctx *ctx, const MeasurementGraph &graph, 
                                  const std::vector<size_t> &edges_to_optimize, RelaxTimers *timers, std::string *error)
 {
     auto t0 = clk::now();
-    // camera table: optimised poses first (a node listed twice is optimised through its first pose), context cameras
-    // (finite graph orientation and position) appended on first use
-    std::vector<double> cam_pos, cam_q;
-    std::vector<uint8_t> cam_opt;
-    std::unordered_map<size_t, size_t> opt_index;
-    std::unordered_map<size_t, uint32_t> cam_of_node;
-    std::vector<uint32_t> pose_cam(poses.size(), UINT32_MAX);
-    auto push = [&](const double *pos, const double *q, bool optimize) {
-        cam_pos.insert(cam_pos.end(), pos, pos + 3);
-        cam_q.insert(cam_q.end(), q, q + 4);
-        cam_opt.push_back(optimize ? 1 : 0);
-    };
-    for (size_t i = 0; i < poses.size(); i++)
-        if (opt_index.emplace(poses[i].node_id, i).second)
-        {
-            pose_cam[i] = (uint32_t)cam_opt.size();
-            cam_of_node.emplace(poses[i].node_id, pose_cam[i]);
-            push(poses[i].position, poses[i].orientation, true);
-        }
-    auto lookup = [&](size_t node_id) { // nodeid2poseopt(graph, id, false)
-        pose_ref po;
-        auto it = opt_index.find(node_id);
-        if (it != opt_index.end())
-        {
-            po.optimize = true;
-            po.loc = poses[it->second].position;
-            po.rot = poses[it->second].orientation;
-            po.cam = pose_cam[it->second];
-            return po;
-        }
-        const MeasurementGraph::Node *node = graph.getNode(node_id);
-        if (node != nullptr && finite4(node->payload.orientation) && finite3(node->payload.position))
-        {
-            po.loc = node->payload.position;
-            po.rot = node->payload.orientation;
-            auto c = cam_of_node.find(node_id);
-            if (c == cam_of_node.end())
-            {
-                c = cam_of_node.emplace(node_id, (uint32_t)cam_opt.size()).first;
-                push(po.loc, po.rot, false);
-            }
-            po.cam = c->second;
-        }
-        return po;
-    };
+    camera_table cams(graph, poses);
     std::vector<uint32_t> rel_cam;
     std::vector<double> rel_pose;
     std::unordered_map<size_t, char> used;
@@ -73,7 +29,7 @@ bool solve_decomposition_problem(ochip_ctx *ctx, const MeasurementGraph &graph, 
             continue;
         if (edge->payload.inlier_matches.empty()) // addRelationCost (:311-350)
             continue;
-        const pose_ref s = lookup(edge->source), d = lookup(edge->dest);
+        const pose_ref s = cams.lookup(edge->source), d = cams.lookup(edge->dest);
         if (s.loc == nullptr || d.loc == nullptr)
             continue;
         if (!finite4(s.rot) || !finite4(d.rot) || !finite3(s.loc) || !finite3(d.loc))
@@ -93,16 +49,16 @@ bool solve_decomposition_problem(ochip_ctx *ctx, const MeasurementGraph &graph, 
     // addDownwardsPrior (:1290-1301)
     std::vector<uint32_t> down_cam;
     for (size_t i = 0; i < poses.size(); i++)
-        if (pose_cam[i] != UINT32_MAX && !hasnan4(poses[i].orientation))
-            down_cam.push_back(pose_cam[i]);
+        if (cams.pose_cam[i] != UINT32_MAX && !hasnan4(poses[i].orientation))
+            down_cam.push_back(cams.pose_cam[i]);
     if (rel_cam.empty() && down_cam.empty())
         return true; // NumResidualBlocks() == 0
     // a camera whose orientation is not finite cannot be evaluated; Ceres would fail the whole solve on it
     ochip_relaxg_desc d{};
-    d.n_cams = (uint32_t)cam_opt.size();
-    d.cam_pos = cam_pos.data();
-    d.cam_q = cam_q.data();
-    d.cam_optimize = cam_opt.data();
+    d.n_cams = (uint32_t)cams.size();
+    d.cam_pos = cams.pos.data();
+    d.cam_q = cams.q.data();
+    d.cam_optimize = cams.optimize.data();
     d.n_down = (uint32_t)down_cam.size();
     d.down_cam = down_cam.data();
     d.down_weight = 1e-3;
@@ -116,42 +72,23 @@ bool solve_decomposition_problem(ochip_ctx *ctx, const MeasurementGraph &graph, 
     d.focal_hi = 20000.0;
     ochip_relaxg_problem *dev = nullptr;
     if (ochip_relaxg_problem_create(ctx, &d, &dev) != OCHIP_OK)
-    {
-        *error = std::string("ochip_relaxg_problem_create: ") + ochip_last_error(ctx);
-        return false;
-    }
+        return device_fail(ctx, error, "ochip_relaxg_problem_create");
     if (timers)
         timers->setup_host += since(t0);
     t0 = clk::now();
     ochip_relax_options o{100, 0.1, 1e-6, 1e-10, 1e-8}; // initial_trust_region_radius = 0.1 (:47)
     ochip_relax_summary s{};
-    std::vector<double> q(cam_opt.size() * 4);
+    std::vector<double> q(cams.size() * 4);
     const bool ok = ochip_relaxg_solve(dev, &o, &s) == OCHIP_OK && ochip_relaxg_get_state(dev, q.data(), nullptr, nullptr) == OCHIP_OK;
     if (!ok)
-        *error = std::string("ochip_relaxg_solve: ") + ochip_last_error(ctx);
+        device_fail(ctx, error, "ochip_relaxg_solve");
     ochip_relaxg_problem_destroy(dev);
     if (timers)
         timers->device += since(t0);
     if (!ok)
         return false;
-    if (timers)
-    {
-        timers->solves++;
-        timers->iterations_total += s.iterations;
-        timers->last_iterations = s.iterations;
-        timers->last_initial_cost = s.initial_cost;
-        timers->last_final_cost = s.final_cost;
-        timers->last_residual_blocks = s.num_residual_blocks;
-    }
-    for (size_t i = 0; i < poses.size(); i++) // orientation.normalize(), :1410-1413
-    {
-        if (pose_cam[i] == UINT32_MAX)
-            continue;
-        const double *s4 = &q[4 * (size_t)pose_cam[i]];
-        const double n = std::sqrt(s4[0] * s4[0] + s4[1] * s4[1] + s4[2] * s4[2] + s4[3] * s4[3]);
-        for (int k = 0; k < 4; k++)
-            poses[i].orientation[k] = s4[k] / n;
-    }
+    note_solve(timers, s);
+    cams.store_orientations(q.data()); // orientation.normalize(), :1410-1413
     return true;
 }
 

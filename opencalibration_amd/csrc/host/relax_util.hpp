@@ -1,9 +1,13 @@
-// Helpers shared by the host assembly of the relax flavours (relax.cpp: ground plane on the pair-record engine;
-// relax_mesh.cpp: mesh / tracks / intrinsics on the general engine).
+// Helpers shared by the host assembly of the five relax set-ups: relax.cpp (the ground plane on the pair-record engine and
+// the resident chain in front of it), relax_mesh.cpp (mesh / tracks / intrinsics on the general engine), relax_points.cpp
+// (3-D points) and relax_relative.cpp (homography decompositions).  What needs no device call - the camera table, the
+// bootstrap plane, the packing of plane edges - is in relax_cameras.hpp; here: small vector algebra, the host's grid filter,
+// the device's grid filter, the lens block of the descriptors and what follows every device solve.
 #pragma once
 
 #include "ransac.hpp" // image_to_3d
-#include "relax.hpp"
+#include "relax_cameras.hpp"
+#include "relax_mesh.hpp" // the OPT_* bits
 
 #include <algorithm>
 #include <chrono>
@@ -46,14 +50,6 @@ inline double dot(const v3 &a, const v3 &b)
 inline v3 cross(const v3 &a, const v3 &b)
 {
     return {a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x};
-}
-inline bool finite4(const double *q)
-{
-    return std::isfinite(q[0]) && std::isfinite(q[1]) && std::isfinite(q[2]) && std::isfinite(q[3]);
-}
-inline bool finite3(const double *p)
-{
-    return std::isfinite(p[0]) && std::isfinite(p[1]) && std::isfinite(p[2]);
 }
 inline bool hasnan4(const double *q)
 {
@@ -105,12 +101,71 @@ inline void ray_intersection(const v3 &d1, const v3 &o1, const v3 &d2, const v3 
     }
 }
 
-struct pose_ref // OptimizationPackage::PoseOpt (relax_problem.cpp:182-232)
+// after every device solve: what the caller's timers take from the summary
+inline void note_solve(RelaxTimers *t, const ochip_relax_summary &s)
 {
-    bool optimize = false;
-    const double *loc = nullptr;
-    const double *rot = nullptr;
-    uint32_t cam = 0; // index into the device camera table
+    if (t == nullptr)
+        return;
+    t->solves++;
+    t->iterations_total += s.iterations;
+    t->last_iterations = s.iterations;
+    t->last_initial_cost = s.initial_cost;
+    t->last_final_cost = s.final_cost;
+    t->last_residual_blocks = s.num_residual_blocks;
+}
+
+// a device call failed: its name and the context's text into *error (which may be null); returns false
+inline bool device_fail(ochip_ctx *ctx, std::string *error, const char *what)
+{
+    if (error)
+        *error = std::string(what) + ": " + ochip_last_error(ctx);
+    return false;
+}
+
+// The lens block of a descriptor: the 8 doubles of a forward or an inverse model ...
+template <typename Model> void pack_model8(const Model &m, double out[8])
+{
+    out[0] = m.focal_length_pixels;
+    out[1] = m.principle_point[0], out[2] = m.principle_point[1];
+    for (int i = 0; i < 3; i++)
+        out[3 + i] = m.radial_distortion[i];
+    out[6] = m.tangential_distortion[0], out[7] = m.tangential_distortion[1];
+}
+// ... and the SubsetManifold of its radial block (relax_problem.cpp:533-556, :1160-1180): Brown k1 / k1 k2 / k1 k2 k3 free.
+// With no parameterisation chosen - also when LENS_DISTORTIONS_RADIAL is not among the options at all - the block stays a
+// free Euclidean one.
+inline int radial_free_count(uint32_t options)
+{
+    if ((options & OPT_LENS_DISTORTIONS_RADIAL) && !(options & OPT_LENS_DISTORTIONS_RADIAL_BROWN246_PARAMETERIZATION))
+    {
+        if (options & OPT_LENS_DISTORTIONS_RADIAL_BROWN24_PARAMETERIZATION)
+            return 2;
+        if (options & OPT_LENS_DISTORTIONS_RADIAL_BROWN2_PARAMETERIZATION)
+            return 1;
+    }
+    return 3;
+}
+
+// page-locked staging from the context's pool: no first-touch faults on ~40 bytes x every inlier of a survey, and the
+// upload runs at the link rate
+struct host_staging
+{
+    ochip_ctx *ctx;
+    void *p = nullptr;
+    explicit host_staging(ochip_ctx *c) : ctx(c)
+    {
+    }
+    host_staging(const host_staging &) = delete;
+    host_staging &operator=(const host_staging &) = delete;
+    ~host_staging()
+    {
+        if (p)
+            ochip_host_free(ctx, p);
+    }
+    bool alloc(size_t bytes, std::string *error)
+    {
+        return ochip_host_alloc(ctx, bytes, &p) == OCHIP_OK || device_fail(ctx, error, "ochip_host_alloc");
+    }
 };
 
 
@@ -141,8 +196,6 @@ inline std::vector<uint8_t> grid_filter(const MeasurementGraph &_graph, const Me
         const double intersection_score = gap < 0 ? 0. : 1. / (1. + gap);
         const double cos_angle = dot(sd, dd);
         const double angle_score = 1.0 - cos_angle * cos_angle;
-        const double descriptor_score =
-            m.match_index < rel.matches.size() ? 1.0 - rel.matches[m.match_index].distance : 1.0;
         double ransac_score = 1.0;
         if (rel.relationType == camera_relations::RelationType::HOMOGRAPHY)
         {
@@ -156,7 +209,7 @@ inline std::vector<uint8_t> grid_filter(const MeasurementGraph &_graph, const Me
             const double ex = dx - hx / hz, ey = dy - hy / hz;
             ransac_score = 1.0 / (1.0 + std::sqrt(ex * ex + ey * ey));
         }
-        scored.emplace_back(intersection_score * angle_score * descriptor_score * ransac_score, idx);
+        scored.emplace_back(intersection_score * angle_score * descriptor_score(rel, m) * ransac_score, idx);
     }
     std::vector<uint8_t> keep(rel.inlier_matches.size(), 0);
     auto cell = [res](double x, double y, int *cx, int *cy) {
@@ -231,12 +284,11 @@ inline std::vector<uint8_t> grid_filter(const MeasurementGraph &_graph, const Me
 // csrc/relax_setup.hip): the edges' inlier matches are packed into page-locked staging (40 bytes each), one wavefront per
 // edge scores and filters them, and the edges the device only flags - two matches sharing a cell's best score, which the
 // reference's unstable std::sort decides, or a match outside the cell table - are decided by grid_filter above.
-// keep: the edges' flags back to back (edge j's start at pe[j].inlier_offset).  The handle stays open for the caller
+// keep: the edges' flags back to back (edge j's start at pk.pe[j].inlier_offset).  The handle stays open for the caller
 // (the ground-plane set-up goes on to ochip_plane_setup_blocks); destroy it with ochip_plane_setup_destroy.
 struct device_filter
 {
-    std::vector<ochip_plane_edge> pe;
-    std::vector<const MeasurementGraph::Edge *> edge;
+    plane_edge_packer pk; // the edges that went in, in order
     std::vector<pose_ref> src, dst;
     std::vector<uint8_t> keep;
     ochip_plane_setup *handle = nullptr;
@@ -249,103 +301,41 @@ struct device_filter
     // edges[k] with poses src[k] / dst[k]; nullptr entries are skipped.  triangle: the plane's border triangle (only the
     // block list uses it).  Returns false with *error set when a device call fails.
     bool run(ochip_ctx *ctx, const MeasurementGraph &graph, const std::vector<const MeasurementGraph::Edge *> &edges,
-             const std::vector<pose_ref> &srcs, const std::vector<pose_ref> &dsts, size_t n_edges, const std::vector<double> &cam_pos,
-             const std::vector<double> &cam_q, const double triangle_xy6[6], double fraction, std::string *error)
+             const std::vector<pose_ref> &srcs, const std::vector<pose_ref> &dsts, size_t n_edges, const camera_table &cams,
+             const double triangle_xy6[6], double fraction, std::string *error)
     {
         const auto t0 = clk::now();
-        std::unordered_map<const CameraModel *, uint32_t> model_index;
-        std::vector<double> models10;
-        auto model_of = [&](const CameraModel *m) {
-            auto it = model_index.find(m);
-            if (it != model_index.end())
-                return it->second;
-            const double row[10] = {m->focal_length_pixels,   m->principle_point[0],   m->principle_point[1],      m->radial_distortion[0],
-                                    m->radial_distortion[1],  m->radial_distortion[2], m->tangential_distortion[0], m->tangential_distortion[1],
-                                    (double)m->pixels_cols,   (double)m->pixels_rows};
-            models10.insert(models10.end(), row, row + 10);
-            return model_index.emplace(m, (uint32_t)model_index.size()).first->second;
-        };
-        uint64_t n_inliers = 0;
         for (size_t k = 0; k < n_edges; k++)
         {
-            const MeasurementGraph::Edge *e = edges[k];
-            if (e == nullptr)
+            if (edges[k] == nullptr)
                 continue;
-            const camera_relations &rel = e->payload;
-            ochip_plane_edge r{};
-            r.cam_a = srcs[k].cam;
-            r.cam_b = dsts[k].cam;
-            r.model_a = model_of(graph.getNode(e->source)->payload.model.get());
-            r.model_b = model_of(graph.getNode(e->dest)->payload.model.get());
-            r.n_inliers = (uint32_t)rel.inlier_matches.size();
-            r.flags = rel.relationType == camera_relations::RelationType::HOMOGRAPHY ? 1u : 0u;
-            r.inlier_offset = n_inliers;
-            std::memcpy(r.H, rel.ransac_relation, sizeof r.H);
-            n_inliers += r.n_inliers;
-            pe.push_back(r);
-            edge.push_back(e);
+            pk.add(graph, *edges[k], srcs[k].cam, dsts[k].cam);
             src.push_back(srcs[k]);
             dst.push_back(dsts[k]);
         }
-        // page-locked staging from the context's pool: no first-touch faults on ~40 bytes x every inlier of the survey,
-        // and the upload runs at the link rate
-        struct staging
-        {
-            ochip_ctx *ctx;
-            void *p = nullptr;
-            ~staging()
-            {
-                if (p)
-                    ochip_host_free(ctx, p);
-            }
-        } inl{ctx};
-        if (ochip_host_alloc(ctx, (n_inliers ? n_inliers : 1) * sizeof(ochip_plane_inlier), &inl.p) != OCHIP_OK)
-        {
-            if (error)
-                *error = std::string("ochip_host_alloc: ") + ochip_last_error(ctx);
+        host_staging inl(ctx);
+        if (!inl.alloc((pk.n_inliers ? pk.n_inliers : 1) * sizeof(ochip_plane_inlier), error))
             return false;
-        }
         ochip_plane_inlier *const rec = static_cast<ochip_plane_inlier *>(inl.p);
-#pragma omp parallel for schedule(dynamic, 16)
-        for (size_t j = 0; j < pe.size(); j++)
-        {
-            const camera_relations &rel = edge[j]->payload;
-            ochip_plane_inlier *o = rec + pe[j].inlier_offset;
-            for (size_t idx = 0; idx < rel.inlier_matches.size(); idx++)
-            {
-                const feature_match_denormalized &m = rel.inlier_matches[idx];
-                o[idx].px1[0] = m.pixel_1[0], o[idx].px1[1] = m.pixel_1[1];
-                o[idx].px2[0] = m.pixel_2[0], o[idx].px2[1] = m.pixel_2[1];
-                o[idx].descriptor_score = m.match_index < rel.matches.size() ? 1.0 - rel.matches[m.match_index].distance : 1.0;
-            }
-        }
+        pk.pack_inliers(rec);
         seconds_pack = since(t0);
-        keep.assign(n_inliers, 0);
-        std::vector<uint8_t> inexact(pe.size());
-        if (ochip_plane_setup_create(ctx, pe.data(), (uint32_t)pe.size(), rec, n_inliers, cam_pos.data(), cam_q.data(),
-                                     (uint32_t)(cam_q.size() / 4), models10.data(), (uint32_t)model_index.size(), triangle_xy6, fraction,
-                                     keep.data(), inexact.data(), &handle) != OCHIP_OK)
-        {
-            if (error)
-                *error = std::string("ochip_plane_setup_create: ") + ochip_last_error(ctx);
-            return false;
-        }
-        for (size_t j = 0; j < pe.size(); j++)
+        keep.assign(pk.n_inliers, 0);
+        std::vector<uint8_t> inexact(pk.pe.size());
+        if (ochip_plane_setup_create(ctx, pk.pe.data(), (uint32_t)pk.pe.size(), rec, pk.n_inliers, cams.pos.data(), cams.q.data(),
+                                     (uint32_t)cams.size(), pk.models10.data(), pk.n_models(), triangle_xy6, fraction, keep.data(),
+                                     inexact.data(), &handle) != OCHIP_OK)
+            return device_fail(ctx, error, "ochip_plane_setup_create");
+        for (size_t j = 0; j < pk.pe.size(); j++)
             if (inexact[j])
             {
-                const std::vector<uint8_t> k8 = grid_filter(graph, *edge[j], src[j], dst[j], fraction);
-                std::copy(k8.begin(), k8.end(), keep.begin() + pe[j].inlier_offset);
-                if (ochip_plane_setup_override(handle, pe[j].inlier_offset, k8.size(), k8.data()) != OCHIP_OK)
-                {
-                    if (error)
-                        *error = std::string("ochip_plane_setup_override: ") + ochip_last_error(ctx);
-                    return false;
-                }
+                const std::vector<uint8_t> k8 = grid_filter(graph, *pk.edge[j], src[j], dst[j], fraction);
+                std::copy(k8.begin(), k8.end(), keep.begin() + pk.pe[j].inlier_offset);
+                if (ochip_plane_setup_override(handle, pk.pe[j].inlier_offset, k8.size(), k8.data()) != OCHIP_OK)
+                    return device_fail(ctx, error, "ochip_plane_setup_override");
             }
         return true;
     }
 };
-
 
 } // namespace relax_detail
 } // namespace opencalibration_amd
