@@ -14,6 +14,11 @@
 // derivatives; determinant + maxima), the diffusion steps run up to four at a time out of registers, the
 // candidate list is built without global atomics in a space-filling tile order, and a wavefront per
 // candidate does suppression and description.  DESIGN.md section 4.4 has the per-kernel numbers.
+//
+// The host side: akaze_plan.hpp holds the level table and decides, per call, the form of every pass and the planes every
+// launch reads and writes; akaze_run reads the environment once, builds the plan and calls the stage functions at the end
+// of this file (scale_space_enqueue, detect_enqueue, suppress_enqueue, describe_enqueue), which execute it.
+#include "akaze_plan.hpp"
 #include "area_table.hpp"
 #include "ctx.hpp"
 
@@ -24,18 +29,10 @@
 #include <type_traits>
 #include <vector>
 
+using namespace ochip::akaze; // (level_info, levels_dev, the tile constants and the plan)
+
 namespace
 {
-
-struct level_info
-{
-    int octave, w, h, sigma_size;
-    float esigma;
-    size_t off; // plane offset (floats) inside one image's pyramid
-    int tile_off, tiles_x; // first id and row length of the level's 64 x 24 detection tiles
-    int mask_off;          // first word of the level's maxima bit mask (one 64-bit word per row of a tile column)
-    int sup_off, sup_tx;   // the suppression's masks: first word and words per row of the level's 8 x 8-pixel mask words
-};
 
 __device__ __forceinline__ int clampi(int v, int lo, int hi)
 {
@@ -258,7 +255,6 @@ struct taps_t
 // from LDS, so one launch moves 4 B/pixel in and 4-8 B/pixel out instead of the 16 + 8..12 of separate passes.
 // Every value is the same float expression as the separate passes (ascending tap order, clamped source
 // coordinates for the blur, reflected coordinates for the stencil), so the fusion does not change a bit.
-constexpr int BT_X = 64, BT_Y = 32; // blur tiles
 // cv::solve(A, b, dst, DECOMP_LU) for AKAZE's 2 x 2 system [Dxx Dxy; Dxy Dyy] d = -[Dx Dy] (core/src/lapack.cpp, the 2 x 2 fast
 // path for CV_32FC1): Cramer's rule in double; a singular system leaves the offset at (0, 0) - the restatement's subpixel_solve
 __device__ __forceinline__ float2 subpixel_solve(float Dxx, float Dxy, float Dyy, float Dx, float Dy)
@@ -275,7 +271,6 @@ __device__ __forceinline__ float2 subpixel_solve(float Dxx, float Dxy, float Dyy
     return r;
 }
 
-constexpr int DT_Y = 24;             // detection tiles are 64 x 24 (16, 24, 32 rows measured: 43, 39, 40 us per image for the determinant kernels)
 enum
 {
     BLUR_PLAIN = 0,
@@ -714,7 +709,6 @@ __global__ void kcontrast_kernel(const unsigned int *__restrict__ hist, const un
 // instead of per step, at ~14 VALU instructions per pixel-step (the LDS-tiled form of this loop was VALU-bound).
 // The arithmetic is the one-step form's: flux (c_a + c_b) * (L_b - L_a) evaluated once per pixel pair and used
 // with both signs, 0 across the image border.
-constexpr int FED_FUSE = 4;
 constexpr int NLD_TY = 16; // output rows per wavefront strip (8, 16, 24, 32 measured: 39, 37, 44, 43 us per image)
 struct fed_tau_group
 {
@@ -873,13 +867,6 @@ __global__ void halfsample_area_kernel(const float *__restrict__ in, int w, int 
     out[(size_t)blockIdx.z * out_stride + (size_t)y * ow + x] = sum;
 }
 
-__global__ void copy_plane_kernel(const float *__restrict__ in, size_t in_stride, float *__restrict__ out,
-                                  size_t out_stride, size_t n)
-{
-    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n)
-        out[(size_t)blockIdx.z * out_stride + i] = in[(size_t)blockIdx.z * in_stride + i];
-}
 
 // ---- detection
 struct cand_t
@@ -1683,11 +1670,6 @@ __global__ __launch_bounds__(256) void level_strip_kernel(level_strip_args A)
 // steps per launch instead of nld_fused_kernel's 4: 31 -> 19 launches per chunk).  Those groups belong to the upper octaves,
 // whose launches have too few strips to fill the SIMDs: 19.1 us per image against the tile kernel's 11.0.
 
-struct levels_dev
-{
-    int n;
-    level_info l[16];
-};
 
 // Candidate list of an image = the non-zero entries of its maxima maps, laid out tile by tile in a space-filling
 // order (tile_seq: level by level, Morton order of the 64 x 24 detection tiles inside a level).  Neighbouring list entries
@@ -2878,68 +2860,6 @@ __global__ __launch_bounds__(256) void compact_ordered_kernel(const unsigned cha
     }
 }
 
-// ---------------------------------------------------------------------------------------- host side
-std::vector<float> gaussian_taps(float sigma)
-{
-    int ksize = (int)std::ceil(2.0f * (1.0f + (sigma - 0.8f) / 0.3f));
-    if ((ksize % 2) == 0)
-        ksize += 1;
-    if (ksize < 1)
-        ksize = 1;
-    std::vector<double> k(ksize);
-    double sum = 0;
-    const int r = ksize / 2;
-    for (int i = 0; i < ksize; i++)
-    {
-        const double x = i - r;
-        k[i] = std::exp(-0.5 * x * x / ((double)sigma * sigma));
-        sum += k[i];
-    }
-    std::vector<float> out(ksize);
-    for (int i = 0; i < ksize; i++)
-        out[i] = (float)(k[i] / sum);
-    return out;
-}
-
-bool is_prime(int n)
-{
-    if (n < 2)
-        return false;
-    for (int d = 2; d * d <= n; d++)
-        if (n % d == 0)
-            return false;
-    return true;
-}
-
-std::vector<float> fed_taus(float T, float tau_max) // FED cycle for stopping time T, kappa-cycle reordering
-{
-    const double t = (double)T;
-    const int n = (int)(std::ceil(std::sqrt(3.0 * t / tau_max + 0.25) - 0.5 - 1.0e-8) + 0.5);
-    std::vector<float> tau;
-    if (n <= 0)
-        return tau;
-    const double scale = 3.0 * t / (tau_max * (double)(n * (n + 1)));
-    const double c = 1.0 / (4.0 * n + 2.0), d = scale * tau_max / 2.0;
-    std::vector<double> tauh(n);
-    for (int k = 0; k < n; k++)
-    {
-        const double hh = std::cos(M_PI * (2.0 * k + 1.0) * c);
-        tauh[k] = d / (hh * hh);
-    }
-    tau.resize(n);
-    const int kappa = n / 2;
-    int prime = n + 1;
-    while (!is_prime(prime))
-        prime++;
-    for (int k = 0, l = 0; l < n; ++k, ++l)
-    {
-        int index = 0;
-        while ((index = ((k + 1) * kappa) % prime - 1) >= n)
-            k++;
-        tau[l] = (float)tauh[index];
-    }
-    return tau;
-}
 
 // ---- synthetic views (test / benchmark DATA, not part of the hot path): a jittered ground lattice of
 // Gaussian blobs on the plane z = a x + b y, seen through a pinhole camera.  Every view of one seed shows
@@ -3387,9 +3307,11 @@ int working_image_enqueue(hipStream_t st, const uint8_t *d_bgr, uint8_t *d_gray,
 
 // The context's tables for this shape (built and uploaded with one wait when the context has none or had another shape's;
 // nothing of the context's stream still reads the old ones then: every akaze_run ends with a wait).
-int akaze_tables_for(ochip_ctx *ctx, int width, int height, int W, int H, double scale, const levels_dev &LV, int n_tiles,
+int akaze_tables_for(ochip_ctx *ctx, int width, int height, const working_size &ws, const level_table &levels,
                      const ochip::akaze_tables **out)
 {
+    const levels_dev &LV = levels.LV;
+    const int W = ws.W, H = ws.H, n_tiles = levels.n_tiles;
     if (!ctx->akaze_tabs)
     {
         ctx->akaze_tabs = new ochip::akaze_tables();
@@ -3439,7 +3361,7 @@ int akaze_tables_for(ochip_ctx *ctx, int width, int height, int W, int H, double
     rc = rc != OCHIP_OK ? rc : T.mem.upload(&g, &host_gather_tab(), 1, ENQ);
     T.gtab = g;
     resize_plan plan; // (alive until the wait below)
-    rc = rc != OCHIP_OK ? rc : resize_tables_enqueue(T.mem, width, height, W, H, scale, &plan, &T.rz);
+    rc = rc != OCHIP_OK ? rc : resize_tables_enqueue(T.mem, width, height, W, H, ws.scale, &plan, &T.rz);
     OCHIP_HIP(ctx, ochip_stream_wait(ctx, ctx->stream));
     if (rc != OCHIP_OK)
         return rc;
@@ -3447,22 +3369,463 @@ int akaze_tables_for(ochip_ctx *ctx, int width, int height, int W, int H, double
     return OCHIP_OK;
 }
 
+// The device buffers of one akaze_run: blocks of the call's arena, and the context's tables of the shape.
+struct buffers
+{
+    uint32_t B = 0;          // images
+    int W = 0, H = 0;        // working size
+    size_t plane0 = 0;       // W * H: an image's stride in img, flow and ping
+    uint32_t max_kp = 0, max_cands = 0;
+    uint8_t *bgr = nullptr, *gray = nullptr;
+    float *img = nullptr, *flow = nullptr, *ping = nullptr; // working image, conductivity, the FED groups' second plane
+    float *Lt = nullptr;     // the pyramids: [image][level_info::off ...], stride level_table::img_stride
+    float2 *Lxy = nullptr;   // (Lx, Ly) interleaved, indexed like the other pyramids
+    float2 *Fit = nullptr;   // (dx, dy) of the sub-pixel fit at the maxima (sparse, like Rmax)
+    float *Rmax = nullptr, *kc = nullptr, *kp = nullptr;
+    unsigned int *hmax = nullptr, *hist = nullptr, *ncand = nullptr, *pmax = nullptr;
+    cand_t *cands = nullptr;
+    unsigned char *dead = nullptr, *valid = nullptr;
+    unsigned long long *desc = nullptr, *descc = nullptr;
+    float *kpc = nullptr;
+    unsigned int *counts = nullptr, *tile_counts = nullptr, *tile_base = nullptr;
+    // maxima / valid keypoints; the suppression's masks (8 x 8 pixels per word): keypoints, points waiting for a turn, points
+    // with a turn (pass 1: the maxima in this layout)
+    unsigned long long *mask = nullptr, *vmask = nullptr, *kmask = nullptr, *pmask = nullptr, *rmask = nullptr;
+    unsigned int *found = nullptr;                     // the suppression's passes 2 / 3: a keypoint's first keypoint of the other level
+    unsigned int *level_first = nullptr;               // first candidate of every level of every image (+ the list's length)
+    unsigned int *turns = nullptr, *waiting = nullptr; // its two lists of points waiting for their turn, their lengths per (image, level)
+    unsigned int *wbase = nullptr, *live = nullptr, *nlive = nullptr;
+    const unsigned int *tile_seq = nullptr; // the context's tables
+    const gather_tab *gtab = nullptr;
+
+    // a plane of the plan and its image stride
+    float *at(const level_table &T, const plane_ref &r, size_t *stride) const
+    {
+        *stride = r.id == plane_id::level ? T.img_stride : plane0;
+        return r.id == plane_id::level ? Lt + T.LV.l[r.level].off : r.id == plane_id::ping ? ping : flow;
+    }
+};
+
+// ---- the stages, in the order akaze_run enqueues them on the context's stream (each called once, from there)
+
+// f(std::integral_constant<int, v>) for the constant in [LO, HI] a runtime value has (beyond: HI; the plan has checked
+// the level table against what is instantiated): a derivative scale, a group of FED steps
+template <int LO, int HI, typename F> void with_constant(int v, F &&f)
+{
+    if constexpr (LO == HI)
+        f(std::integral_constant<int, LO>{});
+    else if (v == LO)
+        f(std::integral_constant<int, LO>{});
+    else
+        with_constant<LO + 1, HI>(v, f);
+}
+
+// 1-D grids of B images padded to a multiple of 8 workgroups (xcd_tile): a workgroup per tile of tw x th outputs; a
+// wavefront per strip of ow x sh outputs, four to a workgroup
+inline dim3 tile_grid(int w, int h, int tw, int th, uint32_t B)
+{
+    return dim3(8 * ((((w + tw - 1) / tw) * ((h + th - 1) / th) + 7) / 8), 1, B);
+}
+inline dim3 strip_grid(int w, int h, int ow, int sh, uint32_t B)
+{
+    const int strips = ((w + ow - 1) / ow) * ((h + sh - 1) / sh);
+    return dim3(8 * (((strips + 3) / 4 + 7) / 8), 1, B);
+}
+
+// the contrast factor, the base image and the levels as the plan has them.  dump: OCHIP_DUMP_PLANES
+int scale_space_enqueue(ochip_ctx *ctx, const level_table &T, const plan &P, const buffers &b, const char *dump)
+{
+    hipStream_t st = ctx->stream;
+    const levels_dev &LV = T.LV;
+    const uint32_t B = b.B;
+    const int W = b.W, H = b.H;
+    const size_t plane0 = b.plane0, img_stride = T.img_stride;
+    auto taps_of = [](const std::vector<float> &k) {
+        taps_t t{};
+        t.n = (int)k.size();
+        for (int i = 0; i < t.n && i < MAX_TAPS; i++)
+            t.k[i] = k[i];
+        return t;
+    };
+    const taps_t g1 = taps_of(gaussian_taps(1.0f)), g0 = taps_of(gaussian_taps(SIGMA_OFFSET)); // (5 and 9 taps: the plan has checked)
+    auto tiles = [&](int w, int h) { return tile_grid(w, h, BT_X, BT_Y, B); };
+    auto grid2 = [&](int w, int h) { return dim3((w + 255) / 256, h, B); };
+
+    // ---- contrast factor: Gaussian(1) + gradient magnitude + per-tile maxima in one pass, then the histogram
+    OCHIP_HIP(ctx, hipMemsetAsync(b.hist, 0, (size_t)B * 301 * 4, st));
+    // (as a register strip - the level kernel's Gaussian and distance-1 pattern with the magnitude where the conductivity is - when
+    // the launch has the strips to fill the device, like the levels below; else the tile kernel and the reduction of its tile maxima)
+    if (P.contrast_strip)
+    {
+        OCHIP_HIP(ctx, hipMemsetAsync(b.hmax, 0, (size_t)B * 4, st));
+        level_strip_args sa{};
+        sa.in = b.img, sa.in_stride = plane0;
+        sa.flow = b.flow, sa.flow_stride = plane0;
+        sa.w = W, sa.h = H;
+        sa.hmax_bits = b.hmax;
+        for (int q = 0; q < 5; q++)
+            sa.k[q] = g1.k[q];
+        typedef level_strip_geom<2, 0> MG;
+        hipLaunchKernelGGL((level_strip_kernel<2, 0, true, true>), strip_grid(W, H, MG::OW, MG::H, B), dim3(256), 0, st, sa);
+    }
+    else
+    {
+        const int n_tiles0 = ((W + BT_X - 1) / BT_X) * ((H + BT_Y - 1) / BT_Y);
+        blur_args a{b.img, plane0, b.flow, nullptr, plane0, W, H, nullptr, 0, b.pmax, nullptr, 0};
+        hipLaunchKernelGGL((blur_fused_kernel<BLUR_MODG, 1, 2>), tiles(W, H), dim3(256), 0, st, a, g1);
+        hipLaunchKernelGGL(hmax_reduce_kernel, dim3(B), dim3(256), 0, st, (const unsigned int *)b.pmax, n_tiles0, b.hmax);
+    }
+    hipLaunchKernelGGL(hist_kernel, dim3((W + 255) / 256, (H + HIST_ROWS - 1) / HIST_ROWS, B), dim3(256), 0, st, (const float *)b.flow, W, H,
+                       plane0, b.hmax, 300, b.hist);
+    hipLaunchKernelGGL(kcontrast_kernel, dim3((B + 63) / 64), dim3(64), 0, st, b.hist, b.hmax, 300, 0.7f, b.kc, (int)B,
+                       (int)((W - 2) * (H - 2))); // (the interior pixels)
+
+    // ---- nonlinear scale space
+    // level 0: the base image (Gaussian(soffset) of the resized view) and - its Lsmooth being its Lt - the detector's scale-s
+    // derivatives of it, one launch (two before: the derivative pass read the base image again)
+    {
+        const level_info &l0 = LV.l[0];
+        blur_args a{b.img, plane0, (float *)(b.Lxy + l0.off), nullptr, img_stride, W, H, nullptr, 0, nullptr, b.Lt + l0.off, img_stride};
+        with_constant<2, 4>(l0.sigma_size, [&](auto S) {
+            hipLaunchKernelGGL((blur_fused_kernel<BLUR_DERIV, decltype(S)::value, 4>), tiles(W, H), dim3(256), 0, st, a, g0);
+        });
+    }
+    // (the detector's: zeroed here, where the stream has always had them)
+    OCHIP_HIP(ctx, hipMemsetAsync(b.ncand, 0, B * 4, st));
+    if (P.det_accumulate)
+    {
+        // the strips add their maxima to zeroed masks and tile counts (the tile form writes every word itself)
+        OCHIP_HIP(ctx, hipMemsetAsync(b.mask, 0, (size_t)B * T.mask_stride * 8, st));
+        OCHIP_HIP(ctx, hipMemsetAsync(b.tile_counts, 0, (size_t)B * T.n_tiles * 4, st));
+    }
+    for (int i = 1; i < LV.n; i++)
+    {
+        const level_info &l = LV.l[i];
+        const level_plan &lp = P.lv[i];
+        for (const launch &L : lp.launches)
+        {
+            size_t src_stride = 0, dst_stride = 0;
+            const float *src = b.at(T, L.src, &src_stride);
+            float *dst = b.at(T, L.dst, &dst_stride);
+            switch (L.kind)
+            {
+            case launch_kind::halfsample_area: // (an odd dimension: OpenCV's general area path)
+                hipLaunchKernelGGL(halfsample_area_kernel, grid2(l.w, l.h), dim3(256), 0, st, src, LV.l[i - 1].w, LV.l[i - 1].h, src_stride, dst,
+                                   l.w, l.h, dst_stride);
+                break;
+            case launch_kind::halfsample:
+                hipLaunchKernelGGL(halfsample_kernel, grid2(l.w, l.h), dim3(256), 0, st, src, LV.l[i - 1].w, LV.l[i - 1].h, src_stride, dst, l.w,
+                                   l.h, dst_stride);
+                break;
+            case launch_kind::smooth:
+            {
+                // Lsmooth of the level (Gaussian(1) of the image it starts from) -> conductivity AND the detector's
+                // scale-s derivatives Lx, Ly (AKAZE computes both on evolution[i].Lsmooth), one pass
+                blur_args a{src, src_stride, dst, (float *)(b.Lxy + l.off), dst_stride, l.w, l.h, b.kc, l.octave, nullptr, nullptr, img_stride};
+                with_constant<2, 4>(l.sigma_size, [&](auto S) {
+                    hipLaunchKernelGGL((blur_fused_kernel<BLUR_FLOW_DERIV, decltype(S)::value, 2>), tiles(l.w, l.h), dim3(256), 0, st, a, g1);
+                });
+                break;
+            }
+            case launch_kind::strip:
+            {
+                // ONE launch: Lsmooth -> conductivity + (Lx, Ly), and the level's first group of diffusion steps behind them (the
+                // whole cycle for the levels of the first octave: then the conductivity plane is not even stored)
+                level_strip_args sa{};
+                sa.in = src, sa.in_stride = src_stride;
+                sa.flow = b.flow, sa.flow_stride = plane0;
+                sa.Lxy = b.Lxy + l.off, sa.lxy_stride = img_stride;
+                sa.Lout = dst, sa.lout_stride = dst_stride;
+                sa.w = l.w, sa.h = l.h;
+                sa.kcontrast = b.kc, sa.n_octave_steps = l.octave;
+                for (int q = 0; q < 5; q++)
+                    sa.k[q] = g1.k[q];
+                for (int q = 0; q < L.n_steps; q++)
+                    sa.T.tau[q] = T.tsteps[i][q];
+                sa.half_out = lp.half_out.id == plane_id::none ? nullptr : b.at(T, lp.half_out, &sa.half_stride);
+                with_constant<2, 4>(l.sigma_size, [&](auto S) {
+                    with_constant<3, 4>(L.n_steps, [&](auto K) {
+                        with_constant<0, 1>(lp.store_flow, [&](auto SF) {
+                            typedef level_strip_geom<decltype(S)::value, decltype(K)::value> G;
+                            hipLaunchKernelGGL((level_strip_kernel<decltype(S)::value, decltype(K)::value, decltype(SF)::value != 0>),
+                                               strip_grid(l.w, l.h, G::OW, G::H, B), dim3(256), 0, st, sa);
+                        });
+                    });
+                });
+                break;
+            }
+            case launch_kind::diffuse:
+            {
+                fed_tau_group G{};
+                for (int q = 0; q < L.n_steps; q++)
+                    G.tau[q] = T.tsteps[i][L.first_step + q];
+                const int ow = 64 - 2 * L.n_steps; // output columns per wavefront
+                const dim3 gr((l.w + 4 * ow - 1) / (4 * ow), (l.h + NLD_TY - 1) / NLD_TY, B);
+                with_constant<1, FED_FUSE>(L.n_steps, [&](auto K) {
+                    hipLaunchKernelGGL((nld_fused_kernel<decltype(K)::value>), gr, dim3(256), 0, st, src, (const float *)b.flow, dst, l.w, l.h,
+                                       src_stride, plane0, dst_stride, G);
+                });
+                break;
+            }
+            }
+            if (dump && i == 1 && (L.kind == launch_kind::smooth || L.kind == launch_kind::strip))
+            {
+                // debugging aid: level 1's conductivity plane of the first image
+                std::vector<float> hf((size_t)l.w * l.h);
+                OCHIP_HIP(ctx, ochip_stream_wait(ctx, st));
+                OCHIP_HIP(ctx, hipMemcpy(hf.data(), b.flow, hf.size() * 4, hipMemcpyDeviceToHost));
+                if (FILE *f = std::fopen((std::string(dump) + "_flow1.f32").c_str(), "wb"))
+                {
+                    std::fwrite(hf.data(), 4, hf.size(), f);
+                    std::fclose(f);
+                }
+            }
+        }
+    }
+    return OCHIP_OK;
+}
+
+// determinant and maxima of every level, then the candidate list in tile order
+void detect_enqueue(hipStream_t st, const level_table &T, const plan &P, const buffers &b)
+{
+    const levels_dev &LV = T.LV;
+    const uint32_t B = b.B;
+    const size_t img_stride = T.img_stride, mask_stride = T.mask_stride;
+    const int n_tiles = T.n_tiles;
+    for (int i = 0; i < LV.n; i++)
+    {
+        const level_info &l = LV.l[i];
+        const float2 *lxy = b.Lxy + l.off;
+        float2 *ld = b.Fit + l.off;
+        float *rm = b.Rmax + l.off;
+        with_constant<2, 4>(l.sigma_size, [&](auto S) {
+            if (P.lv[i].det_strip)
+            {
+                typedef det_strip_geom<decltype(S)::value> G;
+                const det_window_t &dw = P.lv[i].det_win;
+                const int4 win = make_int4(dw.x0, dw.x1, dw.y0, dw.y1);
+                hipLaunchKernelGGL((det_strip_kernel<decltype(S)::value>), strip_grid(l.w, l.h, G::OW, G::H, B), dim3(256), 0, st, lxy, img_stride,
+                                   ld, rm, l.w, l.h, DET_THRESHOLD, b.tile_counts, l.tile_off, n_tiles, win, b.mask + l.mask_off, mask_stride);
+            }
+            else
+                hipLaunchKernelGGL((det_maxima_kernel<decltype(S)::value>), tile_grid(l.w, l.h, BT_X, DT_Y, B), dim3(256), 0, st, lxy, img_stride,
+                                   ld, rm, l.w, l.h, DET_THRESHOLD, b.tile_counts, l.tile_off, n_tiles, det_margin(l), b.mask + l.mask_off,
+                                   mask_stride);
+        });
+    }
+    hipLaunchKernelGGL(scan_tiles_kernel, dim3(B), dim3(256), 0, st, (const unsigned int *)b.tile_counts, b.tile_seq, n_tiles, b.tile_base,
+                       b.ncand);
+    hipLaunchKernelGGL(collect_tiles_kernel, dim3((n_tiles + 4 * COLLECT_TPW - 1) / (4 * COLLECT_TPW), 1, B), dim3(256), 0, st,
+                       (const float *)b.Rmax, (const float2 *)b.Fit, img_stride, (const unsigned long long *)b.mask, mask_stride, LV,
+                       (const unsigned int *)b.tile_base, n_tiles, b.cands, b.max_cands, (const unsigned int *)b.tile_counts);
+}
+
+// the three passes over at most max_n candidates per image, then the list of survivors.  sup_hooks: the test hooks
+// sup_generic | sup_small_lists << 1; verbose: the statistics' print-out (one more wait)
+int suppress_enqueue(ochip_ctx *ctx, ochip::dev_blocks &mem, const level_table &T, const buffers &b, unsigned int max_n, int sup_hooks,
+                     bool verbose)
+{
+    hipStream_t st = ctx->stream;
+    const levels_dev &LV = T.LV;
+    const uint32_t B = b.B, max_cands = b.max_cands;
+    const size_t img_stride = T.img_stride, mask_stride = T.mask_stride, sup_stride = T.sup_stride;
+    const int n_tiles = T.n_tiles;
+    OCHIP_HIP(ctx, hipMemsetAsync(b.vmask, 0, (size_t)B * mask_stride * 8, st)); // (the descriptor's: zeroed here, where the stream has always had it)
+    const dim3 per_cand((max_n + 255) / 256, 1, B);
+    unsigned int *d_sup_stats = nullptr;
+    if (verbose)
+    {
+        OCHIP_TRY(mem.alloc<unsigned int>(&d_sup_stats, (size_t)3 * B * LV.n * 3));
+        OCHIP_HIP(ctx, hipMemsetAsync(d_sup_stats, 0, (size_t)3 * B * LV.n * 3 * 4, st));
+    }
+    OCHIP_HIP(ctx, hipMemsetAsync(b.kmask, 0, (size_t)B * sup_stride * 8, st));
+    OCHIP_HIP(ctx, hipMemsetAsync(b.pmask, 0, (size_t)B * sup_stride * 8, st));
+    OCHIP_HIP(ctx, hipMemsetAsync(b.waiting, 0, (size_t)B * LV.n * 4, st));
+    hipLaunchKernelGGL(suppress_level_first_kernel, dim3(B), dim3(64), 0, st, (const unsigned int *)b.ncand, max_cands, LV,
+                       (const unsigned int *)b.tile_base, b.tile_seq, n_tiles, b.level_first);
+    // (64 x 8-pixel groups: the grid covers the largest level, a level per blockIdx.y)
+    hipLaunchKernelGGL(suppress_tiles_kernel, dim3((unsigned int)((LV.l[0].tiles_x * ((LV.l[0].h + 7) / 8) + 255) / 256), LV.n, B), dim3(256), 0,
+                       st, (const unsigned long long *)b.mask, mask_stride, b.rmask, sup_stride, LV);
+    // a pass: the points' first round, then the rounds of the points that wait for a turn, a workgroup per (image, level)
+    auto pass = [&](auto PASS, int levels) {
+        hipLaunchKernelGGL(suppress_round0_kernel<decltype(PASS)::value>, per_cand, dim3(256), 0, st, (const cand_t *)b.cands,
+                           (const unsigned int *)b.ncand, max_cands, (const float *)b.Rmax, img_stride, (const unsigned long long *)b.rmask,
+                           b.pmask, b.kmask, sup_stride, LV, (const unsigned int *)b.level_first, b.turns, b.waiting,
+                           (const unsigned int *)b.found, sup_hooks);
+        hipLaunchKernelGGL(suppress_rounds_kernel<decltype(PASS)::value>, dim3(B, levels), dim3(SUP_THREADS), 0, st,
+                           (const unsigned int *)b.ncand, max_cands, (const float *)b.Rmax, img_stride, b.pmask, b.kmask, sup_stride, LV,
+                           (const unsigned int *)b.level_first, b.turns, b.waiting, d_sup_stats, sup_hooks);
+    };
+    // passes 2 and 3 first look, per keypoint, for the first keypoint of the other level in its window
+    auto windows = [&](auto PASS) -> int {
+        OCHIP_HIP(ctx, hipMemsetAsync(b.rmask, 0, (size_t)B * sup_stride * 8, st));
+        hipLaunchKernelGGL(suppress_window_kernel<decltype(PASS)::value>, per_cand, dim3(256), 0, st, (const cand_t *)b.cands,
+                           (const unsigned int *)b.ncand, max_cands, (const unsigned long long *)b.kmask, b.rmask, sup_stride, LV, b.found,
+                           sup_hooks);
+        return OCHIP_OK;
+    };
+    pass(std::integral_constant<int, 1>{}, LV.n);
+    if (LV.n > 1)
+    {
+        OCHIP_TRY(windows(std::integral_constant<int, 2>{}));
+        pass(std::integral_constant<int, 2>{}, LV.n - 1);
+        OCHIP_TRY(windows(std::integral_constant<int, 3>{}));
+        pass(std::integral_constant<int, 3>{}, LV.n - 1);
+    }
+    hipLaunchKernelGGL(suppress_dead_kernel, per_cand, dim3(256), 0, st, (const cand_t *)b.cands, (const unsigned int *)b.ncand, max_cands,
+                       (const unsigned long long *)b.kmask, sup_stride, LV, b.dead);
+    if (d_sup_stats)
+    {
+        std::vector<unsigned int> hs((size_t)3 * B * LV.n * 3);
+        OCHIP_HIP(ctx, hipMemcpyAsync(hs.data(), d_sup_stats, hs.size() * 4, hipMemcpyDeviceToHost, st));
+        OCHIP_HIP(ctx, ochip_stream_wait(ctx, st));
+        for (int p = 0; p < 3; p++)
+        {
+            std::string line;
+            for (int i = 0; i < LV.n; i++)
+            {
+                unsigned int rounds = 0, ticks = 0, pts = 0;
+                for (uint32_t b_ = 0; b_ < B; b_++)
+                {
+                    const unsigned int *o = &hs[(((size_t)p * B + b_) * LV.n + i) * 3];
+                    rounds = std::max(rounds, o[0]), ticks = std::max(ticks, o[1]), pts = std::max(pts, o[2]);
+                }
+                char buf[64];
+                std::snprintf(buf, sizeof buf, " %u/%.0fus/%u", rounds, ticks * 0.01, pts);
+                line += buf;
+            }
+            std::fprintf(stderr, "[ochip extract] suppression pass %d, per level max over %u images of rounds/time/points:%s\n", p + 1, B,
+                         line.c_str());
+        }
+    }
+    // the survivors in list order (the descriptor runs over those only; slots it never visits stay invalid)
+    hipLaunchKernelGGL(live_list_kernel, dim3(B), dim3(SCAN_THREADS), 0, st, (const unsigned char *)b.dead, (const unsigned int *)b.ncand,
+                       max_cands, b.live, b.nlive);
+    OCHIP_HIP(ctx, hipMemsetAsync(b.valid, 0, (size_t)B * max_cands, st));
+    return OCHIP_OK;
+}
+
+// orientation and descriptor of at most max_live survivors per image, then the valid keypoints compacted in mask order
+// (max_n == 0: only the counts are zeroed)
+int describe_enqueue(ochip_ctx *ctx, const level_table &T, const buffers &b, unsigned int max_n, unsigned int max_live)
+{
+    hipStream_t st = ctx->stream;
+    const uint32_t B = b.B, max_cands = b.max_cands;
+    if (max_n == 0)
+    {
+        OCHIP_HIP(ctx, hipMemsetAsync(b.counts, 0, B * 4, st));
+        return OCHIP_OK;
+    }
+    const int xcd_remap = 2; // groups of 64 list neighbours per XCD (see xcd_contiguous; 0, 1 and 3 measured slower)
+    // the grid covers the longest list of survivors, not of candidates (a third to a half of the workgroups would
+    // find nothing to do, and an empty workgroup still takes a slot with its 22 KB of LDS for a microsecond)
+    // (capping the workgroups a CU holds with unused dynamic LDS, to leave wave slots to the other sequences' HBM-bound
+    // kernels beside this L2-bound one, was measured: 3 120 images/s with none, 3 100 / 2 940 / 2 830 at 4 / 3 / 2 per CU)
+    if (max_live > 0)
+        hipLaunchKernelGGL(describe3_kernel, dim3(512 * (((max_live + DESC_WPB - 1) / DESC_WPB + 511) / 512), 1, B), dim3(64 * DESC_WPB), 0, st,
+                           (const cand_t *)b.cands, (const unsigned int *)b.nlive, max_cands, (const unsigned int *)b.live, (const float *)b.Lt,
+                           (const float2 *)b.Lxy, T.img_stride, T.LV, DERIVATIVE_FACTOR, b.gtab, b.kp, b.desc, b.valid, xcd_remap, b.vmask,
+                           T.mask_stride);
+    hipLaunchKernelGGL(rank_scan_kernel, dim3(B), dim3(SCAN_THREADS), 0, st, (const unsigned long long *)b.vmask, T.mask_stride, b.wbase,
+                       b.counts);
+    hipLaunchKernelGGL(compact_ordered_kernel, dim3((max_n + 255) / 256, 1, B), dim3(256), 0, st, (const unsigned char *)b.valid,
+                       (const cand_t *)b.cands, (const unsigned int *)b.ncand, max_cands, (const unsigned long long *)b.vmask,
+                       (const unsigned int *)b.wbase, T.mask_stride, T.LV, (const float *)b.kp, (const unsigned long long *)b.desc, b.kpc,
+                       b.descc, b.max_kp);
+    return OCHIP_OK;
+}
+
+// the planes' seam (tests/test_gpu_akaze_planes.py): the first image's Lt and (Lx, Ly) pyramids and its contrast factor
+// as raw float files <prefix>_lt.f32 / _lxy.f32 / _kc.f32
+int dump_planes(ochip_ctx *ctx, const level_table &T, const buffers &b, const char *prefix)
+{
+    std::vector<float> hl(T.img_stride), hx(2 * T.img_stride), hk(1);
+    OCHIP_HIP(ctx, ochip_stream_wait(ctx, ctx->stream));
+    OCHIP_HIP(ctx, hipMemcpy(hl.data(), b.Lt, T.img_stride * 4, hipMemcpyDeviceToHost));
+    OCHIP_HIP(ctx, hipMemcpy(hx.data(), b.Lxy, T.img_stride * 8, hipMemcpyDeviceToHost));
+    OCHIP_HIP(ctx, hipMemcpy(hk.data(), b.kc, 4, hipMemcpyDeviceToHost));
+    const std::vector<float> *planes[3] = {&hl, &hx, &hk};
+    const char *suffix[3] = {"_lt.f32", "_lxy.f32", "_kc.f32"};
+    for (int which = 0; which < 3; which++)
+        if (FILE *f = std::fopen((std::string(prefix) + suffix[which]).c_str(), "wb"))
+        {
+            std::fwrite(planes[which]->data(), 4, planes[which]->size(), f);
+            std::fclose(f);
+        }
+    return OCHIP_OK;
+}
+
+// the call's blocks, sized from the level table
+int alloc_buffers(ochip::dev_scratch &mem, const level_table &T, buffers &b, size_t src_px)
+{
+    const size_t B = b.B, max_cands = b.max_cands, max_kp = b.max_kp;
+    const size_t n_tiles0 = (size_t)((b.W + BT_X - 1) / BT_X) * ((b.H + BT_Y - 1) / BT_Y);
+    OCHIP_TRY(mem.alloc<uint8_t>(&b.gray, B * src_px + 4));
+    OCHIP_TRY(mem.alloc<float>(&b.img, B * b.plane0));
+    OCHIP_TRY(mem.alloc<float>(&b.flow, B * b.plane0));
+    OCHIP_TRY(mem.alloc<float>(&b.ping, B * b.plane0));
+    OCHIP_TRY(mem.alloc<unsigned int>(&b.pmax, B * n_tiles0));
+    OCHIP_TRY(mem.alloc<float>(&b.Lt, B * T.img_stride));
+    OCHIP_TRY(mem.alloc<float2>(&b.Lxy, B * T.img_stride));
+    OCHIP_TRY(mem.alloc<float2>(&b.Fit, B * T.img_stride));
+    OCHIP_TRY(mem.alloc<float>(&b.Rmax, B * T.img_stride));
+    OCHIP_TRY(mem.alloc<float>(&b.kc, B));
+    OCHIP_TRY(mem.alloc<unsigned int>(&b.hmax, B));
+    OCHIP_TRY(mem.alloc<unsigned int>(&b.hist, B * 301));
+    OCHIP_TRY(mem.alloc<unsigned int>(&b.ncand, B));
+    OCHIP_TRY(mem.alloc<cand_t>(&b.cands, B * max_cands));
+    OCHIP_TRY(mem.alloc<unsigned char>(&b.dead, B * max_cands));
+    OCHIP_TRY(mem.alloc<unsigned char>(&b.valid, B * max_cands));
+    OCHIP_TRY(mem.alloc<float>(&b.kp, B * max_cands * 6));
+    OCHIP_TRY(mem.alloc<unsigned long long>(&b.desc, B * max_cands * 8));
+    OCHIP_TRY(mem.alloc<float>(&b.kpc, B * max_kp * 6));
+    OCHIP_TRY(mem.alloc<unsigned long long>(&b.descc, B * max_kp * 8));
+    OCHIP_TRY(mem.alloc<unsigned int>(&b.counts, B));
+    OCHIP_TRY(mem.alloc<unsigned int>(&b.tile_counts, B * T.n_tiles));
+    OCHIP_TRY(mem.alloc<unsigned int>(&b.tile_base, B * T.n_tiles));
+    OCHIP_TRY(mem.alloc<unsigned long long>(&b.mask, B * T.mask_stride));
+    OCHIP_TRY(mem.alloc<unsigned long long>(&b.vmask, B * T.mask_stride));
+    OCHIP_TRY(mem.alloc<unsigned long long>(&b.kmask, B * T.sup_stride));
+    OCHIP_TRY(mem.alloc<unsigned long long>(&b.pmask, B * T.sup_stride));
+    OCHIP_TRY(mem.alloc<unsigned long long>(&b.rmask, B * T.sup_stride));
+    OCHIP_TRY(mem.alloc<unsigned int>(&b.turns, B * 2 * max_cands));
+    OCHIP_TRY(mem.alloc<unsigned int>(&b.waiting, B * T.LV.n));
+    OCHIP_TRY(mem.alloc<unsigned int>(&b.level_first, B * (T.LV.n + 1)));
+    OCHIP_TRY(mem.alloc<unsigned int>(&b.found, B * max_cands));
+    OCHIP_TRY(mem.alloc<unsigned int>(&b.wbase, B * T.mask_stride));
+    OCHIP_TRY(mem.alloc<unsigned int>(&b.live, B * max_cands));
+    OCHIP_TRY(mem.alloc<unsigned int>(&b.nlive, B));
+    return OCHIP_OK;
+}
+
 // images: n_images x h x w x 3 BGR bytes (host, or device when on_device).  Working size: the INTER_AREA
 // downscale to max side 1600 of extract_features.cpp:26-27.  Outputs (host): per image up to max_kp keypoints,
 // in unspecified order: kp6 = {x, y, size, angle(rad), response, level} in working-image pixels, desc = 8 x u64,
 // counts[i] = number written for image i (<= max_kp).  work_wh receives the working width/height.
-int akaze_run(ochip_ctx *ctx, const uint8_t *images_bgr, bool on_device, uint32_t n_images, int width, int height,
-              uint32_t max_kp, float *kp6, uint64_t *desc, uint32_t *counts, int *work_wh, const ochip_feature_lists *lists,
+int akaze_run(ochip_ctx *ctx, const uint8_t *images_bgr, bool on_device, uint32_t n_images, int width, int height, uint32_t max_kp,
+              float *kp6, uint64_t *desc, uint32_t *counts, int *work_wh, const ochip_feature_lists *lists,
               double nms_radius)
 {
     if (!ctx || !counts || (n_images && (!images_bgr || (!lists && (!kp6 || !desc)))))
         return OCHIP_EINVAL;
     if (width <= 0 || height <= 0)
         return ochip_fail(ctx, OCHIP_EINVAL, "bad image size %d x %d", width, height);
+    // the environment, read once: the route hooks, the strips' threshold, the planes' seam, the suppression's hooks
+    plan_inputs in;
+    in.B = n_images;
+    in.tile_levels = ochip_test_hook("tile_levels"), in.tile_det = ochip_test_hook("tile_det");
+    in.strip_levels = ochip_test_hook("strip_levels"), in.strip_det = ochip_test_hook("strip_det");
+    if (const char *strip_env = std::getenv("OCHIP_STRIP_MIN_PIXELS"); strip_env && *strip_env)
+        in.strip_min_pixels = (size_t)std::strtoull(strip_env, nullptr, 10);
+    const char *dump = std::getenv("OCHIP_DUMP_PLANES");
+    in.keep_flow = dump != nullptr;
+    // (the suppression's code for radii beyond the default scale space's / its lists beyond their LDS part)
+    const int sup_hooks = (ochip_test_hook("sup_generic") ? 1 : 0) | (ochip_test_hook("sup_small_lists") ? 2 : 0);
+    const bool verbose = ochip_verbose("extract");
+
     OCHIP_HIP(ctx, hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
     const working_size ws(width, height);
-    const double scale = ws.scale;
     const int W = ws.W, H = ws.H;
     if (work_wh)
     {
@@ -3474,642 +3837,95 @@ int akaze_run(ochip_ctx *ctx, const uint8_t *images_bgr, bool on_device, uint32_
     if (n_images == 0)
         return OCHIP_OK;
 
-    // ---- level table (AKAZEFeatures::Allocate_Memory_Evolution)
-    const int omax = 4, nsub = 4;
-    const float soffset = 1.6f, dfactor = 1.5f, dthreshold = 0.00005f;
-    levels_dev LV{};
-    std::vector<std::vector<float>> tsteps;
-    size_t img_stride = 0;
-    int n_tiles = 0;
-    size_t mask_stride = 0; // words of one image's maxima bit masks
-    size_t sup_stride = 0;  // words of one image's masks of the suppression (8 x 8 pixels per word)
-    {
-        std::vector<float> etime;
-        for (int i = 0; i < omax; i++)
-        {
-            const float rfactor = 1.0f / (float)(1 << i);
-            const int lw = (int)(W * rfactor), lh = (int)(H * rfactor);
-            if ((lw < 80 || lh < 40) && i != 0) // (Allocate_Memory_Evolution: "smallest possible octave" - 80 wide, 40 high)
-                break;
-            for (int j = 0; j < nsub; j++)
-            {
-                level_info &l = LV.l[LV.n++];
-                l.octave = i;
-                l.w = lw;
-                l.h = lh;
-                l.esigma = soffset * std::pow(2.0f, (float)j / (float)nsub + (float)i);
-                l.sigma_size = (int)std::lrintf(l.esigma * dfactor / (float)(1 << i));
-                l.off = img_stride;
-                img_stride += (size_t)lw * lh;
-                l.tiles_x = (lw + BT_X - 1) / BT_X;
-                l.tile_off = n_tiles;
-                n_tiles += l.tiles_x * ((lh + DT_Y - 1) / DT_Y);
-                l.mask_off = (int)mask_stride;
-                mask_stride += (size_t)l.tiles_x * lh;
-                l.sup_off = (int)sup_stride;
-                l.sup_tx = (lw + 7) / 8;
-                sup_stride += (size_t)l.sup_tx * ((lh + 7) / 8);
-                etime.push_back(0.5f * (l.esigma * l.esigma));
-            }
-        }
-        tsteps.resize(LV.n);
-        for (int i = 1; i < LV.n; i++)
-            tsteps[i] = fed_taus(etime[i] - etime[i - 1], 0.25f);
-    }
-    const size_t plane0 = (size_t)W * H;
-    const uint32_t B = n_images;
-    const uint32_t max_cands = std::max<uint32_t>(max_kp * 4, 1u << 16);
-
+    const level_table T(W, H);
+    buffers b;
+    b.B = n_images, b.W = W, b.H = H, b.plane0 = (size_t)W * H;
+    b.max_kp = max_kp, b.max_cands = std::max<uint32_t>(max_kp * 4, 1u << 16);
+    const uint32_t B = b.B;
     // (uploads on the context's own stream, not the device's default stream, where the uploads of all contexts would queue up
     // behind each other; the wait keeps the caller's buffer semantics of a synchronous copy)
     ochip::dev_scratch mem{ctx, "akaze"};
-    constexpr auto WAIT = ochip::copy_mode::enqueue_wait;
-    int rc = OCHIP_OK;
-#define AK(call)                                                                                                       \
-    do                                                                                                                 \
-    {                                                                                                                  \
-        if (rc == OCHIP_OK)                                                                                            \
-            rc = (call);                                                                                               \
-    } while (0)
-    uint8_t *d_bgr = nullptr, *d_gray = nullptr;
-    float *d_img = nullptr, *d_flow = nullptr, *d_ping = nullptr;
-    float2 *d_Lxy = nullptr; // (Lx, Ly) interleaved, indexed like the other pyramids
-    float2 *d_Fit = nullptr; // (dx, dy) of the sub-pixel fit at the maxima (sparse, like d_Rmax)
-    float *d_Lt = nullptr, *d_Rmax = nullptr, *d_kc = nullptr,
-          *d_kp = nullptr;
-    unsigned int *d_hmax = nullptr, *d_hist = nullptr, *d_ncand = nullptr, *d_pmax = nullptr;
-    cand_t *d_cands = nullptr;
-    unsigned char *d_dead = nullptr, *d_valid = nullptr;
-    unsigned long long *d_desc = nullptr, *d_descc = nullptr;
-    float *d_kpc = nullptr;
-    unsigned int *d_counts = nullptr, *d_tile_counts = nullptr, *d_tile_base = nullptr;
-    // maxima / valid keypoints; the suppression's masks (8 x 8 pixels per word): keypoints, points waiting for a turn, points
-    // with a turn (pass 1: the maxima in this layout)
-    unsigned long long *d_mask = nullptr, *d_vmask = nullptr, *d_kmask = nullptr, *d_pmask = nullptr, *d_rmask = nullptr;
-    unsigned int *d_found = nullptr;                       // the suppression's passes 2 / 3: a keypoint's first keypoint of the other level
-    unsigned int *d_level_first = nullptr;                 // first candidate of every level of every image (+ the list's length)
-    unsigned int *d_turns = nullptr, *d_waiting = nullptr; // its two lists of points waiting for their turn, their lengths per (image, level)
-    unsigned int *d_wbase = nullptr, *d_live = nullptr, *d_nlive = nullptr;
     const size_t src_px = (size_t)width * height;
-    // 1-D tile grids padded to a multiple of 8 workgroups (xcd_tile)
-    auto tiles = [&](int w, int h) { return dim3(8 * ((((w + BT_X - 1) / BT_X) * ((h + BT_Y - 1) / BT_Y) + 7) / 8), 1, B); };
-    auto det_tiles = [&](int w, int h) { return dim3(8 * ((((w + BT_X - 1) / BT_X) * ((h + DT_Y - 1) / DT_Y) + 7) / 8), 1, B); };
-    const dim3 tiles0 = tiles(W, H);
-    const int n_tiles0 = ((W + BT_X - 1) / BT_X) * ((H + BT_Y - 1) / BT_Y);
     if (on_device)
-        d_bgr = const_cast<uint8_t *>(images_bgr);
+        b.bgr = const_cast<uint8_t *>(images_bgr);
     else
-        AK(mem.upload(&d_bgr, images_bgr, (size_t)B * src_px * 3, WAIT));
-    AK(mem.alloc<uint8_t>(&d_gray, (size_t)B * src_px + 4));
-    AK(mem.alloc<float>(&d_img, (size_t)B * plane0));
-    AK(mem.alloc<float>(&d_flow, (size_t)B * plane0));
-    AK(mem.alloc<float>(&d_ping, (size_t)B * plane0));
-    AK(mem.alloc<unsigned int>(&d_pmax, (size_t)B * n_tiles0));
-    AK(mem.alloc<float>(&d_Lt, (size_t)B * img_stride));
-    AK(mem.alloc<float2>(&d_Lxy, (size_t)B * img_stride));
-    AK(mem.alloc<float2>(&d_Fit, (size_t)B * img_stride));
-    AK(mem.alloc<float>(&d_Rmax, (size_t)B * img_stride));
-    AK(mem.alloc<float>(&d_kc, B));
-    AK(mem.alloc<unsigned int>(&d_hmax, B));
-    AK(mem.alloc<unsigned int>(&d_hist, (size_t)B * 301));
-    AK(mem.alloc<unsigned int>(&d_ncand, B));
-    AK(mem.alloc<cand_t>(&d_cands, (size_t)B * max_cands));
-    AK(mem.alloc<unsigned char>(&d_dead, (size_t)B * max_cands));
-    AK(mem.alloc<unsigned char>(&d_valid, (size_t)B * max_cands));
-    AK(mem.alloc<float>(&d_kp, (size_t)B * max_cands * 6));
-    AK(mem.alloc<unsigned long long>(&d_desc, (size_t)B * max_cands * 8));
-    AK(mem.alloc<float>(&d_kpc, (size_t)B * max_kp * 6));
-    AK(mem.alloc<unsigned long long>(&d_descc, (size_t)B * max_kp * 8));
-    AK(mem.alloc<unsigned int>(&d_counts, B));
-    AK(mem.alloc<unsigned int>(&d_tile_counts, (size_t)B * n_tiles));
-    AK(mem.alloc<unsigned int>(&d_tile_base, (size_t)B * n_tiles));
-    AK(mem.alloc<unsigned long long>(&d_mask, (size_t)B * mask_stride));
-    AK(mem.alloc<unsigned long long>(&d_vmask, (size_t)B * mask_stride));
-    AK(mem.alloc<unsigned long long>(&d_kmask, (size_t)B * sup_stride));
-    AK(mem.alloc<unsigned long long>(&d_pmask, (size_t)B * sup_stride));
-    AK(mem.alloc<unsigned long long>(&d_rmask, (size_t)B * sup_stride));
-    AK(mem.alloc<unsigned int>(&d_turns, (size_t)B * 2 * max_cands));
-    AK(mem.alloc<unsigned int>(&d_waiting, (size_t)B * LV.n));
-    AK(mem.alloc<unsigned int>(&d_level_first, (size_t)B * (LV.n + 1)));
-    AK(mem.alloc<unsigned int>(&d_found, (size_t)B * max_cands));
-    AK(mem.alloc<unsigned int>(&d_wbase, (size_t)B * mask_stride));
-    AK(mem.alloc<unsigned int>(&d_live, (size_t)B * max_cands));
-    AK(mem.alloc<unsigned int>(&d_nlive, B));
+        OCHIP_TRY(mem.upload(&b.bgr, images_bgr, (size_t)B * src_px * 3, ochip::copy_mode::enqueue_wait));
+    OCHIP_TRY(alloc_buffers(mem, T, b, src_px));
     // the tables of this shape: the context's own, the same from chunk to chunk
     const ochip::akaze_tables *tabs = nullptr;
-    AK(akaze_tables_for(ctx, width, height, W, H, scale, LV, n_tiles, &tabs));
-    if (rc != OCHIP_OK)
-    return rc;
-    const unsigned int *d_tile_seq = tabs->tile_seq;
-    const gather_tab *d_gtab = (const gather_tab *)tabs->gtab;
-    auto grid2 = [&](int w, int h) { return dim3((w + 255) / 256, h, B); };
-    auto taps_of = [](const std::vector<float> &k) {
-        taps_t t{};
-        t.n = (int)k.size();
-        for (int i = 0; i < t.n && i < MAX_TAPS; i++)
-            t.k[i] = k[i];
-        return t;
-    };
-    const taps_t g1 = taps_of(gaussian_taps(1.0f)), g0 = taps_of(gaussian_taps(soffset));
-    if (g1.n != 5 || g0.n != 9)
-    return ochip_fail(ctx, OCHIP_EINVAL, "akaze: unexpected Gaussian kernel sizes %d / %d", g1.n, g0.n);
+    OCHIP_TRY(akaze_tables_for(ctx, width, height, ws, T, &tabs));
+    b.tile_seq = tabs->tile_seq;
+    b.gtab = (const gather_tab *)tabs->gtab;
+    for (const void *p : {(const void *)b.img, (const void *)b.flow, (const void *)b.ping, (const void *)b.Lt, (const void *)b.Lxy})
+        in.aligned16 = in.aligned16 && ((uintptr_t)p & 15) == 0;
+    const plan P = make_plan(T, W, H, in);
+    if (P.error)
+        return ochip_fail(ctx, OCHIP_EINVAL, "%s", P.error);
     hipEvent_t e0, e1;
     ochip_prof_begin(ctx, OCHIP_K_AKAZE, &e0, &e1);
 
-    // ---- grey, downscale, float
-    working_image_enqueue(st, d_bgr, d_gray, d_img, B, width, height, W, H, scale, &tabs->rz);
-
-    // ---- contrast factor: Gaussian(1) + gradient magnitude + per-tile maxima in one pass, then the histogram
-    OCHIP_HIP(ctx, hipMemsetAsync(d_hist, 0, (size_t)B * 301 * 4, st));
-    // (as a register strip - the level kernel's Gaussian and distance-1 pattern with the magnitude where the conductivity is - when
-    // the launch has the strips to fill the device, like the levels below; else the tile kernel and the reduction of its tile maxima)
-    const bool modg_tiles = ochip_test_hook("tile_levels"), modg_force = ochip_test_hook("strip_levels");
-    const bool modg_strip = !modg_tiles && (W & 1) == 0 && (plane0 & 1) == 0 && W >= 64 && H >= 64 && ((uintptr_t)d_img & 15) == 0 &&
-                            ((uintptr_t)d_flow & 15) == 0 && (modg_force || (size_t)W * H * B >= ((size_t)32 << 20));
-    if (modg_strip)
-    {
-        OCHIP_HIP(ctx, hipMemsetAsync(d_hmax, 0, (size_t)B * 4, st));
-        level_strip_args sa{};
-        sa.in = d_img, sa.in_stride = plane0;
-        sa.flow = d_flow, sa.flow_stride = plane0;
-        sa.w = W, sa.h = H;
-        sa.hmax_bits = d_hmax;
-        for (int q = 0; q < 5; q++)
-            sa.k[q] = g1.k[q];
-        typedef level_strip_geom<2, 0> MG;
-        const int strips = ((W + MG::OW - 1) / MG::OW) * ((H + MG::H - 1) / MG::H);
-        hipLaunchKernelGGL((level_strip_kernel<2, 0, true, true>), dim3(8 * (((strips + 3) / 4 + 7) / 8), 1, B), dim3(256), 0, st, sa);
-    }
-    else
-    {
-        blur_args a{d_img, plane0, d_flow, nullptr, plane0, W, H, nullptr, 0, d_pmax, nullptr, 0};
-        hipLaunchKernelGGL((blur_fused_kernel<BLUR_MODG, 1, 2>), tiles0, dim3(256), 0, st, a, g1);
-        hipLaunchKernelGGL(hmax_reduce_kernel, dim3(B), dim3(256), 0, st, (const unsigned int *)d_pmax, n_tiles0, d_hmax);
-    }
-    hipLaunchKernelGGL(hist_kernel, dim3((W + 255) / 256, (H + HIST_ROWS - 1) / HIST_ROWS, B), dim3(256), 0, st, (const float *)d_flow, W, H,
-                       plane0, d_hmax, 300, d_hist);
-    hipLaunchKernelGGL(kcontrast_kernel, dim3((B + 63) / 64), dim3(64), 0, st, d_hist, d_hmax, 300, 0.7f, d_kc, (int)B,
-                       (int)((W - 2) * (H - 2))); // (the interior pixels)
-
-    // ---- nonlinear scale space
-    // level 0: the base image (Gaussian(soffset) of the resized view) and - its Lsmooth being its Lt - the detector's scale-s
-    // derivatives of it, one launch (two before: the derivative pass read the base image again)
-    bool level0_derivatives_done = false;
-    {
-        const level_info &l0 = LV.l[0];
-        blur_args a{d_img, plane0, (float *)(d_Lxy + l0.off), nullptr, img_stride, W, H, nullptr, 0, nullptr, d_Lt + l0.off, img_stride};
-        level0_derivatives_done = true;
-        if (l0.sigma_size == 2)
-            hipLaunchKernelGGL((blur_fused_kernel<BLUR_DERIV, 2, 4>), tiles0, dim3(256), 0, st, a, g0);
-        else if (l0.sigma_size == 3)
-            hipLaunchKernelGGL((blur_fused_kernel<BLUR_DERIV, 3, 4>), tiles0, dim3(256), 0, st, a, g0);
-        else if (l0.sigma_size == 4)
-            hipLaunchKernelGGL((blur_fused_kernel<BLUR_DERIV, 4, 4>), tiles0, dim3(256), 0, st, a, g0);
-        else
-        {
-            level0_derivatives_done = false;
-            blur_args p{d_img, plane0, d_Lt + l0.off, nullptr, img_stride, W, H, nullptr, 0, nullptr, nullptr, 0};
-            hipLaunchKernelGGL((blur_fused_kernel<BLUR_PLAIN, 0, 4>), tiles0, dim3(256), 0, st, p, g0);
-        }
-    }
-    // the register-strip kernels load pairs of pixels with 8 / 16-byte loads: even widths and plane offsets (every level
-    // of an image whose working width is a multiple of 8; the tile kernels take the rest, and OCHIP_TEST_HOOKS=tile_det
-    // / tile_levels all of it)
-    // Which form pays depends on how many strips a launch has: a strip is one wavefront walking 40 - 90 rows, and a level of
-    // 400 x 300 pixels x 100 images is 2 400 of them on 1 024 SIMDs (level kernel: 150 us per launch against the tile kernels'
-    // 75; 200 x 150: 150 against 30) - the strips take the levels of >= STRIP_MIN_PIXELS pixels per launch (the first two
-    // octaves of a chunk of the bench), the tiles the rest; OCHIP_TEST_HOOKS=strip_levels / strip_det: strips wherever they can
-    const bool strip_hook = !ochip_test_hook("tile_det"), level_hook = !ochip_test_hook("tile_levels");
-    const bool force_level_strips = ochip_test_hook("strip_levels"), force_det_strips = ochip_test_hook("strip_det");
-    // (OCHIP_STRIP_MIN_PIXELS: the tests lower the threshold so that a small batch takes the mixed route of a bench chunk -
-    // strips on its large levels, tiles on the small ones - and is compared with the restatement)
-    const char *strip_env = std::getenv("OCHIP_STRIP_MIN_PIXELS");
-    const size_t STRIP_MIN_PIXELS = strip_env && *strip_env ? (size_t)std::strtoull(strip_env, nullptr, 10) : (size_t)32 << 20;
-    auto strips_pay = [&](const level_info &l, bool forced) { return forced || (size_t)l.w * l.h * B >= STRIP_MIN_PIXELS; };
-    bool det_strips = strip_hook && (img_stride & 1) == 0 && (plane0 & 1) == 0 && ((uintptr_t)d_Lxy & 15) == 0 && ((uintptr_t)d_Lt & 15) == 0 &&
-                      ((uintptr_t)d_flow & 15) == 0 && ((uintptr_t)d_ping & 15) == 0;
-    for (int i = 0; i < LV.n; i++)
-        det_strips = det_strips && (LV.l[i].w & 1) == 0 && (LV.l[i].off & 1) == 0 && LV.l[i].w >= 8 && LV.l[i].h >= 8;
-    const bool level_strips = det_strips && level_hook;
-    OCHIP_HIP(ctx, hipMemsetAsync(d_ncand, 0, B * 4, st));
-    if (det_strips)
-    {
-        // the strips add their maxima to zeroed masks and tile counts (the tile form writes every word itself)
-        OCHIP_HIP(ctx, hipMemsetAsync(d_mask, 0, (size_t)B * mask_stride * 8, st));
-        OCHIP_HIP(ctx, hipMemsetAsync(d_tile_counts, 0, (size_t)B * n_tiles * 4, st));
-    }
-    // the columns / rows whose descriptor window [round(x - margin) - 1, round(x + margin) + 1] stays inside the level
-    // (the predicate det_maxima_kernel evaluates per pixel: an interval in x and in y)
-    auto det_window = [&](const level_info &l) {
-        const float margin = (10.0f * std::sqrt(2.0f)) * (float)l.sigma_size; // descriptor window half width, M-LDB
-        int4 win = make_int4(1, 0, 1, 0);
-        auto span = [&](int n, int *lo, int *hi) {
-            bool any = false;
-            for (int v = 1; v < n - 1; v++)
-                if ((int)std::rint((float)v - margin) - 1 >= 0 && (int)std::rint((float)v + margin) + 1 < n)
-                {
-                    if (!any)
-                        *lo = v;
-                    *hi = v;
-                    any = true;
-                }
-        };
-        span(l.w, &win.x, &win.y);
-        span(l.h, &win.z, &win.w);
-        return win;
-    };
-    int octave_steps = 0;
-    int half_sampled_level = -1; // the level whose first image a level kernel has already written (half-sampling epilogue)
-    for (int i = 1; i < LV.n; i++)
-    {
-        const level_info &l = LV.l[i], &p = LV.l[i - 1];
-        float *cur = d_Lt + l.off;
-        const size_t np = (size_t)l.w * l.h;
-        const size_t n_steps = tsteps[i].size();
-        // the level's FED steps in balanced groups of <= FED_FUSE, a launch each; the first group of a strip level (2 .. 4 steps)
-        // rides in the level's launch
-        const size_t tile_groups = (n_steps + FED_FUSE - 1) / FED_FUSE;
-        const size_t first_size = tile_groups ? n_steps / tile_groups + (n_steps % tile_groups ? 1 : 0) : 0;
-        const bool strip_level = level_strips && strips_pay(l, force_level_strips) && l.sigma_size >= 2 && l.sigma_size <= 4 && l.w >= 64 &&
-                                 l.h >= 64 && (tile_groups == 0 || (first_size >= 2 && first_size <= 4));
-        std::vector<size_t> group_sizes;
-        for (size_t g = 0; g < tile_groups; g++)
-            group_sizes.push_back(n_steps / tile_groups + (g < n_steps % tile_groups ? 1 : 0));
-        const size_t n_groups = group_sizes.size();
-        // the level starts from the previous level's image (half-sampled at a new octave); the FED steps ping-pong
-        // between the level plane and a scratch plane, arranged so that the last step lands in the level plane
-        const float *src = d_Lt + p.off;
-        size_t src_stride = img_stride;
-        if (l.octave > p.octave)
-        {
-            float *dst = (n_groups % 2 == 0) ? cur : d_ping;
-            const size_t dst_stride = (n_groups % 2 == 0) ? img_stride : plane0;
-            if (p.w != 2 * l.w || p.h != 2 * l.h) // (an odd dimension: OpenCV's general area path, see halfsample_area_kernel)
-                hipLaunchKernelGGL(halfsample_area_kernel, grid2(l.w, l.h), dim3(256), 0, st, (const float *)(d_Lt + p.off), p.w, p.h,
-                                   img_stride, dst, l.w, l.h, dst_stride);
-            else if (half_sampled_level != i) // (else: the last level kernel of the octave before wrote it with its own rows)
-                hipLaunchKernelGGL(halfsample_kernel, grid2(l.w, l.h), dim3(256), 0, st, (const float *)(d_Lt + p.off), p.w, p.h,
-                                   img_stride, dst, l.w, l.h, dst_stride);
-            src = dst;
-            src_stride = dst_stride;
-            octave_steps++;
-        }
-        auto group_size = [&](size_t g) { return group_sizes[g]; };
-        size_t first_group = 0; // launches of the diffusion kernels start at this group
-        if (strip_level)
-        {
-            // ONE launch: Lsmooth -> conductivity + (Lx, Ly), and the level's first group of diffusion steps behind them (the
-            // whole cycle for the levels of the first octave: then the conductivity plane is not even stored)
-            const int K = n_groups ? (int)group_size(0) : 0;
-            const bool to_cur = n_groups == 0 || ((n_groups - 1) % 2) == 0;
-            float *dst = to_cur ? cur : d_ping;
-            const size_t dst_stride = to_cur ? img_stride : plane0;
-            level_strip_args sa{};
-            sa.in = src, sa.in_stride = src_stride;
-            sa.flow = d_flow, sa.flow_stride = plane0;
-            sa.Lxy = d_Lxy + l.off, sa.lxy_stride = img_stride;
-            sa.Lout = dst, sa.lout_stride = dst_stride;
-            sa.w = l.w, sa.h = l.h;
-            sa.kcontrast = d_kc, sa.n_octave_steps = octave_steps;
-            for (int q = 0; q < 5; q++)
-                sa.k[q] = g1.k[q];
-            for (int q = 0; q < K; q++)
-                sa.T.tau[q] = tsteps[i][q];
-            // the octave's last level with its whole FED cycle in this launch: the next octave's first image - 2 x 2 means of this
-            // level's final rows, a lane's pair of columns x a pair of rows - leaves with them (halfsample_kernel read the
-            // level again: 2.5 us per image at the first octave boundary)
-            sa.half_out = nullptr;
-            sa.half_stride = 0;
-            if (i + 1 < LV.n && LV.l[i + 1].octave > l.octave && n_groups == 1 && K > 0 && l.w == 2 * LV.l[i + 1].w && l.h == 2 * LV.l[i + 1].h)
-            {
-                const size_t next_groups = (tsteps[i + 1].size() + FED_FUSE - 1) / FED_FUSE;
-                const bool next_to_cur = next_groups % 2 == 0;
-                sa.half_out = next_to_cur ? d_Lt + LV.l[i + 1].off : d_ping;
-                sa.half_stride = next_to_cur ? img_stride : plane0;
-                half_sampled_level = i + 1;
-            }
-            const bool store_flow = n_groups > 1 || std::getenv("OCHIP_DUMP_PLANES") != nullptr;
-            auto sgrid = [&](int ow, int sh) {
-                const int strips = ((l.w + ow - 1) / ow) * ((l.h + sh - 1) / sh);
-                return dim3(8 * (((strips + 3) / 4 + 7) / 8), 1, B);
-            };
-#define OCHIP_LEVEL_STRIP(SS, KK, FF)                                                                                                     \
-    hipLaunchKernelGGL((level_strip_kernel<SS, KK, FF>), sgrid(level_strip_geom<SS, KK>::OW, level_strip_geom<SS, KK>::H), dim3(256), 0, st, sa)
-#define OCHIP_LEVEL_STRIP_K(SS)                                                                                                           \
-    do                                                                                                                                    \
-    {                                                                                                                                     \
-        if (K == 0)                                                                                                                       \
-            OCHIP_LEVEL_STRIP(SS, 0, true);                                                                                               \
-        else if (K == 2 && store_flow)                                                                                                    \
-            OCHIP_LEVEL_STRIP(SS, 2, true);                                                                                               \
-        else if (K == 2)                                                                                                                  \
-            OCHIP_LEVEL_STRIP(SS, 2, false);                                                                                              \
-        else if (K == 3 && store_flow)                                                                                                    \
-            OCHIP_LEVEL_STRIP(SS, 3, true);                                                                                               \
-        else if (K == 3)                                                                                                                  \
-            OCHIP_LEVEL_STRIP(SS, 3, false);                                                                                              \
-        else if (store_flow)                                                                                                              \
-            OCHIP_LEVEL_STRIP(SS, 4, true);                                                                                               \
-        else                                                                                                                              \
-            OCHIP_LEVEL_STRIP(SS, 4, false);                                                                                              \
-    } while (0)
-            if (l.sigma_size == 2)
-                OCHIP_LEVEL_STRIP_K(2);
-            else if (l.sigma_size == 3)
-                OCHIP_LEVEL_STRIP_K(3);
-            else
-                OCHIP_LEVEL_STRIP_K(4);
-#undef OCHIP_LEVEL_STRIP_K
-#undef OCHIP_LEVEL_STRIP
-            if (n_groups)
-            {
-                src = dst;
-                src_stride = dst_stride;
-                first_group = 1;
-            }
-        }
-        else
-        {
-            // Lsmooth of the level (Gaussian(1) of the image it starts from) -> conductivity AND the detector's
-            // scale-s derivatives Lx, Ly (AKAZE computes both on evolution[i].Lsmooth), one pass
-            blur_args a{src, src_stride, d_flow, (float *)(d_Lxy + l.off), plane0, l.w, l.h, d_kc, octave_steps, nullptr, nullptr, img_stride};
-            if (l.sigma_size == 2)
-                hipLaunchKernelGGL((blur_fused_kernel<BLUR_FLOW_DERIV, 2, 2>), tiles(l.w, l.h), dim3(256), 0, st, a, g1);
-            else if (l.sigma_size == 3)
-                hipLaunchKernelGGL((blur_fused_kernel<BLUR_FLOW_DERIV, 3, 2>), tiles(l.w, l.h), dim3(256), 0, st, a, g1);
-            else if (l.sigma_size == 4)
-                hipLaunchKernelGGL((blur_fused_kernel<BLUR_FLOW_DERIV, 4, 2>), tiles(l.w, l.h), dim3(256), 0, st, a, g1);
-            else
-            return ochip_fail(ctx, OCHIP_EINVAL, "akaze: derivative scale %d outside 2..4", l.sigma_size);
-        }
-        if (const char *dump = std::getenv("OCHIP_DUMP_PLANES"))
-            if (i == 1)
-            {
-                // debugging aid: level 1's conductivity plane of the first image
-                std::vector<float> hf(np);
-                OCHIP_HIP(ctx, ochip_stream_wait(ctx, st));
-                OCHIP_HIP(ctx, hipMemcpy(hf.data(), d_flow, np * 4, hipMemcpyDeviceToHost));
-                if (FILE *f = std::fopen((std::string(dump) + "_flow1.f32").c_str(), "wb"))
-                {
-                    std::fwrite(hf.data(), 4, hf.size(), f);
-                    std::fclose(f);
-                }
-            }
-        if (n_steps == 0)
-            hipLaunchKernelGGL(copy_plane_kernel, dim3((unsigned)((np + 255) / 256), 1, B), dim3(256), 0, st, src, src_stride,
-                               cur, img_stride, np);
-        for (size_t g = 0, k = 0; g < n_groups; g++)
-        {
-            const size_t gsz = group_size(g);
-            fed_tau_group T{};
-            for (size_t q = 0; q < gsz; q++)
-                T.tau[q] = tsteps[i][k + q];
-            k += gsz;
-            if (g < first_group)
-                continue;
-            const bool to_cur = ((n_groups - 1 - g) % 2) == 0;
-            float *dst = to_cur ? cur : d_ping;
-            const size_t dst_stride = to_cur ? img_stride : plane0;
-            const int ow = 64 - 2 * (int)gsz; // output columns per wavefront
-            const dim3 gr((l.w + 4 * ow - 1) / (4 * ow), (l.h + NLD_TY - 1) / NLD_TY, B);
-            if (gsz == 1)
-                hipLaunchKernelGGL((nld_fused_kernel<1>), gr, dim3(256), 0, st, src, (const float *)d_flow, dst, l.w, l.h,
-                                   src_stride, plane0, dst_stride, T);
-            else if (gsz == 2)
-                hipLaunchKernelGGL((nld_fused_kernel<2>), gr, dim3(256), 0, st, src, (const float *)d_flow, dst, l.w, l.h,
-                                   src_stride, plane0, dst_stride, T);
-            else if (gsz == 3)
-                hipLaunchKernelGGL((nld_fused_kernel<3>), gr, dim3(256), 0, st, src, (const float *)d_flow, dst, l.w, l.h,
-                                   src_stride, plane0, dst_stride, T);
-            else
-                hipLaunchKernelGGL((nld_fused_kernel<4>), gr, dim3(256), 0, st, src, (const float *)d_flow, dst, l.w, l.h,
-                                   src_stride, plane0, dst_stride, T);
-            src = dst;
-            src_stride = dst_stride;
-        }
-    }
-    // ---- derivatives of level 0, determinant, maxima
-    for (int i = 0; i < LV.n; i++)
-    {
-        const level_info &l = LV.l[i];
-        if (i == 0 && !level0_derivatives_done)
-        {
-            // level 0's Lsmooth is its Lt: derivatives without a further blur (a one-tap identity kernel keeps the
-            // same code path; 0 + 1 * x is exact)
-            taps_t one{};
-            one.n = 1;
-            one.k[0] = 1.0f;
-            blur_args a{d_Lt + l.off, img_stride, (float *)(d_Lxy + l.off), nullptr, img_stride, l.w, l.h, nullptr, 0, nullptr, nullptr, 0};
-            if (l.sigma_size == 2)
-                hipLaunchKernelGGL((blur_fused_kernel<BLUR_DERIV, 2, 0>), tiles(l.w, l.h), dim3(256), 0, st, a, one);
-            else if (l.sigma_size == 3)
-                hipLaunchKernelGGL((blur_fused_kernel<BLUR_DERIV, 3, 0>), tiles(l.w, l.h), dim3(256), 0, st, a, one);
-            else if (l.sigma_size == 4)
-                hipLaunchKernelGGL((blur_fused_kernel<BLUR_DERIV, 4, 0>), tiles(l.w, l.h), dim3(256), 0, st, a, one);
-            else
-            return ochip_fail(ctx, OCHIP_EINVAL, "akaze: derivative scale %d outside 2..4", l.sigma_size);
-        }
-        {
-            const float2 *lxy = d_Lxy + l.off;
-            float2 *ld = d_Fit + l.off;
-            float *rm = d_Rmax + l.off;
-            const float margin = (10.0f * std::sqrt(2.0f)) * (float)l.sigma_size; // descriptor window half width, M-LDB
-            const int4 win = det_window(l);
-            auto strip_grid = [&](int ow, int sh) {
-                const int strips = ((l.w + ow - 1) / ow) * ((l.h + sh - 1) / sh);
-                return dim3(8 * (((strips + 3) / 4 + 7) / 8), 1, B);
-            };
-            const bool det_strip = det_strips && strips_pay(l, force_det_strips);
-            if (det_strip && l.sigma_size == 2)
-                hipLaunchKernelGGL((det_strip_kernel<2>), strip_grid(det_strip_geom<2>::OW, det_strip_geom<2>::H), dim3(256), 0, st, lxy, img_stride, ld, rm, l.w,
-                                   l.h, dthreshold, d_tile_counts, l.tile_off, n_tiles, win, d_mask + l.mask_off, mask_stride);
-            else if (det_strip && l.sigma_size == 3)
-                hipLaunchKernelGGL((det_strip_kernel<3>), strip_grid(det_strip_geom<3>::OW, det_strip_geom<3>::H), dim3(256), 0, st, lxy, img_stride, ld, rm, l.w,
-                                   l.h, dthreshold, d_tile_counts, l.tile_off, n_tiles, win, d_mask + l.mask_off, mask_stride);
-            else if (det_strip)
-                hipLaunchKernelGGL((det_strip_kernel<4>), strip_grid(det_strip_geom<4>::OW, det_strip_geom<4>::H), dim3(256), 0, st, lxy, img_stride, ld, rm, l.w,
-                                   l.h, dthreshold, d_tile_counts, l.tile_off, n_tiles, win, d_mask + l.mask_off, mask_stride);
-            else if (l.sigma_size == 2)
-                hipLaunchKernelGGL((det_maxima_kernel<2>), det_tiles(l.w, l.h), dim3(256), 0, st, lxy, img_stride, ld, rm, l.w,
-                                   l.h, dthreshold, d_tile_counts, l.tile_off, n_tiles, margin, d_mask + l.mask_off, mask_stride);
-            else if (l.sigma_size == 3)
-                hipLaunchKernelGGL((det_maxima_kernel<3>), det_tiles(l.w, l.h), dim3(256), 0, st, lxy, img_stride, ld, rm, l.w,
-                                   l.h, dthreshold, d_tile_counts, l.tile_off, n_tiles, margin, d_mask + l.mask_off, mask_stride);
-            else
-                hipLaunchKernelGGL((det_maxima_kernel<4>), det_tiles(l.w, l.h), dim3(256), 0, st, lxy, img_stride, ld, rm, l.w,
-                                   l.h, dthreshold, d_tile_counts, l.tile_off, n_tiles, margin, d_mask + l.mask_off, mask_stride);
-        }
-    }
-    if (const char *dump = std::getenv("OCHIP_DUMP_PLANES"))
-    {
-        // the planes' seam (tests/test_gpu_akaze_planes.py): the first image's Lt and (Lx, Ly) pyramids and its contrast factor
-        // as raw float files <prefix>_lt.f32 / _lxy.f32 / _kc.f32
-        std::vector<float> hl(img_stride), hx(2 * img_stride), hk(1);
-        OCHIP_HIP(ctx, ochip_stream_wait(ctx, st));
-        OCHIP_HIP(ctx, hipMemcpy(hl.data(), d_Lt, img_stride * 4, hipMemcpyDeviceToHost));
-        OCHIP_HIP(ctx, hipMemcpy(hx.data(), d_Lxy, img_stride * 8, hipMemcpyDeviceToHost));
-        OCHIP_HIP(ctx, hipMemcpy(hk.data(), d_kc, 4, hipMemcpyDeviceToHost));
-        const std::vector<float> *planes[3] = {&hl, &hx, &hk};
-        const char *suffix[3] = {"_lt.f32", "_lxy.f32", "_kc.f32"};
-        for (int which = 0; which < 3; which++)
-            if (FILE *f = std::fopen((std::string(dump) + suffix[which]).c_str(), "wb"))
-            {
-                std::fwrite(planes[which]->data(), 4, planes[which]->size(), f);
-                std::fclose(f);
-            }
-    }
-    hipLaunchKernelGGL(scan_tiles_kernel, dim3(B), dim3(256), 0, st, (const unsigned int *)d_tile_counts,
-                       (const unsigned int *)d_tile_seq, n_tiles, d_tile_base, d_ncand);
-    hipLaunchKernelGGL(collect_tiles_kernel, dim3((n_tiles + 4 * COLLECT_TPW - 1) / (4 * COLLECT_TPW), 1, B), dim3(256), 0, st, (const float *)d_Rmax,
-                       (const float2 *)d_Fit, img_stride,
-                       (const unsigned long long *)d_mask, mask_stride, LV, (const unsigned int *)d_tile_base, n_tiles, d_cands,
-                       max_cands, (const unsigned int *)d_tile_counts);
+    working_image_enqueue(st, b.bgr, b.gray, b.img, B, width, height, W, H, ws.scale, &tabs->rz);
+    OCHIP_TRY(scale_space_enqueue(ctx, T, P, b, dump));
+    detect_enqueue(st, T, P, b);
+    if (dump)
+        OCHIP_TRY(dump_planes(ctx, T, b, dump));
     std::vector<unsigned int> ncand(B);
-    OCHIP_HIP(ctx, hipMemcpyAsync(ncand.data(), d_ncand, B * 4, hipMemcpyDeviceToHost, st));
+    OCHIP_HIP(ctx, hipMemcpyAsync(ncand.data(), b.ncand, B * 4, hipMemcpyDeviceToHost, st));
     OCHIP_HIP(ctx, ochip_stream_wait(ctx, st));
     ctx->akaze_readbacks.fetch_add(1, std::memory_order_release); // the scale space is behind this sequence (ochip_akaze_progress)
-    unsigned int max_n = 0;
-    for (uint32_t b = 0; b < B; b++)
+    unsigned int max_n = 0, max_live = 0;
+    for (uint32_t i = 0; i < B; i++)
     {
-        if (ncand[b] > max_cands)
-            return ochip_fail(ctx, OCHIP_ENOMEM, "image %u has %u extrema candidates; raise max_kp (candidate capacity %u)", b,
-                              ncand[b], max_cands);
-        max_n = std::max(max_n, ncand[b]);
+        if (ncand[i] > b.max_cands)
+            return ochip_fail(ctx, OCHIP_ENOMEM, "image %u has %u extrema candidates; raise max_kp (candidate capacity %u)", i, ncand[i],
+                              b.max_cands);
+        max_n = std::max(max_n, ncand[i]);
     }
-    const int xcd_remap = 2; // groups of 64 list neighbours per XCD (see xcd_contiguous; 0, 1 and 3 measured slower)
     if (max_n > 0)
     {
-        OCHIP_HIP(ctx, hipMemsetAsync(d_vmask, 0, (size_t)B * mask_stride * 8, st));
-        const dim3 per_cand((max_n + 255) / 256, 1, B);
-        // test hooks: the suppression's code for radii beyond the default scale space's / its lists beyond their LDS part
-        const int sup_hooks = (ochip_test_hook("sup_generic") ? 1 : 0) | (ochip_test_hook("sup_small_lists") ? 2 : 0);
-        unsigned int *d_sup_stats = nullptr;
-        if (ochip_verbose("extract"))
-        {
-            AK(mem.alloc<unsigned int>(&d_sup_stats, (size_t)3 * B * LV.n * 3));
-            OCHIP_HIP(ctx, hipMemsetAsync(d_sup_stats, 0, (size_t)3 * B * LV.n * 3 * 4, st));
-        }
-        OCHIP_HIP(ctx, hipMemsetAsync(d_kmask, 0, (size_t)B * sup_stride * 8, st));
-        OCHIP_HIP(ctx, hipMemsetAsync(d_pmask, 0, (size_t)B * sup_stride * 8, st));
-        OCHIP_HIP(ctx, hipMemsetAsync(d_waiting, 0, (size_t)B * LV.n * 4, st));
-        hipLaunchKernelGGL(suppress_level_first_kernel, dim3(B), dim3(64), 0, st, (const unsigned int *)d_ncand, max_cands, LV,
-                           (const unsigned int *)d_tile_base, (const unsigned int *)d_tile_seq, n_tiles, d_level_first);
-        // (64 x 8-pixel groups: the grid covers the largest level, a level per blockIdx.y)
-        hipLaunchKernelGGL(suppress_tiles_kernel, dim3((unsigned int)((LV.l[0].tiles_x * ((LV.l[0].h + 7) / 8) + 255) / 256), LV.n, B),
-                           dim3(256), 0, st, (const unsigned long long *)d_mask, mask_stride, d_rmask, sup_stride, LV);
-#define SUP_PASS(PASS, LEVELS)                                                                                                                 \
-    hipLaunchKernelGGL(suppress_round0_kernel<PASS>, per_cand, dim3(256), 0, st, (const cand_t *)d_cands, (const unsigned int *)d_ncand,       \
-                       max_cands, (const float *)d_Rmax, img_stride, (const unsigned long long *)d_rmask, d_pmask, d_kmask, sup_stride, LV,    \
-                       (const unsigned int *)d_level_first, d_turns, d_waiting, (const unsigned int *)d_found, sup_hooks);                     \
-    hipLaunchKernelGGL(suppress_rounds_kernel<PASS>, dim3(B, (LEVELS)), dim3(SUP_THREADS), 0, st, (const unsigned int *)d_ncand, max_cands,    \
-                       (const float *)d_Rmax, img_stride, d_pmask, d_kmask, sup_stride, LV, (const unsigned int *)d_level_first, d_turns,      \
-                       d_waiting, d_sup_stats, sup_hooks)
-#define SUP_WINDOWS(PASS)                                                                                                                      \
-    OCHIP_HIP(ctx, hipMemsetAsync(d_rmask, 0, (size_t)B * sup_stride * 8, st));                                                                \
-    hipLaunchKernelGGL(suppress_window_kernel<PASS>, per_cand, dim3(256), 0, st, (const cand_t *)d_cands, (const unsigned int *)d_ncand,       \
-                       max_cands, (const unsigned long long *)d_kmask, d_rmask, sup_stride, LV, d_found, sup_hooks)
-        SUP_PASS(1, LV.n);
-        if (LV.n > 1)
-        {
-            SUP_WINDOWS(2);
-            SUP_PASS(2, LV.n - 1);
-            SUP_WINDOWS(3);
-            SUP_PASS(3, LV.n - 1);
-        }
-#undef SUP_WINDOWS
-        hipLaunchKernelGGL(suppress_dead_kernel, per_cand, dim3(256), 0, st, (const cand_t *)d_cands, (const unsigned int *)d_ncand,
-                           max_cands, (const unsigned long long *)d_kmask, sup_stride, LV, d_dead);
-        if (d_sup_stats)
-        {
-            std::vector<unsigned int> hs((size_t)3 * B * LV.n * 3);
-            OCHIP_HIP(ctx, hipMemcpyAsync(hs.data(), d_sup_stats, hs.size() * 4, hipMemcpyDeviceToHost, st));
-            OCHIP_HIP(ctx, ochip_stream_wait(ctx, st));
-            for (int pass = 0; pass < 3; pass++)
-            {
-                std::string line;
-                for (int i = 0; i < LV.n; i++)
-                {
-                    unsigned int rounds = 0, ticks = 0, pts = 0;
-                    for (uint32_t b = 0; b < B; b++)
-                    {
-                        const unsigned int *o = &hs[(((size_t)pass * B + b) * LV.n + i) * 3];
-                        rounds = std::max(rounds, o[0]), ticks = std::max(ticks, o[1]), pts = std::max(pts, o[2]);
-                    }
-                    char buf[64];
-                    std::snprintf(buf, sizeof buf, " %u/%.0fus/%u", rounds, ticks * 0.01, pts);
-                    line += buf;
-                }
-                std::fprintf(stderr, "[ochip extract] suppression pass %d, per level max over %u images of rounds/time/points:%s\n", pass + 1, B,
-                             line.c_str());
-            }
-        }
-        // the survivors in list order, then the descriptor over those only (slots it never visits stay invalid)
-        hipLaunchKernelGGL(live_list_kernel, dim3(B), dim3(SCAN_THREADS), 0, st, (const unsigned char *)d_dead, (const unsigned int *)d_ncand,
-                           max_cands, d_live, d_nlive);
-        OCHIP_HIP(ctx, hipMemsetAsync(d_valid, 0, (size_t)B * max_cands, st));
-        // the grid covers the longest list of survivors, not of candidates (a third to a half of the workgroups would
-        // find nothing to do, and an empty workgroup still takes a slot with its 22 KB of LDS for a microsecond): one more
-        // 400-byte read-back per chunk, hidden under the other launch sequences in flight
+        OCHIP_TRY(suppress_enqueue(ctx, mem, T, b, max_n, sup_hooks, verbose));
+        // the descriptor's grid covers the longest list of survivors: one more 400-byte read-back per chunk, hidden under the
+        // other launch sequences in flight
         std::vector<unsigned int> nlive(B);
-        OCHIP_HIP(ctx, hipMemcpyAsync(nlive.data(), d_nlive, B * 4, hipMemcpyDeviceToHost, st));
+        OCHIP_HIP(ctx, hipMemcpyAsync(nlive.data(), b.nlive, B * 4, hipMemcpyDeviceToHost, st));
         OCHIP_HIP(ctx, ochip_stream_wait(ctx, st));
-        const unsigned int max_live = *std::max_element(nlive.begin(), nlive.end());
-        // (capping the workgroups a CU holds with unused dynamic LDS, to leave wave slots to the other sequences' HBM-bound
-        // kernels beside this L2-bound one, was measured: 3 120 images/s with none, 3 100 / 2 940 / 2 830 at 4 / 3 / 2 per CU)
-        if (max_live > 0)
-        {
-            hipLaunchKernelGGL(describe3_kernel, dim3(512 * (((max_live + DESC_WPB - 1) / DESC_WPB + 511) / 512), 1, B), dim3(64 * DESC_WPB), 0, st,
-                               (const cand_t *)d_cands, (const unsigned int *)d_nlive, max_cands, (const unsigned int *)d_live,
-                               (const float *)d_Lt, (const float2 *)d_Lxy, img_stride, LV, dfactor,
-                               (const gather_tab *)d_gtab, d_kp, d_desc, d_valid, xcd_remap, d_vmask,
-                               mask_stride);
-        }
+        max_live = *std::max_element(nlive.begin(), nlive.end());
     }
-    if (max_n > 0)
-    {
-        hipLaunchKernelGGL(rank_scan_kernel, dim3(B), dim3(SCAN_THREADS), 0, st, (const unsigned long long *)d_vmask, mask_stride, d_wbase,
-                           d_counts);
-        hipLaunchKernelGGL(compact_ordered_kernel, dim3((max_n + 255) / 256, 1, B), dim3(256), 0, st,
-                           (const unsigned char *)d_valid, (const cand_t *)d_cands, (const unsigned int *)d_ncand, max_cands,
-                           (const unsigned long long *)d_vmask, (const unsigned int *)d_wbase, mask_stride, LV,
-                           (const float *)d_kp, (const unsigned long long *)d_desc, d_kpc, d_descc, max_kp);
-    }
-    else
-        OCHIP_HIP(ctx, hipMemsetAsync(d_counts, 0, B * 4, st));
+    OCHIP_TRY(describe_enqueue(ctx, T, b, max_n, max_live));
     ochip_prof_end(ctx, OCHIP_K_AKAZE, e0, e1);
     OCHIP_HIP(ctx, hipGetLastError());
     // ---- results: the per-image counts first, then exactly the compacted keypoints and descriptors, straight
     // into the caller's arrays (page-locked ones from ochip_host_alloc make these copies run at link speed)
-    OCHIP_HIP(ctx, hipMemcpyAsync(counts, d_counts, B * 4, hipMemcpyDeviceToHost, st));
+    OCHIP_HIP(ctx, hipMemcpyAsync(counts, b.counts, B * 4, hipMemcpyDeviceToHost, st));
     OCHIP_HIP(ctx, ochip_stream_wait(ctx, st));
+    int rc = OCHIP_OK;
     uint32_t most = 0;
-    for (uint32_t b = 0; b < B && rc == OCHIP_OK; b++)
+    for (uint32_t i = 0; i < B; i++)
     {
-        if (counts[b] > max_kp)
+        if (counts[i] > max_kp)
         {
-            rc = ochip_fail(ctx, OCHIP_ENOMEM, "image %u has %u keypoints, more than max_kp = %u", b, counts[b], max_kp);
+            rc = ochip_fail(ctx, OCHIP_ENOMEM, "image %u has %u keypoints, more than max_kp = %u", i, counts[i], max_kp);
             break;
         }
-        most = std::max(most, counts[b]);
+        most = std::max(most, counts[i]);
     }
     if (rc == OCHIP_OK && lists)
         // the tail of extract_features prepared on the device (features.hip): records, suppression flags, what the
         // host's sort needs - instead of the raw keypoint arrays
-        rc = ochip::feature_lists_enqueue(ctx, mem, B, max_kp, d_kpc, d_descc, d_counts, most, W, H, scale, nms_radius, lists);
+        rc = ochip::feature_lists_enqueue(ctx, mem, B, max_kp, b.kpc, b.descc, b.counts, most, W, H, ws.scale, nms_radius, lists);
     else if (rc == OCHIP_OK && most > 0)
     {
         // one strided copy per array instead of one per image and array (2 x 100 launches per chunk): every image's row is
         // copied up to the longest list of the chunk - a few per cent more bytes, the counts say where each list ends
-        OCHIP_HIP(ctx, hipMemcpy2DAsync(kp6, (size_t)max_kp * 24, d_kpc, (size_t)max_kp * 24, (size_t)most * 24, B, hipMemcpyDeviceToHost, st));
-        OCHIP_HIP(ctx, hipMemcpy2DAsync(desc, (size_t)max_kp * 64, d_descc, (size_t)max_kp * 64, (size_t)most * 64, B, hipMemcpyDeviceToHost, st));
+        OCHIP_HIP(ctx, hipMemcpy2DAsync(kp6, (size_t)max_kp * 24, b.kpc, (size_t)max_kp * 24, (size_t)most * 24, B, hipMemcpyDeviceToHost, st));
+        OCHIP_HIP(ctx, hipMemcpy2DAsync(desc, (size_t)max_kp * 64, b.descc, (size_t)max_kp * 64, (size_t)most * 64, B, hipMemcpyDeviceToHost, st));
     }
     if (rc != OCHIP_OK)
-        for (uint32_t b = 0; b < B; b++)
-            counts[b] = 0;
+        for (uint32_t i = 0; i < B; i++)
+            counts[i] = 0;
     (void)ochip_stream_wait(ctx, st);
     mem.release();
     return rc;
-#undef AK
 }
 
 } // namespace

@@ -25,8 +25,8 @@
 // next survey one by one - the default - or all together when the survey before has finished), OCHIP_EXTRACT_STAGGER=1 (a launch
 // sequence waits with its chunk while another one of its survey is in front of its first host read-back), OCHIP_EXTRACT_PRIORITY=0
 // (host/extract_features.cpp: the launch sequences on the root context and its first siblings at the default stream priority
-// instead of sibling contexts of their own whose streams have the lowest), OCHIP_DUMP_PLANES=<prefix> (akaze.hip, read at every
-// call: the first image's Lt and (Lx, Ly) pyramids and its contrast factor as <prefix>_lt.f32 / _lxy.f32 / _kc.f32 - the seam of
+// instead of sibling contexts of their own whose streams have the lowest), OCHIP_DUMP_PLANES=<prefix> (akaze.hip, read once at the top
+// of every call: the first image's Lt and (Lx, Ly) pyramids and its contrast factor as <prefix>_lt.f32 / _lxy.f32 / _kc.f32 - the seam of
 // tests/test_gpu_akaze_planes.py)
 #pragma once
 
