@@ -1,8 +1,8 @@
 """SURVEY.md section 8 row a9 on the device: ransac<fundamental_matrix_model> / ransac<essential_matrix_model>
-(csrc/ransac.hip: ransac_epipolar_kernel - 8-point / 5-point fits through a restated JacobiSVD, Sampson error, DEGENSAC,
-the shared RANSAC loop) against the oracle's restatement bit for bit - inlier sets, iteration counts, scores, matrices - on
-the reference's unit-test fixtures (test/test_ransac_unit.cpp:58-347) and benchmark scenes (test_ransac_benchmark.cpp:263-301),
-and at the reference's own thresholds."""
+(csrc/ransac_epipolar.hip: ransac_epipolar_kernel - 8-point / 5-point fits through a restated JacobiSVD, Sampson error,
+DEGENSAC; the loop's shared parts are csrc/ransac_loop.hpp's) against the oracle's restatement bit for bit - inlier sets,
+iteration counts, scores, matrices - on the reference's unit-test fixtures (test/test_ransac_unit.cpp:58-347) and benchmark
+scenes (test_ransac_benchmark.cpp:263-301), and at the reference's own thresholds."""
 import numpy as np
 import pytest
 
@@ -71,7 +71,15 @@ def test_fundamental_benchmarks(ctx, oracle, n_in, n_out, planar, prec, rec):
 def test_random_scenes_with_quality(ctx, oracle, seed):
     """general two-view scenes with outliers and match qualities (PROSAC order with ties): both models, long runs"""
     rng = np.random.default_rng(seed)
-    n_in, n_out = 150, 90
+    rays, quality = _two_view_scene(rng, 150, 90)
+    for model in (0, 1):
+        _same(ctx, oracle, model, rays)
+        s, M, inl, it = _same(ctx, oracle, model, rays, quality)
+        assert it >= 20
+
+
+def _two_view_scene(rng, n_in, n_out):
+    """n_in correspondences of a general two-view scene with 1e-3 noise, n_out random ones, shuffled; match qualities"""
     X = np.concatenate([rng.uniform(-2, 2, (n_in, 2)), rng.uniform(4, 9, (n_in, 1))], axis=1)
     ang = 0.15
     R = np.array([[np.cos(ang), 0, np.sin(ang)], [0, 1, 0], [-np.sin(ang), 0, np.cos(ang)]])
@@ -86,7 +94,19 @@ def test_random_scenes_with_quality(ctx, oracle, seed):
     rays = np.concatenate([np.concatenate([x1, x2], axis=1), np.concatenate([o1, o2], axis=1)])
     rays = rays[rng.permutation(len(rays))]
     quality = rng.integers(1, 60, len(rays)) / 486.0            # many ties, as Hamming distances make them
-    for model in (0, 1):
-        _same(ctx, oracle, model, rays)
-        s, M, inl, it = _same(ctx, oracle, model, rays, quality)
-        assert it >= 20
+    return rays, quality
+
+
+@pytest.mark.parametrize("with_quality", [False, True])
+@pytest.mark.parametrize("M", ["K", 9, 21, 63, 64, 65, 127, 128, 129])
+@pytest.mark.parametrize("model", [0, 1])
+def test_walk_chunk_boundaries(ctx, oracle, model, M, with_quality):
+    """The scoring walk takes the matches 64 at a time and asks for the next 64 while it works on these: match counts at the
+    sample size (8 / 5), inside the first chunk, and one below, at and one above the ends of the first and second chunk;
+    5/8 inliers, without and with qualities.  Past 20 matches the SPRT exit is live, so those runs must be real ones.
+    (A case is one wavefront's whole search, 1 800 to 10 000 iterations with a Jacobi SVD each: up to 6 s.)"""
+    M = (8, 5)[model] if M == "K" else M
+    n_in = (5 * M + 4) // 8
+    rays, quality = _two_view_scene(np.random.default_rng(1000 + M), n_in, M - n_in)
+    s, F, inl, it = _same(ctx, oracle, model, rays, quality if with_quality else None)
+    assert M < 21 or it >= 20

@@ -1,4 +1,4 @@
-"""The three homography factorisations of the link stage on the device (csrc/ransac.hip: the wave-cooperative 9 x 9
+"""The three homography factorisations of the link stage on the device (csrc/homography_fit.hpp: the wave-cooperative 9 x 9
 full_piv_lu_solve9, the regenerating regen_lu_solve9 of the tall system, the fast-forward's lane_fit) at the edges the
 pipeline tests never reach - inlier counts at the 64-lane edges and below five, flags in the last chunks, sibling pivot
 rows, exact ties, rank-deficient and out-of-range systems, NaN coordinates (tests/homography_fit_fixtures.py).
