@@ -63,9 +63,13 @@ OCHIP_OL double lab_f(double t)
 OCHIP_OL void lab_from_bgr(const lab_tables &T, const uint8_t bgr[3], double lab[3])
 {
     const double B = T.lin[bgr[0]], G = T.lin[bgr[1]], R = T.lin[bgr[2]];
-    const double X = (0.412453 * R + 0.357580 * G + 0.180423 * B) / 0.950456;
-    const double Y = 0.212671 * R + 0.715160 * G + 0.072169 * B;
-    const double Z = (0.019334 * R + 0.119193 * G + 0.950227 * B) / 1.088754;
+    // Each row of the matrix sums to its white (0.412453 + 0.357580 + 0.180423 = 0.950456, .. = 1, .. = 1.088754), so
+    // X / Xn, Y and Z / Zn are G plus multiples of R - G and B - G: a grey (R = G = B) has the three equal to the bit, and
+    // a = b = 0 exactly, where the plain row sums left them at 1e-13.
+    const double dR = R - G, dB = B - G;
+    const double X = G + (0.412453 / 0.950456) * dR + (0.180423 / 0.950456) * dB;
+    const double Y = G + 0.212671 * dR + 0.072169 * dB;
+    const double Z = G + (0.019334 / 1.088754) * dR + (0.950227 / 1.088754) * dB;
     const double fx = lab_f(X), fy = lab_f(Y), fz = lab_f(Z);
     lab[0] = Y > 0.008856 ? 116.0 * fy - 16.0 : 903.3 * Y;
     lab[1] = 500.0 * (fx - fy);

@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 
 from layers_fixtures import DISTORTED, expected_layers, knn_agrees, four_camera_scene, plan_with_gsd
+from layers_oracle_fixtures import blend_weight_f32, correspondences, ld, mean_bound
 from ortho_fixtures import DOWN, make_graph, project
 from opencalibration_amd import host
 
@@ -61,14 +62,7 @@ def test_sample_fields_exact_float32():
         r = np.clip(np.sqrt(((x - hw) / hw) ** 2 + ((y - hh) / hh) ** 2) * 0.7071067811865475, 0, 1)
         nx = np.clip(f32((x - hw) / hw), f32(-1), f32(1))
         ny = np.clip(f32((y - hh) / hh), f32(-1), f32(1))
-        px, py = f32(x), f32(y)
-        hwf, hhf = f32(w) * f32(0.5), f32(h) * f32(0.5)
-        edge = min(px, f32(w) - f32(1) - px, py, f32(h) - f32(1) - py)
-        ew = max(min(f32(edge / hwf), f32(1)), f32(0.001))
-        cx, cy = f32((px - hwf) / hwf), f32((py - hhf) / hhf)
-        cw = f32(1) - f32(0.5) * min(f32(np.sqrt(f32(cx * cx + cy * cy))), f32(1))
-        prox = f32(1) / f32(f32(1) + f32(d * d))
-        wt = f32(f32(ew * cw) * prox)
+        wt = blend_weight_f32(f32(x), f32(y), w, h, d)
         assert got[0] == f32(r) and got[1] == nx and got[2] == ny and got[3] == wt
 
 
@@ -198,9 +192,13 @@ def test_correspondences_cpu_route(scene, tile):
     key = np.stack([cor["row"] // tile, cor["col"] // tile, cor["row"] % tile, cor["col"] % tile, cor["layer_a"],
                     cor["layer_b"]], 1)
     assert np.all(np.diff(np.lexsort(key.T[::-1])) == 1)
-    # an isolated centre sample's Lab is its own colour's float Lab
-    lab = host.lab_convert(out["bgra"][cor["layer_a"], cor["row"], cor["col"], :3], "bgr2labf")
-    assert np.all(np.abs(cor["lab_a"] - lab).max(1)[: len(lab)] < 200)
+    # each mean against the long-double mean of the window's reference Lab, within float summation's forward bound
+    exp = correspondences(out["bgra"], out["camera_id"], tile, 2, sub)
+    assert [(e["row"], e["col"]) for e in exp] == list(zip(cor["row"].tolist(), cor["col"].tolist()))
+    for side in "ab":
+        mean = np.array([e["mean_" + side] for e in exp])
+        bound = np.array([mean_bound(e["count"], e["abs_" + side]) for e in exp])
+        assert np.all(np.abs(ld(cor["lab_" + side]) - mean) <= bound)
 
 
 def test_tile_size_moves_the_boundary_set(scene):
