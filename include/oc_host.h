@@ -790,6 +790,13 @@ extern "C"
 #define OCH_GEOTIFF_MAX_SIDE OCHIP_GEOTIFF_MAX_SIDE
     typedef struct och_geotiff och_geotiff;
     int och_geotiff_create(ochip_ctx *ctx, int kind, int64_t width, int64_t height, int sparse, och_geotiff **out);
+    /* ochip_geotiff_create_layered over both routes: the layers (kind 2) and cameras (kind 3) rasters of num_layers layers,
+     * layer-major bands in, pixel-interleaved tiles out */
+#define OCH_GEOTIFF_LAYERS8 OCHIP_GEOTIFF_LAYERS8
+#define OCH_GEOTIFF_CAMERAS32 OCHIP_GEOTIFF_CAMERAS32
+#define OCH_GEOTIFF_MAX_LAYERS OCHIP_GEOTIFF_MAX_LAYERS
+    int och_geotiff_create_layered(ochip_ctx *ctx, int kind, int num_layers, int64_t width, int64_t height, int sparse,
+                                   och_geotiff **out);
     int och_geotiff_feed(och_geotiff *e, int64_t row0, int64_t rows, const void *pixels, int on_device);
     int och_geotiff_payloads(och_geotiff *e, const uint8_t *payloads, int64_t n);
     int och_geotiff_collect(och_geotiff *e, uint8_t *buf /* or NULL */, uint64_t cap, uint64_t *bytes,
@@ -850,6 +857,8 @@ extern "C"
     typedef struct och_geotiff_reader och_geotiff_reader;
     int och_geotiff_reader_create(ochip_ctx *ctx, int samples, int is_float, int64_t width, int64_t height, int tile_w, int tile_h,
                                   int predictor, uint64_t scratch_budget, och_geotiff_reader **out);
+    int och_geotiff_reader_create_layered(ochip_ctx *ctx, int kind, int num_layers, int64_t width, int64_t height, int tile_w,
+                                          int tile_h, int predictor, uint64_t scratch_budget, och_geotiff_reader **out);
     int och_geotiff_reader_inflate(och_geotiff_reader *r, int64_t n, const uint8_t *streams, const uint64_t *offsets /* [n + 1] */,
                                    const uint64_t *expect /* [n] */, uint8_t *out, uint64_t out_cap, int32_t *status /* [n] */,
                                    uint64_t *bytes /* [n] */);

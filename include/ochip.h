@@ -1169,6 +1169,21 @@ extern "C"
     int ochip_geotiff_finish(ochip_geotiff *e);
     void ochip_geotiff_destroy(ochip_geotiff *e);
 
+    /* The layers and cameras rasters between the layer pass and the blend (the reference's createMultiBandGeoTIFF,
+     * src/ortho/ortho.cpp:969-1008): a writer as above whose pixel holds num_layers layers, 1 or 2.
+     * kind 2: B G R A bytes per layer, a pixel of 4 num_layers bytes, the predictor over bytes; kind 3: the low and the
+     * high 32-bit word of each layer's 64-bit node id, a pixel of 8 num_layers bytes, the predictor over 32-bit words.
+     * feed takes a band as ortho_layers leaves it, layer-major: [num_layers][rows][width] of 4 bytes, respectively of one
+     * little-endian uint64; the tiles are pixel-interleaved, [row][col][layer][sample].  A tile's payload has
+     * 262 144 x the pixel's bytes, which is also what payloads takes, and no stream exceeds that plus 5 bytes per
+     * 65 535 and 6.  sparse leaves out an all-zero tile of either kind.  Everything else is the writer above; the
+     * refusals name ochip_geotiff_create_layered. */
+#define OCHIP_GEOTIFF_LAYERS8 2
+#define OCHIP_GEOTIFF_CAMERAS32 3
+#define OCHIP_GEOTIFF_MAX_LAYERS 2
+    int ochip_geotiff_create_layered(ochip_ctx *ctx, int kind, int num_layers, int64_t width, int64_t height, int sparse,
+                                     ochip_geotiff **out);
+
     /* ---- PNG files of thumbnails and previews (opencalibration_amd/csrc/png.hip, the rules in csrc/png_rules.hpp; the
      *      reference's cv::imencode(".png") of a node's thumbnail, src/io/serialize_MeasurementGraph.cpp:260-267,
      *      src/ortho/thumbnail_encode.hpp, and thumb.png) ----
@@ -1222,6 +1237,13 @@ extern "C"
     typedef struct ochip_geotiff_reader ochip_geotiff_reader;
     int ochip_geotiff_reader_create(ochip_ctx *ctx, int samples, int is_float, int64_t width, int64_t height, int tile_w,
                                     int tile_h, int predictor, uint64_t scratch_budget, ochip_geotiff_reader **out);
+    /* The reader of a layers (kind OCHIP_GEOTIFF_LAYERS8) or cameras (OCHIP_GEOTIFF_CAMERAS32) raster of num_layers layers,
+     * 1 or 2: the tiles are pixel-interleaved, 4 num_layers bytes or 2 num_layers 32-bit words a
+     * pixel, Predictor 2 at that stride over bytes respectively words; read places layer-major, as ortho_blend takes its
+     * layers: [num_layers][rows][width] of 4 bytes B G R A, respectively of one little-endian uint64, in host or device
+     * memory.  A tile without a stream is a sparse one and reads as zeros.  Everything else is the reader above. */
+    int ochip_geotiff_reader_create_layered(ochip_ctx *ctx, int kind, int num_layers, int64_t width, int64_t height, int tile_w,
+                                            int tile_h, int predictor, uint64_t scratch_budget, ochip_geotiff_reader **out);
     int ochip_geotiff_reader_inflate(ochip_geotiff_reader *r, int64_t n, const uint8_t *streams, const uint64_t *offsets /* [n + 1] */,
                                      const uint64_t *expect /* [n] */, uint8_t *out, uint64_t out_cap, int32_t *status /* [n] */,
                                      uint64_t *bytes /* [n] */);

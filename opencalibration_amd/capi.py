@@ -58,9 +58,9 @@ EXPORTS = [
     "ochip_jpeg_create", "ochip_jpeg_feed", "ochip_jpeg_pending", "ochip_jpeg_collect", "ochip_jpeg_finish", "ochip_jpeg_destroy",
     "ochip_jpeg_decoder_create", "ochip_jpeg_decoder_decode", "ochip_jpeg_decoder_destroy",
     "ochip_geotiff_create", "ochip_geotiff_feed", "ochip_geotiff_payloads", "ochip_geotiff_collect", "ochip_geotiff_finish",
-    "ochip_geotiff_destroy",
+    "ochip_geotiff_destroy", "ochip_geotiff_create_layered",
     "ochip_geotiff_reader_create", "ochip_geotiff_reader_inflate", "ochip_geotiff_reader_read", "ochip_geotiff_reader_launches",
-    "ochip_geotiff_reader_destroy",
+    "ochip_geotiff_reader_destroy", "ochip_geotiff_reader_create_layered",
     "ochip_png_encoder_create", "ochip_png_encoder_encode", "ochip_png_encoder_destroy",
 ]
 
@@ -327,6 +327,7 @@ def load():
         L.ochip_jpeg_decoder_destroy.argtypes = [vp]
         L.ochip_jpeg_decoder_destroy.restype = None
         L.ochip_geotiff_create.argtypes = [vp, i32, C.c_int64, C.c_int64, i32, C.POINTER(vp)]
+        L.ochip_geotiff_create_layered.argtypes = [vp, i32, i32, C.c_int64, C.c_int64, i32, C.POINTER(vp)]
         L.ochip_geotiff_feed.argtypes = [vp, C.c_int64, C.c_int64, vp, i32]
         L.ochip_geotiff_payloads.argtypes = [vp, vp, C.c_int64]
         L.ochip_geotiff_collect.argtypes = [vp, vp, u64, C.POINTER(u64), vp, u64, C.POINTER(u64)]
@@ -334,6 +335,7 @@ def load():
         L.ochip_geotiff_destroy.argtypes = [vp]
         L.ochip_geotiff_destroy.restype = None
         L.ochip_geotiff_reader_create.argtypes = [vp, i32, i32, C.c_int64, C.c_int64, i32, i32, i32, u64, C.POINTER(vp)]
+        L.ochip_geotiff_reader_create_layered.argtypes = [vp, i32, i32, C.c_int64, C.c_int64, i32, i32, i32, u64, C.POINTER(vp)]
         L.ochip_geotiff_reader_inflate.argtypes = [vp, C.c_int64, vp, vp, vp, vp, u64, vp, vp]
         L.ochip_geotiff_reader_read.argtypes = [vp, C.c_int64, vp, vp, C.c_int64, C.c_int64, vp, i32, C.POINTER(C.c_int64)]
         L.ochip_geotiff_reader_launches.argtypes = [vp]

@@ -585,6 +585,56 @@ constexpr int STORED_BYTES = (int)stored_bytes(PAYLOAD);
 static_assert(STORED_BLOCKS == 17 && STORED_BYTES == 1048667, "the bound every buffer is sized from");
 constexpr int TILE_SLOT = (STORED_BYTES + 15) / 16 * 16; // a tile's room in a device buffer
 
+// The layers and cameras rasters between the layer pass and the blend (the reference's
+// createMultiBandGeoTIFF, src/ortho/ortho.cpp:969-1008): the same tiles with a wider pixel.  A layers pixel is B G R A of each
+// of its L layers, 4 L bytes; a cameras pixel the low and the high 32-bit word of each layer's 64-bit node id, 8 L bytes.  The
+// raster comes layer-major, [L][rows][width] units of 1 (B G R A) or 2 (an id) 32-bit words; the payload is pixel-interleaved,
+// [row][col][layer][word].  The candidates stay the pixel to the left and the pixel above, so everything above follows from
+// the pixel's bytes alone.
+constexpr int KIND_RGBA8 = 0, KIND_FLOAT32 = 1, KIND_LAYERS8 = 2, KIND_CAMERAS32 = 3;
+constexpr int MAX_LAYERS = 2; // the reference's pipeline never leaves 2; a pixel of 4, 8 or 16 bytes
+
+OCHIP_DF_HD constexpr bool layered_kind(int kind)
+{
+    return kind == KIND_LAYERS8 || kind == KIND_CAMERAS32;
+}
+OCHIP_DF_HD constexpr int unit_words(int kind) // the 32-bit words of one layer's sample of a pixel
+{
+    return kind == KIND_CAMERAS32 ? 2 : 1;
+}
+OCHIP_DF_HD constexpr int pixel_bytes(int kind, int layers) // layers: 1 for the two kinds without layers
+{
+    return 4 * unit_words(kind) * layers;
+}
+OCHIP_DF_HD constexpr bool word_predictor(int kind) // 32-bit differences; else bytes
+{
+    return kind == KIND_FLOAT32 || kind == KIND_CAMERAS32;
+}
+OCHIP_DF_HD constexpr int tile_row_bytes(int px)
+{
+    return TILE * px;
+}
+OCHIP_DF_HD constexpr int tile_payload(int px)
+{
+    return TILE * TILE * px;
+}
+OCHIP_DF_HD constexpr int tile_segments(int px)
+{
+    return tile_payload(px) / SEGMENT;
+}
+OCHIP_DF_HD constexpr int tile_stored_bytes(int px)
+{
+    return (int)stored_bytes((uint64_t)tile_payload(px));
+}
+OCHIP_DF_HD constexpr int tile_slot(int px) // a tile's room in a device buffer
+{
+    return (tile_stored_bytes(px) + 15) / 16 * 16;
+}
+static_assert(tile_payload(PIXEL_BYTES) == PAYLOAD && tile_segments(PIXEL_BYTES) == SEGMENTS && tile_stored_bytes(PIXEL_BYTES) == STORED_BYTES &&
+                  tile_slot(PIXEL_BYTES) == TILE_SLOT && tile_row_bytes(PIXEL_BYTES) == DIST_UP,
+              "the 4-byte pixel is one case of the geometry");
+static_assert(tile_payload(16) == 4 << 20 && tile_row_bytes(16) == 8192 && tile_stored_bytes(16) == 4194304 + 5 * 65 + 6, "two layers of ids");
+
 // The predictor over one tile row of 512 pixels: the first pixel stays, RGBA bytes take the byte 4 before them away, a
 // float's 32-bit pattern the pattern before it.  src: the row's pixels as 32-bit words, `valid` of them real, zeros behind.
 OCHIP_DF_HD uint32_t predict_word(uint32_t cur, uint32_t left, bool is_float)
@@ -599,6 +649,12 @@ OCHIP_DF_HD uint32_t predict_word(uint32_t cur, uint32_t left, bool is_float)
 inline void encode_tile(const uint8_t *a, std::vector<uint8_t> &out)
 {
     encode_stream(a, PAYLOAD, DIST_LEFT, DIST_UP, out);
+}
+
+// The same for a tile whose pixel has px bytes; at most tile_stored_bytes(px)
+inline void encode_tile(const uint8_t *a, int px, std::vector<uint8_t> &out)
+{
+    encode_stream(a, (uint64_t)tile_payload(px), px, tile_row_bytes(px), out);
 }
 #endif
 

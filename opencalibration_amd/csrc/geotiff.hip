@@ -13,6 +13,8 @@
 //   gt_emit        a workgroup per block of a deflated tile that fits the slot: emit_segment into the tile's words
 //   gt_stored      the stored form of the tiles that did not shrink
 //   gt_finish      78 9C and the Adler-32 of the deflated tiles; offsets and counts for the host
+// The layers and cameras rasters (section 4.24) take the same pass with a pixel of 8 or 16 bytes: gt_payload_layered
+// interleaves the layer-major rows while it predicts, and the kernels behind it are instantiated per pixel size.
 // and two copies to page-locked memory: the offsets and counts, and as many bytes as the pass before suggests.  A pass writes
 // into one of OUT_SLOTS output slots with an event each; the host reads a slot when a pass needs it again, at collect or at
 // finish - one wait, for the slot's event, and so not for what the caller enqueued on the stream since.
@@ -69,9 +71,68 @@ __global__ __launch_bounds__(THREADS) void gt_payload(const uint32_t *rows, int6
         atomicOr(&nz[tile], 1u);
 }
 
+// The layers and cameras rasters: rows is [L][512][w] samples of U words, layer-major as the layer pass
+// leaves them; the payload is [row][col][layer][word].  A lane takes the 4 / U pixels whose samples of one layer are 16 bytes,
+// predicts them against the same layer of the pixel before, and stores them interleaved: L stores of 16 bytes.  Every index
+// into cur, left and o is a constant once unrolled, so they are registers.
+template <int L, int U>
+__global__ __launch_bounds__(THREADS) void gt_payload_layered(const uint32_t *rows, int64_t w, int vec, int tiles, uint8_t *payload, uint32_t *nz)
+{
+    constexpr int PPT = 4 / U, PER_ROW = TILE / PPT, PX = 4 * L * U; // a lane's pixels, the lanes of a tile row, a pixel's bytes
+    const int tile = blockIdx.y, idx = (int)blockIdx.x * THREADS + (int)threadIdx.x;
+    const int r = idx / PER_ROW, q = idx % PER_ROW;
+    if (tile >= tiles || r >= TILE)
+        return;
+    const int64_t X0 = (int64_t)tile * TILE + q * PPT, row_words = w * U;
+    uint32_t cur[L][4], left[L][U];
+    uint32_t any = 0;
+#pragma unroll
+    for (int l = 0; l < L; l++)
+    {
+        const uint32_t *src = rows + ((size_t)l * TILE + (size_t)r) * (size_t)row_words;
+        if (vec && X0 + PPT <= w)
+        {
+            const uint4 v = *reinterpret_cast<const uint4 *>(src + X0 * U);
+            cur[l][0] = v.x, cur[l][1] = v.y, cur[l][2] = v.z, cur[l][3] = v.w;
+        }
+        else
+        {
+#pragma unroll
+            for (int j = 0; j < 4; j++)
+                cur[l][j] = X0 * U + j < row_words ? src[X0 * U + j] : 0;
+        }
+#pragma unroll
+        for (int u = 0; u < U; u++)
+            left[l][u] = q > 0 && X0 - 1 < w ? src[(X0 - 1) * U + u] : 0;
+        any |= cur[l][0] | cur[l][1] | cur[l][2] | cur[l][3];
+    }
+    uint32_t o[4 * L];
+#pragma unroll
+    for (int p = 0; p < PPT; p++)
+#pragma unroll
+        for (int l = 0; l < L; l++)
+#pragma unroll
+            for (int u = 0; u < U; u++)
+            {
+                const uint32_t c = cur[l][p * U + u], before = p == 0 ? left[l][u] : cur[l][(p - 1) * U + u];
+                o[(p * L + l) * U + u] = q == 0 && p == 0 ? c : predict_word(c, before, U == 2);
+            }
+    uint4 *dst = reinterpret_cast<uint4 *>(payload + (size_t)tile * tile_payload(PX) + (size_t)r * tile_row_bytes(PX) + (size_t)q * 16 * L);
+#pragma unroll
+    for (int k = 0; k < L; k++)
+        dst[k] = make_uint4(o[4 * k], o[4 * k + 1], o[4 * k + 2], o[4 * k + 3]);
+    if (__ballot(any != 0) != 0 && (threadIdx.x & 63) == 0)
+        atomicOr(&nz[tile], 1u);
+}
+
+// The kernels below are instantiated per pixel size: PX = 4 (RGBA8, float32, one layer of colours) is the tile of section 4.19
+// with its distances 4 and 2 048; 8 and 16 are the layered kinds, with the same code and their own constants.
+template <int PX>
 __global__ __launch_bounds__(THREADS) void gt_parse(const uint8_t *payload, const uint32_t *nz, int sparse, int blocks, uint16_t *tok,
                                                      uint32_t *counts, uint32_t *seg_adler)
 {
+    constexpr int PAYLOAD = tile_payload(PX), SEGMENTS = tile_segments(PX), DIST_LEFT = PX, DIST_UP = tile_row_bytes(PX);
+    constexpr int W = PX / 4; // a pixel's words: the word to the left is W words back
     const int b = blockIdx.x, t = threadIdx.x;
     if (b >= blocks)
         return;
@@ -82,7 +143,20 @@ __global__ __launch_bounds__(THREADS) void gt_parse(const uint8_t *payload, cons
     // the lane's two masks at the tile's fixed geometry: whole chunks, the row above in aligned 16-byte loads
     const int P0 = seg * SEGMENT + t * CHUNK;
     const bool has_left = P0 >= DIST_LEFT, has_up = P0 >= DIST_UP;
-    uint32_t prev = has_left ? *reinterpret_cast<const uint32_t *>(a + P0 - DIST_LEFT) : 0;
+    uint32_t prev[W]; // the last W words seen: the pixel before, once unrolled all in registers
+    if constexpr (W == 1)
+        prev[0] = has_left ? *reinterpret_cast<const uint32_t *>(a + P0 - DIST_LEFT) : 0;
+    else if constexpr (W == 2)
+    {
+        const uint2 p = has_left ? *reinterpret_cast<const uint2 *>(a + P0 - DIST_LEFT) : make_uint2(0, 0);
+        prev[0] = p.x, prev[1] = p.y;
+    }
+    else
+    {
+        static_assert(W == 4, "a pixel of 4, 8 or 16 bytes");
+        const uint4 p = has_left ? *reinterpret_cast<const uint4 *>(a + P0 - DIST_LEFT) : make_uint4(0, 0, 0, 0);
+        prev[0] = p.x, prev[1] = p.y, prev[2] = p.z, prev[3] = p.w;
+    }
     uint64_t m_left = 0, m_up = 0;
     uint32_t s1 = 0, s2 = 0;
 #pragma unroll
@@ -96,7 +170,7 @@ __global__ __launch_bounds__(THREADS) void gt_parse(const uint8_t *payload, cons
 #pragma unroll
         for (int k = 0; k < 4; k++)
         {
-            const uint32_t xl = c[k] ^ prev, xu = c[k] ^ u[k];
+            const uint32_t xl = c[k] ^ prev[k % W], xu = c[k] ^ u[k];
 #pragma unroll
             for (int y = 0; y < 4; y++)
             {
@@ -108,20 +182,22 @@ __global__ __launch_bounds__(THREADS) void gt_parse(const uint8_t *payload, cons
                     m_up |= 1ull << j;
                 s1 += byte, s2 += (uint32_t)(CHUNK - j) * byte;
             }
-            prev = c[k];
+            prev[k % W] = c[k];
         }
     }
     if (!has_left) // the tile's first pixel has nothing to its left
-        m_left &= ~0xFull;
+        m_left &= ~((1ull << DIST_LEFT) - 1);
     if (!has_up)
         m_up = 0;
     parse_segment(m_left, m_up, s1, s2, CHUNK, a, (uint32_t)(seg * SEGMENT), SEGMENT, DIST_LEFT, DIST_UP, tok + (size_t)tile * PAYLOAD,
                   counts + (size_t)b * NUM_SYMS, seg_adler + 2 * (size_t)b);
 }
 
+template <int PX>
 __global__ __launch_bounds__(64) void gt_codes(const uint32_t *counts, const uint32_t *nz, int sparse, int blocks, uint32_t *codes,
                                                 uint32_t *header, uint32_t *header_bits, uint32_t *block_bits)
 {
+    constexpr int SEGMENTS = tile_segments(PX);
     const int b = blockIdx.x;
     if (b >= blocks)
         return;
@@ -132,10 +208,12 @@ __global__ __launch_bounds__(64) void gt_codes(const uint32_t *counts, const uin
 }
 
 // state: 0 deflated, 1 stored, 2 left out; count: the stream's bytes; size[tiles] = 0 so that the scan's last output is the total
+template <int PX>
 __global__ __launch_bounds__(THREADS) void gt_tile_sizes(const unsigned long long *block_off, const uint32_t *seg_adler, const uint32_t *nz,
                                                           int sparse, int tiles, uint32_t *state, uint32_t *count, uint32_t *size,
                                                           uint32_t *adler)
 {
+    constexpr int PAYLOAD = tile_payload(PX), SEGMENTS = tile_segments(PX), STORED_BYTES = tile_stored_bytes(PX);
     const int i = (int)blockIdx.x * THREADS + (int)threadIdx.x;
     if (i > tiles)
         return;
@@ -156,11 +234,13 @@ __global__ __launch_bounds__(THREADS) void gt_tile_sizes(const unsigned long lon
     adler[i] = stream_adler(seg_adler + 2 * (size_t)i * SEGMENTS, PAYLOAD);
 }
 
+template <int PX>
 __global__ __launch_bounds__(THREADS) void gt_emit(const uint8_t *payload, const uint16_t *tok, const uint32_t *codes, const uint32_t *header,
                                                     const uint32_t *header_bits, const unsigned long long *block_off,
                                                     const unsigned long long *tile_off, const uint32_t *state, const uint32_t *size,
                                                     int blocks, uint8_t *out, unsigned long long out_cap)
 {
+    constexpr int PAYLOAD = tile_payload(PX), SEGMENTS = tile_segments(PX), DIST_LEFT = PX, DIST_UP = tile_row_bytes(PX);
     const int b = blockIdx.x;
     if (b >= blocks)
         return;
@@ -173,9 +253,11 @@ __global__ __launch_bounds__(THREADS) void gt_emit(const uint8_t *payload, const
                  DIST_LEFT, DIST_UP);
 }
 
+template <int PX>
 __global__ __launch_bounds__(THREADS) void gt_stored(const uint8_t *payload, const unsigned long long *tile_off, const uint32_t *state,
                                                       const uint32_t *adler, int tiles, uint8_t *out, unsigned long long out_cap)
 {
+    constexpr int PAYLOAD = tile_payload(PX), TILE_SLOT = tile_slot(PX);
     const int tile = blockIdx.y;
     const uint32_t i = blockIdx.x * THREADS + threadIdx.x;
     if (tile >= tiles || state[tile] != 1 || i >= (uint32_t)TILE_SLOT / 4 || tile_off[tile] + TILE_SLOT > out_cap)
@@ -211,12 +293,13 @@ struct ochip_geotiff
 {
     ochip_ctx *ctx = nullptr;
     int kind = 0, sparse = 1;
+    int layers = 1, unit = 1, px = PIXEL_BYTES; // a pixel: `layers` samples of `unit` 32-bit words, px bytes
     int64_t w = 0, h = 0, tiles_x = 0, next_row = 0;
     bool finished = false;
     ochip::dev_blocks mem; // everything on the device, held until destroy
-    uint32_t *rows = nullptr;  // the tile row being filled: [512][w] pixels, zeros where nothing was fed
-    uint8_t *payload = nullptr; // [tiles_x][PAYLOAD]
-    uint16_t *tok = nullptr;    // [tiles_x][PAYLOAD]
+    uint32_t *rows = nullptr;  // the tile row being filled: [layers][512][w] samples, zeros where nothing was fed
+    uint8_t *payload = nullptr; // [tiles_x][tile_payload(px)]
+    uint16_t *tok = nullptr;    // [tiles_x][tile_payload(px)]
     uint32_t *nz = nullptr, *state = nullptr, *count = nullptr, *size = nullptr, *adler = nullptr; // [tiles_x (+ 1)]
     uint32_t *counts = nullptr, *codes = nullptr;                                                  // [blocks][316]
     uint32_t *header = nullptr, *header_bits = nullptr, *block_bits = nullptr, *seg_adler = nullptr;
@@ -277,7 +360,7 @@ int drain_oldest(ochip_geotiff *e)
     for (size_t i = 0; i < tiles; i++)
     {
         const size_t at = (size_t)info[i], n = (size_t)info[tiles + 1 + i];
-        if (n > (size_t)STORED_BYTES || at + n > total)
+        if (n > (size_t)tile_stored_bytes(e->px) || at + n > total)
             return ochip_fail(ctx, OCHIP_EHIP, "ochip_geotiff: tile %zu of a pass has %zu bytes at %zu of %zu", i, n, at, total);
         std::vector<uint8_t> t(n);
         const size_t from_pin = at >= have ? 0 : (at + n <= have ? n : have - at);
@@ -300,8 +383,9 @@ int drain(ochip_geotiff *e)
 }
 
 // One pass over the first `tiles` payloads: everything behind gt_payload, enqueued
-int encode_payloads(ochip_geotiff *e, int tiles)
+template <int PX> int encode_pass(ochip_geotiff *e, int tiles)
 {
+    constexpr int SEGMENTS = tile_segments(PX), TILE_SLOT = tile_slot(PX);
     ochip_ctx *ctx = e->ctx;
     if (tiles < 1 || tiles > e->tiles_x)
         return ochip_fail(ctx, OCHIP_EINVAL, "ochip_geotiff: a pass of %d tiles, at most %lld", tiles, (long long)e->tiles_x);
@@ -313,21 +397,21 @@ int encode_payloads(ochip_geotiff *e, int tiles)
     const size_t out_bytes = (size_t)tiles * TILE_SLOT; // <= slot_cap
     OCHIP_HIP(ctx, hipMemsetAsync(o.out, 0, out_bytes, st));
     OCHIP_HIP(ctx, hipMemsetAsync(e->block_bits, 0, ((size_t)blocks + 1) * 4, st));
-    hipLaunchKernelGGL(gt_parse, dim3((uint32_t)blocks), dim3(THREADS), 0, st, e->payload, e->nz, e->sparse, blocks, e->tok, e->counts,
+    hipLaunchKernelGGL(gt_parse<PX>, dim3((uint32_t)blocks), dim3(THREADS), 0, st, e->payload, e->nz, e->sparse, blocks, e->tok, e->counts,
                        e->seg_adler);
     OCHIP_TRY(launched(ctx, "gt_parse"));
-    hipLaunchKernelGGL(gt_codes, dim3((uint32_t)blocks), dim3(64), 0, st, e->counts, e->nz, e->sparse, blocks, e->codes, e->header,
+    hipLaunchKernelGGL(gt_codes<PX>, dim3((uint32_t)blocks), dim3(64), 0, st, e->counts, e->nz, e->sparse, blocks, e->codes, e->header,
                        e->header_bits, e->block_bits);
     OCHIP_TRY(launched(ctx, "gt_codes"));
     OCHIP_TRY(scan_offsets(ctx, "ochip_geotiff", e->scan_tmp, e->scan_bytes, e->block_bits, e->block_off, (size_t)blocks + 1, st));
-    hipLaunchKernelGGL(gt_tile_sizes, dim3(blocks_of((size_t)tiles + 1)), dim3(THREADS), 0, st, e->block_off, e->seg_adler, e->nz, e->sparse,
+    hipLaunchKernelGGL(gt_tile_sizes<PX>, dim3(blocks_of((size_t)tiles + 1)), dim3(THREADS), 0, st, e->block_off, e->seg_adler, e->nz, e->sparse,
                        tiles, e->state, e->count, e->size, e->adler);
     OCHIP_TRY(launched(ctx, "gt_tile_sizes"));
     OCHIP_TRY(scan_offsets(ctx, "ochip_geotiff", e->scan_tmp, e->scan_bytes, e->size, e->tile_off, (size_t)tiles + 1, st));
-    hipLaunchKernelGGL(gt_emit, dim3((uint32_t)blocks), dim3(THREADS), 0, st, e->payload, e->tok, e->codes, e->header, e->header_bits,
+    hipLaunchKernelGGL(gt_emit<PX>, dim3((uint32_t)blocks), dim3(THREADS), 0, st, e->payload, e->tok, e->codes, e->header, e->header_bits,
                        e->block_off, e->tile_off, e->state, e->size, blocks, o.out, (unsigned long long)out_bytes);
     OCHIP_TRY(launched(ctx, "gt_emit"));
-    hipLaunchKernelGGL(gt_stored, dim3(blocks_of((size_t)TILE_SLOT / 4), (uint32_t)tiles), dim3(THREADS), 0, st, e->payload, e->tile_off,
+    hipLaunchKernelGGL(gt_stored<PX>, dim3(blocks_of((size_t)TILE_SLOT / 4), (uint32_t)tiles), dim3(THREADS), 0, st, e->payload, e->tile_off,
                        e->state, e->adler, tiles, o.out, (unsigned long long)out_bytes);
     OCHIP_TRY(launched(ctx, "gt_stored"));
     hipLaunchKernelGGL(gt_finish, dim3(blocks_of((size_t)tiles + 1)), dim3(THREADS), 0, st, e->tile_off, e->state, e->count, e->adler, tiles,
@@ -352,6 +436,33 @@ int encode_payloads(ochip_geotiff *e, int tiles)
     return OCHIP_OK;
 }
 
+int encode_payloads(ochip_geotiff *e, int tiles)
+{
+    return e->px == 4 ? encode_pass<4>(e, tiles) : e->px == 8 ? encode_pass<8>(e, tiles) : encode_pass<16>(e, tiles);
+}
+
+// The payloads of the complete tile row in e->rows, enqueued
+int launch_payload(ochip_geotiff *e, int tiles)
+{
+    ochip_ctx *ctx = e->ctx;
+    hipStream_t st = ctx->stream;
+    const int vec = (e->w * e->unit) % 4 == 0 && (uintptr_t)e->rows % 16 == 0;
+    if (e->layers == 1 && e->unit == 1) // one layer of colours is the RGBA8 tile
+    {
+        hipLaunchKernelGGL(gt_payload, dim3((uint32_t)(TILE * 128 / THREADS), (uint32_t)tiles), dim3(THREADS), 0, st, e->rows, e->w,
+                           e->kind == OCHIP_GEOTIFF_FLOAT32 ? 1 : 0, vec, tiles, e->payload, e->nz);
+        return launched(ctx, "gt_payload");
+    }
+    const dim3 grid((uint32_t)(TILE * (TILE * e->unit / 4) / THREADS), (uint32_t)tiles);
+    if (e->kind == OCHIP_GEOTIFF_LAYERS8)
+        hipLaunchKernelGGL((gt_payload_layered<2, 1>), grid, dim3(THREADS), 0, st, e->rows, e->w, vec, tiles, e->payload, e->nz);
+    else if (e->layers == 1)
+        hipLaunchKernelGGL((gt_payload_layered<1, 2>), grid, dim3(THREADS), 0, st, e->rows, e->w, vec, tiles, e->payload, e->nz);
+    else
+        hipLaunchKernelGGL((gt_payload_layered<2, 2>), grid, dim3(THREADS), 0, st, e->rows, e->w, vec, tiles, e->payload, e->nz);
+    return launched(ctx, "gt_payload_layered");
+}
+
 int refuse_feed(ochip_geotiff *e, int64_t row0, int64_t rows)
 {
     ochip_ctx *ctx = e->ctx;
@@ -366,34 +477,25 @@ int refuse_feed(ochip_geotiff *e, int64_t row0, int64_t rows)
     return OCHIP_OK;
 }
 
-} // namespace
-
-extern "C"
+// A writer of a checked kind, layer count and size: every buffer from the pixel's bytes
+int create(ochip_ctx *ctx, int kind, int layers, int64_t width, int64_t height, int sparse, ochip_geotiff **out)
 {
-
-int ochip_geotiff_create(ochip_ctx *ctx, int kind, int64_t width, int64_t height, int sparse, ochip_geotiff **out)
-{
-    if (!ctx)
-        return OCHIP_EINVAL;
-    if (!out)
-        return ochip_fail(ctx, OCHIP_EINVAL, "ochip_geotiff_create: out is NULL");
-    *out = nullptr;
-    if ((kind != OCHIP_GEOTIFF_RGBA8 && kind != OCHIP_GEOTIFF_FLOAT32) || width < 1 || height < 1 || width > OCHIP_GEOTIFF_MAX_SIDE ||
-        height > OCHIP_GEOTIFF_MAX_SIDE)
-        return ochip_fail(ctx, OCHIP_EINVAL, "ochip_geotiff_create: kind 0 (RGBA8) or 1 (float32) and sides of 1 .. %d, not kind %d, %lld x %lld",
-                          OCHIP_GEOTIFF_MAX_SIDE, kind, (long long)width, (long long)height);
     OCHIP_HIP(ctx, hipSetDevice(ctx->device));
     std::unique_ptr<ochip_geotiff> e(new ochip_geotiff);
-    e->ctx = ctx, e->kind = kind, e->sparse = sparse != 0 && kind == OCHIP_GEOTIFF_RGBA8, e->w = width, e->h = height;
+    e->ctx = ctx, e->kind = kind, e->sparse = sparse != 0 && kind != OCHIP_GEOTIFF_FLOAT32, e->w = width, e->h = height;
+    e->layers = layers, e->unit = unit_words(kind), e->px = pixel_bytes(kind, layers);
+    e->bytes_per_tile *= e->px / PIXEL_BYTES;
     e->tiles_x = (width + TILE - 1) / TILE;
     e->mem.ctx = ctx, e->mem.what = "ochip_geotiff";
-    const size_t tiles = (size_t)e->tiles_x, blocks = tiles * SEGMENTS;
+    const size_t PAYLOAD = (size_t)tile_payload(e->px), TILE_SLOT = (size_t)tile_slot(e->px); // this writer's, not the 4-byte pixel's
+    const size_t tiles = (size_t)e->tiles_x, blocks = tiles * (size_t)tile_segments(e->px);
+    const size_t row_words = (size_t)layers * TILE * (size_t)width * (size_t)e->unit;
     e->slot_cap = tiles * TILE_SLOT;
     size_t a = 0, b = 0;
     OCHIP_HIP(ctx, scan_offsets(nullptr, a, nullptr, nullptr, blocks + 1, ctx->stream));
     OCHIP_HIP(ctx, scan_offsets(nullptr, b, nullptr, nullptr, tiles + 1, ctx->stream));
     e->scan_bytes = (a > b ? a : b) + 256;
-    int rc = e->mem.alloc(&e->rows, (size_t)TILE * (size_t)width);
+    int rc = e->mem.alloc(&e->rows, row_words);
     if (rc == OCHIP_OK)
         rc = e->mem.alloc(&e->payload, tiles * PAYLOAD);
     if (rc == OCHIP_OK)
@@ -437,7 +539,7 @@ int ochip_geotiff_create(ochip_ctx *ctx, int kind, int64_t width, int64_t height
         if (rc == OCHIP_OK && hipEventCreateWithFlags(&o.done, hipEventBlockingSync | hipEventDisableTiming) != hipSuccess)
             rc = ochip_fail(ctx, OCHIP_EHIP, "ochip_geotiff_create: hipEventCreateWithFlags failed");
     }
-    if (rc == OCHIP_OK && hipMemsetAsync(e->rows, 0, (size_t)TILE * (size_t)width * 4, ctx->stream) != hipSuccess)
+    if (rc == OCHIP_OK && hipMemsetAsync(e->rows, 0, row_words * 4, ctx->stream) != hipSuccess)
         rc = ochip_fail(ctx, OCHIP_EHIP, "ochip_geotiff_create: hipMemsetAsync failed");
     if (rc != OCHIP_OK)
     {
@@ -452,6 +554,41 @@ int ochip_geotiff_create(ochip_ctx *ctx, int kind, int64_t width, int64_t height
     return OCHIP_OK;
 }
 
+} // namespace
+
+extern "C"
+{
+
+int ochip_geotiff_create(ochip_ctx *ctx, int kind, int64_t width, int64_t height, int sparse, ochip_geotiff **out)
+{
+    if (!ctx)
+        return OCHIP_EINVAL;
+    if (!out)
+        return ochip_fail(ctx, OCHIP_EINVAL, "ochip_geotiff_create: out is NULL");
+    *out = nullptr;
+    if ((kind != OCHIP_GEOTIFF_RGBA8 && kind != OCHIP_GEOTIFF_FLOAT32) || width < 1 || height < 1 || width > OCHIP_GEOTIFF_MAX_SIDE ||
+        height > OCHIP_GEOTIFF_MAX_SIDE)
+        return ochip_fail(ctx, OCHIP_EINVAL, "ochip_geotiff_create: kind 0 (RGBA8) or 1 (float32) and sides of 1 .. %d, not kind %d, %lld x %lld",
+                          OCHIP_GEOTIFF_MAX_SIDE, kind, (long long)width, (long long)height);
+    return create(ctx, kind, 1, width, height, sparse, out);
+}
+
+int ochip_geotiff_create_layered(ochip_ctx *ctx, int kind, int num_layers, int64_t width, int64_t height, int sparse, ochip_geotiff **out)
+{
+    if (!ctx)
+        return OCHIP_EINVAL;
+    if (!out)
+        return ochip_fail(ctx, OCHIP_EINVAL, "ochip_geotiff_create_layered: out is NULL");
+    *out = nullptr;
+    if (!layered_kind(kind) || num_layers < 1 || num_layers > MAX_LAYERS || width < 1 || height < 1 || width > OCHIP_GEOTIFF_MAX_SIDE ||
+        height > OCHIP_GEOTIFF_MAX_SIDE)
+        return ochip_fail(ctx, OCHIP_EINVAL,
+                          "ochip_geotiff_create_layered: kind 2 (layers) or 3 (cameras), 1 .. %d layers and sides of 1 .. %d, not kind %d, "
+                          "%d layers, %lld x %lld",
+                          MAX_LAYERS, OCHIP_GEOTIFF_MAX_SIDE, kind, num_layers, (long long)width, (long long)height);
+    return create(ctx, kind, num_layers, width, height, sparse, out);
+}
+
 int ochip_geotiff_feed(ochip_geotiff *e, int64_t row0, int64_t rows, const void *pixels, int on_device)
 {
     if (!g_live.has(e))
@@ -462,27 +599,26 @@ int ochip_geotiff_feed(ochip_geotiff *e, int64_t row0, int64_t rows, const void 
     OCHIP_TRY(refuse_feed(e, row0, rows));
     OCHIP_HIP(ctx, hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
-    const size_t row_bytes = (size_t)e->w * 4;
-    const uint8_t *band = static_cast<const uint8_t *>(pixels);
+    const size_t row_bytes = (size_t)e->w * (size_t)e->unit * 4; // one layer's row
+    const uint8_t *band = static_cast<const uint8_t *>(pixels);   // layer-major, as the tile row is
     for (int64_t at = 0; at < rows;)
     {
         const int64_t y = row0 + at, in_tile = y % TILE;
         int64_t n = TILE - in_tile;
         n = n < rows - at ? n : rows - at;
-        OCHIP_HIP(ctx, hipMemcpyAsync(e->rows + (size_t)in_tile * (size_t)e->w, band + (size_t)at * row_bytes, (size_t)n * row_bytes,
-                                      on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st));
+        for (int l = 0; l < e->layers; l++)
+            OCHIP_HIP(ctx, hipMemcpyAsync(reinterpret_cast<uint8_t *>(e->rows) + ((size_t)l * TILE + (size_t)in_tile) * row_bytes,
+                                          band + ((size_t)l * (size_t)rows + (size_t)at) * row_bytes, (size_t)n * row_bytes,
+                                          on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st));
         at += n, e->next_row = y + n;
         if (e->next_row % TILE == 0 || e->next_row == e->h)
         {
             const int tiles = (int)e->tiles_x;
             OCHIP_HIP(ctx, hipMemsetAsync(e->nz, 0, (size_t)tiles * 4, st));
-            const int vec = e->w % 4 == 0 && (uintptr_t)e->rows % 16 == 0;
-            hipLaunchKernelGGL(gt_payload, dim3((uint32_t)(TILE * 128 / THREADS), (uint32_t)tiles), dim3(THREADS), 0, st, e->rows, e->w,
-                               e->kind == OCHIP_GEOTIFF_FLOAT32 ? 1 : 0, vec, tiles, e->payload, e->nz);
-            OCHIP_TRY(launched(ctx, "gt_payload"));
+            OCHIP_TRY(launch_payload(e, tiles));
             OCHIP_TRY(encode_payloads(e, tiles));
             if (e->next_row < e->h && e->h - e->next_row < TILE) // the last tile row is ragged: zeros below the raster
-                OCHIP_HIP(ctx, hipMemsetAsync(e->rows, 0, (size_t)TILE * row_bytes, st));
+                OCHIP_HIP(ctx, hipMemsetAsync(e->rows, 0, (size_t)e->layers * TILE * row_bytes, st));
         }
     }
     if (!on_device) // the caller's array may be reused on return
@@ -500,7 +636,7 @@ int ochip_geotiff_payloads(ochip_geotiff *e, const uint8_t *payloads, int64_t n)
                           (long long)e->tiles_x);
     OCHIP_HIP(ctx, hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
-    OCHIP_HIP(ctx, hipMemcpyAsync(e->payload, payloads, (size_t)n * PAYLOAD, hipMemcpyHostToDevice, st));
+    OCHIP_HIP(ctx, hipMemcpyAsync(e->payload, payloads, (size_t)n * (size_t)tile_payload(e->px), hipMemcpyHostToDevice, st));
     OCHIP_HIP(ctx, hipMemsetAsync(e->nz, 1, (size_t)n * 4, st)); // every payload is encoded
     OCHIP_TRY(encode_payloads(e, (int)n));
     OCHIP_HIP(ctx, ochip_stream_wait(ctx, st)); // the caller's array may be reused on return

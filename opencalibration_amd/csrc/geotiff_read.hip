@@ -386,6 +386,70 @@ __global__ __launch_bounds__(THREADS) void gr_unpredict(const uint8_t *payloads,
     }
 }
 
+// The layers and cameras rasters: a pixel of W = layers x unit 32-bit words, summed at that stride -
+// bytes for the colours, whole words for the ids - and placed layer-major, word k of a pixel into plane k / unit.  A wave a
+// tile row as above; acc and v are indexed by unrolled constants only.
+template <int W>
+__global__ __launch_bounds__(THREADS) void gr_unpredict_layered(const uint8_t *payloads, const gr_desc *desc, int first, int count, tile_layout L,
+                                                                 int64_t ty0, int64_t row0, int64_t rows, uint32_t *raster)
+{
+    const uint32_t lane = threadIdx.x & 63;
+    const int64_t wave = ((int64_t)blockIdx.x * THREADS + threadIdx.x) >> 6;
+    const int64_t tile = wave / L.tile_h, r = wave % L.tile_h;
+    if (tile >= count)
+        return;
+    const int64_t g = first + tile, tiles_x = L.tiles_x();
+    const int64_t tx = g % tiles_x, y = (ty0 + g / tiles_x) * L.tile_h + r;
+    if (y < row0 || y >= row0 + rows || y >= L.height)
+        return;
+    const int64_t x0 = tx * L.tile_w;
+    const uint32_t cols = (uint32_t)(L.width - x0 < L.tile_w ? L.width - x0 : L.tile_w);
+    const bool sparse = desc[g].z_bytes == 0, sum = L.predictor == 2, words = L.unit == 2;
+    const int U = L.unit;
+    // a payload's slot and a tile row of W words a pixel, tile_w a multiple of 16, are 16-byte aligned
+    const uint32_t *src = reinterpret_cast<const uint32_t *>(payloads + desc[g].out_off) + (size_t)r * (size_t)L.tile_w * W;
+    const uint32_t run = ((uint32_t)L.tile_w + 63) / 64, p0 = lane * run;
+    const uint32_t p1 = p0 + run < (uint32_t)L.tile_w ? p0 + run : (uint32_t)L.tile_w;
+    uint32_t acc[W];
+#pragma unroll
+    for (int k = 0; k < W; k++)
+        acc[k] = 0;
+    if (sum && !sparse)
+    {
+        for (uint32_t p = p0; p < p1; p++)
+#pragma unroll
+            for (int k = 0; k < W; k++)
+            {
+                const uint32_t v = src[(size_t)p * W + k];
+                acc[k] = words ? acc[k] + v : add_bytes(acc[k], v);
+            }
+#pragma unroll
+        for (int k = 0; k < W; k++)
+        {
+            uint32_t incl = acc[k];
+            for (int o = 1; o < 64; o <<= 1)
+            {
+                const uint32_t up = (uint32_t)__shfl_up((int)incl, o, 64);
+                if ((int)lane >= o)
+                    incl = words ? incl + up : add_bytes(incl, up);
+            }
+            acc[k] = (uint32_t)__shfl_up((int)incl, 1, 64);
+            if (lane == 0)
+                acc[k] = 0;
+        }
+    }
+    const size_t plane = (size_t)rows * (size_t)L.width * (size_t)U, at = ((size_t)(y - row0) * (size_t)L.width + (size_t)x0) * (size_t)U;
+    for (uint32_t p = p0; p < p1 && p < cols; p++)
+#pragma unroll
+        for (int k = 0; k < W; k++)
+        {
+            uint32_t v = sparse ? 0u : src[(size_t)p * W + k];
+            if (sum)
+                v = acc[k] = words ? acc[k] + v : add_bytes(acc[k], v);
+            raster[(size_t)(k / U) * plane + at + (size_t)p * U + (k % U)] = v;
+        }
+}
+
 ochip::live_set<ochip_geotiff_reader> g_live; // the readers that exist
 
 int launched(ochip_ctx *ctx, const char *what)
@@ -463,8 +527,21 @@ int run_streams(ochip_geotiff_reader *r, const char *what, int64_t n, const uint
         if (raster)
         {
             const int64_t waves = (i1 - i0) * r->L.tile_h;
-            hipLaunchKernelGGL(gr_unpredict, dim3((uint32_t)((waves * 64 + THREADS - 1) / THREADS)), dim3(THREADS), 0, st, d_payloads, d_desc, (int)i0,
-                               (int)(i1 - i0), r->L, ty0, row0, rows, raster);
+            const dim3 grid((uint32_t)((waves * 64 + THREADS - 1) / THREADS));
+            uint32_t *planes = reinterpret_cast<uint32_t *>(raster);
+            const int W = r->L.layers * r->L.unit;
+            if (W == 0)
+                hipLaunchKernelGGL(gr_unpredict, grid, dim3(THREADS), 0, st, d_payloads, d_desc, (int)i0, (int)(i1 - i0), r->L, ty0, row0, rows,
+                                   raster);
+            else if (W == 1)
+                hipLaunchKernelGGL(gr_unpredict_layered<1>, grid, dim3(THREADS), 0, st, d_payloads, d_desc, (int)i0, (int)(i1 - i0), r->L, ty0,
+                                   row0, rows, planes);
+            else if (W == 2)
+                hipLaunchKernelGGL(gr_unpredict_layered<2>, grid, dim3(THREADS), 0, st, d_payloads, d_desc, (int)i0, (int)(i1 - i0), r->L, ty0,
+                                   row0, rows, planes);
+            else
+                hipLaunchKernelGGL(gr_unpredict_layered<4>, grid, dim3(THREADS), 0, st, d_payloads, d_desc, (int)i0, (int)(i1 - i0), r->L, ty0,
+                                   row0, rows, planes);
             OCHIP_TRY(launched(ctx, "gr_unpredict"));
         }
         if (out)
@@ -513,6 +590,24 @@ int ochip_geotiff_reader_create(ochip_ctx *ctx, int samples, int is_float, int64
     return OCHIP_OK;
 }
 
+int ochip_geotiff_reader_create_layered(ochip_ctx *ctx, int kind, int num_layers, int64_t width, int64_t height, int tile_w, int tile_h,
+                                        int predictor, uint64_t scratch_budget, ochip_geotiff_reader **out)
+{
+    if (!ctx)
+        return OCHIP_EINVAL;
+    if (!out)
+        return ochip_fail(ctx, OCHIP_EINVAL, "ochip_geotiff_reader_create_layered: out is NULL");
+    *out = nullptr;
+    std::unique_ptr<ochip_geotiff_reader> r(new ochip_geotiff_reader);
+    r->ctx = ctx;
+    if (const char *why = layered_layout(r->L, kind, num_layers, width, height, tile_w, tile_h, predictor))
+        return ochip_fail(ctx, OCHIP_EINVAL, "ochip_geotiff_reader_create_layered: %s", why);
+    r->budget = scratch_budget ? scratch_budget : DEFAULT_BUDGET;
+    g_live.add(r.get());
+    *out = r.release();
+    return OCHIP_OK;
+}
+
 int ochip_geotiff_reader_inflate(ochip_geotiff_reader *r, int64_t n, const uint8_t *streams, const uint64_t *offsets, const uint64_t *expect,
                                  uint8_t *out, uint64_t out_cap, int32_t *status, uint64_t *bytes)
 {
@@ -538,6 +633,8 @@ int ochip_geotiff_reader_read(ochip_geotiff_reader *r, int64_t n, const uint8_t 
         return ochip_fail(ctx, OCHIP_EINVAL, "ochip_geotiff_reader_read: %s", why);
     if (on_device && L.pixel_bytes() == 4 && (uintptr_t)raster % 4 != 0)
         return ochip_fail(ctx, OCHIP_EINVAL, "ochip_geotiff_reader_read: a device raster of 4-byte pixels is 4-byte aligned");
+    if (on_device && L.layers && (uintptr_t)raster % 4 != 0)
+        return ochip_fail(ctx, OCHIP_EINVAL, "ochip_geotiff_reader_read: a device raster of layers is 4-byte aligned");
     *bad_tile = -1;
     if (n == 0 || rows == 0)
         return OCHIP_OK;

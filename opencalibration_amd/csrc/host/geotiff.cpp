@@ -33,30 +33,37 @@ struct och_geotiff
     ochip_geotiff *dev = nullptr; // the device route
     // the CPU route
     int kind = 0, sparse = 1;
+    int layers = 1, unit = 1, px = PIXEL_BYTES; // a pixel: `layers` samples of `unit` 32-bit words, px bytes
     int64_t w = 0, h = 0, tiles_x = 0, next_row = 0;
     bool finished = false;
-    std::vector<uint32_t> rows;              // the tile row being filled: [512][w] pixels, zeros where nothing was fed
+    std::vector<uint32_t> rows;              // the tile row being filled: [layers][512][w] samples, zeros where nothing was fed
     std::deque<std::vector<uint8_t>> ready; // the streams of the complete tiles, in tile order; empty: a sparse tile
 };
 
 namespace
 {
 // The predicted payload of tile tx of the tile row held in e->rows; returns whether any byte of it is non-zero
-bool tile_payload(const och_geotiff *e, int64_t tx, uint8_t *payload)
+bool fill_payload(const och_geotiff *e, int64_t tx, uint8_t *payload)
 {
-    const bool is_float = e->kind == OCH_GEOTIFF_FLOAT32;
+    const bool words = word_predictor(e->kind);
+    const int L = e->layers, U = e->unit;
+    const size_t row_words = (size_t)e->w * (size_t)U, plane = (size_t)TILE * row_words;
     uint32_t any = 0;
     for (int r = 0; r < TILE; r++)
     {
-        const uint32_t *src = e->rows.data() + (size_t)r * (size_t)e->w;
-        uint32_t left = 0;
+        uint32_t left[MAX_LAYERS * 2] = {0, 0, 0, 0};
+        uint8_t *out = payload + (size_t)r * (size_t)tile_row_bytes(e->px);
         for (int x = 0; x < TILE; x++)
         {
             const int64_t X = tx * TILE + x;
-            const uint32_t cur = X < e->w ? src[X] : 0;
-            const uint32_t v = x == 0 ? cur : predict_word(cur, left, is_float);
-            std::memcpy(payload + (size_t)r * ROW_BYTES + (size_t)x * 4, &v, 4);
-            any |= cur, left = cur;
+            for (int l = 0; l < L; l++)
+                for (int u = 0; u < U; u++, out += 4)
+                {
+                    const uint32_t cur = X < e->w ? e->rows[(size_t)l * plane + (size_t)r * row_words + (size_t)X * U + u] : 0;
+                    const uint32_t v = x == 0 ? cur : predict_word(cur, left[l * U + u], words);
+                    std::memcpy(out, &v, 4);
+                    any |= cur, left[l * U + u] = cur;
+                }
         }
     }
     return any != 0;
@@ -68,10 +75,10 @@ void encode_tile_row(och_geotiff *e)
 #pragma omp parallel for schedule(dynamic)
     for (int64_t tx = 0; tx < e->tiles_x; tx++)
     {
-        std::vector<uint8_t> payload(PAYLOAD);
-        const bool any = tile_payload(e, tx, payload.data());
+        std::vector<uint8_t> payload((size_t)tile_payload(e->px));
+        const bool any = fill_payload(e, tx, payload.data());
         if (any || !e->sparse || e->kind == OCH_GEOTIFF_FLOAT32)
-            encode_tile(payload.data(), out[(size_t)tx]);
+            encode_tile(payload.data(), e->px, out[(size_t)tx]);
     }
     for (auto &o : out)
         e->ready.push_back(std::move(o));
@@ -108,6 +115,44 @@ int och_deflate_code_lengths(const uint32_t *counts, int n, int limit, uint8_t *
     return OCHIP_OK;
 }
 
+namespace
+{
+void shape(och_geotiff *e, int kind, int layers, int64_t width, int64_t height, int sparse)
+{
+    e->kind = kind, e->sparse = sparse != 0, e->w = width, e->h = height, e->tiles_x = (width + TILE - 1) / TILE;
+    e->layers = layers, e->unit = unit_words(kind), e->px = pixel_bytes(kind, layers);
+    e->rows.assign((size_t)layers * TILE * (size_t)width * (size_t)e->unit, 0u);
+}
+} // namespace
+
+int och_geotiff_create_layered(ochip_ctx *ctx, int kind, int num_layers, int64_t width, int64_t height, int sparse, och_geotiff **out)
+{
+    if (!out)
+        return fail(OCHIP_EINVAL, "och_geotiff_create_layered: out is NULL");
+    *out = nullptr;
+    std::unique_ptr<och_geotiff> e(new och_geotiff);
+    e->ctx = ctx;
+    if (ctx)
+    {
+        const int rc = ochip_geotiff_create_layered(ctx, kind, num_layers, width, height, sparse, &e->dev);
+        if (rc != OCHIP_OK)
+            return fail(rc, ochip_last_error(ctx));
+    }
+    else
+    {
+        if (!layered_kind(kind) || num_layers < 1 || num_layers > MAX_LAYERS || width < 1 || height < 1 || width > OCH_GEOTIFF_MAX_SIDE ||
+            height > OCH_GEOTIFF_MAX_SIDE)
+            return fail(OCHIP_EINVAL, "och_geotiff_create_layered: kind 2 (layers) or 3 (cameras), 1 .. " + std::to_string(MAX_LAYERS) +
+                                          " layers and sides of 1 .. " + std::to_string(OCH_GEOTIFF_MAX_SIDE) + ", not kind " +
+                                          std::to_string(kind) + ", " + std::to_string(num_layers) + " layers, " + std::to_string(width) +
+                                          " x " + std::to_string(height));
+        shape(e.get(), kind, num_layers, width, height, sparse);
+    }
+    g_live.add(e.get());
+    *out = e.release();
+    return OCHIP_OK;
+}
+
 int och_geotiff_create(ochip_ctx *ctx, int kind, int64_t width, int64_t height, int sparse, och_geotiff **out)
 {
     if (!out)
@@ -128,8 +173,7 @@ int och_geotiff_create(ochip_ctx *ctx, int kind, int64_t width, int64_t height, 
             return fail(OCHIP_EINVAL, "och_geotiff_create: kind 0 (RGBA8) or 1 (float32) and sides of 1 .. " +
                                           std::to_string(OCH_GEOTIFF_MAX_SIDE) + ", not kind " + std::to_string(kind) + ", " +
                                           std::to_string(width) + " x " + std::to_string(height));
-        e->kind = kind, e->sparse = sparse != 0, e->w = width, e->h = height, e->tiles_x = (width + TILE - 1) / TILE;
-        e->rows.assign((size_t)TILE * (size_t)width, 0u);
+        shape(e.get(), kind, 1, width, height, sparse);
     }
     g_live.add(e.get());
     *out = e.release();
@@ -153,10 +197,13 @@ int och_geotiff_feed(och_geotiff *e, int64_t row0, int64_t rows, const void *pix
     if (!refusal.empty())
         return fail(e->finished ? OCHIP_ESTATE : OCHIP_EINVAL, "och_geotiff_feed: " + refusal);
     const uint8_t *band = static_cast<const uint8_t *>(pixels);
+    const size_t row_words = (size_t)e->w * (size_t)e->unit, row_bytes = row_words * 4; // one layer's row
     for (int64_t r = 0; r < rows; r++)
     {
         const int64_t y = row0 + r;
-        std::memcpy(e->rows.data() + (size_t)(y % TILE) * (size_t)e->w, band + (size_t)r * (size_t)e->w * 4, (size_t)e->w * 4);
+        for (int l = 0; l < e->layers; l++) // the band is layer-major, as the tile row is
+            std::memcpy(e->rows.data() + ((size_t)l * TILE + (size_t)(y % TILE)) * row_words,
+                        band + ((size_t)l * (size_t)rows + (size_t)r) * row_bytes, row_bytes);
         e->next_row = y + 1;
         if (e->next_row % TILE == 0 || e->next_row == e->h)
             encode_tile_row(e);
@@ -178,7 +225,7 @@ int och_geotiff_payloads(och_geotiff *e, const uint8_t *payloads, int64_t n)
     std::vector<std::vector<uint8_t>> out((size_t)n);
 #pragma omp parallel for schedule(dynamic)
     for (int64_t i = 0; i < n; i++)
-        encode_tile(payloads + (size_t)i * PAYLOAD, out[(size_t)i]);
+        encode_tile(payloads + (size_t)i * (size_t)tile_payload(e->px), e->px, out[(size_t)i]);
     for (auto &o : out)
         e->ready.push_back(std::move(o));
     return OCHIP_OK;

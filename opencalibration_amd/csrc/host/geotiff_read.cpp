@@ -74,6 +74,35 @@ int och_geotiff_reader_create(ochip_ctx *ctx, int samples, int is_float, int64_t
     return OCHIP_OK;
 }
 
+int och_geotiff_reader_create_layered(ochip_ctx *ctx, int kind, int num_layers, int64_t width, int64_t height, int tile_w, int tile_h,
+                                      int predictor, uint64_t scratch_budget, och_geotiff_reader **out)
+{
+    if (!out)
+        return fail(OCHIP_EINVAL, "och_geotiff_reader_create_layered: out is NULL");
+    *out = nullptr;
+    std::unique_ptr<och_geotiff_reader> r(new och_geotiff_reader);
+    r->ctx = ctx;
+    if (ctx)
+    {
+#ifdef OCHIP_GEOTIFF_READ_STANDALONE
+        return fail(OCHIP_EINVAL, "och_geotiff_reader_create_layered: built without the device route");
+#else
+        const int rc = ochip_geotiff_reader_create_layered(ctx, kind, num_layers, width, height, tile_w, tile_h, predictor, scratch_budget, &r->dev);
+        if (rc != OCHIP_OK)
+            return fail(rc, ochip_last_error(ctx));
+#endif
+    }
+    else
+    {
+        tile_layout &L = r->L;
+        if (const char *why = layered_layout(L, kind, num_layers, width, height, tile_w, tile_h, predictor))
+            return fail(OCHIP_EINVAL, std::string("och_geotiff_reader_create_layered: ") + why);
+    }
+    g_live.add(r.get());
+    *out = r.release();
+    return OCHIP_OK;
+}
+
 int och_geotiff_reader_inflate(och_geotiff_reader *r, int64_t n, const uint8_t *streams, const uint64_t *offsets, const uint64_t *expect,
                                uint8_t *out, uint64_t out_cap, int32_t *status, uint64_t *bytes)
 {

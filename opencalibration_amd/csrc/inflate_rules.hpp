@@ -391,14 +391,23 @@ constexpr int MAX_STREAMS = 65535;                  // a call's most streams
 constexpr uint64_t MAX_EXPECT = (uint64_t)1 << 30;  // a stream's most bytes in the inflate of the C ABI
 constexpr uint64_t MAX_TILE_BYTES = (uint64_t)4 << 20;
 constexpr int64_t MAX_SIDE = 1048576;
+constexpr int MAX_READ_LAYERS = 2; // 2 layers of ids in a 512 x 512 tile are the 4 MiB
 
 struct tile_layout
 {
     int32_t samples = 0, is_float = 0, tile_w = 0, tile_h = 0, predictor = 1;
+    // The layers and cameras rasters: layers > 0, a pixel is `layers` samples of `unit` 32-bit words
+    // - B G R A bytes (unit 1, the predictor over bytes) or the two words of a 64-bit id (unit 2, over words) - interleaved
+    // in the tile and placed layer-major, [layers][rows][width], in the raster.  samples and is_float are 0 then.
+    int32_t layers = 0, unit = 1;
     int64_t width = 0, height = 0;
     OCHIP_INF_HD int64_t pixel_bytes() const
     {
-        return is_float ? 4 : samples;
+        return layers ? 4 * unit * layers : is_float ? 4 : samples;
+    }
+    OCHIP_INF_HD bool word_predictor() const // 32-bit sums; else bytes
+    {
+        return layers ? unit == 2 : is_float != 0;
     }
     OCHIP_INF_HD uint64_t tile_bytes() const
     {
@@ -417,8 +426,9 @@ struct tile_layout
 // nullptr, or why the layout is not one this reader takes
 inline const char *refuse_layout(const tile_layout &L)
 {
-    if (L.is_float ? L.samples != 1 : (L.samples != 1 && L.samples != 3 && L.samples != 4))
-        return "8-bit samples come 1, 3 or 4 to a pixel, float32 one";
+    if (L.layers ? (L.layers > MAX_READ_LAYERS || (L.unit != 1 && L.unit != 2)) : L.is_float ? L.samples != 1
+                                                                                             : (L.samples != 1 && L.samples != 3 && L.samples != 4))
+        return L.layers ? "the layers (kind 2) and cameras (kind 3) rasters have 1 or 2 layers" : "8-bit samples come 1, 3 or 4 to a pixel, float32 one";
     if (L.width < 1 || L.height < 1 || L.width > MAX_SIDE || L.height > MAX_SIDE)
         return "the raster's sides are 1 .. 1048576";
     if (L.tile_w < 16 || L.tile_h < 16 || L.tile_w % 16 != 0 || L.tile_h % 16 != 0 || L.tile_w > 65536 || L.tile_h > 65536)
@@ -428,6 +438,17 @@ inline const char *refuse_layout(const tile_layout &L)
     if (L.predictor != 1 && L.predictor != 2)
         return "the predictor is 1 or 2";
     return nullptr;
+}
+
+// The layout of a layers (kind 2) or cameras (kind 3) raster of num_layers layers into L; nullptr, or why it is refused
+inline const char *layered_layout(tile_layout &L, int kind, int num_layers, int64_t width, int64_t height, int tile_w, int tile_h, int predictor)
+{
+    if ((kind != 2 && kind != 3) || num_layers < 1 || num_layers > MAX_READ_LAYERS)
+        return "the layers (kind 2) and cameras (kind 3) rasters have 1 or 2 layers";
+    L = tile_layout();
+    L.layers = num_layers, L.unit = kind == 3 ? 2 : 1, L.tile_w = tile_w, L.tile_h = tile_h, L.predictor = predictor;
+    L.width = width, L.height = height;
+    return refuse_layout(L);
 }
 
 // The tile rows [ty0, ty1) that cover raster rows [row0, row0 + rows); false: the window is not inside the raster
@@ -515,10 +536,37 @@ inline void place_tile(const tile_layout &L, uint8_t *payload, int64_t tx, int64
         uint8_t *dst = raster + ((size_t)(y - row0) * (size_t)L.width + (size_t)x0) * (size_t)bpp;
         if (!payload)
         {
-            std::memset(dst, 0, (size_t)(cols * bpp));
+            if (!L.layers)
+                std::memset(dst, 0, (size_t)(cols * bpp));
+            for (int64_t l = 0; l < L.layers; l++) // the same pixels of every layer's plane
+                std::memset(raster + (((size_t)l * (size_t)rows + (size_t)(y - row0)) * (size_t)L.width + (size_t)x0) * (size_t)(4 * L.unit), 0,
+                            (size_t)(cols * 4 * L.unit));
             continue;
         }
         uint8_t *row = payload + (size_t)r * (size_t)L.tile_w * (size_t)bpp;
+        if (L.layers)
+        {
+            // sums at the stride of the pixel, then every layer's sample to its own plane of the raster
+            const int64_t W = bpp / 4, sample = 4 * L.unit;
+            if (L.predictor == 2 && L.unit == 2)
+                for (int64_t k = W; k < cols * W; k++)
+                {
+                    uint32_t v, left;
+                    std::memcpy(&v, row + 4 * k, 4), std::memcpy(&left, row + 4 * (k - W), 4);
+                    v += left;
+                    std::memcpy(row + 4 * k, &v, 4);
+                }
+            else if (L.predictor == 2)
+                for (int64_t x = bpp; x < cols * bpp; x++)
+                    row[x] = (uint8_t)(row[x] + row[x - bpp]);
+            for (int64_t l = 0; l < L.layers; l++)
+            {
+                uint8_t *plane = raster + (((size_t)l * (size_t)rows + (size_t)(y - row0)) * (size_t)L.width + (size_t)x0) * (size_t)sample;
+                for (int64_t x = 0; x < cols; x++)
+                    std::memcpy(plane + x * sample, row + x * bpp + l * sample, (size_t)sample);
+            }
+            continue;
+        }
         if (L.predictor == 2 && L.is_float)
         {
             uint32_t left = 0;

@@ -335,6 +335,7 @@ def load():
         L.och_jpeg_decoder_destroy.restype = None
         L.och_jpeg_decode_last_error.restype = C.c_char_p
         L.och_geotiff_create.argtypes = [vp, C.c_int, i64, i64, C.c_int, C.POINTER(vp)]
+        L.och_geotiff_create_layered.argtypes = [vp, C.c_int, C.c_int, i64, i64, C.c_int, C.POINTER(vp)]
         L.och_geotiff_feed.argtypes = [vp, i64, i64, vp, C.c_int]
         L.och_geotiff_payloads.argtypes = [vp, vp, i64]
         L.och_geotiff_collect.argtypes = [vp, vp, C.c_uint64, C.POINTER(C.c_uint64), vp, C.c_uint64, C.POINTER(C.c_uint64)]
@@ -343,6 +344,7 @@ def load():
         L.och_geotiff_destroy.restype = None
         L.och_geotiff_last_error.restype = C.c_char_p
         L.och_geotiff_reader_create.argtypes = [vp, C.c_int, C.c_int, i64, i64, C.c_int, C.c_int, C.c_int, C.c_uint64, C.POINTER(vp)]
+        L.och_geotiff_reader_create_layered.argtypes = [vp, C.c_int, C.c_int, i64, i64, C.c_int, C.c_int, C.c_int, C.c_uint64, C.POINTER(vp)]
         L.och_geotiff_reader_inflate.argtypes = [vp, i64, vp, vp, vp, vp, C.c_uint64, vp, vp]
         L.och_geotiff_reader_read.argtypes = [vp, i64, vp, vp, i64, i64, vp, C.c_int, C.POINTER(i64)]
         L.och_geotiff_reader_launches.argtypes = [vp]
@@ -1562,7 +1564,7 @@ def color_balance_remove_gauge(xy, offsets):
 
 def ortho_mosaic(plan, graph, surfaces, images, mesh=None, config=None, color_balance=None, tile_rows=1, out=None,
                  overviews=False, progress=None, progress_passes=(1, 2), jpeg=None, jpeg_quality=95, geotiff=None,
-                 dsm_geotiff=None, geo=None, progress_png=False):
+                 dsm_geotiff=None, geo=None, progress_png=False, layers_geotiff=None, cameras_geotiff=None):
     """The blended full-resolution orthomosaic of `plan` (dsm_plan), band by band of tile_rows output tile rows: DSM ->
     layers (ortho_layers) -> blend (ortho_blend).  mesh (an OrthoMesh): every step on its device, images as CUDA tensors,
     into `out` (a (height, width, 4) uint8 CUDA tensor, made when None); None: the CPU route, numpy images, into a host
@@ -1591,15 +1593,22 @@ def ortho_mosaic(plan, graph, surfaces, images, mesh=None, config=None, color_ba
     with "solve" in the second sweep alone - the overview levels are built for either (as overviews=True does) and become
     the files' further IFDs, and the files are finished before the function returns and closed on an exception.  geo:
     dict(min_x, max_y, gsd[, epsg]) for the georeferencing tags; its missing keys are the plan's.  Both None: nothing is
-    allocated or launched for them."""
+    allocated or launched for them.
+    layers_geotiff, cameras_geotiff: both or neither; a path or a seekable binary file object each, the two rasters
+    generateLayeredGeoTIFF leaves (GeoTiffWriter's kinds GEOTIFF_LAYERS8 and GEOTIFF_CAMERAS32), written
+    in the sweep that renders the layers, each band's fed right behind its render.  With "solve" that is the first sweep,
+    and the second then blends from the files (read_layer_files' bands) instead of rendering again; the mosaic is the same,
+    bit for bit.  For that a file object must also be readable and at position 0 (opened "w+b", an io.BytesIO); one that is
+    not is refused with OchipError before anything is rendered.  With both None nothing is allocated, launched or changed."""
     return _mosaic(plan, graph, surfaces, mesh, config, color_balance, tile_rows, out, images=images, overviews=overviews,
                    progress=progress, progress_passes=progress_passes, jpeg=jpeg, jpeg_quality=jpeg_quality,
-                   geotiff=geotiff, dsm_geotiff=dsm_geotiff, geo=geo, progress_png=progress_png)
+                   geotiff=geotiff, dsm_geotiff=dsm_geotiff, geo=geo, progress_png=progress_png, layers_geotiff=layers_geotiff,
+                   cameras_geotiff=cameras_geotiff)
 
 
 def ortho_mosaic_streamed(plan, graph, surfaces, fetch, mesh, capacity, config=None, color_balance=None, tile_rows=1, out=None,
                           overviews=False, progress=None, progress_passes=(1, 2), jpeg=None, jpeg_quality=95, geotiff=None,
-                          dsm_geotiff=None, geo=None, progress_png=False, files=None):
+                          dsm_geotiff=None, geo=None, progress_png=False, files=None, layers_geotiff=None, cameras_geotiff=None):
     """ortho_mosaic on mesh's device without the source images resident: fetch(i) returns involved camera i's BGR image
     (ortho_layers_cameras' order) as a numpy array or a page-locked torch CPU tensor, and at most `capacity` images are on
     the device at a time (OrthoStream).  Band k + 1's ahead uploads are issued before band k renders, so that they run
@@ -1612,15 +1621,18 @@ def ortho_mosaic_streamed(plan, graph, surfaces, fetch, mesh, capacity, config=N
     (OrthoStream.upload_jpegs: one call for the band's late loads - all of band 0's - and one for the next band's ahead
     loads), so only the files cross to the device; the others - no file, an unsupported or corrupt one, a scan that turns
     out corrupt - come through fetch(i) as before, or raise OchipError naming the camera, the file and its status when fetch
-    is None, which files allows.  files None: nothing changes."""
+    is None, which files allows.  files None: nothing changes.
+    layers_geotiff, cameras_geotiff: as ortho_mosaic's; with "solve" the second sweep reads the layers back from the two files
+    and so uploads and decodes nothing."""
     return _mosaic(plan, graph, surfaces, mesh, config, color_balance, tile_rows, out, fetch=fetch, capacity=capacity, files=files,
                    overviews=overviews, progress=progress, progress_passes=progress_passes, jpeg=jpeg, jpeg_quality=jpeg_quality,
-                   geotiff=geotiff, dsm_geotiff=dsm_geotiff, geo=geo, progress_png=progress_png)
+                   geotiff=geotiff, dsm_geotiff=dsm_geotiff, geo=geo, progress_png=progress_png, layers_geotiff=layers_geotiff,
+                   cameras_geotiff=cameras_geotiff)
 
 
 def _mosaic(plan, graph, surfaces, mesh, config, color_balance, tile_rows, out, images=None, fetch=None, capacity=None,
             overviews=False, progress=None, progress_passes=(1, 2), jpeg=None, jpeg_quality=95, geotiff=None, dsm_geotiff=None,
-            geo=None, progress_png=False, files=None):
+            geo=None, progress_png=False, files=None, layers_geotiff=None, cameras_geotiff=None):
     """The band loop of ortho_mosaic (images) and ortho_mosaic_streamed (fetch and / or files, capacity): the two differ in
     where a band's layers come from, ortho_layers over the resident images or an OrthoStream's render behind the band's
     uploads."""
@@ -1629,6 +1641,15 @@ def _mosaic(plan, graph, surfaces, mesh, config, color_balance, tile_rows, out, 
     bcfg = {k: cfg[k] for k in BLEND_CONFIG}
     if isinstance(color_balance, str) and color_balance != "solve":
         raise ValueError('color_balance is None, a dict of tables or "solve"')
+    if (layers_geotiff is None) != (cameras_geotiff is None):
+        raise capi.OchipError("layers_geotiff and cameras_geotiff belong together: both, or neither")
+    if color_balance == "solve" and layers_geotiff is not None:  # the second sweep reads what the first wrote: known before it renders
+        for name, target in (("layers_geotiff", layers_geotiff), ("cameras_geotiff", cameras_geotiff)):
+            if not isinstance(target, (str, bytes, os.PathLike)) and not (
+                    hasattr(target, "read") and hasattr(target, "readable") and target.readable() and
+                    hasattr(target, "seekable") and target.seekable() and target.tell() == 0):
+                raise capi.OchipError(f'{name}: with "solve" the second sweep reads the file back, so a file object must be '
+                                      "readable as well as writable and seekable, and at position 0")
     h, w, nl, band_rows = plan["height"], plan["width"], cfg["num_layers"], tile_rows * cfg["tile_size"]
     if mesh is None:
         ctx = None
@@ -1643,6 +1664,7 @@ def _mosaic(plan, graph, surfaces, mesh, config, color_balance, tile_rows, out, 
     builders = [OrthoOverviews(kind, w, h, ctx=ctx, on_device=mesh is not None)
                 for kind in (OVERVIEW_RGBA8, OVERVIEW_FLOAT32)] if overviews or geotiff is not None or dsm_geotiff is not None else []
     tiffs = [None, None]  # the orthomosaic's and the DSM's GeoTiffWriter
+    pair = [None, None]   # the layers' and the cameras' GeoTiffWriter while a sweep renders, their GeoTiffReaders behind it
     passes = {int(p) for p in progress_passes} if progress is not None else set()
     if passes - {TILE_PASS_LAYERS, TILE_PASS_BLEND}:
         raise ValueError("progress_passes names 1 (the layers) and 2 (the blend)")
@@ -1682,10 +1704,10 @@ def _mosaic(plan, graph, surfaces, mesh, config, color_balance, tile_rows, out, 
                 for cam, st in bad:  # the scans that turned out corrupt: the call's other loads are in their slots
                     pixels(cam, st)
 
-    def band(k, balance, blend, emit=frozenset()):
+    def band(k, balance, blend, emit=frozenset(), from_files=False):
         row0 = k * band_rows
         rows = min(band_rows, h - row0)
-        if stream is not None:  # before the band's DSM and render: its own loads still missing, then the next band's ahead ones
+        if stream is not None and not from_files:  # before the band's DSM and render: its own loads still missing, then the next band's ahead ones
             fill(k, stream.loads(0) if k == 0 else stream.loads(k, LOAD_LATE))
             if k + 1 < stream.num_bands:
                 fill(k + 1, stream.loads(k + 1, LOAD_AHEAD))
@@ -1694,15 +1716,20 @@ def _mosaic(plan, graph, surfaces, mesh, config, color_balance, tile_rows, out, 
         else:
             dsm = torch.empty((rows, w), dtype=torch.float32, device=dev)
             dsm_render(plan, surfaces, mesh=mesh, row0=row0, rows=rows, out=dsm)
-            lay = dict(bgra=torch.empty((nl, rows, w, 4), dtype=torch.uint8, device=dev),
-                       camera_id=torch.empty((nl, rows, w), dtype=torch.int64, device=dev))
+            lay = None if from_files else dict(bgra=torch.empty((nl, rows, w, 4), dtype=torch.uint8, device=dev),
+                                               camera_id=torch.empty((nl, rows, w), dtype=torch.int64, device=dev))
             if TILE_PASS_LAYERS in emit:  # the pick among the layers reads their weights
                 lay["weight"] = torch.empty((nl, rows, w), dtype=torch.float32, device=dev)
-        if stream is not None:
+        if from_files:  # the first sweep left the layers in the two files: nothing is uploaded, decoded or rendered
+            layers = dict(_read_layer_band(pair[0], pair[1], nl, row0, rows, mesh is not None), correspondences=None)
+        elif stream is not None:
             layers = stream.render(k, out=lay)
         else:
             layers = ortho_layers(plan, graph, surfaces, images, mesh=mesh, row0=row0, tile_rows=tile_rows, config=lcfg, out=lay,
                                   dsm=dsm if mesh is None else None)
+        if not from_files and pair[0] is not None:  # behind the render on the context's stream: no wait of its own
+            pair[0].feed(row0, layers["bgra"])
+            pair[1].feed(row0, layers["camera_id"])
         before = tiles.pending() if emit else 0
         if TILE_PASS_LAYERS in emit:  # behind the render on the context's stream: no wait of its own
             tiles.feed(TILE_PASS_LAYERS, row0, layers["bgra"], layers["weight"])
@@ -1730,19 +1757,32 @@ def _mosaic(plan, graph, surfaces, mesh, config, color_balance, tile_rows, out, 
             if target is not None:
                 tiffs[i] = GeoTiffWriter(target, kind, w, h, geo={**{k: plan[k] for k in ("min_x", "max_y", "gsd")}, **(geo or {})},
                                          ctx=ctx, on_device=mesh is not None)
+        if layers_geotiff is not None:
+            for i, (target, kind) in enumerate(((layers_geotiff, GEOTIFF_LAYERS8), (cameras_geotiff, GEOTIFF_CAMERAS32))):
+                pair[i] = GeoTiffWriter(target, kind, w, h, geo={**{k: plan[k] for k in ("min_x", "max_y", "gsd")}, **(geo or {})},
+                                        ctx=ctx, on_device=mesh is not None, num_layers=nl)
         bands = range(-(-h // band_rows))
+        from_files = False
         if color_balance == "solve":
             corr = [band(k, None, False, passes & {TILE_PASS_LAYERS}) for k in bands]
             if tiles is not None:
                 deliver(0)
+            if pair[0] is not None:  # the files are complete: the second sweep reads them
+                for t in pair:
+                    t.finish()
+                rl, rc, _ = _open_layer_files(layers_geotiff, cameras_geotiff, ctx)
+                pair[0], pair[1], from_files = rl, rc, True
             color_balance = color_balance_solve(np.concatenate(corr) if corr else np.zeros(0, CORR_DTYPE), graph=graph, ctx=ctx)
-            if stream is not None:
+            if stream is not None and not from_files:
                 stream.rewind()
             passes = passes & {TILE_PASS_BLEND}
         for k in bands:
-            band(k, color_balance, True, passes)
+            band(k, color_balance, True, passes, from_files)
         if tiles is not None:
             deliver(0)
+        if pair[0] is not None and not from_files:
+            for t in pair:
+                t.finish()
         if texture is not None:
             texture.finish()
         if builders:
@@ -1756,7 +1796,7 @@ def _mosaic(plan, graph, surfaces, mesh, config, color_balance, tile_rows, out, 
     finally:
         if texture is not None:
             texture.close()
-        for t in tiffs:
+        for t in tiffs + pair:
             if t is not None:
                 t.close()
         if stream is not None:
@@ -1765,6 +1805,110 @@ def _mosaic(plan, graph, surfaces, mesh, config, color_balance, tile_rows, out, 
             b.close()
         if tiles is not None:
             tiles.close()
+    return out
+
+
+def ortho_layers_files(plan, graph, surfaces, images, layers_geotiff, cameras_geotiff, dsm_geotiff=None, mesh=None, config=None,
+                       tile_rows=1, geo=None):
+    """generateLayeredGeoTIFF (src/ortho/ortho.cpp:1431-1660): the layer pass alone, band by band, into the layers and the
+    cameras raster (GeoTiffWriter's kinds GEOTIFF_LAYERS8 and GEOTIFF_CAMERAS32) and, with dsm_geotiff, the
+    DSM's file with its overview levels, as ortho_mosaic writes it.  Each band's layers and ids are fed right behind its
+    render, and a feed never waits for the band it enqueues.  images, mesh, config, tile_rows, geo: as ortho_mosaic's.
+    Returns the correspondences of all bands, which color_balance_solve takes; ortho_blend_files is the other half."""
+    cfg = {**LAYERS_CONFIG, **(config or {})}
+    lcfg = {k: cfg[k] for k in LAYERS_CONFIG}
+    h, w, nl, band_rows = plan["height"], plan["width"], cfg["num_layers"], tile_rows * cfg["tile_size"]
+    ctx = None if mesh is None else mesh.ctx
+    tags = {**{k: plan[k] for k in ("min_x", "max_y", "gsd")}, **(geo or {})}
+    writers, builder, corr = [], None, []
+    try:
+        for target, kind in ((layers_geotiff, GEOTIFF_LAYERS8), (cameras_geotiff, GEOTIFF_CAMERAS32)):
+            writers.append(GeoTiffWriter(target, kind, w, h, geo=tags, ctx=ctx, on_device=mesh is not None, num_layers=nl))
+        if dsm_geotiff is not None:
+            builder = OrthoOverviews(OVERVIEW_FLOAT32, w, h, ctx=ctx, on_device=mesh is not None)
+            writers.append(GeoTiffWriter(dsm_geotiff, OVERVIEW_FLOAT32, w, h, geo=tags, ctx=ctx, on_device=mesh is not None))
+        for row0 in range(0, h, band_rows):
+            rows = min(band_rows, h - row0)
+            dsm = lay = None
+            if mesh is None:
+                dsm = dsm_render(plan, surfaces, row0=row0, rows=rows)
+            else:  # the band stays on the device: the feeds read it there
+                import torch
+
+                dev = f"cuda:{ctx.device}"
+                lay = dict(bgra=torch.empty((nl, rows, w, 4), dtype=torch.uint8, device=dev),
+                           camera_id=torch.empty((nl, rows, w), dtype=torch.int64, device=dev))
+                if dsm_geotiff is not None:
+                    dsm = torch.empty((rows, w), dtype=torch.float32, device=dev)
+                    dsm_render(plan, surfaces, mesh=mesh, row0=row0, rows=rows, out=dsm)
+            layers = ortho_layers(plan, graph, surfaces, images, mesh=mesh, row0=row0, tile_rows=tile_rows, config=lcfg, out=lay,
+                                  dsm=dsm if mesh is None else None)
+            writers[0].feed(row0, layers["bgra"])
+            writers[1].feed(row0, layers["camera_id"])
+            if dsm_geotiff is not None:
+                builder.feed(row0, dsm)
+                writers[2].feed(row0, dsm)
+            corr.append(layers["correspondences"])
+        writers[0].finish()
+        writers[1].finish()
+        if dsm_geotiff is not None:
+            writers[2].finish(builder.finish())
+    finally:
+        for t in writers:
+            t.close()
+        if builder is not None:
+            builder.close()
+    return np.concatenate(corr) if corr else np.zeros(0, CORR_DTYPE)
+
+
+def ortho_blend_files(plan, graph, surfaces, layers_geotiff, cameras_geotiff, dsm_geotiff, color_balance=None, ctx=None, config=None,
+                      tile_rows=1, out=None, geotiff=None, geo=None):
+    """blendLayeredGeoTIFF (src/ortho/ortho.cpp:1665-1990): the blend alone, from the three files ortho_layers_files leaves -
+    what GeoTiffReader takes each - read band by band (read_layer_files' bands and the DSM's rows) and blended by
+    ortho_blend.  color_balance: None or a dict of tables (color_balance_solve's).  ctx None: the CPU route, else through
+    ctx's device, where the bands and the mosaic stay.  geotiff: the mosaic's file with its overview levels, as ortho_mosaic
+    writes it.  Files whose size or geo tags are not the plan's raise GeoTiffError("refused").  Returns rgba
+    (height, width, 4) uint8 (`out` when given)."""
+    cfg = {**LAYERS_CONFIG, **BLEND_CONFIG, **(config or {})}
+    bcfg = {k: cfg[k] for k in BLEND_CONFIG}
+    h, w, band_rows = plan["height"], plan["width"], tile_rows * cfg["tile_size"]
+    on_device = ctx is not None
+    rl, rc, nl = _open_layer_files(layers_geotiff, cameras_geotiff, ctx)
+    rd = writer = builder = None
+    try:
+        rd = GeoTiffReader(dsm_geotiff, ctx=ctx)
+        for name, r in (("layers", rl), ("cameras", rc), ("DSM", rd)):
+            if (r.width, r.height) != (w, h):
+                raise GeoTiffError("refused", f"the {name} file is {r.width} x {r.height}, the plan {w} x {h}")
+            g = r.geo
+            if g is None or (g["min_x"], g["max_y"], g["gsd_x"], g["gsd_y"]) != (plan["min_x"], plan["max_y"], plan["gsd"], plan["gsd"]):
+                raise GeoTiffError("refused", f"the geo tags of the {name} file, {g}, are not the plan's")
+        if rd.kind != OVERVIEW_FLOAT32:
+            raise GeoTiffError("refused", "the DSM file holds no float32 raster")
+        if on_device:
+            import torch
+
+            out = torch.empty((h, w, 4), dtype=torch.uint8, device=f"cuda:{ctx.device}") if out is None else out
+        else:
+            out = np.zeros((h, w, 4), np.uint8) if out is None else out
+        if geotiff is not None:
+            builder = OrthoOverviews(OVERVIEW_RGBA8, w, h, ctx=ctx, on_device=on_device)
+            writer = GeoTiffWriter(geotiff, OVERVIEW_RGBA8, w, h, geo={**{k: plan[k] for k in ("min_x", "max_y", "gsd")}, **(geo or {})},
+                                   ctx=ctx, on_device=on_device)
+        for row0 in range(0, h, band_rows):
+            rows = min(band_rows, h - row0)
+            layers = _read_layer_band(rl, rc, nl, row0, rows, on_device)
+            dsm = rd.read(row0, rows, on_device=on_device)
+            ortho_blend(plan, graph, surfaces, layers, dsm, color_balance, ctx=ctx, config=bcfg, out=out[row0:row0 + rows])
+            if writer is not None:
+                builder.feed(row0, out[row0:row0 + rows])
+                writer.feed(row0, out[row0:row0 + rows])
+        if writer is not None:
+            writer.finish(builder.finish())
+    finally:
+        for t in (rl, rc, rd, writer, builder):
+            if t is not None:
+                t.close()
     return out
 
 
@@ -2352,6 +2496,18 @@ def ortho_overviews(raster, ctx=None):
 # ---- the orthomosaic and the DSM as tiled DEFLATE GeoTIFFs (include/oc_host.h) ----------------------------
 GEOTIFF_TILE, GEOTIFF_PAYLOAD, GEOTIFF_MAX_STREAM = 512, 1 << 20, 1048667
 GEOTIFF_BIGTIFF_ABOVE = 2_000_000_000  # uncompressed bytes of the full level: GDAL's BIGTIFF=IF_SAFER as remembered, unpinned
+# the rasters between the layer pass and the blend: B G R A per layer, and the two words of a layer's node id
+GEOTIFF_LAYERS8, GEOTIFF_CAMERAS32, GEOTIFF_MAX_LAYERS = 2, 3, 2
+
+
+def geotiff_pixel_bytes(kind, num_layers=1):
+    """The bytes of one pixel of a GeoTiffWriter's kind: 4, or 4 (layers) and 8 (cameras) per layer"""
+    return 8 * int(num_layers) if kind == GEOTIFF_CAMERAS32 else 4 * int(num_layers) if kind == GEOTIFF_LAYERS8 else 4
+
+
+def geotiff_stored_bytes(payload):
+    """stored_bytes of csrc/deflate_rules.hpp: the size of the stored form of a payload, which no stream exceeds"""
+    return 2 + payload + 5 * ((payload + 65534) // 65535) + 4
 
 
 def deflate_code_lengths(counts, limit):
@@ -2370,11 +2526,15 @@ class _TileEncoder(_Handle):
 
     _destroy, _last_error = "och_geotiff_destroy", "och_geotiff_last_error"
 
-    def __init__(self, kind, width, height, ctx, sparse):
+    def __init__(self, kind, width, height, ctx, sparse, num_layers=None):
         self.L, self.ctx, self.h = load(), ctx, None
         h = C.c_void_p()
-        self._check(self.L.och_geotiff_create(ctx.h if ctx is not None else None, int(kind), int(width), int(height), int(bool(sparse)),
-                                              C.byref(h)))
+        if num_layers is None:
+            self._check(self.L.och_geotiff_create(ctx.h if ctx is not None else None, int(kind), int(width), int(height),
+                                                  int(bool(sparse)), C.byref(h)))
+        else:
+            self._check(self.L.och_geotiff_create_layered(ctx.h if ctx is not None else None, int(kind), int(num_layers), int(width),
+                                                          int(height), int(bool(sparse)), C.byref(h)))
         self.h = h
 
     def feed(self, row0, rows, ptr, on_device):
@@ -2435,14 +2595,34 @@ class GeoTiffWriter:
     always written.  feed(row0, band): bands ascend and are contiguous from row 0, of any row count.  finish(overviews): the
     list of overview level arrays or tensors (OrthoOverviews) become further IFDs with NewSubfileType 1; the file is then
     complete, flushed (an object) or closed (a path).  A gap, an overlap, a wrong kind or width, a feed after finish and a
-    finish before the last row raise OchipError naming the rows."""
+    finish before the last row raise OchipError naming the rows.
 
-    def __init__(self, target, kind, width, height, geo=None, ctx=None, on_device=False, bigtiff=None, sparse=True):
+    The reference's createMultiBandGeoTIFF (src/ortho/ortho.cpp:969-1008), the two rasters between
+    generateLayeredGeoTIFF and blendLayeredGeoTIFF, are the kinds GEOTIFF_LAYERS8 and GEOTIFF_CAMERAS32 with num_layers 1 or 2
+    (the reference's pipeline always has 2).  Their bands come layer-major, as ortho_layers returns them: bgra
+    (num_layers, rows, width, 4) uint8, and camera_id (num_layers, rows, width) uint64 - int64 where torch holds it.  The tiles
+    are pixel-interleaved: 4 num_layers Byte samples B G R A per layer, respectively 2 num_layers UInt32 samples, the low and
+    the high word of each layer's id; Predictor 2 differences a sample with the same sample of the pixel before.  Tags:
+    BitsPerSample 8 or 32 per sample, SamplesPerPixel, PlanarConfiguration 1, Photometric 1 (MINISBLACK), ExtraSamples
+    (samples - 1 values of 0), SampleFormat 1, the geo tags as above - Photometric and ExtraSamples are GDAL's for a
+    multi-band file without colour interpretation as remembered, unpinned.  sparse leaves out the all-zero tiles of both; an
+    invalid sample is all zero in both files.  No overview levels: the reference builds none, finish refuses them.  bigtiff: None
+    chooses by the kind's own uncompressed size."""
+
+    def __init__(self, target, kind, width, height, geo=None, ctx=None, on_device=False, bigtiff=None, sparse=True, num_layers=None):
         self.enc = self.f = None
         self.kind, self.width, self.height, self.ctx = int(kind), int(width), int(height), ctx
         self.on_device, self.sparse = bool(on_device), bool(sparse)
-        if self.kind not in (OVERVIEW_RGBA8, OVERVIEW_FLOAT32):
-            raise capi.OchipError("a GeoTIFF's kind is OVERVIEW_RGBA8 or OVERVIEW_FLOAT32")
+        self.layered = self.kind in (GEOTIFF_LAYERS8, GEOTIFF_CAMERAS32)
+        if not self.layered and self.kind not in (OVERVIEW_RGBA8, OVERVIEW_FLOAT32):
+            raise capi.OchipError("a GeoTIFF's kind is OVERVIEW_RGBA8, OVERVIEW_FLOAT32, GEOTIFF_LAYERS8 or GEOTIFF_CAMERAS32")
+        if self.layered and num_layers is None:
+            raise capi.OchipError("a layers or cameras GeoTIFF needs num_layers")
+        if not self.layered and num_layers is not None:
+            raise capi.OchipError("num_layers belongs to the kinds GEOTIFF_LAYERS8 and GEOTIFF_CAMERAS32")
+        if self.layered and not (isinstance(num_layers, (int, np.integer)) and 1 <= num_layers <= GEOTIFF_MAX_LAYERS):
+            raise capi.OchipError(f"num_layers is 1 .. {GEOTIFF_MAX_LAYERS}, not {num_layers!r}")
+        self.num_layers = int(num_layers) if self.layered else None
         if self.on_device and ctx is None:
             raise ValueError("bands on the device need the device route (ctx)")
         self.geo = dict(geo) if geo is not None else None
@@ -2451,12 +2631,13 @@ class GeoTiffWriter:
             if self.geo.get("epsg") is not None:
                 raise ValueError("geo names the local frame (origin / coord) or an epsg code, not both")
             self.centre = _geo_coord(self.geo["coord"] if self.geo.get("coord") is not None else self.geo["origin"]).centre
-        self.big = self.width * self.height * 4 > GEOTIFF_BIGTIFF_ABOVE if bigtiff is None else bool(bigtiff)
+        self.big = self.width * self.height * geotiff_pixel_bytes(self.kind, self.num_layers or 1) > GEOTIFF_BIGTIFF_ABOVE \
+            if bigtiff is None else bool(bigtiff)
         self.own = isinstance(target, (str, bytes, os.PathLike))
         if not self.own and not (hasattr(target, "write") and hasattr(target, "seekable") and target.seekable()):
             raise capi.OchipError("a GeoTIFF's target is a path or a seekable binary file object: the first IFD's offset is "
                                   "written last")
-        self.enc = _TileEncoder(self.kind, self.width, self.height, ctx, self.sparse)
+        self.enc = _TileEncoder(self.kind, self.width, self.height, ctx, self.sparse, self.num_layers)
         self.f = open(target, "wb") if self.own else target
         self.base = self.f.tell()
         self.f.write(b"II+\0\x08\0\0\0" + bytes(8) if self.big else b"II*\0" + bytes(4))
@@ -2510,16 +2691,25 @@ class GeoTiffWriter:
     def feed(self, row0, band):
         if self.enc is None:
             raise capi.OchipError("the writer is closed")
-        try:
-            kind, rows, w = _overview_kind(band.dtype, tuple(band.shape))
-        except ValueError:
-            kind, rows, w = -1, 0, 0
+        if self.layered:
+            name, shape = str(band.dtype).replace("torch.", ""), tuple(int(v) for v in band.shape)
+            want = (self.num_layers, shape[1] if len(shape) > 1 else 0, self.width) + ((4,) if self.kind == GEOTIFF_LAYERS8 else ())
+            if shape != want or name not in (("uint8",) if self.kind == GEOTIFF_LAYERS8 else ("uint64", "int64")):
+                raise capi.OchipError(f"rows from {int(row0)}: a band of this writer is ({self.num_layers}, rows, {self.width}" +
+                                      (", 4) uint8" if self.kind == GEOTIFF_LAYERS8 else ") uint64 or int64") +
+                                      f", not {shape} {name}")
+            kind, rows, w = self.kind, shape[1], self.width
+        else:
+            try:
+                kind, rows, w = _overview_kind(band.dtype, tuple(band.shape))
+            except ValueError:
+                kind, rows, w = -1, 0, 0
         if kind != self.kind or w != self.width:
             raise capi.OchipError(f"rows from {int(row0)}: a band of this writer is {self.width} pixels wide, kind {self.kind}")
         self._take(self.enc)  # what the bands before completed: waits for them alone, not for this band
         self._keep = []
         if self.on_device:
-            shape = (rows, w, 4) if kind == OVERVIEW_RGBA8 else (rows, w)
+            shape = tuple(band.shape) if self.layered else (rows, w, 4) if kind == OVERVIEW_RGBA8 else (rows, w)
             ptr = _device_ptr(band, str(band.dtype), shape, "band", self.ctx.device)
             self._keep.append(band)  # the copy may still read it: alive until the next feed, finish or close
         else:
@@ -2531,17 +2721,23 @@ class GeoTiffWriter:
     def _ifd(self, width, height, overview):
         rgba, big = self.kind == OVERVIEW_RGBA8, self.big
         n = 4 if rgba else 1
+        bits = [8] * 4 if rgba else [32]
+        if self.layered:  # 4 Byte samples or 2 UInt32 samples a layer
+            n = (4 if self.kind == GEOTIFF_LAYERS8 else 2) * self.num_layers
+            bits = [8 if self.kind == GEOTIFF_LAYERS8 else 32] * n
         S, L, D, A, L8 = 3, 4, 12, 2, 16
         offsets = np.array([t[0] for t in self.tiles], np.uint64)
         tags = []
         if overview:
             tags.append((254, L, [1]))
-        tags += [(256, L, [width]), (257, L, [height]), (258, S, [8] * 4 if rgba else [32]), (259, S, [8]), (262, S, [2 if rgba else 1]),
+        tags += [(256, L, [width]), (257, L, [height]), (258, S, bits), (259, S, [8]), (262, S, [2 if rgba else 1]),
                  (277, S, [n]), (284, S, [1]), (317, S, [2]), (322, S, [GEOTIFF_TILE]), (323, S, [GEOTIFF_TILE]),
                  (324, L8 if big else L, offsets), (325, L, [t[1] for t in self.tiles])]
         if rgba:
             tags.append((338, S, [2]))
-        tags.append((339, S, [1] * 4 if rgba else [3]))
+        if self.layered:
+            tags.append((338, S, [0] * (n - 1)))
+        tags.append((339, S, [1] * n if rgba or self.layered else [3]))
         if self.geo is not None and not overview:
             g = self.geo
             keys = [(1025, 0, 1, 1)]
@@ -2561,7 +2757,7 @@ class GeoTiffWriter:
             if doubles:
                 tags.append((34736, D, doubles))
                 tags.append((34737, A, ascii_))
-        if not rgba:
+        if self.kind == OVERVIEW_FLOAT32:
             tags.append((42113, A, b"nan\0"))
         dtypes = {S: "<u2", L: "<u4", D: "<f8", L8: "<u8"}
         inline, entries = 8 if big else 4, []
@@ -2583,6 +2779,8 @@ class GeoTiffWriter:
         if self.enc is None or self.finished:
             raise capi.OchipError("the writer is finished or closed")
         levels = list(overviews) if overviews is not None else []
+        if levels and self.layered:
+            raise capi.OchipError("the layers and cameras rasters have no overview levels")
         sizes = overview_levels(self.width, self.height) if levels else []
         if len(levels) != len(sizes):
             raise capi.OchipError(f"a {self.width} x {self.height} raster has {len(sizes)} overview levels, {len(levels)} came")
@@ -2658,11 +2856,17 @@ class _TileReader(_Handle):
     def _failure(text):
         return GeoTiffError("refused", text)
 
-    def __init__(self, samples, is_float, width, height, tile_w, tile_h, predictor, ctx, budget=0):
+    def __init__(self, samples, is_float, width, height, tile_w, tile_h, predictor, ctx, budget=0, layered=None):
+        """layered: None, or (kind, num_layers) of a layers or cameras raster, for which samples and is_float do not count"""
         self.L, self.ctx, self.h = load(), ctx, None
         h = C.c_void_p()
-        self._check(self.L.och_geotiff_reader_create(ctx.h if ctx is not None else None, int(samples), int(bool(is_float)), int(width),
-                                                     int(height), int(tile_w), int(tile_h), int(predictor), int(budget), C.byref(h)))
+        if layered is None:
+            self._check(self.L.och_geotiff_reader_create(ctx.h if ctx is not None else None, int(samples), int(bool(is_float)), int(width),
+                                                         int(height), int(tile_w), int(tile_h), int(predictor), int(budget), C.byref(h)))
+        else:
+            self._check(self.L.och_geotiff_reader_create_layered(ctx.h if ctx is not None else None, int(layered[0]), int(layered[1]),
+                                                                 int(width), int(height), int(tile_w), int(tile_h), int(predictor),
+                                                                 int(budget), C.byref(h)))
         self.h = h
 
     def launches(self):
@@ -2742,13 +2946,17 @@ class GeoTiffReader:
     route by size.  Measured on the MI355X (profiles/geotiff_read_probe.json) the device route is the slower
     one: a 16 384 x 16 384 RGBA file of 1 024 tiles takes 0.27 - 0.52 s on the device and 0.18 s on 16 host threads, a
     64-tile file 0.12 - 0.25 s against 0.012 s.  Take it for pixels that must end on the device.
-    width, height, samples, kind (OVERVIEW_RGBA8, OVERVIEW_FLOAT32 or None for 1 or 3 samples), levels ([(rows, cols), ...]
+    width, height, samples, kind (OVERVIEW_RGBA8, OVERVIEW_FLOAT32, GEOTIFF_LAYERS8, GEOTIFF_CAMERAS32, or None for 1 or 3
+    Byte samples), num_layers (of the kinds GEOTIFF_LAYERS8 and GEOTIFF_CAMERAS32, else None), levels ([(rows, cols), ...]
     of the overview IFDs), geo (dict(min_x, max_y, gsd_x, gsd_y, epsg) from tags 33550 / 33922 / 34735, or None), projection (dict(kind="tmerc", lat0, lon0, k0, false_easting, false_northing) of a
     user-defined Transverse Mercator in the GeoKeys, or None) and nodata
     (tag 42113 as a float, or None).
     Taken: little-endian classic and BigTIFF, tiles with sides that are multiples of 16 and a payload of at most 4 MiB,
     Compression 8 and 32946, Predictor 1 and 2, PlanarConfiguration 1, 8-bit unsigned samples 1, 3 or 4 to a pixel, one
-    float32.  Everything else - big-endian files, strips, other compressions (none included), Predictor 3, planar 2, other
+    float32, and the two rasters between the layer pass and the blend: 8 Byte samples are GEOTIFF_LAYERS8
+    with two layers of B G R A, 2 or 4 UInt32 samples GEOTIFF_CAMERAS32 with one or two layers' 64-bit ids as a low and a
+    high word.  4 Byte samples stay OVERVIEW_RGBA8, which one layer of colours is (read_layer_files reshapes it).  Those two
+    kinds are read layer-major, as ortho_blend takes its layers.  Everything else - big-endian files, strips, other compressions (none included), Predictor 3, planar 2, other
     sample formats or depths - raises GeoTiffError("unsupported") with the reason; offsets or counts outside the file, IFD
     loops, tile arrays of the wrong length and any tile whose stream does not check raise GeoTiffError("corrupt"), the last
     naming the level and the tile, and no part of the raster is returned."""
@@ -2812,8 +3020,11 @@ class GeoTiffReader:
         first = self._ifds[0]
         self.width, self.height, self.samples, self.is_float = first["width"], first["height"], first["samples"], first["is_float"]
         self.kind = OVERVIEW_FLOAT32 if self.is_float else OVERVIEW_RGBA8 if self.samples == 4 else None
+        self.num_layers = None
+        if first["layered"] is not None:
+            self.kind, self.num_layers = first["layered"]
         for k, lv in enumerate(self._ifds[1:]):
-            if (lv["samples"], lv["is_float"]) != (self.samples, self.is_float):
+            if (lv["samples"], lv["is_float"], lv["layered"]) != (self.samples, self.is_float, first["layered"]):
                 raise GeoTiffError("unsupported", f"level {k + 1} has another sample layout than the full raster")
         self.levels = [(lv["height"], lv["width"]) for lv in self._ifds[1:]]
         tags = first["tags"]
@@ -2904,10 +3115,17 @@ class GeoTiffReader:
         if pred not in (1, 2):
             raise GeoTiffError("unsupported", f"{what}: Predictor {pred}")
         is_float = fmt == 3 and bits == [32] and samples == 1
-        if not is_float and not (fmt == 1 and samples in (1, 3, 4) and bits == [8] * samples):
+        # the rasters between the layer pass and the blend: 8 Byte samples are two layers of B G R A, 2 or 4
+        # UInt32 samples the ids of one or two layers; 4 Byte samples stay RGBA8, which one layer of colours is
+        layered = None
+        if fmt == 1 and samples == 8 and bits == [8] * 8:
+            layered = (GEOTIFF_LAYERS8, 2)
+        elif fmt == 1 and samples in (2, 4) and bits == [32] * samples:
+            layered = (GEOTIFF_CAMERAS32, samples // 2)
+        if layered is None and not is_float and not (fmt == 1 and samples in (1, 3, 4) and bits == [8] * samples):
             raise GeoTiffError("unsupported", f"{what}: {samples} samples of {bits} bits, SampleFormat {fmt}")
         tw, th = one(322), one(323)
-        bpp = 4 if is_float else samples
+        bpp = geotiff_pixel_bytes(*layered) if layered else 4 if is_float else samples
         if tw < 16 or th < 16 or tw % 16 or th % 16 or tw * th * bpp > GEOTIFF_MAX_TILE_BYTES:
             raise GeoTiffError("unsupported", f"{what}: tiles of {tw} x {th} (sides are multiples of 16, a payload at most 4 MiB)")
         tiles_x, tiles_y = -(-width // tw), -(-height // th)
@@ -2922,7 +3140,7 @@ class GeoTiffReader:
             k = int(np.flatnonzero(live & ((offs > len(self.buf)) | (cnts > len(self.buf)) | (offs + cnts > len(self.buf))))[0])
             raise GeoTiffError("corrupt", f"{what}: tile {k} at {int(offs[k])} + {int(cnts[k])} lies outside the file's {len(self.buf)} bytes")
         return dict(width=width, height=height, samples=samples, is_float=is_float, tile_w=tw, tile_h=th, predictor=pred,
-                    tiles_x=tiles_x, tiles_y=tiles_y, offsets=offs, counts=cnts, tags=tags)
+                    tiles_x=tiles_x, tiles_y=tiles_y, offsets=offs, counts=cnts, tags=tags, layered=layered, bpp=bpp)
 
     # -- the pattern of the other classes
     def close(self):
@@ -2955,8 +3173,11 @@ class GeoTiffReader:
 
     def read(self, row0=0, rows=None, level=0, out=None, on_device=False):
         """Rows [row0, row0 + rows) of level `level` (0: the full raster): (rows, width, samples) uint8 or (rows, width)
-        float32, a numpy array, or with on_device a CUDA tensor on ctx's device.  Any row window inside the level is taken;
-        the tile rows that cover it are decoded.  out: the array or tensor to fill."""
+        float32, a numpy array, or with on_device a CUDA tensor on ctx's device.  The kinds GEOTIFF_LAYERS8 and
+        GEOTIFF_CAMERAS32 come layer-major: (num_layers, rows, width, 4) uint8 B G R A, respectively (num_layers, rows, width)
+        ids, uint64 in a numpy array and int64 in a CUDA tensor.  Any row window inside the level is taken; the tile rows
+        that cover it are decoded: their streams are copied into one block tile by tile, and a read on the device waits for
+        torch's stream first.  out: the array or tensor to fill."""
         if self.buf is None:
             raise GeoTiffError("refused", "the reader is closed")
         if not 0 <= int(level) < len(self._ifds):
@@ -2971,6 +3192,10 @@ class GeoTiffReader:
             raise ValueError("a raster on the device needs the device route (ctx)")
         shape = (rows, w) if lv["is_float"] else (rows, w, lv["samples"])
         dtype = "float32" if lv["is_float"] else "uint8"
+        if lv["layered"] is not None:  # layer-major, as ortho_blend takes its layers; torch holds the ids as int64
+            kind, nl = lv["layered"]
+            shape = (nl, rows, w, 4) if kind == GEOTIFF_LAYERS8 else (nl, rows, w)
+            dtype = "uint8" if kind == GEOTIFF_LAYERS8 else "int64" if on_device else "uint64"
         if on_device:
             import torch
 
@@ -2997,12 +3222,13 @@ class GeoTiffReader:
             if c:
                 packed[int(at):int(at + c)] = self.buf[int(o):int(o + c)]
         if level not in self._readers:
-            self._readers[level] = _TileReader(lv["samples"], lv["is_float"], w, h, lv["tile_w"], th, lv["predictor"], self.ctx, self.budget)
+            self._readers[level] = _TileReader(lv["samples"], lv["is_float"], w, h, lv["tile_w"], th, lv["predictor"], self.ctx, self.budget,
+                                               layered=lv["layered"])
         bad = self._readers[level].read(packed, offsets, row0, rows, ptr, on_device)
         if bad >= 0:
             tx, ty = bad % lv["tiles_x"], ty0 + bad // lv["tiles_x"]
             raise GeoTiffError("corrupt", f"level {level}, tile ({tx}, {ty}): its stream is not a zlib stream of exactly "
-                                          f"{lv['tile_w'] * th * (4 if lv['is_float'] else lv['samples'])} bytes")
+                                          f"{lv['tile_w'] * th * lv['bpp']} bytes")
         return out
 
 
@@ -3013,6 +3239,59 @@ def load_geotiff(source, ctx=None, level=0, on_device=False):
     on the device."""
     with GeoTiffReader(source, ctx=ctx) as rd:
         return rd.read(level=level, on_device=on_device), rd.geo
+
+
+def _open_layer_files(layers, cameras, ctx, budget=0):
+    """The two readers of a layers and a cameras file that belong together, checked; the caller closes both"""
+    if layers is None or cameras is None:
+        raise GeoTiffError("refused", f"the {'cameras' if layers is None else 'layers'} file alone: the layers and the cameras "
+                                      "file belong together, and a band is read from both")
+    rl = GeoTiffReader(layers, ctx=ctx, budget=budget)
+    try:
+        rc = GeoTiffReader(cameras, ctx=ctx, budget=budget)
+    except BaseException:
+        rl.close()
+        raise
+    try:
+        # one layer of colours is four Byte samples, which is RGBA8's layout too
+        nl = rl.num_layers if rl.kind == GEOTIFF_LAYERS8 else 1 if rl.kind == OVERVIEW_RGBA8 else None
+        if nl is None:
+            raise GeoTiffError("refused", "the layers file holds no B G R A layers: 4 Byte samples a layer")
+        if rc.kind != GEOTIFF_CAMERAS32:
+            raise GeoTiffError("refused", "the cameras file holds no node ids: 2 UInt32 samples a layer")
+        if (rl.width, rl.height) != (rc.width, rc.height):
+            raise GeoTiffError("refused", f"the layers file is {rl.width} x {rl.height}, the cameras file {rc.width} x {rc.height}")
+        if nl != rc.num_layers:
+            raise GeoTiffError("refused", f"the layers file has {nl} layers, the cameras file {rc.num_layers}")
+        if rl.geo != rc.geo or rl.projection != rc.projection:
+            raise GeoTiffError("refused", f"the geo tags of the layers file, {rl.geo}, are not the cameras file's, {rc.geo}")
+    except BaseException:
+        rl.close()
+        rc.close()
+        raise
+    return rl, rc, nl
+
+
+def _read_layer_band(rl, rc, nl, row0, rows, on_device):
+    bgra = rl.read(row0, rows, on_device=on_device)
+    if rl.kind == OVERVIEW_RGBA8:
+        bgra = bgra.reshape((1,) + tuple(bgra.shape))
+    return dict(bgra=bgra, camera_id=rc.read(row0, rows, on_device=on_device), row0=int(row0), rows=int(bgra.shape[1]))
+
+
+def read_layer_files(layers, cameras=None, row0=0, rows=None, ctx=None, on_device=False):
+    """Rows [row0, row0 + rows) of the two rasters generateLayeredGeoTIFF leaves (GeoTiffWriter's kinds GEOTIFF_LAYERS8 and
+    GEOTIFF_CAMERAS32) as ortho_blend takes its `layers`: dict(bgra (L, rows, width, 4) uint8, camera_id
+    (L, rows, width) uint64 - int64 in a CUDA tensor -, row0, rows).  layers, cameras: what GeoTiffReader takes.  ctx None: the
+    host route; else through ctx's device, where the band stays with on_device.  One file of the pair alone (the other None or
+    left out), two files of different size, layer count or geo tags, and a file of another layout in either place, raise
+    GeoTiffError("refused")."""
+    rl, rc, nl = _open_layer_files(layers, cameras, ctx)
+    try:
+        return _read_layer_band(rl, rc, nl, row0, rows, on_device)
+    finally:
+        rl.close()
+        rc.close()
 
 
 def save_textured_obj_from_geotiff(path, surfaces, geotiff, jpeg=True, ctx=None, quality=95):
